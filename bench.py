@@ -81,6 +81,12 @@ def parse_args(argv=None):
     ap.add_argument("--detail-out", default=None, help="where the whole report is written (default gpurun_out/bench_detail.json)")
     ap.add_argument("--no-build", action="store_true", help="fail instead of building when the library is missing or stale (profiling runs: "
                     "no child process may start under rocprofv3)")
+    ap.add_argument("--full", action="store_true", help="every leg beside the headline as well: the CPU-oracle baseline, the roofline passes, the "
+                    "single-sequence, host-fed, uniform-window, inertial and matrix-unit lines, the sequences-per-GPU and host-CPU sweeps, the stage wall "
+                    "times and the detail file (--no-cpu-baseline / --no-extra-lines leave parts of it out); without it a run sets up, warms up, times "
+                    "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: what the timed loop's last step computed, as "
+                    "DIR/<name>.npy in float32 / float64 (rank 0's sequences; see dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -415,6 +421,69 @@ def write_detail(full, path):
             continue
     return None
 
+
+DUMP_SEQUENCES = 16        # --dump-outputs: the per-keypoint arrays of a fixed sample of this many sequences (~0.6 MB each)
+DUMP_BUDGET = 64 << 20
+
+
+def dump_outputs(loop, out_dir):
+    """--dump-outputs: what the timed loop's last step handed back to its callers, as out_dir/<name>.npy in float32 / float64 (integers and
+    descriptor bytes exactly).  Per sequence of this rank: ORB counts, tracking poses and counts, LiDAR counts, map_incremental's arrays, map
+    sizes.  Per keypoint, concatenated over the valid keypoints of the sequences np.random.default_rng(0) draws (DUMP_SEQUENCES of them,
+    listed in dump_sequences): keypoints, descriptors, stereo matches, the tracking calls' per-keypoint results.  Local mapping: every distinct
+    window of the workload the loop has optimised, in window order, from the batches' last runs (a window's result does not depend on the batch
+    that ran it; which mapping worker took the last step is up to the threads)."""
+    k, F = loop.last_k, loop.F
+    sample = np.sort(np.random.default_rng(0).choice(F, min(F, DUMP_SEQUENCES), replace=False))
+    out = {"dump_sequences": sample.astype(np.float64), "map_sizes": np.array([m.size() for m in loop.maps], np.float64)}
+    if loop.orb_outs[k] is not None:
+        kps, desc, counts, mono = loop.orb_outs[k]
+        imgs = [i for s in sample for i in (2 * s, 2 * s + 1)]   # images 2s / 2s + 1: the left / right image of sequence s
+        left = [(s, int(counts[2 * s])) for s in sample]
+
+        def per_kp(*arrs):   # [F, capacity] arrays of the left images -> one column each over the sample's valid keypoints
+            return np.concatenate([np.stack([a[s, :n] for a in arrs], 1) for s, n in left]).astype(np.float64)
+        out["orb_counts"] = np.stack([counts, mono], 1).astype(np.float64)
+        out["orb_keypoints"] = np.concatenate([np.stack([kps[i, :counts[i]][f] for f in kps.dtype.names], 1).astype(np.float32) for i in imgs])
+        out["orb_descriptors"] = np.concatenate([desc[i, :counts[i]] for i in imgs]).astype(np.float32)
+        if loop.st_outs[k] is not None:
+            out["stereo_matches"] = per_kp(*loop.st_outs[k])
+        if loop.trk_outs[k] is not None:
+            poses, mp, nm, inl = loop.trk_outs[k]
+            out["track_motion_poses"], out["track_motion_counts"] = poses.astype(np.float64), np.stack([nm, inl], 1).astype(np.float64)
+            out["track_motion_map_points"] = per_kp(mp)
+        if loop.tlm_outs[k] is not None:
+            poses, lk, ol, nm, inl = loop.tlm_outs[k]
+            out["track_local_poses"], out["track_local_counts"] = poses.astype(np.float64), np.stack([nm, inl], 1).astype(np.float64)
+            out["track_local_matches"] = per_kp(lk, ol)
+        if getattr(loop, "slp_outs", [None] * 3)[k] is not None:   # (the inertial loop's TrackLocalMap)
+            lk, nm = loop.slp_outs[k]
+            out["search_local_points_counts"], out["search_local_points_matches"] = nm.astype(np.float64), per_kp(lk)
+    if loop.lidar_counts is not None:
+        out["lidar_counts"] = np.asarray(loop.lidar_counts).T.astype(np.float64)
+    if loop.map_inc is not None:
+        out["map_incremental"] = np.stack(loop.map_inc, 1).astype(np.float64)
+    if hasattr(loop, "li"):
+        out["lidar_inertial_states"] = np.asarray(loop.li.states36(), np.float64)
+    done = {}
+    for b in loop.ba_run_batches():
+        for i, wid in enumerate(getattr(b, "window_ids", ())):   # (the inertial loop's LocalLVIBA batches carry no window ids)
+            if wid not in done and (b.stats[i].iterations > 0 or b.results[i] > 0):
+                done[wid] = b.result(i)
+    if done:
+        ids = sorted(done)
+        res = [done[w] for w in ids]
+        out["ba_windows"] = np.array([[w, len(r[0]), len(r[1]), len(r[2]), r[4].iterations, r[4].trials, r[5].n_planes] for w, r in zip(ids, res)], np.float64)
+        out["ba_poses"] = np.concatenate([r[0] for r in res]).astype(np.float64)
+        out["ba_points"] = np.concatenate([r[1] for r in res]).astype(np.float64)
+        out["ba_chi2"] = np.concatenate([r[2] for r in res]).astype(np.float64)
+    size = sum(a.nbytes for a in out.values())
+    if size > DUMP_BUDGET:
+        raise SystemExit("bench.py --dump-outputs: %d bytes, more than the %d allowed" % (size, DUMP_BUDGET))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # workload
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -440,6 +509,17 @@ def uniform_ba_windows(pkg, synthetic):
     return out
 
 
+def render_frame(u, f, W, H):
+    """Frame f of scene u: the stereo pair and the scan (a function of u and f alone, so that worker processes may render it)."""
+    import tc2li_loader
+    tc2li_loader.load()
+    from tc2li_slam_amd import synthetic
+    sc = synthetic.Scene(u)
+    left, _ = sc.render(0.0, W, H, noise_seed=1 + 2 * f, cam_z=float(f))
+    right, _ = sc.render(synthetic.BASELINE, W, H, noise_seed=2 + 2 * f, cam_z=float(f))
+    return left, right, synthetic.lidar_scan(sc, u + 1 + f)
+
+
 class FrameInputs:
     """What one frame index holds for all the unique scenes: stereo images [U, 2, H, W], raw scans, LiDAR states, and (after
     Workload.build_tracking_inputs) the last frame and local map of every scene."""
@@ -451,7 +531,7 @@ class Workload:
     """The synthetic inputs of `unique` distinct sequences: stereo pair, 64-beam scan, the street's accumulated
     LiDAR map, the last frame TrackWithMotionModel projects from and the local map TrackLocalMap searches; sequence s uses set s % unique."""
 
-    def __init__(self, pkg, synthetic, unique, map_length, with_ba, cycle=1):
+    def __init__(self, pkg, synthetic, unique, map_length, with_ba, cycle=1, frames=None):
         self.pkg, self.synthetic, self.U = pkg, synthetic, unique
         self.K = max(1, int(cycle))
         W, H = synthetic.WIDTH, synthetic.HEIGHT
@@ -461,7 +541,7 @@ class Workload:
         self.cam5 = np.float32([synthetic.FX, synthetic.FY, synthetic.CX, synthetic.CY, self.bf]).astype(np.float64)
         # frame f of scene u: the camera f metres down the street (Scene.render's cam_z), the LiDAR at sensor_pose(u + 1 + f) (1 m per frame);
         # frames[0] is what rounds 1-5 processed every step.  The rendered frames are kept in /tmp for the child processes of one bench run.
-        self.frames = self._render_frames(synthetic, unique, self.K, W, H)
+        self.frames = frames if frames is not None else self._render_frames(synthetic, unique, self.K, W, H)
         self.images, self.scans = self.frames[0].images, self.frames[0].scans
         self.maps = []
         for fr in self.frames:
@@ -489,7 +569,9 @@ class Workload:
         self.local = None  # per unique: (held, held_Xw, local map points)
 
     @staticmethod
-    def _render_frames(synthetic, unique, K, W, H):
+    def _render_frames(synthetic, unique, K, W, H, workers=1):
+        """The frames of the cache below, or rendered (by `workers` processes: ~1 s of one CPU per scene and frame, 32 at the defaults) and cached.
+        More than one worker only before this process initialises the GPU."""
         import hashlib
         import tempfile
         gen = hashlib.sha256(open(synthetic.__file__, "rb").read()).hexdigest()[:12]   # (the cache belongs to this generator)
@@ -505,14 +587,19 @@ class Workload:
             return frames
         except Exception:  # noqa: BLE001  (no cache yet, or one of another shape: render)
             pass
+        jobs = [(u, fr.index) for fr in frames for u in range(unique)]
+        if workers > 1 and len(jobs) > 1:
+            import multiprocessing
+            from concurrent.futures import ProcessPoolExecutor
+            with ProcessPoolExecutor(min(workers, len(jobs)), mp_context=multiprocessing.get_context("spawn")) as ex:
+                rendered = list(ex.map(render_frame, *zip(*jobs), [W] * len(jobs), [H] * len(jobs)))
+        else:
+            rendered = [render_frame(u, f, W, H) for u, f in jobs]
         for fr in frames:
-            f = fr.index
             fr.images = np.empty((unique, 2, H, W), np.uint8)
-            for u in range(unique):
-                sc = synthetic.Scene(u)
-                fr.images[u, 0], _ = sc.render(0.0, W, H, noise_seed=1 + 2 * f, cam_z=float(f))
-                fr.images[u, 1], _ = sc.render(synthetic.BASELINE, W, H, noise_seed=2 + 2 * f, cam_z=float(f))
-                fr.scans.append(synthetic.lidar_scan(sc, u + 1 + f))
+        for (u, f), (left, right, scan) in zip(jobs, rendered):
+            frames[f].images[u, 0], frames[f].images[u, 1] = left, right
+            frames[f].scans.append(scan)
         try:
             tmp = cache + ".%d.tmp.npz" % os.getpid()
             np.savez(tmp, images=np.stack([fr.images for fr in frames]),
@@ -800,6 +887,8 @@ class Loop:
         self.trk_outs = [None, None, None]
         self.tlm_outs = [None, None, None]
         self.tlm_out = None
+        self.last_k = 0          # the feature buffer of the last step tracked
+        self.map_inc = None      # map_incremental_batch's arrays of the last LiDAR step
         self.track_ms = [0.0, 0.0, 0.0]
         self.lidar_counts = None
         self.map_adds = [0, 0]
@@ -861,6 +950,7 @@ class Loop:
                                                           fs.held, fs.held_Xw, fs.local_pts, fs.local_off, wl.cam5, th=1.0, stream=stream,
                                                           out=self.tlm_outs[k])
         self.tlm_out = self.tlm_outs[k]
+        self.last_k = k
         self.track_ms[2] = 1e3 * (time.perf_counter() - t0)
 
     def fov_positions(self, f=0):
@@ -883,7 +973,8 @@ class Loop:
                                                       want_points=False)[0]
         self.lidar_times.append(self.lidar.last_timings().astype(float))
         # UpdateMap -> map_incremental (Tracking.cc:1602-1603) for every sequence's map: one batched call
-        na, nn, _ = pkg.capi.map_incremental_batch(self.lidar, self.scan_ids, self.maps, fs.states, stream=self.lidar_stream.cuda_stream)
+        self.map_inc = pkg.capi.map_incremental_batch(self.lidar, self.scan_ids, self.maps, fs.states, stream=self.lidar_stream.cuda_stream)
+        na, nn, _ = self.map_inc
         self.map_adds = [int(na.sum()), int(nn.sum())]
 
     def ba_stats_batch(self):
@@ -1309,6 +1400,7 @@ class InertialLoop(Loop):
         t0 = time.perf_counter()
         self.slp_outs[k] = pkg.capi.search_local_points_batch(self.exts[k], F, self.orb_outs[k][0], self.st_outs[k][0], self.pose_pred, self.held, self.held_Xw,
                                                               self.local_pts, self.local_off, wl.cam5, th=1.0, stream=stream, out=self.slp_outs[k])
+        self.last_k = k
         self.pi.preintegrate()
         self.pi.run(stream)
         self.track_ms[2] = 1e3 * (time.perf_counter() - t0)
@@ -1837,6 +1929,8 @@ def cpu_baseline(wl, args, n_seq_gpu, with_ba):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
+    if not args.full:  # a plain run measures the headline and nothing else
+        args.no_extra_lines = args.no_cpu_baseline = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args, argv)
 
@@ -1876,6 +1970,22 @@ def main(argv=None):
         if under_profiler():
             raise SystemExit("bench.py under a profiler: pass --no-cpu-baseline (the CPU leg builds and runs the oracle; nothing to profile there)")
         ge.build_oracle()
+    if args.scaling == "strong":
+        seq_ids = dist_util.shard_units(args.sequences, rank, world)
+        total_sequences = args.sequences
+    else:
+        seq_ids = list(range(rank * args.frames, (rank + 1) * args.frames))
+        total_sequences = args.frames * world
+    if not seq_ids:
+        raise SystemExit("bench.py: rank %d owns no sequence (%d sequences over %d ranks)" % (rank, args.sequences, world))
+    U = min(args.unique, max(len(seq_ids), 1) if args.scaling == "weak" else args.unique)
+    cycle = 1 if (args.inertial_loop or args.mfma_only) else args.cycle_frames
+    # the inputs are rendered before this process touches the GPU, by as many worker processes as the rank has CPUs (one process: 36 s at
+    # the defaults, most of a plain run's set-up when no earlier run left them in the cache)
+    frames = None
+    if not args.mfma_only:
+        frames = Workload._render_frames(synthetic, U, max(1, int(cycle)), synthetic.WIDTH, synthetic.HEIGHT,
+                                         workers=1 if under_profiler() else host_budget["thread_budget"])
     # ---- the single-sequence line runs FIRST, in a child process of its own (this process has not touched the GPU yet: a process that has
     # may not start children): the HIP runtime maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default), and the ten
     # streams of the five stage threads then queue behind each other -- with one sequence per step, where every kernel is tiny, that false
@@ -1904,17 +2014,7 @@ def main(argv=None):
         return 0
     dist = dist_util.init(args.backend, rank, world, device=torch.device("cuda", local_rank) if args.backend == "nccl" else None)
 
-    if args.scaling == "strong":
-        seq_ids = dist_util.shard_units(args.sequences, rank, world)
-        total_sequences = args.sequences
-    else:
-        seq_ids = list(range(rank * args.frames, (rank + 1) * args.frames))
-        total_sequences = args.frames * world
-    if not seq_ids:
-        raise SystemExit("bench.py: rank %d owns no sequence (%d sequences over %d ranks)" % (rank, args.sequences, world))
-    U = min(args.unique, max(len(seq_ids), 1) if args.scaling == "weak" else args.unique)
-    wl = Workload(pkg, synthetic, U, args.map_length, with_ba=False if args.front_end_only else args.ba_mix,
-                  cycle=1 if (args.inertial_loop or args.mfma_only) else args.cycle_frames)
+    wl = Workload(pkg, synthetic, U, args.map_length, with_ba=False if args.front_end_only else args.ba_mix, cycle=cycle, frames=frames)
     stream = torch.cuda.current_stream().cuda_stream
     ext0 = pkg.OrbExtractor(max_width=wl.W, max_height=wl.H, max_images=2 * U)
     wl.build_tracking_inputs(ext0, stream)
@@ -1954,6 +2054,8 @@ def main(argv=None):
     host_budget["cpu_s_per_wall_s_by_thread_name"] = {k: round((v - tcpu0.get(k, 0.0)) / max(local_elapsed, 1e-9), 2)
                                                        for k, v in sorted(tcpu1.items(), key=lambda kv: -(kv[1] - tcpu0.get(kv[0], 0.0)))
                                                        if v - tcpu0.get(k, 0.0) > 0.02 * local_elapsed}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(loop, args.dump_outputs)
     elapsed = dist_util.max_elapsed(dist, local_elapsed, device="cuda" if args.backend == "nccl" else "cpu")
     ranks_seen = dist_util.count_ranks(dist, device="cuda" if args.backend == "nccl" else "cpu")
     if set(stages) != {"orb", "track", "lidar", "ba"}:  # diagnostics: which stages slow each other down

@@ -74,9 +74,9 @@ pkg.capi.set_host_thread_budget(256)
 print(pkg.capi.host_threads())
 import threading
 n0 = threading.active_count()
-def os_threads():
+def os_threads():   # the library's threads (every one is named tc2li-*): on a machine with a GPU the pool's first HIP call also starts the runtime's own
     import os
-    return len(os.listdir('/proc/self/task'))
+    return sum(open('/proc/self/task/%s/comm' % t).read().startswith('tc2li-') for t in os.listdir('/proc/self/task'))
 t0 = os_threads()
 pkg.capi.set_host_thread_budget(32)
 import ctypes as C
