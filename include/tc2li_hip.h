@@ -155,7 +155,8 @@ int tc2li_stereo_match_batch(tc2li_orb* orb, int n_frames, float bf, float b, fl
 
 /* ------------------------------------------------------------------------------------------------
  * LiDAR front end, camera-LiDAR branch -- replaces the internals of
- *   Preprocess::process / velodyne_handler      SF/include/lidar_front_end/preprocess.cpp:63-167 (non-feature branch)
+ *   Preprocess::process / velodyne_handler      SF/include/lidar_front_end/preprocess.cpp:63-167 (both branches: feature_enabled
+ *                                                through tc2li_lidar_set_preprocess_features, give_feature :169-623)
  *   pcl::VoxelGrid<PointXYZINormal>::filter      call sites LidarFrontEnd.cpp:712-714, 913-915
  *   ikdtree.Build / Add_Points / Nearest_Search  SF/include/ikd-Tree/ikd_Tree.cpp:409-461 (a hash grid here, same 5-NN)
  *   feature_extraction / EstiPlane               LidarFrontEnd.cpp:964-1073, with pointBodyToWorld :130-139
@@ -186,9 +187,30 @@ int tc2li_lidar_create(int max_points_per_scan, int max_scans, tc2li_lidar** out
 void tc2li_lidar_destroy(tc2li_lidar* lidar);
 
 /* Preprocess::process for a Velodyne cloud with feature_enabled = false: keeps point i when i % point_filter_num == 0
- * and |p|^2 > blind^2; curvature = time * time_unit_scale (ms).  Returns the number of points written. */
+ * and |p|^2 > blind^2; curvature = time * time_unit_scale (ms).  Returns the number of points written.  With the handle's
+ * tc2li_lidar_set_preprocess_features switch on: the feature branch instead (see there). */
 int tc2li_lidar_preprocess(tc2li_lidar* lidar, const tc2li_velodyne_point* raw, int n, int point_filter_num, double blind,
                            float time_unit_scale, tc2li_point* out, int capacity);
+
+/* Preprocess::feature_enabled (LidarFrontEnd.cpp:639, :823): f != NULL switches every preprocess of the handle (tc2li_lidar_preprocess,
+ * tc2li_lidar_frontend_batch, tc2li_lidar_inertial_prepare_batch, tc2li_lidar_inertial_frontend_batch) to velodyne_handler's feature
+ * branch (preprocess.cpp:100-143): points whose ring >= n_lines are dropped, the others bucketed into their ring's line in input order,
+ * give_feature (:169-482) labels every line, and the output is pl_surf -- surface points, every point_filter_num-th of a run of them,
+ * an unfinished group averaged, line by line.  blind is compared with the 2-D range sqrt(x^2 + y^2) there.  f == NULL: off (the default).
+ * point_filter_num, blind and time_unit_scale keep coming from the preprocess calls. */
+typedef struct tc2li_preprocess_features {
+    int32_t n_lines;   /* N_SCANS ("preprocess/scan_line"), 1..128 */
+    int32_t reserved;  /* 0 */
+    double  dis_b;     /* Preprocess::disB: the ctor assigns disA twice (preprocess.cpp:40-41) and disB never; 0.0 = zeroed memory */
+} tc2li_preprocess_features;
+int tc2li_lidar_set_preprocess_features(tc2li_lidar* lidar, const tc2li_preprocess_features* f);
+/* pl_corn of scan slot `scan` of the last preprocess with the switch on: the points labelled Edge_Jump or Edge_Plane, line by line.
+ * Returns the number of points written. */
+int tc2li_lidar_corner_points(tc2li_lidar* lidar, int scan, tc2li_point* out, int capacity);
+/* Tests / diagnostics: the Feature label (preprocess.h:40: Nor 0, Poss_Plane 1, Real_Plane 2, Edge_Jump 3, Edge_Plane 4, Wire 5) of every
+ * bucketed point of scan slot `scan` of the last preprocess with the switch on, in line order, and the n_lines + 1 line offsets.  A line
+ * of fewer than 2 points is labelled Nor.  Returns the number of labels written. */
+int tc2li_lidar_point_labels(tc2li_lidar* lidar, int scan, uint8_t* ftype, int32_t* ring_offsets, int capacity);
 
 /* downSizeFilterSurf.setInputCloud(in); downSizeFilterSurf.filter(out) with leaf size `leaf` on all three axes:
  * one centroid (of every field) per occupied voxel, in ascending voxel-index order. */

@@ -75,6 +75,9 @@ def lib():
     L.tc2li_lidar_destroy.restype = None
     L.tc2li_lidar_preprocess.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_void_p, C.c_int]
     L.tc2li_lidar_voxel_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int]
+    L.tc2li_lidar_set_preprocess_features.argtypes = [C.c_void_p, C.c_void_p]
+    L.tc2li_lidar_corner_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.tc2li_lidar_point_labels.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     L.tc2li_lidar_map_create.argtypes = [C.POINTER(C.c_void_p)]
     L.tc2li_lidar_map_destroy.argtypes = [C.c_void_p]
     L.tc2li_lidar_map_destroy.restype = None
@@ -616,6 +619,10 @@ def lidar_fov_segment_batch(local_maps, pos_lid3, cube_len=200.0, det_range=100.
     return boxes, counts
 
 
+class PreprocessFeatures(C.Structure):
+    _fields_ = [("n_lines", C.c_int32), ("reserved", C.c_int32), ("dis_b", C.c_double)]
+
+
 class LidarFrontEnd:
     """Stage functions of the camera-LiDAR front end (Preprocess::process, VoxelGrid::filter, feature_extraction)."""
 
@@ -645,6 +652,30 @@ class LidarFrontEnd:
         n = _check(lib().tc2li_lidar_preprocess(self._h, raw.ctypes.data, len(raw), point_filter_num, blind, time_unit_scale,
                                                 out.ctypes.data, len(out)))
         return out[:n].copy()
+
+    def set_features(self, n_lines=64, dis_b=0.0):
+        """``Preprocess::feature_enabled``: every preprocess of this handle (process, frontend_batch, the inertial batch) takes the plane /
+        edge classifier of ``give_feature`` with N_SCANS = n_lines; ``None``: off (the default)."""
+        if n_lines is None:
+            _check(lib().tc2li_lidar_set_preprocess_features(self._h, None))
+            return
+        f = PreprocessFeatures(int(n_lines), 0, float(dis_b))
+        _check(lib().tc2li_lidar_set_preprocess_features(self._h, C.byref(f)))
+        self._n_lines = int(n_lines)
+
+    def corners(self, scan=0):
+        """``pl_corn`` (Edge_Jump / Edge_Plane points) of scan slot `scan` of the last preprocess with the classifier on."""
+        out = np.zeros(max(self.cap, 1), POINT_DTYPE)
+        n = _check(lib().tc2li_lidar_corner_points(self._h, int(scan), out.ctypes.data, len(out)))
+        return out[:n].copy()
+
+    def labels(self, scan=0):
+        """(Feature label per bucketed point in line order, the n_lines + 1 line offsets) of scan slot `scan` of the last preprocess with
+        the classifier on."""
+        ft = np.zeros(max(self.cap, 1), np.uint8)
+        off = np.zeros(129, np.int32)
+        n = _check(lib().tc2li_lidar_point_labels(self._h, int(scan), ft.ctypes.data, off.ctypes.data, len(ft)))
+        return ft[:n].copy(), off[:self._n_lines + 1].copy()
 
     def voxel_filter(self, points, leaf=0.5):
         points = np.ascontiguousarray(points, POINT_DTYPE)

@@ -72,6 +72,27 @@ void launch_pre_stream(const VelodynePoint* raw, const int* raw_count, const Sca
 void launch_pre_scatter(const VelodynePoint* raw, const int* raw_count, const ScanSlot* slots, const SegBlock* blocks,
                         int nblocks, PreprocessParams prm, const int* block_offsets, PointXYZINormal* out, hipStream_t st);
 
+// b1 with feature_enabled (lidar_feature_kernels.hip): the plane / edge classifier of give_feature.  The cosines are the ctor's
+// (preprocess.cpp:55-58), computed on the host.
+constexpr int kFeatMaxLines = 128, kFeatLineStride = kFeatMaxLines + 1;  // pl_buff[128]; line offsets per scan: [n_lines + 1] in a row of 129
+struct FeatureParams {
+    int32_t n_lines, point_filter_num;
+    float time_unit_scale;
+    int32_t pad_;
+    double blind, dis_b, jump_up_limit, jump_down_limit, cos160, smallp_intersect;
+};
+struct FeatureWork {  // per point of a slot, in line order: position + range, intensity + curvature, dista, Feature label
+    float4* pts;
+    float2* ic;
+    double* dista;
+    uint8_t* lab;
+    int* line_off;   // [scans][kFeatLineStride]: start of each line inside the slot, then the bucketed count
+    int* line_head;  // [scans][kFeatMaxLines]
+    int2* line_cnt;  // [scans][kFeatMaxLines]: surface / corner points of the line, then where they start in the scan's output
+};
+void launch_feature_preprocess(const VelodynePoint* raw, const int* raw_count, const ScanSlot* slots, int nscans, const FeatureParams& fp,
+                               const FeatureWork& w, PointXYZINormal* out, int* out_count, PointXYZINormal* corn, int* corn_count, hipStream_t st);
+
 void launch_voxel_bbox(const PointXYZINormal* pts, const int* count, const ScanSlot* slots, const SegBlock* blocks, int nblocks,
                        int* bbox_enc, hipStream_t st);
 void launch_voxel_params(const int* bbox_enc, const int* count, const ScanSlot* slots, int nscans, float leaf, VoxelParams* vp,

@@ -136,6 +136,18 @@ struct tc2li_lidar {
     int n_scans = 0;
     // stage boundaries of the last tc2li_lidar_frontend_batch call: start, after preprocess, before / after the centroid
     // kernel, after the kNN + plane kernel, end
+    // Preprocess::feature_enabled (tc2li_lidar_set_preprocess_features): the classifier's settings and work arrays, allocated on first use;
+    // feat_scans: the scan slots whose labels / corner clouds the last preprocess left (0 after a preprocess with the switch off)
+    bool feat_on = false;
+    FeatureParams feat{};
+    int feat_scans = 0;
+    DevBuf<float4> d_feat_pts;
+    DevBuf<float2> d_feat_ic;
+    DevBuf<double> d_feat_dista;
+    DevBuf<uint8_t> d_feat_lab;
+    DevBuf<int> d_feat_line_off, d_feat_line_head, d_corn_count;
+    DevBuf<int2> d_feat_line_cnt;
+    DevBuf<PointXYZINormal> d_corn;
     hipEvent_t ev[7] = {};  // [6]: between the two kernels of the neighbour search
     bool timed = false;
     void record(int k, hipStream_t st) { if (ev[k] || hipEventCreate(&ev[k]) == hipSuccess) (void)hipEventRecord(ev[k], st); }
@@ -192,6 +204,27 @@ int compact_segments(tc2li_lidar* L, const int* d_counts, hipStream_t st) {
     return TC2LI_OK;
 }
 
+// b1 with feature_enabled: the classifier (lidar_feature_kernels.hip) into d_pre / d_pre_count, pl_corn into d_corn.  It leaves the
+// voxel filter no bounding boxes or voxel keys and the time sort no key array: those stages compute their own.
+int run_preprocess_features(tc2li_lidar* L, const VelodynePoint* d_raw, int point_filter_num, double blind, float time_unit_scale, hipStream_t st) {
+    const size_t T = L->total, S = L->max_scans;
+    TC2LI_HIP_CHECK(L->d_feat_pts.ensure(T)); TC2LI_HIP_CHECK(L->d_feat_ic.ensure(T)); TC2LI_HIP_CHECK(L->d_feat_dista.ensure(T));
+    TC2LI_HIP_CHECK(L->d_feat_lab.ensure(T)); TC2LI_HIP_CHECK(L->d_corn.ensure(T)); TC2LI_HIP_CHECK(L->d_corn_count.ensure(S));
+    TC2LI_HIP_CHECK(L->d_feat_line_off.ensure(S * kFeatLineStride)); TC2LI_HIP_CHECK(L->d_feat_line_head.ensure(S * kFeatMaxLines));
+    TC2LI_HIP_CHECK(L->d_feat_line_cnt.ensure(S * kFeatMaxLines));
+    FeatureParams fp = L->feat;
+    fp.point_filter_num = point_filter_num;
+    fp.time_unit_scale = time_unit_scale;
+    fp.blind = blind;
+    const FeatureWork w{L->d_feat_pts.p, L->d_feat_ic.p, L->d_feat_dista.p, L->d_feat_lab.p, L->d_feat_line_off.p, L->d_feat_line_head.p,
+                        L->d_feat_line_cnt.p};
+    launch_feature_preprocess(d_raw, L->d_raw_count.p, L->d_slots.p, L->n_scans, fp, w, L->d_pre.p, L->d_pre_count.p, L->d_corn.p,
+                              L->d_corn_count.p, st);
+    TC2LI_HIP_CHECK(hipGetLastError());
+    L->feat_scans = L->n_scans;
+    return TC2LI_OK;
+}
+
 // b1
 int run_preprocess(tc2li_lidar* L, const VelodynePoint* d_raw, int point_filter_num, double blind, float time_unit_scale, hipStream_t st,
                    float* time_out = nullptr, bool* times_written = nullptr, float voxel_leaf = 0.f /* > 0: the voxel filter follows at this leaf */) {
@@ -203,6 +236,8 @@ int run_preprocess(tc2li_lidar* L, const VelodynePoint* d_raw, int point_filter_
     // boxes; a few scans: the three-launch form, whose passes are spread over all points.  TC2LI_PRE_STREAM=0 / 1 forces one (tests run both).
     const char* env = getenv("TC2LI_PRE_STREAM");
     L->pre_bbox_valid = false;
+    L->feat_scans = 0;
+    if (L->feat_on) return run_preprocess_features(L, d_raw, point_filter_num, blind, time_unit_scale, st);
     if (env ? atoi(env) != 0 : L->n_scans >= 64) {
         // (the voxel filter's sorted form follows at voxel_leaf: the pass leaves it the points' voxel coordinates in the sort's second key buffer)
         const char* vk_env = getenv("TC2LI_VOXEL_PRE_KEYS");  // =0: the filter reads the points' positions itself (A/B, tests)
@@ -515,6 +550,50 @@ int tc2li_lidar_preprocess(tc2li_lidar* L, const tc2li_velodyne_point* raw, int 
     TC2LI_HIP_CHECK(copy_sync(&m, L->d_pre_count.p, sizeof(int), hipMemcpyDeviceToHost, ps));
     if (m > capacity) { set_error("output capacity %d < %d", capacity, m); return TC2LI_ERR_CAPACITY; }
     if (m) TC2LI_HIP_CHECK(copy_sync(out, L->d_pre.p, (size_t)m * sizeof(PointXYZINormal), hipMemcpyDeviceToHost, ps));
+    return m;
+}
+
+int tc2li_lidar_set_preprocess_features(tc2li_lidar* L, const tc2li_preprocess_features* f) {
+    if (!L || (f && (f->n_lines < 1 || f->n_lines > kFeatMaxLines || f->reserved != 0))) {
+        set_error("tc2li_lidar_set_preprocess_features: invalid argument");
+        return TC2LI_ERR_INVALID;
+    }
+    L->feat_on = f != nullptr;
+    if (!f) return TC2LI_OK;
+    FeatureParams& fp = L->feat;
+    memset(&fp, 0, sizeof(fp));
+    fp.n_lines = f->n_lines;
+    fp.dis_b = f->dis_b;
+    // Preprocess::Preprocess (preprocess.cpp:46-58): the limits in degrees, then their cosines
+    fp.jump_up_limit = std::cos(170.0 / 180 * M_PI);
+    fp.jump_down_limit = std::cos(8.0 / 180 * M_PI);
+    fp.cos160 = std::cos(160.0 / 180 * M_PI);
+    fp.smallp_intersect = std::cos(172.5 / 180 * M_PI);
+    return TC2LI_OK;
+}
+
+int tc2li_lidar_corner_points(tc2li_lidar* L, int scan, tc2li_point* out, int capacity) {
+    if (!L || !out || capacity < 0) { set_error("tc2li_lidar_corner_points: invalid argument"); return TC2LI_ERR_INVALID; }
+    if (scan < 0 || scan >= L->feat_scans) { set_error("tc2li_lidar_corner_points: slot %d holds no result of the feature branch", scan); return TC2LI_ERR_INVALID; }
+    hipStream_t ps = private_stream();
+    int m = 0;
+    TC2LI_HIP_CHECK(copy_sync(&m, L->d_corn_count.p + scan, sizeof(int), hipMemcpyDeviceToHost, ps));
+    if (m > capacity) { set_error("output capacity %d < %d", capacity, m); return TC2LI_ERR_CAPACITY; }
+    if (m) TC2LI_HIP_CHECK(copy_sync(out, L->d_corn.p + (size_t)scan * L->cap, (size_t)m * sizeof(PointXYZINormal), hipMemcpyDeviceToHost, ps));
+    return m;
+}
+
+int tc2li_lidar_point_labels(tc2li_lidar* L, int scan, uint8_t* ftype, int32_t* ring_offsets, int capacity) {
+    if (!L || !ftype || !ring_offsets || capacity < 0) { set_error("tc2li_lidar_point_labels: invalid argument"); return TC2LI_ERR_INVALID; }
+    if (scan < 0 || scan >= L->feat_scans) { set_error("tc2li_lidar_point_labels: slot %d holds no result of the feature branch", scan); return TC2LI_ERR_INVALID; }
+    hipStream_t ps = private_stream();
+    const int nl = L->feat.n_lines;
+    std::vector<int> off(nl + 1);
+    TC2LI_HIP_CHECK(copy_sync(off.data(), L->d_feat_line_off.p + (size_t)scan * kFeatLineStride, (nl + 1) * sizeof(int), hipMemcpyDeviceToHost, ps));
+    const int m = off[nl];
+    if (m > capacity) { set_error("output capacity %d < %d", capacity, m); return TC2LI_ERR_CAPACITY; }
+    if (m) TC2LI_HIP_CHECK(copy_sync(ftype, L->d_feat_lab.p + (size_t)scan * L->cap, (size_t)m, hipMemcpyDeviceToHost, ps));
+    memcpy(ring_offsets, off.data(), (nl + 1) * sizeof(int));
     return m;
 }
 
