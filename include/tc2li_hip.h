@@ -1025,6 +1025,119 @@ int tc2li_diag_peaks(double* mfma_f64_tflops, double* fma_f64_tflops, double* hb
  * counter: the data sheet's 78.6 TFLOP/s of f64 matrix / vector arithmetic assume 2.4 GHz. */
 int tc2li_diag_clocks(double* mfma_loop_ghz, double* fma_loop_ghz);
 
+/* ------------------------------------------------------------------------------------------------
+ * ORB vocabulary -- DBoW2's TemplatedVocabulary<FORB::TDescriptor, FORB> (ORBVocabulary, SF/Thirdparty/DBoW2/DBoW2/
+ * TemplatedVocabulary.h), the transform behind Frame::ComputeBoW / KeyFrame::ComputeBoW (SF/src/Frame.cc:768-775,
+ * SF/src/KeyFrame.cc:110-119) and ORBmatcher::SearchByBoW(KeyFrame*, Frame&) (SF/src/ORBmatcher.cc:232-434).
+ * Loading and readback are host logic and work without a GPU; the device copy of a vocabulary is made on the first call that
+ * computes with it (once per handle, thread-safe: tracking and local mapping share one vocabulary), on the device current then.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct tc2li_vocabulary tc2li_vocabulary;
+
+/* TemplatedVocabulary::loadFromTextFile (TemplatedVocabulary.h:1350-1436; System.cc:126, 148 load ORBvoc.txt at start-up).  The first
+ * line is "k L scoring weighting" (0 <= k <= 20, 1 <= L <= 10, 0 <= scoring <= 5, 0 <= weighting <= 3), every further line one node in
+ * id order from 1 (the root, node 0, has no line): "parent isLeaf d0 .. d31 weight", separated by any whitespace ('\r' included);
+ * descriptor bytes are read as int and cast to unsigned char (FORB::fromString), the weight as a double (strtod: the value operator>>
+ * gives).  Children are appended to their parent in line order, word ids numbered in the order of the lines with isLeaf > 0.
+ * Blank lines are skipped.  The reference turns the empty line after saveToTextFile's final endl into one more node built from
+ * uninitialised pid / nIsLeaf (undefined behaviour), and spins forever on a missing file; here both are defined.  Rejected with
+ * TC2LI_ERR_INVALID, the file's line named in tc2li_last_error(): an unreadable file, a bad header, a line with fewer than 35 fields or
+ * a field that is not a number, a parent that is not an earlier node, a node flagged as a word that receives children, a childless
+ * node not flagged as a word (the descent's leaf test is children.empty(), :340, so every leaf is a word). */
+int tc2li_vocabulary_load_text(const char* path, tc2li_vocabulary** out);
+/* The same content from arrays in file order: node i + 1 of n_nodes has parent[i], is_leaf[i], descriptors[i][32], weights[i].
+ * Same checks (the message names the node). */
+int tc2li_vocabulary_create(int k, int L, int scoring, int weighting, int n_nodes, const int32_t* parent, const int32_t* is_leaf,
+                            const uint8_t* descriptors, const double* weights, tc2li_vocabulary** out);
+/* info[6] = k, L, scoring, weighting, nodes (the root included), words.  Returns 6. */
+int tc2li_vocabulary_info(const tc2li_vocabulary* voc, int32_t* info);
+/* Host readback per node in reference numbering (root first; arrays [nodes], NULL skips one): parent (-1 for the root), word id
+ * (-1 for a node that is not a word; the reference's default is 0), descriptor [32], weight (the root's 0).  Returns the node count. */
+int tc2li_vocabulary_nodes(const tc2li_vocabulary* voc, int32_t* parent, int32_t* word_id, uint8_t* descriptors, double* weights);
+void tc2li_vocabulary_destroy(tc2li_vocabulary* voc);
+
+/* Output of the transform of a batch (caller arrays).  Frame f owns the slot range [base_f, base_f + n_f) of every per-descriptor
+ * array, base_f = desc_offsets[f] (tc2li_vocabulary_transform_batch) or f * capacity (tc2li_orb_compute_bow_batch):
+ *   word / node       per descriptor i: word id and the node recorded for the FeatureVector, -1 for a stopped feature (weight <= 0);
+ *   n_words[f]        entries of frame f's mBowVec: bow_word[base_f ..] word ids ascending, bow_value[base_f ..] their values;
+ *   n_nodes[f]        entries of frame f's mFeatVec: fv_node[base_f ..] node ids ascending, fv_offset[base_f + f ..] (n_nodes[f] + 1
+ *                     entries, from 0) and fv_index[base_f ..] the feature indices of every node in feature order.
+ * fv_offset holds (total slots + n_frames) entries.  A tc2li_keyframe_view with n_nodes = n_nodes[f], fv_node = fv_node + base_f,
+ * fv_offset = fv_offset + base_f + f and fv_index = fv_index + base_f is frame f's FeatureVector, without copying.  Slots beyond the
+ * counts read -1 (bow_value 0). */
+typedef struct tc2li_bow_out {
+    int32_t* word;
+    int32_t* node;
+    int32_t* n_words;
+    int32_t* bow_word;
+    double* bow_value;
+    int32_t* n_nodes;
+    int32_t* fv_node;
+    int32_t* fv_offset;
+    int32_t* fv_index;
+} tc2li_bow_out;
+
+/* TemplatedVocabulary::transform(features, BowVector&, FeatureVector&, levelsup) (TemplatedVocabulary.h:1139-1206, per feature
+ * :1230-1271) for n_frames frames of host descriptors: frame f's are rows desc_offsets[f] .. desc_offsets[f + 1] of
+ * descriptors [..][32] (desc_offsets [n_frames + 1], desc_offsets[0] = 0).  ComputeBoW passes levelsup = 4.  Bit for bit the
+ * reference: the descent takes at every level the first child of least FORB::distance and stops at a node without children; the
+ * node recorded is the one chosen at level L - levelsup (L the header's), the root (0) when L - levelsup <= 0 -- and the leaf itself
+ * when the leaf lies above that level, where the reference leaves nid uninitialised (undefined behaviour).  A word's value is its weight
+ * added once per feature in feature order (TF, TF_IDF) or its weight (IDF, BINARY); L1 (L1_NORM, CHI_SQUARE, KL, BHATTACHARYYA) or L2
+ * (L2_NORM) normalisation in one pass in ascending word order, applied when the norm is > 0; DOT_PRODUCT with TF / TF_IDF divides by
+ * the number of words instead.  Returns n_frames. */
+int tc2li_vocabulary_transform_batch(tc2li_vocabulary* voc, int n_frames, const uint8_t* descriptors, const int32_t* desc_offsets,
+                                     int levelsup, const tc2li_bow_out* out, void* stream);
+/* The same for the device-resident features of frames: frame f is image 2f of the handle's last tc2li_orb_extract_batch call (lapping
+ * area {0,0}, as the tracking batches), feature i its keypoint i; its slots start at f * capacity.  The descriptors never leave the
+ * device.  Returns n_frames. */
+int tc2li_orb_compute_bow_batch(tc2li_orb* orb, tc2li_vocabulary* voc, int n_frames, int levelsup, int capacity, const tc2li_bow_out* out,
+                                void* stream);
+
+/* ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vpMapPointMatches) (SF/src/ORBmatcher.cc:232-434; ORBmatcher(0.7, true) in
+ * Tracking::TrackReferenceKeyFrame, SF/src/Tracking.cc:2603-2662, (0.75, true) in relocalisation :3517) for a batch of pairs.
+ * keyframe: n, keys (angle), descriptors, has_point (= pMP && !pMP->isBad()) and its FeatureVector (n_nodes, fv_*); frame: n, keys,
+ * descriptors and its FeatureVector (has_point, u_right, depth, pose7 are not read).  Common nodes in ascending order; within a node the
+ * keyframe's features in order, the frame's features not yet matched; best and second-best distance (both from 256, strict <);
+ * accepted when best <= TH_LOW (50) and best < nn_ratio * second (float); with check_orientation the rotation histogram (30 bins,
+ * bin = roundf(rot / 30), so only 0..12 occur) and ComputeThreeMaxima (:2021-2062).  The right-camera branch (F.Nleft != -1) is not
+ * built (pinhole stereo).  At most 4096 frame features per node (TC2LI_ERR_CAPACITY).  Out: kf_keypoint_of_keypoint [n_pairs][capacity]
+ * = the keyframe keypoint whose map point frame keypoint i now holds (vpMapPointMatches[i]) or -1, n_matches[p].  Returns n_pairs. */
+typedef struct tc2li_bow_pair {
+    tc2li_keyframe_view keyframe;
+    tc2li_keyframe_view frame;
+    float nn_ratio;                /* mfNNratio */
+    int32_t check_orientation;     /* mbCheckOrientation */
+} tc2li_bow_pair;
+int tc2li_search_by_bow_batch(const tc2li_bow_pair* pairs, int n_pairs, int capacity, int32_t* kf_keypoint_of_keypoint, int32_t* n_matches,
+                              void* stream);
+
+/* Tracking::TrackReferenceKeyFrame (SF/src/Tracking.cc:2603-2662), data path only, for a batch of independent frames whose features are
+ * device-resident -- the fallback of TrackWithMotionModel (Tracking.cc:2032, 2042, 2147) and the first frames after initialisation.
+ * Frame f is image 2f of the handle's last tc2li_orb_extract_batch call (lapping area {0,0}); keypoints ([2*n_frames][capacity], the
+ * host copy of that call's output: the device-resident copy is what is read) and u_right ([n_frames][capacity]) as for
+ * tc2li_track_motion_model_batch.  One stream, one staging upload: the frame's ComputeBoW (levelsup 4), ORBmatcher(0.7, true).SearchByBoW
+ * against refs[f] (as tc2li_search_by_bow_batch), and with at least 15 matches -- decided on the device -- SetPose(mLastFrame.GetPose()),
+ * Optimizer::PoseOptimization over every keypoint that now holds a point (keypoint order, stereo when uRight >= 0, invSigma2[octave]; the
+ * kernel of tc2li_track_motion_model_batch), outliers discarded, nmatchesMap = inliers whose point has Observations() > 0.
+ * At most 4096 keypoints per frame.  Out: poses7 [n_frames][7] (double: the optimised pose rounded through float, the last pose when
+ * failed), kf_keypoint_of_keypoint [n_frames][capacity] = the reference keyframe keypoint whose map point keypoint i holds after the
+ * discard, or -1 (every entry -1 when failed), n_matches[f] = SearchByBoW's result, n_inliers[f] = PoseOptimization's result or -1 with
+ * fewer than 15 matches, n_matches_map[f].  bow (may be NULL) receives the frames' BowVector / FeatureVector as
+ * tc2li_orb_compute_bow_batch gives them (the Frame keeps them; a new KeyFrame copies them).  The sensor rule (:2658-2661) and the
+ * MapPoint flags stay with the caller.  Returns n_frames. */
+typedef struct tc2li_reference_keyframe {
+    tc2li_keyframe_view kf;        /* mpReferenceKF: n, keys (angle), descriptors, has_point (pMP && !pMP->isBad()), n_nodes / fv_* */
+    const float* Xw;               /* [n][3] GetWorldPos() of the point of every keypoint slot that has one */
+    const uint8_t* observed;       /* [n] pMP->Observations() > 0 */
+    float last_pose7[7];           /* mLastFrame.GetPose() */
+    float pad_;
+} tc2li_reference_keyframe;
+int tc2li_track_reference_keyframe_batch(tc2li_orb* orb, tc2li_vocabulary* voc, int n_frames, const tc2li_keypoint* keypoints,
+                                         const float* u_right, int capacity, const tc2li_reference_keyframe* refs, const tc2li_camera* cam,
+                                         double* poses7, int32_t* kf_keypoint_of_keypoint, int32_t* n_matches, int32_t* n_inliers,
+                                         int32_t* n_matches_map, const tc2li_bow_out* bow, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

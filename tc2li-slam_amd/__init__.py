@@ -35,4 +35,7 @@ from .capi import (  # noqa: F401
     distribute_quadtree_device,
     exported_symbols,
     lib,
+    Vocabulary,
+    search_by_bow_batch,
+    track_reference_keyframe_batch,
 )

@@ -1875,3 +1875,187 @@ class LocalMap:
             self.close()
         except Exception:
             pass
+
+
+# ---- ORB vocabulary (DBoW2): Frame::ComputeBoW / KeyFrame::ComputeBoW, ORBmatcher::SearchByBoW(KeyFrame*, Frame&) ----------------------
+class BowOut(C.Structure):
+    """tc2li_bow_out"""
+    _fields_ = [(name, C.c_void_p) for name in ("word", "node", "n_words", "bow_word", "bow_value", "n_nodes", "fv_node", "fv_offset", "fv_index")]
+
+
+class BowPair(C.Structure):
+    """tc2li_bow_pair"""
+    _fields_ = [("keyframe", KeyframeView), ("frame", KeyframeView), ("nn_ratio", C.c_float), ("check_orientation", C.c_int32)]
+
+
+def _bow_arrays(total, n_frames):
+    a = dict(word=np.full(total, -1, np.int32), node=np.full(total, -1, np.int32), n_words=np.zeros(n_frames, np.int32),
+             bow_word=np.full(total, -1, np.int32), bow_value=np.zeros(total, np.float64), n_nodes=np.zeros(n_frames, np.int32),
+             fv_node=np.full(total, -1, np.int32), fv_offset=np.full(total + n_frames, -1, np.int32), fv_index=np.full(total, -1, np.int32))
+    s = BowOut(*[a[f].ctypes.data for f, _ in BowOut._fields_])
+    return a, s
+
+
+def _bow_frames(a, bases, counts):
+    """Splits the batch arrays into per-frame dicts: word / node [n], bow_word / bow_value (mBowVec), fv_node / fv_offset / fv_index
+    (mFeatVec, the slices a tc2li_keyframe_view points at)."""
+    out = []
+    for f, (b, n) in enumerate(zip(bases, counts)):
+        nw, nn = int(a["n_words"][f]), int(a["n_nodes"][f])
+        fo = a["fv_offset"][b + f:b + f + nn + 1]
+        out.append(dict(word=a["word"][b:b + n], node=a["node"][b:b + n], bow_word=a["bow_word"][b:b + nw], bow_value=a["bow_value"][b:b + nw],
+                        fv_node=a["fv_node"][b:b + nn], fv_offset=fo, fv_index=a["fv_index"][b:b + int(fo[-1])]))
+    return out
+
+
+class Vocabulary:
+    """``ORBVocabulary`` (DBoW2 TemplatedVocabulary<FORB>): ``load_text`` / ``from_arrays`` build it on the host (no GPU needed),
+    ``transform`` / ``transform_orb`` are ``ComputeBoW`` on the device."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def load_text(cls, path):
+        h = C.c_void_p()
+        f = lib().tc2li_vocabulary_load_text
+        f.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+        _check(f(os.fsencode(path), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_arrays(cls, k, L, scoring, weighting, parent, is_leaf, descriptors, weights):
+        """Nodes 1 .. n in file order (the root has no entry)."""
+        p = np.ascontiguousarray(parent, np.int32); lf = np.ascontiguousarray(is_leaf, np.int32)
+        d = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32); w = np.ascontiguousarray(weights, np.float64)
+        h = C.c_void_p()
+        f = lib().tc2li_vocabulary_create
+        f.argtypes = [C.c_int] * 5 + [C.c_void_p] * 4 + [C.POINTER(C.c_void_p)]
+        _check(f(k, L, scoring, weighting, len(p), p.ctypes.data, lf.ctypes.data, d.ctypes.data, w.ctypes.data, C.byref(h)))
+        return cls(h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            f = lib().tc2li_vocabulary_destroy
+            f.argtypes = [C.c_void_p]
+            f.restype = None
+            f(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{k, L, scoring, weighting, nodes, words}"""
+        out = (C.c_int32 * 6)()
+        f = lib().tc2li_vocabulary_info
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        _check(f(self._h, out))
+        return dict(zip(("k", "L", "scoring", "weighting", "nodes", "words"), [int(v) for v in out]))
+
+    def nodes(self):
+        """(parent, word_id, descriptors [n, 32], weight) per node, root first."""
+        n = self.info()["nodes"]
+        p, wid, d, w = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, 32), np.uint8), np.zeros(n)
+        f = lib().tc2li_vocabulary_nodes
+        f.argtypes = [C.c_void_p] * 5
+        _check(f(self._h, p.ctypes.data, wid.ctypes.data, d.ctypes.data, w.ctypes.data))
+        return p, wid, d, w
+
+    def transform(self, descriptors_per_frame, levelsup=4, stream=0):
+        """``TemplatedVocabulary::transform`` of every frame's host descriptors -> list of per-frame dicts (see ``_bow_frames``)."""
+        ds = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in descriptors_per_frame]
+        offs = np.concatenate([[0], np.cumsum([len(d) for d in ds])]).astype(np.int32)
+        alld = np.ascontiguousarray(np.concatenate(ds) if ds else np.zeros((0, 32), np.uint8))
+        a, s = _bow_arrays(max(int(offs[-1]), 1), len(ds))
+        f = lib().tc2li_vocabulary_transform_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _check(f(self._h, len(ds), alld.ctypes.data, offs.ctypes.data, int(levelsup), C.byref(s), C.c_void_p(stream)))
+        return _bow_frames(a, offs[:-1], np.diff(offs))
+
+    def transform_orb(self, ext, n_keypoints, capacity=None, levelsup=4, stream=0, raw=False):
+        """``ComputeBoW`` of frames 0 .. len(n_keypoints) - 1 of the extractor's last ``extract_batch_dev`` call (image 2f, with
+        n_keypoints[f] keypoints: the counts that call returned for the even images), on the device-resident descriptors -> list of
+        per-frame dicts, or with raw=True the batch arrays (slots at f * capacity)."""
+        n_frames = len(n_keypoints)
+        capacity = ext.capacity if capacity is None else capacity
+        a, s = _bow_arrays(max(n_frames * capacity, 1), n_frames)
+        f = lib().tc2li_orb_compute_bow_batch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _check(f(ext._h, self._h, n_frames, int(levelsup), capacity, C.byref(s), C.c_void_p(stream)))
+        if raw:
+            return a
+        return _bow_frames(a, [i * capacity for i in range(n_frames)], [int(n) for n in n_keypoints])
+
+
+def search_by_bow_batch(pairs, capacity=None, stream=0):
+    """``ORBmatcher::SearchByBoW(KeyFrame*, Frame&)`` for a list of pairs; each pair is a dict with ``keyframe`` and ``frame`` (dicts as
+    ``pack_keyframe_views`` takes: keys, descriptors, has_point (keyframe), fv_node / fv_offset / fv_index), ``nn_ratio`` and
+    ``check_orientation`` -> (kf_keypoint_of_keypoint [n_pairs, capacity], n_matches [n_pairs])."""
+    views, keep = [], []
+    for p in pairs:
+        for side in ("keyframe", "frame"):
+            it = dict(p[side])
+            n = len(it["keys"])
+            it.setdefault("u_right", np.full(n, -1, np.float32)); it.setdefault("depth", np.full(n, -1, np.float32))
+            it.setdefault("has_point", np.zeros(n, np.uint8)); it.setdefault("pose7", [0, 0, 0, 1, 0, 0, 0])
+            views.append(it)
+    arr, keep = pack_keyframe_views(views)
+    if capacity is None:
+        capacity = max([len(p["frame"]["keys"]) for p in pairs] + [1])
+    bp = (BowPair * max(len(pairs), 1))()
+    for i, p in enumerate(pairs):
+        bp[i].keyframe, bp[i].frame = arr[2 * i], arr[2 * i + 1]
+        bp[i].nn_ratio, bp[i].check_orientation = float(p.get("nn_ratio", 0.7)), int(bool(p.get("check_orientation", True)))
+    match = np.full((max(len(pairs), 1), capacity), -1, np.int32)
+    nm = np.zeros(max(len(pairs), 1), np.int32)
+    f = lib().tc2li_search_by_bow_batch
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(f(C.addressof(bp), len(pairs), capacity, match.ctypes.data, nm.ctypes.data, C.c_void_p(stream)))
+    del keep
+    return match[:len(pairs)], nm[:len(pairs)]
+
+
+class ReferenceKeyframe(C.Structure):
+    """tc2li_reference_keyframe"""
+    _fields_ = [("kf", KeyframeView), ("Xw", C.c_void_p), ("observed", C.c_void_p), ("last_pose7", C.c_float * 7), ("pad_", C.c_float)]
+
+
+def track_reference_keyframe_batch(ext, voc, keypoints, u_right, refs, cam5, stream=0, with_bow=False):
+    """``Tracking::TrackReferenceKeyFrame`` data path for the frames of the preceding ``extract_batch_dev`` / ``stereo_match_batch`` calls.
+    refs: one dict per frame with the reference keyframe (keys, descriptors, has_point, fv_node / fv_offset / fv_index as
+    ``pack_keyframe_views`` takes them), Xw [n, 3], observed [n] and last_pose7 -> (poses7 [F, 7], kf_keypoint_of_keypoint [F, capacity],
+    n_matches, n_inliers, n_matches_map[, bow arrays])."""
+    keypoints = np.ascontiguousarray(keypoints, KEYPOINT_DTYPE)
+    u_right = np.ascontiguousarray(u_right, np.float32)
+    cam5 = np.ascontiguousarray(cam5, np.float64)
+    F, cap = len(refs), keypoints.shape[1]
+    views = []
+    for r in refs:
+        it = dict(r)
+        n = len(it["keys"])
+        it.setdefault("u_right", np.full(n, -1, np.float32)); it.setdefault("depth", np.full(n, -1, np.float32))
+        it.setdefault("pose7", [0, 0, 0, 1, 0, 0, 0])
+        views.append(it)
+    arr, keep = pack_keyframe_views(views)
+    rk = (ReferenceKeyframe * max(F, 1))()
+    for i, r in enumerate(refs):
+        xw = np.ascontiguousarray(r["Xw"], np.float32).reshape(-1, 3)
+        ob = np.ascontiguousarray(r["observed"], np.uint8)
+        keep.append((xw, ob))
+        rk[i].kf = arr[i]
+        rk[i].Xw, rk[i].observed = xw.ctypes.data, ob.ctypes.data
+        rk[i].last_pose7 = (C.c_float * 7)(*[float(x) for x in r["last_pose7"]])
+    poses, mp = np.zeros((max(F, 1), 7)), np.full((max(F, 1), cap), -1, np.int32)
+    nm, inl, nmap = np.zeros(max(F, 1), np.int32), np.zeros(max(F, 1), np.int32), np.zeros(max(F, 1), np.int32)
+    bow_arrays, bow_s = _bow_arrays(max(F * cap, 1), max(F, 1)) if with_bow else (None, None)
+    f = lib().tc2li_track_reference_keyframe_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 9
+    _check(f(ext._h, voc._h, F, keypoints.ctypes.data, u_right.ctypes.data, cap, C.addressof(rk), cam5.ctypes.data, poses.ctypes.data,
+             mp.ctypes.data, nm.ctypes.data, inl.ctypes.data, nmap.ctypes.data, C.byref(bow_s) if with_bow else None, C.c_void_p(stream)))
+    del keep
+    out = (poses[:F], mp[:F], nm[:F], inl[:F], nmap[:F])
+    return out + (bow_arrays,) if with_bow else out

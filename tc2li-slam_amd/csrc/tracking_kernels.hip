@@ -11,6 +11,7 @@
 #pragma clang fp contract(off)
 #include <stdint.h>
 
+#include "rot_hist.hpp"
 #include "tracking_device.hpp"
 
 namespace tc2li {
@@ -221,45 +222,24 @@ __global__ __launch_bounds__(256) void k_track_count(const TrackFrameDev* __rest
     if (tid < 30) s_count[tid] = 0;
     if (tid == 0) s_nm = 0;
     __syncthreads();
-    const float factor = 1.0f / 30;
     int nm = 0;
     for (int q = tid; q < F.n_q; q += 256) {
         int m = match[F.q_off + q];
         if (F.n_keys == 0) { m = -1; match[F.q_off + q] = -1; }
         if (m < 0) continue;
         ++nm;
-        if (check_orientation) {
-            float rot = queries[F.q_off + q].angle - key_angles[F.key_off + m];
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == 30) bin = 0;
-            atomicAdd(&s_count[bin], 1);
-        }
+        if (check_orientation) atomicAdd(&s_count[rot_hist_bin(queries[F.q_off + q].angle, key_angles[F.key_off + m])], 1);
     }
     atomicAdd(&s_nm, nm);
     __syncthreads();
     if (!check_orientation) { if (tid == 0) n_matches[f] = s_nm; return; }
-    if (tid == 0) {  // ORBmatcher::ComputeThreeMaxima
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < 30; i++) {
-            const int s = s_count[i];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-            else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-        s_ind[0] = ind1; s_ind[1] = ind2; s_ind[2] = ind3;
-    }
+    if (tid == 0) rot_hist_three_maxima(s_count, s_ind);  // ORBmatcher::ComputeThreeMaxima
     __syncthreads();
     int removed = 0;
     for (int q = tid; q < F.n_q; q += 256) {
         const int m = match[F.q_off + q];
         if (m < 0) continue;
-        float rot = queries[F.q_off + q].angle - key_angles[F.key_off + m];
-        if (rot < 0.0) rot += 360.0f;
-        int bin = (int)roundf(rot * factor);
-        if (bin == 30) bin = 0;
+        const int bin = rot_hist_bin(queries[F.q_off + q].angle, key_angles[F.key_off + m]);
         if (bin != s_ind[0] && bin != s_ind[1] && bin != s_ind[2]) { match[F.q_off + q] = -1; ++removed; }
     }
     atomicSub(&s_nm, removed);

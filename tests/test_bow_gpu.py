@@ -1,0 +1,272 @@
+"""GPU parity of the ORB vocabulary: ComputeBoW (tc2li_orb_compute_bow_batch on the device-resident features, and the host-descriptor
+entry) and SearchByBoW(KeyFrame*, Frame&) against the line-by-line restatement tests/bow_ref.py, byte for byte."""
+import numpy as np
+import pytest
+
+import bow_ref as R
+
+pytestmark = pytest.mark.gpu
+
+W, H = 640, 240
+
+
+def _drive(pkg, synthetic, xs, seed=5, nfeatures=1000):
+    """Left / right images of one scene seen from camera positions xs along the baseline axis, extracted on the device."""
+    import torch
+    sc = synthetic.Scene(seed)
+    imgs = []
+    for k, x in enumerate(xs):
+        imgs.append(sc.render(float(x), W, H, noise_seed=2 * k + 1)[0])
+        imgs.append(sc.render(float(x) + synthetic.BASELINE, W, H, noise_seed=2 * k + 2)[0])
+    dev = torch.from_numpy(np.stack(imgs)).cuda()
+    ext = pkg.OrbExtractor(nfeatures=nfeatures, max_width=W, max_height=H, max_images=len(imgs))
+    kps, desc, counts, _ = ext.extract_batch_dev(dev.data_ptr(), len(imgs), W, H, W, W * H)
+    torch.cuda.synchronize()
+    frames = [dict(keys=kps[2 * f][:counts[2 * f]].copy(), descriptors=desc[2 * f][:counts[2 * f]].copy()) for f in range(len(xs))]
+    return ext, dev, frames, counts[0::2].copy()
+
+
+@pytest.fixture(scope="module")
+def drive(pkg, synthetic):
+    return _drive(pkg, synthetic, [0.0, 0.15, 0.3, 0.6])
+
+
+@pytest.fixture(scope="module")
+def full_voc(pkg):
+    p, lf, d, w = R.random_tree(10, 6, seed=11)
+    ref = R.Voc(10, 6, R.L1_NORM, R.TF_IDF, p, lf, d, w)
+    return ref, pkg.Vocabulary.from_arrays(10, 6, R.L1_NORM, R.TF_IDF, p, lf, d, w)
+
+
+@pytest.fixture(scope="module")
+def trained(drive):
+    descs = np.concatenate([f["descriptors"] for f in drive[2][:2]])
+    return R.trained_tree(descs, k=5, L=3, seed=2)
+
+
+def _same(got, want, what=""):
+    for key in ("word", "node", "bow_word", "fv_node", "fv_offset", "fv_index"):
+        assert np.array_equal(got[key], want[key]), (what, key)
+    assert got["bow_value"].dtype == np.float64
+    assert got["bow_value"].tobytes() == want["bow_value"].tobytes(), what
+
+
+def test_compute_bow_full_vocabulary(pkg, drive, full_voc):
+    ext, _, frames, counts = drive
+    ref, h = full_voc
+    assert h.info() == dict(k=10, L=6, scoring=0, weighting=0, nodes=1111111, words=10 ** 6)
+    got = h.transform_orb(ext, counts, levelsup=4)
+    for f, fr in enumerate(frames):
+        assert len(fr["descriptors"]) > 300
+        _same(got[f], R.transform(ref, fr["descriptors"], 4), "frame %d" % f)
+    # levelsup 0 .. L on one frame (nid_level from L down to the root)
+    d0 = frames[0]["descriptors"][:200]
+    for lu in range(0, 7):
+        _same(h.transform([d0], levelsup=lu)[0], R.transform(ref, d0, lu), "levelsup %d" % lu)
+
+
+def test_host_entry_equals_device_entry_and_repeats(pkg, drive, full_voc):
+    ext, _, frames, counts = drive
+    _, h = full_voc
+    a = h.transform_orb(ext, counts, levelsup=4, raw=True)
+    b = h.transform_orb(ext, counts, levelsup=4, raw=True)
+    for k in a:
+        assert a[k].tobytes() == b[k].tobytes(), k
+    dev = h.transform_orb(ext, counts, levelsup=4)
+    host = h.transform([fr["descriptors"] for fr in frames], levelsup=4)
+    for f in range(len(frames)):
+        for k in dev[f]:
+            assert dev[f][k].tobytes() == host[f][k].tobytes(), (f, k)
+
+
+@pytest.mark.parametrize("scoring", range(6))
+@pytest.mark.parametrize("weighting", range(4))
+def test_trained_vocabulary_from_text(pkg, tmp_path, drive, trained, scoring, weighting):
+    _, _, frames, _ = drive
+    p, lf, d, w = trained
+    ref = R.Voc(5, 3, scoring, weighting, p, lf, d, w)
+    path = tmp_path / "voc.txt"
+    R.write_text(path, ref)
+    ref.weight = np.array([R.read_weight_6(x) for x in ref.weight])   # what the file holds
+    h = pkg.Vocabulary.load_text(str(path))
+    descs = [frames[2]["descriptors"], np.zeros((0, 32), np.uint8), frames[3]["descriptors"][:300]]   # a frame without keypoints
+    got = h.transform(descs, levelsup=1)
+    for f, dd in enumerate(descs):
+        _same(got[f], R.transform(ref, dd, 1), "frame %d" % f)
+    assert len(got[1]["fv_offset"]) == 1 and got[1]["fv_offset"][0] == 0 and len(got[1]["bow_word"]) == 0
+
+
+def test_k20_vocabulary(pkg, drive):
+    _, _, frames, _ = drive
+    p, lf, d, w = R.random_tree(20, 3, seed=4, flips=30, stop_frac=0.1)
+    ref = R.Voc(20, 3, R.L2_NORM, R.TF, p, lf, d, w)
+    h = pkg.Vocabulary.from_arrays(20, 3, R.L2_NORM, R.TF, p, lf, d, w)
+    descs = [frames[1]["descriptors"][:400]]
+    for lu in (0, 1, 2):
+        _same(h.transform(descs, levelsup=lu)[0], R.transform(ref, descs[0], lu), "levelsup %d" % lu)
+
+
+def _view(fr, bow, has_point=None):
+    v = dict(keys=fr["keys"], descriptors=fr["descriptors"], fv_node=bow["fv_node"], fv_offset=bow["fv_offset"], fv_index=bow["fv_index"])
+    if has_point is not None:
+        v["has_point"] = has_point
+    return v
+
+
+def _ref_view(fr, bow, has_point=None):
+    return dict(angle=fr["keys"]["angle"], descriptors=fr["descriptors"], fv_node=bow["fv_node"], fv_offset=bow["fv_offset"],
+                fv_index=bow["fv_index"], has_point=has_point)
+
+
+def test_search_by_bow_batch(pkg, drive, trained):
+    ext, _, frames, counts = drive
+    p, lf, d, w = trained
+    h = pkg.Vocabulary.from_arrays(5, 3, R.L1_NORM, R.TF_IDF, p, lf, d, w)
+    bows = h.transform_orb(ext, counts, levelsup=1)
+    rng = np.random.default_rng(3)
+    pairs, refs = [], []
+    for kf in range(len(frames)):
+        for f in range(len(frames)):
+            if kf == f:
+                continue
+            n = len(frames[kf]["keys"])
+            hp = (rng.random(n) > (0.0 if (kf + f) % 2 else 0.3)).astype(np.uint8)   # keyframes with missing / bad points
+            ratio, orient = (0.7, True) if (kf + 2 * f) % 4 < 2 else (0.75, bool((kf + f) % 2))
+            pairs.append(dict(keyframe=_view(frames[kf], bows[kf], hp), frame=_view(frames[f], bows[f]), nn_ratio=ratio, check_orientation=orient))
+            refs.append(R.search_by_bow(_ref_view(frames[kf], bows[kf], hp), _ref_view(frames[f], bows[f]), ratio, orient))
+    match, nm = pkg.search_by_bow_batch(pairs, capacity=ext.capacity)
+    total = 0
+    for i, (m, n) in enumerate(refs):
+        N = len(m)
+        assert np.array_equal(match[i][:N], m), i
+        assert (match[i][N:] == -1).all()
+        assert nm[i] == n, (i, nm[i], n)
+        total += n
+    assert total > 100
+    assert any(p["check_orientation"] for p in pairs) and any(not p["check_orientation"] for p in pairs)
+
+
+def test_host_entry_frame_beyond_one_tile(pkg, drive, full_voc):
+    """More than 1024 descriptors (the LDS tile of the per-frame assembly) and more than 1024 distinct words in one frame."""
+    _, _, frames, _ = drive
+    ref, h = full_voc
+    rows = np.random.default_rng(9).integers(0, 256, (2500, 32), dtype=np.uint8)
+    descs = [frames[0]["descriptors"], rows, frames[1]["descriptors"][:5]]
+    got = h.transform(descs, levelsup=4)
+    for f, dd in enumerate(descs):
+        want = R.transform(ref, dd, 4)
+        _same(got[f], want, "frame %d" % f)
+    assert len(got[1]["bow_word"]) > 1024
+    for scoring, weighting in ((R.L2_NORM, R.TF), (R.DOT_PRODUCT, R.TF_IDF)):
+        p, lf, d, w = R.random_tree(4, 6, seed=6, flips=25, stop_frac=0.05)
+        r2 = R.Voc(4, 6, scoring, weighting, p, lf, d, w)
+        h2 = pkg.Vocabulary.from_arrays(4, 6, scoring, weighting, p, lf, d, w)
+        _same(h2.transform([rows], levelsup=2)[0], R.transform(r2, rows, 2), "scoring %d" % scoring)
+
+
+def test_slices_feed_search_for_triangulation(pkg, oracle, synthetic):
+    """A transform's FeatureVector slices, handed to tc2li_keyframe_view as they are, give SearchForTriangulation the oracle's matches."""
+    import test_mapping as M
+    kfs = M.make_keyframes(synthetic, M.oracle_features(oracle, synthetic), None, 2)
+    p, lf, d, w = R.trained_tree(np.concatenate([k["descriptors"] for k in kfs]), k=6, L=4, seed=1)
+    h = pkg.Vocabulary.from_arrays(6, 4, R.L1_NORM, R.TF_IDF, p, lf, d, w)
+    raw = h.transform([k["descriptors"] for k in kfs], levelsup=2)
+    for k, b in zip(kfs, raw):
+        k["fv_node"], k["fv_offset"], k["fv_index"] = b["fv_node"], b["fv_offset"], b["fv_index"]
+    cam4, mbf, _ = M.cam_of(synthetic)
+    cam5 = np.float32([cam4[0], cam4[1], cam4[2], cam4[3], mbf]).astype(np.float64)
+    sf, sg = M.tables()
+    for kw in (dict(), dict(check_orientation=True)):
+        want = oracle.search_for_triangulation(kfs[0], kfs[1], cam4, sf, sg, **kw)
+        got = pkg.capi.search_for_triangulation(kfs[0], kfs[1], cam5, sf, sg, **kw)
+        assert got[0] == want[0] and np.array_equal(got[1], want[1]), kw
+        assert want[0] > 20
+
+
+def test_search_by_bow_rejects_malformed_feature_vectors(pkg, drive, trained):
+    ext, _, frames, counts = drive
+    p, lf, d, w = trained
+    h = pkg.Vocabulary.from_arrays(5, 3, R.L1_NORM, R.TF_IDF, p, lf, d, w)
+    b = h.transform_orb(ext, counts[:2], levelsup=1)
+    good = _view(frames[1], b[1])
+    for bad_field in ("offset", "node"):
+        bb = dict(b[0])
+        if bad_field == "offset":  # up and down, with a sane last entry
+            off = bb["fv_offset"].copy(); off[1], off[2] = off[2], off[1]; bb["fv_offset"] = off
+        else:
+            nodes = bb["fv_node"].copy(); nodes[0], nodes[1] = nodes[1], nodes[0]; bb["fv_node"] = nodes
+        kf = _view(frames[0], bb, np.ones(len(frames[0]["keys"]), np.uint8))
+        with pytest.raises(pkg.Tc2liError) as e:
+            pkg.search_by_bow_batch([dict(keyframe=kf, frame=good, nn_ratio=0.7, check_orientation=True)], capacity=ext.capacity)
+        assert e.value.code == -2
+
+
+def test_track_reference_keyframe_batch(pkg, oracle, synthetic):
+    """The batch against 'restatement ComputeBoW -> SearchByBoW(0.7, true) -> oracle.pose_optimization -> discard', frames above and below
+    15 matches in one batch."""
+    import torch
+    xs = [0.0, 0.2, 0.4, 0.6]
+    bf = np.float32(synthetic.BF); b = np.float32(bf / np.float32(synthetic.FX))
+    fx, fy, cx, cy = [np.float32(v) for v in (synthetic.FX, synthetic.FY, synthetic.CX, synthetic.CY)]
+    # reference keyframes: 0.1 m behind every frame, own extractor, depth from the stereo match
+    ext_kf, dev_kf, kfs, kcounts = _drive(pkg, synthetic, [x - 0.1 for x in xs], seed=8)
+    _, kdepth, _ = pkg.stereo_match_batch(ext_kf, len(xs), float(bf), float(b))
+    ext, dev, frames, counts = _drive(pkg, synthetic, xs, seed=8)
+    keypoints = np.zeros((2 * len(xs), ext.capacity), pkg.capi.KEYPOINT_DTYPE)
+    for f, fr in enumerate(frames):
+        keypoints[2 * f, :len(fr["keys"])] = fr["keys"]
+    u_right, _, _ = pkg.stereo_match_batch(ext, len(xs), float(bf), float(b))
+    p, lf, d, w = R.trained_tree(np.concatenate([k["descriptors"] for k in kfs[:2]]), k=6, L=6, seed=3)
+    voc_ref = R.Voc(6, 6, R.L1_NORM, R.TF_IDF, p, lf, d, w)
+    h = pkg.Vocabulary.from_arrays(6, 6, R.L1_NORM, R.TF_IDF, p, lf, d, w)
+    kbows = h.transform([k["descriptors"] for k in kfs], levelsup=4)
+    rng = np.random.default_rng(4)
+    refs = []
+    for f, kf in enumerate(kfs):
+        n = len(kf["keys"])
+        z = kdepth[f, :n]
+        hp = ((z > 0) & (rng.random(n) < 0.85)).astype(np.uint8)
+        if f == 2:  # too few points: the search finds fewer than 15 matches
+            hp[np.flatnonzero(hp)[10:]] = 0
+        zz = np.where(z > 0, z, 1).astype(np.float32)
+        Xw = np.stack([(kf["keys"]["x"] - cx) * zz / fx, (kf["keys"]["y"] - cy) * zz / fy, zz], 1).astype(np.float32)
+        Xw[:, 0] += np.float32(xs[f] - 0.1)   # world = the first keyframe's camera frame, cameras along x
+        last = np.array([0, 0, 0, 1, -xs[f] + 0.01, 0.004, -0.008], np.float32)
+        refs.append(dict(keys=kf["keys"], descriptors=kf["descriptors"], has_point=hp, fv_node=kbows[f]["fv_node"],
+                         fv_offset=kbows[f]["fv_offset"], fv_index=kbows[f]["fv_index"], Xw=Xw,
+                         observed=(rng.random(n) < 0.9).astype(np.uint8), last_pose7=last))
+    cam5 = np.float32([fx, fy, cx, cy, bf]).astype(np.float64)
+    poses, mp, nm, inl, nmap, braw = pkg.capi.track_reference_keyframe_batch(ext, h, keypoints, u_right, refs, cam5, with_bow=True)
+    inv_sigma2 = ext.GetInverseScaleSigmaSquares()
+    cap = ext.capacity
+    results = []
+    for f, fr in enumerate(frames):
+        n = len(fr["keys"])
+        fb = R.transform(voc_ref, fr["descriptors"], 4)
+        assert np.array_equal(braw["fv_node"][f * cap:f * cap + braw["n_nodes"][f]], fb["fv_node"])
+        assert braw["bow_value"][f * cap:f * cap + braw["n_words"][f]].tobytes() == fb["bow_value"].tobytes()
+        r = refs[f]
+        m, nmatch = R.search_by_bow(dict(angle=r["keys"]["angle"], descriptors=r["descriptors"], has_point=r["has_point"], fv_node=r["fv_node"],
+                                         fv_offset=r["fv_offset"], fv_index=r["fv_index"]),
+                                    dict(angle=fr["keys"]["angle"], descriptors=fr["descriptors"], **{k: fb[k] for k in ("fv_node", "fv_offset", "fv_index")}),
+                                    0.7, True)
+        assert nm[f] == nmatch, (f, nm[f], nmatch)
+        assert np.all(mp[f, n:] == -1)
+        if nmatch < 15:
+            assert inl[f] == -1 and nmap[f] == 0 and np.all(mp[f] == -1)
+            assert np.array_equal(poses[f], r["last_pose7"].astype(np.float64))
+            results.append(None)
+            continue
+        ids = np.flatnonzero(m >= 0)
+        edges6 = np.array([[e, 0, fr["keys"]["x"][i], fr["keys"]["y"][i], u_right[f, i], inv_sigma2[fr["keys"]["octave"][i]]]
+                           for e, i in enumerate(ids)], np.float64)
+        Xe = r["Xw"][m[ids]].astype(np.float64)
+        pose, outl, ninl, _ = oracle.pose_optimization(r["last_pose7"].astype(np.float64), Xe, edges6, cam5)
+        want = m.copy()
+        want[ids[outl.astype(bool)]] = -1
+        assert np.array_equal(mp[f, :n], want), f
+        assert inl[f] == ninl
+        assert nmap[f] == int(sum(r["observed"][want[i]] for i in np.flatnonzero(want >= 0)))
+        assert np.allclose(poses[f], pose, rtol=1e-4, atol=1e-6), (poses[f], pose)
+        results.append(ninl)
+    assert results[2] is None and sum(x is not None and x > 50 for x in results) >= 2, (nm, inl)
