@@ -1138,6 +1138,176 @@ int tc2li_track_reference_keyframe_batch(tc2li_orb* orb, tc2li_vocabulary* voc, 
                                          double* poses7, int32_t* kf_keypoint_of_keypoint, int32_t* n_matches, int32_t* n_inliers,
                                          int32_t* n_matches_map, const tc2li_bow_out* bow, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Relocalisation -- the keyframe database and DetectRelocalizationCandidates, the stage of Tracking::Relocalization
+ * (SF/src/Tracking.cc:3478-3646) between the frame's ComputeBoW (tc2li_orb_compute_bow_batch) and SearchByBoW
+ * (tc2li_search_by_bow_batch with nn_ratio 0.75).  MLPnPsolver stays the reference's host code.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* One BowVector: n entries, word ids strictly ascending (std::map order), their values. */
+typedef struct tc2li_bow_vector {
+    const int32_t* word;
+    const double* value;
+    int32_t n;
+    int32_t pad_;
+} tc2li_bow_vector;
+
+/* TemplatedVocabulary::score(v1, v2) (TemplatedVocabulary.h:1274-1280 -> SF/Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-311) for n_pairs
+ * pairs, scores[p] = score(v1[p], v2[p]) in double, with the scoring type of the vocabulary (tc2li_vocabulary_info).  Bit for bit the
+ * reference for L1_NORM, L2_NORM, CHI_SQUARE, BHATTACHARYYA and DOT_PRODUCT: the terms of the common words are added one at a time in
+ * ascending word order into a double that starts at 0 (vi is v1's value, wi is v2's), then the closing step of the type (-score / 2;
+ * score >= 1 ? 1 : 1 - sqrt(1 - score); 2 * score; none; none).  CHI_SQUARE skips a word with vi + wi == 0.  Two vectors without a common
+ * word score what the closing step makes of 0 (L1_NORM: -0.0).  KL is rejected with TC2LI_ERR_INVALID: it calls log(), whose device
+ * result is not the host library's to the last bit.  Word ids not strictly ascending or outside the vocabulary: TC2LI_ERR_INVALID; more
+ * than 4096 words in a vector: TC2LI_ERR_CAPACITY.  Returns n_pairs. */
+int tc2li_vocabulary_score_batch(tc2li_vocabulary* voc, int n_pairs, const tc2li_bow_vector* v1, const tc2li_bow_vector* v2, double* scores,
+                                 void* stream);
+
+/* KeyFrameDatabase (SF/src/KeyFrameDatabase.cc:40-107), bound to one vocabulary (the constructor's argument, :41-45), which must outlive
+ * it.  Host logic that works without a GPU; the device copy is brought up to date by the first query after a change.  Instead of the
+ * reference's inverted file (a std::list<KeyFrame*> per word) the handle keeps the keyframes' BowVectors as rows of one pool, with a
+ * sequence number per tc2li_keyframe_db_add call: every word's list is in the order of the add calls, so the order in which a query
+ * meets the keyframes (lKFsSharingWords) is the order by (smallest word shared with the frame, sequence number).  Calls on one handle
+ * are serialised by a mutex (mMutex).  At most 4096 live keyframes and 4096 words per keyframe (TC2LI_ERR_CAPACITY). */
+typedef struct tc2li_keyframe_db tc2li_keyframe_db;
+int tc2li_keyframe_db_create(const tc2li_vocabulary* voc, tc2li_keyframe_db** out);
+void tc2li_keyframe_db_destroy(tc2li_keyframe_db* db);
+/* KeyFrameDatabase::add (:48-54): kf_id is the keyframe's mnId (>= 0, unique among the live entries: a live duplicate is TC2LI_ERR_INVALID,
+ * as are word ids not strictly ascending or outside the vocabulary), map_id its GetMap(), the BowVector its mBowVec.  The entry takes the
+ * handle's next sequence number, has no covisibility list and the score state 0.0f (the reference leaves KeyFrame::mRelocScore
+ * uninitialised, KeyFrame.h:349).  Returns the sequence number. */
+int tc2li_keyframe_db_add(tc2li_keyframe_db* db, int32_t kf_id, int32_t map_id, int n_words, const int32_t* bow_word, const double* bow_value);
+/* KeyFrameDatabase::erase (:56-75; KeyFrame::SetBadFlag calls it).  An unknown id is a no-op like the reference's loop.  Returns 1 when an
+ * entry was erased, 0 otherwise.  The dead rows leave the pool when they pass half of it. */
+int tc2li_keyframe_db_erase(tc2li_keyframe_db* db, int32_t kf_id);
+/* KeyFrameDatabase::clear (:77-81) and clearMap (:83-107): every entry / every entry of map_id.  Returns the number of entries erased. */
+int tc2li_keyframe_db_clear(tc2li_keyframe_db* db);
+int tc2li_keyframe_db_clear_map(tc2li_keyframe_db* db, int32_t map_id);
+/* Live entries. */
+int tc2li_keyframe_db_size(const tc2li_keyframe_db* db);
+/* pKF->GetBestCovisibilityKeyFrames(10) of entry kf_id as the caller's graph has it now (KeyFrameDatabase.cc:808): n <= 10 ids in the
+ * reference's order, replacing the entry's list.  Ids that are not live entries when a query runs are skipped by it, as a neighbour that
+ * shares no word with the frame is (:816).  TC2LI_ERR_INVALID for n > 10 or an unknown kf_id.  Returns n. */
+int tc2li_keyframe_db_set_covisibility(tc2li_keyframe_db* db, int32_t kf_id, int n, const int32_t* neighbour_ids);
+/* Host readback of the live entries in sequence order (arrays [capacity], NULL skips one): kf_id, map_id, sequence number and the score
+ * state (mRelocScore: what the last query that scored the entry left).  Returns the number of live entries; TC2LI_ERR_CAPACITY when
+ * capacity is smaller. */
+int tc2li_keyframe_db_entries(const tc2li_keyframe_db* db, int capacity, int32_t* kf_id, int32_t* map_id, int32_t* sequence, float* score);
+
+/* One query of DetectRelocalizationCandidates: the database, pMap as its map_id, and F->mBowVec as tc2li_bow_out gives it. */
+typedef struct tc2li_reloc_query {
+    tc2li_keyframe_db* db;
+    int32_t map_id;
+    int32_t n_words;
+    const int32_t* bow_word;
+    const double* bow_value;
+} tc2li_reloc_query;
+/* Optional output: the scored list of every query in lScoreAndMatch order (KeyFrameDatabase.cc:780-830), arrays [n_queries][capacity]:
+ * the keyframe, mnRelocWords, si, accScore and pBestKF of every entry; n_scored [n_queries]. */
+typedef struct tc2li_reloc_scored {
+    int32_t capacity;
+    int32_t pad_;
+    int32_t* n_scored;
+    int32_t* kf_id;
+    int32_t* words;
+    float* si;
+    float* acc_score;
+    int32_t* best_kf_id;
+} tc2li_reloc_scored;
+/* KeyFrameDatabase::DetectRelocalizationCandidates(F, pMap) (:742-854) for n_queries <= 512 queries, each against its own database (the
+ * queries of one database depend on each other through the score state: the same handle twice is TC2LI_ERR_INVALID).  Line for line:
+ * mnRelocWords = words the keyframe shares with the frame, keyframes without one take no part (:750-768); minCommonWords =
+ * (int)(maxCommonWords * 0.8f) (:778); for the keyframes with more words than that, in lKFsSharingWords order, si = (float)score(F, KF),
+ * stored as the keyframe's score state (:785-796); accScore in float over the keyframe's covisibility list in its order, a neighbour
+ * counting iff it is a live entry that shares a word with this frame, with its STORED score -- this query's si if it passed the word
+ * gate, otherwise what an earlier query left, 0.0f on a fresh entry (:805-830); kept are the entries with accScore > 0.75f * bestAccScore
+ * whose best keyframe has the query's map_id, first occurrence of each best keyframe, in list order (:833-851).
+ * Out: n_candidates [n_queries], candidates [n_queries][capacity] kf_ids, -1 beyond the count.  TC2LI_ERR_CAPACITY when a list (or a
+ * scored list) does not fit (the score states have been updated then), for a frame with more than 4096 words or more than 512 queries.
+ * The databases of one call share the scoring type of their vocabularies (TC2LI_ERR_INVALID otherwise); KL vocabularies are rejected as in
+ * tc2li_vocabulary_score_batch.  Returns n_queries. */
+int tc2li_detect_relocalization_candidates_batch(const tc2li_reloc_query* queries, int n_queries, int capacity, int32_t* n_candidates,
+                                                 int32_t* candidates, const tc2li_reloc_scored* scored, void* stream);
+
+/* One item of ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, th, ORBdist)
+ * (SF/src/ORBmatcher.cc:1898-2019; Tracking::Relocalization calls it with (10, 100) and (3, 64), SF/src/Tracking.cc:3578, 3594): the frame
+ * and the candidate keyframe's points in keypoint order (vpMPs = pKF->GetMapPointMatches()). */
+typedef struct tc2li_projection_keyframe_item {
+    int32_t n;                         /* CurrentFrame.N (at most 3072, the matcher's limit) */
+    int32_t n_points;                  /* vpMPs.size() */
+    const tc2li_keypoint* keys;        /* CurrentFrame.mvKeysUn */
+    const uint8_t* descriptors;        /* CurrentFrame.mDescriptors, [n][32] */
+    const uint8_t* held;               /* [n] CurrentFrame.mvpMapPoints[i] != NULL: any held point blocks the keypoint (:1961) */
+    float pose7[7];                    /* CurrentFrame.GetPose(): qx qy qz qw tx ty tz of Tcw */
+    float bounds[4];                   /* mnMinX, mnMaxX, mnMinY, mnMaxY */
+    float pad_;
+    const uint8_t* has_point;          /* [n_points] pMP && !pMP->isBad() */
+    const uint8_t* found;              /* [n_points] sAlreadyFound.count(pMP) */
+    const float* Xw;                   /* [n_points][3] pMP->GetWorldPos() */
+    const uint8_t* point_descriptors;  /* [n_points][32] pMP->GetDescriptor() -- the map point's, not the keyframe keypoint's */
+    const float* min_distance;         /* [n_points] GetMinDistanceInvariance() */
+    const float* max_distance;         /* [n_points] GetMaxDistanceInvariance() */
+    const float* max_distance_raw;     /* [n_points] mfMaxDistance (MapPoint::PredictScale) */
+    const float* angle;                /* [n_points] pKF->mvKeysUn[i].angle */
+} tc2li_projection_keyframe_item;
+/* The overload for a batch of items with one (th, ORBdist, mbCheckOrientation).  Per keyframe keypoint in order, for a point that is
+ * there, not bad and not in sAlreadyFound: projection with the frame's pose (no depth-sign and no viewing-cosine test), the image
+ * bounds, dist3D = |Xw - Ow| with Ow = Tcw.inverse().translation() inside [min_distance, max_distance], PredictScale(dist3D,
+ * &CurrentFrame) with log_scale_factor = mfLogScaleFactor and n_levels, the window th * scale_factors[level] over the levels level - 1 ..
+ * level + 1 (handed to GetFeaturesInArea unclamped), among the keypoints that hold no point the one of least descriptor distance (from
+ * 256, strict <, first wins), accepted when bestDist <= orb_dist; a matched keypoint blocks later points.  With check_orientation the
+ * rotation histogram (bin = round(rot * (1.0f / 30)), 30 -> 0) and ComputeThreeMaxima remove the matches outside the three maxima.
+ * Out: kf_keypoint_of_keypoint [n_items][capacity] = the keyframe keypoint whose point the frame keypoint received, -1 elsewhere (held
+ * keypoints included), n_matches [n_items] after the removals.  Returns n_items. */
+int tc2li_search_by_projection_keyframe_batch(const tc2li_projection_keyframe_item* items, int n_items, const float* cam4,
+                                              const float* scale_factors, int n_levels, float log_scale_factor, float th, int orb_dist,
+                                              int check_orientation, int capacity, int32_t* kf_keypoint_of_keypoint, int32_t* n_matches,
+                                              void* stream);
+
+/* One hypothesis of the refinement ladder: a frame, a candidate keyframe, the pose MLPnPsolver::iterate returned for the pair and its
+ * inliers among SearchByBoW's matches. */
+typedef struct tc2li_reloc_hypothesis {
+    int32_t frame_index;               /* the frame is image 2 * frame_index of the handle's last tc2li_orb_extract_batch call */
+    int32_t n_points;                  /* keypoints of the candidate keyframe (vpCandidateKFs[i]) */
+    const uint8_t* has_point;          /* the candidate as in tc2li_projection_keyframe_item */
+    const float* Xw;
+    const uint8_t* point_descriptors;
+    const float* min_distance;
+    const float* max_distance;
+    const float* max_distance_raw;
+    const float* angle;
+    const int32_t* match;              /* [keypoints of the frame] the keyframe keypoint vvpMapPointMatches[i][j] names, or -1 */
+    const uint8_t* inlier;             /* [keypoints of the frame] vbInliers[j] */
+    float pose7[7];                    /* Tcw of the PnP solution: qx qy qz qw tx ty tz */
+    float pad_;
+} tc2li_reloc_hypothesis;
+enum tc2li_reloc_status {
+    TC2LI_RELOC_OPT1 = 1,              /* the first PoseOptimization ran (always) */
+    TC2LI_RELOC_REJECTED = 2,          /* nGood < 10 after it: the reference's `continue` */
+    TC2LI_RELOC_SEARCH1 = 4,           /* nGood < 50: SearchByProjection(.., 10, 100) ran */
+    TC2LI_RELOC_OPT2 = 8,              /* nadditional + nGood >= 50: the second PoseOptimization ran */
+    TC2LI_RELOC_SEARCH2 = 16,          /* 30 < nGood < 50: SearchByProjection(.., 3, 64) ran */
+    TC2LI_RELOC_OPT3 = 32,             /* nGood + nadditional >= 50: the third PoseOptimization ran */
+    TC2LI_RELOC_SUCCESS = 64           /* nGood >= 50 at the end */
+};
+/* What Tracking::Relocalization does with a PnP pose (SF/src/Tracking.cc:3562-3631), for n_hyps independent hypotheses on the device-resident
+ * features of the last tc2li_orb_extract_batch call (lapping area {0,0}; n_frames frames, u_right [n_frames][capacity] as for
+ * tc2li_track_motion_model_batch); several hypotheses may name one frame, each works on its own copy of the frame's map points.  One stream,
+ * one staging upload, every branch decided on the device:
+ *   mvpMapPoints = match where inlier, sFound = those points; PoseOptimization (the kernel of tc2li_track_motion_model_batch: one edge per
+ *   keypoint that holds a point, keypoint order, stereo when uRight >= 0); nGood < 10: rejected, the frame stays as PoseOptimization left it;
+ *   outliers discarded; if nGood < 50: ORBmatcher(0.9, true).SearchByProjection(F, pKF, sFound, 10, 100)
+ *   (tc2li_search_by_projection_keyframe_batch); if nadditional + nGood >= 50: PoseOptimization -- no discard after this one --; if then
+ *   30 < nGood < 50: sFound = every point the frame holds (flagged outliers included), SearchByProjection(.., 3, 64); if nGood +
+ *   nadditional >= 50: PoseOptimization and discard.  Success iff nGood >= 50.
+ * Out per hypothesis: status (tc2li_reloc_status bits), n_good, n_additional [2] (0 for a search that did not run), poses7 [3][7] the pose
+ * after each PoseOptimization that ran (double, rounded through float as Frame::SetPose stores it; zeros otherwise),
+ * kf_keypoint_of_keypoint [capacity] the frame's map points at the end as keyframe keypoints, outlier [capacity] mvbOutlier of the last
+ * PoseOptimization that ran.  The MapPoint flags and mnLastRelocFrameId stay with the caller.  Returns n_hyps. */
+int tc2li_relocalization_refine_batch(tc2li_orb* orb, const tc2li_reloc_hypothesis* hyps, int n_hyps, int n_frames, const float* u_right,
+                                      int capacity, const tc2li_camera* cam, int32_t* status, int32_t* n_good, int32_t* n_additional,
+                                      double* poses7, int32_t* kf_keypoint_of_keypoint, uint8_t* outlier, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

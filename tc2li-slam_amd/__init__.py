@@ -38,4 +38,8 @@ from .capi import (  # noqa: F401
     Vocabulary,
     search_by_bow_batch,
     track_reference_keyframe_batch,
+    KeyFrameDatabase,
+    detect_relocalization_candidates_batch,
+    search_by_projection_keyframe_batch,
+    relocalization_refine_batch,
 )

@@ -2059,3 +2059,244 @@ def track_reference_keyframe_batch(ext, voc, keypoints, u_right, refs, cam5, str
     del keep
     out = (poses[:F], mp[:F], nm[:F], inl[:F], nmap[:F])
     return out + (bow_arrays,) if with_bow else out
+
+
+# ---- relocalisation: TemplatedVocabulary::score, KeyFrameDatabase, DetectRelocalizationCandidates --------------------------------------
+class BowVector(C.Structure):
+    """tc2li_bow_vector"""
+    _fields_ = [("word", C.c_void_p), ("value", C.c_void_p), ("n", C.c_int32), ("pad_", C.c_int32)]
+
+
+class RelocQuery(C.Structure):
+    """tc2li_reloc_query"""
+    _fields_ = [("db", C.c_void_p), ("map_id", C.c_int32), ("n_words", C.c_int32), ("bow_word", C.c_void_p), ("bow_value", C.c_void_p)]
+
+
+class RelocScored(C.Structure):
+    """tc2li_reloc_scored"""
+    _fields_ = [("capacity", C.c_int32), ("pad_", C.c_int32)] + [(name, C.c_void_p) for name in ("n_scored", "kf_id", "words", "si", "acc_score",
+                                                                                                  "best_kf_id")]
+
+
+def _bow_pair_arrays(word, value):
+    w = np.ascontiguousarray(word, np.int32).reshape(-1)
+    v = np.ascontiguousarray(value, np.float64).reshape(-1)
+    if len(w) != len(v):
+        raise ValueError("a BowVector has as many values as words")
+    return w, v
+
+
+def _vocabulary_score(self, pairs, stream=0):
+    """``TemplatedVocabulary::score(v1, v2)`` for a list of pairs ((word1, value1), (word2, value2)) -> float64 [n_pairs]."""
+    n = len(pairs)
+    a, b, keep = (BowVector * max(n, 1))(), (BowVector * max(n, 1))(), []
+    for i, (p1, p2) in enumerate(pairs):
+        for arr, p in ((a, p1), (b, p2)):
+            w, v = _bow_pair_arrays(*p)
+            keep.append((w, v))
+            arr[i].word, arr[i].value, arr[i].n = w.ctypes.data, v.ctypes.data, len(w)
+    out = np.zeros(max(n, 1), np.float64)
+    f = lib().tc2li_vocabulary_score_batch
+    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(f(self._h, n, C.addressof(a), C.addressof(b), out.ctypes.data, C.c_void_p(stream)))
+    del keep
+    return out[:n]
+
+
+Vocabulary.score = _vocabulary_score
+
+
+class KeyFrameDatabase:
+    """``KeyFrameDatabase`` bound to one ``Vocabulary``: ``add`` / ``erase`` / ``clear`` / ``clear_map`` / ``set_covisibility`` / ``entries``
+    are host logic (no GPU needed); ``detect_relocalization_candidates_batch`` queries it on the device."""
+
+    def __init__(self, voc):
+        self._voc = voc  # the vocabulary must outlive the database
+        h = C.c_void_p()
+        f = lib().tc2li_keyframe_db_create
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        _check(f(voc._h, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            f = lib().tc2li_keyframe_db_destroy
+            f.argtypes = [C.c_void_p]
+            f.restype = None
+            f(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        f = lib().tc2li_keyframe_db_size
+        f.argtypes = [C.c_void_p]
+        return _check(f(self._h))
+
+    def add(self, kf_id, map_id, bow_word, bow_value):
+        """``KeyFrameDatabase::add`` -> the entry's sequence number."""
+        w, v = _bow_pair_arrays(bow_word, bow_value)
+        f = lib().tc2li_keyframe_db_add
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p]
+        return _check(f(self._h, int(kf_id), int(map_id), len(w), w.ctypes.data, v.ctypes.data))
+
+    def erase(self, kf_id):
+        f = lib().tc2li_keyframe_db_erase
+        f.argtypes = [C.c_void_p, C.c_int32]
+        return _check(f(self._h, int(kf_id)))
+
+    def clear(self):
+        f = lib().tc2li_keyframe_db_clear
+        f.argtypes = [C.c_void_p]
+        return _check(f(self._h))
+
+    def clear_map(self, map_id):
+        f = lib().tc2li_keyframe_db_clear_map
+        f.argtypes = [C.c_void_p, C.c_int32]
+        return _check(f(self._h, int(map_id)))
+
+    def set_covisibility(self, kf_id, neighbour_ids):
+        ids = np.ascontiguousarray(neighbour_ids, np.int32).reshape(-1)
+        f = lib().tc2li_keyframe_db_set_covisibility
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.c_void_p]
+        return _check(f(self._h, int(kf_id), len(ids), ids.ctypes.data))
+
+    def entries(self):
+        """Live entries in sequence order -> dict(kf_id, map_id, sequence, score)."""
+        n = len(self)
+        out = dict(kf_id=np.zeros(n, np.int32), map_id=np.zeros(n, np.int32), sequence=np.zeros(n, np.int32), score=np.zeros(n, np.float32))
+        f = lib().tc2li_keyframe_db_entries
+        f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        _check(f(self._h, n, out["kf_id"].ctypes.data, out["map_id"].ctypes.data, out["sequence"].ctypes.data, out["score"].ctypes.data))
+        return out
+
+
+def detect_relocalization_candidates_batch(queries, capacity=None, scored_capacity=None, stream=0):
+    """``KeyFrameDatabase::DetectRelocalizationCandidates`` for a list of queries (db, map_id, bow_word, bow_value), each against its own
+    database -> (list of candidate kf_id arrays, scored) where scored is None or, with ``scored_capacity``, a list of dicts
+    (kf_id, words, si, acc_score, best_kf_id) in ``lScoreAndMatch`` order."""
+    n = len(queries)
+    if capacity is None:
+        capacity = max([len(q[0]) for q in queries] + [1])
+    qs, keep = (RelocQuery * max(n, 1))(), []
+    for i, (db, map_id, word, value) in enumerate(queries):
+        w, v = _bow_pair_arrays(word, value)
+        keep.append((w, v))
+        qs[i].db, qs[i].map_id, qs[i].n_words, qs[i].bow_word, qs[i].bow_value = db._h, int(map_id), len(w), w.ctypes.data, v.ctypes.data
+    nc = np.zeros(max(n, 1), np.int32)
+    cand = np.full((max(n, 1), max(capacity, 1)), -1, np.int32)
+    sc, sa = None, None
+    if scored_capacity is not None:
+        m = (max(n, 1), max(scored_capacity, 1))
+        sa = dict(n_scored=np.zeros(max(n, 1), np.int32), kf_id=np.full(m, -1, np.int32), words=np.zeros(m, np.int32), si=np.zeros(m, np.float32),
+                  acc_score=np.zeros(m, np.float32), best_kf_id=np.full(m, -1, np.int32))
+        sc = RelocScored(int(scored_capacity), 0, *[sa[name].ctypes.data for name, _ in RelocScored._fields_[2:]])
+    f = lib().tc2li_detect_relocalization_candidates_batch
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(f(C.addressof(qs), n, int(capacity), nc.ctypes.data, cand.ctypes.data, C.byref(sc) if sc is not None else None, C.c_void_p(stream)))
+    del keep
+    cands = [cand[i, :nc[i]].copy() for i in range(n)]
+    if sa is None:
+        return cands, None
+    scored = []
+    for i in range(n):
+        k = int(sa["n_scored"][i])
+        scored.append({name: sa[name][i, :k].copy() for name in ("kf_id", "words", "si", "acc_score", "best_kf_id")})
+    return cands, scored
+
+
+class ProjectionKeyframeItem(C.Structure):
+    """tc2li_projection_keyframe_item"""
+    _fields_ = [("n", C.c_int32), ("n_points", C.c_int32), ("keys", C.c_void_p), ("descriptors", C.c_void_p), ("held", C.c_void_p),
+                ("pose7", C.c_float * 7), ("bounds", C.c_float * 4), ("pad_", C.c_float), ("has_point", C.c_void_p), ("found", C.c_void_p),
+                ("Xw", C.c_void_p), ("point_descriptors", C.c_void_p), ("min_distance", C.c_void_p), ("max_distance", C.c_void_p),
+                ("max_distance_raw", C.c_void_p), ("angle", C.c_void_p)]
+
+
+def search_by_projection_keyframe_batch(items, cam4, scale_factors, log_scale_factor, th, orb_dist, check_orientation=True, capacity=None, stream=0):
+    """``ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist)`` for a list of items; each item is a dict with the
+    frame (keys, descriptors, held, pose7, bounds = mnMinX, mnMaxX, mnMinY, mnMaxY) and the candidate keyframe's points in keypoint order
+    (has_point, found, Xw, point_descriptors, min_distance, max_distance, max_distance_raw, angle)
+    -> (kf_keypoint_of_keypoint [n_items, capacity], n_matches [n_items])."""
+    n = len(items)
+    arr, keep = (ProjectionKeyframeItem * max(n, 1))(), []
+    for i, it in enumerate(items):
+        k = np.ascontiguousarray(it["keys"], KEYPOINT_DTYPE)
+        d = np.ascontiguousarray(it["descriptors"], np.uint8).reshape(-1, 32)
+        held = np.ascontiguousarray(it["held"], np.uint8)
+        hp, fd = np.ascontiguousarray(it["has_point"], np.uint8), np.ascontiguousarray(it["found"], np.uint8)
+        xw = np.ascontiguousarray(it["Xw"], np.float32).reshape(-1, 3)
+        pd = np.ascontiguousarray(it["point_descriptors"], np.uint8).reshape(-1, 32)
+        fl = [np.ascontiguousarray(it[name], np.float32) for name in ("min_distance", "max_distance", "max_distance_raw", "angle")]
+        if not (len(d) == len(held) == len(k)) or not all(len(a) == len(hp) for a in [fd, xw, pd] + fl):
+            raise ValueError("item %d: array lengths differ" % i)
+        keep.append((k, d, held, hp, fd, xw, pd, fl))
+        arr[i].n, arr[i].n_points = len(k), len(hp)
+        arr[i].keys, arr[i].descriptors, arr[i].held = k.ctypes.data, d.ctypes.data, held.ctypes.data
+        arr[i].pose7 = (C.c_float * 7)(*[float(v) for v in it["pose7"]])
+        arr[i].bounds = (C.c_float * 4)(*[float(v) for v in it["bounds"]])
+        arr[i].has_point, arr[i].found, arr[i].Xw, arr[i].point_descriptors = hp.ctypes.data, fd.ctypes.data, xw.ctypes.data, pd.ctypes.data
+        arr[i].min_distance, arr[i].max_distance, arr[i].max_distance_raw, arr[i].angle = [a.ctypes.data for a in fl]
+    if capacity is None:
+        capacity = max([len(it["keys"]) for it in items] + [1])
+    cam4 = np.ascontiguousarray(cam4, np.float32)
+    sf = np.ascontiguousarray(scale_factors, np.float32)
+    match = np.full((max(n, 1), max(capacity, 1)), -1, np.int32)
+    nm = np.zeros(max(n, 1), np.int32)
+    f = lib().tc2li_search_by_projection_keyframe_batch
+    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(f(C.addressof(arr), n, cam4.ctypes.data, sf.ctypes.data, len(sf), float(log_scale_factor), float(th), int(orb_dist), int(bool(check_orientation)),
+             int(capacity), match.ctypes.data, nm.ctypes.data, C.c_void_p(stream)))
+    del keep
+    return match[:n], nm[:n]
+
+
+class RelocHypothesis(C.Structure):
+    """tc2li_reloc_hypothesis"""
+    _fields_ = [("frame_index", C.c_int32), ("n_points", C.c_int32), ("has_point", C.c_void_p), ("Xw", C.c_void_p), ("point_descriptors", C.c_void_p),
+                ("min_distance", C.c_void_p), ("max_distance", C.c_void_p), ("max_distance_raw", C.c_void_p), ("angle", C.c_void_p),
+                ("match", C.c_void_p), ("inlier", C.c_void_p), ("pose7", C.c_float * 7), ("pad_", C.c_float)]
+
+
+RELOC_OPT1, RELOC_REJECTED, RELOC_SEARCH1, RELOC_OPT2, RELOC_SEARCH2, RELOC_OPT3, RELOC_SUCCESS = 1, 2, 4, 8, 16, 32, 64
+
+
+def relocalization_refine_batch(ext, hyps, u_right, cam5, stream=0):
+    """The refinement ladder of ``Tracking::Relocalization`` after a PnP pose, for the frames of the preceding ``extract_batch_dev`` /
+    ``stereo_match_batch`` calls.  hyps: dicts with frame_index, the candidate keyframe (has_point, Xw, point_descriptors, min_distance,
+    max_distance, max_distance_raw, angle), pose7, match and inlier (per frame keypoint) -> dict(status, n_good, n_additional [H, 2],
+    poses7 [H, 3, 7], kf_keypoint_of_keypoint [H, capacity], outlier [H, capacity])."""
+    u_right = np.ascontiguousarray(u_right, np.float32)
+    cam5 = np.ascontiguousarray(cam5, np.float64)
+    n_frames, cap = u_right.shape
+    H = len(hyps)
+    arr, keep = (RelocHypothesis * max(H, 1))(), []
+    for i, hy in enumerate(hyps):
+        hp = np.ascontiguousarray(hy["has_point"], np.uint8)
+        xw = np.ascontiguousarray(hy["Xw"], np.float32).reshape(-1, 3)
+        pd = np.ascontiguousarray(hy["point_descriptors"], np.uint8).reshape(-1, 32)
+        fl = [np.ascontiguousarray(hy[name], np.float32) for name in ("min_distance", "max_distance", "max_distance_raw", "angle")]
+        m = np.full(cap, -1, np.int32); inl = np.zeros(cap, np.uint8)
+        m[:len(hy["match"])] = hy["match"]; inl[:len(hy["inlier"])] = hy["inlier"]
+        if not all(len(a) == len(hp) for a in [xw, pd] + fl):
+            raise ValueError("hypothesis %d: array lengths differ" % i)
+        keep.append((hp, xw, pd, fl, m, inl))
+        arr[i].frame_index, arr[i].n_points = int(hy["frame_index"]), len(hp)
+        arr[i].has_point, arr[i].Xw, arr[i].point_descriptors = hp.ctypes.data, xw.ctypes.data, pd.ctypes.data
+        arr[i].min_distance, arr[i].max_distance, arr[i].max_distance_raw, arr[i].angle = [a.ctypes.data for a in fl]
+        arr[i].match, arr[i].inlier = m.ctypes.data, inl.ctypes.data
+        arr[i].pose7 = (C.c_float * 7)(*[float(v) for v in hy["pose7"]])
+    n1 = max(H, 1)
+    out = dict(status=np.zeros(n1, np.int32), n_good=np.zeros(n1, np.int32), n_additional=np.zeros((n1, 2), np.int32), poses7=np.zeros((n1, 3, 7)),
+               kf_keypoint_of_keypoint=np.full((n1, cap), -1, np.int32), outlier=np.zeros((n1, cap), np.uint8))
+    f = lib().tc2li_relocalization_refine_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 8
+    _check(f(ext._h, C.addressof(arr), H, n_frames, u_right.ctypes.data, cap, cam5.ctypes.data, out["status"].ctypes.data, out["n_good"].ctypes.data,
+             out["n_additional"].ctypes.data, out["poses7"].ctypes.data, out["kf_keypoint_of_keypoint"].ctypes.data, out["outlier"].ctypes.data,
+             C.c_void_p(stream)))
+    del keep
+    return {k: v[:H] for k, v in out.items()}

@@ -50,9 +50,12 @@ struct MatchLists {
 };
 // only the feature grids (cell_start, items) of the frames: used by the fuse search as well
 void launch_match_grid(const MatchFrameDev* frames, int nframes, const MatchLists& L, hipStream_t st);
+// max_dist: the best distance a match may have -- TH_HIGH of the frame and map-point overloads, ORBdist of the keyframe overload
+constexpr int kMatchThHigh = 100;
 void launch_match_lists(const MatchFrameDev* frames, int nframes, const int32_t* query_frame, int total_q, const MatchLists& L, int mode,
-                        float nn_ratio, int32_t* match_of_query, int32_t* prev_claim, int32_t* rounds_out, hipStream_t st);
+                        float nn_ratio, int32_t* match_of_query, int32_t* prev_claim, int32_t* rounds_out, hipStream_t st,
+                        int max_dist = kMatchThHigh);
 void launch_match_by_projection(const MatchFrameDev* frames, int nframes, int mode, float nn_ratio, int32_t* match_of_query,
-                                int32_t* prev_claim, int32_t* rounds_out, hipStream_t st);
+                                int32_t* prev_claim, int32_t* rounds_out, hipStream_t st, int max_dist = kMatchThHigh);
 
 }  // namespace tc2li

@@ -21,7 +21,7 @@ namespace tc2li {
 constexpr int kGridCols = 64, kGridRows = 48, kCells = kGridCols * kGridRows;
 constexpr int kThreads = 512;
 
-__global__ __launch_bounds__(kThreads) void k_match_by_projection(const MatchFrameDev* __restrict__ frames, int mode, float nn_ratio,
+__global__ __launch_bounds__(kThreads) void k_match_by_projection(const MatchFrameDev* __restrict__ frames, int mode, float nn_ratio, int max_dist,
                                                                  int32_t* __restrict__ match_of_query, int32_t* __restrict__ prev_claim,
                                                                  int32_t* __restrict__ rounds_out) {
     __shared__ int s_cell_start[kCells + 1];
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(kThreads) void k_match_by_projection(const MatchFra
                                 }
                             }
                         }
-                if (bestDist <= 100) {  // TH_HIGH
+                if (bestDist <= max_dist) {  // TH_HIGH (100), or the ORBdist of the keyframe overload
                     bool ok = true;
                     if (mode != 0) {
                         if (bestLevel == bestLevel2 && (float)bestDist > nn_ratio * (float)bestDist2) ok = false;
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(256) void k_match_candidates(const MatchFrameDev* _
         }
 }
 
-__global__ __launch_bounds__(kThreads) void k_match_resolve(const MatchFrameDev* __restrict__ frames, int mode, float nn_ratio, MatchLists L,
+__global__ __launch_bounds__(kThreads) void k_match_resolve(const MatchFrameDev* __restrict__ frames, int mode, float nn_ratio, int max_dist, MatchLists L,
                                                            int32_t* __restrict__ match_of_query, int32_t* __restrict__ prev_claim,
                                                            int32_t* __restrict__ rounds_out) {
     __shared__ int s_claim[2][kMaxMatchKeys];
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(kThreads) void k_match_resolve(const MatchFrameDev*
                 }
             }
             int claim = -1;
-            if (bestDist <= 100) {  // TH_HIGH
+            if (bestDist <= max_dist) {  // TH_HIGH (100), or the ORBdist of the keyframe overload
                 bool ok = true;
                 if (mode != 0) {
                     if (bestLevel == bestLevel2 && (float)bestDist > nn_ratio * (float)bestDist2) ok = false;
@@ -356,18 +356,18 @@ void launch_match_grid(const MatchFrameDev* frames, int nframes, const MatchList
 }
 
 void launch_match_lists(const MatchFrameDev* frames, int nframes, const int32_t* query_frame, int total_q, const MatchLists& L, int mode,
-                        float nn_ratio, int32_t* match_of_query, int32_t* prev_claim, int32_t* rounds_out, hipStream_t st) {
+                        float nn_ratio, int32_t* match_of_query, int32_t* prev_claim, int32_t* rounds_out, hipStream_t st, int max_dist) {
     if (nframes <= 0) return;
     (void)hipMemsetAsync(L.pool_top, 0, 2 * sizeof(int32_t), st);
     TC2LI_LAUNCH(k_match_grid, dim3(nframes), dim3(kThreads), 0, st, frames, L);
     TC2LI_LAUNCH(k_match_candidates, dim3((total_q + 255) / 256), dim3(256), 0, st, frames, nframes, query_frame, total_q, L);
-    TC2LI_LAUNCH(k_match_resolve, dim3(nframes), dim3(kThreads), 0, st, frames, mode, nn_ratio, L, match_of_query, prev_claim, rounds_out);
+    TC2LI_LAUNCH(k_match_resolve, dim3(nframes), dim3(kThreads), 0, st, frames, mode, nn_ratio, max_dist, L, match_of_query, prev_claim, rounds_out);
 }
 
 void launch_match_by_projection(const MatchFrameDev* frames, int nframes, int mode, float nn_ratio, int32_t* match_of_query,
-                                int32_t* prev_claim, int32_t* rounds_out, hipStream_t st) {
+                                int32_t* prev_claim, int32_t* rounds_out, hipStream_t st, int max_dist) {
     if (nframes > 0)
-        TC2LI_LAUNCH(k_match_by_projection, dim3(nframes), dim3(kThreads), 0, st, frames, mode, nn_ratio, match_of_query, prev_claim,
+        TC2LI_LAUNCH(k_match_by_projection, dim3(nframes), dim3(kThreads), 0, st, frames, mode, nn_ratio, max_dist, match_of_query, prev_claim,
                            rounds_out);
 }
 

@@ -1,0 +1,794 @@
+// Host side of relocalisation (include/tc2li_hip.h "Relocalisation"): the keyframe database handle -- KeyFrameDatabase's add / erase /
+// clear / clearMap (SF/src/KeyFrameDatabase.cc:40-107) as rows of one pool of BowVectors, host logic that needs no GPU --, its device
+// copy (brought up to date by the first query after a change), the calls of tc2li_vocabulary_score_batch and
+// tc2li_detect_relocalization_candidates_batch (reloc_kernels.hip), and tc2li_search_by_projection_keyframe_batch (the matcher's kernels).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <unordered_map>
+#include <vector>
+
+#include "common.hpp"
+#include "matcher_device.hpp"
+#include "orb_handle.hpp"
+#include "pose_opt_device.hpp"
+#include "reloc_device.hpp"
+#include "tracking_device.hpp"
+
+using namespace tc2li;
+
+namespace {
+
+struct DbRow {
+    int32_t kf_id, map_id, seq;
+    int32_t off, n;
+    bool live;
+    float score;                 // mRelocScore
+    int32_t n_cov;
+    int32_t cov[kRelocMaxNeighbours];  // kf_ids
+};
+
+}  // namespace
+
+struct tc2li_keyframe_db {
+    const tc2li_vocabulary* voc = nullptr;
+    int n_voc_words = 0, scoring = 0;
+    mutable std::mutex mu;
+    std::vector<DbRow> rows;             // in sequence order, dead rows included until the pool is compacted
+    std::vector<int32_t> word;           // the pool
+    std::vector<double> value;
+    std::unordered_map<int32_t, int> row_of;  // live kf_id -> row
+    int next_seq = 0, dead = 0;
+    // device copy
+    bool rows_dirty = true;              // row table (live flags, neighbours, scores) differs from the device's
+    size_t words_on_device = 0;          // pool entries the device holds; 0 after a compaction
+    DevBuf<int32_t> d_word;
+    DevBuf<double> d_value;
+    DevBuf<RelocRowDev> d_rows;
+    DevBuf<float> d_score;
+    std::vector<float> score_down;       // download target of a query
+};
+
+namespace {
+
+int voc_info(const tc2li_vocabulary* v, int* n_words, int* scoring) {
+    int32_t info[6];
+    if (tc2li_vocabulary_info(v, info) < 0) return TC2LI_ERR_INVALID;
+    *scoring = info[2]; *n_words = info[5];
+    return TC2LI_OK;
+}
+
+// a BowVector as std::map holds it: ids strictly ascending, inside the vocabulary
+bool bow_ok(int n, const int32_t* w, const double* v, int n_voc_words) {
+    if (n < 0 || (n > 0 && (!w || !v))) return false;
+    for (int i = 0; i < n; ++i)
+        if (w[i] < 0 || w[i] >= n_voc_words || (i > 0 && w[i] <= w[i - 1])) return false;
+    return true;
+}
+
+void kill_row(tc2li_keyframe_db* db, int r) {
+    db->rows[r].live = false;
+    db->row_of.erase(db->rows[r].kf_id);
+    ++db->dead;
+    db->rows_dirty = true;
+}
+
+// the dead rows leave the pool when they pass half of it; sequence order is kept
+void compact_if_due(tc2li_keyframe_db* db) {
+    if ((size_t)db->dead * 2 <= db->rows.size()) return;
+    std::vector<DbRow> rows;
+    std::vector<int32_t> word;
+    std::vector<double> value;
+    rows.reserve(db->rows.size() - db->dead);
+    for (const DbRow& r : db->rows) {
+        if (!r.live) continue;
+        DbRow c = r;
+        c.off = (int32_t)word.size();
+        word.insert(word.end(), db->word.begin() + r.off, db->word.begin() + r.off + r.n);
+        value.insert(value.end(), db->value.begin() + r.off, db->value.begin() + r.off + r.n);
+        db->row_of[c.kf_id] = (int)rows.size();
+        rows.push_back(c);
+    }
+    db->rows.swap(rows); db->word.swap(word); db->value.swap(value);
+    db->dead = 0;
+    db->words_on_device = 0;
+    db->rows_dirty = true;
+}
+
+// brings the device copy up to date (the caller holds db->mu): new pool entries are appended, the row table is rebuilt
+int sync_device(tc2li_keyframe_db* db, std::vector<RelocRowDev>& stage, std::vector<float>& stage_score, hipStream_t st) {
+    const size_t nw = db->word.size(), nr = db->rows.size();
+    if (nw > db->d_word.n) {  // growing loses the content
+        TC2LI_HIP_CHECK(hipStreamSynchronize(st));
+        TC2LI_HIP_CHECK(db->d_word.ensure(nw)); TC2LI_HIP_CHECK(db->d_value.ensure(nw));
+        db->words_on_device = 0;
+    }
+    if (nw > db->words_on_device) {
+        const size_t a = db->words_on_device;
+        TC2LI_HIP_CHECK(hipMemcpyAsync(db->d_word.p + a, db->word.data() + a, (nw - a) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        TC2LI_HIP_CHECK(hipMemcpyAsync(db->d_value.p + a, db->value.data() + a, (nw - a) * sizeof(double), hipMemcpyHostToDevice, st));
+        db->words_on_device = nw;
+    }
+    if (db->rows_dirty && nr > 0) {
+        if (nr > db->d_rows.n) {
+            TC2LI_HIP_CHECK(hipStreamSynchronize(st));
+            TC2LI_HIP_CHECK(db->d_rows.ensure(nr)); TC2LI_HIP_CHECK(db->d_score.ensure(nr));
+        }
+        stage.resize(nr); stage_score.resize(nr);
+        for (size_t r = 0; r < nr; ++r) {
+            const DbRow& s = db->rows[r];
+            RelocRowDev& d = stage[r];
+            d.off = s.off; d.n = s.n; d.live = s.live ? 1 : 0; d.map_id = s.map_id; d.kf_id = s.kf_id;
+            d.n_cov = s.live ? s.n_cov : 0;
+            for (int k = 0; k < kRelocMaxNeighbours; ++k) {
+                d.cov[k] = -1;
+                if (k < d.n_cov) { auto it = db->row_of.find(s.cov[k]); if (it != db->row_of.end()) d.cov[k] = it->second; }
+            }
+            stage_score[r] = s.score;
+        }
+        TC2LI_HIP_CHECK(hipMemcpyAsync(db->d_rows.p, stage.data(), nr * sizeof(RelocRowDev), hipMemcpyHostToDevice, st));
+        TC2LI_HIP_CHECK(hipMemcpyAsync(db->d_score.p, stage_score.data(), nr * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    db->rows_dirty = false;
+    return TC2LI_OK;
+}
+
+struct RelocWs {
+    DevBuf<int32_t> d_word, d_i32;
+    DevBuf<double> d_value, d_out;
+    DevBuf<float> d_f32;
+    DevBuf<RelocPairDev> d_pairs;
+    DevBuf<RelocQueryDev> d_queries;
+};
+RelocWs& rws() { static thread_local RelocWs w; return w; }
+
+const char* kKlText = "scoring type KL is not supported on the device (it calls log(), whose device result is not the host library's to the last bit)";
+
+}  // namespace
+
+extern "C" int tc2li_keyframe_db_create(const tc2li_vocabulary* voc, tc2li_keyframe_db** out) {
+    if (!voc || !out) { set_error("tc2li_keyframe_db_create: invalid argument"); return TC2LI_ERR_INVALID; }
+    *out = nullptr;
+    int nw = 0, sc = 0;
+    if (int rc = voc_info(voc, &nw, &sc)) return rc;
+    tc2li_keyframe_db* db = new tc2li_keyframe_db();
+    db->voc = voc; db->n_voc_words = nw; db->scoring = sc;
+    *out = db;
+    return TC2LI_OK;
+}
+
+extern "C" void tc2li_keyframe_db_destroy(tc2li_keyframe_db* db) { delete db; }
+
+extern "C" int tc2li_keyframe_db_add(tc2li_keyframe_db* db, int32_t kf_id, int32_t map_id, int n_words, const int32_t* bow_word,
+                                     const double* bow_value) {
+    if (!db || kf_id < 0) { set_error("tc2li_keyframe_db_add: invalid argument"); return TC2LI_ERR_INVALID; }
+    if (!bow_ok(n_words, bow_word, bow_value, db->n_voc_words)) {
+        set_error("tc2li_keyframe_db_add: keyframe %d: word ids must be strictly ascending and inside the vocabulary (%d words)", kf_id, db->n_voc_words);
+        return TC2LI_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(db->mu);
+    if (db->row_of.count(kf_id)) { set_error("tc2li_keyframe_db_add: keyframe %d is in the database already", kf_id); return TC2LI_ERR_INVALID; }
+    if (n_words > kRelocMaxWords) { set_error("tc2li_keyframe_db_add: keyframe %d has %d words (at most %d)", kf_id, n_words, kRelocMaxWords); return TC2LI_ERR_CAPACITY; }
+    if ((int)db->row_of.size() >= kRelocMaxLive) { set_error("tc2li_keyframe_db_add: the database holds %d keyframes already", kRelocMaxLive); return TC2LI_ERR_CAPACITY; }
+    DbRow r{};
+    r.kf_id = kf_id; r.map_id = map_id; r.seq = db->next_seq++; r.off = (int32_t)db->word.size(); r.n = n_words; r.live = true; r.score = 0.0f;
+    db->word.insert(db->word.end(), bow_word, bow_word + n_words);
+    db->value.insert(db->value.end(), bow_value, bow_value + n_words);
+    db->row_of[kf_id] = (int)db->rows.size();
+    db->rows.push_back(r);
+    db->rows_dirty = true;
+    return r.seq;
+}
+
+extern "C" int tc2li_keyframe_db_erase(tc2li_keyframe_db* db, int32_t kf_id) {
+    if (!db) { set_error("tc2li_keyframe_db_erase: invalid argument"); return TC2LI_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(db->mu);
+    auto it = db->row_of.find(kf_id);
+    if (it == db->row_of.end()) return 0;
+    kill_row(db, it->second);
+    compact_if_due(db);
+    return 1;
+}
+
+extern "C" int tc2li_keyframe_db_clear(tc2li_keyframe_db* db) {
+    if (!db) { set_error("tc2li_keyframe_db_clear: invalid argument"); return TC2LI_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(db->mu);
+    const int n = (int)db->row_of.size();
+    db->rows.clear(); db->word.clear(); db->value.clear(); db->row_of.clear();
+    db->dead = 0; db->words_on_device = 0; db->rows_dirty = true;
+    return n;
+}
+
+extern "C" int tc2li_keyframe_db_clear_map(tc2li_keyframe_db* db, int32_t map_id) {
+    if (!db) { set_error("tc2li_keyframe_db_clear_map: invalid argument"); return TC2LI_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(db->mu);
+    int n = 0;
+    for (size_t r = 0; r < db->rows.size(); ++r)
+        if (db->rows[r].live && db->rows[r].map_id == map_id) { kill_row(db, (int)r); ++n; }
+    compact_if_due(db);
+    return n;
+}
+
+extern "C" int tc2li_keyframe_db_size(const tc2li_keyframe_db* db) {
+    if (!db) { set_error("tc2li_keyframe_db_size: invalid argument"); return TC2LI_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(db->mu);
+    return (int)db->row_of.size();
+}
+
+extern "C" int tc2li_keyframe_db_set_covisibility(tc2li_keyframe_db* db, int32_t kf_id, int n, const int32_t* ids) {
+    if (!db || n < 0 || (n > 0 && !ids)) { set_error("tc2li_keyframe_db_set_covisibility: invalid argument"); return TC2LI_ERR_INVALID; }
+    if (n > kRelocMaxNeighbours) { set_error("tc2li_keyframe_db_set_covisibility: %d neighbours (at most %d)", n, kRelocMaxNeighbours); return TC2LI_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(db->mu);
+    auto it = db->row_of.find(kf_id);
+    if (it == db->row_of.end()) { set_error("tc2li_keyframe_db_set_covisibility: keyframe %d is not in the database", kf_id); return TC2LI_ERR_INVALID; }
+    DbRow& r = db->rows[it->second];
+    r.n_cov = n;
+    for (int k = 0; k < n; ++k) r.cov[k] = ids[k];
+    db->rows_dirty = true;
+    return n;
+}
+
+extern "C" int tc2li_keyframe_db_entries(const tc2li_keyframe_db* db, int capacity, int32_t* kf_id, int32_t* map_id, int32_t* sequence, float* score) {
+    if (!db || capacity < 0) { set_error("tc2li_keyframe_db_entries: invalid argument"); return TC2LI_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(db->mu);
+    const int n = (int)db->row_of.size();
+    if (n > capacity) { set_error("tc2li_keyframe_db_entries: capacity %d < %d entries", capacity, n); return TC2LI_ERR_CAPACITY; }
+    int i = 0;
+    for (const DbRow& r : db->rows) {
+        if (!r.live) continue;
+        if (kf_id) kf_id[i] = r.kf_id;
+        if (map_id) map_id[i] = r.map_id;
+        if (sequence) sequence[i] = r.seq;
+        if (score) score[i] = r.score;
+        ++i;
+    }
+    return n;
+}
+
+extern "C" int tc2li_vocabulary_score_batch(tc2li_vocabulary* voc, int n_pairs, const tc2li_bow_vector* v1, const tc2li_bow_vector* v2,
+                                            double* scores, void* stream_) {
+    if (!device_ready()) return TC2LI_ERR_NO_DEVICE;  // no CPU fallback: before anything else
+    if (!voc || n_pairs < 0 || (n_pairs > 0 && (!v1 || !v2 || !scores))) { set_error("tc2li_vocabulary_score_batch: invalid argument"); return TC2LI_ERR_INVALID; }
+    int nw = 0, sc = 0;
+    if (int rc = voc_info(voc, &nw, &sc)) return rc;
+    if (sc == 3) { set_error("tc2li_vocabulary_score_batch: %s", kKlText); return TC2LI_ERR_INVALID; }
+    std::vector<RelocPairDev> P(n_pairs);
+    size_t total = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        for (const tc2li_bow_vector* v : {&v1[p], &v2[p]}) {
+            if (!bow_ok(v->n, v->word, v->value, nw)) {
+                set_error("tc2li_vocabulary_score_batch: pair %d: word ids must be strictly ascending and inside the vocabulary (%d words)", p, nw);
+                return TC2LI_ERR_INVALID;
+            }
+            if (v->n > kRelocMaxWords) { set_error("tc2li_vocabulary_score_batch: pair %d: %d words (at most %d)", p, v->n, kRelocMaxWords); return TC2LI_ERR_CAPACITY; }
+        }
+        P[p] = RelocPairDev{(int32_t)total, v1[p].n, (int32_t)(total + v1[p].n), v2[p].n};
+        total += (size_t)v1[p].n + v2[p].n;
+    }
+    if (n_pairs == 0) return 0;
+    std::vector<int32_t> word(std::max<size_t>(total, 1));
+    std::vector<double> value(std::max<size_t>(total, 1));
+    for (int p = 0; p < n_pairs; ++p) {
+        if (v1[p].n) { memcpy(&word[P[p].off1], v1[p].word, v1[p].n * sizeof(int32_t)); memcpy(&value[P[p].off1], v1[p].value, v1[p].n * sizeof(double)); }
+        if (v2[p].n) { memcpy(&word[P[p].off2], v2[p].word, v2[p].n * sizeof(int32_t)); memcpy(&value[P[p].off2], v2[p].value, v2[p].n * sizeof(double)); }
+    }
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : private_stream();
+    RelocWs& w = rws();
+    TC2LI_HIP_CHECK(w.d_word.ensure(word.size())); TC2LI_HIP_CHECK(w.d_value.ensure(value.size()));
+    TC2LI_HIP_CHECK(w.d_pairs.ensure(n_pairs)); TC2LI_HIP_CHECK(w.d_out.ensure(n_pairs));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_word.p, word.data(), word.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_value.p, value.data(), value.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_pairs.p, P.data(), n_pairs * sizeof(RelocPairDev), hipMemcpyHostToDevice, st));
+    launch_bow_score(w.d_pairs.p, n_pairs, w.d_word.p, w.d_value.p, sc, w.d_out.p, st);
+    TC2LI_HIP_CHECK(hipGetLastError());
+    TC2LI_HIP_CHECK(hipMemcpyAsync(scores, w.d_out.p, n_pairs * sizeof(double), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(stream_wait_blocking(st));
+    return n_pairs;
+}
+
+extern "C" int tc2li_detect_relocalization_candidates_batch(const tc2li_reloc_query* queries, int n_queries, int capacity, int32_t* n_candidates,
+                                                            int32_t* candidates, const tc2li_reloc_scored* scored, void* stream_) {
+    if (!device_ready()) return TC2LI_ERR_NO_DEVICE;  // no CPU fallback: before anything else
+    const char* fn = "tc2li_detect_relocalization_candidates_batch";
+    if (n_queries < 0 || capacity < 0 || (n_queries > 0 && (!queries || !n_candidates || (capacity > 0 && !candidates))) ||
+        (scored && (scored->capacity < 0 || !scored->n_scored ||
+                    (scored->capacity > 0 && (!scored->kf_id || !scored->words || !scored->si || !scored->acc_score || !scored->best_kf_id))))) {
+        set_error("%s: invalid argument", fn);
+        return TC2LI_ERR_INVALID;
+    }
+    if (n_queries > 512) { set_error("%s: %d queries (at most 512 per call)", fn, n_queries); return TC2LI_ERR_CAPACITY; }
+    if (n_queries == 0) return 0;
+    std::vector<tc2li_keyframe_db*> dbs(n_queries);
+    int scoring = -1;
+    size_t n_f = 0;
+    for (int q = 0; q < n_queries; ++q) {
+        const tc2li_reloc_query& Q = queries[q];
+        if (!Q.db) { set_error("%s: query %d has no database", fn, q); return TC2LI_ERR_INVALID; }
+        if (Q.db->scoring == 3) { set_error("%s: query %d: %s", fn, q, kKlText); return TC2LI_ERR_INVALID; }
+        if (scoring >= 0 && Q.db->scoring != scoring) { set_error("%s: the databases of one call must share the scoring type", fn); return TC2LI_ERR_INVALID; }
+        scoring = Q.db->scoring;
+        if (!bow_ok(Q.n_words, Q.bow_word, Q.bow_value, Q.db->n_voc_words)) {
+            set_error("%s: query %d: word ids must be strictly ascending and inside the vocabulary (%d words)", fn, q, Q.db->n_voc_words);
+            return TC2LI_ERR_INVALID;
+        }
+        if (Q.n_words > kRelocMaxWords) { set_error("%s: query %d: %d words (at most %d)", fn, q, Q.n_words, kRelocMaxWords); return TC2LI_ERR_CAPACITY; }
+        dbs[q] = Q.db;
+        n_f += Q.n_words;
+    }
+    // every database once: its queries depend on each other through the score state.  Locked in address order.
+    std::vector<tc2li_keyframe_db*> order(dbs);
+    std::sort(order.begin(), order.end());
+    if (std::adjacent_find(order.begin(), order.end()) != order.end()) {
+        set_error("%s: the same database twice in one call (the queries of one database are sequential: they share its score state)", fn);
+        return TC2LI_ERR_INVALID;
+    }
+    std::vector<std::unique_lock<std::mutex>> locks;
+    locks.reserve(n_queries);
+    for (tc2li_keyframe_db* d : order) locks.emplace_back(d->mu);
+
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : private_stream();
+    RelocWs& w = rws();
+    // the frames' BowVectors, one upload
+    std::vector<int32_t> f_word(std::max<size_t>(n_f, 1));
+    std::vector<double> f_value(std::max<size_t>(n_f, 1));
+    std::vector<RelocQueryDev> QD(n_queries);
+    std::vector<std::vector<RelocRowDev>> stage(n_queries);
+    std::vector<std::vector<float>> stage_score(n_queries);
+    size_t pos = 0, row_off = 0;
+    int max_rows = 0;
+    for (int q = 0; q < n_queries; ++q) {
+        const tc2li_reloc_query& Q = queries[q];
+        tc2li_keyframe_db* db = Q.db;
+        if (int rc = sync_device(db, stage[q], stage_score[q], st)) return rc;
+        if (Q.n_words) { memcpy(&f_word[pos], Q.bow_word, Q.n_words * sizeof(int32_t)); memcpy(&f_value[pos], Q.bow_value, Q.n_words * sizeof(double)); }
+        RelocQueryDev& D = QD[q];
+        D.kf_word = db->d_word.p; D.kf_value = db->d_value.p; D.rows = db->d_rows.p; D.score = db->d_score.p;
+        D.n_rows = (int32_t)db->rows.size();
+        D.f_off = (int32_t)pos; D.f_n = Q.n_words; D.map_id = Q.map_id; D.row_off = (int32_t)row_off; D.pad_ = 0;
+        if (D.n_rows > 2 * kRelocMaxLive) { set_error("%s: query %d: the pool holds %d rows", fn, q, D.n_rows); return TC2LI_ERR_CAPACITY; }
+        pos += Q.n_words;
+        row_off += D.n_rows;
+        max_rows = std::max(max_rows, D.n_rows);
+    }
+    const size_t nq = n_queries, nr = std::max<size_t>(row_off, 1), cap = std::max(capacity, 1);
+    const size_t lc = std::min<size_t>(kRelocMaxLive, std::max(max_rows, 1));
+    TC2LI_HIP_CHECK(w.d_word.ensure(f_word.size())); TC2LI_HIP_CHECK(w.d_value.ensure(f_value.size())); TC2LI_HIP_CHECK(w.d_queries.ensure(nq));
+    // int32: common, first_word [nr]; n_candidates, n_scored [nq]; candidates [nq][cap]; sc_row, sc_kf, sc_words, sc_best_row, sc_best [nq][lc]
+    TC2LI_HIP_CHECK(w.d_i32.ensure(2 * nr + 2 * nq + nq * cap + 5 * nq * lc));
+    TC2LI_HIP_CHECK(w.d_f32.ensure(nr + 2 * nq * lc));  // si [nr]; sc_si, sc_acc [nq][lc]
+    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_word.p, f_word.data(), f_word.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_value.p, f_value.data(), f_value.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_queries.p, QD.data(), nq * sizeof(RelocQueryDev), hipMemcpyHostToDevice, st));
+    RelocArgs A{};
+    A.queries = w.d_queries.p; A.n_queries = n_queries; A.max_rows = max_rows; A.scoring = scoring;
+    A.f_word = w.d_word.p; A.f_value = w.d_value.p;
+    int32_t* ip = w.d_i32.p;
+    A.common = ip; A.first_word = ip + nr; A.n_candidates = ip + 2 * nr; A.n_scored = A.n_candidates + nq; A.candidates = A.n_scored + nq;
+    A.sc_row = A.candidates + nq * cap; A.sc_kf = A.sc_row + nq * lc; A.sc_words = A.sc_kf + nq * lc; A.sc_best_row = A.sc_words + nq * lc;
+    A.sc_best = A.sc_best_row + nq * lc;
+    A.si = w.d_f32.p; A.sc_si = A.si + nr; A.sc_acc = A.sc_si + nq * lc;
+    A.capacity = capacity; A.list_cap = (int)lc;
+    TC2LI_HIP_CHECK(hipMemsetAsync(A.candidates, 0xff, nq * cap * sizeof(int32_t), st));
+    launch_reloc_candidates(A, st);
+    TC2LI_HIP_CHECK(hipGetLastError());
+    // results; the score states come back to the handles, which own them
+    std::vector<int32_t> n_scored(nq);
+    TC2LI_HIP_CHECK(hipMemcpyAsync(n_candidates, A.n_candidates, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(n_scored.data(), A.n_scored, nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (capacity > 0) TC2LI_HIP_CHECK(hipMemcpyAsync(candidates, A.candidates, nq * cap * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    for (int q = 0; q < n_queries; ++q) {
+        tc2li_keyframe_db* db = dbs[q];
+        db->score_down.resize(db->rows.size());
+        if (!db->rows.empty())
+            TC2LI_HIP_CHECK(hipMemcpyAsync(db->score_down.data(), db->d_score.p, db->rows.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    TC2LI_HIP_CHECK(stream_wait_blocking(st));
+    for (int q = 0; q < n_queries; ++q) {
+        tc2li_keyframe_db* db = dbs[q];
+        for (size_t r = 0; r < db->rows.size(); ++r) db->rows[r].score = db->score_down[r];
+    }
+    int rc = n_queries;
+    for (int q = 0; q < n_queries && rc >= 0; ++q) {
+        if (n_candidates[q] > capacity) { set_error("%s: query %d has %d candidates, capacity %d", fn, q, n_candidates[q], capacity); rc = TC2LI_ERR_CAPACITY; }
+        else if (scored && n_scored[q] > scored->capacity) {
+            set_error("%s: query %d scored %d keyframes, the scored list's capacity is %d", fn, q, n_scored[q], scored->capacity);
+            rc = TC2LI_ERR_CAPACITY;
+        }
+    }
+    if (rc < 0) return rc;
+    if (scored) {
+        memcpy(scored->n_scored, n_scored.data(), nq * sizeof(int32_t));
+        const size_t sc = scored->capacity;
+        if (sc > 0) {
+            std::vector<int32_t> h_i(3 * nq * lc);
+            std::vector<float> h_f(2 * nq * lc);
+            TC2LI_HIP_CHECK(hipMemcpyAsync(h_i.data(), A.sc_kf, 2 * nq * lc * sizeof(int32_t), hipMemcpyDeviceToHost, st));  // sc_kf, sc_words
+            TC2LI_HIP_CHECK(hipMemcpyAsync(h_i.data() + 2 * nq * lc, A.sc_best, nq * lc * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            TC2LI_HIP_CHECK(hipMemcpyAsync(h_f.data(), A.sc_si, 2 * nq * lc * sizeof(float), hipMemcpyDeviceToHost, st));    // sc_si, sc_acc
+            TC2LI_HIP_CHECK(stream_wait_blocking(st));
+            for (size_t q = 0; q < nq; ++q) {
+                const size_t n = n_scored[q];
+                for (size_t i = 0; i < sc; ++i) {
+                    const bool in = i < n;
+                    scored->kf_id[q * sc + i] = in ? h_i[q * lc + i] : -1;
+                    scored->words[q * sc + i] = in ? h_i[nq * lc + q * lc + i] : 0;
+                    scored->best_kf_id[q * sc + i] = in ? h_i[2 * nq * lc + q * lc + i] : -1;
+                    scored->si[q * sc + i] = in ? h_f[q * lc + i] : 0.0f;
+                    scored->acc_score[q * sc + i] = in ? h_f[nq * lc + q * lc + i] : 0.0f;
+                }
+            }
+        }
+    }
+    return n_queries;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) (SF/src/ORBmatcher.cc:1898-2019) for a batch of items.  The
+// queries come from k_track_queries_keyframe; the search is the matcher's (matcher_kernels.hip: feature grid, candidate lists, the rounds
+// that reproduce "a matched keypoint blocks later points") with ORBdist as its distance bound; the rotation filter is k_track_count.
+namespace {
+
+constexpr int kCellsPlus1 = 64 * 48 + 1;  // the matcher's feature grid (matcher_kernels.hip)
+
+struct KfSearchWs {
+    PinnedBuf<uint8_t> h_stage;
+    DevBuf<uint8_t> d_stage;
+    DevBuf<MatchQuery> d_queries;
+    DevBuf<int32_t> d_i32;
+    DevBuf<float> d_f32;
+    DevBuf<uint16_t> d_items;
+    DevBuf<uint32_t> d_pool;
+    PinnedBuf<int32_t> h_small;
+    PinnedBuf<float> h_ratio;
+};
+KfSearchWs& kws() { static thread_local KfSearchWs w; return w; }
+
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" int tc2li_search_by_projection_keyframe_batch(const tc2li_projection_keyframe_item* items, int n_items, const float* cam4,
+                                                         const float* scale_factors, int n_levels, float log_scale_factor, float th, int orb_dist,
+                                                         int check_orientation, int capacity, int32_t* kf_keypoint_of_keypoint, int32_t* n_matches,
+                                                         void* stream_) {
+    if (!device_ready()) return TC2LI_ERR_NO_DEVICE;  // no CPU fallback: before anything else
+    const char* fn = "tc2li_search_by_projection_keyframe_batch";
+    if (n_items < 0 || capacity < 0 || (n_items > 0 && (!items || !kf_keypoint_of_keypoint || !n_matches)) || !cam4 || !scale_factors || n_levels < 1 ||
+        n_levels > kMaxLevels) {
+        set_error("%s: invalid argument (at most %d levels)", fn, kMaxLevels);
+        return TC2LI_ERR_INVALID;
+    }
+    if (n_items == 0) return 0;
+    size_t nk = 0, nq = 0;
+    for (int f = 0; f < n_items; ++f) {
+        const tc2li_projection_keyframe_item& I = items[f];
+        if (I.n < 0 || I.n_points < 0 || (I.n > 0 && (!I.keys || !I.descriptors || !I.held)) ||
+            (I.n_points > 0 && (!I.has_point || !I.found || !I.Xw || !I.point_descriptors || !I.min_distance || !I.max_distance || !I.max_distance_raw ||
+                                !I.angle))) {
+            set_error("%s: item %d has null arrays", fn, f);
+            return TC2LI_ERR_INVALID;
+        }
+        if (I.n > capacity) { set_error("%s: capacity %d < %d keypoints of item %d", fn, capacity, I.n, f); return TC2LI_ERR_CAPACITY; }
+        if (I.n > kMaxMatchKeys) { set_error("%s: item %d has %d keypoints, the matcher supports %d", fn, f, I.n, kMaxMatchKeys); return TC2LI_ERR_CAPACITY; }
+        nk += I.n; nq += I.n_points;
+    }
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : private_stream();
+    KfSearchWs& w = kws();
+    const size_t nf = n_items, k1 = std::max<size_t>(nk, 1), q1 = std::max<size_t>(nq, 1);
+    const int total_q = (int)nq;
+    // one staging block: per frame keypoint the matcher's key, descriptor, angle, held flag and a u_right of -1 (the overload has no stereo
+    // test); per keyframe keypoint the point; per frame the records
+    const size_t o_keys = 0, o_desc = up256(o_keys + sizeof(MatchKey) * k1), o_ang = up256(o_desc + 32 * k1), o_ur = up256(o_ang + 4 * k1),
+                 o_held = up256(o_ur + 4 * k1), o_hp = up256(o_held + k1), o_found = up256(o_hp + q1), o_Xw = up256(o_found + q1),
+                 o_pd = up256(o_Xw + 12 * q1), o_min = up256(o_pd + 32 * q1), o_max = up256(o_min + 4 * q1), o_raw = up256(o_max + 4 * q1),
+                 o_pang = up256(o_raw + 4 * q1), o_frames = up256(o_pang + 4 * q1), o_bounds = up256(o_frames + sizeof(TrackFrameDev) * nf),
+                 o_mframes = up256(o_bounds + 16 * nf), o_kbase = up256(o_mframes + sizeof(MatchFrameDev) * nf), bytes = up256(o_kbase + 4 * nf);
+    TC2LI_HIP_CHECK(w.h_stage.ensure(bytes)); TC2LI_HIP_CHECK(w.d_stage.ensure(bytes));
+    TC2LI_HIP_CHECK(w.d_queries.ensure(q1));
+    const int pool_cap = 32 * (int)q1;
+    // int32: query_frame, match, prev, cand_off, cand_cnt, amb_ids, amb_level [q1]; rounds, n_matches [nf]; cell_start [nf][cells + 1];
+    // pool_top [2]; amb_count [1]; of_key [nf][capacity]
+    const size_t cap1 = std::max(capacity, 1);
+    TC2LI_HIP_CHECK(w.d_i32.ensure(7 * q1 + 2 * nf + nf * kCellsPlus1 + 4 + nf * cap1));
+    TC2LI_HIP_CHECK(w.d_f32.ensure(2 * q1));  // amb_ratio, amb_r
+    TC2LI_HIP_CHECK(w.d_items.ensure(k1)); TC2LI_HIP_CHECK(w.d_pool.ensure(pool_cap));
+    TC2LI_HIP_CHECK(w.h_small.ensure(4 + q1)); TC2LI_HIP_CHECK(w.h_ratio.ensure(q1));
+    uint8_t* h = w.h_stage.p;
+    uint8_t* d = w.d_stage.p;
+    MatchKey* hk = reinterpret_cast<MatchKey*>(h + o_keys);
+    float* hang = reinterpret_cast<float*>(h + o_ang);
+    float* hur = reinterpret_cast<float*>(h + o_ur);
+    TrackFrameDev* hf = reinterpret_cast<TrackFrameDev*>(h + o_frames);
+    float* hb = reinterpret_cast<float*>(h + o_bounds);
+    MatchFrameDev* hm = reinterpret_cast<MatchFrameDev*>(h + o_mframes);
+    int32_t* hkb = reinterpret_cast<int32_t*>(h + o_kbase);
+    size_t key = 0, q = 0;
+    for (int f = 0; f < n_items; ++f) {
+        const tc2li_projection_keyframe_item& I = items[f];
+        for (int i = 0; i < I.n; ++i) {
+            hk[key + i] = MatchKey{I.keys[i].x, I.keys[i].y, I.keys[i].octave};
+            hang[key + i] = I.keys[i].angle;
+            hur[key + i] = -1.0f;
+            h[o_held + key + i] = I.held[i] ? 1 : 0;
+        }
+        if (I.n) memcpy(h + o_desc + 32 * key, I.descriptors, 32 * (size_t)I.n);
+        for (int i = 0; i < I.n_points; ++i) { h[o_hp + q + i] = I.has_point[i] ? 1 : 0; h[o_found + q + i] = I.found[i] ? 1 : 0; }
+        if (I.n_points) {
+            memcpy(h + o_Xw + 12 * q, I.Xw, 12 * (size_t)I.n_points);
+            memcpy(h + o_pd + 32 * q, I.point_descriptors, 32 * (size_t)I.n_points);
+            memcpy(h + o_min + 4 * q, I.min_distance, 4 * (size_t)I.n_points);
+            memcpy(h + o_max + 4 * q, I.max_distance, 4 * (size_t)I.n_points);
+            memcpy(h + o_raw + 4 * q, I.max_distance_raw, 4 * (size_t)I.n_points);
+            memcpy(h + o_pang + 4 * q, I.angle, 4 * (size_t)I.n_points);
+        }
+        TrackFrameDev& F = hf[f];
+        memset(&F, 0, sizeof(F));
+        memcpy(F.pose7, I.pose7, 7 * sizeof(float));
+        F.th = th; F.q_off = (int32_t)q; F.n_q = I.n_points; F.key_off = (int32_t)key; F.n_keys = I.n; F.slot = f;
+        memcpy(hb + 4 * f, I.bounds, 16);
+        hm[f] = MatchFrameDev{reinterpret_cast<const MatchKey*>(d + o_keys) + key, d + o_desc + 32 * key, reinterpret_cast<const float*>(d + o_ur) + key,
+                              d + o_held + key, w.d_queries.p + q, I.n, I.n_points, (int32_t)q, 0, I.bounds[0], I.bounds[1], I.bounds[2], I.bounds[3]};
+        hkb[f] = (int32_t)key;
+        key += I.n; q += I.n_points;
+    }
+    TrackConst C;
+    memset(&C, 0, sizeof(C));
+    memcpy(C.cam4, cam4, 16);
+    C.n_levels = n_levels; C.capacity = capacity; C.log_scale = log_scale_factor;
+    for (int l = 0; l < n_levels; ++l) C.scale[l] = scale_factors[l];
+    TC2LI_HIP_CHECK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
+    int32_t* ip = w.d_i32.p;
+    int32_t *d_qf = ip, *d_match = ip + q1, *d_prev = ip + 2 * q1, *d_coff = ip + 3 * q1, *d_ccnt = ip + 4 * q1, *d_amb_ids = ip + 5 * q1,
+            *d_amb_level = ip + 6 * q1, *d_rounds = ip + 7 * q1, *d_nm = d_rounds + nf, *d_cells = d_nm + nf, *d_top = d_cells + nf * kCellsPlus1,
+            *d_amb = d_top + 2, *d_of_key = d_amb + 2;
+    float *d_amb_ratio = w.d_f32.p, *d_amb_r = w.d_f32.p + q1;
+    const TrackFrameDev* d_frames = reinterpret_cast<const TrackFrameDev*>(d + o_frames);
+    const MatchFrameDev* d_mframes = reinterpret_cast<const MatchFrameDev*>(d + o_mframes);
+    const KeyframePointArrays A{d + o_hp, d + o_found, reinterpret_cast<const float*>(d + o_Xw), d + o_pd, reinterpret_cast<const float*>(d + o_min),
+                                reinterpret_cast<const float*>(d + o_max), reinterpret_cast<const float*>(d + o_raw), reinterpret_cast<const float*>(d + o_pang)};
+    TC2LI_HIP_CHECK(hipMemsetAsync(d_of_key, 0xff, nf * cap1 * sizeof(int32_t), st));
+    TC2LI_HIP_CHECK(hipMemsetAsync(d_nm, 0, nf * sizeof(int32_t), st));
+    if (total_q > 0) {
+        TC2LI_HIP_CHECK(hipMemsetAsync(d_amb, 0, sizeof(int32_t), st));
+        launch_track_queries_keyframe(d_frames, n_items, reinterpret_cast<const float4*>(d + o_bounds), C, A, total_q, w.d_queries.p, d_qf, d_match, d_amb,
+                                      d_amb_ids, d_amb_ratio, d_amb_r, st);
+        TC2LI_HIP_CHECK(hipGetLastError());
+        // MapPoint::PredictScale on a level boundary: the host's logf decides, as in tc2li_track_local_map_batch
+        TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_small.p, d_amb, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TC2LI_HIP_CHECK(stream_wait_blocking(st));
+        const int n_amb = w.h_small.p[0];
+        if (n_amb > 0) {
+            TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_ratio.p, d_amb_ratio, n_amb * sizeof(float), hipMemcpyDeviceToHost, st));
+            TC2LI_HIP_CHECK(stream_wait_blocking(st));
+            int32_t* lev = w.h_small.p + 4;
+            for (int k = 0; k < n_amb; ++k) {
+                int level = (int)ceilf(logf(w.h_ratio.p[k]) / log_scale_factor);  // MapPoint::PredictScale (SF/src/MapPoint.cc:540-555)
+                if (level < 0) level = 0; else if (level >= n_levels) level = n_levels - 1;
+                lev[k] = level;
+            }
+            TC2LI_HIP_CHECK(hipMemcpyAsync(d_amb_level, lev, n_amb * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            launch_track_patch_levels_keyframe(d_amb_ids, d_amb_level, d_amb_r, n_amb, C, w.d_queries.p, st);
+        }
+        MatchLists L{d_cells, w.d_items.p, reinterpret_cast<const int32_t*>(d + o_kbase), d_coff, d_ccnt, w.d_pool.p, d_top, pool_cap, 0};
+        launch_match_lists(d_mframes, n_items, d_qf, total_q, L, 0, 0.0f, d_match, d_prev, d_rounds, st, orb_dist);
+        TC2LI_HIP_CHECK(hipGetLastError());
+        TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_small.p, d_top, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TC2LI_HIP_CHECK(stream_wait_blocking(st));
+        if (w.h_small.p[1]) {  // candidate pool exhausted (very dense windows): the one-kernel form, same result
+            TC2LI_HIP_CHECK(hipMemsetAsync(d_match, 0xff, q1 * sizeof(int32_t), st));
+            launch_match_by_projection(d_mframes, n_items, 0, 0.0f, d_match, d_prev, d_rounds, st, orb_dist);
+        }
+        launch_track_count(d_frames, nullptr, n_items, w.d_queries.p, reinterpret_cast<const float*>(d + o_ang), check_orientation ? 1 : 0, d_match, d_nm, st);
+        launch_track_assign_keyframe(d_frames, n_items, capacity, total_q, d_match, d_of_key, st);
+        TC2LI_HIP_CHECK(hipGetLastError());
+    }
+    if (capacity > 0) TC2LI_HIP_CHECK(hipMemcpyAsync(kf_keypoint_of_keypoint, d_of_key, nf * cap1 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(n_matches, d_nm, nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(stream_wait_blocking(st));
+    return n_items;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The refinement ladder of Tracking::Relocalization after a PnP pose (SF/src/Tracking.cc:3562-3631) for a batch of independent hypotheses
+// on the frames of the last tc2li_orb_extract_batch call: one stream, one staging upload, every branch decided on the device
+// (reloc_kernels.hip k_reloc_ladder_*).  The host waits only where the searches need it: the host's logf for PredictScale on a level boundary
+// and the candidate pool's overflow flag, as in tc2li_track_local_map_batch.
+namespace {
+
+struct LadderWs {
+    PinnedBuf<uint8_t> h_stage;
+    DevBuf<uint8_t> d_stage, d_u8;
+    DevBuf<TrackFrameDev> d_frames;
+    DevBuf<MatchQuery> d_queries;
+    DevBuf<int32_t> d_i32;
+    DevBuf<float> d_f32;
+    DevBuf<uint16_t> d_items;
+    DevBuf<uint32_t> d_pool;
+    DevBuf<PoseProblem> d_probs;
+    DevBuf<BaEdge> d_edges;
+    DevBuf<double> d_f64;
+    PinnedBuf<int32_t> h_small;
+    PinnedBuf<float> h_ratio;
+};
+LadderWs& lws() { static thread_local LadderWs w; return w; }
+
+}  // namespace
+
+extern "C" int tc2li_relocalization_refine_batch(tc2li_orb* o, const tc2li_reloc_hypothesis* hyps, int n_hyps, int n_frames, const float* u_right,
+                                                 int capacity, const tc2li_camera* cam, int32_t* status, int32_t* n_good, int32_t* n_additional,
+                                                 double* poses7, int32_t* kf_keypoint_of_keypoint, uint8_t* outlier, void* stream_) {
+    if (!device_ready()) return TC2LI_ERR_NO_DEVICE;  // no CPU fallback: before anything else
+    const char* fn = "tc2li_relocalization_refine_batch";
+    if (!o || n_hyps < 0 || n_frames < 0 || capacity < 0 || !u_right || !cam ||
+        (n_hyps > 0 && (!hyps || !status || !n_good || !n_additional || !poses7 || !kf_keypoint_of_keypoint || !outlier))) {
+        set_error("%s: invalid argument", fn);
+        return TC2LI_ERR_INVALID;
+    }
+    if (n_hyps == 0) return 0;
+    if (2 * n_frames > o->last_nimg || !o->last_plain_order) {
+        set_error("%s: needs the features of a preceding tc2li_orb_extract_batch call with lapping area {0,0} and 2*n_frames images", fn);
+        return TC2LI_ERR_INVALID;
+    }
+    const int n_levels = o->prm.nlevels;
+    if (n_levels > kMaxLevels) { set_error("%s: %d levels (at most %d)", fn, n_levels, kMaxLevels); return TC2LI_ERR_INVALID; }
+    size_t nq = 0;
+    for (int h = 0; h < n_hyps; ++h) {
+        const tc2li_reloc_hypothesis& Hy = hyps[h];
+        if (Hy.frame_index < 0 || Hy.frame_index >= n_frames) { set_error("%s: hypothesis %d names frame %d of %d", fn, h, Hy.frame_index, n_frames); return TC2LI_ERR_INVALID; }
+        if (Hy.n_points < 0 || !Hy.match || !Hy.inlier ||
+            (Hy.n_points > 0 && (!Hy.has_point || !Hy.Xw || !Hy.point_descriptors || !Hy.min_distance || !Hy.max_distance || !Hy.max_distance_raw || !Hy.angle))) {
+            set_error("%s: hypothesis %d has null arrays", fn, h);
+            return TC2LI_ERR_INVALID;
+        }
+        const int n = o->last_kp_cnt[2 * Hy.frame_index];
+        if (n > capacity) { set_error("%s: capacity %d < %d keypoints", fn, capacity, n); return TC2LI_ERR_CAPACITY; }
+        if (n > kMaxMatchKeys) { set_error("%s: frame has %d keypoints, the matcher supports %d", fn, n, kMaxMatchKeys); return TC2LI_ERR_CAPACITY; }
+        for (int i = 0; i < n; ++i)
+            if (Hy.inlier[i] && (Hy.match[i] < -1 || Hy.match[i] >= Hy.n_points)) {
+                set_error("%s: hypothesis %d: match[%d] = %d is no keypoint of the keyframe (%d)", fn, h, i, Hy.match[i], Hy.n_points);
+                return TC2LI_ERR_INVALID;
+            }
+        nq += Hy.n_points;
+    }
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : private_stream();
+    LadderWs& w = lws();
+    const size_t nh = n_hyps, cap1 = std::max(capacity, 1), q1 = std::max<size_t>(nq, 1), ne = nh * cap1, nfr = std::max(n_frames, 1);
+    const int total_q = (int)nq;
+    const size_t o_hp = 0, o_Xw = up256(o_hp + q1), o_pd = up256(o_Xw + 12 * q1), o_min = up256(o_pd + 32 * q1), o_max = up256(o_min + 4 * q1),
+                 o_raw = up256(o_max + 4 * q1), o_pang = up256(o_raw + 4 * q1), o_match = up256(o_pang + 4 * q1), o_inl = up256(o_match + 4 * ne),
+                 o_ur = up256(o_inl + ne), o_neg = up256(o_ur + 4 * nfr * cap1), o_frames = up256(o_neg + 4 * cap1),
+                 o_bounds = up256(o_frames + sizeof(TrackFrameDev) * nh), o_mframes = up256(o_bounds + 16 * nh),
+                 o_kbase = up256(o_mframes + sizeof(MatchFrameDev) * nh), o_foh = up256(o_kbase + 4 * nh), bytes = up256(o_foh + 4 * nh);
+    TC2LI_HIP_CHECK(w.h_stage.ensure(bytes)); TC2LI_HIP_CHECK(w.d_stage.ensure(bytes));
+    TC2LI_HIP_CHECK(w.d_frames.ensure(nh)); TC2LI_HIP_CHECK(w.d_queries.ensure(q1));
+    const int pool_cap = 32 * (int)q1;
+    // int32: query_frame, match, prev, cand_off, cand_cnt, amb_ids, amb_level [q1]; rounds, n_matches, active, status, n_good, inliers [nh];
+    // n_additional [nh][2]; cell_start [nh][cells + 1]; pool_top [2]; amb_count [2]; assign, edge_kp [nh][capacity]
+    TC2LI_HIP_CHECK(w.d_i32.ensure(7 * q1 + 8 * nh + nh * kCellsPlus1 + 4 + 2 * ne));
+    TC2LI_HIP_CHECK(w.d_f32.ensure(2 * q1));
+    TC2LI_HIP_CHECK(w.d_u8.ensure(q1 + 3 * ne));  // found [q1]; occupied, outlier_of_key, outlier [nh][capacity]
+    TC2LI_HIP_CHECK(w.d_items.ensure(ne)); TC2LI_HIP_CHECK(w.d_pool.ensure(pool_cap));
+    TC2LI_HIP_CHECK(w.d_probs.ensure(nh)); TC2LI_HIP_CHECK(w.d_edges.ensure(ne));
+    TC2LI_HIP_CHECK(w.d_f64.ensure(3 * ne + 7 * nh + 21 * nh + ne));  // Xw, poses, stage_poses, chi2
+    TC2LI_HIP_CHECK(w.h_small.ensure(4 + q1)); TC2LI_HIP_CHECK(w.h_ratio.ensure(q1));
+    uint8_t* h = w.h_stage.p;
+    uint8_t* d = w.d_stage.p;
+    memset(h + o_match, 0xff, 4 * ne);
+    memset(h + o_inl, 0, ne);
+    memcpy(h + o_ur, u_right, 4 * (size_t)n_frames * capacity);
+    for (size_t i = 0; i < cap1; ++i) reinterpret_cast<float*>(h + o_neg)[i] = -1.0f;  // the overload has no stereo test
+    TrackFrameDev* hf = reinterpret_cast<TrackFrameDev*>(h + o_frames);
+    MatchFrameDev* hm = reinterpret_cast<MatchFrameDev*>(h + o_mframes);
+    uint8_t* d_u8 = w.d_u8.p;
+    uint8_t *d_found = d_u8, *d_occ = d_u8 + q1, *d_outl_key = d_occ + ne, *d_outl = d_outl_key + ne;
+    size_t q = 0;
+    for (int k = 0; k < n_hyps; ++k) {
+        const tc2li_reloc_hypothesis& Hy = hyps[k];
+        const int n = o->last_kp_cnt[2 * Hy.frame_index], key_off = o->last_kp_off[2 * Hy.frame_index];
+        for (int i = 0; i < Hy.n_points; ++i) h[o_hp + q + i] = Hy.has_point[i] ? 1 : 0;
+        if (Hy.n_points) {
+            memcpy(h + o_Xw + 12 * q, Hy.Xw, 12 * (size_t)Hy.n_points);
+            memcpy(h + o_pd + 32 * q, Hy.point_descriptors, 32 * (size_t)Hy.n_points);
+            memcpy(h + o_min + 4 * q, Hy.min_distance, 4 * (size_t)Hy.n_points);
+            memcpy(h + o_max + 4 * q, Hy.max_distance, 4 * (size_t)Hy.n_points);
+            memcpy(h + o_raw + 4 * q, Hy.max_distance_raw, 4 * (size_t)Hy.n_points);
+            memcpy(h + o_pang + 4 * q, Hy.angle, 4 * (size_t)Hy.n_points);
+        }
+        memcpy(h + o_match + 4 * (size_t)k * cap1, Hy.match, 4 * (size_t)n);
+        for (int i = 0; i < n; ++i) h[o_inl + (size_t)k * cap1 + i] = Hy.inlier[i] ? 1 : 0;
+        TrackFrameDev& F = hf[k];
+        memset(&F, 0, sizeof(F));
+        memcpy(F.pose7, Hy.pose7, 7 * sizeof(float));
+        F.th = 10.0f; F.q_off = (int32_t)q; F.n_q = Hy.n_points; F.key_off = key_off; F.n_keys = n; F.slot = -1;
+        const float B[4] = {0.0f, (float)o->cur_w, 0.0f, (float)o->cur_h};
+        memcpy(h + o_bounds + 16 * (size_t)k, B, 16);
+        hm[k] = MatchFrameDev{o->d_mkeys.p + key_off, o->d_desc.p + (size_t)key_off * 32, reinterpret_cast<const float*>(d + o_neg), d_occ + (size_t)k * cap1,
+                              w.d_queries.p + q, n, Hy.n_points, (int32_t)q, 0, B[0], B[1], B[2], B[3]};
+        reinterpret_cast<int32_t*>(h + o_kbase)[k] = (int32_t)(k * cap1);
+        reinterpret_cast<int32_t*>(h + o_foh)[k] = Hy.frame_index;
+        q += Hy.n_points;
+    }
+    TrackConst C;
+    memset(&C, 0, sizeof(C));
+    C.cam4[0] = (float)cam->fx; C.cam4[1] = (float)cam->fy; C.cam4[2] = (float)cam->cx; C.cam4[3] = (float)cam->cy;
+    C.n_levels = n_levels; C.capacity = capacity;
+    C.log_scale = std::log(o->prm.scale_factor);  // mfLogScaleFactor = log(mfScaleFactor) (SF/src/Frame.cc:96)
+    for (int l = 0; l < n_levels; ++l) C.scale[l] = o->scale[l];
+    TC2LI_HIP_CHECK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_frames.p, hf, nh * sizeof(TrackFrameDev), hipMemcpyHostToDevice, st));
+    int32_t* ip = w.d_i32.p;
+    int32_t *d_qf = ip, *d_match = ip + q1, *d_prev = ip + 2 * q1, *d_coff = ip + 3 * q1, *d_ccnt = ip + 4 * q1, *d_amb_ids = ip + 5 * q1,
+            *d_amb_level = ip + 6 * q1, *d_rounds = ip + 7 * q1, *d_nm = d_rounds + nh, *d_active = d_nm + nh, *d_status = d_active + nh,
+            *d_ngood = d_status + nh, *d_inl = d_ngood + nh, *d_nadd = d_inl + nh, *d_cells = d_nadd + 2 * nh, *d_top = d_cells + nh * kCellsPlus1,
+            *d_amb = d_top + 2, *d_assign = d_amb + 2, *d_edge_kp = d_assign + ne;
+    float *d_amb_ratio = w.d_f32.p, *d_amb_r = w.d_f32.p + q1;
+    double *d_Xw = w.d_f64.p, *d_poses = d_Xw + 3 * ne, *d_stage_poses = d_poses + 7 * nh, *d_chi2 = d_stage_poses + 21 * nh;
+    const KeyframePointArrays A{d + o_hp, d_found, reinterpret_cast<const float*>(d + o_Xw), d + o_pd, reinterpret_cast<const float*>(d + o_min),
+                                reinterpret_cast<const float*>(d + o_max), reinterpret_cast<const float*>(d + o_raw), reinterpret_cast<const float*>(d + o_pang)};
+    RelocLadder L{};
+    L.n_hyps = n_hyps; L.capacity = (int)cap1; L.frames = w.d_frames.p; L.frame_of_hyp = reinterpret_cast<const int32_t*>(d + o_foh);
+    L.keys = o->d_mkeys.p; L.u_right = reinterpret_cast<const float*>(d + o_ur);
+    for (int l = 0; l < n_levels; ++l) L.inv_sigma2[l] = o->inv_sigma2[l];
+    L.kf_Xw = A.Xw; L.in_match = reinterpret_cast<const int32_t*>(d + o_match); L.in_inlier = d + o_inl;
+    L.found = d_found; L.occupied = d_occ; L.assign = d_assign; L.outlier_of_key = d_outl_key; L.n_matches = d_nm; L.active = d_active;
+    L.status = d_status; L.n_good = d_ngood; L.n_additional = d_nadd; L.stage_poses = d_stage_poses;
+    L.probs = w.d_probs.p; L.edges = w.d_edges.p; L.Xw = d_Xw; L.edge_kp = d_edge_kp; L.poses = d_poses; L.outlier = d_outl; L.inliers = d_inl;
+    CameraD cd;
+    memcpy(&cd, cam, sizeof(cd));
+    const MatchFrameDev* d_mframes = reinterpret_cast<const MatchFrameDev*>(d + o_mframes);
+    const MatchLists ML{d_cells, w.d_items.p, reinterpret_cast<const int32_t*>(d + o_kbase), d_coff, d_ccnt, w.d_pool.p, d_top, pool_cap, 0};
+    // ORBmatcher matcher2(0.9, true).SearchByProjection(mCurrentFrame, pKF, sFound, th, orb_dist) for the hypotheses k_reloc_ladder_after chose
+    auto search = [&](int orb_dist) -> int {
+        if (total_q == 0) return TC2LI_OK;
+        TC2LI_HIP_CHECK(hipMemsetAsync(d_amb, 0, sizeof(int32_t), st));
+        launch_track_queries_keyframe(w.d_frames.p, n_hyps, reinterpret_cast<const float4*>(d + o_bounds), C, A, total_q, w.d_queries.p, d_qf, d_match, d_amb,
+                                      d_amb_ids, d_amb_ratio, d_amb_r, st);
+        TC2LI_HIP_CHECK(hipGetLastError());
+        TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_small.p, d_amb, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TC2LI_HIP_CHECK(stream_wait_blocking(st));
+        const int n_amb = w.h_small.p[0];
+        if (n_amb > 0) {  // MapPoint::PredictScale on a level boundary: the host's logf decides
+            TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_ratio.p, d_amb_ratio, n_amb * sizeof(float), hipMemcpyDeviceToHost, st));
+            TC2LI_HIP_CHECK(stream_wait_blocking(st));
+            int32_t* lev = w.h_small.p + 4;
+            for (int k = 0; k < n_amb; ++k) {
+                int level = (int)ceilf(logf(w.h_ratio.p[k]) / C.log_scale);
+                if (level < 0) level = 0; else if (level >= n_levels) level = n_levels - 1;
+                lev[k] = level;
+            }
+            TC2LI_HIP_CHECK(hipMemcpyAsync(d_amb_level, lev, n_amb * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            launch_track_patch_levels_keyframe(d_amb_ids, d_amb_level, d_amb_r, n_amb, C, w.d_queries.p, st);
+        }
+        launch_match_lists(d_mframes, n_hyps, d_qf, total_q, ML, 0, 0.0f, d_match, d_prev, d_rounds, st, orb_dist);
+        TC2LI_HIP_CHECK(hipGetLastError());
+        TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_small.p, d_top, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TC2LI_HIP_CHECK(stream_wait_blocking(st));
+        if (w.h_small.p[1]) {  // candidate pool exhausted: the one-kernel form, same result
+            TC2LI_HIP_CHECK(hipMemsetAsync(d_match, 0xff, q1 * sizeof(int32_t), st));
+            launch_match_by_projection(d_mframes, n_hyps, 0, 0.0f, d_match, d_prev, d_rounds, st, orb_dist);
+        }
+        launch_track_count(w.d_frames.p, nullptr, n_hyps, w.d_queries.p, o->d_angles.p, 1, d_match, d_nm, st);
+        launch_track_assign_keyframe(w.d_frames.p, n_hyps, (int)cap1, total_q, d_match, d_assign, st);
+        TC2LI_HIP_CHECK(hipGetLastError());
+        return TC2LI_OK;
+    };
+    launch_reloc_ladder_init(L, st);
+    for (int stage = 0; stage < 3; ++stage) {
+        launch_reloc_ladder_edges(L, stage, st);
+        launch_pose_optimization(w.d_probs.p, n_hyps, d_Xw, w.d_edges.p, cd, d_poses, d_outl, d_chi2, d_inl, (int)cap1, st);
+        launch_reloc_ladder_after(L, stage, st);
+        TC2LI_HIP_CHECK(hipGetLastError());
+        if (stage < 2) { if (int rc = search(stage == 0 ? 100 : 64)) return rc; }
+    }
+    TC2LI_HIP_CHECK(hipMemcpyAsync(status, d_status, nh * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(n_good, d_ngood, nh * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(n_additional, d_nadd, 2 * nh * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(poses7, d_stage_poses, 21 * nh * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (capacity > 0) {
+        TC2LI_HIP_CHECK(hipMemcpyAsync(kf_keypoint_of_keypoint, d_assign, ne * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TC2LI_HIP_CHECK(hipMemcpyAsync(outlier, d_outl_key, ne, hipMemcpyDeviceToHost, st));
+    }
+    TC2LI_HIP_CHECK(stream_wait_blocking(st));
+    return n_hyps;
+}

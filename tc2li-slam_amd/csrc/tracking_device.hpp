@@ -39,6 +39,18 @@ struct LastFrameArrays {
     const uint8_t* desc;   // [32] each
 };
 
+// The candidate keyframes' keypoints of all frames, packed (query-indexed): ORBmatcher::SearchByProjection(Frame&, KeyFrame*, ...).
+struct KeyframePointArrays {
+    const uint8_t* has_point;   // pMP && !pMP->isBad()
+    const uint8_t* found;       // sAlreadyFound.count(pMP)
+    const float* Xw;            // [3] each
+    const uint8_t* desc;        // [32] each: pMP->GetDescriptor()
+    const float* min_distance;  // GetMinDistanceInvariance()
+    const float* max_distance;  // GetMaxDistanceInvariance()
+    const float* max_distance_raw;  // mfMaxDistance (PredictScale)
+    const float* angle;         // pKF->mvKeysUn[i].angle
+};
+
 // tc2li_map_point, 68 bytes
 struct LocalPointDev {
     float pos[3], normal[3];
@@ -54,6 +66,13 @@ void launch_track_queries_last(const TrackFrameDev* frames, int n_frames, const 
 void launch_track_queries_local(const TrackFrameDev* frames, int n_frames, const TrackConst& C, const LocalPointDev* points, int total_q, MatchQuery* queries,
                                 int32_t* query_frame, int32_t* match, int32_t* amb_count, int32_t* amb_ids, float* amb_ratio, float* amb_r, hipStream_t st);
 void launch_track_patch_levels(const int32_t* ids, const int32_t* levels, const float* r, int n, const TrackConst& C, MatchQuery* queries, hipStream_t st);
+// the keyframe overload: bounds[f] = mnMinX, mnMaxX, mnMinY, mnMaxY of frame f; the ambiguity lists as above (amb_r holds th); the patch
+// of the listed queries; of_key[f * capacity + matched keypoint] = the keyframe keypoint of every match left after the rotation filter
+void launch_track_queries_keyframe(const TrackFrameDev* frames, int n_frames, const float4* bounds, const TrackConst& C, const KeyframePointArrays& A, int total_q,
+                                   MatchQuery* queries, int32_t* query_frame, int32_t* match, int32_t* amb_count, int32_t* amb_ids, float* amb_ratio, float* amb_r,
+                                   hipStream_t st);
+void launch_track_patch_levels_keyframe(const int32_t* ids, const int32_t* levels, const float* r, int n, const TrackConst& C, MatchQuery* queries, hipStream_t st);
+void launch_track_assign_keyframe(const TrackFrameDev* frames, int n_frames, int capacity, int total_q, const int32_t* match, int32_t* of_key, hipStream_t st);
 void launch_track_occupied(const uint8_t* held, size_t n, uint8_t* occ, hipStream_t st);
 // per frame of the pass: rotation histogram filter (check_orientation) and the number of matches
 void launch_track_count(const TrackFrameDev* frames, const int32_t* pass_frames, int n_pass, const MatchQuery* queries, const float* key_angles,

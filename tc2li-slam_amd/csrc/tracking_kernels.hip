@@ -2,6 +2,7 @@
 //   * query construction of the two ORBmatcher::SearchByProjection overloads the tracking thread uses -- the last-frame overload
 //     (SF/src/ORBmatcher.cc:1696-1739) and the local-map overload with Frame::isInFrustum + MapPoint::PredictScale
 //     (SF/src/Frame.cc:542-603, ORBmatcher.cc:62-81) -- one lane per source point, float arithmetic in the reference's order;
+//     and the keyframe overload of relocalisation (ORBmatcher.cc:1898-1952);
 //   * the rotation-consistency filter of the last-frame overload (:1783-1799, 1858-1881, ComputeThreeMaxima :2021-2062);
 //   * mvpMapPoints of the current frame and the edge list of Optimizer::PoseOptimization (SF/src/Optimizer.cc:858-990) in keypoint
 //     order, and what the callers do with its result (Tracking.cc:2798-2822, 3192-3227).
@@ -190,6 +191,94 @@ __global__ __launch_bounds__(256) void k_track_queries_local(const TrackFrameDev
         for (int k = 0; k < 8; ++k) reinterpret_cast<uint32_t*>(Q.desc)[k] = d[k];
     }
     store_query(queries + g, Q);
+}
+
+// ---- ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (SF/src/ORBmatcher.cc:1898-1952): one query per
+// keyframe keypoint.  No viewing-cosine test and no depth-sign test; the distance gate uses dist3D = |Xw - Ow|; the window is
+// th * mvScaleFactors[level] over the levels level - 1 .. level + 1, handed to GetFeaturesInArea unclamped; the descriptor is the map
+// point's.  PredictScale as in k_track_queries_local (the host's logf decides the listed ones).
+__global__ __launch_bounds__(256) void k_track_queries_keyframe(const TrackFrameDev* __restrict__ frames, int n_frames, const float4* __restrict__ bounds,
+                                                                TrackConst C, KeyframePointArrays A, int total_q, MatchQuery* __restrict__ queries,
+                                                                int32_t* __restrict__ query_frame, int32_t* __restrict__ match, int32_t* __restrict__ amb_count,
+                                                                int32_t* __restrict__ amb_ids, float* __restrict__ amb_ratio, float* __restrict__ amb_r) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= total_q) return;
+    const int f = frame_of_query(frames, n_frames, g);
+    if (f < 0 || g >= frames[f].q_off + frames[f].n_q) return;
+    const TrackFrameDev& F = frames[f];
+    if (F.slot < 0) { query_frame[g] = -1; return; }
+    query_frame[g] = F.slot;
+    match[g] = -1;
+    MatchQuery Q;
+    Q.u = 0; Q.v = 0; Q.radius = 0; Q.u_right = -1; Q.min_level = -1; Q.max_level = -1; Q.angle = 0; Q.valid = 0; Q.has_observations = 1;
+#pragma unroll
+    for (int k = 0; k < 32; ++k) Q.desc[k] = 0;
+    bool ok = A.has_point[g] && !A.found[g];  // pMP && !pMP->isBad() && !sAlreadyFound.count(pMP)
+    if (ok) {
+        const float* q = F.pose7;
+        const float X[3] = {A.Xw[3 * (size_t)g], A.Xw[3 * (size_t)g + 1], A.Xw[3 * (size_t)g + 2]};
+        float pc[3];
+        quat_rotate_f(q, X, pc);  // Tcw * x3Dw
+        pc[0] += q[4]; pc[1] += q[5]; pc[2] += q[6];
+        const float u = C.cam4[0] * pc[0] / pc[2] + C.cam4[2], v = C.cam4[1] * pc[1] / pc[2] + C.cam4[3];
+        const float4 B = bounds[f];  // mnMinX, mnMaxX, mnMinY, mnMaxY
+        if (u < B.x || u > B.y) ok = false;
+        if (v < B.z || v > B.w) ok = false;
+        float Ow[3];
+        {  // Tcw.inverse().translation()
+            const float qi[4] = {-q[0], -q[1], -q[2], q[3]};
+            const float nt[3] = {q[4] * -1.f, q[5] * -1.f, q[6] * -1.f};
+            quat_rotate_f(qi, nt, Ow);
+        }
+        const float po[3] = {X[0] - Ow[0], X[1] - Ow[1], X[2] - Ow[2]};
+        const float dist = sqrtf((po[0] * po[0] + po[1] * po[1]) + po[2] * po[2]);
+        if (dist < A.min_distance[g] || dist > A.max_distance[g]) ok = false;
+        if (ok) {
+            const float ratio = A.max_distance_raw[g] / dist;
+            const double quot = log((double)ratio) / (double)C.log_scale;
+            int level = 0;
+            const double nearest = rint(quot);
+            if (!(fabs(quot) < 1e6) || fabs(quot - nearest) <= 4.8e-7 * fmax(1.0, fabs(quot))) {
+                const int at = atomicAdd(amb_count, 1);
+                amb_ids[at] = g; amb_ratio[at] = ratio; amb_r[at] = F.th;
+            } else {
+                level = (int)ceil(quot);
+                if (level < 0) level = 0; else if (level >= C.n_levels) level = C.n_levels - 1;
+            }
+            Q.u = u; Q.v = v;
+            Q.radius = F.th * C.scale[level];
+            Q.min_level = level - 1; Q.max_level = level + 1;
+            Q.angle = A.angle[g];
+            Q.valid = 1;
+            const uint4* d = reinterpret_cast<const uint4*>(A.desc + 32 * (size_t)g);
+            const uint4 d0 = d[0], d1 = d[1];
+            *reinterpret_cast<uint4*>(Q.desc) = d0;
+            *reinterpret_cast<uint4*>(Q.desc + 16) = d1;
+        }
+    }
+    store_query(queries + g, Q);
+}
+
+// level (from the host's logf) and window of the listed queries of the keyframe overload
+__global__ __launch_bounds__(256) void k_track_patch_levels_keyframe(const int32_t* __restrict__ ids, const int32_t* __restrict__ levels, const float* __restrict__ r,
+                                                                     int n, TrackConst C, MatchQuery* __restrict__ queries) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    MatchQuery& Q = queries[ids[k]];
+    const int level = levels[k];
+    Q.radius = r[k] * C.scale[level];
+    Q.min_level = level - 1; Q.max_level = level + 1;
+}
+
+// CurrentFrame.mvpMapPoints[bestIdx2] = pMP of the matches that are left: of_key[f * capacity + keypoint] = the keyframe keypoint
+__global__ __launch_bounds__(256) void k_track_assign_keyframe(const TrackFrameDev* __restrict__ frames, int n_frames, int capacity, int total_q,
+                                                               const int32_t* __restrict__ match, int32_t* __restrict__ of_key) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= total_q) return;
+    const int f = frame_of_query(frames, n_frames, g);
+    if (f < 0 || g >= frames[f].q_off + frames[f].n_q || frames[f].slot < 0) return;
+    const int m = match[g];
+    if (m >= 0 && m < capacity) of_key[(size_t)f * capacity + m] = g - frames[f].q_off;
 }
 
 // level (from the host's logf) and window of the listed queries
@@ -390,6 +479,19 @@ void launch_track_queries_local(const TrackFrameDev* frames, int n_frames, const
 }
 void launch_track_patch_levels(const int32_t* ids, const int32_t* levels, const float* r, int n, const TrackConst& C, MatchQuery* queries, hipStream_t st) {
     if (n > 0) TC2LI_LAUNCH(k_track_patch_levels, dim3((n + 255) / 256), dim3(256), 0, st, ids, levels, r, n, C, queries);
+}
+void launch_track_queries_keyframe(const TrackFrameDev* frames, int n_frames, const float4* bounds, const TrackConst& C, const KeyframePointArrays& A, int total_q,
+                                   MatchQuery* queries, int32_t* query_frame, int32_t* match, int32_t* amb_count, int32_t* amb_ids, float* amb_ratio, float* amb_r,
+                                   hipStream_t st) {
+    if (total_q > 0)
+        TC2LI_LAUNCH(k_track_queries_keyframe, dim3((total_q + 255) / 256), dim3(256), 0, st, frames, n_frames, bounds, C, A, total_q, queries, query_frame, match,
+                     amb_count, amb_ids, amb_ratio, amb_r);
+}
+void launch_track_patch_levels_keyframe(const int32_t* ids, const int32_t* levels, const float* r, int n, const TrackConst& C, MatchQuery* queries, hipStream_t st) {
+    if (n > 0) TC2LI_LAUNCH(k_track_patch_levels_keyframe, dim3((n + 255) / 256), dim3(256), 0, st, ids, levels, r, n, C, queries);
+}
+void launch_track_assign_keyframe(const TrackFrameDev* frames, int n_frames, int capacity, int total_q, const int32_t* match, int32_t* of_key, hipStream_t st) {
+    if (total_q > 0) TC2LI_LAUNCH(k_track_assign_keyframe, dim3((total_q + 255) / 256), dim3(256), 0, st, frames, n_frames, capacity, total_q, match, of_key);
 }
 void launch_track_occupied(const uint8_t* held, size_t n, uint8_t* occ, hipStream_t st) {
     if (n > 0) TC2LI_LAUNCH(k_track_occupied, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, held, n, occ);
