@@ -1308,6 +1308,63 @@ int tc2li_relocalization_refine_batch(tc2li_orb* orb, const tc2li_reloc_hypothes
                                       int capacity, const tc2li_camera* cam, int32_t* status, int32_t* n_good, int32_t* n_additional,
                                       double* poses7, int32_t* kf_keypoint_of_keypoint, uint8_t* outlier, void* stream);
 
+/* ---- MLPnP RANSAC: the PnP stage of Tracking::Relocalization (SF/src/MLPnPsolver.cpp, SF/include/MLPnPsolver.h) -------------------------
+ * The solver is a function of its inputs once the caller hands in the rand() values it would have drawn: DUtils::Random::RandomInt
+ * (Thirdparty/DBoW2/DUtils/Random.cpp:47-50) is a pure function of rand()'s return value. */
+/* SetRansacParameters' arguments (MLPnPsolver.cpp:205; (0.99, 10, 300, 6, 0.5, 5.991) at SF/src/Tracking.cc:3526).  min_set must be 6. */
+typedef struct tc2li_mlpnp_params {
+    double probability;
+    int32_t min_inliers, max_iterations, min_set;
+    float epsilon, th2;
+    int32_t pad_;
+} tc2li_mlpnp_params;
+/* What a solver carries from one iterate() call to the next, besides the best flags: mnIterations, mnBestInliers, mBestTcw (rows 0-2,
+ * row-major 3 x 4).  All zero = a fresh solver. */
+typedef struct tc2li_mlpnp_state {
+    int32_t iterations, best_inliers;
+    float best_Tcw[12];
+} tc2li_mlpnp_state;
+/* One solver and one iterate() call on it.  The constructor (MLPnPsolver.cpp:35-77) takes keypoint i when match[i] >= 0: mvP2D = (x, y),
+ * mvSigma2 = level_sigma2[octave], bearing = ((x - cx) / fx, (y - cy) / fy, 1) in float (not of unit length), mvP3Dw = Xw[match[i]]
+ * widened, mvKeyPointIndices = i.  All pointers are host memory. */
+typedef struct tc2li_mlpnp_problem {
+    const tc2li_keypoint* keys;        /* mvKeysUn of the frame */
+    const int32_t* match;              /* [n_keypoints] index into Xw or -1: vpMapPointMatches with bad points already removed */
+    const float* Xw;                   /* [n_points][3] */
+    const uint32_t* draws;             /* rand() return values, 6 per iteration (:110), consumed in order */
+    tc2li_mlpnp_state* state;          /* in / out */
+    uint8_t* best_inlier;              /* in / out [n_keypoints]: mvbBestInliers per frame keypoint; zeros for a fresh solver */
+    int32_t n_keypoints, n_points, n_draws;
+    int32_t n_iterations;              /* iterate()'s argument: 5 at Tracking.cc:3552 */
+} tc2li_mlpnp_problem;
+/* SetRansacParameters (:205-240) for N correspondences: min_inliers = max(int(N * epsilon), min_inliers, min_set), epsilon raised to
+ * (float)min_inliers / N, max_iterations = clamp(ceil(log(1 - p) / log(1 - pow(epsilon, 3))), 1, max_iterations), 1 when min_inliers == N.
+ * Host arithmetic (libm).  Returns 0. */
+int tc2li_mlpnp_iterations(int n_correspondences, const tc2li_mlpnp_params* params, int32_t* min_inliers, int32_t* max_iterations);
+/* One MLPnPsolver::iterate(n_iterations, ..) call (:80-203) per problem, all problems at once on the device.  Kept as written:
+ *   N < min_inliers: no_more, not found (:86-90).  The loop runs while state.iterations < max_iterations OR fewer than n_iterations
+ *   passes were made (:95), so a fresh solver runs up to max(max_iterations, n_iterations) iterations in its first call.  Each draws six
+ *   correspondences without replacement (:108-120), computePose (:336-638: null spaces, planar test on the uncentred second moment,
+ *   the eigenvector of A^T A, nearest rotation, direction test, rot2rodrigues, at most 5 Gauss-Newton steps), CheckInliers (:242-273,
+ *   mixed float / double).  A count >= min_inliers that beats the best replaces it (:149-167).  Refine() (:275-333) throws its N-point
+ *   solve away and re-tests the iteration's own pose, so an iteration whose count is > min_inliers returns with its own pose and flags.
+ *   When the loop ends with state.iterations >= max_iterations: no_more, and the best is returned if it reaches min_inliers (:185-200).
+ * A call that may run K = max(max_iterations - state.iterations, n_iterations) iterations needs 6 K draws; unused draws are not consumed
+ * (an early return after j iterations has used the first 6 j: the caller keeps the rest for the next call to stay on the reference's
+ * sequence).  TC2LI_ERR_INVALID before any launch for min_set != 6, too few draws, a draw above RAND_MAX = 2^31 - 1, a match outside
+ * [-1, n_points), an octave outside [0, n_levels); TC2LI_ERR_CAPACITY for n_keypoints > capacity.
+ * Out per problem: found (the return value), no_more (bNoMore), n_inliers, inlier [capacity] per frame keypoint (vbInliers, zeros
+ * beyond), pose7 = Tcw as qx qy qz qw tx ty tz in float -- what tc2li_reloc_hypothesis.pose7 takes --, identity when not found (:81);
+ * Rt12 (may be NULL) the double [R | t] row-major 3 x 4 the pose was rounded from (the widened mBestTcw when the best of an earlier
+ * call is returned).  state and best_inlier are updated.  found, no_more, n_inliers may be NULL.  Returns n_problems. */
+int tc2li_mlpnp_ransac_batch(const tc2li_mlpnp_problem* problems, int n_problems, const tc2li_mlpnp_params* params,
+                             const float* level_sigma2, int n_levels, const tc2li_camera* cam, int32_t* found, int32_t* no_more,
+                             int32_t* n_inliers, float* pose7, double* Rt12, uint8_t* inlier, int capacity, void* stream);
+/* The same arithmetic on the CPU (the kernels and this entry share mlpnp_math.hpp); needs no device. */
+int tc2li_host_mlpnp_ransac_batch(const tc2li_mlpnp_problem* problems, int n_problems, const tc2li_mlpnp_params* params,
+                                  const float* level_sigma2, int n_levels, const tc2li_camera* cam, int32_t* found, int32_t* no_more,
+                                  int32_t* n_inliers, float* pose7, double* Rt12, uint8_t* inlier, int capacity);
+
 #ifdef __cplusplus
 }
 #endif

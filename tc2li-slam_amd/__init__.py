@@ -42,4 +42,7 @@ from .capi import (  # noqa: F401
     detect_relocalization_candidates_batch,
     search_by_projection_keyframe_batch,
     relocalization_refine_batch,
+    mlpnp_iterations,
+    mlpnp_params,
+    mlpnp_ransac_batch,
 )

@@ -2300,3 +2300,88 @@ def relocalization_refine_batch(ext, hyps, u_right, cam5, stream=0):
              C.c_void_p(stream)))
     del keep
     return {k: v[:H] for k, v in out.items()}
+
+
+class MlpnpParams(C.Structure):
+    """tc2li_mlpnp_params; the defaults are SetRansacParameters(0.99, 10, 300, 6, 0.5, 5.991) of Tracking.cc:3526"""
+    _fields_ = [("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("min_set", C.c_int32),
+                ("epsilon", C.c_float), ("th2", C.c_float), ("pad_", C.c_int32)]
+
+
+class MlpnpState(C.Structure):
+    """tc2li_mlpnp_state"""
+    _fields_ = [("iterations", C.c_int32), ("best_inliers", C.c_int32), ("best_Tcw", C.c_float * 12)]
+
+
+class MlpnpProblem(C.Structure):
+    """tc2li_mlpnp_problem"""
+    _fields_ = [("keys", C.c_void_p), ("match", C.c_void_p), ("Xw", C.c_void_p), ("draws", C.c_void_p), ("state", C.c_void_p),
+                ("best_inlier", C.c_void_p), ("n_keypoints", C.c_int32), ("n_points", C.c_int32), ("n_draws", C.c_int32),
+                ("n_iterations", C.c_int32)]
+
+
+def mlpnp_params(probability=0.99, min_inliers=10, max_iterations=300, min_set=6, epsilon=0.5, th2=5.991):
+    return MlpnpParams(float(probability), int(min_inliers), int(max_iterations), int(min_set), float(epsilon), float(th2), 0)
+
+
+def mlpnp_iterations(n_correspondences, params=None):
+    """``MLPnPsolver::SetRansacParameters`` for N correspondences -> (min_inliers, max_iterations)."""
+    params = params or mlpnp_params()
+    a, b = C.c_int32(0), C.c_int32(0)
+    f = lib().tc2li_mlpnp_iterations
+    f.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(f(int(n_correspondences), C.addressof(params), C.addressof(a), C.addressof(b)))
+    return a.value, b.value
+
+
+def mlpnp_ransac_batch(problems, level_sigma2, cam5, params=None, capacity=None, host=False, stream=0):
+    """One ``MLPnPsolver::iterate`` call per problem.  problems: dicts with keys (KEYPOINT_DTYPE), match [n_keypoints] (index into Xw or
+    -1), Xw [n_points, 3], draws (rand() values, 6 per iteration), n_iterations (default 5) and optionally the solver's state from an
+    earlier call: iterations, best_inliers, best_Tcw [12], best_inlier [n_keypoints].  -> dict(found, no_more, n_inliers, pose7 [P, 7],
+    Rt12 [P, 12], inlier [P, capacity], iterations, best_inliers, best_Tcw [P, 12], best_inlier [P, capacity]); the last four are the
+    state to hand to the next call.  host=True runs the same arithmetic on the CPU."""
+    params = params or mlpnp_params()
+    level_sigma2 = np.ascontiguousarray(level_sigma2, np.float32)
+    cam5 = np.ascontiguousarray(cam5, np.float64)
+    P = len(problems)
+    if capacity is None:
+        capacity = max([len(p["keys"]) for p in problems] + [1])
+    arr, states, keep = (MlpnpProblem * max(P, 1))(), (MlpnpState * max(P, 1))(), []
+    n1 = max(P, 1)
+    best = np.zeros((n1, capacity), np.uint8)
+    for i, p in enumerate(problems):
+        keys = np.ascontiguousarray(p["keys"], KEYPOINT_DTYPE)
+        match = np.ascontiguousarray(p["match"], np.int32)
+        xw = np.ascontiguousarray(p["Xw"], np.float32).reshape(-1, 3)
+        draws = np.ascontiguousarray(p["draws"], np.uint32)
+        if len(match) != len(keys):
+            raise ValueError("problem %d: match and keys differ in length" % i)
+        keep.append((keys, match, xw, draws))
+        states[i].iterations, states[i].best_inliers = int(p.get("iterations", 0)), int(p.get("best_inliers", 0))
+        states[i].best_Tcw = (C.c_float * 12)(*[float(v) for v in p.get("best_Tcw", np.zeros(12))])
+        if "best_inlier" in p and len(keys) <= capacity:
+            best[i, :len(keys)] = np.asarray(p["best_inlier"], np.uint8)[:len(keys)]
+        arr[i].keys, arr[i].match, arr[i].Xw, arr[i].draws = keys.ctypes.data, match.ctypes.data, xw.ctypes.data, draws.ctypes.data
+        arr[i].state, arr[i].best_inlier = C.addressof(states[i]), best[i].ctypes.data
+        arr[i].n_keypoints, arr[i].n_points, arr[i].n_draws = len(keys), len(xw), len(draws)
+        arr[i].n_iterations = int(p.get("n_iterations", 5))
+    out = dict(found=np.zeros(n1, np.int32), no_more=np.zeros(n1, np.int32), n_inliers=np.zeros(n1, np.int32), pose7=np.zeros((n1, 7), np.float32),
+               Rt12=np.zeros((n1, 12)), inlier=np.zeros((n1, capacity), np.uint8))
+    args = [C.addressof(arr), P, C.addressof(params), level_sigma2.ctypes.data, len(level_sigma2), cam5.ctypes.data, out["found"].ctypes.data,
+            out["no_more"].ctypes.data, out["n_inliers"].ctypes.data, out["pose7"].ctypes.data, out["Rt12"].ctypes.data, out["inlier"].ctypes.data,
+            int(capacity)]
+    if host:
+        f = lib().tc2li_host_mlpnp_ransac_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int]
+        _check(f(*args))
+    else:
+        f = lib().tc2li_mlpnp_ransac_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p]
+        _check(f(*(args + [C.c_void_p(stream)])))
+    del keep
+    out = {k: v[:P] for k, v in out.items()}
+    out["iterations"] = np.array([states[i].iterations for i in range(P)], np.int32)
+    out["best_inliers"] = np.array([states[i].best_inliers for i in range(P)], np.int32)
+    out["best_Tcw"] = np.array([list(states[i].best_Tcw) for i in range(P)], np.float32).reshape(P, 12)
+    out["best_inlier"] = best[:P]
+    return out
