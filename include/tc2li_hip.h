@@ -1365,6 +1365,112 @@ int tc2li_host_mlpnp_ransac_batch(const tc2li_mlpnp_problem* problems, int n_pro
                                   const float* level_sigma2, int n_levels, const tc2li_camera* cam, int32_t* found, int32_t* no_more,
                                   int32_t* n_inliers, float* pose7, double* Rt12, uint8_t* inlier, int capacity);
 
+/* ---- local mapping: culling (SF/src/LocalMapping.cc:360-399 MapPointCulling, :913-1065 KeyFrameCulling) -----------------------------------
+ * The two culling stages of LocalMapping::Run on the flat graph (matches per keyframe, observations per point).  The library returns the
+ * decisions; the caller applies them to its own objects in list order (INTEGRATION.md "KeyFrameCulling / MapPointCulling").  Rig: pinhole
+ * stereo, NLeft == -1, mpCamera2 == nullptr; the NLeft != -1 branches of :979-1003 are not covered.  mbMonocular is false, so the
+ * redundancy threshold is 0.9f without IMU and 0.5f with (:923-929). */
+enum tc2li_cull_verdict {
+    TC2LI_CULL_SKIPPED = -1,           /* the init keyframe or a bad one (:955) */
+    TC2LI_CULL_NOT_VISITED = -2,       /* after the break of :1060 */
+    TC2LI_CULL_REDUNDANT = 1,          /* otherwise a mask: nRedundantObservations > redundant_th * nMPs (:1021) */
+    TC2LI_CULL_SET_BAD = 2,            /* SetBadFlag() was called (:1042, :1051, :1057) */
+    TC2LI_CULL_MERGED = 4,             /* MergePrevious and the relink of mPrevKF / mNextKF before it (:1037-1041, :1046-1050) */
+    TC2LI_CULL_DEFERRED = 8            /* mbNotErase: SetBadFlag only set mbToBeErased (SF/src/KeyFrame.cc:593-597), nothing was erased */
+};
+/* One call of LocalMapping::KeyFrameCulling.  All pointers are host memory, the arrays are copied by the call; indices are rows of the
+ * problem's own tables.
+ *   keyframes (n_keyframes rows, every keyframe that appears anywhere in the problem):
+ *     kf_flags  bit 0 isBad(), bit 1 mnId == GetMap()->GetInitKFid(), bit 2 mbNotErase;  kf_id mnId;  kf_prev / kf_next mPrevKF / mNextKF
+ *     (-1 = none);  kf_time mTimeStamp;  kf_imu_pos [n][3] GetImuPosition();  kf_th_depth mThDepth
+ *   slots: CSR slot_offsets [n_keyframes + 1] (keyframes outside `local` may have empty rows); slot_point mvpMapPoints[i] (-1 = NULL),
+ *     slot_depth mvDepth[i], slot_octave mvKeysUn[i].octave
+ *   local [n_local]: GetVectorCovisibleKeyFrames() after UpdateBestCovisibles() (:920-921), in that order
+ *   points (n_points rows): point_bad isBad(); point_nobs Observations() = nObs, which counts a stereo observation twice; CSR obs_offsets
+ *     [n_points + 1]; obs_kf the observing keyframe, obs_octave mvKeysUn[leftIndex].octave there, obs_weight 2 if mvuRight[leftIndex] >= 0
+ *     else 1: what MapPoint::EraseObservation subtracts (SF/src/MapPoint.cc:187-192).  THE ORDER OF A POINT'S OBSERVATIONS MATTERS TO NO
+ *     RESULT (the early break of :1008 only ends a count that has already passed the threshold).  A keyframe appears at most once in a
+ *     row (mObservations is a map); if it appears more often, every such entry is erased with it.  A bad point holds no observations
+ *     (MapPoint.cc:233): the row of a point that is bad on entry is ignored.
+ *   scalars: inertial mbInertial; imu_initialized mpAtlas->isImuInitialized(); inertial_ba2 GetIniertialBA2(); abort_ba mbAbortBA AS IT
+ *     IS WHEN THE CALL IS MADE -- the reference reads it live at :1060, where it only bounds the work after 20 keyframes; this snapshot is a
+ *     deviation --; keyframes_in_map mpAtlas->KeyFramesInMap(); current_id mpCurrentKeyFrame->mnId; last_id the last_ID of :935-946 (at
+ *     most 21 hops along mPrevKF from the current keyframe; read only when inertial).
+ * Out: verdict [n_local] (tc2li_cull_verdict), n_mps / n_redundant [n_local] nMPs and nRedundantObservations as they were when the
+ * keyframe was decided (untouched where verdict < 0), n_visited [1] the entries of local the loop reached, and optionally (may be NULL)
+ * point_bad_after / point_nobs_after [n_points]: the simulated end state of isBad() and nObs. */
+typedef struct tc2li_culling_problem {
+    const uint8_t* kf_flags;
+    const int64_t* kf_id;
+    const int32_t* kf_prev;
+    const int32_t* kf_next;
+    const double* kf_time;
+    const float* kf_imu_pos;
+    const float* kf_th_depth;
+    const int32_t* slot_offsets;
+    const int32_t* slot_point;
+    const float* slot_depth;
+    const int8_t* slot_octave;
+    const int32_t* local;
+    const uint8_t* point_bad;
+    const int32_t* point_nobs;
+    const int32_t* obs_offsets;
+    const int32_t* obs_kf;
+    const int8_t* obs_octave;
+    const uint8_t* obs_weight;
+    int32_t* verdict;
+    int32_t* n_mps;
+    int32_t* n_redundant;
+    int32_t* n_visited;
+    uint8_t* point_bad_after;
+    int32_t* point_nobs_after;
+    int64_t current_id, last_id;
+    int32_t n_keyframes, n_local, n_points, keyframes_in_map;
+    uint8_t inertial, imu_initialized, inertial_ba2, abort_ba;
+    int32_t pad_;
+} tc2li_culling_problem;
+/* LocalMapping::KeyFrameCulling (:913-1065) for n_problems independent calls (one per sequence) at once on the device, with the side
+ * effects of every cull simulated so that the later verdicts of the same call are the reference's:
+ *   walk local in order, count incremented first (:952); the init keyframe and bad keyframes are skipped (:955) -- this continue and the
+ *   inertial ones below jump over the closing test (count > 20 && abort_ba) || count > 100 (:1060), which is reached only at the end of an
+ *   iteration that did not continue.  Per slot with a non-NULL, non-bad point: dropped if depth > th_depth || depth < 0 (:972), otherwise
+ *   nMPs++; if Observations() > 3 (:977) the point's live observations in OTHER keyframes with octave <= own octave + 1 are counted
+ *   (:984-1011) and the slot is redundant iff there are more than 3.  Redundant keyframe iff (float)nRedundant > th * (float)nMPs in float
+ *   (:1021; 0 > 0 is false).  Without IMU: SetBadFlag() (:1057).  With (:1023-1054): continue if keyframes_in_map <= 21 (:1025); continue
+ *   if kf_id > current_id - 2 in unsigned 64-bit arithmetic (:1028); only if prev and next both exist: t = (float)(time[next] -
+ *   time[prev]) (:1033); merge and cull if (imu_initialized && kf_id < last_id && t < 3.) || t < 0.5 (:1035), else if !inertial_ba2 &&
+ *   |imu_pos - imu_pos[prev]| < 0.02 && t < 3 (:1044).  The norm is float, sqrtf(x*x + (y*y + z*z)) without contraction: Eigen leaves the
+ *   order of that sum to its build, THIS CHOICE DEFINES PARITY.  A merge sets next.prev = prev, prev.next = next, clears the keyframe's own
+ *   links (:1038-1041) and then calls SetBadFlag(); later keyframes see the new links.
+ *   SetBadFlag() (SF/src/KeyFrame.cc:585-691): with mbNotErase nothing is erased (the relink before it has still happened).  Otherwise the
+ *   point of every non-NULL slot drops its observation of this keyframe if it holds one (:605-611): nObs -= weight, and at nObs <= 2 the
+ *   point turns bad and loses all its observations (MapPoint.cc:177-248); a point held by two slots of the keyframe loses its observation
+ *   once.  Then the keyframe is bad and keyframes_in_map is one less (Map::EraseKeyFrame).  KeyFrame::UpdateConnections and the
+ *   spanning-tree repair of SetBadFlag stay with the caller's objects.
+ * Two kernel launches, one upload and one download for the whole batch; the results are in host memory when the call returns (stream:
+ * NULL = the calling thread's private stream).  TC2LI_ERR_INVALID before any launch for negative sizes, NULL required pointers, offsets
+ * that do not ascend from 0 and indices out of range.  Returns n_problems. */
+int tc2li_keyframe_culling_batch(const tc2li_culling_problem* problems, int n_problems, void* stream);
+/* The same contract as plain sequential C++ (one problem per worker thread); needs no device. */
+int tc2li_host_keyframe_culling_batch(const tc2li_culling_problem* problems, int n_problems);
+enum tc2li_mp_cull_action {
+    TC2LI_MP_CULL_KEEP = 0,            /* stays in mlpRecentAddedMapPoints (:393-397) */
+    TC2LI_MP_CULL_DROP_BAD = 1,        /* already bad: erased from the list (:379-380) */
+    TC2LI_MP_CULL_BAD_RATIO = 2,       /* GetFoundRatio() < 0.25f: SetBadFlag and erased (:381-385) */
+    TC2LI_MP_CULL_BAD_OBS = 3,         /* two keyframes old with Observations() <= th_obs: SetBadFlag and erased (:386-390) */
+    TC2LI_MP_CULL_DROP_AGE = 4         /* three keyframes old: erased from the list (:391-392) */
+};
+/* LocalMapping::MapPointCulling (:360-399) for n_points entries of mlpRecentAddedMapPoints, of any number of sequences (current_kf_id is
+ * per point): the first rule that holds, in the order above.  The found ratio is (float)n_found / (float)n_visible < 0.25f as IEEE float
+ * (SF/src/MapPoint.cc GetFoundRatio; a zero denominator gives inf or NaN, which are not below 0.25); the ages are (int)current_kf_id -
+ * (int)first_kf_id, through int as :386 and :391 cast.  th_obs: 3 for stereo, 2 for monocular (:366-371).  A point's action depends on no
+ * other point.  One launch, one upload, one download.  Returns n_points. */
+int tc2li_map_point_culling_batch(const uint8_t* bad, const int32_t* n_found, const int32_t* n_visible, const int64_t* first_kf_id,
+                                  const int32_t* n_obs, const int64_t* current_kf_id, int n_points, int th_obs, uint8_t* action, void* stream);
+/* The same on the CPU; needs no device. */
+int tc2li_host_map_point_culling_batch(const uint8_t* bad, const int32_t* n_found, const int32_t* n_visible, const int64_t* first_kf_id,
+                                       const int32_t* n_obs, const int64_t* current_kf_id, int n_points, int th_obs, uint8_t* action);
+
 #ifdef __cplusplus
 }
 #endif

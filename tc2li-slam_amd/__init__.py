@@ -45,4 +45,6 @@ from .capi import (  # noqa: F401
     mlpnp_iterations,
     mlpnp_params,
     mlpnp_ransac_batch,
+    keyframe_culling_batch,
+    map_point_culling_batch,
 )

@@ -2385,3 +2385,90 @@ def mlpnp_ransac_batch(problems, level_sigma2, cam5, params=None, capacity=None,
     out["best_Tcw"] = np.array([list(states[i].best_Tcw) for i in range(P)], np.float32).reshape(P, 12)
     out["best_inlier"] = best[:P]
     return out
+
+
+class CullingProblem(C.Structure):
+    """tc2li_culling_problem"""
+    _fields_ = [(k, C.c_void_p) for k in ("kf_flags", "kf_id", "kf_prev", "kf_next", "kf_time", "kf_imu_pos", "kf_th_depth", "slot_offsets",
+                                          "slot_point", "slot_depth", "slot_octave", "local", "point_bad", "point_nobs", "obs_offsets", "obs_kf",
+                                          "obs_octave", "obs_weight", "verdict", "n_mps", "n_redundant", "n_visited", "point_bad_after",
+                                          "point_nobs_after")] \
+        + [("current_id", C.c_int64), ("last_id", C.c_int64), ("n_keyframes", C.c_int32), ("n_local", C.c_int32), ("n_points", C.c_int32),
+           ("keyframes_in_map", C.c_int32), ("inertial", C.c_uint8), ("imu_initialized", C.c_uint8), ("inertial_ba2", C.c_uint8),
+           ("abort_ba", C.c_uint8), ("pad_", C.c_int32)]
+
+
+CULL_SKIPPED, CULL_NOT_VISITED, CULL_REDUNDANT, CULL_SET_BAD, CULL_MERGED, CULL_DEFERRED = -1, -2, 1, 2, 4, 8
+_CULLING_ARRAYS = (("kf_flags", np.uint8), ("kf_id", np.int64), ("kf_prev", np.int32), ("kf_next", np.int32), ("kf_time", np.float64),
+                   ("kf_imu_pos", np.float32), ("kf_th_depth", np.float32), ("slot_offsets", np.int32), ("slot_point", np.int32),
+                   ("slot_depth", np.float32), ("slot_octave", np.int8), ("local", np.int32), ("point_bad", np.uint8), ("point_nobs", np.int32),
+                   ("obs_offsets", np.int32), ("obs_kf", np.int32), ("obs_octave", np.int8), ("obs_weight", np.uint8))
+_CULLING_SCALARS = ("inertial", "imu_initialized", "inertial_ba2", "abort_ba", "keyframes_in_map", "current_id", "last_id")
+
+
+def pack_culling_problems(problems):
+    """The tc2li_culling_problem array of a batch with its output arrays -> (array, outputs per problem, what must stay alive)."""
+    P = len(problems)
+    arr, outs, keep = (CullingProblem * max(P, 1))(), [], []
+    for i, p in enumerate(problems):
+        a = {k: np.ascontiguousarray(p[k], t) for k, t in _CULLING_ARRAYS}
+        nk, npts, nl = len(a["kf_flags"]), len(a["point_bad"]), len(a["local"])
+        for k in ("kf_id", "kf_prev", "kf_next", "kf_time", "kf_th_depth"):
+            if len(a[k]) != nk:
+                raise ValueError("problem %d: %s has %d rows for %d keyframes" % (i, k, len(a[k]), nk))
+        if a["kf_imu_pos"].size != 3 * nk or len(a["slot_offsets"]) != nk + 1 or len(a["point_nobs"]) != npts or len(a["obs_offsets"]) != npts + 1:
+            raise ValueError("problem %d: kf_imu_pos, slot_offsets, point_nobs or obs_offsets do not fit the tables" % i)
+        ns, no = int(a["slot_offsets"][-1]), int(a["obs_offsets"][-1])
+        if min(len(a[k]) for k in ("slot_point", "slot_depth", "slot_octave")) < ns or min(len(a[k]) for k in ("obs_kf", "obs_octave", "obs_weight")) < no:
+            raise ValueError("problem %d: slot or observation arrays are shorter than their offsets say" % i)
+        o = dict(verdict=np.zeros(nl, np.int32), n_mps=np.zeros(nl, np.int32), n_redundant=np.zeros(nl, np.int32), n_visited=np.zeros(1, np.int32),
+                 point_bad_after=np.zeros(npts, np.uint8), point_nobs_after=np.zeros(npts, np.int32))
+        for k, v in list(a.items()) + list(o.items()):
+            setattr(arr[i], k, v.ctypes.data)
+        for k in _CULLING_SCALARS:
+            setattr(arr[i], k, int(p.get(k, 0)))
+        arr[i].n_keyframes, arr[i].n_local, arr[i].n_points = nk, nl, npts
+        keep.append(a)
+        outs.append(o)
+    return arr, outs, keep
+
+
+def keyframe_culling_batch(problems, host=False, stream=0):
+    """One ``LocalMapping::KeyFrameCulling`` call per problem.  problems: dicts with the arrays of tc2li_culling_problem (kf_flags, kf_id,
+    kf_prev, kf_next, kf_time, kf_imu_pos [n, 3], kf_th_depth, slot_offsets, slot_point, slot_depth, slot_octave, local, point_bad, point_nobs,
+    obs_offsets, obs_kf, obs_octave, obs_weight) and its scalars (inertial, imu_initialized, inertial_ba2, abort_ba, keyframes_in_map,
+    current_id, last_id; default 0) -> one dict per problem: verdict, n_mps, n_redundant [n_local] (the counters are 0 where verdict < 0),
+    n_visited, point_bad_after, point_nobs_after [n_points].  host=True walks the same graph on the CPU."""
+    arr, outs, keep = pack_culling_problems(problems)
+    if host:
+        f = lib().tc2li_host_keyframe_culling_batch
+        f.argtypes = [C.c_void_p, C.c_int]
+        _check(f(C.addressof(arr), len(problems)))
+    else:
+        f = lib().tc2li_keyframe_culling_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _check(f(C.addressof(arr), len(problems), C.c_void_p(stream)))
+    del keep
+    return [dict(o, n_visited=int(o["n_visited"][0])) for o in outs]
+
+
+def map_point_culling_batch(points, th_obs=3, host=False, stream=0):
+    """``LocalMapping::MapPointCulling`` for the entries of mlpRecentAddedMapPoints of any number of sequences.  points: dict of arrays bad,
+    n_found, n_visible, first_kf_id, n_obs, current_kf_id (one entry per point) -> action [n] uint8: 0 stays, 1 dropped (bad), 2 SetBadFlag
+    (found ratio), 3 SetBadFlag (observations), 4 dropped by age."""
+    a = [np.ascontiguousarray(points[k], t) for k, t in (("bad", np.uint8), ("n_found", np.int32), ("n_visible", np.int32), ("first_kf_id", np.int64),
+                                                         ("n_obs", np.int32), ("current_kf_id", np.int64))]
+    n = len(a[0])
+    if any(len(v) != n for v in a):
+        raise ValueError("the arrays differ in length")
+    action = np.zeros(n, np.uint8)
+    args = [v.ctypes.data for v in a] + [n, int(th_obs), action.ctypes.data]
+    if host:
+        f = lib().tc2li_host_map_point_culling_batch
+        f.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
+        _check(f(*args))
+    else:
+        f = lib().tc2li_map_point_culling_batch
+        f.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _check(f(*(args + [C.c_void_p(stream)])))
+    return action
