@@ -15,6 +15,7 @@
 #include "common.hpp"
 #include "orb_handle.hpp"
 #include "pose_opt_device.hpp"
+#include "projection_search.hpp"
 
 using namespace tc2li;
 
@@ -136,8 +137,6 @@ struct BowWs {
     DevBuf<uint8_t> d_outlier;
 };
 BowWs& bws() { static thread_local BowWs w; return w; }
-
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 bool out_ok(const tc2li_bow_out* o) {
     return o && o->word && o->node && o->n_words && o->bow_word && o->bow_value && o->n_nodes && o->fv_node && o->fv_offset && o->fv_index;
@@ -342,11 +341,7 @@ extern "C" int tc2li_orb_compute_bow_batch(tc2li_orb* o, tc2li_vocabulary* v, in
     if (!device_ready()) return TC2LI_ERR_NO_DEVICE;  // no CPU fallback: before anything else
     if (!o || !v || n_frames < 0 || capacity < 0 || !out_ok(out)) { set_error("tc2li_orb_compute_bow_batch: invalid argument"); return TC2LI_ERR_INVALID; }
     if (n_frames == 0) return 0;
-    if (2 * n_frames > o->last_nimg || !o->last_plain_order) {
-        set_error("tc2li_orb_compute_bow_batch: needs the features of a preceding tc2li_orb_extract_batch call with lapping area {0,0} and "
-                  "2*n_frames images");
-        return TC2LI_ERR_INVALID;
-    }
+    if (!orb_features_ready(o, n_frames, "tc2li_orb_compute_bow_batch")) return TC2LI_ERR_INVALID;
     std::vector<BowFrameDev> frames(n_frames);
     for (int f = 0; f < n_frames; ++f) {
         const int n = o->last_kp_cnt[2 * f];
@@ -461,11 +456,7 @@ extern "C" int tc2li_track_reference_keyframe_batch(tc2li_orb* o, tc2li_vocabula
         return TC2LI_ERR_INVALID;
     }
     if (n_frames == 0) return 0;
-    if (2 * n_frames > o->last_nimg || !o->last_plain_order) {
-        set_error("tc2li_track_reference_keyframe_batch: needs the features of a preceding tc2li_orb_extract_batch call with lapping area {0,0} "
-                  "and 2*n_frames images");
-        return TC2LI_ERR_INVALID;
-    }
+    if (!orb_features_ready(o, n_frames, "tc2li_track_reference_keyframe_batch")) return TC2LI_ERR_INVALID;
     if (o->prm.nlevels > kMaxLevels) { set_error("tc2li_track_reference_keyframe_batch: %d levels (at most %d)", o->prm.nlevels, kMaxLevels); return TC2LI_ERR_INVALID; }
     std::vector<BowFrameDev> frames(n_frames);
     std::vector<BowPairDev> P(n_frames);

@@ -342,7 +342,7 @@ extern "C" int tc2li_fuse_search(const tc2li_frame_view* kf, const float pose7[7
     for (int i = 0; i < N; ++i) mk[i] = MatchKey{kf->keys[i].x, kf->keys[i].y, kf->keys[i].octave};
     TC2LI_HIP_CHECK(w.keys.ensure(6 * (size_t)N)); TC2LI_HIP_CHECK(w.u_right.ensure(N)); TC2LI_HIP_CHECK(w.desc.ensure(32 * (size_t)N)); TC2LI_HIP_CHECK(w.mkeys.ensure(N));
     TC2LI_HIP_CHECK(w.scale.ensure(n_levels)); TC2LI_HIP_CHECK(w.inv_sigma.ensure(n_levels)); TC2LI_HIP_CHECK(w.points.ensure(68 * (size_t)n_points));
-    TC2LI_HIP_CHECK(w.valid.ensure(n_points)); TC2LI_HIP_CHECK(w.frame.ensure(1)); TC2LI_HIP_CHECK(w.cell_start.ensure(64 * 48 + 1)); TC2LI_HIP_CHECK(w.key_base.ensure(1));
+    TC2LI_HIP_CHECK(w.valid.ensure(n_points)); TC2LI_HIP_CHECK(w.frame.ensure(1)); TC2LI_HIP_CHECK(w.cell_start.ensure(kCellsPlus1)); TC2LI_HIP_CHECK(w.key_base.ensure(1));
     TC2LI_HIP_CHECK(w.items.ensure(N)); TC2LI_HIP_CHECK(w.best_idx.ensure(n_points)); TC2LI_HIP_CHECK(w.best_dist.ensure(n_points));
     TC2LI_HIP_CHECK(hipMemcpyAsync(w.keys.p, kf->keys, (size_t)N * sizeof(tc2li_keypoint), hipMemcpyHostToDevice, st));
     TC2LI_HIP_CHECK(hipMemcpyAsync(w.mkeys.p, mk.data(), N * sizeof(MatchKey), hipMemcpyHostToDevice, st));

@@ -9,6 +9,7 @@
 namespace tc2li {
 
 constexpr int kMaxMatchKeys = 3072;  // keypoints of one frame that fit the LDS working set
+constexpr int kCellsPlus1 = 64 * 48 + 1;  // cell_start entries of one frame: the feature grid of matcher_kernels.hip (kCells) + 1
 
 struct MatchQuery {  // tc2li_proj_query, 64 bytes
     float u, v, radius, u_right;
@@ -39,7 +40,7 @@ __device__ __forceinline__ MatchFrameDev global_record(MatchFrameDev f) {  // gl
 // the three-launch form (grid, candidate lists, rounds over the lists); the tables live in the caller's workspace.  When
 // pool_top[1] comes back non-zero the candidate pool was too small and launch_match_by_projection has to be used instead.
 struct MatchLists {
-    int32_t* cell_start;   // [nframes][kCells + 1]
+    int32_t* cell_start;   // [nframes][kCellsPlus1]
     uint16_t* items;       // [total keys], frame f at key_base[f]
     const int32_t* key_base;  // [nframes]
     int32_t* cand_off;     // [total queries]

@@ -9,9 +9,11 @@
 #include <cstring>
 #include <mutex>
 
+#include "balm_math.hpp"  // quat_rotate_f
 #include "common.hpp"
 #include "matcher_device.hpp"
 #include "orb_handle.hpp"
+#include "projection_search.hpp"
 
 using namespace tc2li;
 
@@ -39,13 +41,6 @@ struct MatcherWorkspace {
 // one workspace per host thread: two threads that search different batches side by side do not wait for each other
 MatcherWorkspace& mws() { static thread_local MatcherWorkspace w; return w; }
 
-inline void quat_rotate_f(const float q[4], const float v[3], float out[3]) {  // Eigen::Quaternionf::_transformVector
-    float uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    out[0] = v[0] + q[3] * uv[0] + (q[1] * uv[2] - q[2] * uv[1]);
-    out[1] = v[1] + q[3] * uv[1] + (q[2] * uv[0] - q[0] * uv[2]);
-    out[2] = v[2] + q[3] * uv[2] + (q[0] * uv[1] - q[1] * uv[0]);
-}
 inline void camera_centre(const float pose7[7], float out[3]) {  // Tcw.inverse().translation()
     const float qi[4] = {-pose7[0], -pose7[1], -pose7[2], pose7[3]};
     const float nt[3] = {pose7[4] * -1.f, pose7[5] * -1.f, pose7[6] * -1.f};
@@ -215,9 +210,7 @@ int tc2li_project_local_map(const float pose7[7], const float cam4[4], float bf,
         if (dist < M.min_distance || dist > M.max_distance) continue;
         const float view_cos = ((po[0] * M.normal[0] + po[1] * M.normal[1]) + po[2] * M.normal[2]) / dist;
         if (view_cos < viewing_cos_limit) continue;
-        const float ratio = M.max_distance_raw / dist;  // MapPoint::PredictScale
-        int level = (int)ceilf(logf(ratio) / log_scale_factor);
-        if (level < 0) level = 0; else if (level >= n_levels) level = n_levels - 1;
+        const int level = predict_scale_level(M.max_distance_raw / dist, log_scale_factor, n_levels);
         if (far_points && pc_dist > th_far_points) continue;
         float r = view_cos > 0.998f ? 2.5f : 4.0f;
         if (factor) r *= th;

@@ -93,4 +93,11 @@ struct tc2li_orb {
 
 namespace tc2li {
 void stereo_release_workspace(const tc2li_orb* o);  // stereo_host.cpp: drops the matcher workspace of a handle
+
+// the check of every entry point that works on the features of the last tc2li_orb_extract_batch call
+inline bool orb_features_ready(const tc2li_orb* o, int n_frames, const char* fn) {
+    if (2 * n_frames <= o->last_nimg && o->last_plain_order) return true;
+    set_error("%s: needs the features of a preceding tc2li_orb_extract_batch call with lapping area {0,0} and 2*n_frames images", fn);
+    return false;
+}
 }

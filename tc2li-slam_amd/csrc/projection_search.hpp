@@ -1,0 +1,125 @@
+// The host driver every projection search shares (tracking_host.cpp: TrackWithMotionModel / TrackLocalMap; reloc_host.cpp: the keyframe
+// overload and the refinement ladder): the scratch buffers of a search, MapPoint::PredictScale on the host for ratios on a level boundary,
+// the list-form matcher with its fall-back to the one-kernel form, and the small helpers those entry points had a copy of each.
+#pragma once
+#include <cmath>
+#include <cstring>
+#include <functional>
+
+#include "common.hpp"
+#include "matcher_device.hpp"
+#include "orb_handle.hpp"
+#include "tracking_device.hpp"
+
+namespace tc2li {
+
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// MapPoint::PredictScale (SF/src/MapPoint.cc:540-555) with the host library's logf: the one definition
+inline int predict_scale_level(float ratio, float log_scale, int n_levels) {
+    int level = (int)ceilf(logf(ratio) / log_scale);
+    if (level < 0) level = 0; else if (level >= n_levels) level = n_levels - 1;
+    return level;
+}
+
+// ---- argument checks of the entry points that search the features of the last tc2li_orb_extract_batch call (orb_features_ready) ----
+// item >= 0: the frame is item `item` of the caller's list
+inline int check_capacity(const char* fn, int n_keys, int capacity, int item = -1) {
+    if (n_keys <= capacity) return TC2LI_OK;
+    if (item < 0) set_error("%s: capacity %d < %d keypoints", fn, capacity, n_keys);
+    else set_error("%s: capacity %d < %d keypoints of item %d", fn, capacity, n_keys, item);
+    return TC2LI_ERR_CAPACITY;
+}
+inline int check_match_keys(const char* fn, int n_keys, int item = -1) {
+    if (n_keys <= kMaxMatchKeys) return TC2LI_OK;
+    if (item < 0) set_error("%s: frame has %d keypoints, the matcher supports %d", fn, n_keys, kMaxMatchKeys);
+    else set_error("%s: item %d has %d keypoints, the matcher supports %d", fn, item, n_keys, kMaxMatchKeys);
+    return TC2LI_ERR_CAPACITY;
+}
+
+// ---- TrackConst ----
+inline TrackConst track_const(const float cam4[4], const float* scale, int n_levels, float log_scale, int capacity) {
+    TrackConst C;
+    memset(&C, 0, sizeof(C));
+    memcpy(C.cam4, cam4, 4 * sizeof(float));
+    C.n_levels = n_levels; C.capacity = capacity; C.log_scale = log_scale;
+    for (int l = 0; l < n_levels; ++l) C.scale[l] = scale[l];
+    return C;
+}
+inline TrackConst track_const(const tc2li_orb* o, const tc2li_camera* cam, float b, int capacity) {
+    const float cam4[4] = {(float)cam->fx, (float)cam->fy, (float)cam->cx, (float)cam->cy};
+    // mfLogScaleFactor = log(mfScaleFactor) (SF/src/Frame.cc:96)
+    TrackConst C = track_const(cam4, o->scale.data(), o->prm.nlevels, std::log(o->prm.scale_factor), capacity);
+    C.b = b; C.bf = (float)cam->bf;
+    for (int l = 0; l < C.n_levels; ++l) C.inv_sigma2[l] = o->inv_sigma2[l];
+    C.cols = o->cur_w; C.rows = o->cur_h;
+    return C;
+}
+
+// ---- the keyframe's points of the keyframe overload (tc2li_projection_keyframe_item / tc2li_reloc_hypothesis), query-indexed ----
+struct KeyframePointStage {  // offsets in the caller's staging block, q1 points
+    size_t o_hp, o_Xw, o_pd, o_min, o_max, o_raw, o_pang, end;
+    KeyframePointStage(size_t begin, size_t q1)
+        : o_hp(begin), o_Xw(up256(o_hp + q1)), o_pd(up256(o_Xw + 12 * q1)), o_min(up256(o_pd + 32 * q1)), o_max(up256(o_min + 4 * q1)),
+          o_raw(up256(o_max + 4 * q1)), o_pang(up256(o_raw + 4 * q1)), end(up256(o_pang + 4 * q1)) {}
+    KeyframePointArrays arrays(const uint8_t* d, const uint8_t* d_found) const {
+        auto f = [&](size_t off) { return reinterpret_cast<const float*>(d + off); };
+        return KeyframePointArrays{d + o_hp, d_found, f(o_Xw), d + o_pd, f(o_min), f(o_max), f(o_raw), f(o_pang)};
+    }
+};
+// packs the points of `it` at query offset q of the host block h
+template <typename Item>
+void stage_keyframe_points(const KeyframePointStage& S, uint8_t* h, size_t q, const Item& it) {
+    const size_t n = (size_t)it.n_points;
+    for (size_t i = 0; i < n; ++i) h[S.o_hp + q + i] = it.has_point[i] ? 1 : 0;
+    if (!n) return;
+    memcpy(h + S.o_Xw + 12 * q, it.Xw, 12 * n);
+    memcpy(h + S.o_pd + 32 * q, it.point_descriptors, 32 * n);
+    memcpy(h + S.o_min + 4 * q, it.min_distance, 4 * n);
+    memcpy(h + S.o_max + 4 * q, it.max_distance, 4 * n);
+    memcpy(h + S.o_raw + 4 * q, it.max_distance_raw, 4 * n);
+    memcpy(h + S.o_pang + 4 * q, it.angle, 4 * n);
+}
+
+// ---- the buffers of a search: one per work space (TrackWs, KfSearchWs, LadderWs) ----
+struct SearchScratch {
+    DevBuf<MatchQuery> d_queries;                                                               // [total_q]
+    DevBuf<int32_t> d_query_frame, d_match, d_prev, d_cand_off, d_cand_cnt, d_amb_ids, d_amb_level;  // [total_q]
+    DevBuf<float> d_amb_ratio, d_amb_r;                                                         // [total_q]
+    DevBuf<int32_t> d_rounds, d_nmatch;                                                         // [n_frames]
+    DevBuf<int32_t> d_cell_start;                                                               // [n_frames][kCellsPlus1]
+    DevBuf<int32_t> d_small;                                                                    // pool_top [2], amb_count [1]
+    DevBuf<uint16_t> d_items;                                                                   // [n_frames][capacity]
+    DevBuf<uint32_t> d_pool;                                                                    // [pool_cap]
+    PinnedBuf<int32_t> h_small, h_amb_level;                                                    // as d_small; [total_q]
+    PinnedBuf<float> h_amb_ratio;                                                               // [total_q]
+    int pool_cap = 0;  // TC2LI_MATCH_POOL_PER_QUERY (default 32) entries per query
+
+    int32_t* pool_top() const { return d_small.p; }
+    int32_t* amb_count() const { return d_small.p + 2; }
+    int ensure(int n_frames, int total_q, int capacity);
+};
+
+// After the query kernel (launch_track_queries_local / _keyframe with s.amb_count(), s.d_amb_ids, s.d_amb_ratio, s.d_amb_r; the caller
+// zeroes the count before): the listed ratios get their level from predict_scale_level and `patch` writes level and window of those
+// queries.  Waits for the stream once, twice when something is listed.
+using PatchLauncher = void (*)(const int32_t* ids, const int32_t* levels, const float* r, int n, const TrackConst& C, MatchQuery* queries, hipStream_t st);
+int resolve_ambiguous_levels(SearchScratch& s, const TrackConst& C, PatchLauncher patch, hipStream_t st);
+
+struct SearchPass {
+    const MatchFrameDev* d_mframes;   // [n_pass], on the device
+    const int32_t* d_key_base;        // [n_pass]: where the frame's keys start in d_items
+    int n_pass, total_q;
+    const TrackFrameDev* h_frames;    // host records; frame k of the pass is h_frames[h_pass ? h_pass[k] : k]
+    const int32_t* h_pass;
+    int mode;
+    float nn_ratio;
+    int orb_dist;
+};
+// The search of one pass into s.d_match: queues the list form, then `behind` (what the caller wants queued before the single wait; may be
+// empty), waits, and when the candidate pool overflowed resets the pass's matches and queues the one-kernel form -- same result -- and
+// `behind` again with a second wait.  Without `behind` the fall-back is left queued: the caller's follow-up kernels go behind it.
+// `behind` must overwrite what it writes: after a fall-back it has run on a partial match list before.
+int projection_search(SearchScratch& s, const SearchPass& P, hipStream_t st, const std::function<int()>& behind = nullptr);
+
+}  // namespace tc2li

@@ -13,6 +13,7 @@
 #include "matcher_device.hpp"
 #include "orb_handle.hpp"
 #include "pose_opt_device.hpp"
+#include "projection_search.hpp"
 #include "reloc_device.hpp"
 #include "tracking_device.hpp"
 
@@ -429,22 +430,13 @@ extern "C" int tc2li_detect_relocalization_candidates_batch(const tc2li_reloc_qu
 // that reproduce "a matched keypoint blocks later points") with ORBdist as its distance bound; the rotation filter is k_track_count.
 namespace {
 
-constexpr int kCellsPlus1 = 64 * 48 + 1;  // the matcher's feature grid (matcher_kernels.hip)
-
 struct KfSearchWs {
     PinnedBuf<uint8_t> h_stage;
     DevBuf<uint8_t> d_stage;
-    DevBuf<MatchQuery> d_queries;
-    DevBuf<int32_t> d_i32;
-    DevBuf<float> d_f32;
-    DevBuf<uint16_t> d_items;
-    DevBuf<uint32_t> d_pool;
-    PinnedBuf<int32_t> h_small;
-    PinnedBuf<float> h_ratio;
+    SearchScratch s;
+    DevBuf<int32_t> d_of_key;
 };
 KfSearchWs& kws() { static thread_local KfSearchWs w; return w; }
-
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -469,31 +461,25 @@ extern "C" int tc2li_search_by_projection_keyframe_batch(const tc2li_projection_
             set_error("%s: item %d has null arrays", fn, f);
             return TC2LI_ERR_INVALID;
         }
-        if (I.n > capacity) { set_error("%s: capacity %d < %d keypoints of item %d", fn, capacity, I.n, f); return TC2LI_ERR_CAPACITY; }
-        if (I.n > kMaxMatchKeys) { set_error("%s: item %d has %d keypoints, the matcher supports %d", fn, f, I.n, kMaxMatchKeys); return TC2LI_ERR_CAPACITY; }
+        if (int rc = check_capacity(fn, I.n, capacity, f)) return rc;
+        if (int rc = check_match_keys(fn, I.n, f)) return rc;
         nk += I.n; nq += I.n_points;
     }
     hipStream_t st = stream_ ? (hipStream_t)stream_ : private_stream();
     KfSearchWs& w = kws();
-    const size_t nf = n_items, k1 = std::max<size_t>(nk, 1), q1 = std::max<size_t>(nq, 1);
+    SearchScratch& S = w.s;
+    const size_t nf = n_items, k1 = std::max<size_t>(nk, 1), q1 = std::max<size_t>(nq, 1), cap1 = std::max(capacity, 1);
     const int total_q = (int)nq;
     // one staging block: per frame keypoint the matcher's key, descriptor, angle, held flag and a u_right of -1 (the overload has no stereo
     // test); per keyframe keypoint the point; per frame the records
     const size_t o_keys = 0, o_desc = up256(o_keys + sizeof(MatchKey) * k1), o_ang = up256(o_desc + 32 * k1), o_ur = up256(o_ang + 4 * k1),
-                 o_held = up256(o_ur + 4 * k1), o_hp = up256(o_held + k1), o_found = up256(o_hp + q1), o_Xw = up256(o_found + q1),
-                 o_pd = up256(o_Xw + 12 * q1), o_min = up256(o_pd + 32 * q1), o_max = up256(o_min + 4 * q1), o_raw = up256(o_max + 4 * q1),
-                 o_pang = up256(o_raw + 4 * q1), o_frames = up256(o_pang + 4 * q1), o_bounds = up256(o_frames + sizeof(TrackFrameDev) * nf),
+                 o_held = up256(o_ur + 4 * k1);
+    const KeyframePointStage pts(up256(o_held + k1), q1);
+    const size_t o_found = pts.end, o_frames = up256(o_found + q1), o_bounds = up256(o_frames + sizeof(TrackFrameDev) * nf),
                  o_mframes = up256(o_bounds + 16 * nf), o_kbase = up256(o_mframes + sizeof(MatchFrameDev) * nf), bytes = up256(o_kbase + 4 * nf);
     TC2LI_HIP_CHECK(w.h_stage.ensure(bytes)); TC2LI_HIP_CHECK(w.d_stage.ensure(bytes));
-    TC2LI_HIP_CHECK(w.d_queries.ensure(q1));
-    const int pool_cap = 32 * (int)q1;
-    // int32: query_frame, match, prev, cand_off, cand_cnt, amb_ids, amb_level [q1]; rounds, n_matches [nf]; cell_start [nf][cells + 1];
-    // pool_top [2]; amb_count [1]; of_key [nf][capacity]
-    const size_t cap1 = std::max(capacity, 1);
-    TC2LI_HIP_CHECK(w.d_i32.ensure(7 * q1 + 2 * nf + nf * kCellsPlus1 + 4 + nf * cap1));
-    TC2LI_HIP_CHECK(w.d_f32.ensure(2 * q1));  // amb_ratio, amb_r
-    TC2LI_HIP_CHECK(w.d_items.ensure(k1)); TC2LI_HIP_CHECK(w.d_pool.ensure(pool_cap));
-    TC2LI_HIP_CHECK(w.h_small.ensure(4 + q1)); TC2LI_HIP_CHECK(w.h_ratio.ensure(q1));
+    if (int rc = S.ensure(n_items, total_q, capacity)) return rc;
+    TC2LI_HIP_CHECK(w.d_of_key.ensure(nf * cap1));
     uint8_t* h = w.h_stage.p;
     uint8_t* d = w.d_stage.p;
     MatchKey* hk = reinterpret_cast<MatchKey*>(h + o_keys);
@@ -513,78 +499,40 @@ extern "C" int tc2li_search_by_projection_keyframe_batch(const tc2li_projection_
             h[o_held + key + i] = I.held[i] ? 1 : 0;
         }
         if (I.n) memcpy(h + o_desc + 32 * key, I.descriptors, 32 * (size_t)I.n);
-        for (int i = 0; i < I.n_points; ++i) { h[o_hp + q + i] = I.has_point[i] ? 1 : 0; h[o_found + q + i] = I.found[i] ? 1 : 0; }
-        if (I.n_points) {
-            memcpy(h + o_Xw + 12 * q, I.Xw, 12 * (size_t)I.n_points);
-            memcpy(h + o_pd + 32 * q, I.point_descriptors, 32 * (size_t)I.n_points);
-            memcpy(h + o_min + 4 * q, I.min_distance, 4 * (size_t)I.n_points);
-            memcpy(h + o_max + 4 * q, I.max_distance, 4 * (size_t)I.n_points);
-            memcpy(h + o_raw + 4 * q, I.max_distance_raw, 4 * (size_t)I.n_points);
-            memcpy(h + o_pang + 4 * q, I.angle, 4 * (size_t)I.n_points);
-        }
+        stage_keyframe_points(pts, h, q, I);
+        for (int i = 0; i < I.n_points; ++i) h[o_found + q + i] = I.found[i] ? 1 : 0;
         TrackFrameDev& F = hf[f];
         memset(&F, 0, sizeof(F));
         memcpy(F.pose7, I.pose7, 7 * sizeof(float));
         F.th = th; F.q_off = (int32_t)q; F.n_q = I.n_points; F.key_off = (int32_t)key; F.n_keys = I.n; F.slot = f;
         memcpy(hb + 4 * f, I.bounds, 16);
         hm[f] = MatchFrameDev{reinterpret_cast<const MatchKey*>(d + o_keys) + key, d + o_desc + 32 * key, reinterpret_cast<const float*>(d + o_ur) + key,
-                              d + o_held + key, w.d_queries.p + q, I.n, I.n_points, (int32_t)q, 0, I.bounds[0], I.bounds[1], I.bounds[2], I.bounds[3]};
+                              d + o_held + key, S.d_queries.p + q, I.n, I.n_points, (int32_t)q, 0, I.bounds[0], I.bounds[1], I.bounds[2], I.bounds[3]};
         hkb[f] = (int32_t)key;
         key += I.n; q += I.n_points;
     }
-    TrackConst C;
-    memset(&C, 0, sizeof(C));
-    memcpy(C.cam4, cam4, 16);
-    C.n_levels = n_levels; C.capacity = capacity; C.log_scale = log_scale_factor;
-    for (int l = 0; l < n_levels; ++l) C.scale[l] = scale_factors[l];
+    const TrackConst C = track_const(cam4, scale_factors, n_levels, log_scale_factor, capacity);
     TC2LI_HIP_CHECK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
-    int32_t* ip = w.d_i32.p;
-    int32_t *d_qf = ip, *d_match = ip + q1, *d_prev = ip + 2 * q1, *d_coff = ip + 3 * q1, *d_ccnt = ip + 4 * q1, *d_amb_ids = ip + 5 * q1,
-            *d_amb_level = ip + 6 * q1, *d_rounds = ip + 7 * q1, *d_nm = d_rounds + nf, *d_cells = d_nm + nf, *d_top = d_cells + nf * kCellsPlus1,
-            *d_amb = d_top + 2, *d_of_key = d_amb + 2;
-    float *d_amb_ratio = w.d_f32.p, *d_amb_r = w.d_f32.p + q1;
     const TrackFrameDev* d_frames = reinterpret_cast<const TrackFrameDev*>(d + o_frames);
-    const MatchFrameDev* d_mframes = reinterpret_cast<const MatchFrameDev*>(d + o_mframes);
-    const KeyframePointArrays A{d + o_hp, d + o_found, reinterpret_cast<const float*>(d + o_Xw), d + o_pd, reinterpret_cast<const float*>(d + o_min),
-                                reinterpret_cast<const float*>(d + o_max), reinterpret_cast<const float*>(d + o_raw), reinterpret_cast<const float*>(d + o_pang)};
-    TC2LI_HIP_CHECK(hipMemsetAsync(d_of_key, 0xff, nf * cap1 * sizeof(int32_t), st));
-    TC2LI_HIP_CHECK(hipMemsetAsync(d_nm, 0, nf * sizeof(int32_t), st));
+    const KeyframePointArrays A = pts.arrays(d, d + o_found);
+    TC2LI_HIP_CHECK(hipMemsetAsync(w.d_of_key.p, 0xff, nf * cap1 * sizeof(int32_t), st));
+    TC2LI_HIP_CHECK(hipMemsetAsync(S.d_nmatch.p, 0, nf * sizeof(int32_t), st));
     if (total_q > 0) {
-        TC2LI_HIP_CHECK(hipMemsetAsync(d_amb, 0, sizeof(int32_t), st));
-        launch_track_queries_keyframe(d_frames, n_items, reinterpret_cast<const float4*>(d + o_bounds), C, A, total_q, w.d_queries.p, d_qf, d_match, d_amb,
-                                      d_amb_ids, d_amb_ratio, d_amb_r, st);
-        TC2LI_HIP_CHECK(hipGetLastError());
-        // MapPoint::PredictScale on a level boundary: the host's logf decides, as in tc2li_track_local_map_batch
-        TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_small.p, d_amb, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        TC2LI_HIP_CHECK(stream_wait_blocking(st));
-        const int n_amb = w.h_small.p[0];
-        if (n_amb > 0) {
-            TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_ratio.p, d_amb_ratio, n_amb * sizeof(float), hipMemcpyDeviceToHost, st));
-            TC2LI_HIP_CHECK(stream_wait_blocking(st));
-            int32_t* lev = w.h_small.p + 4;
-            for (int k = 0; k < n_amb; ++k) {
-                int level = (int)ceilf(logf(w.h_ratio.p[k]) / log_scale_factor);  // MapPoint::PredictScale (SF/src/MapPoint.cc:540-555)
-                if (level < 0) level = 0; else if (level >= n_levels) level = n_levels - 1;
-                lev[k] = level;
-            }
-            TC2LI_HIP_CHECK(hipMemcpyAsync(d_amb_level, lev, n_amb * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            launch_track_patch_levels_keyframe(d_amb_ids, d_amb_level, d_amb_r, n_amb, C, w.d_queries.p, st);
-        }
-        MatchLists L{d_cells, w.d_items.p, reinterpret_cast<const int32_t*>(d + o_kbase), d_coff, d_ccnt, w.d_pool.p, d_top, pool_cap, 0};
-        launch_match_lists(d_mframes, n_items, d_qf, total_q, L, 0, 0.0f, d_match, d_prev, d_rounds, st, orb_dist);
-        TC2LI_HIP_CHECK(hipGetLastError());
-        TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_small.p, d_top, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        TC2LI_HIP_CHECK(stream_wait_blocking(st));
-        if (w.h_small.p[1]) {  // candidate pool exhausted (very dense windows): the one-kernel form, same result
-            TC2LI_HIP_CHECK(hipMemsetAsync(d_match, 0xff, q1 * sizeof(int32_t), st));
-            launch_match_by_projection(d_mframes, n_items, 0, 0.0f, d_match, d_prev, d_rounds, st, orb_dist);
-        }
-        launch_track_count(d_frames, nullptr, n_items, w.d_queries.p, reinterpret_cast<const float*>(d + o_ang), check_orientation ? 1 : 0, d_match, d_nm, st);
-        launch_track_assign_keyframe(d_frames, n_items, capacity, total_q, d_match, d_of_key, st);
+        TC2LI_HIP_CHECK(hipMemsetAsync(S.amb_count(), 0, sizeof(int32_t), st));
+        launch_track_queries_keyframe(d_frames, n_items, reinterpret_cast<const float4*>(d + o_bounds), C, A, total_q, S.d_queries.p, S.d_query_frame.p,
+                                      S.d_match.p, S.amb_count(), S.d_amb_ids.p, S.d_amb_ratio.p, S.d_amb_r.p, st);
+        if (int rc = resolve_ambiguous_levels(S, C, launch_track_patch_levels_keyframe, st)) return rc;
+        // the follow-up kernels go behind the overflow decision: k_track_assign_keyframe scatters into of_key and must not see a partial list
+        const SearchPass P{reinterpret_cast<const MatchFrameDev*>(d + o_mframes), reinterpret_cast<const int32_t*>(d + o_kbase), n_items, total_q, hf, nullptr,
+                           0, 0.0f, orb_dist};
+        if (int rc = projection_search(S, P, st)) return rc;
+        launch_track_count(d_frames, nullptr, n_items, S.d_queries.p, reinterpret_cast<const float*>(d + o_ang), check_orientation ? 1 : 0, S.d_match.p,
+                           S.d_nmatch.p, st);
+        launch_track_assign_keyframe(d_frames, n_items, capacity, total_q, S.d_match.p, w.d_of_key.p, st);
         TC2LI_HIP_CHECK(hipGetLastError());
     }
-    if (capacity > 0) TC2LI_HIP_CHECK(hipMemcpyAsync(kf_keypoint_of_keypoint, d_of_key, nf * cap1 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(n_matches, d_nm, nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (capacity > 0) TC2LI_HIP_CHECK(hipMemcpyAsync(kf_keypoint_of_keypoint, w.d_of_key.p, nf * cap1 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(n_matches, S.d_nmatch.p, nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     TC2LI_HIP_CHECK(stream_wait_blocking(st));
     return n_items;
 }
@@ -600,16 +548,11 @@ struct LadderWs {
     PinnedBuf<uint8_t> h_stage;
     DevBuf<uint8_t> d_stage, d_u8;
     DevBuf<TrackFrameDev> d_frames;
-    DevBuf<MatchQuery> d_queries;
+    SearchScratch s;
     DevBuf<int32_t> d_i32;
-    DevBuf<float> d_f32;
-    DevBuf<uint16_t> d_items;
-    DevBuf<uint32_t> d_pool;
     DevBuf<PoseProblem> d_probs;
     DevBuf<BaEdge> d_edges;
     DevBuf<double> d_f64;
-    PinnedBuf<int32_t> h_small;
-    PinnedBuf<float> h_ratio;
 };
 LadderWs& lws() { static thread_local LadderWs w; return w; }
 
@@ -626,10 +569,7 @@ extern "C" int tc2li_relocalization_refine_batch(tc2li_orb* o, const tc2li_reloc
         return TC2LI_ERR_INVALID;
     }
     if (n_hyps == 0) return 0;
-    if (2 * n_frames > o->last_nimg || !o->last_plain_order) {
-        set_error("%s: needs the features of a preceding tc2li_orb_extract_batch call with lapping area {0,0} and 2*n_frames images", fn);
-        return TC2LI_ERR_INVALID;
-    }
+    if (!orb_features_ready(o, n_frames, fn)) return TC2LI_ERR_INVALID;
     const int n_levels = o->prm.nlevels;
     if (n_levels > kMaxLevels) { set_error("%s: %d levels (at most %d)", fn, n_levels, kMaxLevels); return TC2LI_ERR_INVALID; }
     size_t nq = 0;
@@ -642,8 +582,8 @@ extern "C" int tc2li_relocalization_refine_batch(tc2li_orb* o, const tc2li_reloc
             return TC2LI_ERR_INVALID;
         }
         const int n = o->last_kp_cnt[2 * Hy.frame_index];
-        if (n > capacity) { set_error("%s: capacity %d < %d keypoints", fn, capacity, n); return TC2LI_ERR_CAPACITY; }
-        if (n > kMaxMatchKeys) { set_error("%s: frame has %d keypoints, the matcher supports %d", fn, n, kMaxMatchKeys); return TC2LI_ERR_CAPACITY; }
+        if (int rc = check_capacity(fn, n, capacity)) return rc;
+        if (int rc = check_match_keys(fn, n)) return rc;
         for (int i = 0; i < n; ++i)
             if (Hy.inlier[i] && (Hy.match[i] < -1 || Hy.match[i] >= Hy.n_points)) {
                 set_error("%s: hypothesis %d: match[%d] = %d is no keypoint of the keyframe (%d)", fn, h, i, Hy.match[i], Hy.n_points);
@@ -653,25 +593,21 @@ extern "C" int tc2li_relocalization_refine_batch(tc2li_orb* o, const tc2li_reloc
     }
     hipStream_t st = stream_ ? (hipStream_t)stream_ : private_stream();
     LadderWs& w = lws();
+    SearchScratch& S = w.s;
     const size_t nh = n_hyps, cap1 = std::max(capacity, 1), q1 = std::max<size_t>(nq, 1), ne = nh * cap1, nfr = std::max(n_frames, 1);
     const int total_q = (int)nq;
-    const size_t o_hp = 0, o_Xw = up256(o_hp + q1), o_pd = up256(o_Xw + 12 * q1), o_min = up256(o_pd + 32 * q1), o_max = up256(o_min + 4 * q1),
-                 o_raw = up256(o_max + 4 * q1), o_pang = up256(o_raw + 4 * q1), o_match = up256(o_pang + 4 * q1), o_inl = up256(o_match + 4 * ne),
-                 o_ur = up256(o_inl + ne), o_neg = up256(o_ur + 4 * nfr * cap1), o_frames = up256(o_neg + 4 * cap1),
-                 o_bounds = up256(o_frames + sizeof(TrackFrameDev) * nh), o_mframes = up256(o_bounds + 16 * nh),
+    const KeyframePointStage pts(0, q1);
+    const size_t o_match = pts.end, o_inl = up256(o_match + 4 * ne), o_ur = up256(o_inl + ne), o_neg = up256(o_ur + 4 * nfr * cap1),
+                 o_frames = up256(o_neg + 4 * cap1), o_bounds = up256(o_frames + sizeof(TrackFrameDev) * nh), o_mframes = up256(o_bounds + 16 * nh),
                  o_kbase = up256(o_mframes + sizeof(MatchFrameDev) * nh), o_foh = up256(o_kbase + 4 * nh), bytes = up256(o_foh + 4 * nh);
     TC2LI_HIP_CHECK(w.h_stage.ensure(bytes)); TC2LI_HIP_CHECK(w.d_stage.ensure(bytes));
-    TC2LI_HIP_CHECK(w.d_frames.ensure(nh)); TC2LI_HIP_CHECK(w.d_queries.ensure(q1));
-    const int pool_cap = 32 * (int)q1;
-    // int32: query_frame, match, prev, cand_off, cand_cnt, amb_ids, amb_level [q1]; rounds, n_matches, active, status, n_good, inliers [nh];
-    // n_additional [nh][2]; cell_start [nh][cells + 1]; pool_top [2]; amb_count [2]; assign, edge_kp [nh][capacity]
-    TC2LI_HIP_CHECK(w.d_i32.ensure(7 * q1 + 8 * nh + nh * kCellsPlus1 + 4 + 2 * ne));
-    TC2LI_HIP_CHECK(w.d_f32.ensure(2 * q1));
+    TC2LI_HIP_CHECK(w.d_frames.ensure(nh));
+    if (int rc = S.ensure(n_hyps, total_q, capacity)) return rc;
+    // int32: active, status, n_good, inliers [nh]; n_additional [nh][2]; assign, edge_kp [nh][capacity]
+    TC2LI_HIP_CHECK(w.d_i32.ensure(6 * nh + 2 * ne));
     TC2LI_HIP_CHECK(w.d_u8.ensure(q1 + 3 * ne));  // found [q1]; occupied, outlier_of_key, outlier [nh][capacity]
-    TC2LI_HIP_CHECK(w.d_items.ensure(ne)); TC2LI_HIP_CHECK(w.d_pool.ensure(pool_cap));
     TC2LI_HIP_CHECK(w.d_probs.ensure(nh)); TC2LI_HIP_CHECK(w.d_edges.ensure(ne));
     TC2LI_HIP_CHECK(w.d_f64.ensure(3 * ne + 7 * nh + 21 * nh + ne));  // Xw, poses, stage_poses, chi2
-    TC2LI_HIP_CHECK(w.h_small.ensure(4 + q1)); TC2LI_HIP_CHECK(w.h_ratio.ensure(q1));
     uint8_t* h = w.h_stage.p;
     uint8_t* d = w.d_stage.p;
     memset(h + o_match, 0xff, 4 * ne);
@@ -686,15 +622,7 @@ extern "C" int tc2li_relocalization_refine_batch(tc2li_orb* o, const tc2li_reloc
     for (int k = 0; k < n_hyps; ++k) {
         const tc2li_reloc_hypothesis& Hy = hyps[k];
         const int n = o->last_kp_cnt[2 * Hy.frame_index], key_off = o->last_kp_off[2 * Hy.frame_index];
-        for (int i = 0; i < Hy.n_points; ++i) h[o_hp + q + i] = Hy.has_point[i] ? 1 : 0;
-        if (Hy.n_points) {
-            memcpy(h + o_Xw + 12 * q, Hy.Xw, 12 * (size_t)Hy.n_points);
-            memcpy(h + o_pd + 32 * q, Hy.point_descriptors, 32 * (size_t)Hy.n_points);
-            memcpy(h + o_min + 4 * q, Hy.min_distance, 4 * (size_t)Hy.n_points);
-            memcpy(h + o_max + 4 * q, Hy.max_distance, 4 * (size_t)Hy.n_points);
-            memcpy(h + o_raw + 4 * q, Hy.max_distance_raw, 4 * (size_t)Hy.n_points);
-            memcpy(h + o_pang + 4 * q, Hy.angle, 4 * (size_t)Hy.n_points);
-        }
+        stage_keyframe_points(pts, h, q, Hy);
         memcpy(h + o_match + 4 * (size_t)k * cap1, Hy.match, 4 * (size_t)n);
         for (int i = 0; i < n; ++i) h[o_inl + (size_t)k * cap1 + i] = Hy.inlier[i] ? 1 : 0;
         TrackFrameDev& F = hf[k];
@@ -704,28 +632,19 @@ extern "C" int tc2li_relocalization_refine_batch(tc2li_orb* o, const tc2li_reloc
         const float B[4] = {0.0f, (float)o->cur_w, 0.0f, (float)o->cur_h};
         memcpy(h + o_bounds + 16 * (size_t)k, B, 16);
         hm[k] = MatchFrameDev{o->d_mkeys.p + key_off, o->d_desc.p + (size_t)key_off * 32, reinterpret_cast<const float*>(d + o_neg), d_occ + (size_t)k * cap1,
-                              w.d_queries.p + q, n, Hy.n_points, (int32_t)q, 0, B[0], B[1], B[2], B[3]};
+                              S.d_queries.p + q, n, Hy.n_points, (int32_t)q, 0, B[0], B[1], B[2], B[3]};
         reinterpret_cast<int32_t*>(h + o_kbase)[k] = (int32_t)(k * cap1);
         reinterpret_cast<int32_t*>(h + o_foh)[k] = Hy.frame_index;
         q += Hy.n_points;
     }
-    TrackConst C;
-    memset(&C, 0, sizeof(C));
-    C.cam4[0] = (float)cam->fx; C.cam4[1] = (float)cam->fy; C.cam4[2] = (float)cam->cx; C.cam4[3] = (float)cam->cy;
-    C.n_levels = n_levels; C.capacity = capacity;
-    C.log_scale = std::log(o->prm.scale_factor);  // mfLogScaleFactor = log(mfScaleFactor) (SF/src/Frame.cc:96)
-    for (int l = 0; l < n_levels; ++l) C.scale[l] = o->scale[l];
+    const TrackConst C = track_const(o, cam, 0.f, capacity);
     TC2LI_HIP_CHECK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
     TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_frames.p, hf, nh * sizeof(TrackFrameDev), hipMemcpyHostToDevice, st));
     int32_t* ip = w.d_i32.p;
-    int32_t *d_qf = ip, *d_match = ip + q1, *d_prev = ip + 2 * q1, *d_coff = ip + 3 * q1, *d_ccnt = ip + 4 * q1, *d_amb_ids = ip + 5 * q1,
-            *d_amb_level = ip + 6 * q1, *d_rounds = ip + 7 * q1, *d_nm = d_rounds + nh, *d_active = d_nm + nh, *d_status = d_active + nh,
-            *d_ngood = d_status + nh, *d_inl = d_ngood + nh, *d_nadd = d_inl + nh, *d_cells = d_nadd + 2 * nh, *d_top = d_cells + nh * kCellsPlus1,
-            *d_amb = d_top + 2, *d_assign = d_amb + 2, *d_edge_kp = d_assign + ne;
-    float *d_amb_ratio = w.d_f32.p, *d_amb_r = w.d_f32.p + q1;
+    int32_t *d_nm = S.d_nmatch.p, *d_active = ip, *d_status = d_active + nh, *d_ngood = d_status + nh, *d_inl = d_ngood + nh, *d_nadd = d_inl + nh,
+            *d_assign = d_nadd + 2 * nh, *d_edge_kp = d_assign + ne;
     double *d_Xw = w.d_f64.p, *d_poses = d_Xw + 3 * ne, *d_stage_poses = d_poses + 7 * nh, *d_chi2 = d_stage_poses + 21 * nh;
-    const KeyframePointArrays A{d + o_hp, d_found, reinterpret_cast<const float*>(d + o_Xw), d + o_pd, reinterpret_cast<const float*>(d + o_min),
-                                reinterpret_cast<const float*>(d + o_max), reinterpret_cast<const float*>(d + o_raw), reinterpret_cast<const float*>(d + o_pang)};
+    const KeyframePointArrays A = pts.arrays(d, d_found);
     RelocLadder L{};
     L.n_hyps = n_hyps; L.capacity = (int)cap1; L.frames = w.d_frames.p; L.frame_of_hyp = reinterpret_cast<const int32_t*>(d + o_foh);
     L.keys = o->d_mkeys.p; L.u_right = reinterpret_cast<const float*>(d + o_ur);
@@ -736,40 +655,18 @@ extern "C" int tc2li_relocalization_refine_batch(tc2li_orb* o, const tc2li_reloc
     L.probs = w.d_probs.p; L.edges = w.d_edges.p; L.Xw = d_Xw; L.edge_kp = d_edge_kp; L.poses = d_poses; L.outlier = d_outl; L.inliers = d_inl;
     CameraD cd;
     memcpy(&cd, cam, sizeof(cd));
-    const MatchFrameDev* d_mframes = reinterpret_cast<const MatchFrameDev*>(d + o_mframes);
-    const MatchLists ML{d_cells, w.d_items.p, reinterpret_cast<const int32_t*>(d + o_kbase), d_coff, d_ccnt, w.d_pool.p, d_top, pool_cap, 0};
     // ORBmatcher matcher2(0.9, true).SearchByProjection(mCurrentFrame, pKF, sFound, th, orb_dist) for the hypotheses k_reloc_ladder_after chose
     auto search = [&](int orb_dist) -> int {
         if (total_q == 0) return TC2LI_OK;
-        TC2LI_HIP_CHECK(hipMemsetAsync(d_amb, 0, sizeof(int32_t), st));
-        launch_track_queries_keyframe(w.d_frames.p, n_hyps, reinterpret_cast<const float4*>(d + o_bounds), C, A, total_q, w.d_queries.p, d_qf, d_match, d_amb,
-                                      d_amb_ids, d_amb_ratio, d_amb_r, st);
-        TC2LI_HIP_CHECK(hipGetLastError());
-        TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_small.p, d_amb, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        TC2LI_HIP_CHECK(stream_wait_blocking(st));
-        const int n_amb = w.h_small.p[0];
-        if (n_amb > 0) {  // MapPoint::PredictScale on a level boundary: the host's logf decides
-            TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_ratio.p, d_amb_ratio, n_amb * sizeof(float), hipMemcpyDeviceToHost, st));
-            TC2LI_HIP_CHECK(stream_wait_blocking(st));
-            int32_t* lev = w.h_small.p + 4;
-            for (int k = 0; k < n_amb; ++k) {
-                int level = (int)ceilf(logf(w.h_ratio.p[k]) / C.log_scale);
-                if (level < 0) level = 0; else if (level >= n_levels) level = n_levels - 1;
-                lev[k] = level;
-            }
-            TC2LI_HIP_CHECK(hipMemcpyAsync(d_amb_level, lev, n_amb * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            launch_track_patch_levels_keyframe(d_amb_ids, d_amb_level, d_amb_r, n_amb, C, w.d_queries.p, st);
-        }
-        launch_match_lists(d_mframes, n_hyps, d_qf, total_q, ML, 0, 0.0f, d_match, d_prev, d_rounds, st, orb_dist);
-        TC2LI_HIP_CHECK(hipGetLastError());
-        TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_small.p, d_top, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        TC2LI_HIP_CHECK(stream_wait_blocking(st));
-        if (w.h_small.p[1]) {  // candidate pool exhausted: the one-kernel form, same result
-            TC2LI_HIP_CHECK(hipMemsetAsync(d_match, 0xff, q1 * sizeof(int32_t), st));
-            launch_match_by_projection(d_mframes, n_hyps, 0, 0.0f, d_match, d_prev, d_rounds, st, orb_dist);
-        }
-        launch_track_count(w.d_frames.p, nullptr, n_hyps, w.d_queries.p, o->d_angles.p, 1, d_match, d_nm, st);
-        launch_track_assign_keyframe(w.d_frames.p, n_hyps, (int)cap1, total_q, d_match, d_assign, st);
+        TC2LI_HIP_CHECK(hipMemsetAsync(S.amb_count(), 0, sizeof(int32_t), st));
+        launch_track_queries_keyframe(w.d_frames.p, n_hyps, reinterpret_cast<const float4*>(d + o_bounds), C, A, total_q, S.d_queries.p, S.d_query_frame.p,
+                                      S.d_match.p, S.amb_count(), S.d_amb_ids.p, S.d_amb_ratio.p, S.d_amb_r.p, st);
+        if (int rc = resolve_ambiguous_levels(S, C, launch_track_patch_levels_keyframe, st)) return rc;
+        const SearchPass P{reinterpret_cast<const MatchFrameDev*>(d + o_mframes), reinterpret_cast<const int32_t*>(d + o_kbase), n_hyps, total_q, hf, nullptr,
+                           0, 0.0f, orb_dist};
+        if (int rc = projection_search(S, P, st)) return rc;  // the follow-up waits for the overflow decision: assign scatters
+        launch_track_count(w.d_frames.p, nullptr, n_hyps, S.d_queries.p, o->d_angles.p, 1, S.d_match.p, d_nm, st);
+        launch_track_assign_keyframe(w.d_frames.p, n_hyps, (int)cap1, total_q, S.d_match.p, d_assign, st);
         TC2LI_HIP_CHECK(hipGetLastError());
         return TC2LI_OK;
     };

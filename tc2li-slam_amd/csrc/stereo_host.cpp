@@ -64,11 +64,7 @@ int tc2li_stereo_match_batch(tc2li_orb* o, int n_frames, float bf, float b, floa
         return TC2LI_ERR_INVALID;
     }
     if (n_frames == 0) return 0;
-    if (2 * n_frames > o->last_nimg || !o->last_plain_order) {
-        set_error("tc2li_stereo_match_batch: needs the features of a preceding tc2li_orb_extract_batch call with "
-                  "lapping area {0,0} and 2*n_frames images");
-        return TC2LI_ERR_INVALID;
-    }
+    if (!orb_features_ready(o, n_frames, "tc2li_stereo_match_batch")) return TC2LI_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream_;
     StereoWorkspace* ws = workspace_for(o);
     std::vector<StereoFrame> frames(n_frames);

@@ -11,17 +11,17 @@
 #include <cstring>
 #include <vector>
 
+#include "balm_math.hpp"  // quat_rotate_f
 #include "common.hpp"
 #include "matcher_device.hpp"
 #include "orb_handle.hpp"
 #include "pose_opt_device.hpp"
+#include "projection_search.hpp"
 #include "tracking_device.hpp"
 
 using namespace tc2li;
 
 namespace {
-
-constexpr int kCellsPlus1 = 64 * 48 + 1;  // the matcher's feature grid (matcher_kernels.hip)
 
 struct TrackWs {
     PinnedBuf<uint8_t> h_stage;
@@ -30,17 +30,9 @@ struct TrackWs {
     DevBuf<TrackFrameDev> d_frames;
     PinnedBuf<MatchFrameDev> h_mframes;
     DevBuf<MatchFrameDev> d_mframes;
-    PinnedBuf<int32_t> h_pass, h_key_base, h_small, h_nmatch, h_amb;
+    PinnedBuf<int32_t> h_pass, h_key_base, h_nmatch;
     DevBuf<int32_t> d_pass, d_key_base;
-    DevBuf<MatchQuery> d_queries;
-    DevBuf<float> d_amb_ratio, d_amb_r;
-    PinnedBuf<float> h_amb_ratio;
-    DevBuf<int32_t> d_amb_ids, d_amb_level;
-    PinnedBuf<int32_t> h_amb_level;
-    DevBuf<int32_t> d_query_frame, d_match, d_prev, d_rounds, d_nmatch, d_amb;
-    DevBuf<int32_t> d_cell_start, d_cand_off, d_cand_cnt, d_pool_top;
-    DevBuf<uint16_t> d_items;
-    DevBuf<uint32_t> d_pool;
+    SearchScratch s;
     DevBuf<PoseProblem> d_probs;
     DevBuf<BaEdge> d_edges;
     DevBuf<double> d_Xw, d_poses, d_chi2;
@@ -50,31 +42,7 @@ struct TrackWs {
 // one work space per host thread: TrackWithMotionModel and TrackLocalMap of different batches run side by side
 TrackWs& tws() { static thread_local TrackWs w; return w; }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-inline void quat_rotate_f(const float q[4], const float v[3], float out[3]) {  // Eigen::Quaternionf::_transformVector
-    float uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    out[0] = v[0] + q[3] * uv[0] + (q[1] * uv[2] - q[2] * uv[1]);
-    out[1] = v[1] + q[3] * uv[1] + (q[2] * uv[0] - q[0] * uv[2]);
-    out[2] = v[2] + q[3] * uv[2] + (q[0] * uv[1] - q[1] * uv[0]);
-}
-
-void fill_const(const tc2li_orb* o, const tc2li_camera* cam, float b, int capacity, TrackConst& C) {
-    memset(&C, 0, sizeof(C));
-    C.cam4[0] = (float)cam->fx; C.cam4[1] = (float)cam->fy; C.cam4[2] = (float)cam->cx; C.cam4[3] = (float)cam->cy;
-    C.b = b; C.bf = (float)cam->bf;
-    C.n_levels = o->prm.nlevels;
-    for (int l = 0; l < C.n_levels; ++l) { C.scale[l] = o->scale[l]; C.inv_sigma2[l] = o->inv_sigma2[l]; }
-    C.cols = o->cur_w; C.rows = o->cur_h; C.capacity = capacity;
-    C.log_scale = std::log(o->prm.scale_factor);  // mfLogScaleFactor = log(mfScaleFactor) (SF/src/Frame.cc:96)
-}
-
-}  // namespace
-
-// ------------------------------------------------------------------------------------------------------------------------------------
-namespace {
-
+// The searches of one call: SearchByProjection for the frames of a pass, the rotation filter and the match counts.
 struct Pass {
     TrackWs& w;
     tc2li_orb* o;
@@ -85,58 +53,37 @@ struct Pass {
     float nn_ratio;
     bool check_orientation;
     hipStream_t st;
-    int pool_cap = 0;
 
     int prepare() {
-        const char* per_query = getenv("TC2LI_MATCH_POOL_PER_QUERY");  // tests shrink the pool to reach the overflow path
-        pool_cap = std::max(1, per_query ? atoi(per_query) : 32) * std::max(total_q, 1);
         TC2LI_HIP_CHECK(w.d_mframes.ensure(n_frames)); TC2LI_HIP_CHECK(w.h_mframes.ensure(n_frames));
         TC2LI_HIP_CHECK(w.d_pass.ensure(n_frames)); TC2LI_HIP_CHECK(w.h_pass.ensure(n_frames));
         TC2LI_HIP_CHECK(w.d_key_base.ensure(n_frames)); TC2LI_HIP_CHECK(w.h_key_base.ensure(n_frames));
-        TC2LI_HIP_CHECK(w.d_prev.ensure(std::max(total_q, 1))); TC2LI_HIP_CHECK(w.d_rounds.ensure(n_frames));
-        TC2LI_HIP_CHECK(w.d_nmatch.ensure(n_frames)); TC2LI_HIP_CHECK(w.h_nmatch.ensure(n_frames));
-        TC2LI_HIP_CHECK(w.d_cell_start.ensure((size_t)n_frames * kCellsPlus1));
-        TC2LI_HIP_CHECK(w.d_cand_off.ensure(std::max(total_q, 1))); TC2LI_HIP_CHECK(w.d_cand_cnt.ensure(std::max(total_q, 1)));
-        TC2LI_HIP_CHECK(w.d_pool_top.ensure(2)); TC2LI_HIP_CHECK(w.h_small.ensure(8));
-        TC2LI_HIP_CHECK(w.d_items.ensure((size_t)n_frames * std::max(capacity, 1))); TC2LI_HIP_CHECK(w.d_pool.ensure(pool_cap));
-        return TC2LI_OK;
+        TC2LI_HIP_CHECK(w.h_nmatch.ensure(n_frames));
+        return w.s.ensure(n_frames, total_q, capacity);
     }
-    // frames of the pass are in w.h_pass[0 .. n_pass); their TrackFrameDev (slot set) are on the device already
-    int queue(int n_pass, bool lists) {
+    // frames of the pass are in w.h_pass[0 .. n_pass); their TrackFrameDev (slot set) are on the device already.  Returns with the
+    // stream drained and w.h_nmatch holding every frame's count (the pass rewrote its own): the count rides behind the list form.
+    int search(int n_pass) {
         for (int k = 0; k < n_pass; ++k) {
             const int f = w.h_pass.p[k];
             const TrackFrameDev& F = w.h_frames.p[f];
             w.h_mframes.p[k] = MatchFrameDev{o->d_mkeys.p + F.key_off, o->d_desc.p + (size_t)F.key_off * 32, d_ur + (size_t)f * capacity,
-                                             d_occ ? d_occ + (size_t)f * capacity : nullptr, w.d_queries.p + F.q_off, F.n_keys, F.n_q, F.q_off, 0,
+                                             d_occ ? d_occ + (size_t)f * capacity : nullptr, w.s.d_queries.p + F.q_off, F.n_keys, F.n_q, F.q_off, 0,
                                              0.0f, (float)o->cur_w, 0.0f, (float)o->cur_h};
             w.h_key_base.p[k] = f * capacity;
         }
         TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_mframes.p, w.h_mframes.p, n_pass * sizeof(MatchFrameDev), hipMemcpyHostToDevice, st));
         TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_key_base.p, w.h_key_base.p, n_pass * sizeof(int32_t), hipMemcpyHostToDevice, st));
         TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_pass.p, w.h_pass.p, n_pass * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (lists) {
-            MatchLists L{w.d_cell_start.p, w.d_items.p, w.d_key_base.p, w.d_cand_off.p, w.d_cand_cnt.p, w.d_pool.p, w.d_pool_top.p, pool_cap, 0};
-            launch_match_lists(w.d_mframes.p, n_pass, w.d_query_frame.p, total_q, L, mode, nn_ratio, w.d_match.p, w.d_prev.p, w.d_rounds.p, st);
-            TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_small.p, w.d_pool_top.p, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        } else {  // the one-kernel form: same result, no candidate pool
-            launch_match_by_projection(w.d_mframes.p, n_pass, mode, nn_ratio, w.d_match.p, w.d_prev.p, w.d_rounds.p, st);
-            w.h_small.p[1] = 0;
-        }
-        launch_track_count(w.d_frames.p, w.d_pass.p, n_pass, w.d_queries.p, o->d_angles.p, check_orientation ? 1 : 0, w.d_match.p, w.d_nmatch.p, st);
-        TC2LI_HIP_CHECK(hipGetLastError());
-        TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_nmatch.p, w.d_nmatch.p, n_frames * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        return TC2LI_OK;
+        const SearchPass P{w.d_mframes.p, w.d_key_base.p, n_pass, total_q, w.h_frames.p, w.h_pass.p, mode, nn_ratio, kMatchThHigh};
+        return projection_search(w.s, P, st, [&]() -> int {
+            launch_track_count(w.d_frames.p, w.d_pass.p, n_pass, w.s.d_queries.p, o->d_angles.p, check_orientation ? 1 : 0, w.s.d_match.p, w.s.d_nmatch.p, st);
+            TC2LI_HIP_CHECK(hipGetLastError());
+            TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_nmatch.p, w.s.d_nmatch.p, n_frames * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            return TC2LI_OK;
+        });
     }
 };
-
-// Resets the matches of the pass's frames (the query kernels do that when they rebuild the queries; the overflow path needs it alone).
-int reset_matches(TrackWs& w, int n_pass, hipStream_t st) {
-    for (int k = 0; k < n_pass; ++k) {
-        const TrackFrameDev& F = w.h_frames.p[w.h_pass.p[k]];
-        if (F.n_q) TC2LI_HIP_CHECK(hipMemsetAsync(w.d_match.p + F.q_off, 0xff, (size_t)F.n_q * sizeof(int32_t), st));
-    }
-    return TC2LI_OK;
-}
 
 }  // namespace
 
@@ -144,25 +91,22 @@ extern "C" int tc2li_track_motion_model_batch(tc2li_orb* o, int n_frames, const 
                                               int capacity, const tc2li_last_frame* last, const float* pose_pred7,
                                               const tc2li_camera* cam, float b, float th, double* poses7,
                                               int32_t* map_point_of_keypoint, int32_t* n_matches, int32_t* n_inliers, void* stream_) {
+    const char* fn = "tc2li_track_motion_model_batch";
     if (!o || n_frames < 0 || capacity < 0 || !keypoints || !u_right || !last || !pose_pred7 || !cam || !poses7 || !map_point_of_keypoint ||
         !n_matches || !n_inliers) {
-        set_error("tc2li_track_motion_model_batch: invalid argument");
+        set_error("%s: invalid argument", fn);
         return TC2LI_ERR_INVALID;
     }
     if (n_frames == 0) return 0;
-    if (2 * n_frames > o->last_nimg || !o->last_plain_order) {
-        set_error("tc2li_track_motion_model_batch: needs the features of a preceding tc2li_orb_extract_batch call with lapping area "
-                  "{0,0} and 2*n_frames images");
-        return TC2LI_ERR_INVALID;
-    }
+    if (!orb_features_ready(o, n_frames, fn)) return TC2LI_ERR_INVALID;
     if (!device_ready()) return TC2LI_ERR_NO_DEVICE;
     hipStream_t st = (hipStream_t)stream_;
     static const bool kTiming = getenv("TC2LI_TRACK_TIMING") != nullptr;
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double tm[6] = {0, 0, 0, 0, 0, 0}, t0 = now();
     TrackWs& w = tws();
-    TrackConst C;
-    fill_const(o, cam, b, capacity, C);
+    SearchScratch& S = w.s;
+    const TrackConst C = track_const(o, cam, b, capacity);
     const int L = C.n_levels;
 
     TC2LI_HIP_CHECK(w.h_frames.ensure(n_frames)); TC2LI_HIP_CHECK(w.d_frames.ensure(n_frames));
@@ -172,8 +116,8 @@ extern "C" int tc2li_track_motion_model_batch(tc2li_orb* o, int n_frames, const 
         memset(&F, 0, sizeof(F));
         F.key_off = o->last_kp_off[2 * f];
         F.n_keys = o->last_kp_cnt[2 * f];
-        if (F.n_keys > capacity) { set_error("capacity %d < %d keypoints", capacity, F.n_keys); return TC2LI_ERR_CAPACITY; }
-        if (F.n_keys > kMaxMatchKeys) { set_error("frame has %d keypoints, the matcher supports %d", F.n_keys, kMaxMatchKeys); return TC2LI_ERR_CAPACITY; }
+        if (int rc = check_capacity(fn, F.n_keys, capacity)) return rc;
+        if (int rc = check_match_keys(fn, F.n_keys)) return rc;
         if (last[f].n < 0 || (last[f].n > 0 && (!last[f].has_point || !last[f].outlier || !last[f].Xw || !last[f].keys || !last[f].descriptors))) {
             set_error("tc2li_track_motion_model_batch: last frame %d has null arrays", f);
             return TC2LI_ERR_INVALID;
@@ -225,26 +169,18 @@ extern "C" int tc2li_track_motion_model_batch(tc2li_orb* o, int n_frames, const 
     const LastFrameArrays A{ds + o_flags, reinterpret_cast<const float*>(ds + o_Xw), reinterpret_cast<const float*>(ds + o_ang),
                             reinterpret_cast<const int32_t*>(ds + o_oct), ds + o_desc};
     const float* d_ur = reinterpret_cast<const float*>(ds + o_ur);
-    TC2LI_HIP_CHECK(w.d_queries.ensure(nq)); TC2LI_HIP_CHECK(w.d_query_frame.ensure(nq)); TC2LI_HIP_CHECK(w.d_match.ensure(nq));
     Pass pass{w, o, n_frames, total_q, capacity, d_ur, nullptr, 0, 0.9f, true, st};
     int rc = pass.prepare();
     if (rc != TC2LI_OK) return rc;
     for (int f = 0; f < n_frames; ++f) w.h_pass.p[f] = f;
     if (total_q > 0) {
-        launch_track_queries_last(w.d_frames.p, n_frames, C, A, total_q, w.d_queries.p, w.d_query_frame.p, w.d_match.p, st);
-        rc = pass.queue(n_frames, true);
+        launch_track_queries_last(w.d_frames.p, n_frames, C, A, total_q, S.d_queries.p, S.d_query_frame.p, S.d_match.p, st);
+        rc = pass.search(n_frames);
         if (rc != TC2LI_OK) return rc;
-        TC2LI_HIP_CHECK(stream_wait_blocking(st));
-        if (w.h_small.p[1]) {  // candidate pool exhausted (very dense windows)
-            rc = reset_matches(w, n_frames, st);
-            if (rc == TC2LI_OK) rc = pass.queue(n_frames, false);
-            if (rc != TC2LI_OK) return rc;
-            TC2LI_HIP_CHECK(stream_wait_blocking(st));
-        }
         memcpy(n_matches, w.h_nmatch.p, n_frames * sizeof(int32_t));
     } else {
         for (int f = 0; f < n_frames; ++f) n_matches[f] = 0;
-        TC2LI_HIP_CHECK(hipMemsetAsync(w.d_nmatch.p, 0, n_frames * sizeof(int32_t), st));
+        TC2LI_HIP_CHECK(hipMemsetAsync(S.d_nmatch.p, 0, n_frames * sizeof(int32_t), st));
     }
     tm[1] = now() - t0; t0 = now();
     // fewer than 20 matches: wider window (Tracking.cc:2774-2783), those frames only
@@ -256,16 +192,9 @@ extern "C" int tc2li_track_motion_model_batch(tc2li_orb* o, int n_frames, const 
     }
     if (n_retry > 0) {
         TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_frames.p, w.h_frames.p, n_frames * sizeof(TrackFrameDev), hipMemcpyHostToDevice, st));
-        launch_track_queries_last(w.d_frames.p, n_frames, C, A, total_q, w.d_queries.p, w.d_query_frame.p, w.d_match.p, st);
-        rc = pass.queue(n_retry, true);
+        launch_track_queries_last(w.d_frames.p, n_frames, C, A, total_q, S.d_queries.p, S.d_query_frame.p, S.d_match.p, st);
+        rc = pass.search(n_retry);
         if (rc != TC2LI_OK) return rc;
-        TC2LI_HIP_CHECK(stream_wait_blocking(st));
-        if (w.h_small.p[1]) {
-            rc = reset_matches(w, n_retry, st);
-            if (rc == TC2LI_OK) rc = pass.queue(n_retry, false);
-            if (rc != TC2LI_OK) return rc;
-            TC2LI_HIP_CHECK(stream_wait_blocking(st));
-        }
         memcpy(n_matches, w.h_nmatch.p, n_frames * sizeof(int32_t));  // d_nmatch holds every frame: the pass rewrote its own
     }
     tm[2] = now() - t0; t0 = now();
@@ -274,12 +203,12 @@ extern "C" int tc2li_track_motion_model_batch(tc2li_orb* o, int n_frames, const 
     TC2LI_HIP_CHECK(w.d_of_key.ensure(ne)); TC2LI_HIP_CHECK(w.d_probs.ensure(n_frames)); TC2LI_HIP_CHECK(w.d_edges.ensure(ne)); TC2LI_HIP_CHECK(w.d_Xw.ensure(3 * ne));
     TC2LI_HIP_CHECK(w.d_edge_kp.ensure(ne)); TC2LI_HIP_CHECK(w.d_poses.ensure(7 * (size_t)n_frames)); TC2LI_HIP_CHECK(w.d_outlier.ensure(ne));
     TC2LI_HIP_CHECK(w.d_chi2.ensure(ne)); TC2LI_HIP_CHECK(w.d_inliers.ensure(n_frames)); TC2LI_HIP_CHECK(w.d_ninl.ensure(n_frames));
-    launch_track_edges_last(w.d_frames.p, n_frames, C, o->d_mkeys.p, d_ur, w.d_match.p, w.d_nmatch.p, A.Xw, w.d_of_key.p, w.d_probs.p, w.d_edges.p, w.d_Xw.p,
+    launch_track_edges_last(w.d_frames.p, n_frames, C, o->d_mkeys.p, d_ur, S.d_match.p, S.d_nmatch.p, A.Xw, w.d_of_key.p, w.d_probs.p, w.d_edges.p, w.d_Xw.p,
                             w.d_edge_kp.p, w.d_poses.p, st);
     CameraD cd;
     memcpy(&cd, cam, sizeof(cd));
     launch_pose_optimization(w.d_probs.p, n_frames, w.d_Xw.p, w.d_edges.p, cd, w.d_poses.p, w.d_outlier.p, w.d_chi2.p, w.d_inliers.p, capacity, st);
-    launch_track_finish_last(w.d_frames.p, n_frames, capacity, w.d_nmatch.p, w.d_probs.p, w.d_outlier.p, w.d_edge_kp.p, w.d_inliers.p, w.d_of_key.p, w.d_poses.p,
+    launch_track_finish_last(w.d_frames.p, n_frames, capacity, S.d_nmatch.p, w.d_probs.p, w.d_outlier.p, w.d_edge_kp.p, w.d_inliers.p, w.d_of_key.p, w.d_poses.p,
                              w.d_ninl.p, st);
     TC2LI_HIP_CHECK(hipGetLastError());
     TC2LI_HIP_CHECK(hipMemcpyAsync(map_point_of_keypoint, w.d_of_key.p, ne * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -301,17 +230,14 @@ static int track_local_map_impl(tc2li_orb* o, int n_frames, const tc2li_keypoint
                                 const int32_t* local_offsets, const tc2li_camera* cam, float th, int far_points, float th_far_points,
                                 double* poses7_out, int32_t* local_of_keypoint, uint8_t* outlier, int32_t* n_matches,
                                 int32_t* n_inliers, void* stream_, const bool optimise) {
+    const char* fn = "tc2li_track_local_map_batch";
     if (!o || n_frames < 0 || capacity < 0 || !keypoints || !u_right || !poses7 || !held || !held_Xw || !local_offsets || !cam || !local_of_keypoint || !n_matches ||
         (optimise && (!poses7_out || !outlier || !n_inliers))) {
-        set_error("tc2li_track_local_map_batch: invalid argument");
+        set_error("%s: invalid argument", fn);
         return TC2LI_ERR_INVALID;
     }
     if (n_frames == 0) return 0;
-    if (2 * n_frames > o->last_nimg || !o->last_plain_order) {
-        set_error("tc2li_track_local_map_batch: needs the features of a preceding tc2li_orb_extract_batch call with lapping area {0,0} and "
-                  "2*n_frames images");
-        return TC2LI_ERR_INVALID;
-    }
+    if (!orb_features_ready(o, n_frames, fn)) return TC2LI_ERR_INVALID;
     if (local_offsets[0] != 0) { set_error("tc2li_track_local_map_batch: local_offsets[0] must be 0"); return TC2LI_ERR_INVALID; }
     const int total_q = local_offsets[n_frames];
     if (total_q < 0 || (total_q > 0 && !local_points)) { set_error("tc2li_track_local_map_batch: invalid local points"); return TC2LI_ERR_INVALID; }
@@ -322,8 +248,8 @@ static int track_local_map_impl(tc2li_orb* o, int n_frames, const tc2li_keypoint
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double tm[5] = {0, 0, 0, 0, 0}, t0 = now();
     TrackWs& w = tws();
-    TrackConst C;
-    fill_const(o, cam, 0.f, capacity, C);
+    SearchScratch& S = w.s;
+    TrackConst C = track_const(o, cam, 0.f, capacity);
     C.far_points = far_points; C.th_far = th_far_points; C.view_cos_limit = 0.5f;
 
     TC2LI_HIP_CHECK(w.h_frames.ensure(n_frames)); TC2LI_HIP_CHECK(w.d_frames.ensure(n_frames));
@@ -332,8 +258,8 @@ static int track_local_map_impl(tc2li_orb* o, int n_frames, const tc2li_keypoint
         memset(&F, 0, sizeof(F));
         F.key_off = o->last_kp_off[2 * f];
         F.n_keys = o->last_kp_cnt[2 * f];
-        if (F.n_keys > capacity) { set_error("capacity %d < %d keypoints", capacity, F.n_keys); return TC2LI_ERR_CAPACITY; }
-        if (F.n_keys > kMaxMatchKeys) { set_error("frame has %d keypoints, the matcher supports %d", F.n_keys, kMaxMatchKeys); return TC2LI_ERR_CAPACITY; }
+        if (int rc = check_capacity(fn, F.n_keys, capacity)) return rc;
+        if (int rc = check_match_keys(fn, F.n_keys)) return rc;
         if (local_offsets[f + 1] < local_offsets[f]) { set_error("tc2li_track_local_map_batch: local_offsets must not decrease"); return TC2LI_ERR_INVALID; }
         F.q_off = local_offsets[f]; F.n_q = local_offsets[f + 1] - local_offsets[f];
         memcpy(F.pose7, poses7 + 7 * (size_t)f, 7 * sizeof(float));
@@ -364,52 +290,23 @@ static int track_local_map_impl(tc2li_orb* o, int n_frames, const tc2li_keypoint
     const float* d_ur = reinterpret_cast<const float*>(ds + o_ur);
     const uint8_t* d_held = ds + o_held;
     const float* d_hx = reinterpret_cast<const float*>(ds + o_hx);
-    TC2LI_HIP_CHECK(w.d_queries.ensure(nq)); TC2LI_HIP_CHECK(w.d_query_frame.ensure(nq)); TC2LI_HIP_CHECK(w.d_match.ensure(nq));
-    TC2LI_HIP_CHECK(w.d_occ.ensure(nk)); TC2LI_HIP_CHECK(w.d_amb.ensure(1)); TC2LI_HIP_CHECK(w.h_amb.ensure(1));
-    TC2LI_HIP_CHECK(w.d_amb_ids.ensure(nq)); TC2LI_HIP_CHECK(w.d_amb_ratio.ensure(nq)); TC2LI_HIP_CHECK(w.d_amb_r.ensure(nq)); TC2LI_HIP_CHECK(w.d_amb_level.ensure(nq));
-    TC2LI_HIP_CHECK(w.h_amb_ratio.ensure(nq)); TC2LI_HIP_CHECK(w.h_amb_level.ensure(nq));
+    TC2LI_HIP_CHECK(w.d_occ.ensure(nk));
     Pass pass{w, o, n_frames, total_q, capacity, d_ur, w.d_occ.p, 1, 0.8f, false, st};
     int rc = pass.prepare();
     if (rc != TC2LI_OK) return rc;
     for (int f = 0; f < n_frames; ++f) w.h_pass.p[f] = f;
     launch_track_occupied(d_held, nk, w.d_occ.p, st);
     if (total_q > 0) {
-        TC2LI_HIP_CHECK(hipMemsetAsync(w.d_amb.p, 0, sizeof(int32_t), st));
-        launch_track_queries_local(w.d_frames.p, n_frames, C, d_pts, total_q, w.d_queries.p, w.d_query_frame.p, w.d_match.p, w.d_amb.p, w.d_amb_ids.p, w.d_amb_ratio.p,
-                                   w.d_amb_r.p, st);
-        TC2LI_HIP_CHECK(hipGetLastError());
+        TC2LI_HIP_CHECK(hipMemsetAsync(S.amb_count(), 0, sizeof(int32_t), st));
+        launch_track_queries_local(w.d_frames.p, n_frames, C, d_pts, total_q, S.d_queries.p, S.d_query_frame.p, S.d_match.p, S.amb_count(), S.d_amb_ids.p,
+                                   S.d_amb_ratio.p, S.d_amb_r.p, st);
         // MapPoint::PredictScale on a level boundary: the host's logf decides (see k_track_queries_local).  One count comes back; the
-        // listed ratios get their level here and a patch kernel writes level and window before the search starts.
-        TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_amb.p, w.d_amb.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        TC2LI_HIP_CHECK(stream_wait_blocking(st));
-        const int n_amb = w.h_amb.p[0];
-        if (n_amb > 0) {
-            TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_amb_ratio.p, w.d_amb_ratio.p, n_amb * sizeof(float), hipMemcpyDeviceToHost, st));
-            TC2LI_HIP_CHECK(stream_wait_blocking(st));
-            const float ls = C.log_scale;
-            const int nl = C.n_levels;
-            const int chunk = 16384, n_chunks = (n_amb + chunk - 1) / chunk;
-            tracking_pool().parallel_for(n_chunks, [&](int c) {
-                const int k1 = std::min(n_amb, (c + 1) * chunk);
-                for (int k = c * chunk; k < k1; ++k) {
-                    int level = (int)ceilf(logf(w.h_amb_ratio.p[k]) / ls);  // as tc2li_project_local_map / MapPoint::PredictScale
-                    if (level < 0) level = 0; else if (level >= nl) level = nl - 1;
-                    w.h_amb_level.p[k] = level;
-                }
-            });
-            TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_amb_level.p, w.h_amb_level.p, n_amb * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            launch_track_patch_levels(w.d_amb_ids.p, w.d_amb_level.p, w.d_amb_r.p, n_amb, C, w.d_queries.p, st);
-        }
-        tm[1] = now() - t0; t0 = now();
-        rc = pass.queue(n_frames, true);
+        // listed ratios get their level on the host and a patch kernel writes level and window before the search starts.
+        rc = resolve_ambiguous_levels(S, C, launch_track_patch_levels, st);
         if (rc != TC2LI_OK) return rc;
-        TC2LI_HIP_CHECK(stream_wait_blocking(st));
-        if (w.h_small.p[1]) {
-            rc = reset_matches(w, n_frames, st);
-            if (rc == TC2LI_OK) rc = pass.queue(n_frames, false);
-            if (rc != TC2LI_OK) return rc;
-            TC2LI_HIP_CHECK(stream_wait_blocking(st));
-        }
+        tm[1] = now() - t0; t0 = now();
+        rc = pass.search(n_frames);
+        if (rc != TC2LI_OK) return rc;
         memcpy(n_matches, w.h_nmatch.p, n_frames * sizeof(int32_t));
     } else {
         for (int f = 0; f < n_frames; ++f) n_matches[f] = 0;
@@ -421,7 +318,7 @@ static int track_local_map_impl(tc2li_orb* o, int n_frames, const tc2li_keypoint
     TC2LI_HIP_CHECK(w.d_edge_kp.ensure(ne)); TC2LI_HIP_CHECK(w.d_poses.ensure(7 * (size_t)n_frames)); TC2LI_HIP_CHECK(w.d_outlier.ensure(ne));
     TC2LI_HIP_CHECK(w.d_chi2.ensure(ne)); TC2LI_HIP_CHECK(w.d_inliers.ensure(n_frames)); TC2LI_HIP_CHECK(w.d_ninl.ensure(n_frames));
     TC2LI_HIP_CHECK(w.d_outlier_key.ensure(ne));
-    launch_track_edges_local(w.d_frames.p, n_frames, C, o->d_mkeys.p, d_ur, w.d_match.p, d_held, d_hx, d_pts, w.d_of_key.p, w.d_probs.p, w.d_edges.p, w.d_Xw.p,
+    launch_track_edges_local(w.d_frames.p, n_frames, C, o->d_mkeys.p, d_ur, S.d_match.p, d_held, d_hx, d_pts, w.d_of_key.p, w.d_probs.p, w.d_edges.p, w.d_Xw.p,
                              w.d_edge_kp.p, w.d_poses.p, st);
     if (!optimise) {  // the keypoints' new map points are what the caller wants; the optimisation is the pose-inertial one, elsewhere
         TC2LI_HIP_CHECK(hipGetLastError());

@@ -266,18 +266,20 @@ def predict_scale(max_distance_raw, dist, log_scale_factor, n_levels):
 def search_by_projection_keyframe(oracle, frame, kf, cam4, scale_factors, log_scale_factor, th, orb_dist, check_orientation):
     """SF/src/ORBmatcher.cc:1898-2019 with the frame's image bounds 0 .. cols, 0 .. rows (what oracle.features_in_area's grid covers).
     frame: keys, descriptors, held, pose7 (float32), cols, rows; kf: has_point, found, Xw, point_descriptors, min_distance, max_distance,
-    max_distance_raw, angle -> (kf_keypoint_of_keypoint [N] for the new matches, nmatches, how many points every gate rejected)."""
+    max_distance_raw, angle -> (kf_keypoint_of_keypoint [N] for the new matches, nmatches, how many points every gate rejected; under
+    "candidates" the keypoints in the points' windows that the frame did not hold on entry: what a candidate pool has to take)."""
     keys = frame["keys"]
     N = len(keys)
     assigned = np.full(N, -1, np.int32)
     held = np.asarray(frame["held"]).astype(bool).copy()
+    held_on_entry = held.copy()
     q = [F32(x) for x in frame["pose7"]]
     fx, fy, cx, cy = [F32(x) for x in cam4]
     min_x, max_x, min_y, max_y = F32(0), F32(frame["cols"]), F32(0), F32(frame["rows"])
     Ow = quat_rotate([F32(-q[0]), F32(-q[1]), F32(-q[2]), q[3]], [F32(q[4] * F32(-1)), F32(q[5] * F32(-1)), F32(q[6] * F32(-1))])
     rot_hist = [[] for _ in range(30)]
     nmatches = 0
-    rejected = dict(bounds=0, distance=0, orb_dist=0, histogram=0)
+    rejected = dict(bounds=0, distance=0, orb_dist=0, histogram=0, candidates=0)
     for i in range(len(kf["has_point"])):
         if not kf["has_point"][i] or kf["found"][i]:
             continue
@@ -299,6 +301,7 @@ def search_by_projection_keyframe(oracle, frame, kf, cam4, scale_factors, log_sc
         idx = oracle.features_in_area(keys, frame["cols"], frame["rows"], float(u), float(v), float(radius), level - 1, level + 1)
         if len(idx) == 0:
             continue
+        rejected["candidates"] += int((~held_on_entry[np.asarray(idx, np.int64)]).sum())
         best_dist, best_idx = 256, -1
         for i2 in idx:
             if held[i2]:
@@ -337,7 +340,8 @@ def relocalization_refine(oracle, frame, kf, pose7, match, inlier, cam5, inv_sig
     made here); match / inlier per frame keypoint.  device_poses [3][7]: when given, every stage after a PoseOptimization goes on from the
     device's pose of that stage instead of the oracle's (the searches then see the device's float pose exactly).
     -> dict(status, n_good, n_additional [2], poses [3][7] (the oracle's), outliers [3] (per keypoint, None for a stage that did not run),
-    searches [2] ((assignment, nmatches) of the search alone, None when it did not run), assign, outlier)."""
+    searches [2] ((assignment, nmatches, held, found, pose, window candidates) of the search alone, None when it did not run), assign,
+    outlier)."""
     keys = frame["keys"]
     N = len(keys)
     cam4 = [cam5[0], cam5[1], cam5[2], cam5[3]]
@@ -365,8 +369,8 @@ def relocalization_refine(oracle, frame, kf, pose7, match, inlier, cam5, inv_sig
 
     def search(th, orb_dist, which):
         fr = dict(keys=keys, descriptors=frame["descriptors"], held=(assign >= 0).astype(np.uint8), pose7=pose, cols=frame["cols"], rows=frame["rows"])
-        new, n, _ = search_by_projection_keyframe(oracle, fr, dict(kf, found=found), cam4, scale_factors, log_scale_factor, th, orb_dist, True)
-        out["searches"][which] = (new.copy(), n, fr["held"].copy(), found.copy(), pose.copy())
+        new, n, rej = search_by_projection_keyframe(oracle, fr, dict(kf, found=found), cam4, scale_factors, log_scale_factor, th, orb_dist, True)
+        out["searches"][which] = (new.copy(), n, fr["held"].copy(), found.copy(), pose.copy(), rej["candidates"])
         out["n_additional"][which] = n
         out["status"] |= (SEARCH1, SEARCH2)[which]
         assign[new >= 0] = new[new >= 0]

@@ -382,8 +382,11 @@ def _cam4(synthetic):
     return np.float32([synthetic.FX, synthetic.FY, synthetic.CX, synthetic.CY])
 
 
-def test_search_by_projection_keyframe_batch(pkg, oracle, synthetic, reloc_scene):
-    S = reloc_scene
+def _check_search_by_projection_keyframe(pkg, oracle, synthetic, S):
+    """Runs the search for both windows with and without the rotation filter and checks every result against reloc_ref.py.  Returns the
+    results and, per search, (th, the window candidates of all items, the queries of the batch): with one pool entry per query a search
+    overflows the pool when it has more candidates than queries."""
+    got, pool = [], []
     sf = S["scale_factors"]
     log_sf = float(np.log(np.float32(sf[1])))          # mfLogScaleFactor = log(mfScaleFactor)
     rng = np.random.default_rng(31)
@@ -401,7 +404,8 @@ def test_search_by_projection_keyframe_batch(pkg, oracle, synthetic, reloc_scene
     for th, orb_dist in ((10, 100), (3, 64)):
         for orient in (True, False):
             match, nm = pkg.search_by_projection_keyframe_batch(items, cam4, sf, log_sf, th, orb_dist, orient, capacity=S["ext"].capacity)
-            total = dict(bounds=0, distance=0, orb_dist=0, histogram=0)
+            got += [match, nm]
+            total = dict(bounds=0, distance=0, orb_dist=0, histogram=0, candidates=0)
             for f in range(len(items)):
                 want, n, rejected = R.search_by_projection_keyframe(oracle, ref_frames[f], ref_kfs[f], cam4, sf, log_sf, th, orb_dist, orient)
                 N = len(want)
@@ -413,6 +417,24 @@ def test_search_by_projection_keyframe_batch(pkg, oracle, synthetic, reloc_scene
             print("th %d ORBdist %d orientation %s: matches %s, rejected %s" % (th, orb_dist, orient, nm.tolist(), total))
             assert total["bounds"] > 0 and total["distance"] > 0 and total["orb_dist"] > 0, total
             assert (total["histogram"] > 0) == orient, total
+            pool.append((th, total["candidates"], sum(len(kf["has_point"]) for kf in ref_kfs)))
+    return got, pool
+
+
+def test_search_by_projection_keyframe_batch(pkg, oracle, synthetic, reloc_scene):
+    _check_search_by_projection_keyframe(pkg, oracle, synthetic, reloc_scene)
+
+
+def test_search_by_projection_keyframe_pool_overflow_takes_the_one_kernel_path(pkg, oracle, synthetic, reloc_scene, monkeypatch):
+    """With a candidate pool of one entry per query the list form overflows and the batch falls back to the one-kernel matcher: the
+    results equal reloc_ref.py's (checked inside) and the default run's, array for array.  That the pool overflows is reloc_ref.py's count:
+    the th = 10 searches have more window candidates than the batch has queries."""
+    ref, _ = _check_search_by_projection_keyframe(pkg, oracle, synthetic, reloc_scene)
+    monkeypatch.setenv("TC2LI_MATCH_POOL_PER_QUERY", "1")
+    got, pool = _check_search_by_projection_keyframe(pkg, oracle, synthetic, reloc_scene)
+    print("(th, window candidates, queries):", pool)
+    assert all(cand > queries for th, cand, queries in pool if th == 10) and [th for th, _, _ in pool] == [10, 10, 3, 3], pool
+    assert len(got) == len(ref) and all(np.array_equal(a, b) for a, b in zip(got, ref))
 
 
 # ---- the refinement ladder ---------------------------------------------------------------------------------------------------------------
@@ -423,11 +445,13 @@ def _restrict(kf, keep):
     return dict(kf, has_point=hp)
 
 
-def test_relocalization_refine_batch(pkg, oracle, synthetic, reloc_scene):
+def _check_relocalization_refine(pkg, oracle, synthetic, S, dense=False):
     """Hypotheses from SearchByBoW matches (ratio 0.75), a true pose a few centimetres off and only the first k matches flagged as inliers;
     candidates with few points steer the searches, so that the batch reaches every exit of the ladder.  Every stage is checked from the
-    device's own pose of the previous stage: searches byte for byte, each PoseOptimization against the oracle on the same edges."""
-    S = reloc_scene
+    device's own pose of the previous stage: searches byte for byte, each PoseOptimization against the oracle on the same edges.  `dense`
+    keeps only hypotheses whose candidate has all its points, so that nearly every query of the batch is a live one.  Returns the batch's
+    outputs and, per search, (its window candidates over all hypotheses, the queries of the batch): with one pool entry per query a
+    search overflows the pool when it has more candidates than queries."""
     sf = S["scale_factors"]
     log_sf = float(np.log(np.float32(sf[1])))
     ext = S["ext"]
@@ -464,6 +488,13 @@ def test_relocalization_refine_batch(pkg, oracle, synthetic, reloc_scene):
             hyps.append(dict(frame_index=f, pose7=pose, match=match, inlier=inl, **{n: cand[n] for n in (
                 "has_point", "Xw", "point_descriptors", "min_distance", "max_distance", "max_distance_raw", "angle")}))
             refs.append((f, cand, inl))
+        if dense:
+            hyp(14, kf)
+            for shift in (0.3, 0.6):                                             # as below, with every point
+                moved = dict(kf, Xw=kf["Xw"].copy())
+                moved["Xw"][match[ids[:14]], 0] += np.float32(shift)
+                hyp(14, moved)
+            continue
         hyp(5, kf)                                                               # rejected
         hyp(len(ids), kf)                                                        # success without a search
         hyp(14, _restrict(kf, np.concatenate([match[ids[:14]], others[:10]])))   # the first search is not enough
@@ -508,13 +539,34 @@ def test_relocalization_refine_batch(pkg, oracle, synthetic, reloc_scene):
                  "third optimisation" if st & R.OPT3 else "final failure" if not st & R.SUCCESS else "other")
         if st & R.OPT3 and not st & R.SUCCESS:
             seen.add("final failure")
-    assert {"rejected", "success without search", "first search not enough", "second optimisation", "third optimisation", "final failure"} <= seen, seen
+    assert dense or {"rejected", "success without search", "first search not enough", "second optimisation", "third optimisation", "final failure"} <= seen, seen
+    queries = sum(len(h["has_point"]) for h in hyps)
+    pool = [(sum(s[5] for _, _, _, s in by_hand[which]), queries) for which in range(2)]
     # the chain's searches are tc2li_search_by_projection_keyframe_batch with the same inputs
     for which, (th, orb_dist) in enumerate(((10, 100), (3, 64))):
-        assert by_hand[which]
+        assert by_hand[which] or (dense and which == 1)
+        if not by_hand[which]:
+            continue
         items = [dict(keys=S["frames"][f]["keys"], descriptors=S["frames"][f]["descriptors"], held=s[2], pose7=s[4], bounds=[0, W, 0, H],
                       **dict({n: cand[n] for n in ("has_point", "Xw", "point_descriptors", "min_distance", "max_distance", "max_distance_raw", "angle")},
                              found=s[3])) for h, f, cand, s in by_hand[which]]
         match, nm = pkg.search_by_projection_keyframe_batch(items, cam4, sf, log_sf, th, orb_dist, True, capacity=ext.capacity)
         for k, (h, f, cand, s) in enumerate(by_hand[which]):
             assert np.array_equal(match[k, :len(s[0])], s[0]) and nm[k] == s[1] == got["n_additional"][h, which], (which, h)
+    return got, pool
+
+
+def test_relocalization_refine_batch(pkg, oracle, synthetic, reloc_scene):
+    _check_relocalization_refine(pkg, oracle, synthetic, reloc_scene)
+
+
+def test_relocalization_refine_pool_overflow_takes_the_one_kernel_path(pkg, oracle, synthetic, reloc_scene, monkeypatch):
+    """The ladder with a candidate pool of one entry per query: every output equals the default run's (and, inside the check, the oracle's /
+    reloc_ref.py's).  The pool is sized from the points of all hypotheses, so the batch is the dense one, and that its first search
+    overflows the pool is reloc_ref.py's count: more window candidates than the batch has queries."""
+    ref, _ = _check_relocalization_refine(pkg, oracle, synthetic, reloc_scene, dense=True)
+    monkeypatch.setenv("TC2LI_MATCH_POOL_PER_QUERY", "1")
+    got, pool = _check_relocalization_refine(pkg, oracle, synthetic, reloc_scene, dense=True)
+    print("(window candidates, queries) of the two searches:", pool)
+    assert pool[0][0] > pool[0][1], pool
+    assert sorted(got) == sorted(ref) and all(np.array_equal(got[k], ref[k]) for k in ref)
