@@ -212,20 +212,37 @@ struct BaBatchSlot {
     double lambda_init, lidar_information;
     int32_t iterations, lm_pad_;
 };
-// The windows of one launch and their state in this phase, passed BY VALUE in the kernel arguments (HIP gives a kernel 4 KB of them):
-// workgroups of window position y = blockIdx.y (z for the tiled GEMM) work on table[win[y]].
+// The windows of one launch and their state in this phase, passed BY VALUE in the kernel arguments (HIP gives a kernel 4 KB of them).
+// The many-workgroup kernels run on a COMPACT 1-D grid: window position y owns the workgroups first_block[y] .. first_block[y + 1] - 1 --
+// as many as ITS sizes need for the kernel of the launch -- and a workgroup finds (y, its number within the window) by a search of the
+// prefix (ba_phase_block).  The launch wrapper fills the prefix for its own kernel from the windows' sizes (BaPhaseHost::own) in its copy of
+// the phase.  The one-workgroup-per-window kernels and the dense path keep blockIdx.x / y (z for the tiled GEMM) = window position.
 constexpr int kBaPhaseMax = 192;   // windows per launch; a longer phase list is launched in pieces
 constexpr int kBaXpStride = 192;   // doubles per window in the staging area of the steps x_p: 6 x 32 free keyframes
 struct BaPhase {
     const BaBatchSlot* table;      // the call's table in device memory
     const double* xp_area;         // steps of a trial phase, window position y at (first + y) * kBaXpStride; NULL: slot.xp
     int32_t first, pad_;           // position of win[0] in the phase's list
-    int32_t expect, pad2_;         // device-side LM: the kernels of this launch run for windows whose BaLmState::status equals `expect` (0: for all)
+    int32_t expect, n;             // device-side LM: the kernels of this launch run for windows whose BaLmState::status equals `expect` (0: for all); n: windows in win[]
     uint16_t win[kBaPhaseMax];
     uint8_t flags[kBaPhaseMax];    // kBaAcceptedInTrial: the accepted estimate lives in the trial buffers (an odd number of accepted steps);
                                    // kBaWantMaxdiag: computeLambdaInit's diagonal maxima; kBaWantHpp: Hpp / b_p to slot.hpp_out
     double lambda[kBaPhaseMax];
+    uint32_t first_block[kBaPhaseMax + 1];  // compact grids: first workgroup of window position y in the launch; [n] = the grid
 };
+static_assert(sizeof(BaPhase) + 256 <= 4096, "BaPhase travels by value beside the kernels' other arguments: HIP gives a kernel 4 KB");
+// What a window needs of each batched kernel follows from its own sizes; the host keeps them beside the phase (never in the kernel arguments).
+struct BaWindowExtent {
+    int32_t n_groups, n_free_edges, n_edges, n_points, n_poses, n_free;
+    int32_t schur_lean_blocks;     // workgroups of k_ba_schur_lean_b: parts (x 2 for a wide window); 0 off the sparse path
+    int32_t trial_fused, has_lidar, lidar_chunks, lidar_W;
+};
+struct BaPhaseHost : BaPhase { BaWindowExtent own[kBaPhaseMax]; };
+// TC2LI_BA_TIMING: per batched launch kind, the workgroups a 2-D grid of (largest extent among the windows) x (windows) would start and
+// the workgroups the windows own (what the compact grid starts), summed over a call
+enum BaGridKind { kGridLinearize, kGridReduceAll, kGridSchurLean, kGridSchurFinish, kGridTrialFused, kGridTrialUpdate, kGridErrors, kGridDepth,
+                  kGridBalmHessian, kGridBalmCombine, kGridKinds };
+struct BaGridTally { uint64_t launches[kGridKinds], rect[kGridKinds], own[kGridKinds]; };
 constexpr unsigned kBaAcceptedInTrial = 1, kBaWantMaxdiag = 2, kBaWantHpp = 4;
 struct BaBatchExtent {
     int max_edges, max_points, max_poses, max_free, max_free_edges, max_groups, max_np_pad, max_slices, max_planes, max_chunks, max_W;
@@ -240,10 +257,11 @@ struct BaBatchExtent {
     int any_dups;  // some window has duplicate (point, free pose) edges: k_ba_dups_b after the linearisation's sums
     int any_trial_fused, any_trial_unfused;  // windows with / without pb.trial_fused in the call (each kind has its launches; a kernel skips the other kind)
     int inertial;  // the windows' vertices are ImuCamPose records (LocalLVIBA batch): the linearisation kernel of that vertex type
+    BaGridTally* tally;  // TC2LI_BA_TIMING: where the launch wrappers count workgroups (NULL: nowhere)
 };
 // n_active <= kBaPhaseMax windows per call (the host cuts a longer list)
-void ba_batch_launch_linearize(const BaPhase& ph, int n_active, const BaBatchExtent& x, bool any_maxdiag, hipStream_t st);
-void ba_batch_launch_schur(const BaPhase& ph, int n_active, const BaBatchExtent& x, hipStream_t st);
+void ba_batch_launch_linearize(const BaPhaseHost& ph, int n_active, const BaBatchExtent& x, bool any_maxdiag, hipStream_t st);
+void ba_batch_launch_schur(const BaPhaseHost& ph, int n_active, const BaBatchExtent& x, hipStream_t st);
 // x = (S + Hl)^-1 (b_s + bl) per window by dense LDL^T, one workgroup per window (windows of at most 21 free keyframes)
 void ba_batch_launch_solve(const BaPhase& ph, int n_active, const BaBatchExtent& x, hipStream_t st);
 bool lvi_device_solve_available();  // the kernels below get the LDS of their largest window on this device
@@ -251,15 +269,15 @@ bool lvi_device_solve_available();  // the kernels below get the LDS of their la
 void lvi_batch_launch_solve(const BaPhase& ph, int n_active, int max_np, int max_ni, hipStream_t st);
 // one window: S / bs as k_ba_schur_finish left them in device memory, x (n unknowns, the caller's numbering) to x_dev and x_host, ok_host[0] = the pivots were usable
 void lvi_launch_solve(const LviSolveDev& q, const double* S, const double* bs, double lambda, double* x_dev, double* x_host, int32_t* ok_host, hipStream_t st);
-void ba_batch_launch_trial(const BaPhase& ph, int n_active, const BaBatchExtent& x, hipStream_t st);
-void ba_batch_launch_depth(const BaPhase& ph, int n_active, const BaBatchExtent& x, hipStream_t st);
+void ba_batch_launch_trial(const BaPhaseHost& ph, int n_active, const BaBatchExtent& x, hipStream_t st);
+void ba_batch_launch_depth(const BaPhaseHost& ph, int n_active, const BaBatchExtent& x, hipStream_t st);
 // device-side LM (ba_lm_kernels.hip): one wavefront per window of the phase
 void ba_batch_launch_lm_begin(const BaPhase& ph, int n_active, hipStream_t st);
 void ba_batch_launch_lm_decide(const BaPhase& ph, int n_active, hipStream_t st);
 // the LiDAR term of the listed windows (all with W <= 7 and at most 2048 planes): residual at the accepted or the trial poses,
 // Jacobian / Hessian at the accepted poses
 void balm_batch_launch_residual(const BaPhase& ph, int n, bool trial, hipStream_t st);
-void balm_batch_launch_hessian(const BaPhase& ph, int n, const BaBatchExtent& x, hipStream_t st);
+void balm_batch_launch_hessian(const BaPhaseHost& ph, int n, const BaBatchExtent& x, hipStream_t st);
 
 #if defined(__HIPCC__)
 // *p for an object no kernel of the launch writes, at an address that is the same for the whole wavefront: read through the constant
@@ -291,6 +309,20 @@ __device__ __forceinline__ void ba_problem_pointers_are_global(BaProblemDev& pb)
 // loads, and everything addressed through their result would be fetched per lane (readfirstlane: the value is the same in every lane)
 __device__ __forceinline__ int ba_phase_window(const BaPhase& ph, int pos) { return __builtin_amdgcn_readfirstlane((int)ph.win[pos]); }
 __device__ __forceinline__ unsigned ba_phase_flags(const BaPhase& ph, int pos) { return (unsigned)__builtin_amdgcn_readfirstlane((int)ph.flags[pos]); }
+// Compact grids: the window position and the workgroup's number within that window, from blockIdx.x -- the last position whose first
+// workgroup is not beyond it, so windows that own none (equal neighbouring entries) are passed over.  At most 8 steps for kBaPhaseMax
+// windows, all of them scalar: dword loads from the argument block at a uniform index, and nothing of the slot record depends on a vector
+// register afterwards (ba_slot_view's note).
+struct BaBlock { int pos, block; };
+__device__ __forceinline__ BaBlock ba_phase_block(const BaPhase& ph) {
+    const unsigned b = blockIdx.x;
+    int lo = 0, hi = ph.n;  // first_block[lo] <= b < first_block[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((unsigned)__builtin_amdgcn_readfirstlane((int)ph.first_block[mid]) <= b) lo = mid; else hi = mid;
+    }
+    return BaBlock{lo, (int)(b - (unsigned)__builtin_amdgcn_readfirstlane((int)ph.first_block[lo]))};
+}
 // What a batched kernel needs of the window's LM state (device-side LM): whether the launch is meant for the window now, the parity / request
 // bits in BaPhase::flags' encoding, lambda.  Scalar loads: the state was written by an earlier launch of the stream (k_ba_lm_begin_b /
 // k_ba_lm_decide_b / the call's upload), never by this one.

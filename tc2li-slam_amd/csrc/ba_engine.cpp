@@ -421,7 +421,7 @@ void tc2li_ba_engine::run() {
         }
         if (!failed && !retire.empty()) {
             const BaBatchExtent XR = batch_extent(W, retire);
-            pieces_for(retire, 0, [&](const BaPhase& ph, int cnt) { ba_batch_launch_depth(ph, cnt, XR, st); });
+            pieces_for(retire, 0, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_depth(ph, cnt, XR, st); });
             if (G.h_copies_r.ensure(4 * retire.size()) != hipSuccess) failed = 1;
             size_t n_tasks = 0, max_bytes = 0;
             for (int s : retire) {

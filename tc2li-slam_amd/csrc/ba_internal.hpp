@@ -576,16 +576,26 @@ struct LockstepWindow {
     bool wants_iteration() const { return rc >= 0 && it < p->iterations && !stopped() && ok; }
 };
 
-// The windows `list[c0 .. c1)` of a phase as kernel arguments (ba_device.hpp BaPhase): table index, parity / request bits, lambda.
+// The windows `list[c0 .. c1)` of a phase as kernel arguments (ba_device.hpp BaPhase): table index, parity / request bits, lambda --
+// and, beside them on the host, each window's own sizes, from which a launch wrapper cuts the compact grid of its kernel.
 template <typename Win>
-BaPhase make_phase(const BaBatchSlot* d_table, const double* d_xp_area, const std::vector<Win>& W, const std::vector<int>& list, size_t c0, size_t c1, int expect = 0) {
-    BaPhase ph;
-    ph.table = d_table; ph.xp_area = d_xp_area; ph.first = (int32_t)c0; ph.pad_ = 0; ph.expect = expect; ph.pad2_ = 0;
+BaPhaseHost make_phase(const BaBatchSlot* d_table, const double* d_xp_area, const std::vector<Win>& W, const std::vector<int>& list, size_t c0, size_t c1, int expect = 0) {
+    BaPhaseHost ph;
+    ph.table = d_table; ph.xp_area = d_xp_area; ph.first = (int32_t)c0; ph.pad_ = 0; ph.expect = expect; ph.n = (int32_t)(c1 - c0);
+    ph.first_block[0] = 0;
     for (size_t k = c0; k < c1; ++k) {
         const Win& w = W[list[k]];
         ph.win[k - c0] = (uint16_t)list[k];
         ph.flags[k - c0] = (uint8_t)((w.parity ? kBaAcceptedInTrial : 0u) | (w.want_maxdiag ? kBaWantMaxdiag : 0u) | (w.wants_hpp() ? kBaWantHpp : 0u));
         ph.lambda[k - c0] = w.lambda;
+        BaWindowExtent& e = ph.own[k - c0];
+        e = BaWindowExtent{};
+        if (w.rc < 0) continue;  // (its slot is empty: no kernel has work for it)
+        const BaProblemDev& pb = w.vp.pb;
+        e.n_groups = pb.n_groups; e.n_free_edges = pb.n_free_edges; e.n_edges = pb.n_edges; e.n_points = pb.n_points; e.n_poses = pb.n_poses; e.n_free = pb.n_free;
+        if (pb.sparse_schur && pb.n_free > 0) e.schur_lean_blocks = w.vp.n_slices * (pb.n_free > kSchurBlocksMaxFree ? 2 : 1);
+        e.trial_fused = pb.trial_fused;
+        if (w.lidar) { e.has_lidar = 1; e.lidar_chunks = w.lidar->dev.n_chunks; e.lidar_W = w.lidar->W; }
     }
     return ph;
 }
@@ -594,7 +604,7 @@ template <typename Win, typename Fn>
 void for_phase_pieces(const BaBatchSlot* d_table, const double* d_xp_area, const std::vector<Win>& W, const std::vector<int>& list, Fn&& fn, int expect = 0) {
     for (size_t c0 = 0; c0 < list.size(); c0 += kBaPhaseMax) {
         const size_t c1 = std::min(list.size(), c0 + (size_t)kBaPhaseMax);
-        const BaPhase ph = make_phase(d_table, d_xp_area, W, list, c0, c1, expect);
+        const BaPhaseHost ph = make_phase(d_table, d_xp_area, W, list, c0, c1, expect);
         fn(ph, (int)(c1 - c0));
     }
 }
@@ -736,17 +746,17 @@ inline void fill_device_lm_slot(BaBatchSlot& s, const LockstepWindow& w, Lockste
 inline void queue_lm_round(const BaBatchSlot* d_table, const std::vector<LockstepWindow>& W, const std::vector<int>& live, const std::vector<int>& live_lidar,
                            const std::vector<int>& lidar_first, const BaBatchExtent& XL, bool want_maxdiag, hipStream_t st) {
     auto pieces_for = [&](const std::vector<int>& list, int expect, auto&& fn) { for_phase_pieces(d_table, (const double*)nullptr, W, list, fn, expect); };
-    pieces_for(live, kLmIterate, [&](const BaPhase& ph, int cnt) { ba_batch_launch_linearize(ph, cnt, XL, want_maxdiag, st); });
-    pieces_for(lidar_first, kLmIterate, [&](const BaPhase& ph, int cnt) { balm_batch_launch_residual(ph, cnt, false, st); });
-    pieces_for(live_lidar, kLmIterate, [&](const BaPhase& ph, int cnt) { balm_batch_launch_hessian(ph, cnt, XL, st); });
-    pieces_for(live, kLmIterate, [&](const BaPhase& ph, int cnt) { ba_batch_launch_lm_begin(ph, cnt, st); });
-    pieces_for(live, kLmTrial, [&](const BaPhase& ph, int cnt) {
+    pieces_for(live, kLmIterate, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_linearize(ph, cnt, XL, want_maxdiag, st); });
+    pieces_for(lidar_first, kLmIterate, [&](const BaPhaseHost& ph, int cnt) { balm_batch_launch_residual(ph, cnt, false, st); });
+    pieces_for(live_lidar, kLmIterate, [&](const BaPhaseHost& ph, int cnt) { balm_batch_launch_hessian(ph, cnt, XL, st); });
+    pieces_for(live, kLmIterate, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_lm_begin(ph, cnt, st); });
+    pieces_for(live, kLmTrial, [&](const BaPhaseHost& ph, int cnt) {
         ba_batch_launch_schur(ph, cnt, XL, st);
         ba_batch_launch_solve(ph, cnt, XL, st);
         ba_batch_launch_trial(ph, cnt, XL, st);
     });
-    if (XL.any_trial_unfused) pieces_for(live_lidar, kLmTrial, [&](const BaPhase& ph, int cnt) { balm_batch_launch_residual(ph, cnt, true, st); });  // (windows with pb.trial_fused: inside the trial kernel)
-    pieces_for(live, kLmTrial, [&](const BaPhase& ph, int cnt) { ba_batch_launch_lm_decide(ph, cnt, st); });
+    if (XL.any_trial_unfused) pieces_for(live_lidar, kLmTrial, [&](const BaPhaseHost& ph, int cnt) { balm_batch_launch_residual(ph, cnt, true, st); });  // (windows with pb.trial_fused: inside the trial kernel)
+    pieces_for(live, kLmTrial, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_lm_decide(ph, cnt, st); });
 }
 
 // the lock-step drivers (ba_lockstep.cpp, lvi_host.cpp): false = the batch goes through the one-window path

@@ -1267,7 +1267,9 @@ __device__ __forceinline__ void d_ba_depth(const BaProblemDev& pb, const int bx,
 __global__ __launch_bounds__(256) void k_ba_depth(BaProblemDev pb, uint8_t* __restrict__ depth_pos) { d_ba_depth(pb, blockIdx.x, depth_pos); }
 
 
-// ---- lock-step batch: the same bodies, the window taken from a slot table (blockIdx.y / z = position in the active list) ----
+// ---- lock-step batch: the same bodies, the window taken from a slot table ----
+// The many-workgroup kernels run on the phase's compact 1-D grid (ba_device.hpp: ba_phase_block gives the position in the active list and
+// the workgroup's number within the window); the one-workgroup-per-window kernels and the dense path take the position from blockIdx.
 static inline __device__ int blocks256(int n) { return (n + 255) / 256; }
 // s_setprio 3: the lock-step kernels are links of a dependent chain with a host step after every phase, running beside the front end's
 // long kernels; their wavefronts go first in the SIMDs' issue arbitration (41.7 against 42.1 ms per step of the whole loop).
@@ -1306,10 +1308,12 @@ __device__ __forceinline__ BaSlotView ba_slot_view(const BaPhase& ph, int pos) {
     if (ph.xp_area && 6 * v.pb.n_free <= kBaXpStride) v.xp = global_ptr(ph.xp_area) + (size_t)(ph.first + pos) * kBaXpStride;
     return v;
 }
+// TC2LI_SLOT_BLOCK: the compact grid -- the window of this workgroup and `bx`, its number among the window's own workgroups of this launch
+#define TC2LI_SLOT_BLOCK const BaBlock blk_ = ba_phase_block(ph); const int bx = blk_.block; const BaSlotView view_ = ba_slot_view(ph, blk_.pos); if (!view_.active) return; const BaBatchSlot& sl = view_.sl; (void)sl; const BaProblemDev& pb = view_.pb
 #define TC2LI_SLOT(axis) const BaSlotView view_ = ba_slot_view(ph, blockIdx.axis); if (!view_.active) return; const BaBatchSlot& sl = view_.sl; (void)sl; const BaProblemDev& pb = view_.pb
 
-// workgroups [0, max_groups) of a window: the landmark role; [max_groups, ...): the pose role -- one launch (two before: the second
-// waited for the first to drain although neither reads what the other writes)
+// workgroups [0, n_groups) of a window: the landmark role; the blocks256(n_free_edges) behind them: the pose role -- one launch (two
+// before: the second waited for the first to drain although neither reads what the other writes)
 // A kernel per vertex type (the windows of a batch call share it): the SE3 form does not carry the registers of the ImuCamPose Jacobians
 // (196 VGPRs with both in one body: two wavefronts per SIMD for a kernel that waits on scattered loads; 142 / 148 now, three.  Holding
 // the body to four with amdgpu_waves_per_eu -- 126 registers, 68 bytes of scratch per lane -- measured the same in the loop: 361 against 375 us.
@@ -1317,32 +1321,32 @@ __device__ __forceinline__ BaSlotView ba_slot_view(const BaPhase& ph, int pos) {
 // (96 registers + 12 B of scratch) the kernel runs 254-273 us and the step does not change: 29.5 against 29.7 ms over five A/B pairs).
 // fuse != 0: the closing sums (k_ba_reduce_all_b, k_ba_maxdiag_b) by the window's last workgroup instead of two more launches (round 5)
 template <bool INERTIAL>
-__device__ __forceinline__ void linearize_b_body(const BaPhase& ph, int max_groups, int fuse, LinearizeLds& lds) {
-    TC2LI_SLOT(y);
-    const int bx = blockIdx.x;
+__device__ __forceinline__ void linearize_b_body(const BaPhase& ph, int fuse, LinearizeLds& lds) {
+    TC2LI_SLOT_BLOCK;
     const int nbe = blocks256(pb.n_free_edges);
+    if (bx >= pb.n_groups + nbe) return;  // (never on a grid cut from the window's own sizes)
     if (!fuse) {
-        if (bx < max_groups) { if (bx < pb.n_groups) d_ba_linearize<INERTIAL>(pb, bx, lds); }
-        else if (bx - max_groups < nbe) d_ba_linearize_pose<INERTIAL>(pb, bx - max_groups, lds);
+        if (bx < pb.n_groups) d_ba_linearize<INERTIAL>(pb, bx, lds);
+        else d_ba_linearize_pose<INERTIAL>(pb, bx - pb.n_groups, lds);
         return;
     }
-    if (bx < max_groups) { if (bx >= pb.n_groups) return; d_ba_linearize<INERTIAL, true>(pb, bx, lds); }
-    else { if (bx - max_groups >= nbe) return; d_ba_linearize_pose<INERTIAL, true>(pb, bx - max_groups, lds); }
+    if (bx < pb.n_groups) d_ba_linearize<INERTIAL, true>(pb, bx, lds);
+    else d_ba_linearize_pose<INERTIAL, true>(pb, bx - pb.n_groups, lds);
     if (!ba_last_of(pb.ticket + 0, pb.n_groups + nbe)) return;
     d_ba_linearize_close(pb, lds.big, sl.chi_out, view_.hpp_out(), (view_.flags & kBaWantMaxdiag) ? sl.maxdiag_out : nullptr);
 }
-__global__ __launch_bounds__(256) void k_ba_linearize_b(const BaPhase ph, int max_groups, int fuse) {
+__global__ __launch_bounds__(256) void k_ba_linearize_b(const BaPhase ph, int fuse) {
     __shared__ LinearizeLds lds;
-    linearize_b_body<false>(ph, max_groups, fuse, lds);
+    linearize_b_body<false>(ph, fuse, lds);
 }
-__global__ __launch_bounds__(256) void k_ba_linearize_imu_b(const BaPhase ph, int max_groups, int fuse) {
+__global__ __launch_bounds__(256) void k_ba_linearize_imu_b(const BaPhase ph, int fuse) {
     __shared__ LinearizeLds lds;
-    linearize_b_body<true>(ph, max_groups, fuse, lds);
+    linearize_b_body<true>(ph, fuse, lds);
 }
 __global__ __launch_bounds__(256) void k_ba_reduce_all_b(const BaPhase ph) {
-    TC2LI_SLOT(y);
-    if ((int)blockIdx.x >= pb.n_free + 1) return;
-    d_ba_reduce_all(pb, blockIdx.x, sl.chi_out, view_.hpp_out());
+    TC2LI_SLOT_BLOCK;
+    if (bx >= pb.n_free + 1) return;
+    d_ba_reduce_all(pb, bx, sl.chi_out, view_.hpp_out());
 }
 __global__ __launch_bounds__(64) void k_ba_dups_b(const BaPhase ph) {
     TC2LI_SLOT(y);
@@ -1381,18 +1385,18 @@ __global__ __launch_bounds__(256) void k_ba_schur_units_b(const BaPhase ph) {
 }
 __global__ __launch_bounds__(256, 3) void k_ba_schur_lean_b(const BaPhase ph) {
     extern __shared__ double s_schur[];
-    TC2LI_SLOT(y);
-    if (!pb.sparse_schur || !pb.n_free) return;
+    TC2LI_SLOT_BLOCK;
     // a wide window (more than kSchurBlocksMaxFree free keyframes): two workgroups per part, the same launch as everybody else's
-    const int halves = pb.n_free > kSchurBlocksMaxFree ? 2 : 1, part = (int)blockIdx.x / halves;
+    if (!pb.sparse_schur || !pb.n_free) return;
+    const int halves = pb.n_free > kSchurBlocksMaxFree ? 2 : 1, part = bx / halves;
     if (part >= sl.n_slices) return;
-    d_ba_schur_lean(pb, part, view_.lambda, s_schur, 256 * ((int)blockIdx.x - part * halves));
+    d_ba_schur_lean(pb, part, view_.lambda, s_schur, 256 * (bx - part * halves));
 }
 __global__ __launch_bounds__(256) void k_ba_schur_finish_b(const BaPhase ph) {
-    TC2LI_SLOT(y);
+    TC2LI_SLOT_BLOCK;
     const int np = 6 * pb.n_free;
-    if (!pb.n_free || (int)blockIdx.x >= blocks256(np * np)) return;
-    d_ba_schur_finish(pb, blockIdx.x, view_.lambda, sl.n_slices, sl.S_out, sl.bs_out, sl.bp_host);
+    if (!pb.n_free || bx >= blocks256(np * np)) return;
+    d_ba_schur_finish(pb, bx, view_.lambda, sl.n_slices, sl.S_out, sl.bs_out, sl.bp_host);
 }
 // The reduced camera system of a window on the device: (S + Hl) x = b_s + bl by the dense LDL^T of ldlt_solve_small (ba_math.hpp), one
 // workgroup per window, lane i = row i.  Every element is formed by the same operations in the same order as on the host -- a row's
@@ -1951,54 +1955,52 @@ __global__ __launch_bounds__(kLviThreads) void k_lvi_solve_b(const BaPhase ph) {
     if (q.n == 0) return;
     d_lvi_solve(q, load_uniform(&sl.S_out), load_uniform(&sl.bs_out), view_.lambda, load_uniform(&sl.x_dev), load_uniform(&sl.x_host), load_uniform(&sl.ok_host), s_lvi);
 }
-// The fused trial launch of the lock-step batch: workgroups [0, max_groups) the window's landmark groups, workgroup max_groups its LiDAR
-// plane residual at the trial poses (formed in LDS as the groups form them: the launch that wrote them to memory is this one).
+// The fused trial launch of the lock-step batch: workgroups [0, n_groups) the window's landmark groups, workgroup n_groups (a window with
+// a LiDAR edge has it) its LiDAR plane residual at the trial poses (formed in LDS as the groups form them: the launch that wrote them to memory is this one).
 template <bool INERTIAL>
-__device__ __forceinline__ void trial_fused_b_body(const BaPhase& ph, int max_groups, TrialLds& L) {
-    TC2LI_SLOT(y);
+__device__ __forceinline__ void trial_fused_b_body(const BaPhase& ph, TrialLds& L) {
+    TC2LI_SLOT_BLOCK;
     if (!pb.trial_fused) return;
-    const int bx = blockIdx.x;
-    if (bx < max_groups) {
-        if (bx >= pb.n_groups) return;
+    if (bx < pb.n_groups) {
         d_ba_trial_group<INERTIAL>(pb, bx, view_.xp, view_.lambda, L, sl.iposes_host);
         if (!ba_last_of(pb.ticket + 1, pb.n_groups)) return;
         d_ba_trial_close(pb, L.sum, sl.scale_out, sl.chi_trial_out);
         return;
     }
-    if (!load_uniform(&sl.has_lidar)) return;
+    if (bx > pb.n_groups || !load_uniform(&sl.has_lidar)) return;
     const int np = 6 * pb.n_free;
     for (int j = threadIdx.x; j < np; j += 256) L.x[j] = view_.xp[j];
     __syncthreads();
     trial_poses_lds<INERTIAL>(pb, L.x, L.poses, false, nullptr);
     __syncthreads();
-    BalmSlotView v = balm_slot_view(ph, blockIdx.y, true);
+    BalmSlotView v = balm_slot_view(ph, blk_.pos, true);
     d_balm_residual_total(v.b, reinterpret_cast<const Se3*>(L.poses));
 }
-__global__ __launch_bounds__(256) void k_ba_trial_fused_b(const BaPhase ph, int max_groups) {
+__global__ __launch_bounds__(256) void k_ba_trial_fused_b(const BaPhase ph) {
     __shared__ TrialLds L;
-    trial_fused_b_body<false>(ph, max_groups, L);
+    trial_fused_b_body<false>(ph, L);
 }
-__global__ __launch_bounds__(256) void k_ba_trial_fused_imu_b(const BaPhase ph, int max_groups) {
+__global__ __launch_bounds__(256) void k_ba_trial_fused_imu_b(const BaPhase ph) {
     __shared__ TrialLds L;
-    trial_fused_b_body<true>(ph, max_groups, L);
+    trial_fused_b_body<true>(ph, L);
 }
 __global__ __launch_bounds__(256) void k_ba_trial_update_b(const BaPhase ph) {
-    TC2LI_SLOT(y);
+    TC2LI_SLOT_BLOCK;
     const int nbp = (pb.n_points + kBacksubPerBlock - 1) / kBacksubPerBlock;
-    if (pb.trial_fused || (int)blockIdx.x >= nbp + blocks256(pb.n_poses)) return;
-    d_ba_trial_update(pb, blockIdx.x, nbp, view_.xp, view_.lambda, sl.iposes_host);
+    if (pb.trial_fused || bx >= nbp + blocks256(pb.n_poses)) return;
+    d_ba_trial_update(pb, bx, nbp, view_.xp, view_.lambda, sl.iposes_host);
 }
 __global__ __launch_bounds__(256) void k_ba_errors_b(const BaPhase ph) {
-    TC2LI_SLOT(y);
-    if (pb.trial_fused || (int)blockIdx.x >= blocks256(pb.n_edges)) return;
-    d_ba_errors(pb, blockIdx.x);
+    TC2LI_SLOT_BLOCK;
+    if (pb.trial_fused || bx >= blocks256(pb.n_edges)) return;
+    d_ba_errors(pb, bx);
 }
 // the same, and the last workgroup of a window does k_ba_trial_reduce_b's work for it: the gain-ratio scale's landmark part (partials of
 // k_ba_trial_update_b, an earlier launch) and the trial's cost
 __global__ __launch_bounds__(256) void k_ba_errors_reduce_b(const BaPhase ph) {
-    TC2LI_SLOT(y);
-    if (pb.trial_fused || (int)blockIdx.x >= blocks256(pb.n_edges)) return;
-    d_ba_errors<true>(pb, blockIdx.x);
+    TC2LI_SLOT_BLOCK;
+    if (pb.trial_fused || bx >= blocks256(pb.n_edges)) return;
+    d_ba_errors<true>(pb, bx);
     if (!ba_last_of(pb.ticket + 1, blocks256(pb.n_edges))) return;
     d_ba_trial_reduce<true>(pb, 0, sl.scale_out, sl.chi_trial_out);
     __syncthreads();
@@ -2010,11 +2012,12 @@ __global__ __launch_bounds__(256) void k_ba_trial_reduce_b(const BaPhase ph) {
     d_ba_trial_reduce(pb, blockIdx.x, sl.scale_out, sl.chi_trial_out);
 }
 __global__ __launch_bounds__(256) void k_ba_depth_b(const BaPhase ph) {
-    TC2LI_SLOT(y);
-    if ((int)blockIdx.x >= blocks256(pb.n_edges)) return;
-    d_ba_depth(pb, blockIdx.x, sl.depth_out);
+    TC2LI_SLOT_BLOCK;
+    if (bx >= blocks256(pb.n_edges)) return;
+    d_ba_depth(pb, bx, sl.depth_out);
 }
 #undef TC2LI_SLOT
+#undef TC2LI_SLOT_BLOCK
 
 // ---- launch wrappers ----------------------------------------------------------------------------------------------
 static inline int blocks(int n) { return (n + 255) / 256; }
@@ -2069,38 +2072,62 @@ void ba_launch_depth(const BaProblemDev& pb, uint8_t* depth_pos, hipStream_t st)
     TC2LI_LAUNCH(k_ba_depth, dim3(blocks(pb.n_edges)), dim3(256), 0, st, pb, depth_pos);
 }
 
-void ba_batch_launch_linearize(const BaPhase& ph, int n_active, const BaBatchExtent& x, bool any_maxdiag, hipStream_t st) {
+// Compact grids of the lock-step launches.  own(e): the workgroups window extent `e` needs of the kernel about to be launched (the same
+// expression the kernel body uses to tell its roles apart).  Fills the prefix of `k` over the phase's windows and returns the grid; with
+// TC2LI_BA_TIMING also counts what a 2-D grid (largest extent x windows) would have started.
+template <typename Own>
+static unsigned compact_grid(BaPhase& k, const BaPhaseHost& ph, int n_active, const BaBatchExtent& x, BaGridKind kind, Own&& own) {
+    unsigned at = 0, widest = 0;
+    for (int i = 0; i < n_active; ++i) {
+        const unsigned m = (unsigned)own(ph.own[i]);
+        k.first_block[i] = at;
+        at += m;
+        widest = std::max(widest, m);
+    }
+    k.first_block[n_active] = at;
+    k.n = n_active;
+    if (x.tally) { x.tally->launches[kind] += 1; x.tally->rect[kind] += (uint64_t)widest * n_active; x.tally->own[kind] += at; }
+    return at;
+}
+void ba_batch_launch_linearize(const BaPhaseHost& ph, int n_active, const BaBatchExtent& x, bool any_maxdiag, hipStream_t st) {
     if (!n_active) return;
     const int fuse = x.fuse_linearize && !x.any_dups;  // (a window with duplicate edges takes the separate sums: k_ba_dups_b stands between them and the maxima)
-    if (x.inertial) TC2LI_LAUNCH(k_ba_linearize_imu_b, dim3(x.max_groups + blocks(x.max_free_edges), n_active), dim3(256), 0, st, ph, x.max_groups, fuse);
-    else TC2LI_LAUNCH(k_ba_linearize_b, dim3(x.max_groups + blocks(x.max_free_edges), n_active), dim3(256), 0, st, ph, x.max_groups, fuse);
+    BaPhase k = ph;
+    if (const unsigned grid = compact_grid(k, ph, n_active, x, kGridLinearize, [](const BaWindowExtent& e) { return e.n_groups + blocks(e.n_free_edges); })) {
+        if (x.inertial) TC2LI_LAUNCH(k_ba_linearize_imu_b, dim3(grid), dim3(256), 0, st, k, fuse);
+        else TC2LI_LAUNCH(k_ba_linearize_b, dim3(grid), dim3(256), 0, st, k, fuse);
+    }
     if (fuse) return;  // the closing sums ran in the windows' last workgroups
-    TC2LI_LAUNCH(k_ba_reduce_all_b, dim3(x.max_free + 1, n_active), dim3(256), 0, st, ph);
-    if (x.any_dups) TC2LI_LAUNCH(k_ba_dups_b, dim3((x.max_free + 63) / 64, n_active), dim3(64), 0, st, ph);
-    if (any_maxdiag) TC2LI_LAUNCH(k_ba_maxdiag_b, dim3(2, n_active), dim3(256), 0, st, ph);
+    if (const unsigned grid = compact_grid(k, ph, n_active, x, kGridReduceAll, [](const BaWindowExtent& e) { return e.n_free + 1; }))
+        TC2LI_LAUNCH(k_ba_reduce_all_b, dim3(grid), dim3(256), 0, st, k);
+    if (x.any_dups) TC2LI_LAUNCH(k_ba_dups_b, dim3((x.max_free + 63) / 64, n_active), dim3(64), 0, st, k);
+    if (any_maxdiag) TC2LI_LAUNCH(k_ba_maxdiag_b, dim3(2, n_active), dim3(256), 0, st, k);
 }
-void ba_batch_launch_schur(const BaPhase& ph, int n_active, const BaBatchExtent& x, hipStream_t st) {
+void ba_batch_launch_schur(const BaPhaseHost& ph, int n_active, const BaBatchExtent& x, hipStream_t st) {
     if (!n_active || !x.max_free) return;
+    BaPhase k = ph;
     if (x.max_block_parts && x.any_block_lean)  // (a wide window -- 22 .. 24 free keyframes -- takes two workgroups per part)
-        TC2LI_LAUNCH(k_ba_schur_lean_b, dim3(x.max_block_parts * (x.any_block_wide ? 2 : 1), n_active), dim3(256), schur_lean_lds_bytes(x.max_block_free), st, ph);
+        if (const unsigned grid = compact_grid(k, ph, n_active, x, kGridSchurLean, [](const BaWindowExtent& e) { return e.schur_lean_blocks; }))
+            TC2LI_LAUNCH(k_ba_schur_lean_b, dim3(grid), dim3(256), schur_lean_lds_bytes(x.max_block_free), st, k);
     if (x.any_dense) {
-        if (x.max_free_edges) TC2LI_LAUNCH(k_ba_schur_coef_b, dim3(blocks(x.max_free_edges), n_active), dim3(256), 0, st, ph, dense_full_form() ? 1 : 0);
-        TC2LI_LAUNCH(k_ba_reduce_coef_b, dim3(x.max_free, n_active), dim3(256), 0, st, ph);
+        if (x.max_free_edges) TC2LI_LAUNCH(k_ba_schur_coef_b, dim3(blocks(x.max_free_edges), n_active), dim3(256), 0, st, k, dense_full_form() ? 1 : 0);
+        TC2LI_LAUNCH(k_ba_reduce_coef_b, dim3(x.max_free, n_active), dim3(256), 0, st, k);
         // windows of at most 176 columns: the full-width form; wider ones (or TC2LI_BA_DENSE_FULL=0): 64 x 64 units.  Both kernels skip the
         // windows of the other kind.
         const bool full = dense_full_form();
         if (full) {
             (void)ensure_dynamic_lds((const void*)k_ba_schur_full_b, (int)sizeof(FullLds));
-            TC2LI_LAUNCH(k_ba_schur_full_b, dim3(x.max_slices, n_active), dim3(kFullThreads), sizeof(FullLds), st, ph);
+            TC2LI_LAUNCH(k_ba_schur_full_b, dim3(x.max_slices, n_active), dim3(kFullThreads), sizeof(FullLds), st, k);
         }
         if (!full || x.max_np_pad > 16 * kFullTilesMax) {
-            BaPhase ph2 = ph;
+            BaPhase ph2 = k;
             ph2.pad_ = full ? 0 : 1;
             const int ub = (x.max_np_pad / 16 + 3) / 4;
             TC2LI_LAUNCH(k_ba_schur_units_b, dim3(ub * (ub + 1) / 2, x.max_slices, n_active), dim3(256), 0, st, ph2);
         }
     }
-    TC2LI_LAUNCH(k_ba_schur_finish_b, dim3(blocks(36 * x.max_free * x.max_free), n_active), dim3(256), 0, st, ph);
+    if (const unsigned grid = compact_grid(k, ph, n_active, x, kGridSchurFinish, [](const BaWindowExtent& e) { return blocks(36 * e.n_free * e.n_free); }))
+        TC2LI_LAUNCH(k_ba_schur_finish_b, dim3(grid), dim3(256), 0, st, k);
 }
 void ba_batch_launch_solve(const BaPhase& ph, int n_active, const BaBatchExtent& x, hipStream_t st) {
     if (!n_active || !x.max_free) return;
@@ -2133,23 +2160,31 @@ void lvi_launch_solve(const LviSolveDev& q, const double* S, const double* bs, d
     const LviSolveArgs a{q, S, bs, lambda, x_dev, x_host, ok_host};
     TC2LI_LAUNCH(k_lvi_solve, dim3(1), dim3(kLviThreads), lvi_solve_lds_bytes(q.np, q.ni), st, a);
 }
-void ba_batch_launch_trial(const BaPhase& ph, int n_active, const BaBatchExtent& x, hipStream_t st) {
+void ba_batch_launch_trial(const BaPhaseHost& ph, int n_active, const BaBatchExtent& x, hipStream_t st) {
     if (!n_active) return;
-    if (x.any_trial_fused) {  // + 1: the windows' LiDAR residual at the trial poses rides in the same launch
-        if (x.inertial) TC2LI_LAUNCH(k_ba_trial_fused_imu_b, dim3(x.max_groups + 1, n_active), dim3(256), 0, st, ph, x.max_groups);
-        else TC2LI_LAUNCH(k_ba_trial_fused_b, dim3(x.max_groups + 1, n_active), dim3(256), 0, st, ph, x.max_groups);
+    BaPhase k = ph;
+    if (x.any_trial_fused) {  // + 1: the LiDAR residual of a window at the trial poses rides in the same launch
+        if (const unsigned grid = compact_grid(k, ph, n_active, x, kGridTrialFused, [](const BaWindowExtent& e) { return e.trial_fused ? e.n_groups + (e.has_lidar ? 1 : 0) : 0; })) {
+            if (x.inertial) TC2LI_LAUNCH(k_ba_trial_fused_imu_b, dim3(grid), dim3(256), 0, st, k);
+            else TC2LI_LAUNCH(k_ba_trial_fused_b, dim3(grid), dim3(256), 0, st, k);
+        }
     }
     if (!x.any_trial_unfused) return;
-    TC2LI_LAUNCH(k_ba_trial_update_b, dim3((x.max_points + kBacksubPerBlock - 1) / kBacksubPerBlock + blocks(x.max_poses), n_active), dim3(256), 0, st, ph);
+    if (const unsigned grid = compact_grid(k, ph, n_active, x, kGridTrialUpdate, [](const BaWindowExtent& e) { return e.trial_fused ? 0 : (e.n_points + kBacksubPerBlock - 1) / kBacksubPerBlock + blocks(e.n_poses); }))
+        TC2LI_LAUNCH(k_ba_trial_update_b, dim3(grid), dim3(256), 0, st, k);
+    const unsigned grid = compact_grid(k, ph, n_active, x, kGridErrors, [](const BaWindowExtent& e) { return e.trial_fused ? 0 : blocks(e.n_edges); });
     if (x.fuse_trial) {
-        TC2LI_LAUNCH(k_ba_errors_reduce_b, dim3(blocks(x.max_edges), n_active), dim3(256), 0, st, ph);
+        if (grid) TC2LI_LAUNCH(k_ba_errors_reduce_b, dim3(grid), dim3(256), 0, st, k);
         return;
     }
-    TC2LI_LAUNCH(k_ba_errors_b, dim3(blocks(x.max_edges), n_active), dim3(256), 0, st, ph);
-    TC2LI_LAUNCH(k_ba_trial_reduce_b, dim3(2, n_active), dim3(256), 0, st, ph);
+    if (grid) TC2LI_LAUNCH(k_ba_errors_b, dim3(grid), dim3(256), 0, st, k);
+    TC2LI_LAUNCH(k_ba_trial_reduce_b, dim3(2, n_active), dim3(256), 0, st, k);
 }
-void ba_batch_launch_depth(const BaPhase& ph, int n_active, const BaBatchExtent& x, hipStream_t st) {
-    if (n_active) TC2LI_LAUNCH(k_ba_depth_b, dim3(blocks(x.max_edges), n_active), dim3(256), 0, st, ph);
+void ba_batch_launch_depth(const BaPhaseHost& ph, int n_active, const BaBatchExtent& x, hipStream_t st) {
+    if (!n_active) return;
+    BaPhase k = ph;
+    if (const unsigned grid = compact_grid(k, ph, n_active, x, kGridDepth, [](const BaWindowExtent& e) { return blocks(e.n_edges); }))
+        TC2LI_LAUNCH(k_ba_depth_b, dim3(grid), dim3(256), 0, st, k);
 }
 
 }  // namespace tc2li

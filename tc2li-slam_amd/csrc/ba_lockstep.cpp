@@ -120,6 +120,8 @@ bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_came
     for (int i = 0; i < n; ++i) all_windows[i] = i;
     bool all_block_parts = true;
     BaBatchExtent X = batch_extent(W, all_windows, &all_block_parts);
+    BaGridTally tally{};  // TC2LI_BA_TIMING: the launch wrappers count workgroups here
+    X.tally = kTiming ? &tally : nullptr;
     // The sums behind a trial's errors (k_ba_trial_reduce_b: two workgroups per window) are taken by the LAST workgroup of the window's
     // error pass (a ticket per window, ba_kernels.hip: ba_last_of): one launch fewer per LM trial -- BA stage alone 15.0-15.2 against 15.2-15.6 ms
     // per 128 windows, the loop 28.3 / 28.7 against 28.4 / 28.9 ms.  (The same for the Schur product's closing sums measured SLOWER, 29.5-29.8
@@ -228,7 +230,7 @@ bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_came
                 if (W[i].rc >= 0 && C.h_lm.p[i].status != kLmDone) { live.push_back(i); if (W[i].lidar) live_lidar.push_back(i); }
             if (live.size() != before && !live.empty()) {
                 XL = batch_extent(W, live);
-                XL.fuse_trial = X.fuse_trial; XL.fuse_linearize = X.fuse_linearize; XL.inertial = X.inertial;
+                XL.fuse_trial = X.fuse_trial; XL.fuse_linearize = X.fuse_linearize; XL.inertial = X.inertial; XL.tally = X.tally;
             }
         };
         refresh();
@@ -282,7 +284,7 @@ bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_came
             any_maxdiag |= w.want_maxdiag;
             if (w.lidar) with_lidar.push_back(i);
         }
-        pieces(active, nullptr, [&](const BaPhase& ph, int cnt) { ba_batch_launch_linearize(ph, cnt, X, any_maxdiag, st); });
+        pieces(active, nullptr, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_linearize(ph, cnt, X, any_maxdiag, st); });
         // (running the LiDAR kernels on a second stream of the group beside the visual ones -- fork / join by events around the plane
         // Hessian and around the planes' residual of a trial -- was measured twice: round 3 with the BA stage alone, no gain; round 4 in
         // the whole loop, three A/B pairs in one call: 30.2-30.5 ms per step against 28.8-29.5 without: the events' cross-stream waits cost
@@ -291,7 +293,7 @@ bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_came
         // trial, whose residual and plane decompositions are still in place (same bits)
         bool first_pass = false;
         for (int i : with_lidar) first_pass |= W[i].it == 0;
-        pieces(with_lidar, nullptr, [&](const BaPhase& ph, int cnt) {
+        pieces(with_lidar, nullptr, [&](const BaPhaseHost& ph, int cnt) {
             if (first_pass) balm_batch_launch_residual(ph, cnt, false, st);
             balm_batch_launch_hessian(ph, cnt, X, st);
         });
@@ -303,7 +305,7 @@ bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_came
         bool pre_schur = kPreSchur && !dev_solve && !any_maxdiag;
         if (pre_schur) {
             for (int i : active) if (W[i].it == 0) W[i].lambda = W[i].p->lambda_init;  // (what the host's part sets below)
-            pieces(active, nullptr, [&](const BaPhase& ph, int cnt) { ba_batch_launch_schur(ph, cnt, X, st); });
+            pieces(active, nullptr, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_schur(ph, cnt, X, st); });
         }
         tm[6] += now() - t0;  // of the phase: the time to queue it
         sync();
@@ -362,12 +364,12 @@ bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_came
                 // factorisation went through, and the sums at the one synchronisation
                 std::vector<int> trial_lidar;
                 for (int i : trial) if (W[i].lidar) trial_lidar.push_back(i);
-                pieces(trial, nullptr, [&](const BaPhase& ph, int cnt) {
+                pieces(trial, nullptr, [&](const BaPhaseHost& ph, int cnt) {
                     ba_batch_launch_schur(ph, cnt, X, st);
                     ba_batch_launch_solve(ph, cnt, X, st);
                     ba_batch_launch_trial(ph, cnt, X, st);
                 });
-                if (X.any_trial_unfused) pieces(trial_lidar, nullptr, [&](const BaPhase& ph, int cnt) { balm_batch_launch_residual(ph, cnt, true, st); });  // (windows with pb.trial_fused: inside the trial launch)
+                if (X.any_trial_unfused) pieces(trial_lidar, nullptr, [&](const BaPhaseHost& ph, int cnt) { balm_batch_launch_residual(ph, cnt, true, st); });  // (windows with pb.trial_fused: inside the trial launch)
                 sync();
                 if (failed) break;
                 tm[3] += now() - t0; t0 = now();
@@ -387,7 +389,7 @@ bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_came
             } else {
             if (pre_schur) pre_schur = false;  // (the product of this trial came with the linearisation)
             else {
-                pieces(trial, nullptr, [&](const BaPhase& ph, int cnt) { ba_batch_launch_schur(ph, cnt, X, st); });
+                pieces(trial, nullptr, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_schur(ph, cnt, X, st); });
                 sync();
                 if (failed) break;
             }
@@ -415,8 +417,8 @@ bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_came
             for (int i : trial) if (W[i].ok2) { step.push_back(i); if (W[i].lidar) step_lidar.push_back(i); }
             if (!step.empty()) {
                 stage_steps(step);
-                pieces(step, xp_pinned ? h_xp_area : d_xp_area, [&](const BaPhase& ph, int cnt) { ba_batch_launch_trial(ph, cnt, X, st); });
-                if (X.any_trial_unfused) pieces(step_lidar, nullptr, [&](const BaPhase& ph, int cnt) { balm_batch_launch_residual(ph, cnt, true, st); });  // (windows with pb.trial_fused: inside the trial launch)
+                pieces(step, xp_pinned ? h_xp_area : d_xp_area, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_trial(ph, cnt, X, st); });
+                if (X.any_trial_unfused) pieces(step_lidar, nullptr, [&](const BaPhaseHost& ph, int cnt) { balm_batch_launch_residual(ph, cnt, true, st); });  // (windows with pb.trial_fused: inside the trial launch)
                 sync();
                 if (failed) break;
             }
@@ -468,7 +470,7 @@ bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_came
     std::vector<int> all;
     for (int i = 0; i < n; ++i) if (W[i].rc >= 0) all.push_back(i);
     if (!failed && !all.empty()) {
-        pieces(all, nullptr, [&](const BaPhase& ph, int cnt) { ba_batch_launch_depth(ph, cnt, X, st); });
+        pieces(all, nullptr, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_depth(ph, cnt, X, st); });
         // device -> pinned staging: one launch writes every window's results (the setup's copy list is done with: the stream has been
         // synchronised many times since), then the copies into the caller's arrays run in parallel
         size_t n_tasks = 0, max_bytes = 0;
@@ -519,6 +521,15 @@ bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_came
     }
     if (kTiming) fprintf(stderr, "BA lock-step timing ms (%d windows): setup %.3f linearize %.3f (queueing %.3f) host-lin %.3f schur %.3f solve %.3f trial %.3f results %.3f total %.3f\n",
                          n, tm[0], tm[1], tm[6], tm[2], tm[3], tm[4], tm[5], now() - t0, now() - t_begin);
+    if (kTiming) {
+        // per batched launch kind: what 2-D grids of (largest extent among the launch's windows) x (windows) would start, and what the windows own
+        static const char* const kNames[kGridKinds] = {"linearize", "reduce_all", "schur_lean", "schur_finish", "trial_fused", "trial_update", "errors", "depth",
+                                                       "balm_hessian", "balm_combine"};
+        for (int k = 0; k < kGridKinds; ++k)
+            if (tally.launches[k])
+                fprintf(stderr, "BA lock-step grids (%d windows): %-12s launches %llu workgroups 2-D %llu own %llu (%.1f %%)\n", n, kNames[k], (unsigned long long)tally.launches[k],
+                        (unsigned long long)tally.rect[k], (unsigned long long)tally.own[k], tally.rect[k] ? 100.0 * (double)tally.own[k] / (double)tally.rect[k] : 0.0);
+    }
     return true;
 }
 

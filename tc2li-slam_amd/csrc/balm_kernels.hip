@@ -298,11 +298,13 @@ __global__ __launch_bounds__(256) void k_balm_residual_total_b(const BaPhase ph,
     if (!v.active) return;
     d_balm_residual_total(v.b, v.poses);
 }
+// (the phase's compact grid, ba_device.hpp: a window owns n_chunks workgroups of the Hessian launch, its combine blocks of the combine launch)
 __global__ __launch_bounds__(kHessThreadsSmall) void k_balm_hessian_b(const BaPhase ph) {
-    const BalmSlotView v = balm_slot_view(ph, blockIdx.y, false);
-    if (!v.active || (int)blockIdx.x >= v.b.n_chunks) return;
+    const BaBlock blk = ba_phase_block(ph);
+    const BalmSlotView v = balm_slot_view(ph, blk.pos, false);
+    if (!v.active || blk.block >= v.b.n_chunks) return;
     __shared__ HessLds<kHessPlanesSmall, 8> lds;
-    d_balm_hessian<kItemsSmall, kHessThreadsSmall, kHessPlanesSmall, 8, 8>(v.b, v.poses, blockIdx.x, lds);
+    d_balm_hessian<kItemsSmall, kHessThreadsSmall, kHessPlanesSmall, 8, 8>(v.b, v.poses, blk.block, lds);
 }
 // The same body with its tables in DYNAMIC LDS and the wavefront held to TC2LI_HESS_WAVES per SIMD.  With the 36 KB declared statically the
 // compiler counts four workgroups per CU -- one wavefront per SIMD -- and lets the body take 325 registers (256 + 69 accumulation
@@ -311,14 +313,15 @@ __global__ __launch_bounds__(kHessThreadsSmall) void k_balm_hessian_b(const BaPh
 #define TC2LI_HESS_LEAN_KERNEL(name, waves)                                                                                                  \
     __global__ __launch_bounds__(kHessThreadsSmall) __attribute__((amdgpu_waves_per_eu(waves, waves))) void name(const BaPhase ph, int fuse) { \
         extern __shared__ double s_hess_dyn[];                                                                                               \
-        const BalmSlotView v = balm_slot_view(ph, blockIdx.y, false);                                                                        \
-        if (!v.active || (int)blockIdx.x >= v.b.n_chunks) return;                                                                            \
+        const BaBlock blk = ba_phase_block(ph);                                                                                              \
+        const BalmSlotView v = balm_slot_view(ph, blk.pos, false);                                                                           \
+        if (!v.active || blk.block >= v.b.n_chunks) return;                                                                                  \
         auto& L = *reinterpret_cast<HessLds<kHessPlanesSmall, 8>*>(s_hess_dyn);                                                              \
         /* one instantiation of the body: the partials always leave at device scope (harmless before the separate combine launch) */         \
-        d_balm_hessian<kItemsSmall, kHessThreadsSmall, kHessPlanesSmall, 8, 8, true, true>(v.b, v.poses, blockIdx.x, L);                      \
+        d_balm_hessian<kItemsSmall, kHessThreadsSmall, kHessPlanesSmall, 8, 8, true, true>(v.b, v.poses, blk.block, L);                       \
         if (!fuse) return;                                                                                                                   \
         /* round 5: the window's last chunk adds the chunks' partials (k_balm_combine_b's sums, value by value in chunk order: same bits) */  \
-        if (!ba_last_of(global_ptr(load_uniform(&(ph.table + ba_phase_window(ph, blockIdx.y))->pb.ticket)) + 2, v.b.n_chunks)) return;        \
+        if (!ba_last_of(global_ptr(load_uniform(&(ph.table + ba_phase_window(ph, blk.pos))->pb.ticket)) + 2, v.b.n_chunks)) return;           \
         const int n_values = max(balm_part_stride_dev(v.b.W), 12 * v.b.W);                                                                   \
         for (int idx = threadIdx.x; idx < n_values; idx += kHessThreadsSmall) d_balm_combine_value<true>(v.b, idx);                          \
     }
@@ -326,25 +329,44 @@ TC2LI_HESS_LEAN_KERNEL(k_balm_hessian_lean3_b, 3)  // 168 registers, 13 values i
 TC2LI_HESS_LEAN_KERNEL(k_balm_hessian_lean4_b, 4)  // 128 registers, 84 values in scratch
 #undef TC2LI_HESS_LEAN_KERNEL
 __global__ __launch_bounds__(256) void k_balm_combine_b(const BaPhase ph) {
-    const BalmSlotView v = balm_slot_view(ph, blockIdx.y, false);
-    if (!v.active || (int)blockIdx.x >= (max(balm_part_stride_dev(v.b.W), 12 * v.b.W) + 255) / 256) return;
-    d_balm_combine(v.b, blockIdx.x);
+    const BaBlock blk = ba_phase_block(ph);
+    const BalmSlotView v = balm_slot_view(ph, blk.pos, false);
+    if (!v.active || blk.block >= (max(balm_part_stride_dev(v.b.W), 12 * v.b.W) + 255) / 256) return;
+    d_balm_combine(v.b, blk.block);
 }
 void balm_batch_launch_residual(const BaPhase& ph, int n, bool trial, hipStream_t st) {
     if (n) TC2LI_LAUNCH(k_balm_residual_total_b, dim3(n), dim3(256), 0, st, ph, trial ? 1 : 0);
 }
-void balm_batch_launch_hessian(const BaPhase& ph, int n, const BaBatchExtent& x, hipStream_t st) {
+void balm_batch_launch_hessian(const BaPhaseHost& ph, int n, const BaBatchExtent& x, hipStream_t st) {
     if (!n) return;
     // TC2LI_BALM_HESS_LEAN = 0: the 325-register form; 3 (default) / 4: the lean forms (read per call: A/B switch of the measurements)
     const char* lean_env = getenv("TC2LI_BALM_HESS_LEAN");
     const int lean = lean_env ? atoi(lean_env) : 3;
     const size_t lds = sizeof(HessLds<kHessPlanesSmall, 8>);
     const int fuse = x.fuse_linearize && lean != 0;  // the chunks' sums by the window's last chunk (round 5; ba_last_of, ticket word 2)
-    if (lean == 4) TC2LI_LAUNCH(k_balm_hessian_lean4_b, dim3(x.max_chunks, n), dim3(kHessThreadsSmall), lds, st, ph, fuse);
-    else if (lean == 3) TC2LI_LAUNCH(k_balm_hessian_lean3_b, dim3(x.max_chunks, n), dim3(kHessThreadsSmall), lds, st, ph, fuse);
-    else TC2LI_LAUNCH(k_balm_hessian_b, dim3(x.max_chunks, n), dim3(kHessThreadsSmall), 0, st, ph);
+    // compact grids: the prefix over the windows' own chunk / combine-block counts
+    BaPhase k = ph;
+    auto cut = [&](BaGridKind kind, auto&& own) {
+        unsigned at = 0, widest = 0;
+        for (int i = 0; i < n; ++i) {
+            const unsigned m = ph.own[i].has_lidar ? (unsigned)own(ph.own[i]) : 0u;
+            k.first_block[i] = at;
+            at += m;
+            widest = std::max(widest, m);
+        }
+        k.first_block[n] = at;
+        k.n = n;
+        if (x.tally) { x.tally->launches[kind] += 1; x.tally->rect[kind] += (uint64_t)widest * n; x.tally->own[kind] += at; }
+        return at;
+    };
+    if (const unsigned grid = cut(kGridBalmHessian, [](const BaWindowExtent& e) { return e.lidar_chunks; })) {
+        if (lean == 4) TC2LI_LAUNCH(k_balm_hessian_lean4_b, dim3(grid), dim3(kHessThreadsSmall), lds, st, k, fuse);
+        else if (lean == 3) TC2LI_LAUNCH(k_balm_hessian_lean3_b, dim3(grid), dim3(kHessThreadsSmall), lds, st, k, fuse);
+        else TC2LI_LAUNCH(k_balm_hessian_b, dim3(grid), dim3(kHessThreadsSmall), 0, st, k);
+    }
     if (fuse) return;
-    TC2LI_LAUNCH(k_balm_combine_b, dim3((std::max(balm_part_stride(x.max_W), 12 * x.max_W) + 255) / 256, n), dim3(256), 0, st, ph);
+    if (const unsigned grid = cut(kGridBalmCombine, [](const BaWindowExtent& e) { return (std::max(balm_part_stride(e.lidar_W), 12 * e.lidar_W) + 255) / 256; }))
+        TC2LI_LAUNCH(k_balm_combine_b, dim3(grid), dim3(256), 0, st, k);
 }
 
 }  // namespace tc2li

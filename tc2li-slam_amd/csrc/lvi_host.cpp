@@ -540,10 +540,10 @@ bool lvi_batch_lockstep(const tc2li_lvi_problem* problems, int n, const tc2li_im
             any_maxdiag |= w.want_maxdiag;
             if (w.lidar) with_lidar.push_back(i);
         }
-        pieces(active, nullptr, [&](const BaPhase& ph, int cnt) { ba_batch_launch_linearize(ph, cnt, X, any_maxdiag, st); });
+        pieces(active, nullptr, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_linearize(ph, cnt, X, any_maxdiag, st); });
         // computeActiveErrors + linearizeOplus of the LiDAR edge: the residual at the accepted estimate and the Hessian, every iteration
         // (the one-window path's enqueue_error + enqueue_linearization)
-        pieces(with_lidar, nullptr, [&](const BaPhase& ph, int cnt) {
+        pieces(with_lidar, nullptr, [&](const BaPhaseHost& ph, int cnt) {
             balm_batch_launch_residual(ph, cnt, false, st);
             balm_batch_launch_hessian(ph, cnt, X, st);
         });
@@ -553,7 +553,7 @@ bool lvi_batch_lockstep(const tc2li_lvi_problem* problems, int n, const tc2li_im
         bool pre_schur = kPreSchur && !any_maxdiag;
         if (pre_schur) {
             for (int i : active) if (W[i].it == 0) W[i].lambda = W[i].p->lambda_init;  // (what the host's part sets below)
-            pieces(active, nullptr, [&](const BaPhase& ph, int cnt) { ba_batch_launch_schur(ph, cnt, X, st); });
+            pieces(active, nullptr, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_schur(ph, cnt, X, st); });
         }
         pool.parallel_for((int)active.size(), [&](int k) { LviWindow& w = W[active[k]]; w.chi_imu = w.inertial.cost(w.hp, w.sv, true); });
         lap(8);
@@ -617,12 +617,12 @@ bool lvi_batch_lockstep(const tc2li_lvi_problem* problems, int n, const tc2li_im
             for (int i : trial) if (W[i].lidar) trial_lidar.push_back(i);
             const bool have_schur = pre_schur;  // (this trial's product came with the linearisation)
             pre_schur = false;
-            pieces(trial, nullptr, [&](const BaPhase& ph, int cnt) {
+            pieces(trial, nullptr, [&](const BaPhaseHost& ph, int cnt) {
                 if (!have_schur) ba_batch_launch_schur(ph, cnt, X, st);
                 lvi_batch_launch_solve(ph, cnt, max_lvi_np, max_lvi_ni, st);
                 ba_batch_launch_trial(ph, cnt, X, st);
             });
-            if (X.any_trial_unfused) pieces(trial_lidar, nullptr, [&](const BaPhase& ph, int cnt) { balm_batch_launch_residual(ph, cnt, true, st); });
+            if (X.any_trial_unfused) pieces(trial_lidar, nullptr, [&](const BaPhaseHost& ph, int cnt) { balm_batch_launch_residual(ph, cnt, true, st); });
             sync();
             if (failed) break;
             lap(3);
@@ -657,7 +657,7 @@ bool lvi_batch_lockstep(const tc2li_lvi_problem* problems, int n, const tc2li_im
         while (!trial.empty() && !failed && !dev_solve) {
             if (pre_schur) pre_schur = false;  // (this trial's product came with the linearisation)
             else {
-                pieces(trial, nullptr, [&](const BaPhase& ph, int cnt) { ba_batch_launch_schur(ph, cnt, X, st); });
+                pieces(trial, nullptr, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_schur(ph, cnt, X, st); });
                 sync();
                 if (failed) break;
             }
@@ -684,8 +684,8 @@ bool lvi_batch_lockstep(const tc2li_lvi_problem* problems, int n, const tc2li_im
             if (!step.empty()) {
                 stage_steps(step);
                 // (the trial ImuCamPose states come back through slot.iposes_host, written by the trial kernel: a copy launch per trial before)
-                pieces(step, xp_pinned ? h_xp_area : d_xp_area, [&](const BaPhase& ph, int cnt) { ba_batch_launch_trial(ph, cnt, X, st); });
-                if (X.any_trial_unfused) pieces(step_lidar, nullptr, [&](const BaPhase& ph, int cnt) { balm_batch_launch_residual(ph, cnt, true, st); });  // (windows with pb.trial_fused: inside the trial launch)
+                pieces(step, xp_pinned ? h_xp_area : d_xp_area, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_trial(ph, cnt, X, st); });
+                if (X.any_trial_unfused) pieces(step_lidar, nullptr, [&](const BaPhaseHost& ph, int cnt) { balm_batch_launch_residual(ph, cnt, true, st); });  // (windows with pb.trial_fused: inside the trial launch)
                 pool.parallel_for((int)step.size(), [&](int k) {  // velocity / bias part of the step, on the host
                     LviWindow& w = W[step[k]];
                     const int np = w.vp.np;
@@ -725,7 +725,7 @@ bool lvi_batch_lockstep(const tc2li_lvi_problem* problems, int n, const tc2li_im
     std::vector<int> all;
     for (int i = 0; i < n; ++i) if (W[i].rc >= 0) all.push_back(i);
     if (!failed && !all.empty()) {
-        pieces(all, nullptr, [&](const BaPhase& ph, int cnt) { ba_batch_launch_depth(ph, cnt, X, st); });
+        pieces(all, nullptr, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_depth(ph, cnt, X, st); });
         size_t n_tasks = 0, max_bytes = 0;
         if (C.h_tasks.ensure(3 * all.size()) != hipSuccess) failed = true;
         for (int i : all) {
