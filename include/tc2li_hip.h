@@ -872,6 +872,80 @@ int tc2li_fuse_search(const tc2li_frame_view* keyframe, const float pose7[7], co
                       const float* inv_level_sigma2, int n_levels, float log_scale_factor, const tc2li_map_point* points,
                       const uint8_t* valid, int n_points, float th, int32_t* best_idx, int32_t* best_dist, void* stream);
 
+/* ---- local mapping for many keyframes: keyframe store, CreateNewMapPoints and Fuse search in batches ----
+ * The store keeps on the device what a KeyFrame never changes after its constructor (SF/src/KeyFrame.cc:56-104: mvKeysUn,
+ * mDescriptors, mvuRight, mvDepth, mFeatVec, mnMinX .. mnMaxY, and the feature grid mGrid that GetFeaturesInArea :716-760 walks),
+ * so that the batch entries below upload only what changes between calls: the poses (GetPose() after a BA) and has_point
+ * (GetMapPoint(i) != NULL after every created or fused point).
+ * One slab is allocated at create; a slot has a fixed size derived from max_keypoints, so a put never moves another slot, and puts
+ * into other slots are safe while searches run.  Slots are numbered 0 .. max_keyframes - 1; the caller keeps the keyframe -> slot
+ * map: put at Tracking::CreateNewKeyFrame, erase at KeyFrame::SetBadFlag (:585). */
+typedef struct tc2li_keyframe_store tc2li_keyframe_store;
+int tc2li_keyframe_store_create(int max_keyframes, int max_keypoints, tc2li_keyframe_store** out);
+int tc2li_keyframe_store_destroy(tc2li_keyframe_store* store);
+/* Stores n keyframes: views[k] goes to slots[k] (an occupied slot is replaced), bounds4[k] = mnMinX, mnMaxX, mnMinY, mnMaxY.  The
+ * has_point and pose7 fields of the views are IGNORED: they are inputs of every search.  All views are packed into one pinned
+ * staging block, copied once, and the feature grids of the n keyframes are built by one launch; the call returns when the data is
+ * resident, so a search on any stream may follow.  Every check comes before any device work, and a refused call leaves the store
+ * unchanged: the checks of tc2li_create_new_map_points on a view plus octaves in [0, n_levels); TC2LI_ERR_CAPACITY for a keyframe
+ * with more keypoints (or feature-vector entries) than max_keypoints or than the feature grid's 3072; TC2LI_ERR_INVALID for a slot
+ * out of range or named twice in the call. */
+int tc2li_keyframe_store_put_batch(tc2li_keyframe_store* store, int n, const int32_t* slots, const tc2li_keyframe_view* views,
+                                   const float* bounds4, int n_levels, void* stream);
+int tc2li_keyframe_store_erase(tc2li_keyframe_store* store, int slot);
+/* n_keypoints / n_nodes of the keyframe in the slot; -1 / -1 for an empty slot */
+int tc2li_keyframe_store_info(tc2li_keyframe_store* store, int slot, int32_t* n_keypoints, int32_t* n_nodes);
+
+/* One LocalMapping::CreateNewMapPoints (SF/src/LocalMapping.cc:402-726): mpCurrentKeyFrame and vpNeighKFs as store slots, with the
+ * poses and has_point they have at the time of the call.  The same slot may appear in many problems with different poses and
+ * has_point. */
+typedef struct tc2li_new_points_problem {
+    int32_t current;                 /* store slot of mpCurrentKeyFrame */
+    int32_t n_neighbours;
+    const int32_t* neighbours;       /* store slots, vpNeighKFs in order */
+    const float* poses7;             /* [1 + n_neighbours][7]: GetPose() of current, then of each neighbour */
+    const uint8_t* const* has_point; /* [1 + n_neighbours] arrays, each of that keyframe's n */
+    uint8_t inertial, far_points, coarse, pad_; /* mbInertial, mbFarPoints, bCoarse */
+    float th_far_points;             /* mThFarPoints */
+} tc2li_new_points_problem;
+
+/* tc2li_create_new_map_points for n_problems keyframes in one call: problem p yields exactly the records of the single call for
+ * the same keyframe, neighbours, poses, has_point and flags -- same creation order (neighbour-major, keypoint-ascending, a
+ * keypoint served by an earlier neighbour skipped for the later ones), same x3D bits -- at points[point_offsets[p] ...], and
+ * n_points[p] of them (at most one per keypoint of the current keyframe).  One packed upload, three kernel launches whatever the
+ * batch, one download, one wait; the stream is the caller's or, when NULL, the calling thread's own, and concurrent callers share no
+ * work space.  Room point_offsets[p + 1] - point_offsets[p] smaller than a problem's count: TC2LI_ERR_CAPACITY, with n_points
+ * filled for all problems (and the records that fit written).  An empty or out-of-range slot: TC2LI_ERR_INVALID before any launch.
+ * Returns the number of points written. */
+int tc2li_create_new_map_points_batch(tc2li_keyframe_store* store, const tc2li_new_points_problem* problems, int n_problems,
+                                      const tc2li_camera* cam, float mb, const float* scale_factors, const float* level_sigma2,
+                                      int n_levels, float scale_factor, tc2li_new_map_point* points, const int32_t* point_offsets,
+                                      int32_t* n_points, void* stream);
+
+/* One ORBmatcher::Fuse(pKF, vpMapPoints, th) search (SF/src/ORBmatcher.cc:1157-1330) of LocalMapping::SearchInNeighbors (:728-837). */
+typedef struct tc2li_fuse_item {
+    int32_t keyframe;          /* store slot of the keyframe the points are fused into */
+    int32_t first_point;       /* into points[] */
+    int32_t first_valid;       /* into valid[]: valid differs per target (IsInKeyFrame), the point list often does not */
+    int32_t n_points;
+    float pose7[7];            /* GetPose() of that keyframe */
+    float th;
+} tc2li_fuse_item;
+
+/* tc2li_fuse_search for n_items (keyframe, point list) items in one call, on the grids the store built at put: the results of item k
+ * lie at best_idx / best_dist [first_valid, first_valid + n_points) -- the output is indexed like valid -- and equal those of the
+ * single call for that keyframe, pose, points, valid and th; n_fused[k] counts them.  Several items may name one point range.
+ * SearchInNeighbors has two stages and the second reads what the first changed, so the caller issues stage 1 (the current
+ * keyframe's points into every target keyframe, :778-788) for all sequences in one call, applies the results (Replace /
+ * AddObservation on its objects, as for the single call), then issues stage 2 (the targets' points into the current keyframe,
+ * :795-817: one item per sequence) in a second call.  One upload, one launch over all (item, point) pairs, one download.  An empty or
+ * out-of-range slot, a range outside n_points_total / n_valid_total or log_scale_factor <= 0: TC2LI_ERR_INVALID before any
+ * launch.  best_dist may be NULL.  Returns the sum of n_fused. */
+int tc2li_fuse_search_batch(tc2li_keyframe_store* store, const tc2li_fuse_item* items, int n_items, const float cam4[4], float bf,
+                            const float* scale_factors, const float* inv_level_sigma2, int n_levels, float log_scale_factor,
+                            const tc2li_map_point* points, int n_points_total, const uint8_t* valid, int n_valid_total,
+                            int32_t* best_idx, int32_t* best_dist, int32_t* n_fused, void* stream);
+
 /* Per-map-point refresh of local mapping after a local BA / after creating or fusing points (LocalMapping.cc, Optimizer.cc:1506,
  * OptimizerWithLidar.cc:484 `pMP->UpdateNormalAndDepth()`; `ComputeDistinctiveDescriptors` in CreateNewMapPoints / Fuse):
  * MapPoint::ComputeDistinctiveDescriptors (SF/src/MapPoint.cc:338-412) and MapPoint::UpdateNormalAndDepth (:444-503) for a flat

@@ -47,4 +47,7 @@ from .capi import (  # noqa: F401
     mlpnp_ransac_batch,
     keyframe_culling_batch,
     map_point_culling_batch,
+    KeyframeStore,
+    create_new_map_points_batch,
+    fuse_search_batch,
 )

@@ -987,6 +987,10 @@ class NewMapPoint(C.Structure):
     _fields_ = [("idx1", C.c_int32), ("neighbour", C.c_int32), ("idx2", C.c_int32), ("stereo", C.c_int32), ("x3D", C.c_float * 3), ("pad_", C.c_float)]
 
 
+NEW_MAP_POINT_DTYPE = np.dtype([("idx1", "<i4"), ("neighbour", "<i4"), ("idx2", "<i4"), ("stereo", "<i4"), ("x3D", "<f4", (3,)), ("pad_", "<f4")])
+assert NEW_MAP_POINT_DTYPE.itemsize == C.sizeof(NewMapPoint)
+
+
 def pack_keyframe_views(items):
     """items: dicts with keys (KEYPOINT_DTYPE), descriptors, u_right, depth, has_point, fv_node, fv_offset, fv_index, pose7 ->
     (ctypes array of tc2li_keyframe_view, keep-alive list)."""
@@ -1108,6 +1112,164 @@ def fuse_search(keys, desc, u_right, cols, rows, pose7, cam4, bf, scale_factors,
     nf = _check(f(C.addressof(fv), p7.ctypes.data, c4.ctypes.data, bf, sf.ctypes.data, isg.ctypes.data, len(sf), log_scale_factor, pts.ctypes.data,
                   val.ctypes.data, m, th, bi.ctypes.data, bd.ctypes.data, C.c_void_p(stream)))
     return nf, bi[:m], bd[:m]
+
+
+# ---- local mapping for many keyframes: keyframe store, CreateNewMapPoints / Fuse search in batches ---------------------------------------
+class NewPointsProblem(C.Structure):
+    """tc2li_new_points_problem"""
+    _fields_ = [("current", C.c_int32), ("n_neighbours", C.c_int32), ("neighbours", C.c_void_p), ("poses7", C.c_void_p), ("has_point", C.c_void_p),
+                ("inertial", C.c_uint8), ("far_points", C.c_uint8), ("coarse", C.c_uint8), ("pad_", C.c_uint8), ("th_far_points", C.c_float)]
+
+
+class FuseItem(C.Structure):
+    """tc2li_fuse_item"""
+    _fields_ = [("keyframe", C.c_int32), ("first_point", C.c_int32), ("first_valid", C.c_int32), ("n_points", C.c_int32), ("pose7", C.c_float * 7),
+                ("th", C.c_float)]
+
+
+class KeyframeStore:
+    """``tc2li_keyframe_store``: what a keyframe never changes after creation, resident on the device.  Slots are 0 .. max_keyframes - 1."""
+
+    def __init__(self, max_keyframes, max_keypoints):
+        self._h = C.c_void_p()
+        f = lib().tc2li_keyframe_store_create
+        f.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        _check(f(int(max_keyframes), int(max_keypoints), C.byref(self._h)))
+        self.max_keyframes, self.max_keypoints = int(max_keyframes), int(max_keypoints)
+
+    def _handle(self):
+        if not self._h:
+            raise Tc2liError(-1, "keyframe store is closed")
+        return self._h
+
+    def put_batch(self, slots, keyframes, bounds, n_levels=8, stream=0):
+        """keyframes: the dicts ``pack_keyframe_views`` takes (``has_point`` / ``pose7`` may be absent: they are not stored);
+        bounds: (min_x, max_x, min_y, max_y), one for all or one per keyframe."""
+        items = []
+        for kf in keyframes:
+            it = dict(kf)
+            it.setdefault("has_point", np.zeros(len(kf["keys"]), np.uint8))
+            it.setdefault("pose7", np.float32([0, 0, 0, 1, 0, 0, 0]))
+            items.append(it)
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        if len(sl) != len(items):
+            raise ValueError("one slot per keyframe")
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(bounds, np.float32).reshape(-1, 4), (len(items), 4)), np.float32)
+        arr, keep = pack_keyframe_views(items)
+        f = lib().tc2li_keyframe_store_put_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _check(f(self._handle(), len(items), sl.ctypes.data, C.addressof(arr), b.ctypes.data, int(n_levels), C.c_void_p(stream)))
+        del keep
+
+    def erase(self, slot):
+        f = lib().tc2li_keyframe_store_erase
+        f.argtypes = [C.c_void_p, C.c_int]
+        _check(f(self._handle(), int(slot)))
+
+    def info(self, slot):
+        """(n_keypoints, n_nodes) of the keyframe in the slot, (-1, -1) for an empty slot."""
+        n, m = C.c_int32(0), C.c_int32(0)
+        f = lib().tc2li_keyframe_store_info
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _check(f(self._handle(), int(slot), C.byref(n), C.byref(m)))
+        return n.value, m.value
+
+    def close(self):
+        if self._h:
+            f = lib().tc2li_keyframe_store_destroy
+            f.argtypes = [C.c_void_p]
+            f(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pack_new_points_problems(store, problems):
+    """problems: dicts with current (slot), neighbours (slots), poses7 [1 + k, 7], has_point (1 + k arrays: of the current keyframe, then of
+    each neighbour) and optionally inertial, far_points, th_far_points, coarse -> (ctypes array, keep-alive list, keypoints of each current)."""
+    arr = (NewPointsProblem * max(len(problems), 1))()
+    keep, n_cur = [], []
+    for i, pr in enumerate(problems):
+        nb = np.ascontiguousarray(pr["neighbours"], np.int32).reshape(-1)
+        p7 = np.ascontiguousarray(pr["poses7"], np.float32).reshape(-1, 7)
+        hps = [np.ascontiguousarray(h, np.uint8).reshape(-1) for h in pr["has_point"]]
+        if len(p7) != 1 + len(nb) or len(hps) != 1 + len(nb):
+            raise ValueError("problem %d: one pose and one has_point array for the current keyframe and for each neighbour" % i)
+        for s, h in zip([int(pr["current"])] + [int(v) for v in nb], hps):
+            n = store.info(s)[0] if 0 <= s < store.max_keyframes else -1
+            if n >= 0 and len(h) != n:
+                raise ValueError("problem %d: has_point of slot %d has %d entries, the keyframe %d keypoints" % (i, s, len(h), n))
+        ptrs = (C.c_void_p * len(hps))(*[h.ctypes.data for h in hps])
+        keep.append((nb, p7, hps, ptrs))
+        arr[i].current, arr[i].n_neighbours = int(pr["current"]), len(nb)
+        arr[i].neighbours, arr[i].poses7, arr[i].has_point = nb.ctypes.data, p7.ctypes.data, C.addressof(ptrs)
+        arr[i].inertial, arr[i].far_points, arr[i].coarse = int(bool(pr.get("inertial", False))), int(bool(pr.get("far_points", False))), int(bool(pr.get("coarse", False)))
+        arr[i].th_far_points = float(pr.get("th_far_points", 0.0))
+        n0 = store.info(int(pr["current"]))[0] if 0 <= int(pr["current"]) < store.max_keyframes else 0
+        n_cur.append(max(n0, 0))
+    return arr, keep, n_cur
+
+
+def create_new_map_points_batch(store, problems, cam5, mb, scale_factors, level_sigma2, scale_factor=1.2, capacities=None, stream=0, raw=False):
+    """``tc2li_create_new_map_points_batch`` -> one (idx [k, 4] = idx1, neighbour, idx2, stereo; x3D [k, 3]) per problem, as
+    ``create_new_map_points`` gives it.  capacities: room per problem (default: the keypoints of its current keyframe, which always
+    suffices).  raw=True -> (return code, n_points [P], records) without raising on TC2LI_ERR_CAPACITY."""
+    arr, keep, n_cur = pack_new_points_problems(store, problems)
+    cam5 = np.ascontiguousarray(cam5, np.float64)
+    sf, sg = np.ascontiguousarray(scale_factors, np.float32), np.ascontiguousarray(level_sigma2, np.float32)
+    caps = np.asarray(n_cur if capacities is None else capacities, np.int64).reshape(-1)
+    off = np.concatenate([[0], np.cumsum(caps)]).astype(np.int32)
+    pts = np.zeros(max(int(off[-1]), 1), NEW_MAP_POINT_DTYPE)
+    cnt = np.zeros(max(len(problems), 1), np.int32)
+    f = lib().tc2li_create_new_map_points_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p]
+    rc = f(store._handle(), C.addressof(arr), len(problems), cam5.ctypes.data, mb, sf.ctypes.data, sg.ctypes.data, len(sf), scale_factor, pts.ctypes.data,
+           off.ctypes.data, cnt.ctypes.data, C.c_void_p(stream))
+    del keep
+    cnt = cnt[:len(problems)]
+    if raw:
+        return rc, cnt, [pts[off[p]:off[p] + min(int(cnt[p]), int(caps[p]))] for p in range(len(problems))]
+    _check(rc)
+    out = []
+    for p in range(len(problems)):
+        r = pts[off[p]:off[p] + cnt[p]]
+        out.append((np.stack([r["idx1"], r["neighbour"], r["idx2"], r["stereo"]], 1).astype(np.int32).reshape(-1, 4), r["x3D"].astype(np.float32).reshape(-1, 3)))
+    return out
+
+
+def fuse_search_batch(store, items, cam4, bf, scale_factors, inv_level_sigma2, log_scale_factor, points, valid, stream=0):
+    """``tc2li_fuse_search_batch``.  items: dicts with keyframe (slot), first_point, first_valid, n_points, pose7, th; points:
+    MAP_POINT_DTYPE (all lists, concatenated), valid: uint8 (one range per item) -> (n_fused [items], best_idx, best_dist), the last
+    two indexed like ``valid``."""
+    arr = (FuseItem * max(len(items), 1))()
+    for i, it in enumerate(items):
+        arr[i].keyframe, arr[i].first_point, arr[i].first_valid, arr[i].n_points = int(it["keyframe"]), int(it["first_point"]), int(it["first_valid"]), int(it["n_points"])
+        arr[i].pose7 = (C.c_float * 7)(*[float(v) for v in it["pose7"]])
+        arr[i].th = float(it.get("th", 3.0))
+    pts = np.ascontiguousarray(points, MAP_POINT_DTYPE)
+    val = np.ascontiguousarray(valid, np.uint8).reshape(-1)
+    sf, isg = np.ascontiguousarray(scale_factors, np.float32), np.ascontiguousarray(inv_level_sigma2, np.float32)
+    c4 = np.ascontiguousarray(cam4, np.float32)
+    m = len(val)
+    bi, bd, nf = np.full(max(m, 1), -1, np.int32), np.full(max(m, 1), 256, np.int32), np.zeros(max(len(items), 1), np.int32)
+    f = lib().tc2li_fuse_search_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(f(store._handle(), C.addressof(arr), len(items), c4.ctypes.data, bf, sf.ctypes.data, isg.ctypes.data, len(sf), log_scale_factor,
+             pts.ctypes.data if len(pts) else None, len(pts), val.ctypes.data if m else None, m, bi.ctypes.data, bd.ctypes.data, nf.ctypes.data,
+             C.c_void_p(stream)))
+    return nf[:len(items)], bi[:m], bd[:m]
 
 
 def map_points_refresh(obs_off, descriptors, centres, positions, ref_centres, level_scale, last_scale, stream=0):

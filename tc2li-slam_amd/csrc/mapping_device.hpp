@@ -43,6 +43,20 @@ struct FuseDev {  // ORBmatcher::Fuse, search part
     const uint8_t* valid;
     int32_t *best_idx, *best_dist;
 };
+// ---- the batch entries over the keyframe store (keyframe_store.cpp) ----
+constexpr int kNewPointsMaxKeys = 3072;  // = kMaxMatchKeys: what a slot of the store holds at most
+struct PairRef { int32_t problem, neighbour; };  // one (problem, neighbour) pair of a batch; problems[problem].neigh[neighbour]
+struct NewPointsOut {  // where k_new_points_compact puts the records of a problem
+    int32_t pair_first;    // the problem's first pair: its per-neighbour counts live at neigh_count[pair_first ...]
+    int32_t first_record;  // into records, in tc2li_new_map_point units
+    int32_t room;          // records the caller has room for
+    int32_t pad_;
+};
+// search + point kernels over all pairs, then the first-neighbour rule and the ordered compaction: three launches whatever the batch
+void launch_new_points_batch(const MappingDev* problems, int n_problems, const PairRef* pairs, int n_pairs, int max_entries, int max_keys,
+                             const NewPointsOut* outs, int32_t* neigh_count, int32_t* n_points, uint8_t* records, hipStream_t st);
+// one launch over all (item, point) pairs; best_idx / best_dist / points / valid of every FuseDev point at the item's range
+void launch_fuse_search_batch(const FuseDev* items, int n_items, int max_points, hipStream_t st);
 void launch_fuse_search(const FuseDev& f, hipStream_t st);
 void launch_tri_search(const MappingDev& m, int max_entries, hipStream_t st);
 void launch_tri_points(const MappingDev& m, hipStream_t st);

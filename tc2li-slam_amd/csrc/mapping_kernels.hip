@@ -4,7 +4,9 @@
 //   k_tri_points   the per-pair body of LocalMapping::CreateNewMapPoints (SF/src/LocalMapping.cc:497-723): parallax gates,
 //                  GeometricTools::Triangulate or KeyFrame::UnprojectStereo, depth / reprojection / scale gates
 // The reference lets a keypoint that received a point from an earlier neighbour drop out of the later neighbours; a pair's result
-// does not depend on any other pair, so every (neighbour, keypoint) is evaluated here and the host keeps the first success.
+// does not depend on any other pair, so every (neighbour, keypoint) is evaluated here and the first success is kept afterwards: by
+// the host in the single-keyframe entry, by k_new_points_compact in the batch entry.  The *_batch kernels run the same device
+// functions over a device table of (problem, neighbour) pairs or fuse items (keyframe_store.cpp).
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
@@ -23,8 +25,8 @@ __device__ __forceinline__ Kp load_kp(const float* keys, int i) {
     return o;
 }
 
-__global__ __launch_bounds__(256) void k_tri_search(MappingDev m) {
-    const int j = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;
+// feature-vector entry e of the current keyframe against neighbour j: the body shared by k_tri_search and k_tri_search_batch
+__device__ __forceinline__ void tri_search_entry(const MappingDev& m, int j, int e) {
     const KfDev& k2 = m.neigh[j];
     const KfDev& k1 = m.cur;
     if (e >= k1.fv_off[k1.n_nodes] || k2.skip) return;
@@ -75,6 +77,14 @@ __global__ __launch_bounds__(256) void k_tri_search(MappingDev m) {
         if (ok) { bestIdx2 = idx2; bestDist = dist; }
     }
     if (bestIdx2 >= 0) m.match[(size_t)j * k1.n + idx1] = bestIdx2;
+}
+
+__global__ __launch_bounds__(256) void k_tri_search(MappingDev m) { tri_search_entry(m, blockIdx.y, blockIdx.x * 256 + threadIdx.x); }
+// every (problem, neighbour) pair of a batch: `chunks` workgroups per pair, the problems' MappingDev records in a device table
+__global__ __launch_bounds__(256) void k_tri_search_batch(const MappingDev* __restrict__ problems, const PairRef* __restrict__ pairs, int chunks) {
+    const PairRef pr = pairs[blockIdx.x / chunks];
+    const MappingDev m = problems[pr.problem];
+    tri_search_entry(m, pr.neighbour, (blockIdx.x % chunks) * 256 + threadIdx.x);
 }
 
 // eigenvector of the smallest eigenvalue of the symmetric 4 x 4 M (cyclic Jacobi, double) -- stands in for JacobiSVD<Matrix4f>
@@ -131,8 +141,8 @@ __device__ __forceinline__ bool reproj_gate(const MappingDev& m, const float* Rc
     return !((double)(ex * ex + ey * ey + er * er) > 7.8 * (double)sig);
 }
 
-__global__ __launch_bounds__(128) void k_tri_points(MappingDev m) {
-    const int j = blockIdx.y, idx1 = blockIdx.x * 128 + threadIdx.x;
+// keypoint idx1 of the current keyframe and its match in neighbour j: the body shared by k_tri_points and k_tri_points_batch
+__device__ __forceinline__ void tri_point_pair(const MappingDev& m, int j, int idx1) {
     const KfDev& k1 = m.cur;
     const KfDev& k2 = m.neigh[j];
     if (idx1 >= k1.n || k2.skip) return;
@@ -217,6 +227,73 @@ __global__ __launch_bounds__(128) void k_tri_points(MappingDev m) {
     m.x3D[3 * slot] = x3D[0]; m.x3D[3 * slot + 1] = x3D[1]; m.x3D[3 * slot + 2] = x3D[2];
 }
 
+__global__ __launch_bounds__(128) void k_tri_points(MappingDev m) { tri_point_pair(m, blockIdx.y, blockIdx.x * 128 + threadIdx.x); }
+__global__ __launch_bounds__(128) void k_tri_points_batch(const MappingDev* __restrict__ problems, const PairRef* __restrict__ pairs, int chunks) {
+    const PairRef pr = pairs[blockIdx.x / chunks];
+    const MappingDev m = problems[pr.problem];
+    tri_point_pair(m, pr.neighbour, (blockIdx.x % chunks) * 128 + threadIdx.x);
+}
+
+// The "first neighbour that yields a point keeps the keypoint" rule of LocalMapping::CreateNewMapPoints and the ordered output
+// (neighbour-major, keypoint-ascending), one workgroup per problem.  first[i] = the smallest j with ok[j][i]; a wavefront counts the
+// keypoints of its neighbours (j = wave, wave + 4, ...) with ballots, wavefront 0 scans the counts over the neighbours, and the second
+// walk over the same 64-wide strides gives every point the rank base + mbcnt(ballot).  No atomic takes part: the order is a function
+// of ok alone.  The count is written whatever the room; records beyond the problem's room are dropped (the host reports it).
+__global__ __launch_bounds__(256) void k_new_points_compact(const MappingDev* __restrict__ problems, const NewPointsOut* __restrict__ outs,
+                                                            int32_t* neigh_count, int32_t* n_points, uint8_t* records) {
+    __shared__ int32_t s_first[kNewPointsMaxKeys];
+    const MappingDev m = problems[blockIdx.x];
+    const NewPointsOut o = outs[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = m.cur.n, nn = m.n_neigh;
+    int32_t* cnt = neigh_count + o.pair_first;
+    for (int i = tid; i < n; i += 256) {
+        int first = -1;
+        for (int j = 0; j < nn; ++j)
+            if (m.ok[(size_t)j * n + i]) { first = j; break; }
+        s_first[i] = first;
+    }
+    __syncthreads();
+    for (int j = wave; j < nn; j += 4) {
+        int c = 0;
+        for (int base = 0; base < n; base += 64) {
+            const int i = base + lane;
+            c += __popcll(__ballot(i < n && s_first[i] == j));
+        }
+        if (lane == 0) cnt[j] = c;
+    }
+    __syncthreads();
+    if (wave == 0) {  // exclusive scan over the neighbours, 64 at a time with a running base
+        int run = 0;
+        for (int base = 0; base < nn; base += 64) {
+            const int j = base + lane;
+            const int c = j < nn ? cnt[j] : 0;
+            int incl = c;
+            for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d, 64); if (lane >= d) incl += t; }
+            if (j < nn) cnt[j] = run + incl - c;
+            run += __shfl(incl, 63, 64);
+        }
+        if (lane == 0) n_points[blockIdx.x] = run;
+    }
+    __syncthreads();
+    for (int j = wave; j < nn; j += 4) {
+        int run = cnt[j];
+        for (int base = 0; base < n; base += 64) {
+            const int i = base + lane;
+            const bool mine = i < n && s_first[i] == j;
+            const unsigned long long mask = __ballot(mine);
+            const int rank = run + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+            if (mine && rank < o.room) {
+                const size_t slot = (size_t)j * n + i;
+                int32_t* r = reinterpret_cast<int32_t*>(records + 32 * ((size_t)o.first_record + rank));  // tc2li_new_map_point
+                r[0] = i; r[1] = j; r[2] = m.match[slot]; r[3] = (m.ok[slot] & 2) ? 1 : 0;
+                r[4] = __float_as_int(m.x3D[3 * slot]); r[5] = __float_as_int(m.x3D[3 * slot + 1]); r[6] = __float_as_int(m.x3D[3 * slot + 2]);
+                r[7] = 0;
+            }
+            run += __popcll(mask);
+        }
+    }
+}
+
 // ORBmatcher::Fuse, the search of one map point (SF/src/ORBmatcher.cc:1185-1300): projection and gates, predicted level, the
 // keypoints of the window on the keyframe's feature grid, level / reprojection gates, best descriptor distance
 __device__ __forceinline__ void q_rot_dev(const float q[4], const float v[3], float out[3]) {  // Eigen _transformVector
@@ -227,8 +304,8 @@ __device__ __forceinline__ void q_rot_dev(const float q[4], const float v[3], fl
     out[2] = v[2] + q[3] * uv[2] + (q[0] * uv[1] - q[1] * uv[0]);
 }
 constexpr int kFuseGridCols = 64, kFuseGridRows = 48;
-__global__ __launch_bounds__(128) void k_fuse_search(FuseDev f) {
-    const int i = blockIdx.x * 128 + threadIdx.x;
+// map point i of the list against the keyframe: the body shared by k_fuse_search and k_fuse_search_batch
+__device__ __forceinline__ void fuse_point(const FuseDev& f, int i) {
     if (i >= f.n_points) return;
     int best_idx = -1, best_dist = 256;
     const float* P = reinterpret_cast<const float*>(f.points + 68 * (size_t)i);  // pos 3, normal 3, min, max, max_raw, descriptor
@@ -297,8 +374,27 @@ __global__ __launch_bounds__(128) void k_fuse_search(FuseDev f) {
     f.best_idx[i] = best_dist <= 50 ? best_idx : -1;  // TH_LOW
 }
 
+__global__ __launch_bounds__(128) void k_fuse_search(FuseDev f) { fuse_point(f, blockIdx.x * 128 + threadIdx.x); }
+// every (item, point) of a batch: `chunks` workgroups per item, the items' FuseDev records (grids of the keyframe store) in a device table
+__global__ __launch_bounds__(128) void k_fuse_search_batch(const FuseDev* __restrict__ items, int chunks) {
+    const FuseDev f = items[blockIdx.x / chunks];
+    fuse_point(f, (blockIdx.x % chunks) * 128 + threadIdx.x);
+}
+
 void launch_fuse_search(const FuseDev& f, hipStream_t st) {
     if (f.n_points > 0) TC2LI_LAUNCH(k_fuse_search, dim3((f.n_points + 127) / 128), dim3(128), 0, st, f);
+}
+
+void launch_fuse_search_batch(const FuseDev* items, int n_items, int max_points, hipStream_t st) {
+    const int chunks = (max_points + 127) / 128;
+    if (n_items > 0 && chunks > 0) TC2LI_LAUNCH(k_fuse_search_batch, dim3((unsigned)n_items * chunks), dim3(128), 0, st, items, chunks);
+}
+void launch_new_points_batch(const MappingDev* problems, int n_problems, const PairRef* pairs, int n_pairs, int max_entries, int max_keys,
+                             const NewPointsOut* outs, int32_t* neigh_count, int32_t* n_points, uint8_t* records, hipStream_t st) {
+    const int cs = (max_entries + 255) / 256, cp = (max_keys + 127) / 128;
+    if (n_pairs > 0 && cs > 0) TC2LI_LAUNCH(k_tri_search_batch, dim3((unsigned)n_pairs * cs), dim3(256), 0, st, problems, pairs, cs);
+    if (n_pairs > 0 && cp > 0) TC2LI_LAUNCH(k_tri_points_batch, dim3((unsigned)n_pairs * cp), dim3(128), 0, st, problems, pairs, cp);
+    if (n_problems > 0) TC2LI_LAUNCH(k_new_points_compact, dim3(n_problems), dim3(256), 0, st, problems, outs, neigh_count, n_points, records);
 }
 
 void launch_tri_search(const MappingDev& m, int max_entries, hipStream_t st) {

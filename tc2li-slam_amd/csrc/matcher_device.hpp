@@ -48,6 +48,7 @@ struct MatchLists {
     uint32_t* pool;
     int32_t* pool_top;     // [0] = entries used, [1] = overflow flag
     int32_t pool_cap, pad_;
+    const int32_t* cell_row;  // k_match_grid only: frame f writes row cell_row[f] of cell_start; NULL = row f (the keyframe store: row = slot)
 };
 // only the feature grids (cell_start, items) of the frames: used by the fuse search as well
 void launch_match_grid(const MatchFrameDev* frames, int nframes, const MatchLists& L, hipStream_t st);

@@ -212,7 +212,7 @@ __global__ __launch_bounds__(kThreads) void k_match_grid(const MatchFrameDev* __
         }
     }
     __syncthreads();
-    int32_t* cs = L.cell_start + (size_t)blockIdx.x * (kCells + 1);
+    int32_t* cs = L.cell_start + (size_t)(L.cell_row ? L.cell_row[blockIdx.x] : (int)blockIdx.x) * (kCells + 1);
     uint16_t* it = L.items + L.key_base[blockIdx.x];
     for (int c = tid; c <= kCells; c += kThreads) cs[c] = s_cell_start[c];
     const int n_in = s_cell_start[kCells];

@@ -39,7 +39,7 @@ int resolve_ambiguous_levels(SearchScratch& s, const TrackConst& C, PatchLaunche
 }
 
 int projection_search(SearchScratch& s, const SearchPass& P, hipStream_t st, const std::function<int()>& behind) {
-    const MatchLists L{s.d_cell_start.p, s.d_items.p, P.d_key_base, s.d_cand_off.p, s.d_cand_cnt.p, s.d_pool.p, s.pool_top(), s.pool_cap, 0};
+    const MatchLists L{s.d_cell_start.p, s.d_items.p, P.d_key_base, s.d_cand_off.p, s.d_cand_cnt.p, s.d_pool.p, s.pool_top(), s.pool_cap, 0, nullptr};
     launch_match_lists(P.d_mframes, P.n_pass, s.d_query_frame.p, P.total_q, L, P.mode, P.nn_ratio, s.d_match.p, s.d_prev.p, s.d_rounds.p, st, P.orb_dist);
     TC2LI_HIP_CHECK(hipGetLastError());
     TC2LI_HIP_CHECK(hipMemcpyAsync(s.h_small.p, s.pool_top(), 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
