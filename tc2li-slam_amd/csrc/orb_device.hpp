@@ -51,6 +51,9 @@ void launch_quadtree_gather(const QuadJob* jobs, const uint32_t* picked, const i
 
 void launch_resize(const LevelDesc& src, const LevelDesc& dst, const int* xofs, const short* ialpha, const int* yofs,
                    const short* ibeta, int nimg, hipStream_t st);
+// the strip form (and with it the tail) reads the eight taps of four columns out of 8 bytes and stores one destination row per source row
+// at most: 1 < scale <= 2, rows of 8 bytes or more
+bool resize_strips_cover(const LevelDesc& src, const LevelDesc& dst);
 // levels l0 .. n_levels - 1 of every image in one launch (one workgroup per image walks them; batches: the chain of dependent launches is the cost)
 void launch_resize_tail(const LevelTable& lv, const int* const* xofs, const short* const* ialpha, const int* const* yofs, const short* const* ibeta, int l0, int n_levels,
                         int nimg, hipStream_t st);

@@ -384,7 +384,9 @@ int tc2li_orb_extract_batch(tc2li_orb* o, const uint8_t* dev_images, int n_image
         // the pyramid: the large levels a launch each over the whole GPU, the small ones (from level kTailFrom on) in ONE launch, a workgroup per
         // image -- seven dependent launches cost the chunk's stream ~0.6 ms each beside the other stages' kernels, whatever their size
         static const int kTailFromEnv = getenv("TC2LI_RESIZE_TAIL_FROM") ? atoi(getenv("TC2LI_RESIZE_TAIL_FROM")) : 3;
-        const int tail_from = (m >= 32 && kTailFromEnv >= 1) ? std::min(kTailFromEnv, L) : L;
+        int tail_from = (m >= 32 && kTailFromEnv >= 1) ? std::min(kTailFromEnv, L) : L;
+        for (int l = std::max(tail_from, 1); l < L; ++l)
+            if (!resize_strips_cover(craw.lv[l - 1], craw.lv[l])) tail_from = L;  // (launch_resize then takes the pixel form for that level)
         for (int l = 1; l < tail_from; ++l)
             launch_resize(craw.lv[l - 1], craw.lv[l], o->d_xofs[l].p, o->d_ialpha[l].p, o->d_yofs[l].p, o->d_ibeta[l].p, m, cst);
         if (tail_from < L) {

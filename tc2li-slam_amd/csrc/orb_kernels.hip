@@ -113,76 +113,132 @@ __global__ __launch_bounds__(256) void k_resize_linear(const uint8_t* __restrict
 // lane-operations per pixel: 363 -> 196 us per launch of 1024 images.  Same integers as the kernel above: tests/test_orb_gpu.py
 // compares every level with the oracle.
 constexpr int kResizeRows = 16;
-__device__ __forceinline__ uint32_t load_u16_unaligned(const uint8_t* p) {
-    uint16_t w;
-    __builtin_memcpy(&w, p, 2);
-    return w;
-}
+// Round 4's unit walked its destination rows one after the other: per row a scalar load of the row's table entries, then the taps of its new
+// source row, then the blend -- two dependent trips to memory per destination row with nothing else in flight (the kernel issued vector
+// instructions 9 % of its cycles and waited the rest; beside kernels that issue it took three times its stand-alone time).  The unit below
+// computes the same integers and changes when the loads are REQUESTED ("Pyramid resize: rows in flight"):
+//  * row tables up front: lane r loads the table entries of destination row dy_begin + r (one vector load per unit; a unit has at most 64
+//    rows), clamps its two source rows as before, and the walk reads them as scalars with readlane;
+//  * the walk goes over the unit's SOURCE rows sy0(first row) .. sy1(last row) -- they are contiguous, a destination row blends source rows
+//    sy1 - 1 (sy1 itself where the clamp folds the two) and sy1 -- in groups of kResizeGroup: every load of a group is requested before the
+//    first is used, and the next group is requested before this one is blended and stored (two register buffers).  Four source rows are 3.3
+//    destination rows at scale 1.2.  Every source row is loaded and passed horizontally once per unit, as before (`hp`);
+//  * ONE unaligned 8-byte load per source row holds the eight taps of the lane's four columns (scale <= 2: they span at most 8 bytes), and
+//    v_perm_b32 cuts tap pair k out of it with a selector made once per unit.  Near the row's end the load starts at sw - 8 instead of
+//    running past the row, and the clamped right tap (x + 1 == sw -> x, its weight is 0) is a selector like any other: edge lanes take the
+//    path of the interior lanes, without byte loads.  Lanes past the last column (dx0 >= dw) load what the last column loads and store
+//    nothing: all 64 lanes stay active, each holds a row of the table;
+//  * a partial last dword is stored byte-wise, as before.
+// No load leaves [row start, row start + sw) of a source row < sh.  What the form does not cover (scale > 2 or <= 1, rows shorter than 8
+// bytes: resize_strips_cover) goes through k_resize_linear.
+constexpr int kResizeGroup = 4;         // source rows per group: 3 / 4 / 6 / 8 measured, DESIGN.md
+constexpr int kResizeMaxUnitRows = 64;  // a lane per row of the unit's table
+typedef unsigned long long resize_u64_unaligned __attribute__((aligned(1)));
+__device__ __forceinline__ int clamp_row(int y, int sh) { return y < 0 ? 0 : (y >= sh ? sh - 1 : y); }
+
 // one wavefront's unit of the strip form: destination columns [dx0, dx0 + 4) of this lane, rows [dy_begin, dy_end) of one image
-// (S: the source image, D: the destination image + dx0)
+// (S: the source image, D: the destination image).  ALL 64 lanes enter.
 __device__ __forceinline__ void resize_strip_unit(const uint8_t* __restrict__ S, int src_pitch, int sw, int sh, uint8_t* __restrict__ D, int dst_pitch, int dw,
                                                   const int* __restrict__ xofs, const short* __restrict__ ialpha, const int* __restrict__ yofs,
                                                   const short* __restrict__ ibeta, int dx0, int dy_begin, int dy_end) {
-    int sx[4], a0[4], a1[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int dx = min(dx0 + k, dw - 1);
-        sx[k] = xofs[dx]; a0[k] = ialpha[2 * dx]; a1[k] = ialpha[2 * dx + 1];
-    }
-    const bool interior = dx0 + 3 < dw && sx[0] >= 0 && sx[3] + 1 < sw;  // every tap pair inside the row: two bytes from one load
-    // horizontal pass of source row `sy` for the lane's four columns, already shifted (r >> 4)
-    auto hpass = [&](int sy, int h[4]) {
-        const uint8_t* R = S + (size_t)sy * src_pitch;
-        if (interior) {
-            uint32_t w[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) w[k] = load_u16_unaligned(R + sx[k]);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) h[k] = ((int)(w[k] & 0xffu) * a0[k] + (int)(w[k] >> 8) * a1[k]) >> 4;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int x0 = sx[k], x1 = x0 + 1 < sw ? x0 + 1 : x0;  // weight of the clamped tap is 0
-                h[k] = dx0 + k < dw ? ((int)R[x0] * a0[k] + (int)R[x1] * a1[k]) >> 4 : 0;
-            }
-        }
-    };
-    int have = -1, hc[4] = {0, 0, 0, 0};
-    for (int dy = dy_begin; dy < dy_end; ++dy) {
-        int sy0 = yofs[dy], sy1 = sy0 + 1;
-        sy0 = sy0 < 0 ? 0 : (sy0 >= sh ? sh - 1 : sy0);
-        sy1 = sy1 < 0 ? 0 : (sy1 >= sh ? sh - 1 : sy1);
-        const int b0 = ibeta[2 * dy], b1 = ibeta[2 * dy + 1];
-        int h0[4], h1[4];
-        if (sy0 == have) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) h0[k] = hc[k];
-        } else {
-            hpass(sy0, h0);
-        }
-        if (sy1 == sy0) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) h1[k] = h0[k];
-        } else {
-            hpass(sy1, h1);
-        }
-        have = sy1;
-        uint32_t packed = 0;
+    constexpr int NS = kResizeGroup;
+    struct Taps { uint32_t lo, hi; };  // the 8 bytes of one source row at the lane's offset
+    const int lane = (int)(threadIdx.x & 63), nrows = dy_end - dy_begin;
+    // the unit's row table, a row per lane
+    const int dy_lane = min(dy_begin + lane, dy_end - 1);
+    const int y_lane = yofs[dy_lane];
+    const int sy0_lane = clamp_row(y_lane, sh), sy1_lane = clamp_row(y_lane + 1, sh);
+    uint32_t beta_lane;  // b0 | b1 << 16
+    __builtin_memcpy(&beta_lane, ibeta + 2 * dy_lane, 4);
+    // the lane's columns: weights, and where its taps lie in a source row
+    typedef short short2v __attribute__((ext_vector_type(2)));
+    uint32_t al[4], sel[4], off;  // ialpha pair of column k (a0 | a1 << 16); v_perm selector of its tap pair; byte offset of the lane's 8-byte load
+    {
+        int sx[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            hc[k] = h1[k];
-            const int v = (((b0 * h0[k]) >> 16) + ((b1 * h1[k]) >> 16) + 2) >> 2;
-            packed |= (uint32_t)(v & 0xff) << (8 * k);
+            const int dx = min(dx0 + k, dw - 1);
+            __builtin_memcpy(&al[k], ialpha + 2 * dx, 4);
+            sx[k] = xofs[dx];
         }
-        uint8_t* Drow = D + (size_t)dy * dst_pitch;
-        if (dx0 + 3 < dw) {
-            *reinterpret_cast<uint32_t*>(Drow) = packed;  // dst_pitch and dx0 are multiples of 4
-        } else {
-            for (int k = 0; k < 4 && dx0 + k < dw; ++k) Drow[k] = (uint8_t)(packed >> (8 * k));
+        const int first = min(sx[0], sw - 8);
+        off = (uint32_t)first;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int x0 = sx[k], x1 = x0 + 1 < sw ? x0 + 1 : x0;                            // weight of the clamped tap is 0
+            sel[k] = 0x0c000c00u | (uint32_t)(x0 - first) | ((uint32_t)(x1 - first) << 16);  // -> tap 0 | tap 1 << 16
         }
     }
+    const int sy_first = __builtin_amdgcn_readlane(sy0_lane, 0), sy_last = __builtin_amdgcn_readlane(sy1_lane, nrows - 1);
+    const auto* Sg = as_global(S);
+    // request source rows base .. base + NS - 1 (past the unit's last source row: that row again)
+    auto request = [&](Taps (&t)[NS], int base) {
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            // The load is to take the row's address as a scalar and the lane's 32-bit offset.  Left alone the compiler forms a 64-bit vector
+            // address per request and keeps several of them in registers.  The two empty statements keep the scalar and the offset apart
+            // until the load itself.
+            uint64_t row = (uint64_t)(Sg + (size_t)min(base + j, sy_last) * src_pitch);
+            asm volatile("" : "+s"(row));
+            uint32_t o = off;
+            asm volatile("" : "+v"(o));
+            const unsigned long long q = *reinterpret_cast<const __attribute__((address_space(1))) resize_u64_unaligned*>((const __attribute__((address_space(1))) uint8_t*)row + o);
+            t[j].lo = (uint32_t)q; t[j].hi = (uint32_t)(q >> 32);
+        }
+    };
+    int r = 0, hp[4] = {0, 0, 0, 0};  // r: the next destination row of the unit; hp: the horizontal pass of the source row before the current one
+    // the group's source rows in turn: horizontal pass, then blend and store the destination row whose lower source row this is
+    auto consume = [&](const Taps (&t)[NS], int base, auto last) {
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int sy = base + j;
+            if (decltype(last)::value && sy > sy_last) break;  // only the unit's last group can be short
+            int hn[4];  // horizontal pass of source row sy for the lane's four columns, already shifted (r >> 4)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t taps = __builtin_amdgcn_perm(t[j].hi, t[j].lo, sel[k]);
+                // t0 * a0 + t1 * a1 in one instruction (v_dot2_i32_i16: the exact 32-bit sum of the two 16-bit products)
+                hn[k] = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, taps), __builtin_bit_cast(short2v, al[k]), 0, false) >> 4;
+            }
+            // scale > 1: the rows' sy1 increase strictly, so a source row is the lower row of one destination row at most.  (An `if`, not a loop:
+            // behind a loop of stores the compiler no longer counts the requests in flight and waits for all of them.)
+            if (r < nrows && __builtin_amdgcn_readlane(sy1_lane, r) == sy) {
+                const bool folded = __builtin_amdgcn_readlane(sy0_lane, r) == sy;  // sy0 == sy1: the clamp at the last source row
+                const uint32_t beta = (uint32_t)__builtin_amdgcn_readlane((int)beta_lane, r);
+                const int b0 = (short)(beta & 0xffffu), b1 = (short)(beta >> 16);
+                uint32_t packed = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int h0 = folded ? hn[k] : hp[k];
+                    const int v = (((b0 * h0) >> 16) + ((b1 * hn[k]) >> 16) + 2) >> 2;
+                    packed |= (uint32_t)(v & 0xff) << (8 * k);
+                }
+                uint8_t* Drow = D + (size_t)(dy_begin + r) * dst_pitch + dx0;
+                if (dx0 + 3 < dw) {
+                    *reinterpret_cast<uint32_t*>(Drow) = packed;  // dst_pitch and dx0 are multiples of 4
+                } else {
+                    for (int k = 0; k < 4 && dx0 + k < dw; ++k) Drow[k] = (uint8_t)(packed >> (8 * k));
+                }
+                ++r;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) hp[k] = hn[k];
+        }
+    };
+    // Two buffers in turn.  A group is consumed either with the next one already requested or as the unit's last: the two cases are separate
+    // code, so that the wait in front of a group counts the requests behind it (after a join of "requested" and "not requested" the compiler
+    // waits for everything in flight).
+    Taps ta[NS], tb[NS];
+    request(ta, sy_first);
+    for (int base = sy_first;; base += 2 * NS) {
+        if (base + NS > sy_last) { consume(ta, base, std::true_type()); break; }
+        request(tb, base + NS);
+        consume(ta, base, std::false_type());
+        if (base + 2 * NS > sy_last) { consume(tb, base + NS, std::true_type()); break; }
+        request(ta, base + 2 * NS);
+        consume(tb, base + NS, std::false_type());
+    }
 }
-
 
 __global__ __launch_bounds__(256) void k_resize_strips(const uint8_t* __restrict__ src, int src_pitch, size_t src_img_stride, int sw, int sh,
                                                        uint8_t* __restrict__ dst, int dst_pitch, size_t dst_img_stride, int dw, int dh,
@@ -194,10 +250,9 @@ __global__ __launch_bounds__(256) void k_resize_strips(const uint8_t* __restrict
     const int logical = ((int)blockIdx.x & 7) * per_xcd + u;
     if (u >= per_xcd || logical >= n_units) return;
     const int img = logical / (gx * gy), rem = logical - img * (gx * gy), by = rem / gx, bx = rem - by * gx;
-    const int dx0 = (bx * 64 + (int)(threadIdx.x & 63)) * 4;
-    if (dx0 >= dw) return;
+    const int dx0 = (bx * 64 + (int)(threadIdx.x & 63)) * 4;  // (gx covers dw: every wavefront has a lane with dx0 < dw)
     const uint8_t* S = src + (size_t)img * src_img_stride;
-    uint8_t* D = dst + (size_t)img * dst_img_stride + dx0;
+    uint8_t* D = dst + (size_t)img * dst_img_stride;
     const int dy_begin = by * rows_per_wave, dy_end = min(dy_begin + rows_per_wave, dh);
     resize_strip_unit(S, src_pitch, sw, sh, D, dst_pitch, dw, xofs, ialpha, yofs, ibeta, dx0, dy_begin, dy_end);
 }
@@ -207,21 +262,25 @@ __global__ __launch_bounds__(256) void k_resize_strips(const uint8_t* __restrict
 // From level `l0` on a level is small enough for one workgroup per image to make it whole: the workgroup walks levels l0 .. n_levels - 1,
 // its wavefronts take the strip units of a level in turn, a barrier between two levels (the level just written is read back by the same
 // workgroup: through L2, no other workgroup touches this image).  Same arithmetic as k_resize_strips, unit by unit.
+// Rows per unit are chosen per level: as many rounds of the workgroup's wavefronts as kResizeRows-row units would take, and the level's rows
+// dealt evenly over the units those rounds have room for -- no wavefront sits out a level (1242 x 375, level 7: 14 units of 16 rows for 16
+// wavefronts -> 16 units of 14 rows) and the last round is as full as the others (level 3: 42 units of 16 rows -> 48 of 14).
 struct ResizeTables { const int* xofs[kMaxLevels]; const short* ialpha[kMaxLevels]; const int* yofs[kMaxLevels]; const short* ibeta[kMaxLevels]; };
-constexpr int kResizeTailThreads = 1024;
-__global__ __launch_bounds__(kResizeTailThreads) void k_resize_tail(LevelTable lv, ResizeTables tb, int l0, int n_levels) {
-    const int img = blockIdx.x, wave = wave_in_block(), lane = threadIdx.x & 63;
+constexpr int kResizeTailMaxThreads = 1024, kResizeTailThreads = 512;
+__global__ __launch_bounds__(kResizeTailMaxThreads) void k_resize_tail(LevelTable lv, ResizeTables tb, int l0, int n_levels) {
+    const int img = blockIdx.x, wave = wave_in_block(), lane = threadIdx.x & 63, n_waves = (int)blockDim.x >> 6;
     for (int l = l0; l < n_levels; ++l) {
         const LevelDesc S = lv.lv[l - 1], D = lv.lv[l];
         const uint8_t* src = S.img + (size_t)img * S.img_stride;
         uint8_t* dst = const_cast<uint8_t*>(D.img) + (size_t)img * D.img_stride;
-        const int gx = (D.w + 255) / 256, gy = (D.h + kResizeRows - 1) / kResizeRows;
-        for (int u = wave; u < gx * gy; u += kResizeTailThreads / 64) {
+        const int gx = (D.w + 255) / 256;
+        const int rounds = (gx * ((D.h + kResizeRows - 1) / kResizeRows) + n_waves - 1) / n_waves;
+        const int strips = max(rounds * n_waves / gx, 1);  // row strips the rounds have room for
+        const int rows = min((D.h + strips - 1) / strips, kResizeMaxUnitRows), gy = (D.h + rows - 1) / rows;
+        for (int u = wave; u < gx * gy; u += n_waves) {
             const int by = u / gx, bx = u - by * gx;
-            const int dx0 = (bx * 64 + lane) * 4;
-            if (dx0 >= D.w) continue;
-            resize_strip_unit(src, S.pitch, S.w, S.h, dst + dx0, D.pitch, D.w, tb.xofs[l], tb.ialpha[l], tb.yofs[l], tb.ibeta[l], dx0, by * kResizeRows,
-                              min((by + 1) * kResizeRows, D.h));
+            resize_strip_unit(src, S.pitch, S.w, S.h, dst, D.pitch, D.w, tb.xofs[l], tb.ialpha[l], tb.yofs[l], tb.ibeta[l], (bx * 64 + lane) * 4, by * rows,
+                              min((by + 1) * rows, D.h));
         }
         __syncthreads();  // level l is complete (and visible to this workgroup) before level l + 1 reads it
     }
@@ -871,10 +930,12 @@ __global__ __launch_bounds__(256) void k_orient_describe(LevelTable raw, LevelTa
 }
 
 // ---- launch wrappers (host side of this translation unit) ----------------------------------------------
+// what resize_strip_unit assumes of a level pair (see there)
+bool resize_strips_cover(const LevelDesc& src, const LevelDesc& dst) { return src.w >= 8 && src.w <= 2 * dst.w && src.h > dst.h; }
 void launch_resize(const LevelDesc& src, const LevelDesc& dst, const int* xofs, const short* ialpha, const int* yofs,
                    const short* ibeta, int nimg, hipStream_t st) {
     static const bool pixel_form = getenv("TC2LI_RESIZE_PIXELS") && atoi(getenv("TC2LI_RESIZE_PIXELS")) != 0;  // the round-1 kernel: four pixels per thread
-    if (pixel_form) {
+    if (pixel_form || !resize_strips_cover(src, dst)) {
         const int gx = (dst.w + 255) / 256, gy = (dst.h + 3) / 4;
         TC2LI_LAUNCH(k_resize_linear, dim3(((gx * gy * nimg + 7) / 8) * 8), dim3(256), 0, st, src.img, src.pitch, src.img_stride, src.w, src.h,
                      const_cast<uint8_t*>(dst.img), dst.pitch, dst.img_stride, dst.w, dst.h, xofs, ialpha, yofs, ibeta, gx, gy, nimg);
@@ -895,7 +956,11 @@ void launch_resize_tail(const LevelTable& lv, const int* const* xofs, const shor
     if (nimg <= 0 || l0 >= n_levels) return;
     ResizeTables tb{};
     for (int l = l0; l < n_levels; ++l) { tb.xofs[l] = xofs[l]; tb.ialpha[l] = ialpha[l]; tb.yofs[l] = yofs[l]; tb.ibeta[l] = ibeta[l]; }
-    TC2LI_LAUNCH(k_resize_tail, dim3(nimg), dim3(kResizeTailThreads), 0, st, lv, tb, l0, n_levels);
+    // threads per image: alone 1024 are 5 % faster (362 / 382 us), in the loop 512 are (a smaller workgroup finds its wavefront slots sooner:
+    // 817 / 947 us per launch); TC2LI_RESIZE_TAIL_THREADS for A/B measurements
+    static const int threads_env = getenv("TC2LI_RESIZE_TAIL_THREADS") ? atoi(getenv("TC2LI_RESIZE_TAIL_THREADS")) : 0;
+    const int threads = threads_env >= 64 && threads_env <= kResizeTailMaxThreads ? threads_env & ~63 : kResizeTailThreads;
+    TC2LI_LAUNCH(k_resize_tail, dim3(nimg), dim3(threads), 0, st, lv, tb, l0, n_levels);
 }
 
 void launch_fast(const LevelTable& levels, const FastCell* cells, int ncells, int ini_th, int min_th, uint32_t* slab,
