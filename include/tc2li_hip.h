@@ -1545,6 +1545,125 @@ int tc2li_map_point_culling_batch(const uint8_t* bad, const int32_t* n_found, co
 int tc2li_host_map_point_culling_batch(const uint8_t* bad, const int32_t* n_found, const int32_t* n_visible, const int64_t* first_kf_id,
                                        const int32_t* n_obs, const int64_t* current_kf_id, int n_points, int th_obs, uint8_t* action);
 
+/* ---- tracking: stereo map points and the keyframe decision (SF/src/Tracking.cc:2942-3076 NeedNewKeyFrame, :3078-3212 CreateNewKeyFrame,
+ * :2676-2734 UpdateLastFrame, :2477-2495 StereoInitialization) ----------------------------------------------------------------------------
+ * The step between TrackLocalMap and local mapping: whether the frame becomes a keyframe, and which of its stereo keypoints become new map
+ * points, with their world positions.  The library returns the decision, the keypoints in creation order and their positions; the caller
+ * makes the objects (INTEGRATION.md "NeedNewKeyFrame / CreateNewKeyFrame / UpdateLastFrame / StereoInitialization").  Rig: pinhole stereo,
+ * Nleft == -1, mpCamera2 == nullptr; the fisheye / two-camera branches (:2496-2517, :3171-3184, :3019) are not covered. */
+enum tc2li_stereo_points_mode {
+    TC2LI_STEREO_POINTS_CLOSEST = 0,   /* CreateNewKeyFrame (:3132-3203) and UpdateLastFrame (:2676-2734): the depth-sorted walk */
+    TC2LI_STEREO_POINTS_ALL = 1        /* StereoInitialization (:2477-2495): every keypoint with depth, if the frame has more than 500 */
+};
+#define TC2LI_STEREO_POINTS_MAX_KEYPOINTS 4096
+/* One frame.  All pointers are host memory, the arrays are copied by the call.
+ *   n keypoints (Frame::N; more than 4096: TC2LI_ERR_CAPACITY);  depth [n] mvDepth;  keys [n] mvKeysUn (only x, y are read);
+ *   held [n] as in tc2li_track_local_map_batch: 0 = mvpMapPoints[i] is NULL, 1 = a point with Observations() > 0, 2 = a point without
+ *   observations;  outlier [n] mvbOutlier (read only by the counts of tc2li_new_keyframe_batch; may be NULL for tc2li_stereo_points_batch);
+ *   Rwc [9] mRwc row-major and Ow [3] mOw as Frame::UpdatePoseMatrices left them (SF/src/Frame.cc:505-506);  th_depth mThDepth;
+ *   max_point 100 at both sites (:2731, :3128);  mode tc2li_stereo_points_mode.
+ * Out: created_keypoint [n] and x3D [n][3] (room for n; the first n_created entries are written, in creation order), counts [3] =
+ * n_created, n_visited (nPoints when the walk ended; in mode ALL = n_created), n_with_depth (keypoints with depth > 0). */
+typedef struct tc2li_stereo_points_frame {
+    const float* depth;
+    const tc2li_keypoint* keys;
+    const uint8_t* held;
+    const uint8_t* outlier;
+    int32_t* created_keypoint;
+    float* x3D;
+    int32_t* counts;
+    float Rwc[9];
+    float Ow[3];
+    float th_depth;
+    int32_t n, max_point, mode;
+} tc2li_stereo_points_frame;
+/* The stereo map points of n_frames frames (one per sequence) at once on the device.  unproject4 = {cx, cy, invfx, invfy} as floats, as
+ * Frame holds them (invfx = 1.0f / fx, SF/src/Frame.cc:188).
+ *   CLOSEST: the pairs (depth[i], i) with depth[i] > 0 (NaN fails the test, +inf passes) in the order of std::sort on pair<float, int>:
+ *   by depth, ties by index -- a total order, the result is unique.  The walk visits them in that order, nPoints counts every entry, an
+ *   entry with held != 1 is created (:3156-3162, :2704-2707), and the walk ends AFTER an entry with depth > th_depth && nPoints >
+ *   max_point (:3199, :2731).  So with c entries of depth <= th_depth out of M it takes min(M, max(c, max_point) + 1) entries: one more
+ *   than max_point, or all close ones and one far one.  That is the reference's behaviour.
+ *   ALL: every i with depth[i] > 0 in index order, held is ignored; nothing when n <= 500 (:2433).
+ *   Position of keypoint i (Frame::UnprojectStereo, SF/src/Frame.cc:1037-1050), float, every product and sum rounded (no contraction):
+ *     x = ((u - cx) * z) * invfx;  y = ((v - cy) * z) * invfy;  x3D[r] = ((R[r][0] * x + R[r][1] * y) + R[r][2] * z) + Ow[r]
+ *   Eigen leaves the order of the three-term sum to its build: THIS CHOICE DEFINES PARITY.
+ * One workgroup per frame: the keys (depth bits << 32 | index; positive floats order as their bit patterns) are compacted into the LDS,
+ * sorted there and walked.  One upload, one launch, one download; the results are in host memory when the call returns (stream: NULL =
+ * the calling thread's private stream).  Before any device work: TC2LI_ERR_CAPACITY for n > 4096; TC2LI_ERR_INVALID for negative sizes,
+ * NULL required arrays, held outside {0, 1, 2}, an unknown mode, max_point < 0.  A refused call writes nothing.  Returns n_frames. */
+int tc2li_stereo_points_batch(const tc2li_stereo_points_frame* frames, int n_frames, const float unproject4[4], void* stream);
+/* The same contract as plain sequential C++ (the reference's loops with std::sort, one frame per worker thread); needs no device. */
+int tc2li_host_stereo_points_batch(const tc2li_stereo_points_frame* frames, int n_frames, const float unproject4[4]);
+
+enum tc2li_new_keyframe_condition {    /* tc2li_keyframe_verdict.conditions */
+    TC2LI_NEWKF_C1A = 1, TC2LI_NEWKF_C1B = 2, TC2LI_NEWKF_C1C = 4, TC2LI_NEWKF_C2 = 8, TC2LI_NEWKF_C3 = 16
+};
+enum tc2li_new_keyframe_exit {         /* tc2li_keyframe_verdict.exit_rule: the rule that answered */
+    TC2LI_NEWKF_EXIT_IMU_NOT_INITIALIZED = 1,   /* :2944-2950 */
+    TC2LI_NEWKF_EXIT_ONLY_TRACKING = 2,         /* :2952 */
+    TC2LI_NEWKF_EXIT_MAPPER_STOPPED = 3,        /* :2956 */
+    TC2LI_NEWKF_EXIT_AFTER_RELOC = 4,           /* :2967 */
+    TC2LI_NEWKF_EXIT_CONDITIONS = 5,            /* :3049 was false */
+    TC2LI_NEWKF_EXIT_MAPPER_ACCEPTS = 6,        /* :3053 */
+    TC2LI_NEWKF_EXIT_MAPPER_BUSY = 7            /* :3059-3065: InterruptBA, then the queue length decides */
+};
+/* What Tracking::NeedNewKeyFrame reads besides the frame (:2942-3076).
+ *   inertial mSensor == IMU_STEREO_LIDAR;  imu_initialized GetCurrentMap()->isImuInitialized();  only_tracking mbOnlyTracking;
+ *   mapper_stopped isStopped() || stopRequested();  mapper_idle AcceptKeyFrames();  mapper_initializing IsInitializing();
+ *   keyframes_in_queue KeyframesInQueue();  has_last_kf mpLastKeyFrame != NULL (0 with inertial && !imu_initialized is refused: the
+ *   reference would dereference NULL at :2946);  time_frame / time_last_kf the two mTimeStamp;
+ *   create_blocked: the gates of CreateNewKeyFrame (:3080-3084), IsInitializing() && !isImuInitialized() or SetNotStop(true) failing
+ *     because local mapping has stopped, AS THEY ARE WHEN THE CALL IS MADE -- the reference evaluates SetNotStop(true) live, after the
+ *     decision; this snapshot is a deviation (the caller still makes the SetNotStop calls on its own objects);
+ *   frame_id mCurrentFrame.mnId (unsigned long);  last_reloc_frame_id mnLastRelocFrameId, last_keyframe_id mnLastKeyFrameId: unsigned int
+ *     in the reference (SF/include/Tracking.h:335-336), so last + max_frames / + min_frames at :2967, :3023, :3025 is an unsigned 32-bit
+ *     sum that is then compared with the 64-bit frame_id; the library does the same, and a value above 2^32 - 1 is refused;
+ *   max_frames, min_frames mMaxFrames, mMinFrames;  n_kfs KeyFramesInMap();  matches_inliers mnMatchesInliers;
+ *   n_ref_matches mpReferenceKF->TrackedMapPoints(n_kfs <= 2 ? 2 : 3) -- or ref_nobs [n_ref] != NULL: Observations() of every non-NULL,
+ *     non-bad map point of the reference keyframe and -1 for the other slots, and the library counts the entries >= that minimum itself
+ *     (SF/src/KeyFrame.cc:352-377, Tracking.cc:2973-2976; n_ref_matches is then not read). */
+typedef struct tc2li_keyframe_decision {
+    const int32_t* ref_nobs;
+    uint64_t frame_id, last_reloc_frame_id, last_keyframe_id;
+    double time_frame, time_last_kf;
+    int32_t n_ref, max_frames, min_frames, n_kfs, matches_inliers, n_ref_matches, keyframes_in_queue;
+    uint8_t inertial, imu_initialized, only_tracking, mapper_stopped, mapper_idle, mapper_initializing, create_blocked, has_last_kf;
+    int32_t pad_;
+} tc2li_keyframe_decision;
+typedef struct tc2li_keyframe_verdict {
+    int32_t need;                      /* NeedNewKeyFrame()'s return value */
+    int32_t interrupt_ba;              /* 1: the caller calls mpLocalMapper->InterruptBA() (:3059) */
+    int32_t conditions;                /* tc2li_new_keyframe_condition mask; 0 where exit_rule < 5 */
+    int32_t exit_rule;                 /* tc2li_new_keyframe_exit */
+    int32_t n_tracked_close, n_non_tracked_close;   /* :2982-2998; computed whichever rule answered */
+    int32_t n_ref_matches;             /* the value the rules used */
+    int32_t pad_;
+} tc2li_keyframe_verdict;
+/* Tracking::NeedNewKeyFrame for n_frames frames at once and, where it says yes and create_blocked is 0, the CLOSEST creation of
+ * tc2li_stereo_points_batch for the new keyframe (frames[f].mode must be TC2LI_STEREO_POINTS_CLOSEST, outlier must not be NULL); elsewhere
+ * counts = {0, 0, n_with_depth}.  The rules in the reference's order:
+ *   1. inertial && !imu_initialized: need = time_frame - time_last_kf >= 0.25 and nothing else is evaluated (:2944-2950)
+ *   2. only_tracking: no (:2952)      3. mapper_stopped: no (:2956)
+ *   4. frame_id < last_reloc_frame_id + max_frames && n_kfs > max_frames: no (:2967)
+ *   5. over the keypoints with depth > 0 && depth < th_depth (:2990; depth == th_depth is not close here, though the walk above treats it
+ *      as close): tracked iff held != 0 && !outlier.  close = nTrackedClose < 100 && nNonTrackedClose > 70;  thRefRatio = n_kfs < 2 ? 0.4f
+ *      : 0.75f;  c1a = frame_id >= last_keyframe_id + max_frames;  c1b = frame_id >= last_keyframe_id + min_frames && mapper_idle;
+ *      c1c = !inertial && ((double)inliers < (double)ref * 0.25 || close);  c2 = ((float)inliers < (float)ref * thRefRatio || close) &&
+ *      inliers > 15 -- the int-by-double and int-by-float products of :3027, :3029 as C++ evaluates them;  c3 = has_last_kf && inertial &&
+ *      time_frame - time_last_kf >= 0.5;  c4 is false (:3044)
+ *   6. if ((c1a || c1b || c1c) && c2) || c3: yes if mapper_idle || mapper_initializing; otherwise interrupt_ba = 1 and the answer is
+ *      keyframes_in_queue < 3.  Else no.
+ * The counts, the decision, the sort and the walk of a frame are one workgroup's work in one launch; with the upload, the download and the
+ * wait that is the whole step of a batch of sequences.  Refusals as tc2li_stereo_points_batch, and TC2LI_ERR_INVALID for outlier == NULL,
+ * a mode other than CLOSEST, n_ref < 0, has_last_kf == 0 with inertial && !imu_initialized, last ids above 2^32 - 1.  A refused call
+ * writes nothing.  Returns n_frames. */
+int tc2li_new_keyframe_batch(const tc2li_stereo_points_frame* frames, const tc2li_keyframe_decision* decisions, tc2li_keyframe_verdict* verdicts,
+                             int n_frames, const float unproject4[4], void* stream);
+/* The same contract as plain sequential C++; needs no device. */
+int tc2li_host_new_keyframe_batch(const tc2li_stereo_points_frame* frames, const tc2li_keyframe_decision* decisions,
+                                  tc2li_keyframe_verdict* verdicts, int n_frames, const float unproject4[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,4 +50,6 @@ from .capi import (  # noqa: F401
     KeyframeStore,
     create_new_map_points_batch,
     fuse_search_batch,
+    stereo_points_batch,
+    new_keyframe_batch,
 )

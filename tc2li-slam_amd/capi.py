@@ -2634,3 +2634,123 @@ def map_point_culling_batch(points, th_obs=3, host=False, stream=0):
         f.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _check(f(*(args + [C.c_void_p(stream)])))
     return action
+
+
+class StereoPointsFrame(C.Structure):
+    """tc2li_stereo_points_frame"""
+    _fields_ = [(k, C.c_void_p) for k in ("depth", "keys", "held", "outlier", "created_keypoint", "x3D", "counts")] \
+        + [("Rwc", C.c_float * 9), ("Ow", C.c_float * 3), ("th_depth", C.c_float), ("n", C.c_int32), ("max_point", C.c_int32), ("mode", C.c_int32)]
+
+
+class KeyframeDecision(C.Structure):
+    """tc2li_keyframe_decision"""
+    _fields_ = [("ref_nobs", C.c_void_p), ("frame_id", C.c_uint64), ("last_reloc_frame_id", C.c_uint64), ("last_keyframe_id", C.c_uint64),
+                ("time_frame", C.c_double), ("time_last_kf", C.c_double)] \
+        + [(k, C.c_int32) for k in ("n_ref", "max_frames", "min_frames", "n_kfs", "matches_inliers", "n_ref_matches", "keyframes_in_queue")] \
+        + [(k, C.c_uint8) for k in ("inertial", "imu_initialized", "only_tracking", "mapper_stopped", "mapper_idle", "mapper_initializing",
+                                    "create_blocked", "has_last_kf")] + [("pad_", C.c_int32)]
+
+
+class KeyframeVerdict(C.Structure):
+    """tc2li_keyframe_verdict"""
+    _fields_ = [(k, C.c_int32) for k in ("need", "interrupt_ba", "conditions", "exit_rule", "n_tracked_close", "n_non_tracked_close",
+                                         "n_ref_matches", "pad_")]
+
+
+STEREO_POINTS_CLOSEST, STEREO_POINTS_ALL = 0, 1
+NEWKF_C1A, NEWKF_C1B, NEWKF_C1C, NEWKF_C2, NEWKF_C3 = 1, 2, 4, 8, 16
+(NEWKF_EXIT_IMU_NOT_INITIALIZED, NEWKF_EXIT_ONLY_TRACKING, NEWKF_EXIT_MAPPER_STOPPED, NEWKF_EXIT_AFTER_RELOC, NEWKF_EXIT_CONDITIONS,
+ NEWKF_EXIT_MAPPER_ACCEPTS, NEWKF_EXIT_MAPPER_BUSY) = range(1, 8)
+_DECISION_SCALARS = tuple(k for k, _ in KeyframeDecision._fields_ if k not in ("ref_nobs", "n_ref", "pad_"))
+
+
+def pack_stereo_points_frames(frames):
+    """The tc2li_stereo_points_frame array of a batch with its output arrays -> (array, outputs per frame, what must stay alive).  A frame
+    is a dict: depth [n], keys [n] (KEYPOINT_DTYPE, or an [n, 2] array of x, y), held [n], optionally outlier [n], Rwc [3, 3] or [9], Ow [3],
+    th_depth, and optionally max_point (100) and mode (STEREO_POINTS_CLOSEST)."""
+    arr, outs, keep = (StereoPointsFrame * max(len(frames), 1))(), [], []
+    for i, f in enumerate(frames):
+        depth = np.ascontiguousarray(f["depth"], np.float32).reshape(-1)
+        n = len(depth)
+        keys = f["keys"]
+        if getattr(keys, "dtype", None) != KEYPOINT_DTYPE:
+            xy = np.asarray(keys, np.float32).reshape(n, 2)
+            keys = np.zeros(n, KEYPOINT_DTYPE)
+            keys["x"], keys["y"] = xy[:, 0], xy[:, 1]
+        keys = np.ascontiguousarray(keys)
+        held = np.ascontiguousarray(f["held"], np.uint8).reshape(-1)
+        outlier = None if f.get("outlier") is None else np.ascontiguousarray(f["outlier"], np.uint8).reshape(-1)
+        if len(keys) != n or len(held) != n or (outlier is not None and len(outlier) != n):
+            raise ValueError("frame %d: keys, held or outlier do not have depth's %d rows" % (i, n))
+        o = dict(created_keypoint=np.full(n, -1, np.int32), x3D=np.zeros((n, 3), np.float32), counts=np.zeros(3, np.int32))
+        a = arr[i]
+        a.depth, a.keys, a.held = depth.ctypes.data, keys.ctypes.data, held.ctypes.data
+        a.outlier = None if outlier is None else outlier.ctypes.data
+        a.created_keypoint, a.x3D, a.counts = o["created_keypoint"].ctypes.data, o["x3D"].ctypes.data, o["counts"].ctypes.data
+        a.Rwc = (C.c_float * 9)(*np.asarray(f["Rwc"], np.float32).reshape(9))
+        a.Ow = (C.c_float * 3)(*np.asarray(f["Ow"], np.float32).reshape(3))
+        a.th_depth, a.n, a.max_point, a.mode = float(np.float32(f["th_depth"])), n, int(f.get("max_point", 100)), int(f.get("mode", STEREO_POINTS_CLOSEST))
+        keep.append((depth, keys, held, outlier))
+        outs.append(o)
+    return arr, outs, keep
+
+
+def _stereo_points_results(outs):
+    res = []
+    for o in outs:
+        k = int(o["counts"][0])
+        res.append(dict(created_keypoint=o["created_keypoint"][:k].copy(), x3D=o["x3D"][:k].copy(), n_created=k, n_visited=int(o["counts"][1]),
+                        n_with_depth=int(o["counts"][2])))
+    return res
+
+
+def stereo_points_batch(frames, unproject4, host=False, stream=0):
+    """The stereo map points of ``Tracking::CreateNewKeyFrame`` / ``UpdateLastFrame`` (mode STEREO_POINTS_CLOSEST) or
+    ``StereoInitialization`` (STEREO_POINTS_ALL), one frame per dict (pack_stereo_points_frames); unproject4 = (cx, cy, invfx, invfy) ->
+    one dict per frame: created_keypoint [n_created], x3D [n_created, 3] in creation order, n_created, n_visited, n_with_depth.
+    host=True runs the reference's loops on the CPU."""
+    arr, outs, keep = pack_stereo_points_frames(frames)
+    u = np.ascontiguousarray(unproject4, np.float32).reshape(4)
+    if host:
+        f = lib().tc2li_host_stereo_points_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _check(f(C.addressof(arr), len(frames), u.ctypes.data))
+    else:
+        f = lib().tc2li_stereo_points_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _check(f(C.addressof(arr), len(frames), u.ctypes.data, C.c_void_p(stream)))
+    del keep
+    return _stereo_points_results(outs)
+
+
+def new_keyframe_batch(frames, decisions, unproject4, host=False, stream=0):
+    """``Tracking::NeedNewKeyFrame`` per frame and, where it says yes and create_blocked is 0, the new keyframe's stereo points.  frames as
+    for stereo_points_batch (outlier required); decisions: dicts with the scalars of tc2li_keyframe_decision (default 0) and optionally
+    ref_nobs -> one dict per frame: the fields of stereo_points_batch plus need, interrupt_ba, conditions, exit_rule, n_tracked_close,
+    n_non_tracked_close, n_ref_matches."""
+    if len(frames) != len(decisions):
+        raise ValueError("%d frames, %d decisions" % (len(frames), len(decisions)))
+    arr, outs, keep = pack_stereo_points_frames(frames)
+    dec, ver = (KeyframeDecision * max(len(frames), 1))(), (KeyframeVerdict * max(len(frames), 1))()
+    for i, d in enumerate(decisions):
+        for k in _DECISION_SCALARS:
+            v = d.get(k, 0)
+            setattr(dec[i], k, float(v) if k.startswith("time_") else int(v))
+        if d.get("ref_nobs") is not None:
+            r = np.ascontiguousarray(d["ref_nobs"], np.int32).reshape(-1)
+            keep.append(r)
+            dec[i].ref_nobs, dec[i].n_ref = r.ctypes.data, len(r)
+    u = np.ascontiguousarray(unproject4, np.float32).reshape(4)
+    if host:
+        f = lib().tc2li_host_new_keyframe_batch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _check(f(C.addressof(arr), C.addressof(dec), C.addressof(ver), len(frames), u.ctypes.data))
+    else:
+        f = lib().tc2li_new_keyframe_batch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _check(f(C.addressof(arr), C.addressof(dec), C.addressof(ver), len(frames), u.ctypes.data, C.c_void_p(stream)))
+    del keep
+    res = _stereo_points_results(outs)
+    for r, v in zip(res, ver):
+        r.update({k: int(getattr(v, k)) for k, _ in KeyframeVerdict._fields_ if k != "pad_"})
+    return res
