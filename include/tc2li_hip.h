@@ -1545,6 +1545,117 @@ int tc2li_map_point_culling_batch(const uint8_t* bad, const int32_t* n_found, co
 int tc2li_host_map_point_culling_batch(const uint8_t* bad, const int32_t* n_found, const int32_t* n_visible, const int64_t* first_kf_id,
                                        const int32_t* n_obs, const int64_t* current_kf_id, int n_points, int th_obs, uint8_t* action);
 
+/* ---- local mapping: covisibility graph (SF/src/KeyFrame.cc:391-486 UpdateConnections, :201-214 AddConnection, :216-238
+ * UpdateBestCovisibles) ---------------------------------------------------------------------------------------------------------------------
+ * The covisibility update that LocalMapping makes for every new keyframe (SF/src/LocalMapping.cc:348 in ProcessNewKeyFrame, :836 at the
+ * end of SearchInNeighbors) on the flat graph: slots of the keyframe, observations per point, weight rows per keyframe.  The library
+ * returns the new weight map and ordered lists of the keyframe and of every neighbour whose lists change; the caller writes them into its
+ * objects (INTEGRATION.md "UpdateConnections / UpdateBestCovisibles").  Row order stands in for the address order of the reference's
+ * std::map<KeyFrame*, ...> containers, and where the reference compares mnId (:418) row equality is used: one row per keyframe. */
+enum tc2li_connections_status {
+    TC2LI_CONNECTIONS_UNCHANGED = 0,   /* KFcounter was empty: the reference returns at :426-427, nothing is to be applied */
+    TC2LI_CONNECTIONS_UPDATED = 1
+};
+/* the entries of tc2li_connections_problem.counts */
+enum tc2li_connections_count {
+    TC2LI_CONNECTIONS_STATUS = 0,      /* tc2li_connections_status */
+    TC2LI_CONNECTIONS_N_COUNTER = 1,   /* entries of counter_kf / counter_weight */
+    TC2LI_CONNECTIONS_N_ORDERED = 2,   /* entries of ordered_kf / ordered_weight, and of touched_kf / touched_changed */
+    TC2LI_CONNECTIONS_N_CHANGED = 3,   /* touched keyframes with changed = 1: rows of changed_offsets */
+    TC2LI_CONNECTIONS_N_CHANGED_ENTRIES = 4,   /* entries of changed_kf / changed_weight = changed_offsets[n_changed] */
+    TC2LI_CONNECTIONS_PARENT = 5,      /* the new mpParent, or -1: mpParent stays */
+    TC2LI_CONNECTIONS_COUNTS = 8       /* ints in the block (the last two are 0) */
+};
+#define TC2LI_CONNECTIONS_TH 15        /* th of :433 */
+/* One call of KeyFrame::UpdateConnections.  All pointers are host memory, the arrays are copied by the call; indices are rows of the
+ * problem's own tables.  Problems of one batch are independent: two problems over the same graph both see the input state.
+ *   keyframes (n_keyframes rows: the current keyframe, every keyframe that observes one of its points, and whatever their rows name):
+ *     kf_flags  bit 0 isBad(), bit 1 GetMap() != mpMap of the current keyframe
+ *     conn_offsets [n_keyframes + 1], conn_kf, conn_weight: mConnectedKeyFrameWeights per keyframe as a CSR.  A row ascends strictly by
+ *     keyframe row (map order; at most one entry per keyframe).  The row of a keyframe that the call cannot touch may be left empty;
+ *     every keyframe that observes a point of the current keyframe needs its row.  The current keyframe's own row is not read.
+ *   current: the row of the keyframe the call is made on;  slot_point [n_slots]: its mvpMapPoints, -1 = NULL
+ *   points (n_points rows): point_bad isBad(); CSR obs_offsets [n_points + 1], obs_kf: the keyframes of GetObservations(), in any order
+ *   scalars: first_connection mbFirstConnection; is_init_kf mnId == mpMap->GetInitKFid()
+ * Out (capacities are the caller's; an array whose capacity is 0 may be NULL):
+ *   counts [TC2LI_CONNECTIONS_COUNTS]: always written.
+ *   counter_kf / counter_weight [counter_capacity]: KFcounter, ascending by row = the new mConnectedKeyFrameWeights (:473)
+ *   ordered_kf / ordered_weight [ordered_capacity]: the new mvpOrderedConnectedKeyFrames / mvOrderedWeights (:474-475)
+ *   touched_kf [ordered_capacity]: the keyframes that got AddConnection(current, weight) (:451, :458), ascending by row -- the same set as
+ *     ordered_kf;  touched_changed [ordered_capacity]: 1 if AddConnection went on to UpdateBestCovisibles, 0 if it returned at :210
+ *   changed_offsets [ordered_capacity + 1], changed_kf / changed_weight [changed_capacity]: a CSR over the touched keyframes with
+ *     changed = 1, in touched order: their new mvpOrderedConnectedKeyFrames / mvOrderedWeights.  Their map entry is (current, weight). */
+typedef struct tc2li_connections_problem {
+    const uint8_t* kf_flags;
+    const int32_t* conn_offsets;
+    const int32_t* conn_kf;
+    const int32_t* conn_weight;
+    const int32_t* slot_point;
+    const uint8_t* point_bad;
+    const int32_t* obs_offsets;
+    const int32_t* obs_kf;
+    int32_t* counts;
+    int32_t* counter_kf;
+    int32_t* counter_weight;
+    int32_t* ordered_kf;
+    int32_t* ordered_weight;
+    int32_t* touched_kf;
+    uint8_t* touched_changed;
+    int32_t* changed_offsets;
+    int32_t* changed_kf;
+    int32_t* changed_weight;
+    int32_t n_keyframes, n_slots, n_points, current;
+    int32_t counter_capacity, ordered_capacity, changed_capacity;
+    uint8_t first_connection, is_init_kf;
+    uint8_t pad_[2];
+} tc2li_connections_problem;
+/* KeyFrame::UpdateConnections (:391-486) for n_problems independent calls at once on the device, with the AddConnection (:201-214) and
+ * UpdateBestCovisibles (:216-238) it triggers in the connected keyframes.  Line for line:
+ *   votes (:404-423): for every slot whose point is not NULL (:408) and not bad (:411), every observation of the point adds one to its
+ *   keyframe's counter unless that keyframe is the current one (row equality for :418's mnId), is bad or belongs to another map (:418).
+ *   The loop runs over slots: a point held by two slots votes twice.
+ *   empty counter (:426-427): status TC2LI_CONNECTIONS_UNCHANGED, all sizes 0, parent -1; NO OTHER OUTPUT IS WRITTEN.
+ *   threshold (:431-459): every counted keyframe with at least th = 15 votes enters vPairs and gets AddConnection(current, votes); if none
+ *   does, the one with the most votes, the lowest row among equals (`>` at :443 in map order), enters alone (:455-459).
+ *   own lists (:461-475): vPairs sorted ascending as (weight, keyframe) and pushed to the front: weight descending, equal weights by row
+ *   DESCENDING.  No isBad() test here beyond the one of the vote.  The weight map becomes the WHOLE counter, entries below 15 included
+ *   (:473).
+ *   spanning tree (:478-483): parent = ordered_kf[0] if first_connection && !is_init_kf, else -1 = unchanged.  The caller then does
+ *   mpParent->AddChild(this) and clears mbFirstConnection.
+ *   every touched keyframe k (:201-214): if k's row holds (current, the same weight), AddConnection returns before UpdateBestCovisibles
+ *   (:209-210): changed = 0 and no list is given -- k's stored lists may be stale and the reference does not refresh them here.  Otherwise
+ *   the entry is inserted or overwritten and k's new lists are UpdateBestCovisibles of its updated row (:216-238): every entry, THOSE
+ *   BELOW 15 INCLUDED, except bad keyframes (:229; bit 0 of kf_flags, the current keyframe's too), weight descending, equal weights by row
+ *   descending.
+ * Two kernel launches, one upload and one download for the whole batch; the results are in host memory when the call returns (stream:
+ * NULL = the calling thread's private stream).  TC2LI_ERR_INVALID before any launch for negative sizes or capacities, NULL required
+ * pointers, offsets that do not ascend from 0, indices out of range (current, conn_kf, slot_point below -1, obs_kf) and conn rows that
+ * do not ascend strictly.  TC2LI_ERR_CAPACITY when a list of some problem does not fit: then counts is written for every problem and no
+ * list for any; N_COUNTER and N_ORDERED are the sizes needed, N_CHANGED and N_CHANGED_ENTRIES too once those two fit (they are 0 until
+ * then).  Returns n_problems. */
+int tc2li_update_connections_batch(const tc2li_connections_problem* problems, int n_problems, void* stream);
+/* The same contract as plain sequential C++ (one problem per worker thread); needs no device. */
+int tc2li_host_update_connections_batch(const tc2li_connections_problem* problems, int n_problems);
+/* KeyFrame::UpdateBestCovisibles (:216-238) alone for n_rows keyframes of any number of sequences: what LocalMapping::KeyFrameCulling
+ * calls first (SF/src/LocalMapping.cc:920) and what KeyFrame::EraseConnection (SF/src/KeyFrame.cc:699-713) calls in every neighbour of a
+ * culled keyframe.  In: the CSR row_offsets [n_rows + 1], row_kf, row_weight of the keyframes' mConnectedKeyFrameWeights -- a row ascends
+ * strictly by keyframe (map order); row_kf are rows of bad [n_keyframes], isBad() of every keyframe the rows name (non-zero = bad).
+ * Out: out_offsets [n_rows + 1], out_kf / out_weight [row_offsets[n_rows]]: per keyframe its entries without the bad ones (:229), weight
+ * descending, equal weights by row descending (the sort of :224 on (weight, keyframe) read from the back, :231-232) -- the device function
+ * that orders the neighbours' lists of tc2li_update_connections_batch.  An empty row gives an empty list.  One launch, one upload, one
+ * download.  TC2LI_ERR_INVALID before any launch as above.  Returns n_rows. */
+int tc2li_update_best_covisibles_batch(const int32_t* row_offsets, const int32_t* row_kf, const int32_t* row_weight, int n_rows,
+                                       const uint8_t* bad, int n_keyframes, int32_t* out_offsets, int32_t* out_kf, int32_t* out_weight,
+                                       void* stream);
+/* The same on the CPU; needs no device. */
+int tc2li_host_update_best_covisibles_batch(const int32_t* row_offsets, const int32_t* row_kf, const int32_t* row_weight, int n_rows,
+                                            const uint8_t* bad, int n_keyframes, int32_t* out_offsets, int32_t* out_kf,
+                                            int32_t* out_weight);
+/* The sizes at which tc2li_update_connections_batch changes path (for tests): out[0] = the largest n_keyframes whose vote counters are
+ * kept in LDS (beyond: in global memory), out[1] = lanes per ranking group (a wavefront), out[2] = threads per problem in the vote
+ * kernel.  Returns 3.  No reference counterpart. */
+int tc2li_connections_limits(int32_t* out, int capacity);
+
 /* ---- tracking: stereo map points and the keyframe decision (SF/src/Tracking.cc:2942-3076 NeedNewKeyFrame, :3078-3212 CreateNewKeyFrame,
  * :2676-2734 UpdateLastFrame, :2477-2495 StereoInitialization) ----------------------------------------------------------------------------
  * The step between TrackLocalMap and local mapping: whether the frame becomes a keyframe, and which of its stereo keypoints become new map

@@ -2754,3 +2754,111 @@ def new_keyframe_batch(frames, decisions, unproject4, host=False, stream=0):
     for r, v in zip(res, ver):
         r.update({k: int(getattr(v, k)) for k, _ in KeyframeVerdict._fields_ if k != "pad_"})
     return res
+
+
+class ConnectionsProblem(C.Structure):
+    """tc2li_connections_problem"""
+    _fields_ = [(k, C.c_void_p) for k in ("kf_flags", "conn_offsets", "conn_kf", "conn_weight", "slot_point", "point_bad", "obs_offsets", "obs_kf",
+                                          "counts", "counter_kf", "counter_weight", "ordered_kf", "ordered_weight", "touched_kf", "touched_changed",
+                                          "changed_offsets", "changed_kf", "changed_weight")] \
+        + [(k, C.c_int32) for k in ("n_keyframes", "n_slots", "n_points", "current", "counter_capacity", "ordered_capacity", "changed_capacity")] \
+        + [("first_connection", C.c_uint8), ("is_init_kf", C.c_uint8), ("pad_", C.c_uint8 * 2)]
+
+
+CONNECTIONS_UNCHANGED, CONNECTIONS_UPDATED, CONNECTIONS_TH = 0, 1, 15
+_CONNECTIONS_ARRAYS = (("kf_flags", np.uint8), ("conn_offsets", np.int32), ("conn_kf", np.int32), ("conn_weight", np.int32), ("slot_point", np.int32),
+                       ("point_bad", np.uint8), ("obs_offsets", np.int32), ("obs_kf", np.int32))
+_CONNECTIONS_COUNTS = ("status", "n_counter", "n_ordered", "n_changed", "n_changed_entries", "parent")
+
+
+def connections_limits():
+    """tc2li_connections_limits -> {lds_keyframes, rank_lanes, vote_threads}: the sizes at which the device path of update_connections_batch
+    changes (the vote counters leave LDS above lds_keyframes keyframes; a wavefront of rank_lanes orders a list)."""
+    out = (C.c_int32 * 3)()
+    f = lib().tc2li_connections_limits
+    f.argtypes = [C.c_void_p, C.c_int]
+    _check(f(out, 3))
+    return dict(zip(("lds_keyframes", "rank_lanes", "vote_threads"), [int(v) for v in out]))
+
+
+def pack_connections_problems(problems, fill=0):
+    """The tc2li_connections_problem array of a batch with its output arrays (prefilled with `fill`) -> (array, outputs per problem, what must
+    stay alive).  Capacities: counter_capacity / ordered_capacity / changed_capacity of the problem's dict, by default what can never be too
+    small (n_keyframes, n_keyframes, every row one longer)."""
+    P = len(problems)
+    arr, outs, keep = (ConnectionsProblem * max(P, 1))(), [], []
+    for i, p in enumerate(problems):
+        a = {k: np.ascontiguousarray(p[k], t).reshape(-1) for k, t in _CONNECTIONS_ARRAYS}
+        nk, ns, npts = len(a["kf_flags"]), len(a["slot_point"]), len(a["point_bad"])
+        if len(a["conn_offsets"]) != nk + 1 or len(a["obs_offsets"]) != npts + 1:
+            raise ValueError("problem %d: conn_offsets or obs_offsets do not fit the tables" % i)
+        nc, no = int(a["conn_offsets"][-1]), int(a["obs_offsets"][-1])
+        if min(len(a["conn_kf"]), len(a["conn_weight"])) < nc or len(a["obs_kf"]) < no:
+            raise ValueError("problem %d: conn or observation arrays are shorter than their offsets say" % i)
+        cc, oc, hc = (int(p.get(k, d)) for k, d in (("counter_capacity", nk), ("ordered_capacity", nk), ("changed_capacity", nc + nk)))
+        full = lambda n, t: np.full(max(n, 0), fill, np.int64).astype(t)
+        o = dict(counts=full(8, np.int32), counter_kf=full(cc, np.int32), counter_weight=full(cc, np.int32), ordered_kf=full(oc, np.int32),
+                 ordered_weight=full(oc, np.int32), touched_kf=full(oc, np.int32), touched_changed=full(oc, np.uint8),
+                 changed_offsets=full(oc + 1, np.int32), changed_kf=full(hc, np.int32), changed_weight=full(hc, np.int32))
+        for k, v in list(a.items()) + list(o.items()):
+            setattr(arr[i], k, v.ctypes.data)
+        arr[i].n_keyframes, arr[i].n_slots, arr[i].n_points, arr[i].current = nk, ns, npts, int(p["current"])
+        arr[i].counter_capacity, arr[i].ordered_capacity, arr[i].changed_capacity = cc, oc, hc
+        arr[i].first_connection, arr[i].is_init_kf = int(bool(p.get("first_connection", 0))), int(bool(p.get("is_init_kf", 0)))
+        keep.append(a)
+        outs.append(o)
+    return arr, outs, keep
+
+
+def update_connections_batch(problems, host=False, stream=0, raw=False, fill=0):
+    """One ``KeyFrame::UpdateConnections`` call per problem.  problems: dicts with the arrays of tc2li_connections_problem (kf_flags,
+    conn_offsets, conn_kf, conn_weight, slot_point, point_bad, obs_offsets, obs_kf), current and optionally first_connection, is_init_kf and
+    the three capacities -> one dict per problem: status, parent, counter_kf, counter_weight, ordered_kf, ordered_weight, touched_kf,
+    touched_changed, changed_offsets [n_changed + 1], changed_kf, changed_weight, cut to their counts.  raw=True: the arrays at their full
+    capacity as the library left them (prefilled with `fill`) and counts.  host=True walks the same graph on the CPU."""
+    arr, outs, keep = pack_connections_problems(problems, fill)
+    if host:
+        f = lib().tc2li_host_update_connections_batch
+        f.argtypes = [C.c_void_p, C.c_int]
+        _check(f(C.addressof(arr), len(problems)))
+    else:
+        f = lib().tc2li_update_connections_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _check(f(C.addressof(arr), len(problems), C.c_void_p(stream)))
+    del keep
+    if raw:
+        return outs
+    res = []
+    for o in outs:
+        c = dict(zip(_CONNECTIONS_COUNTS, [int(v) for v in o["counts"][:6]]))
+        r = dict(status=c["status"], parent=c["parent"])
+        for k, n in (("counter_kf", "n_counter"), ("counter_weight", "n_counter"), ("ordered_kf", "n_ordered"), ("ordered_weight", "n_ordered"),
+                     ("touched_kf", "n_ordered"), ("touched_changed", "n_ordered"), ("changed_kf", "n_changed_entries"),
+                     ("changed_weight", "n_changed_entries")):
+            r[k] = o[k][:c[n]]
+        r["changed_offsets"] = o["changed_offsets"][:c["n_changed"] + 1] if c["status"] else np.zeros(1, np.int32)
+        res.append(r)
+    return res
+
+
+def update_best_covisibles_batch(rows, bad, host=False, stream=0):
+    """``KeyFrame::UpdateBestCovisibles`` for a flat list of keyframes of any number of sequences.  rows: dict with the CSR offsets, kf, weight of
+    their mConnectedKeyFrameWeights (a row ascends by kf); bad [n_keyframes]: isBad() of every keyframe the rows name -> dict offsets, kf,
+    weight: the ordered lists without the bad keyframes.  host=True orders on the CPU."""
+    off, kf, w = (np.ascontiguousarray(rows[k], np.int32).reshape(-1) for k in ("offsets", "kf", "weight"))
+    b = np.ascontiguousarray(bad, np.uint8).reshape(-1)
+    n = len(off) - 1
+    if n < 0 or min(len(kf), len(w)) < int(off[-1]):
+        raise ValueError("offsets are empty or kf / weight are shorter than they say")
+    out_off, out_kf, out_w = np.zeros(n + 1, np.int32), np.zeros(int(off[-1]), np.int32), np.zeros(int(off[-1]), np.int32)
+    args = [off.ctypes.data, kf.ctypes.data, w.ctypes.data, n, b.ctypes.data, len(b), out_off.ctypes.data, out_kf.ctypes.data, out_w.ctypes.data]
+    if host:
+        f = lib().tc2li_host_update_best_covisibles_batch
+        f.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        _check(f(*args))
+    else:
+        f = lib().tc2li_update_best_covisibles_batch
+        f.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        _check(f(*(args + [C.c_void_p(stream)])))
+    m = int(out_off[-1])
+    return dict(offsets=out_off, kf=out_kf[:m], weight=out_w[:m])
