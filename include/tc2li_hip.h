@@ -495,6 +495,12 @@ int tc2li_pose_optimization(double pose7[7], const double* Xw, const tc2li_ba_ed
 int tc2li_pose_optimization_batch(int n_frames, double* poses7, const int32_t* edge_offsets, const double* Xw,
                                   const tc2li_ba_edge* edges, const tc2li_camera* cam, uint8_t* outlier, int32_t* n_inliers,
                                   void* stream);
+/* The sizes at which the pose optimisation (every caller: the two entries above, the tracking, BoW and relocalisation batches) changes
+ * kernel, and which kernel ran last (for tests): out[0] = the largest number of correspondences of a batch's largest frame at which the
+ * frames are staged in LDS (beyond: every frame of the batch works in global memory), out[1] = the step in correspondences by which the
+ * LDS block grows, out[2] = threads per frame, out[3] = what the most recent pose optimisation of this process launched: 0 nothing yet,
+ * 1 the LDS kernel, 2 the global-memory kernel.  Returns 4.  Needs no device.  No reference counterpart. */
+int tc2li_pose_optimization_limits(int32_t* out, int capacity);
 
 /* Statistics of one bundle adjustment (all optional). */
 typedef struct tc2li_ba_stats {

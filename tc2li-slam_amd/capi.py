@@ -843,6 +843,16 @@ def pose_optimization_batch(poses7, edge_offsets, Xw, edges, cam5, stream=0):
     return poses, out[:len(edges)], inl
 
 
+def pose_optimization_limits():
+    """tc2li_pose_optimization_limits -> {lds_max_edges, lds_granule, threads, last_form}: a batch whose largest frame has more than lds_max_edges
+    correspondences runs the global-memory kernel; last_form is what the most recent pose optimisation launched (0 none, 1 LDS, 2 global)."""
+    out = (C.c_int32 * 4)()
+    f = lib().tc2li_pose_optimization_limits
+    f.argtypes = [C.c_void_p, C.c_int]
+    _check(f(out, 4))
+    return dict(zip(("lds_max_edges", "lds_granule", "threads", "last_form"), [int(v) for v in out]))
+
+
 class BaStats(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("trials", C.c_int32), ("n_free_poses", C.c_int32), ("pad_", C.c_int32),
                 ("initial_chi2", C.c_double), ("final_chi2", C.c_double), ("final_lambda", C.c_double)]

@@ -6,8 +6,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
+#include "common.hpp"
 #include "launch.hpp"
 #pragma clang fp contract(off)
 #include <stdint.h>
@@ -19,6 +21,8 @@
 namespace tc2li {
 
 constexpr int kPoThreads = 256;
+constexpr int kPoLdsMaxEdges = 2048;  // the largest frame whose correspondences are staged in LDS (at kPoLdsPerEdge: 125 KB)
+constexpr int kPoLdsGranule = 64;     // the dynamic LDS block is sized in steps of this many correspondences
 constexpr int kRed = 28;  // 21 upper-triangular H entries + 6 b entries + chi
 
 __device__ __forceinline__ void block_reduce(double (&v)[kRed], double* s_red /*[4][kRed]*/, double* s_out /*[kRed]*/) {
@@ -277,6 +281,10 @@ __global__ __launch_bounds__(kPoThreads) void k_pose_optimization_lds(const Pose
     for (int i = tid; i < N; i += kPoThreads) out[i] = s_out[i];
 }
 
+// what the most recent launch_pose_optimization of this process launched (tc2li_pose_optimization_limits): 0 nothing yet, 1 the LDS form, 2 the
+// global-memory form
+static std::atomic<int> g_po_last_form{0};
+
 void launch_pose_optimization(const PoseProblem* probs, int nprobs, const double* Xw, const BaEdge* edges, const CameraD& cam,
                               double* poses7, uint8_t* outlier, double* chi2_scratch, int* inliers, int max_edges, hipStream_t st) {
     if (nprobs <= 0) return;
@@ -284,13 +292,26 @@ void launch_pose_optimization(const PoseProblem* probs, int nprobs, const double
     // classes: a workgroup lives for the whole optimisation (milliseconds), and what it does not take of its CU's 160 KB the other stages'
     // kernels can (1200 correspondences: 73 KB; <= 1311: two workgroups per CU).  TC2LI_PO_LDS_CLASSES=1: the two classes (A/B).
     static const bool kClasses = getenv("TC2LI_PO_LDS_CLASSES") && atoi(getenv("TC2LI_PO_LDS_CLASSES")) != 0;
-    const int cap = kClasses ? (max_edges <= 1024 ? 1024 : 2048) : std::max(64, (max_edges + 63) / 64 * 64);
-    if (max_edges <= 2048 && ensure_dynamic_lds((const void*)k_pose_optimization_lds, 2048 * kPoLdsPerEdge + 64)) {
+    const int cap = kClasses ? (max_edges <= kPoLdsMaxEdges / 2 ? kPoLdsMaxEdges / 2 : kPoLdsMaxEdges)
+                             : std::max(kPoLdsGranule, (max_edges + kPoLdsGranule - 1) / kPoLdsGranule * kPoLdsGranule);
+    if (max_edges <= kPoLdsMaxEdges && ensure_dynamic_lds((const void*)k_pose_optimization_lds, kPoLdsMaxEdges * kPoLdsPerEdge + 64)) {
         TC2LI_LAUNCH(k_pose_optimization_lds, dim3(nprobs), dim3(kPoThreads), (size_t)cap * kPoLdsPerEdge + 64, st, probs, Xw, edges, cam, poses7, outlier,
                      inliers, cap);
+        g_po_last_form.store(1, std::memory_order_relaxed);
     } else {
         TC2LI_LAUNCH(k_pose_optimization, dim3(nprobs), dim3(kPoThreads), 0, st, probs, Xw, edges, cam, poses7, outlier, chi2_scratch, inliers);
+        g_po_last_form.store(2, std::memory_order_relaxed);
     }
 }
 
 }  // namespace tc2li
+
+extern "C" int tc2li_pose_optimization_limits(int32_t* out, int capacity) {
+    using namespace tc2li;
+    if (!out || capacity < 4) {
+        set_error("tc2li_pose_optimization_limits: room for 4 values is needed");
+        return TC2LI_ERR_INVALID;
+    }
+    out[0] = kPoLdsMaxEdges; out[1] = kPoLdsGranule; out[2] = kPoThreads; out[3] = g_po_last_form.load(std::memory_order_relaxed);
+    return 4;
+}

@@ -4,16 +4,11 @@ the order of the floating-point reductions)."""
 import numpy as np
 import pytest
 
+from pose_opt_cases import frame_problem
+
 pytestmark = pytest.mark.gpu
 
 POSE_RTOL = 1e-4  # the tolerance BASELINE.json states for optimised SE3 poses
-
-
-def frame_problem(w, k, truth_points=True):
-    ed = w["edges"][w["edges"][:, 1] == k].copy()
-    Xw = (w["points_true"] if truth_points else w["points"])[ed[:, 0].astype(int)]
-    ed[:, 0] = np.arange(len(ed)); ed[:, 1] = 0
-    return Xw, ed
 
 
 @pytest.mark.parametrize("seed,outliers", [(2, 0.08), (5, 0.0), (7, 0.3)])

@@ -6,12 +6,17 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def scenario(pkg, synthetic, seeds, w=1242, h=375, variants=None):
+def last_form(pkg):
+    """Which kernel the most recent pose optimisation launched: 1 = correspondences staged in LDS, 2 = in global memory."""
+    return pkg.pose_optimization_limits()["last_form"]
+
+
+def scenario(pkg, synthetic, seeds, w=1242, h=375, variants=None, nfeatures=2000):
     import torch
     F = len(seeds)
     imgs = np.stack([np.stack(synthetic.stereo_pair(s, w, h)) for s in seeds]).reshape(2 * F, h, w)
     dev = torch.from_numpy(imgs).cuda()
-    ext = pkg.OrbExtractor(max_width=w, max_height=h, max_images=2 * F)
+    ext = pkg.OrbExtractor(nfeatures=nfeatures, max_width=w, max_height=h, max_images=2 * F)
     kps, desc, counts, _ = ext.extract_batch_dev(dev.data_ptr(), 2 * F, w, h, w, w * h)
     bf = np.float32(synthetic.BF); b = np.float32(bf / np.float32(synthetic.FX))
     u_right, depth, _ = pkg.stereo_match_batch(ext, F, float(bf), float(b))
@@ -72,6 +77,7 @@ def check(pkg, oracle, synthetic, sc, th=7.0):
 def test_track_motion_model_batch(pkg, oracle, synthetic):
     sc = scenario(pkg, synthetic, [0, 1, 2, 3, 4, 5])
     res = check(pkg, oracle, synthetic, sc)
+    assert last_form(pkg) == 1
     assert all(nm > 300 and inl > 200 for nm, inl in res)
 
 
@@ -93,8 +99,8 @@ def test_track_motion_model_argument_errors(pkg, synthetic):
 
 
 # ---- Tracking::TrackLocalMap --------------------------------------------------------------------------------------------------
-def local_map_scenario(pkg, oracle, synthetic, seeds):
-    sc = scenario(pkg, synthetic, seeds)
+def local_map_scenario(pkg, oracle, synthetic, seeds, nfeatures=2000):
+    sc = scenario(pkg, synthetic, seeds, nfeatures=nfeatures)
     F = len(seeds)
     cap = sc["kps"].shape[1]
     fx, fy, cx, cy = [np.float32(v) for v in (synthetic.FX, synthetic.FY, synthetic.CX, synthetic.CY)]
@@ -132,9 +138,7 @@ def local_map_scenario(pkg, oracle, synthetic, seeds):
     return sc
 
 
-@pytest.mark.parametrize("th,far", [(1.0, False), (6.0, False), (2.0, True)])
-def test_track_local_map_batch(pkg, oracle, synthetic, th, far):
-    sc = local_map_scenario(pkg, oracle, synthetic, [10, 11, 12, 13])
+def check_local_map(pkg, oracle, synthetic, sc, th, far):
     F = len(sc["poses"])
     cam5 = np.float32([synthetic.FX, synthetic.FY, synthetic.CX, synthetic.CY, sc["bf"]]).astype(np.float64)
     got = pkg.capi.track_local_map_batch(sc["ext"], F, sc["kps"], sc["u_right"], sc["poses"], sc["held"], sc["held_Xw"], sc["local"], sc["local_off"], cam5,
@@ -153,6 +157,24 @@ def test_track_local_map_batch(pkg, oracle, synthetic, th, far):
         assert np.allclose(got[0][f], want[0], rtol=1e-4, atol=1e-6)
         # a keypoint that holds a point with observations keeps it
         assert np.all(got[1][f, :n][sc["held"][f, :n] == 1] == -1)
+
+
+@pytest.mark.parametrize("th,far", [(1.0, False), (6.0, False), (2.0, True)])
+def test_track_local_map_batch(pkg, oracle, synthetic, th, far):
+    check_local_map(pkg, oracle, synthetic, local_map_scenario(pkg, oracle, synthetic, [10, 11, 12, 13]), th, far)
+
+
+def test_tracking_through_the_global_memory_pose_optimisation(pkg, oracle, synthetic):
+    """nfeatures = 2100: the batches' capacity (nfeatures + 4 * nlevels) is beyond what the pose optimisation stages in LDS, and so are the frames'
+    keypoint counts: TrackWithMotionModel and TrackLocalMap end in the global-memory kernel, with the same results against the oracle."""
+    L = pkg.pose_optimization_limits()["lds_max_edges"]
+    sc = local_map_scenario(pkg, oracle, synthetic, [0, 1], nfeatures=2100)
+    assert sc["kps"].shape[1] > L and all(int(sc["counts"][2 * f]) > L for f in range(2))
+    res = check(pkg, oracle, synthetic, sc)
+    assert last_form(pkg) == 2
+    assert all(nm > 300 and inl > 200 for nm, inl in res)
+    check_local_map(pkg, oracle, synthetic, sc, 1.0, False)
+    assert last_form(pkg) == 2
 
 
 @pytest.mark.parametrize("th,far", [(1.0, False), (2.0, True)])
