@@ -90,7 +90,8 @@ typedef struct tc2li_orb_params {
 
 typedef struct tc2li_orb tc2li_orb;
 
-/* Creates an extractor able to process up to `max_images` images of at most max_width x max_height per call. */
+/* Creates an extractor able to process up to `max_images` images of at most max_width x max_height per call.
+ * The FAST thresholds are differences of 8-bit pixels: 0 <= ini_th_fast, min_th_fast <= 255, anything else is TC2LI_ERR_INVALID. */
 int tc2li_orb_create(const tc2li_orb_params* params, int max_width, int max_height, int max_images, tc2li_orb** out);
 void tc2li_orb_destroy(tc2li_orb* orb);
 
@@ -108,6 +109,14 @@ int tc2li_orb_extract(tc2li_orb* orb, const uint8_t* image, int width, int heigh
 int tc2li_orb_extract_batch(tc2li_orb* orb, const uint8_t* dev_images, int n_images, int width, int height, int stride,
                             size_t image_pitch_bytes, const int32_t lapping_area[2], tc2li_keypoint* keypoints,
                             uint8_t* descriptors, int capacity, int32_t* n_keypoints, int32_t* mono_index, void* stream);
+
+/* Host-only: the per-pixel forms of the FAST kernel (csrc/fast_forms.hpp, the source k_fast_cells runs), exposed so that their exactness
+ * can be checked without a GPU.  Item i is a centre v[i] and its 16 circle pixels p[16 i .. 16 i + 15] (cv::FAST's order); th in 0 .. 255.
+ * pretest[i]: the compass pre-test (items go through it four at a time, item i in byte i & 3); mask_bright / mask_dark[i]: bit j = circle
+ * pixel j is brighter than v + th / darker than v - th; polarity[i]: bit 0 a darker arc of nine, bit 1 a brighter one; score_dark /
+ * score_bright[i]: the largest arc contrast of either sign (a corner at th <=> the larger one exceeds th).  Outputs may be NULL. */
+int tc2li_host_fast_forms(const uint8_t* v, const uint8_t* p, int n, int th, uint8_t* pretest, uint16_t* mask_bright, uint16_t* mask_dark,
+                          uint8_t* polarity, int16_t* score_dark, int16_t* score_bright);
 
 /* Accessors the reference reads off the extractor: GetLevels/GetScaleFactors/... (SF/include/ORBextractor.h:70-90)
  * and mvImagePyramid (:92; used by Frame::ComputeStereoMatches, SF/src/Frame.cc:848,938,953). */

@@ -595,6 +595,19 @@ def host_reduced_solve(Hi, S, lam, rhs):
     return x if ok else None
 
 
+def host_fast_forms(v, p, th):
+    """``tc2li_host_fast_forms``: the FAST kernel's per-pixel forms (csrc/fast_forms.hpp) on the host, for centres ``v`` [n] and circles
+    ``p`` [n, 16] -> dict of pretest, mask_bright, mask_dark, polarity, score_dark, score_bright (arrays of n)."""
+    v = np.ascontiguousarray(v, np.uint8).reshape(-1)
+    p = np.ascontiguousarray(p, np.uint8).reshape(len(v), 16)
+    out = {"pretest": np.zeros(len(v), np.uint8), "mask_bright": np.zeros(len(v), np.uint16), "mask_dark": np.zeros(len(v), np.uint16),
+           "polarity": np.zeros(len(v), np.uint8), "score_dark": np.zeros(len(v), np.int16), "score_bright": np.zeros(len(v), np.int16)}
+    f = lib().tc2li_host_fast_forms
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
+    _check(f(v.ctypes.data, p.ctypes.data, len(v), int(th), *[a.ctypes.data for a in out.values()]))
+    return out
+
+
 def device_reduced_solve(Hi, S, lam, rhs, stream=0):
     """``tc2li_device_reduced_solve``: the same system through k_lvi_solve -> x, or None when a pivot fails."""
     Hi = np.ascontiguousarray(Hi, np.float64)

@@ -12,6 +12,7 @@
 #include <memory>
 
 #include "common.hpp"
+#include "fast_forms.hpp"
 #include "orb_device.hpp"
 #include "quadtree.hpp"
 #include "orb_handle.hpp"
@@ -216,7 +217,8 @@ extern "C" {
 
 int tc2li_orb_create(const tc2li_orb_params* p, int max_width, int max_height, int max_images, tc2li_orb** out) {
     if (!p || !out || max_width <= 0 || max_height <= 0 || max_images <= 0 || p->nlevels < 1 ||
-        p->nlevels > kMaxLevels || p->nfeatures < 1 || !(p->scale_factor > 1.f)) {
+        p->nlevels > kMaxLevels || p->nfeatures < 1 || !(p->scale_factor > 1.f) ||
+        p->ini_th_fast < 0 || p->ini_th_fast > 255 || p->min_th_fast < 0 || p->min_th_fast > 255) {  // fast_forms.hpp: 16-bit halves
         set_error("tc2li_orb_create: invalid argument");
         return TC2LI_ERR_INVALID;
     }
@@ -278,6 +280,36 @@ void tc2li_orb_destroy(tc2li_orb* orb) {
     if (!orb) return;
     tc2li::stereo_release_workspace(orb);
     delete orb;
+}
+
+int tc2li_host_fast_forms(const uint8_t* v, const uint8_t* p, int n, int th, uint8_t* pretest, uint16_t* mask_bright, uint16_t* mask_dark,
+                          uint8_t* pol, int16_t* score_dark, int16_t* score_bright) {
+    if (!v || !p || n < 0 || th < 0 || th > 255) { set_error("tc2li_host_fast_forms: invalid argument"); return TC2LI_ERR_INVALID; }
+    namespace ff = fastforms;
+    for (int i0 = 0; i0 < n; i0 += 4) {  // the pre-test as the kernel runs it: four items side by side, item i0 + k in byte k
+        uint32_t V = 0, P0 = 0, P4 = 0, P8 = 0, P12 = 0;
+        for (int k = 0; k < 4 && i0 + k < n; ++k) {
+            const uint8_t* c = p + 16 * (size_t)(i0 + k);
+            V |= (uint32_t)v[i0 + k] << (8 * k);
+            P0 |= (uint32_t)c[0] << (8 * k); P4 |= (uint32_t)c[4] << (8 * k); P8 |= (uint32_t)c[8] << (8 * k); P12 |= (uint32_t)c[12] << (8 * k);
+        }
+        const ff::Pre4 pre = ff::pretest4(V, P0, P4, P8, P12, th);
+        for (int k = 0; k < 4 && i0 + k < n; ++k)
+            if (pretest) pretest[i0 + k] = ff::pretest_flag(pre, k) ? 1 : 0;
+    }
+    for (int i = 0; i < n; ++i) {
+        const uint8_t* c = p + 16 * (size_t)i;
+        ff::pk16 r[8];
+        for (int k = 0; k < 8; ++k) r[k] = ff::pk_make(c[k], c[k + 8]);
+        uint32_t xb, xd;
+        ff::segment_words(r, v[i], th, xb, xd);
+        if (mask_bright) mask_bright[i] = (uint16_t)(xb & 0xffffu);
+        if (mask_dark) mask_dark[i] = (uint16_t)(xd & 0xffffu);
+        if (pol) pol[i] = (uint8_t)ff::polarity(r, v[i], th);
+        if (score_dark) score_dark[i] = (int16_t)ff::arc_score(r, v[i], true);
+        if (score_bright) score_bright[i] = (int16_t)ff::arc_score(r, v[i], false);
+    }
+    return TC2LI_OK;
 }
 
 int tc2li_orb_levels(const tc2li_orb* o) { return o ? o->prm.nlevels : TC2LI_ERR_INVALID; }

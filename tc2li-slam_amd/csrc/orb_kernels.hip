@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "det_math.hpp"
+#include "fast_forms.hpp"
 #include "orb_device.hpp"
 
 namespace tc2li {
@@ -294,16 +295,13 @@ __global__ __launch_bounds__(kResizeTailMaxThreads) void k_resize_tail(LevelTabl
 // Survivors go into an LDS list through a counter atomic and are then ranked by counting the survivors that precede them in
 // row-major order (the order cv::FAST returns them in), so the emitted list is ordered without a ballot pass (a ballot
 // compaction was tried: 1.05 ms against 0.64 ms per 128 images).
+// The per-pixel arithmetic -- the compass pre-test, the segment test's flags and the arc contrast -- is in fast_forms.hpp, two 16-bit values
+// per instruction (the host test runs the same source): the pre-test on two packed pairs of pixels, the 32 flags as sign bits of packed
+// differences (no compare / select chain), and ONE min / max network per survivor on eight (k, k + 8) pairs signed by the lane's polarity,
+// where there were two 16-wide networks in two branches.  The circle is eight registers instead of sixteen: 95 -> 60 VGPRs, 5 -> 8
+// wavefronts per SIMD by registers.  Numbers, and what was tried and dropped (one list append per lane and group, in two forms):
+// DESIGN.md "FAST cells: packed forms".
 // ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool has_arc9(uint32_t m16) {
-    uint32_t x = m16 | (m16 << 16);
-    uint32_t r = x & (x >> 1);
-    r &= r >> 2;
-    r &= r >> 4;
-    r &= x >> 8;
-    return (r & 0xffffu) != 0;
-}
-
 // i / n for 0 <= i < 2^16, 1 <= n < 256: the float quotient is off by less than one unit, one correction step makes it exact
 __device__ __forceinline__ int row_of(int i, int n, float inv_n) {
     int q = (int)((float)i * inv_n);
@@ -312,33 +310,16 @@ __device__ __forceinline__ int row_of(int i, int n, float inv_n) {
     return q;
 }
 
-template <bool DARK>
-__device__ __forceinline__ int arc_contrast(const int (&p)[16], int v) {
-    // max over the 16 arcs of 9 contiguous circle pixels of min(v - p) (DARK) or min(p - v)
-    int d[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) d[k] = DARK ? v - p[k] : p[k] - v;
-    int m2[16], m4[16], m8[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) m2[k] = min(d[k], d[(k + 1) & 15]);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) m4[k] = min(m2[k], m2[(k + 2) & 15]);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) m8[k] = min(m4[k], m4[(k + 4) & 15]);
-    int best = -256;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) best = max(best, min(m8[k], d[(k + 8) & 15]));
-    return best;
-}
-
 // TH x TW: the largest cell window the instantiation holds (LDS is sized by it: the small variant fits 8 workgroups per CU)
 // Threads per cell.  A cell's six phases are barrier-separated steps of about a microsecond, and the kernel issues VALU instructions 18 % of
 // the time (profiles/r02_pmc_instruction_mix.json): what counts is how many cells a CU has in flight.  128 threads per cell keep 15
 // workgroups resident (10.3 KB of LDS each) where 256 allow 8: 0.53 -> 0.43 ms per 128 images; 64: 0.52.  (Round 1 measured the
 // opposite, 1.13 against 0.89 ms, on the kernel that tested every pixel at the low threshold.)  Scoring inside the segment-test pass
 // (one barrier-separated step less, worse lane balance) was tried: 0.45 ms.
-constexpr int kFastThreads = 128;
-template <int TH, int TW>
+// The width is a template argument (kFastThreads) so that 64 can be measured against 128 in place, alone and in the loop
+// (TC2LI_FAST_THREADS; alone, with the packed forms: 2.65 against 2.41 ms per 1 024 images, DESIGN.md "FAST cells: packed forms").
+constexpr int kFastThreadsDefault = 128;
+template <int TH, int TW, int kFastThreads>
 __global__ __launch_bounds__(kFastThreads) void k_fast_cells(LevelTable levels, const FastCell* __restrict__ cells, int ini_th,
                                                     int min_th, uint32_t* __restrict__ slab, size_t slab_img_stride,
                                                     int* __restrict__ cell_counts, int ncells, int nimg,
@@ -401,11 +382,13 @@ __global__ __launch_bounds__(kFastThreads) void k_fast_cells(LevelTable levels, 
 
     const int ew = w - 6, eh = h - 6;
     // the 16 circle pixels and the centre of window position (cx, cy)
-    auto circle = [&](int cx, int cy, int (&p)[16]) -> int {
+    // as eight packed pairs (fast_forms.hpp): p[k] = (circle pixel k, circle pixel k + 8)
+    namespace ff = fastforms;
+    auto circle = [&](int cx, int cy, ff::pk16 (&p)[8]) -> int {
         const uint8_t* r3 = tile + cy * kTileP + cx;
         const uint8_t *r0 = r3 - 3 * kTileP, *r1 = r3 - 2 * kTileP, *r2 = r3 - kTileP, *r4 = r3 + kTileP, *r5 = r3 + 2 * kTileP, *r6 = r3 + 3 * kTileP;
-        p[0] = r6[0];  p[1] = r6[1];  p[2] = r5[2];  p[3] = r4[3];  p[4] = r3[3];  p[5] = r2[3];  p[6] = r1[2];  p[7] = r0[1];
-        p[8] = r0[0];  p[9] = r0[-1]; p[10] = r1[-2]; p[11] = r2[-3]; p[12] = r3[-3]; p[13] = r4[-3]; p[14] = r5[-2]; p[15] = r6[-1];
+        p[0] = ff::pk_make(r6[0], r0[0]);  p[1] = ff::pk_make(r6[1], r0[-1]); p[2] = ff::pk_make(r5[2], r1[-2]); p[3] = ff::pk_make(r4[3], r2[-3]);
+        p[4] = ff::pk_make(r3[3], r3[-3]); p[5] = ff::pk_make(r2[3], r4[-3]); p[6] = ff::pk_make(r1[2], r5[-2]); p[7] = ff::pk_make(r0[1], r6[-1]);
         return r3[0];
     };
     // The reference runs cv::FAST(iniThFAST) on the cell and only if that finds nothing cv::FAST(minThFAST) (SF/src/ORBextractor.cc:799-812).
@@ -445,13 +428,10 @@ __global__ __launch_bounds__(kFastThreads) void k_fast_cells(LevelTable levels, 
             const uint32_t u0 = rc[-3 * kDw], u1 = rc[-3 * kDw + 1], d0 = rc[3 * kDw], d1 = rc[3 * kDw + 1];
             const uint32_t V = __builtin_amdgcn_alignbyte(a1, a0, 3), P4 = __builtin_amdgcn_alignbyte(a2, a1, 2), P12 = a0;
             const uint32_t P8 = __builtin_amdgcn_alignbyte(u1, u0, 3), P0 = __builtin_amdgcn_alignbyte(d1, d0, 3);
+            const ff::Pre4 pre = ff::pretest4(V, P0, P4, P8, P12, th);  // two packed pairs of pixels, no compare per compass pixel
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int v = (int)((V >> (8 * k)) & 0xffu);
-                const int p0 = (int)((P0 >> (8 * k)) & 0xffu), p8 = (int)((P8 >> (8 * k)) & 0xffu), p4 = (int)((P4 >> (8 * k)) & 0xffu), p12 = (int)((P12 >> (8 * k)) & 0xffu);
-                const int most = min(max(p0, p8), max(p4, p12)), least = max(min(p0, p8), min(p4, p12));
-                if ((most > v + th || least < v - th) && 4 * g0 + k < ew) s_list[atomicAdd(&s_nlist, 1)] = (uint16_t)(cy * TW + 3 + 4 * g0 + k);
-            }
+            for (int k = 0; k < 4; ++k)
+                if (ff::pretest_flag(pre, k) && 4 * g0 + k < ew) s_list[atomicAdd(&s_nlist, 1)] = (uint16_t)(cy * TW + 3 + 4 * g0 + k);
         }
     }
     __syncthreads();
@@ -468,15 +448,9 @@ __global__ __launch_bounds__(kFastThreads) void k_fast_cells(LevelTable levels, 
             uint32_t entry = 0;
             if (k < npre) {
                 const int at = s_list[k], cy = at / TW, cx = at - cy * TW;
-                int p[16];
+                ff::pk16 p[8];
                 const int v = circle(cx, cy, p);
-                uint32_t mb = 0, md = 0;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    mb |= (uint32_t)(p[j] > v + th) << j;
-                    md |= (uint32_t)(p[j] < v - th) << j;
-                }
-                const uint32_t pol = (has_arc9(md) ? 1u : 0u) | (has_arc9(mb) ? 2u : 0u);  // bit 0: darker arc, bit 1: brighter arc
+                const uint32_t pol = ff::polarity(p, v, th);  // bit 0: darker arc, bit 1: brighter arc (the flags are sign bits of packed differences)
                 if (pol) entry = (uint32_t)at | (pol << 14);
             }
             __syncthreads();  // every entry of this round has been read
@@ -484,18 +458,15 @@ __global__ __launch_bounds__(kFastThreads) void k_fast_cells(LevelTable levels, 
         }
     }
     __syncthreads();
-    // Pass 2, survivors only, packed densely over the lanes: S = the largest arc contrast of the polarity that has an arc
-    // (the other polarity cannot exceed the threshold, so it cannot be the maximum).
+    // Pass 2, survivors only, packed densely over the lanes: S = the largest arc contrast of the polarity that has an arc.
     nlist = s_nlist;
     for (int k = tid; k < nlist; k += kFastThreads) {
         const uint32_t e = s_list[k];
         const int at = e & 0x3fff, cy = at / TW, cx = at - cy * TW;
-        int p[16];
+        ff::pk16 p[8];
         const int v = circle(cx, cy, p);
-        int S = 0;
-        if (e & 0x4000) S = arc_contrast<true>(p, v);
-        if (e & 0x8000) S = max(S, arc_contrast<false>(p, v));
-        score[at] = (uint8_t)S;
+        // a survivor has exactly one polarity (nine of sixteen pixels): one min / max network, the differences signed by the lane's polarity
+        score[at] = (uint8_t)ff::arc_score(p, v, (e & 0x4000) != 0);
     }
     __syncthreads();
     // Pass 3, survivors only: 3x3 strict non-max suppression at the attempt's threshold (every survivor has S > th; a neighbour
@@ -969,14 +940,23 @@ void launch_fast(const LevelTable& levels, const FastCell* cells, int ncells, in
     // cell windows are 35-px cells + 6: 48 x 48 holds all but the levels whose height leaves one or two tall rows of cells; those go
     // through the full-size variant (a third of the LDS-limited occupancy), each window class in its own launch
     static const int kCellsEnv = getenv("TC2LI_FAST_CELLS_PER_WG") ? atoi(getenv("TC2LI_FAST_CELLS_PER_WG")) : 4;
+    // threads per cell, 64 or 128 (anything else: the default), for A/B measurements in the loop
+    static const int kThreadsEnv = getenv("TC2LI_FAST_THREADS") ? atoi(getenv("TC2LI_FAST_THREADS")) : kFastThreadsDefault;
+    const bool narrow = kThreadsEnv == 64;
     const int cpw = nimg >= 32 ? std::max(1, std::min(kCellsEnv, 16)) : 1;  // a few images: every cell its own workgroup (the launch is latency-bound)
     auto grid = [&](int n_ids) { const int per_xcd = (n_ids * nimg + 7) / 8; return ((per_xcd + cpw - 1) / cpw) * 8; };
-    if (n_small > 0)
-        TC2LI_LAUNCH((k_fast_cells<48, 48>), dim3(grid(n_small)), dim3(kFastThreads), 0, st, levels, cells, ini_th, min_th, slab,
-                           slab_img_stride, cell_counts, ncells, nimg, small_ids, n_small, cpw);
-    if (n_large > 0)
-        TC2LI_LAUNCH((k_fast_cells<kFastTileH, kFastTilePitch>), dim3(grid(n_large)), dim3(kFastThreads), 0, st, levels, cells, ini_th,
-                           min_th, slab, slab_img_stride, cell_counts, ncells, nimg, large_ids, n_large, cpw);
+#define TC2LI_FAST_LAUNCH(TH, TW, NT, ids, n_ids)                                                                                         \
+    TC2LI_LAUNCH((k_fast_cells<TH, TW, NT>), dim3(grid(n_ids)), dim3(NT), 0, st, levels, cells, ini_th, min_th, slab, slab_img_stride, cell_counts, \
+                 ncells, nimg, ids, n_ids, cpw)
+    if (n_small > 0) {
+        if (narrow) TC2LI_FAST_LAUNCH(48, 48, 64, small_ids, n_small);
+        else TC2LI_FAST_LAUNCH(48, 48, 128, small_ids, n_small);
+    }
+    if (n_large > 0) {
+        if (narrow) TC2LI_FAST_LAUNCH(kFastTileH, kFastTilePitch, 64, large_ids, n_large);
+        else TC2LI_FAST_LAUNCH(kFastTileH, kFastTilePitch, 128, large_ids, n_large);
+    }
+#undef TC2LI_FAST_LAUNCH
 }
 
 void launch_compact(const FastCell* cells, const int* level_cell_begin, const int* cell_counts, int ncells,

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+typedef short ss2 __attribute__((ext_vector_type(2)));
 template <int OP>
 __global__ __launch_bounds__(512) void k(unsigned* out, int iters, unsigned seed) {
     unsigned a[8];
@@ -24,6 +25,18 @@ __global__ __launch_bounds__(512) void k(unsigned* out, int iters, unsigned seed
                 if (OP == 8) a[i] = min(a[i], a[(i + 3) & 7]) ^ b;                         // 2 ops
                 if (OP == 9) { float f = __builtin_bit_cast(float, a[i]); f = __builtin_fmaf(f, 1.0001f, 0.5f); a[i] = __builtin_bit_cast(unsigned, f); }
                 if (OP == 10) a[i] = __shfl_up(a[i], 1, 64);
+                // the packed 16-bit forms of k_fast_cells (csrc/fast_forms.hpp) and what they stand beside
+                const unsigned o = a[(i + 3) & 7];
+                if (OP == 11) a[i] = __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(ss2, a[i]), __builtin_bit_cast(ss2, o)));
+                if (OP == 12) a[i] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(ss2, a[i]), __builtin_bit_cast(ss2, o)));
+                if (OP == 13) a[i] = __builtin_bit_cast(unsigned, __builtin_bit_cast(ss2, a[i]) - __builtin_bit_cast(ss2, o));
+                if (OP == 14) a[i] = __builtin_bit_cast(unsigned, __builtin_elementwise_sub_sat(__builtin_bit_cast(us2, a[i]), __builtin_bit_cast(us2, o)));
+                if (OP == 15) asm volatile("v_max_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:BYTE_2" : "=v"(a[i]) : "v"(a[i]), "v"(o));
+                if (OP == 16) a[i] = __builtin_amdgcn_alignbit(a[i], o, 5);
+                if (OP == 17) asm volatile("v_and_or_b32 %0, %1, %2, %3" : "=v"(a[i]) : "v"(a[i]), "v"(b), "v"(o));
+                if (OP == 18) a[i] = __builtin_bit_cast(unsigned, __builtin_bit_cast(ss2, a[i]) * __builtin_bit_cast(ss2, b) + __builtin_bit_cast(ss2, o));
+                if (OP == 19) a[i] = __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(ss2, a[i]), __builtin_shufflevector(__builtin_bit_cast(ss2, o), __builtin_bit_cast(ss2, o), 1, 0)));
+                if (OP == 20) asm volatile("v_pk_lshrrev_b16 %0, 15, %1 op_sel_hi:[0,1]" : "=v"(a[i]) : "v"(o));
             }
     }
     unsigned s = 0;
@@ -47,5 +60,8 @@ int main() {
     run<9>("v_fma_f32", d, 1); run<7>("v_add_u32", d, 1); run<0>("v_dot4_u32_u8", d, 1); run<1>("v_dot2_u32_u16", d, 1); run<2>("v_perm_b32", d, 1);
     run<3>("v_alignbyte_b32", d, 1); run<4>("mul + add (u32)", d, 1); run<5>("shift | shift", d, 1); run<6>("v_mov_dpp wave_shr:1", d, 1); run<8>("min, xor (2 ops)", d, 2);
     run<10>("__shfl_up(., 1)", d, 1);
+    run<11>("v_pk_min_i16", d, 1); run<12>("v_pk_max_i16", d, 1); run<13>("v_pk_sub_i16", d, 1); run<14>("v_pk_sub_u16 clamp", d, 1);
+    run<15>("v_max_u32_sdwa (byte sel)", d, 1); run<16>("v_alignbit_b32", d, 1); run<17>("v_and_or_b32", d, 1); run<18>("v_pk_mad_u16", d, 1);
+    run<19>("v_pk_min_i16 op_sel swap", d, 1); run<20>("v_pk_lshrrev_b16", d, 1);
     return 0;
 }
