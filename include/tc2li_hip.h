@@ -518,9 +518,9 @@ typedef struct tc2li_ba_stats {
 } tc2li_ba_stats;
 
 /* The optimisation of Optimizer::LocalBundleAdjustment / OptimizerWithLidar::LocalLVBundleAdjustment (visual edges;
- * SF/src/Optimizer.cc:1118, SF/src/OptimizerWithLidar.cc:60; callers LocalMapping.cc:170,173): the host shim gathers
- * local / fixed keyframes and map points exactly as the reference does (OptimizerWithLidar.cc:63-130) and passes them
- * flattened -- poses in vertex-id order with their fixed flags, points, one edge per observation.  Runs
+ * SF/src/Optimizer.cc:1118, SF/src/OptimizerWithLidar.cc:60; callers LocalMapping.cc:170,173).  In: the window as the reference
+ * gathers it (OptimizerWithLidar.cc:63-130), flattened -- poses in vertex-id order with their fixed flags, points, one edge
+ * per observation: the arrays tc2li_ba_window_batch ("the window of the local BA" below) fills from the flat graph.  Runs
  * optimizer.optimize(iterations) with Huber sqrt(5.991) / sqrt(7.815); lambda_init <= 0 selects tau * max diagonal,
  * the inertial-map branch passes 100 (OptimizerWithLidar.cc:141-142).  stop_flag is *pbStopFlag, polled between
  * Levenberg trials like g2o's forceStopFlag.  Outputs: poses and points updated in place (double; the shim casts to
@@ -1670,6 +1670,119 @@ int tc2li_host_update_best_covisibles_batch(const int32_t* row_offsets, const in
  * kept in LDS (beyond: in global memory), out[1] = lanes per ranking group (a wavefront), out[2] = threads per problem in the vote
  * kernel.  Returns 3.  No reference counterpart. */
 int tc2li_connections_limits(int32_t* out, int capacity);
+
+/* ---- local mapping: the window of the local BA (SF/src/OptimizerWithLidar.cc:63-130 the gather, :157-187 the pose vertices, :226-253 the
+ * keyframes of the BALM edge, :263-384 the point vertices and edges; the identical gather of Optimizer::LocalBundleAdjustment,
+ * SF/src/Optimizer.cc:1124-1190) -----------------------------------------------------------------------------------------------------------
+ * The graph walk that turns "the current keyframe" into the arrays of tc2li_local_bundle_adjustment / tc2li_ba_problem /
+ * tc2li_lidar_window, on the flat graph of tc2li_connections_problem, for many sequences at once.  The pixel, the right coordinate and the
+ * octave of every observation are read from the keyframe store's slots; floats are widened to double, so every output is exact.
+ * Not covered: the temporal window of LocalLVIBA / LocalInertialBA (:493-607) and the two-camera branch (:347-381). */
+enum tc2li_ba_window_status {
+    TC2LI_BA_WINDOW_OK = 0,
+    TC2LI_BA_WINDOW_ABORTED = 1        /* num_fixedKF == 0 (:126-130): the reference returns without a BA */
+};
+enum tc2li_ba_window_count {
+    TC2LI_BA_WINDOW_STATUS = 0,        /* tc2li_ba_window_status */
+    TC2LI_BA_WINDOW_NUM_FIXED_KF = 1,  /* num_fixedKF of :123: the fixed cameras, plus the 1 of :85-88 when a local keyframe is the initial one */
+    TC2LI_BA_WINDOW_NUM_OPT_KF = 2,    /* num_OptKF of :171: lLocalKeyFrames.size() */
+    TC2LI_BA_WINDOW_N_POSES = 3,       /* entries of pose_row / poses7_out / fixed: local keyframes + fixed cameras */
+    TC2LI_BA_WINDOW_N_POINTS = 4,      /* entries of point_row / points3_out: lLocalMapPoints.size() */
+    TC2LI_BA_WINDOW_N_EDGES = 5,       /* entries of edges (num_edges of :385) */
+    TC2LI_BA_WINDOW_N_LIDAR = 6,       /* entries of lidar_pose_index: 0, or 3 .. 6 */
+    TC2LI_BA_WINDOW_N_POINTS_WITHOUT_EDGE = 7,   /* listed points that got no edge (tc2li_local_bundle_adjustment refuses such a point) */
+    TC2LI_BA_WINDOW_COUNTS = 8
+};
+#define TC2LI_BA_WINDOW_MAX_LIDAR 6    /* win_size_ of :245 */
+/* One call of the gather for one current keyframe.  All pointers are host memory, the arrays are copied by the call; indices are rows of the
+ * problem's own tables; problems of one batch are independent.  The row order of the keyframes stands in for the address order of the
+ * reference's std::map<KeyFrame*, ...>, as in tc2li_connections_problem.
+ *   keyframes (n_keyframes rows: the current keyframe, cov_kf, every observer of their points):
+ *     kf_slot   the slot of the keyframe in the store (the host entry: the index into views)
+ *     kf_id     mnId
+ *     kf_flags  bit 0 isBad(), bit 1 GetMap() != pCurrentMap, bit 2 mLidarProps->GetSurfacePcl()->size() > 0
+ *     poses7    [n_keyframes][7] GetPose() as tc2li_ba_problem takes it (qx qy qz qw tx ty tz, widened)
+ *     slot_offsets [n_keyframes + 1], slot_point: GetMapPointMatches() per keyframe as a CSR, -1 = NULL.  Only the rows of the current
+ *     keyframe and of cov_kf are read; others may be empty.
+ *   current: the row of pKF;  cov_kf [n_cov]: GetVectorCovisibleKeyFrames() in its order (no row twice, not the current one);
+ *   init_kf_id: pMap->GetInitKFid()
+ *   points (n_points rows): point_flags bit 0 isBad(), bit 1 GetMap() != pCurrentMap; positions [n_points][3] GetWorldPos() widened; CSR
+ *     obs_offsets [n_points + 1], obs_kf, obs_index: GetObservations(), a row ascending strictly by keyframe row, obs_index = get<0> of
+ *     the tuple (the left keypoint, or -1)
+ * Out (capacities are the caller's; an array whose capacity is 0 may be NULL):
+ *   counts [TC2LI_BA_WINDOW_COUNTS]: always written.  ABORTED: every count after NUM_FIXED_KF is 0 and NO OTHER OUTPUT IS WRITTEN.
+ *   pose_row [pose_capacity], poses7_out [pose_capacity][7], fixed [pose_capacity]: the local keyframes and the fixed cameras ascending by
+ *     kf_id (by row among equal ids) -- the vertex-id order tc2li_local_bundle_adjustment asks for; fixed = 1 for a fixed camera (:181) and
+ *     for a local keyframe whose id is init_kf_id (:164)
+ *   point_row [point_capacity], points3_out [point_capacity][3]: lLocalMapPoints in the reference's order
+ *   edges [edge_capacity]: one per observation in the creation order of :263-384; point / pose index the two lists above
+ *   lidar_pose_index [TC2LI_BA_WINDOW_MAX_LIDAR]: the entries of pose_row of vOptKeyFrames[0 .. n_lidar), -1 beyond; the clouds stay with
+ *     the caller (tc2li_lidar_window::win_pose) */
+typedef struct tc2li_ba_window_problem {
+    const int32_t* kf_slot;
+    const int64_t* kf_id;
+    const uint8_t* kf_flags;
+    const double* poses7;
+    const int32_t* slot_offsets;
+    const int32_t* slot_point;
+    const int32_t* cov_kf;
+    const uint8_t* point_flags;
+    const double* positions;
+    const int32_t* obs_offsets;
+    const int32_t* obs_kf;
+    const int32_t* obs_index;
+    int32_t* counts;
+    int32_t* pose_row;
+    double* poses7_out;
+    uint8_t* fixed;
+    int32_t* point_row;
+    double* points3_out;
+    tc2li_ba_edge* edges;
+    int32_t* lidar_pose_index;
+    int64_t init_kf_id;
+    int32_t n_keyframes, n_points, n_cov, current;
+    int32_t pose_capacity, point_capacity, edge_capacity;
+    int32_t pad_;
+} tc2li_ba_window_problem;
+/* The gather for n_problems current keyframes at once on the device.  Line for line:
+ *   local keyframes (:63-76): the current keyframe whatever its flags (:65), then every keyframe of cov_kf in order that is neither bad nor
+ *   of another map (:74).  EVERY keyframe of cov_kf is marked local (:73 comes before the test of :74): a bad or other-map neighbour is
+ *   neither local nor ever fixed (:115).
+ *   local points (:78-104): the local keyframes in list order, their slots ascending; a point that is not NULL (:93), not bad and of this
+ *   map (:94) is listed at its first occurrence (:97-101), whether two slots or two keyframes hold it.
+ *   fixed cameras (:107-122): every observer of a listed point that is not marked local and is neither bad nor of another map (:115-119),
+ *   WHATEVER ITS obs_index: a fixed pose may end up with no edge.
+ *   num_fixedKF (:123) = the fixed cameras + 1 if a local keyframe has init_kf_id (:85-88); 0: ABORTED (:126-130).
+ *   poses (:157-187): setId(mnId) is what orders them.
+ *   BALM keyframes (:226-253): the local keyframes in list order with bit 2 set; n_lidar = min(their number, 6) if there are more than 2,
+ *   else 0.
+ *   edges (:263-384): the listed points in order, the observations of a point ascending by row; an observer that is bad or of another map
+ *   is skipped (:281), so is obs_index -1 (:286, :313).  u, v = mvKeysUn[obs_index].pt, u_right = mvuRight[obs_index] when >= 0 (:313),
+ *   else -1 (:286), inv_sigma2 = inv_level_sigma2[octave] (mvInvLevelSigma2, :297, :325).
+ * Two kernel launches, one upload and one download for the whole batch; the results are in host memory when the call returns (stream:
+ * NULL = the calling thread's private stream).  TC2LI_ERR_INVALID before any launch for negative sizes or capacities, NULL required
+ * pointers, offsets that do not ascend from 0, indices out of range (current, cov_kf, slot_point below -1, obs_kf, obs_index below -1 or
+ * beyond the keypoints of the observer's slot), a row of cov_kf named twice or equal to current, observation rows that do not ascend
+ * strictly, a kf_slot that is empty or out of range, and a slot that holds an octave outside [0, n_levels).  TC2LI_ERR_CAPACITY when a
+ * list of some problem does not fit: then counts is written for every problem, with the sizes needed, and no list for any.  Returns
+ * n_problems. */
+int tc2li_ba_window_batch(tc2li_keyframe_store* store, const tc2li_ba_window_problem* problems, int n_problems,
+                          const float* inv_level_sigma2, int n_levels, void* stream);
+/* The same contract as plain sequential C++ (one problem per worker thread): the walk the host shim made until now.  kf_slot indexes
+ * views [n_views], of which n, keys and u_right are read (n < 0: an empty slot).  Needs no device. */
+int tc2li_host_ba_window_batch(const tc2li_keyframe_view* views, int n_views, const tc2li_ba_window_problem* problems, int n_problems,
+                               const float* inv_level_sigma2, int n_levels);
+/* The sizes at which tc2li_ba_window_batch changes path (for tests): out[0] = the largest n_keyframes whose local / fixed marks are kept
+ * in LDS (beyond: in global memory), out[1] = the largest n_points whose first-occurrence keys are kept in LDS (beyond: in global
+ * memory), out[2] = threads per problem.  Returns 3.  Needs no device.  No reference counterpart. */
+int tc2li_ba_window_limits(int32_t* out, int capacity);
+/* The outlier rule after the BA (:402-449), host only: vToErase as (pose index, point index) pairs in the reference's order -- the
+ * monocular edges (u_right < 0) with chi2 > 5.991 || !depthPositive (:406-419) in creation order, then the stereo edges with 7.815
+ * (:436-449); edges of a point with point_bad_now (pMP->isBad() after the BA, :411, :441) are skipped.  edges, edge_chi2 and
+ * edge_depth_positive are those of the finished tc2li_local_bundle_adjustment; erase_pose / erase_point [capacity].  Returns the count;
+ * TC2LI_ERR_CAPACITY (nothing written) when it exceeds capacity, TC2LI_ERR_INVALID for an edge whose point is outside [0, n_points). */
+int tc2li_ba_window_outliers(const tc2li_ba_edge* edges, const double* edge_chi2, const uint8_t* edge_depth_positive, int n_edges,
+                             const uint8_t* point_bad_now, int n_points, int32_t* erase_pose, int32_t* erase_point, int capacity);
 
 /* ---- tracking: stereo map points and the keyframe decision (SF/src/Tracking.cc:2942-3076 NeedNewKeyFrame, :3078-3212 CreateNewKeyFrame,
  * :2676-2734 UpdateLastFrame, :2477-2495 StereoInitialization) ----------------------------------------------------------------------------

@@ -2885,3 +2885,126 @@ def update_best_covisibles_batch(rows, bad, host=False, stream=0):
         _check(f(*(args + [C.c_void_p(stream)])))
     m = int(out_off[-1])
     return dict(offsets=out_off, kf=out_kf[:m], weight=out_w[:m])
+
+
+class BaWindowProblem(C.Structure):
+    """tc2li_ba_window_problem"""
+    _fields_ = [(k, C.c_void_p) for k in ("kf_slot", "kf_id", "kf_flags", "poses7", "slot_offsets", "slot_point", "cov_kf", "point_flags", "positions",
+                                          "obs_offsets", "obs_kf", "obs_index", "counts", "pose_row", "poses7_out", "fixed", "point_row", "points3_out",
+                                          "edges", "lidar_pose_index")] \
+        + [("init_kf_id", C.c_int64)] \
+        + [(k, C.c_int32) for k in ("n_keyframes", "n_points", "n_cov", "current", "pose_capacity", "point_capacity", "edge_capacity", "pad_")]
+
+
+BA_WINDOW_OK, BA_WINDOW_ABORTED, BA_WINDOW_MAX_LIDAR = 0, 1, 6
+_BA_WINDOW_ARRAYS = (("kf_slot", np.int32), ("kf_id", np.int64), ("kf_flags", np.uint8), ("poses7", np.float64), ("slot_offsets", np.int32),
+                     ("slot_point", np.int32), ("cov_kf", np.int32), ("point_flags", np.uint8), ("positions", np.float64), ("obs_offsets", np.int32),
+                     ("obs_kf", np.int32), ("obs_index", np.int32))
+_BA_WINDOW_COUNTS = ("status", "num_fixed_kf", "num_opt_kf", "n_poses", "n_points", "n_edges", "n_lidar", "n_points_without_edge")
+
+
+def ba_window_limits():
+    """tc2li_ba_window_limits -> {lds_keyframes, lds_points, threads}: the sizes at which the device path of ba_window_batch changes (the
+    keyframe marks leave LDS above lds_keyframes keyframes, the first-occurrence keys above lds_points points)."""
+    out = (C.c_int32 * 3)()
+    f = lib().tc2li_ba_window_limits
+    f.argtypes = [C.c_void_p, C.c_int]
+    _check(f(out, 3))
+    return dict(zip(("lds_keyframes", "lds_points", "threads"), [int(v) for v in out]))
+
+
+def pack_ba_window_problems(problems, fill=0):
+    """The tc2li_ba_window_problem array of a batch with its output arrays (prefilled with `fill`) -> (array, outputs per problem, what must
+    stay alive).  Capacities: pose_capacity / point_capacity / edge_capacity of the problem's dict, by default what can never be too small
+    (the keyframes, the points, the observations)."""
+    arr, outs, keep = (BaWindowProblem * max(len(problems), 1))(), [], []
+    for i, p in enumerate(problems):
+        a = {k: np.ascontiguousarray(p[k], t).reshape(-1) for k, t in _BA_WINDOW_ARRAYS}
+        nk, npts = len(a["kf_slot"]), len(a["point_flags"])
+        if len(a["kf_id"]) != nk or len(a["kf_flags"]) != nk or len(a["poses7"]) != 7 * nk or len(a["slot_offsets"]) != nk + 1:
+            raise ValueError("problem %d: the keyframe arrays do not have one row per keyframe" % i)
+        if len(a["positions"]) != 3 * npts or len(a["obs_offsets"]) != npts + 1:
+            raise ValueError("problem %d: the point arrays do not have one row per point" % i)
+        ns, no = int(a["slot_offsets"][-1]), int(a["obs_offsets"][-1])
+        if len(a["slot_point"]) < ns or min(len(a["obs_kf"]), len(a["obs_index"])) < no:
+            raise ValueError("problem %d: slot or observation arrays are shorter than their offsets say" % i)
+        pc, tc, ec = (int(p.get(k, d)) for k, d in (("pose_capacity", nk), ("point_capacity", npts), ("edge_capacity", no)))
+        full = lambda n, t: np.full(max(n, 0), fill, np.int64).astype(t)
+        edges = np.zeros(max(ec, 0), BA_EDGE_DTYPE)
+        edges.view(np.uint8)[:] = fill & 0xff
+        o = dict(counts=full(8, np.int32), pose_row=full(pc, np.int32), poses7_out=full(7 * pc, np.float64), fixed=full(pc, np.uint8),
+                 point_row=full(tc, np.int32), points3_out=full(3 * tc, np.float64), edges=edges, lidar_pose_index=full(BA_WINDOW_MAX_LIDAR, np.int32))
+        for k, v in list(a.items()) + list(o.items()):
+            setattr(arr[i], k, v.ctypes.data)
+        arr[i].init_kf_id = int(p["init_kf_id"])
+        arr[i].n_keyframes, arr[i].n_points, arr[i].n_cov, arr[i].current = nk, npts, len(a["cov_kf"]), int(p["current"])
+        arr[i].pose_capacity, arr[i].point_capacity, arr[i].edge_capacity = pc, tc, ec
+        keep.append(a)
+        outs.append(o)
+    return arr, outs, keep
+
+
+def _pack_ba_window_views(views):
+    """views: per slot None (empty) or a dict with keys (KEYPOINT_DTYPE) and u_right -> (tc2li_keyframe_view array with n, keys, u_right, keep)."""
+    arr, keep = (KeyframeView * max(len(views), 1))(), []
+    for i, v in enumerate(views):
+        if v is None:
+            arr[i].n = -1
+            continue
+        k, ur = np.ascontiguousarray(v["keys"], KEYPOINT_DTYPE), np.ascontiguousarray(v["u_right"], np.float32)
+        if len(k) != len(ur):
+            raise ValueError("view %d: one u_right per keypoint" % i)
+        keep.append((k, ur))
+        arr[i].n, arr[i].keys, arr[i].u_right = len(k), k.ctypes.data, ur.ctypes.data
+    return arr, keep
+
+
+def ba_window_batch(problems, inv_level_sigma2, store=None, views=None, stream=0, raw=False, fill=0):
+    """The gather of ``OptimizerWithLidar::LocalLVBundleAdjustment`` (the window of the local BA), one per problem.  problems: dicts with the
+    arrays of tc2li_ba_window_problem (kf_slot, kf_id, kf_flags, poses7, slot_offsets, slot_point, cov_kf, point_flags, positions, obs_offsets,
+    obs_kf, obs_index), current, init_kf_id and optionally the three capacities.  store: a :class:`KeyframeStore` -- the device entry; views:
+    per slot None or a dict with keys and u_right -- the host entry.  -> one dict per problem: status, num_fixed_kf, num_opt_kf, n_lidar,
+    n_points_without_edge, pose_row, poses7 [n, 7], fixed, point_row, points3 [n, 3], edges (BA_EDGE_DTYPE), lidar_pose_index [n_lidar], cut to
+    their counts.  raw=True: the arrays at their full capacity as the library left them (prefilled with `fill`) and counts."""
+    if (store is None) == (views is None):
+        raise ValueError("either a store (the device entry) or views (the host entry)")
+    arr, outs, keep = pack_ba_window_problems(problems, fill)
+    sg = np.ascontiguousarray(inv_level_sigma2, np.float32).reshape(-1)
+    if views is not None:
+        varr, vkeep = _pack_ba_window_views(views)
+        f = lib().tc2li_host_ba_window_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        _check(f(C.addressof(varr), len(views), C.addressof(arr), len(problems), sg.ctypes.data, len(sg)))
+        del vkeep
+    else:
+        f = lib().tc2li_ba_window_batch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        _check(f(store._handle(), C.addressof(arr), len(problems), sg.ctypes.data, len(sg), C.c_void_p(stream)))
+    del keep
+    if raw:
+        return outs
+    res = []
+    for o in outs:
+        c = dict(zip(_BA_WINDOW_COUNTS, [int(v) for v in o["counts"]]))
+        r = {k: c[k] for k in ("status", "num_fixed_kf", "num_opt_kf", "n_lidar", "n_points_without_edge")}
+        r.update(pose_row=o["pose_row"][:c["n_poses"]], poses7=o["poses7_out"].reshape(-1, 7)[:c["n_poses"]], fixed=o["fixed"][:c["n_poses"]],
+                 point_row=o["point_row"][:c["n_points"]], points3=o["points3_out"].reshape(-1, 3)[:c["n_points"]], edges=o["edges"][:c["n_edges"]],
+                 lidar_pose_index=o["lidar_pose_index"][:c["n_lidar"]])
+        res.append(r)
+    return res
+
+
+def ba_window_outliers(edges, edge_chi2, edge_depth_positive, point_bad_now, capacity=None):
+    """tc2li_ba_window_outliers: vToErase of the local BA as (pose index, point index) pairs [n, 2] in the reference's order -- the monocular
+    edges over 5.991 or behind the camera, then the stereo edges with 7.815; edges of points that are bad by now are skipped."""
+    e = np.ascontiguousarray(edges, BA_EDGE_DTYPE)
+    chi2, dpos = np.ascontiguousarray(edge_chi2, np.float64).reshape(-1), np.ascontiguousarray(edge_depth_positive, np.uint8).reshape(-1)
+    bad = np.ascontiguousarray(point_bad_now, np.uint8).reshape(-1)
+    if min(len(chi2), len(dpos)) < len(e):
+        raise ValueError("one chi2 and one depth flag per edge")
+    cap = len(e) if capacity is None else int(capacity)
+    pose, point = np.full(max(cap, 0), -1, np.int32), np.full(max(cap, 0), -1, np.int32)
+    f = lib().tc2li_ba_window_outliers
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    n = _check(f(e.ctypes.data, chi2.ctypes.data, dpos.ctypes.data, len(e), bad.ctypes.data, len(bad), pose.ctypes.data, point.ctypes.data, cap))
+    return np.stack([pose[:n], point[:n]], 1)

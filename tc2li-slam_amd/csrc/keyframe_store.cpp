@@ -15,6 +15,7 @@
 #include <mutex>
 #include <vector>
 
+#include "ba_window_device.hpp"
 #include "common.hpp"
 #include "mapping_device.hpp"
 #include "mapping_host.hpp"
@@ -140,6 +141,14 @@ extern "C" int tc2li_keyframe_store_info(tc2li_keyframe_store* S, int slot, int3
     if (n_keypoints) *n_keypoints = S->info[slot].n < 0 ? -1 : S->info[slot].n;
     if (n_nodes) *n_nodes = S->info[slot].n < 0 ? -1 : S->info[slot].n_nodes;
     return 0;
+}
+
+// what tc2li_ba_window_batch reads of the store (ba_window_host.cpp)
+int tc2li::keyframe_store_slots(const tc2li_keyframe_store* S) { return S->max_kf; }
+void tc2li::keyframe_store_baw(tc2li_keyframe_store* S, BawStore* where, int32_t* n_keypoints, int32_t* n_levels, int capacity) {
+    *where = BawStore{S->slab + S->o_slots, S->stride, S->s_keys, S->s_ur};
+    std::lock_guard<std::mutex> lk(S->info_mu);
+    for (int s = 0; s < capacity && s < S->max_kf; ++s) { n_keypoints[s] = S->info[s].n < 0 ? -1 : S->info[s].n; n_levels[s] = S->info[s].n_levels; }
 }
 
 extern "C" int tc2li_keyframe_store_put_batch(tc2li_keyframe_store* S, int n, const int32_t* slots, const tc2li_keyframe_view* views,
