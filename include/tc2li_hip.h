@@ -1677,7 +1677,7 @@ int tc2li_connections_limits(int32_t* out, int capacity);
  * The graph walk that turns "the current keyframe" into the arrays of tc2li_local_bundle_adjustment / tc2li_ba_problem /
  * tc2li_lidar_window, on the flat graph of tc2li_connections_problem, for many sequences at once.  The pixel, the right coordinate and the
  * octave of every observation are read from the keyframe store's slots; floats are widened to double, so every output is exact.
- * Not covered: the temporal window of LocalLVIBA / LocalInertialBA (:493-607) and the two-camera branch (:347-381). */
+ * Not covered: the two-camera branch (:347-381). */
 enum tc2li_ba_window_status {
     TC2LI_BA_WINDOW_OK = 0,
     TC2LI_BA_WINDOW_ABORTED = 1        /* num_fixedKF == 0 (:126-130): the reference returns without a BA */
@@ -1783,6 +1783,145 @@ int tc2li_ba_window_limits(int32_t* out, int capacity);
  * TC2LI_ERR_CAPACITY (nothing written) when it exceeds capacity, TC2LI_ERR_INVALID for an edge whose point is outside [0, n_points). */
 int tc2li_ba_window_outliers(const tc2li_ba_edge* edges, const double* edge_chi2, const uint8_t* edge_depth_positive, int n_edges,
                              const uint8_t* point_bad_now, int n_points, int32_t* erase_pose, int32_t* erase_point, int capacity);
+
+/* ---- local mapping: the window of the inertial local BA (OptimizerWithLidar::LocalLVIBA, SF/src/OptimizerWithLidar.cc:489-607 the gather,
+ * :632-727 the vertices and the keyframes of the LiDAR edge, :729-800 the inertial links, :832-969 the point vertices and edges, :985-1045
+ * the outlier rule; the twin Optimizer::LocalInertialBA, SF/src/Optimizer.cc:1512-1631 and on) -------------------------------------------
+ * The graph walk that turns "the current keyframe" into the arrays of tc2li_local_inertial_bundle_adjustment /
+ * tc2li_local_lvi_bundle_adjustment / tc2li_lvi_problem, on the flat graph of tc2li_ba_window_problem, for many sequences at once.  Line
+ * numbers below are OptimizerWithLidar.cc's.  The two reference functions were compared line by line: gather, vertices, links, edges and
+ * outlier rule are the same text; they differ in the LiDAR edge alone (:697-727), which `with_lidar` selects.  It is NOT the visual gather
+ * with another list: it follows mPrevKF, tests points with isBad() only, may turn its oldest keyframe into the fixed one, picks fixed
+ * observers greedily up to 200, and takes the LiDAR keyframes by position.  maxCovKF is 0 and the loop of :557-584 breaks on entry
+ * (size() >= 0), so GetVectorCovisibleKeyFrames() is never read and the problem has no cov_kf.  Not covered: the two-camera branch
+ * (:934-966). */
+enum tc2li_inertial_window_status {
+    TC2LI_INERTIAL_WINDOW_OK = 0,
+    TC2LI_INERTIAL_WINDOW_EMPTY = 1      /* the window was one keyframe without predecessor: :553 popped it and nothing is left to optimise */
+};
+enum tc2li_inertial_window_count {
+    TC2LI_INERTIAL_WINDOW_STATUS = 0,        /* tc2li_inertial_window_status */
+    TC2LI_INERTIAL_WINDOW_N_FIXED_KF = 1,    /* lFixedKeyFrames.size(): the keyframe of :542-554 and the picks of :586-607 */
+    TC2LI_INERTIAL_WINDOW_N_OPT_KF = 2,      /* vpOptimizableKFs.size() after :553 (N of :633) */
+    TC2LI_INERTIAL_WINDOW_N_VERTICES = 3,    /* entries of kf_row / keyframes_out / fixed / has_imu: the two above added */
+    TC2LI_INERTIAL_WINDOW_N_POINTS = 4,      /* entries of point_row / points3_out: lLocalMapPoints.size() */
+    TC2LI_INERTIAL_WINDOW_N_EDGES = 5,       /* entries of edges */
+    TC2LI_INERTIAL_WINDOW_N_LINKS = 6,       /* entries of links / link_kf2_row */
+    TC2LI_INERTIAL_WINDOW_N_LIDAR = 7,       /* entries of lidar_pose_index: 0 or 6 */
+    TC2LI_INERTIAL_WINDOW_N_POINTS_WITHOUT_EDGE = 8,   /* listed points that got no edge */
+    TC2LI_INERTIAL_WINDOW_N_VERTICES_UNDER_3_EDGES = 9,   /* vertices with mVisEdges < 3: the assert of :972-975, reported and not enforced */
+    TC2LI_INERTIAL_WINDOW_COUNTS = 10
+};
+#define TC2LI_INERTIAL_WINDOW_MAX_LIDAR 6    /* N1 of :712 */
+#define TC2LI_INERTIAL_WINDOW_MAX_OPT 25     /* maxOpt of :497 */
+#define TC2LI_INERTIAL_WINDOW_MAX_FIXED 200  /* maxFixKF of :586 */
+/* One call of the gather for one current keyframe.  All pointers are host memory, the arrays are copied by the call; indices are rows of the
+ * problem's own tables; problems of one batch are independent.  The row order of the keyframes stands in for the address order of the
+ * reference's std::map<KeyFrame*, ...>, as in tc2li_ba_window_problem.
+ *   keyframes (n_keyframes rows: the current keyframe, its chain of predecessors, every observer of their points):
+ *     kf_slot   the slot of the keyframe in the store (the host entry: the index into views)
+ *     kf_id     mnId
+ *     kf_flags  bit 0 isBad(), bit 1 GetMap() != pCurrentMap, bit 2 bImu, bit 3 mpImuPreintegrated != NULL
+ *     prev_kf   the row of mPrevKF, -1 = NULL
+ *     states    [n_keyframes] what the optimiser takes of a keyframe; read only for the rows that get a vertex
+ *     slot_offsets [n_keyframes + 1], slot_point: GetMapPointMatches() per keyframe as a CSR, -1 = NULL.  Only the rows of the window
+ *     keyframes are read; others may be empty.
+ *   points (n_points rows): point_flags bit 0 isBad() (no other bit is read: :532 has no map test); positions [n_points][3] GetWorldPos()
+ *     widened; CSR obs_offsets [n_points + 1], obs_kf, obs_index: GetObservations(), a row ascending strictly by keyframe row, obs_index =
+ *     get<0> of the tuple (the left keypoint, or -1)
+ *   current: the row of pKF;  keyframes_in_map: pCurrentMap->KeyFramesInMap();  large, rec_init: bLarge, bRecInit;  with_lidar: non-zero =
+ *     LocalLVIBA, 0 = LocalInertialBA
+ * Out (capacities are the caller's; an array whose capacity is 0 may be NULL):
+ *   counts [TC2LI_INERTIAL_WINDOW_COUNTS]: always written.  EMPTY: N_FIXED_KF is 1, every later count is 0 and NO OTHER OUTPUT IS WRITTEN.
+ *   kf_row, keyframes_out, fixed, has_imu [kf_capacity]: the optimisable keyframes and the fixed ones ascending by kf_id (by row among equal
+ *     ids) -- the vertex-id order tc2li_local_inertial_bundle_adjustment asks for; has_imu = bit 2 of kf_flags
+ *   point_row [point_capacity], points3_out [point_capacity][3]: lLocalMapPoints in the reference's order
+ *   edges [edge_capacity]: one per observation in creation order; point / pose index the two lists above
+ *   links, link_kf2_row [link_capacity]: the inertial links in the order of :734 (the current keyframe's first); kf1 / kf2 index the vertex
+ *     list, preintegrated is NULL: the caller sets it to the mpImuPreintegrated of row link_kf2_row[i], after
+ *     SetNewBias(mPrevKF->GetImuBias()) (:745)
+ *   lidar_pose_index [TC2LI_INERTIAL_WINDOW_MAX_LIDAR]: the vertices of vpOptimizableKFs[0 .. n_lidar), -1 beyond */
+typedef struct tc2li_inertial_window_problem {
+    const int32_t* kf_slot;
+    const int64_t* kf_id;
+    const uint8_t* kf_flags;
+    const int32_t* prev_kf;
+    const tc2li_inertial_keyframe* states;
+    const int32_t* slot_offsets;
+    const int32_t* slot_point;
+    const uint8_t* point_flags;
+    const double* positions;
+    const int32_t* obs_offsets;
+    const int32_t* obs_kf;
+    const int32_t* obs_index;
+    int32_t* counts;
+    int32_t* kf_row;
+    tc2li_inertial_keyframe* keyframes_out;
+    uint8_t* fixed;
+    uint8_t* has_imu;
+    int32_t* point_row;
+    double* points3_out;
+    tc2li_ba_edge* edges;
+    tc2li_inertial_link* links;
+    int32_t* link_kf2_row;
+    int32_t* lidar_pose_index;
+    int32_t n_keyframes, n_points, current, keyframes_in_map;
+    int32_t large, rec_init, with_lidar;
+    int32_t kf_capacity, point_capacity, edge_capacity, link_capacity;
+    int32_t pad_;
+} tc2li_inertial_window_problem;
+/* The gather for n_problems current keyframes at once on the device.  Line for line:
+ *   temporal window (:493-519): Nd = min(keyframes_in_map - 2, large ? 25 : 10).  The current keyframe is taken whatever Nd is (:508), then
+ *   mPrevKF is followed while i < Nd and a predecessor exists.  No flag of any keyframe is tested.
+ *   points (:524-539): the window keyframes in list order, their slots ascending; a point that is not NULL and not bad is listed at its
+ *   first occurrence.  A point of another map IS listed.
+ *   fixed keyframe (:542-554): the predecessor of the last window keyframe, whatever its flags; without one, the last window keyframe
+ *   itself leaves the window (its points stay listed) and is the first fixed keyframe.  A window of one such keyframe is EMPTY.
+ *   fixed observers (:586-607), a sequential rule: for the listed points in order, the observers ascending by row; the first observer that
+ *   carries neither the local nor the fixed mark gets the fixed mark WHETHER IT IS BAD OR NOT; if it is not bad it joins the fixed keyframes
+ *   and the point is done, if it is bad the point's next observer is looked at.  No map test.  After every point the walk stops if the
+ *   fixed keyframes are 200 or more, the one of :542-554 included.  A bad keyframe with the mark passes :862 and is dropped by :865: no
+ *   vertex, no edge.
+ *   vertices (:632-696): the window keyframes (free) and the fixed keyframes (fixed); setId(mnId) is what orders them.
+ *   LiDAR keyframes (:699-727, with_lidar only): N > 5: vpOptimizableKFs[0 .. 6) BY POSITION; vLiDAROptKeyFrames (those with a surface
+ *   cloud) is computed and never used, so no cloud bit is read.  Otherwise none.
+ *   links (:734-800): for window keyframe i with a predecessor, bit 2 of both and bit 3 of its own: kf1 = the predecessor's vertex, kf2 =
+ *   its own, robust = (i == N-1) || rec_init, info_scale = 1e-2 for i == N-1, else 1.  The lookups of :746-759 cannot fail: the predecessor
+ *   of window keyframe i < N-1 is window keyframe i+1, and the predecessor of the last one is the fixed keyframe of :542-554 in either arm;
+ *   both have a vertex, and the velocity / bias vertices exist where bit 2 is set (:643, :681), which the link already requires.
+ *   edges (:845-969): the listed points in order, the observers ascending by row; an observer needs one of the two marks (:862) and must be
+ *   neither bad nor of another map (:865); obs_index -1 makes no edge; u_right < 0 a monocular edge, else stereo; inv_sigma2 =
+ *   inv_level_sigma2[octave] (Pinhole::uncertainty2 is 1.0f).  mVisEdges is kept per row, not per mnId.
+ * Marks and first-occurrence keys live in LDS up to the sizes tc2li_inertial_window_limits reports, in global memory beyond.  Two kernel
+ * launches, one upload and one download for the whole batch; the results are in host memory when the call returns (stream: NULL = the
+ * calling thread's private stream).  TC2LI_ERR_INVALID before any launch for negative sizes or capacities, NULL required pointers,
+ * offsets that do not ascend from 0, indices out of range (current, prev_kf below -1 or >= n_keyframes, slot_point below -1, obs_kf,
+ * obs_index below -1 or beyond the keypoints of the observer's slot), observation rows that do not ascend strictly, a kf_slot that is
+ * empty or out of range, a slot that holds an octave outside [0, n_levels), and a prev_kf chain that, within the window and the one
+ * predecessor behind it, returns to a keyframe already in the window.  TC2LI_ERR_CAPACITY when a list of some problem does not fit: then
+ * counts is written for every problem, with the sizes needed, and no list for any.  Returns n_problems; 0 for an empty batch. */
+int tc2li_inertial_window_batch(tc2li_keyframe_store* store, const tc2li_inertial_window_problem* problems, int n_problems,
+                                const float* inv_level_sigma2, int n_levels, void* stream);
+/* The same contract as plain sequential C++ with the reference's mark fields (one problem per worker thread).  kf_slot indexes views
+ * [n_views], of which n, keys and u_right are read (n < 0: an empty slot).  Needs no device. */
+int tc2li_host_inertial_window_batch(const tc2li_keyframe_view* views, int n_views, const tc2li_inertial_window_problem* problems,
+                                     int n_problems, const float* inv_level_sigma2, int n_levels);
+/* The sizes at which tc2li_inertial_window_batch changes path (for tests): out[0] = the largest n_keyframes whose marks are kept in LDS
+ * (beyond: in global memory), out[1] = the largest n_points whose first-occurrence keys are kept in LDS (beyond: in global memory),
+ * out[2] = threads per problem.  Returns 3.  Needs no device.  No reference counterpart. */
+int tc2li_inertial_window_limits(int32_t* out, int capacity);
+/* The outlier rule after the BA (:985-1045), host only: vToErase as (pose index, point index) pairs in the reference's order.  The
+ * rejection of :1028 comes first: *rejected = (2 * err < err_end || isnan(err) || isnan(err_end)) && !large with err / err_end =
+ * (float)initial_chi2 / (float)final_chi2; a rejected window returns 0 pairs (the reference returns before any erasure and any write-back).
+ * Otherwise the monocular edges (u_right < 0) in creation order, erased if (chi2 > chi2Mono2 && !close) || (chi2 > 1.5f * chi2Mono2 &&
+ * close) || !depthPositive with close = track_depth[point] < 10.f (:994-999), then the stereo edges, erased if chi2 > chi2Stereo2 alone --
+ * no depth test (:1016).  The thresholds are the reference's float variables widened: (double)5.991f, (double)(1.5f * 5.991f),
+ * (double)7.815f.  Edges of a point with point_bad_now are skipped.  track_depth [n_points] = pMP->mTrackDepth.  Returns the count;
+ * TC2LI_ERR_CAPACITY (nothing written but *rejected) when it exceeds capacity, TC2LI_ERR_INVALID for an edge whose point is outside
+ * [0, n_points). */
+int tc2li_inertial_window_outliers(const tc2li_ba_edge* edges, const double* edge_chi2, const uint8_t* edge_depth_positive, int n_edges,
+                                   const uint8_t* point_bad_now, const float* track_depth, int n_points, double initial_chi2,
+                                   double final_chi2, int large, int32_t* rejected, int32_t* erase_pose, int32_t* erase_point, int capacity);
 
 /* ---- tracking: stereo map points and the keyframe decision (SF/src/Tracking.cc:2942-3076 NeedNewKeyFrame, :3078-3212 CreateNewKeyFrame,
  * :2676-2734 UpdateLastFrame, :2477-2495 StereoInitialization) ----------------------------------------------------------------------------

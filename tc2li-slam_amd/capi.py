@@ -3008,3 +3008,129 @@ def ba_window_outliers(edges, edge_chi2, edge_depth_positive, point_bad_now, cap
     f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     n = _check(f(e.ctypes.data, chi2.ctypes.data, dpos.ctypes.data, len(e), bad.ctypes.data, len(bad), pose.ctypes.data, point.ctypes.data, cap))
     return np.stack([pose[:n], point[:n]], 1)
+
+
+class InertialWindowProblem(C.Structure):
+    """tc2li_inertial_window_problem"""
+    _fields_ = [(k, C.c_void_p) for k in ("kf_slot", "kf_id", "kf_flags", "prev_kf", "states", "slot_offsets", "slot_point", "point_flags", "positions",
+                                          "obs_offsets", "obs_kf", "obs_index", "counts", "kf_row", "keyframes_out", "fixed", "has_imu", "point_row",
+                                          "points3_out", "edges", "links", "link_kf2_row", "lidar_pose_index")] \
+        + [(k, C.c_int32) for k in ("n_keyframes", "n_points", "current", "keyframes_in_map", "large", "rec_init", "with_lidar", "kf_capacity",
+                                    "point_capacity", "edge_capacity", "link_capacity", "pad_")]
+
+
+INERTIAL_WINDOW_OK, INERTIAL_WINDOW_EMPTY, INERTIAL_WINDOW_MAX_LIDAR, INERTIAL_WINDOW_MAX_OPT = 0, 1, 6, 25
+INERTIAL_LINK_DTYPE = np.dtype([("kf1", "<i4"), ("kf2", "<i4"), ("robust", "<i4"), ("pad_", "<i4"), ("info_scale", "<f8"), ("preintegrated", "<u8")])
+_INERTIAL_WINDOW_ARRAYS = (("kf_slot", np.int32), ("kf_id", np.int64), ("kf_flags", np.uint8), ("prev_kf", np.int32), ("states", np.float64),
+                           ("slot_offsets", np.int32), ("slot_point", np.int32), ("point_flags", np.uint8), ("positions", np.float64),
+                           ("obs_offsets", np.int32), ("obs_kf", np.int32), ("obs_index", np.int32))
+_INERTIAL_WINDOW_COUNTS = ("status", "n_fixed_kf", "n_opt_kf", "n_vertices", "n_points", "n_edges", "n_links", "n_lidar", "n_points_without_edge",
+                           "n_vertices_under_3_edges")
+
+
+def inertial_window_limits():
+    """tc2li_inertial_window_limits -> {lds_keyframes, lds_points, threads}: the sizes at which the device path of inertial_window_batch
+    changes (the keyframe marks leave LDS above lds_keyframes keyframes, the first-occurrence keys above lds_points points)."""
+    out = (C.c_int32 * 3)()
+    f = lib().tc2li_inertial_window_limits
+    f.argtypes = [C.c_void_p, C.c_int]
+    _check(f(out, 3))
+    return dict(zip(("lds_keyframes", "lds_points", "threads"), [int(v) for v in out]))
+
+
+def pack_inertial_window_problems(problems, fill=0):
+    """The tc2li_inertial_window_problem array of a batch with its output arrays (prefilled with `fill`) -> (array, outputs per problem, what
+    must stay alive).  Capacities: kf_capacity / point_capacity / edge_capacity / link_capacity of the problem's dict, by default what can
+    never be too small (the keyframes, the points, the observations, 25)."""
+    arr, outs, keep = (InertialWindowProblem * max(len(problems), 1))(), [], []
+    for i, p in enumerate(problems):
+        a = {k: np.ascontiguousarray(p[k], t).reshape(-1) for k, t in _INERTIAL_WINDOW_ARRAYS}
+        nk, npts = len(a["kf_slot"]), len(a["point_flags"])
+        if len(a["kf_id"]) != nk or len(a["kf_flags"]) != nk or len(a["prev_kf"]) != nk or len(a["states"]) != 33 * nk or len(a["slot_offsets"]) != nk + 1:
+            raise ValueError("problem %d: the keyframe arrays do not have one row per keyframe" % i)
+        if len(a["positions"]) != 3 * npts or len(a["obs_offsets"]) != npts + 1:
+            raise ValueError("problem %d: the point arrays do not have one row per point" % i)
+        ns, no = int(a["slot_offsets"][-1]), int(a["obs_offsets"][-1])
+        if len(a["slot_point"]) < ns or min(len(a["obs_kf"]), len(a["obs_index"])) < no:
+            raise ValueError("problem %d: slot or observation arrays are shorter than their offsets say" % i)
+        kc, tc, ec, lc = (int(p.get(k, d)) for k, d in (("kf_capacity", nk), ("point_capacity", npts), ("edge_capacity", no),
+                                                        ("link_capacity", INERTIAL_WINDOW_MAX_OPT)))
+        full = lambda n, t: np.full(max(n, 0), fill, np.int64).astype(t)
+        edges, links = np.zeros(max(ec, 0), BA_EDGE_DTYPE), np.zeros(max(lc, 0), INERTIAL_LINK_DTYPE)
+        edges.view(np.uint8)[:] = fill & 0xff
+        links.view(np.uint8)[:] = fill & 0xff
+        o = dict(counts=full(len(_INERTIAL_WINDOW_COUNTS), np.int32), kf_row=full(kc, np.int32), keyframes_out=full(33 * kc, np.float64),
+                 fixed=full(kc, np.uint8), has_imu=full(kc, np.uint8), point_row=full(tc, np.int32), points3_out=full(3 * tc, np.float64), edges=edges,
+                 links=links, link_kf2_row=full(lc, np.int32), lidar_pose_index=full(INERTIAL_WINDOW_MAX_LIDAR, np.int32))
+        for k, v in list(a.items()) + list(o.items()):
+            setattr(arr[i], k, v.ctypes.data)
+        arr[i].n_keyframes, arr[i].n_points, arr[i].current, arr[i].keyframes_in_map = nk, npts, int(p["current"]), int(p["keyframes_in_map"])
+        arr[i].large, arr[i].rec_init, arr[i].with_lidar = int(bool(p.get("large", 0))), int(bool(p.get("rec_init", 0))), int(bool(p.get("with_lidar", 0)))
+        arr[i].kf_capacity, arr[i].point_capacity, arr[i].edge_capacity, arr[i].link_capacity = kc, tc, ec, lc
+        keep.append(a)
+        outs.append(o)
+    return arr, outs, keep
+
+
+def inertial_window_batch(problems, inv_level_sigma2, store=None, views=None, stream=0, raw=False, fill=0):
+    """The gather of ``OptimizerWithLidar::LocalLVIBA`` / ``Optimizer::LocalInertialBA`` (the window of the inertial local BA), one per
+    problem.  problems: dicts with the arrays of tc2li_inertial_window_problem (kf_slot, kf_id, kf_flags, prev_kf, states [n, 33],
+    slot_offsets, slot_point, point_flags, positions, obs_offsets, obs_kf, obs_index), current, keyframes_in_map and optionally large,
+    rec_init, with_lidar and the four capacities.  store: a :class:`KeyframeStore` -- the device entry; views: per slot None or a dict with
+    keys and u_right -- the host entry.  -> one dict per problem: status, n_fixed_kf, n_opt_kf, n_lidar, n_points_without_edge,
+    n_vertices_under_3_edges, kf_row, kf33 [n, 33], fixed, has_imu, point_row, points3 [n, 3], edges (BA_EDGE_DTYPE), link4 [n, 4] = kf1,
+    kf2, robust, info_scale as local_inertial_bundle_adjustment takes them, link_kf2_row, lidar_pose_index [n_lidar], cut to their counts.
+    raw=True: the arrays at their full capacity as the library left them (prefilled with `fill`) and counts."""
+    if (store is None) == (views is None):
+        raise ValueError("either a store (the device entry) or views (the host entry)")
+    arr, outs, keep = pack_inertial_window_problems(problems, fill)
+    sg = np.ascontiguousarray(inv_level_sigma2, np.float32).reshape(-1)
+    if views is not None:
+        varr, vkeep = _pack_ba_window_views(views)
+        f = lib().tc2li_host_inertial_window_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        _check(f(C.addressof(varr), len(views), C.addressof(arr), len(problems), sg.ctypes.data, len(sg)))
+        del vkeep
+    else:
+        f = lib().tc2li_inertial_window_batch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        _check(f(store._handle(), C.addressof(arr), len(problems), sg.ctypes.data, len(sg), C.c_void_p(stream)))
+    del keep
+    if raw:
+        return outs
+    res = []
+    for o in outs:
+        c = dict(zip(_INERTIAL_WINDOW_COUNTS, [int(v) for v in o["counts"]]))
+        r = {k: c[k] for k in ("status", "n_fixed_kf", "n_opt_kf", "n_lidar", "n_points_without_edge", "n_vertices_under_3_edges")}
+        nv, nl = c["n_vertices"], c["n_links"]
+        lk = o["links"][:nl]
+        r.update(kf_row=o["kf_row"][:nv], kf33=o["keyframes_out"].reshape(-1, 33)[:nv], fixed=o["fixed"][:nv], has_imu=o["has_imu"][:nv],
+                 point_row=o["point_row"][:c["n_points"]], points3=o["points3_out"].reshape(-1, 3)[:c["n_points"]], edges=o["edges"][:c["n_edges"]],
+                 link4=np.stack([lk["kf1"], lk["kf2"], lk["robust"], lk["info_scale"]], 1).astype(np.float64).reshape(-1, 4),
+                 link_null=bool((lk["preintegrated"] == 0).all() and (lk["pad_"] == 0).all()), link_kf2_row=o["link_kf2_row"][:nl],
+                 lidar_pose_index=o["lidar_pose_index"][:c["n_lidar"]])
+        res.append(r)
+    return res
+
+
+def inertial_window_outliers(edges, edge_chi2, edge_depth_positive, point_bad_now, track_depth, initial_chi2, final_chi2, large=False,
+                             capacity=None):
+    """tc2li_inertial_window_outliers: -> (vToErase of the inertial local BA as (pose index, point index) pairs [n, 2] in the reference's
+    order, rejected).  rejected: the test of ``FAIL LOCAL-INERTIAL BA`` on float(initial_chi2) / float(final_chi2) and large; then no pairs.
+    Monocular edges go by 5.991f, or 1.5f * 5.991f for points with track_depth < 10, or a negative depth; stereo edges by 7.815f alone."""
+    e = np.ascontiguousarray(edges, BA_EDGE_DTYPE)
+    chi2, dpos = np.ascontiguousarray(edge_chi2, np.float64).reshape(-1), np.ascontiguousarray(edge_depth_positive, np.uint8).reshape(-1)
+    bad, depth = np.ascontiguousarray(point_bad_now, np.uint8).reshape(-1), np.ascontiguousarray(track_depth, np.float32).reshape(-1)
+    if min(len(chi2), len(dpos)) < len(e):
+        raise ValueError("one chi2 and one depth flag per edge")
+    if len(depth) != len(bad):
+        raise ValueError("one track_depth per point")
+    cap = len(e) if capacity is None else int(capacity)
+    pose, point = np.full(max(cap, 0), -1, np.int32), np.full(max(cap, 0), -1, np.int32)
+    rejected = C.c_int32(0)
+    f = lib().tc2li_inertial_window_outliers
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_int]
+    n = _check(f(e.ctypes.data, chi2.ctypes.data, dpos.ctypes.data, len(e), bad.ctypes.data, depth.ctypes.data, len(bad), float(initial_chi2),
+                 float(final_chi2), int(bool(large)), C.addressof(rejected), pose.ctypes.data, point.ctypes.data, cap))
+    return np.stack([pose[:n], point[:n]], 1), bool(rejected.value)
