@@ -1784,6 +1784,142 @@ int tc2li_ba_window_limits(int32_t* out, int capacity);
 int tc2li_ba_window_outliers(const tc2li_ba_edge* edges, const double* edge_chi2, const uint8_t* edge_depth_positive, int n_edges,
                              const uint8_t* point_bad_now, int n_points, int32_t* erase_pose, int32_t* erase_point, int capacity);
 
+/* ---- local mapping: the optimiser's index structure of a window (no reference counterpart: g2o builds its own containers) ----------------
+ * What tc2li_local_bundle_adjustment builds from (fixed, edges) before its first kernel: the numbering of the free poses, the edges by
+ * landmark and by free pose, one slot per (landmark, free pose) pair in landmark-major order, the slices of the Schur product, duplicate
+ * pairs, the blocks of 256 slots sorted by pose, the groups of the linearisation, and the sizes that follow
+ * (tc2li-slam_amd/csrc/ba_structure.hpp:69-229 ba_build_structure, :39-65 the sizes of the Schur product, :231-264 the layout of the
+ * window's input block from the sizes alone; VisualProblem::setup, csrc/ba_internal.hpp:230-285, calls them).  The arrays come back in one
+ * int32 buffer; table [TC2LI_BA_STRUCTURE_FIELDS][2] holds (offset, count) of every field in it. */
+enum tc2li_ba_structure_field {
+    TC2LI_BA_STRUCTURE_SCALARS = 0,   /* [TC2LI_BA_STRUCTURE_SCALAR_COUNT], see tc2li_ba_structure_scalar */
+    TC2LI_BA_STRUCTURE_POSE_VAR,      /* [n_poses] the number of a free pose that is used by an edge (or extra_used), -1 otherwise */
+    TC2LI_BA_STRUCTURE_PT_OFF,        /* [n_points + 1] CSR of the edges by point */
+    TC2LI_BA_STRUCTURE_PT_EDGES,      /* [n_edges] */
+    TC2LI_BA_STRUCTURE_PV_OFF,        /* [n_free + 1] CSR of the edges with a slot by free pose */
+    TC2LI_BA_STRUCTURE_PV_EDGES,      /* [pv_off[n_free]] */
+    TC2LI_BA_STRUCTURE_FL_OFF,        /* [2 * n_points] begin, end of a point's slots */
+    TC2LI_BA_STRUCTURE_FL_POSE,       /* [n_slots] the slot's free pose */
+    TC2LI_BA_STRUCTURE_FL_LM,         /* [n_slots] its point */
+    TC2LI_BA_STRUCTURE_FL_PLACE,      /* [n_slots] the point's number within its slice */
+    TC2LI_BA_STRUCTURE_FL_EDGE,       /* [n_slots] its edge */
+    TC2LI_BA_STRUCTURE_W_SLOT,        /* [n_edges] the edge's slot, -1: a fixed pose or a duplicate */
+    TC2LI_BA_STRUCTURE_SLICE_OFF,     /* [n_schur_slices + 1] first slot of every slice */
+    TC2LI_BA_STRUCTURE_DUP_OFF,       /* [n_free + 1] CSR of the duplicates by free pose (all 0 without duplicates) */
+    TC2LI_BA_STRUCTURE_DUP_EDGE,      /* [n_dups] */
+    TC2LI_BA_STRUCTURE_DUP_SLOT,      /* [n_dups] the slot of the pair's first edge */
+    TC2LI_BA_STRUCTURE_BLK_OFF,       /* [max(n_blocks, 1)][n_free + 1] per block of 256 slots: CSR of its rows by pose */
+    TC2LI_BA_STRUCTURE_BLK_ROWS,      /* [max(n_blocks, 1)][256] the block's slots (0 .. 255) sorted by pose, stable; bytes widened to int32 */
+    TC2LI_BA_STRUCTURE_GRP_K0,        /* [n_groups + 1] first edge (in pt_edges order) of every group */
+    TC2LI_BA_STRUCTURE_GRP_L0,        /* [n_groups + 1] first point of every group */
+    TC2LI_BA_STRUCTURE_CHUNK_MASK,    /* dense windows only: [max(n_schur_slices, 1)] the 16-column tiles a chunk touches */
+    TC2LI_BA_STRUCTURE_FIELDS
+};
+enum tc2li_ba_structure_scalar {
+    TC2LI_BA_STRUCTURE_N_FREE = 0,
+    TC2LI_BA_STRUCTURE_N_SLOTS,              /* n_free_edges after the slots are made */
+    TC2LI_BA_STRUCTURE_N_FREE_POSE_EDGES,    /* edges with a free pose, duplicates counted */
+    TC2LI_BA_STRUCTURE_N_DUPS,
+    TC2LI_BA_STRUCTURE_N_BLOCKS,
+    TC2LI_BA_STRUCTURE_N_GROUPS,
+    TC2LI_BA_STRUCTURE_MAX_GROUP_LANDMARKS,
+    TC2LI_BA_STRUCTURE_NP,                   /* 6 * n_free */
+    TC2LI_BA_STRUCTURE_NP_PAD,
+    TC2LI_BA_STRUCTURE_N_SCHUR_SLICES,
+    TC2LI_BA_STRUCTURE_N_SLICES,             /* partial sums of the Schur product */
+    TC2LI_BA_STRUCTURE_K_PER_SLICE,
+    TC2LI_BA_STRUCTURE_SCHUR_GROUP,
+    TC2LI_BA_STRUCTURE_SPARSE,               /* 1: the lean block-by-block product (at most 24 free poses) */
+    TC2LI_BA_STRUCTURE_SCHUR_RD,
+    TC2LI_BA_STRUCTURE_SCHUR_RO,
+    TC2LI_BA_STRUCTURE_SCALAR_COUNT
+};
+/* Host only, needs no device.  fixed [n_poses], edges [n_edges] (point, pose and nothing else is read), extra_used [n_poses] or NULL: poses
+ * that count as used without an edge (the keyframes of the LiDAR edge).  table [TC2LI_BA_STRUCTURE_FIELDS][2] and out [capacity] are
+ * written; out == NULL with capacity 0 is a sizing call that writes the table alone.  Returns the number of int32 the fields take;
+ * TC2LI_ERR_CAPACITY when that exceeds a non-zero capacity (the table is written); TC2LI_ERR_INVALID, as tc2li_local_bundle_adjustment
+ * would, for an edge whose pose or point is out of range, a point without an edge, a point with more than 256 edges, more than 256 points
+ * in a group, more than 85 free poses. */
+int tc2li_host_ba_structure(const uint8_t* fixed, int n_poses, int n_points, const tc2li_ba_edge* edges, int n_edges, const uint8_t* extra_used,
+                            int32_t* table, int32_t* out, int capacity);
+/* The gather of tc2li_ba_window_batch followed by the structure of every window, built ON THE DEVICE from the gather's device output: the
+ * front half of the hand-over of a window to the BA without a trip over the bus.  Per window the kernels write the arrays and a size
+ * record; the host reads the records, lays out the window's input block -- [poses | points | edges | pose_var | pt_off | pt_edges | pv_off
+ * | fl_off | fl_pose | fl_lm | fl_place | slice_off | fl_edge | grp_k0 | grp_l0 | blk_off | blk_rows | ticket words], what the BA's kernels
+ * read -- and the pieces are moved there device to device.  This entry then downloads the blocks and returns them in the flat form of
+ * tc2li_host_ba_structure, for tests and tools: tables [n_problems][TC2LI_BA_STRUCTURE_FIELDS][2], out [n_problems][out_stride].  The fields
+ * a sparse window's block does not hold (pv_edges, w_slot, dup_*, chunk_mask) have count 0; every other field equals
+ * tc2li_host_ba_structure of the gathered window, integer for integer.  with_lidar [n_problems] or NULL (= all 1): whether the window's
+ * keyframes of lidar_pose_index count as used (extra_used), as they do when the window gets the LiDAR edge.
+ * The problems are those of tc2li_ba_window_batch, and their outputs are written as it writes them (so is its TC2LI_ERR_CAPACITY).
+ * results [n_problems]: the int32 written to the window's row of out; 0 for an ABORTED window; TC2LI_ERR_INVALID for what
+ * tc2li_local_bundle_adjustment refuses (a listed point without an edge, a point with more than 256 edges, more than 256 points in a
+ * group), decided on the device; TC2LI_BA_STRUCTURE_DECLINED for a window outside the device range (tc2li_ba_window_solve_limits).  Returns
+ * n_problems; TC2LI_ERR_CAPACITY when out_stride is too small for some window (results then holds the sizes needed). */
+#define TC2LI_BA_STRUCTURE_DECLINED (-1000)
+int tc2li_ba_window_structure_batch(tc2li_keyframe_store* store, const tc2li_ba_window_problem* problems, int n_problems,
+                                    const float* inv_level_sigma2, int n_levels, const uint8_t* with_lidar, int32_t* tables, int32_t* out,
+                                    int out_stride, int32_t* results, void* stream);
+/* The range in which a window's structure is built on the device: out[0] = the most free poses (the lean sparse path of the BA), out[1] =
+ * the most poses, out[2] = the most points (both live in LDS), out[3] = threads per window.  Returns 4.  Needs no device. */
+int tc2li_ba_window_solve_limits(int32_t* out, int capacity);
+
+/* ---- local mapping: gather, local BA and outlier rule of LocalBundleAdjustment / LocalLVBundleAdjustment in one call
+ * (SF/src/OptimizerWithLidar.cc:63-130 the gather, :157-384 the graph, :386-400 the optimisation, :402-449 the outlier rule) ---------------
+ * What tc2li_ba_window_batch, tc2li_local_bundle_adjustment_batch_group and tc2li_ba_window_outliers do one after the other, without the
+ * window's points, edges and index structure crossing the bus in between: the gather's output stays on the device, the structure is built
+ * there (tc2li_ba_window_structure_batch above; csrc/ba_structure_kernels.hip), the lock-step batch adopts the windows' input blocks device
+ * to device (VisualProblem::adopt, csrc/ba_internal.hpp:290-320, in place of setup's host structure and upload), and the outlier rule
+ * runs on the device after the last iteration.  Downloaded: the counts, the lists of poses and points, the optimised poses and points, the
+ * outlier pairs (and the edges, chi2 and depth flags a problem asks for).  Uploaded: the flat graph.
+ *   window: a problem of tc2li_ba_window_batch.  Its inputs as there; edges may be NULL (with any edge_capacity): the window's edges are then
+ *     never downloaded.  counts, pose_row, fixed, point_row and lidar_pose_index are written as the gather writes them; poses7_out and
+ *     points3_out receive the OPTIMISED values.
+ *   iterations, lambda_init, stop_flag, stats, edge_chi2, edge_depth_positive [edge_out_capacity]: the arguments of
+ *     tc2li_local_bundle_adjustment; the two arrays may be NULL.
+ *   The LiDAR edge: cloud_xyz == NULL means none.  Otherwise cloud_offsets [n_keyframes + 1] (in points) and cloud_xyz give GetSurfacePcl() of
+ *     every keyframe ROW of the window's tables, back to back (rows without bit 2 of kf_flags may be empty), Tcl and weight as in
+ *     tc2li_lidar_window; the window of n_lidar keyframes is put together from lidar_pose_index (n_lidar == 0: no LiDAR edge) and goes
+ *     through the plane extraction with the gathered poses.  lidar_stats as in tc2li_local_lv_bundle_adjustment (may be NULL).
+ *   erase_pose, erase_point [erase_capacity], n_erase: vToErase of :402-449 as (pose index, point index) pairs in the reference's order,
+ *     what tc2li_ba_window_outliers gives with no point bad (the caller applies pMP->isBad(): the test skips single pairs, so the order of
+ *     the others stands).  n_erase may be NULL: the rule is then not evaluated. */
+typedef struct tc2li_ba_window_solve_problem {
+    tc2li_ba_window_problem window;
+    const volatile uint8_t* stop_flag;
+    tc2li_ba_stats* stats;
+    double* edge_chi2;
+    uint8_t* edge_depth_positive;
+    const int32_t* cloud_offsets;
+    const float* cloud_xyz;
+    tc2li_lidar_ba_stats* lidar_stats;
+    int32_t* erase_pose;
+    int32_t* erase_point;
+    int32_t* n_erase;
+    double lambda_init, weight;
+    float Tcl[7];
+    int32_t iterations, edge_out_capacity, erase_capacity;
+} tc2li_ba_window_solve_problem;
+/* One lock-step group on context `group` (0 .. 7), like tc2li_local_bundle_adjustment_batch_group.  results [n_problems]:
+ *   a window that was optimised: the iterations done, as the two-step path returns them, every output written;
+ *   an ABORTED window (:126-130): 0, counts alone written;
+ *   a window the BA refuses (a listed point without an edge, a point with more than 256 edges, more than 256 points in a group -- decided
+ *   on the device): TC2LI_ERR_INVALID, the lists as the gather leaves them, stats zeroed, n_erase 0.
+ * Every window's outputs are bit for bit those of tc2li_ba_window_batch followed by tc2li_local_bundle_adjustment_batch_group over the
+ * windows that are not ABORTED and by tc2li_ba_window_outliers: the device builds the same structure, and the structure fixes the order of
+ * every sum.  A window outside the device range (tc2li_ba_window_solve_limits: more than 24 free keyframes, 1024 poses or 6144 points), every
+ * window of a call in which at most one is not ABORTED, of a call with TC2LI_BA_NO_LOCKSTEP set, or of a call whose lock-step group declines
+ * (a LiDAR window with more than 2048 planes) is finished inside the call through tc2li_local_lv_bundle_adjustment and
+ * tc2li_ba_window_outliers: its edges are copied down for that, and the caller sees the same contract.
+ * TC2LI_ERR_CAPACITY for the whole call, with every counts written, nothing else written and no BA run, when a pose or point capacity, a
+ * non-NULL edges' edge_capacity, or the edge_out_capacity of a non-NULL edge_chi2 / edge_depth_positive is too small in any problem.  An
+ * erase_capacity that turns out too small is only known after the BA: the call then returns TC2LI_ERR_CAPACITY as well, every other output
+ * is written, n_erase holds the number of pairs and the first erase_capacity of them are in the arrays.  TC2LI_ERR_INVALID before any
+ * launch as tc2li_ba_window_batch, and for NULL cloud_offsets when cloud_xyz is given (a LiDAR keyframe with an empty cloud is refused
+ * for its window, as tc2li_local_lv_bundle_adjustment refuses it).  Returns n_problems. */
+int tc2li_ba_window_solve_batch(tc2li_keyframe_store* store, const tc2li_ba_window_solve_problem* problems, int n_problems,
+                                const float* inv_level_sigma2, int n_levels, const tc2li_camera* cam, int group, int32_t* results);
+
 /* ---- local mapping: the window of the inertial local BA (OptimizerWithLidar::LocalLVIBA, SF/src/OptimizerWithLidar.cc:489-607 the gather,
  * :632-727 the vertices and the keyframes of the LiDAR edge, :729-800 the inertial links, :832-969 the point vertices and edges, :985-1045
  * the outlier rule; the twin Optimizer::LocalInertialBA, SF/src/Optimizer.cc:1512-1631 and on) -------------------------------------------

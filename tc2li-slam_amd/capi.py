@@ -3010,6 +3010,164 @@ def ba_window_outliers(edges, edge_chi2, edge_depth_positive, point_bad_now, cap
     return np.stack([pose[:n], point[:n]], 1)
 
 
+BA_STRUCTURE_FIELDS = ("scalars", "pose_var", "pt_off", "pt_edges", "pv_off", "pv_edges", "fl_off", "fl_pose", "fl_lm", "fl_place", "fl_edge", "w_slot",
+                       "slice_off", "dup_off", "dup_edge", "dup_slot", "blk_off", "blk_rows", "grp_k0", "grp_l0", "chunk_mask")
+BA_STRUCTURE_SCALARS = ("n_free", "n_slots", "n_free_pose_edges", "n_dups", "n_blocks", "n_groups", "max_group_landmarks", "np", "np_pad",
+                        "n_schur_slices", "n_slices", "k_per_slice", "schur_group", "sparse", "schur_rd", "schur_ro")
+
+
+def unpack_ba_structure(table, out):
+    """The flat form of tc2li_host_ba_structure (table [fields][2], one int32 buffer) -> a dict: every scalar of BA_STRUCTURE_SCALARS as an
+    int, every other field of BA_STRUCTURE_FIELDS as an int32 array of its count."""
+    t = np.asarray(table, np.int32).reshape(len(BA_STRUCTURE_FIELDS), 2)
+    r = {k: np.array(out[t[i, 0]:t[i, 0] + t[i, 1]], np.int32) for i, k in enumerate(BA_STRUCTURE_FIELDS)}
+    r.update(zip(BA_STRUCTURE_SCALARS, [int(v) for v in r.pop("scalars")]))
+    return r
+
+
+def host_ba_structure(fixed, n_points, edges, extra_used=None):
+    """tc2li_host_ba_structure: the index structure the local BA builds from (fixed, edges) -- see unpack_ba_structure.  edges: BA_EDGE_DTYPE
+    (point and pose are read); extra_used [n_poses]: poses that count as used without an edge.  Needs no device."""
+    fx, e = np.ascontiguousarray(fixed, np.uint8).reshape(-1), np.ascontiguousarray(edges, BA_EDGE_DTYPE)
+    xu = None if extra_used is None else np.ascontiguousarray(extra_used, np.uint8).reshape(-1)
+    if xu is not None and len(xu) != len(fx):
+        raise ValueError("one extra_used flag per pose")
+    table = np.zeros((len(BA_STRUCTURE_FIELDS), 2), np.int32)
+    f = lib().tc2li_host_ba_structure
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    args = [fx.ctypes.data, len(fx), int(n_points), e.ctypes.data, len(e), None if xu is None else xu.ctypes.data, table.ctypes.data]
+    n = _check(f(*(args + [None, 0])))
+    out = np.full(max(n, 1), -7, np.int32)
+    assert _check(f(*(args + [out.ctypes.data, n]))) == n
+    return unpack_ba_structure(table, out)
+
+
+BA_STRUCTURE_DECLINED = -1000
+
+
+def ba_window_solve_limits():
+    """tc2li_ba_window_solve_limits -> {max_free, max_poses, max_points, threads}: the range in which a window's structure is built on the
+    device; a window beyond it is declined."""
+    out = (C.c_int32 * 4)()
+    f = lib().tc2li_ba_window_solve_limits
+    f.argtypes = [C.c_void_p, C.c_int]
+    _check(f(out, 4))
+    return dict(zip(("max_free", "max_poses", "max_points", "threads"), [int(v) for v in out]))
+
+
+def _cut_ba_window_outputs(o):
+    """The output arrays of one tc2li_ba_window_problem cut to their counts, as ba_window_batch returns them (edges: None stays None)
+    -> (the dict, the counts by name)."""
+    c = dict(zip(_BA_WINDOW_COUNTS, [int(v) for v in o["counts"]]))
+    r = {k: c[k] for k in ("status", "num_fixed_kf", "num_opt_kf", "n_lidar", "n_points_without_edge")}
+    r.update(pose_row=o["pose_row"][:c["n_poses"]], poses7=o["poses7_out"].reshape(-1, 7)[:c["n_poses"]], fixed=o["fixed"][:c["n_poses"]],
+             point_row=o["point_row"][:c["n_points"]], points3=o["points3_out"].reshape(-1, 3)[:c["n_points"]],
+             edges=None if o["edges"] is None else o["edges"][:c["n_edges"]], lidar_pose_index=o["lidar_pose_index"][:c["n_lidar"]])
+    return r, c
+
+
+def ba_window_structure_batch(problems, inv_level_sigma2, store, with_lidar=None, stream=0, out_stride=None):
+    """tc2li_ba_window_structure_batch: the gather of ba_window_batch on the device followed by the optimiser's index structure of every
+    window, built on the device from the gather's device output and read back from the windows' input blocks.  -> (the gather's results as
+    ba_window_batch returns them, per problem the structure as unpack_ba_structure returns it -- the fields a sparse window's block does not
+    hold are empty -- or the result code: 0 ABORTED, -2 refused as the BA would refuse it, BA_STRUCTURE_DECLINED outside the device range)."""
+    arr, outs, keep = pack_ba_window_problems(problems, 0)
+    sg = np.ascontiguousarray(inv_level_sigma2, np.float32).reshape(-1)
+    n = len(problems)
+    wl = None if with_lidar is None else np.ascontiguousarray(with_lidar, np.uint8).reshape(-1)
+    if wl is not None and len(wl) != n:
+        raise ValueError("one with_lidar flag per problem")
+    if out_stride is None:   # no structure is larger: every field is bounded by the tables of its problem
+        out_stride = max([len(BA_STRUCTURE_SCALARS) + 600 + 2 * arr[i].pose_capacity + 6 * arr[i].point_capacity + 8 * arr[i].edge_capacity for i in range(n)] + [1])
+    tables = np.zeros((max(n, 1), len(BA_STRUCTURE_FIELDS), 2), np.int32)
+    out, results = np.full((max(n, 1), out_stride), -7, np.int32), np.zeros(max(n, 1), np.int32)
+    f = lib().tc2li_ba_window_structure_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    _check(f(store._handle(), C.addressof(arr), n, sg.ctypes.data, len(sg), None if wl is None else wl.ctypes.data, tables.ctypes.data,
+             out.ctypes.data, out_stride, results.ctypes.data, C.c_void_p(stream)))
+    del keep
+    gathered = [_cut_ba_window_outputs(o)[0] for o in outs]
+    return gathered, [unpack_ba_structure(tables[i], out[i]) if results[i] > 0 else int(results[i]) for i in range(n)]
+
+
+class BaWindowSolveProblem(C.Structure):
+    """tc2li_ba_window_solve_problem"""
+    _fields_ = [("window", BaWindowProblem)] \
+        + [(k, C.c_void_p) for k in ("stop_flag", "stats", "edge_chi2", "edge_depth_positive", "cloud_offsets", "cloud_xyz", "lidar_stats", "erase_pose",
+                                     "erase_point", "n_erase")] \
+        + [("lambda_init", C.c_double), ("weight", C.c_double), ("Tcl", C.c_float * 7)] \
+        + [(k, C.c_int32) for k in ("iterations", "edge_out_capacity", "erase_capacity")]
+
+
+def pack_ba_window_solve_problems(problems, fill=0):
+    """The tc2li_ba_window_solve_problem array of a batch -> (array, outputs per problem, what must stay alive).  problems: the dicts of
+    pack_ba_window_problems plus, all optional: iterations (10), lambda_init (0), stop_flag (a uint8 array of one element), want_edges
+    (True; False passes edges = NULL), want_chi2 (True: edge_chi2 and edge_depth_positive are asked for), edge_out_capacity and
+    erase_capacity (the observations), clouds (per keyframe row None or [n, 3] points) with Tcl7 and weight (1)."""
+    warr, wouts, wkeep = pack_ba_window_problems(problems, fill)
+    n = len(problems)
+    arr, outs, keep = (BaWindowSolveProblem * max(n, 1))(), [], [wkeep]
+    stats, lstats = (BaStats * max(n, 1))(), (LidarBaStats * max(n, 1))()
+    keep += [stats, lstats]
+    for i, p in enumerate(problems):
+        q, o = arr[i], dict(wouts[i])
+        C.memmove(C.addressof(q.window), C.addressof(warr[i]), C.sizeof(BaWindowProblem))
+        n_obs = int(np.asarray(p["obs_offsets"]).reshape(-1)[-1])
+        if not p.get("want_edges", True):
+            q.window.edges = None
+            o["edges"] = None
+        ec, rc = int(p.get("edge_out_capacity", n_obs)), int(p.get("erase_capacity", n_obs))
+        full = lambda m, t: np.full(max(m, 0), fill, np.int64).astype(t)
+        o.update(erase_pose=full(rc, np.int32), erase_point=full(rc, np.int32), n_erase=full(1, np.int32), stats=stats[i], lidar_stats=lstats[i])
+        q.erase_pose, q.erase_point, q.n_erase, q.erase_capacity = o["erase_pose"].ctypes.data, o["erase_point"].ctypes.data, o["n_erase"].ctypes.data, rc
+        q.stats, q.lidar_stats = C.addressof(stats) + i * C.sizeof(BaStats), C.addressof(lstats) + i * C.sizeof(LidarBaStats)
+        q.edge_out_capacity = ec
+        if p.get("want_chi2", True):
+            o.update(edge_chi2=np.full(max(ec, 0), float(fill)), edge_depth_positive=full(ec, np.uint8))
+            q.edge_chi2, q.edge_depth_positive = o["edge_chi2"].ctypes.data, o["edge_depth_positive"].ctypes.data
+        else:
+            o.update(edge_chi2=None, edge_depth_positive=None)
+        q.iterations, q.lambda_init = int(p.get("iterations", 10)), float(p.get("lambda_init", 0.0))
+        if p.get("stop_flag") is not None:
+            q.stop_flag = p["stop_flag"].ctypes.data
+            keep.append(p["stop_flag"])
+        if p.get("clouds") is not None:
+            cl = [np.zeros((0, 3), np.float32) if c is None else np.asarray(c, np.float32).reshape(-1, 3) for c in p["clouds"]]
+            if len(cl) != q.window.n_keyframes:
+                raise ValueError("problem %d: one cloud (or None) per keyframe row" % i)
+            off = np.concatenate([[0], np.cumsum([len(c) for c in cl])]).astype(np.int32)
+            xyz = np.ascontiguousarray(np.concatenate(cl + [np.zeros((1, 3), np.float32)]), np.float32)
+            q.cloud_offsets, q.cloud_xyz, q.weight = off.ctypes.data, xyz.ctypes.data, float(p.get("weight", 1.0))
+            q.Tcl = (C.c_float * 7)(*[float(x) for x in p["Tcl7"]])
+            keep.append((off, xyz))
+        outs.append(o)
+    return arr, outs, keep
+
+
+def ba_window_solve_batch(problems, inv_level_sigma2, store, cam5, group=0, fill=0):
+    """tc2li_ba_window_solve_batch: gather, local BA and outlier rule of the windows in one call, the windows staying on the device in
+    between (problems: see pack_ba_window_solve_problems).  -> one dict per problem: result (iterations done, 0 ABORTED, -2 refused), the
+    gather's status / counts / pose_row / fixed / point_row / lidar_pose_index / edges (None unless asked for), the OPTIMISED poses7 and
+    points3, chi2 and depth_positive (None unless asked for), stats, lidar_stats, erase [n, 2] (pose, point) and n_erase."""
+    arr, outs, keep = pack_ba_window_solve_problems(problems, fill)
+    sg = np.ascontiguousarray(inv_level_sigma2, np.float32).reshape(-1)
+    cam = np.ascontiguousarray(cam5, np.float64)
+    n = len(problems)
+    results = np.zeros(max(n, 1), np.int32)
+    f = lib().tc2li_ba_window_solve_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    _check(f(store._handle(), C.addressof(arr), n, sg.ctypes.data, len(sg), cam.ctypes.data, int(group), results.ctypes.data))
+    res = []
+    for i, o in enumerate(outs):
+        r, c = _cut_ba_window_outputs(o)
+        ne, m = c["n_edges"], int(o["n_erase"][0])
+        r.update(result=int(results[i]), chi2=None if o["edge_chi2"] is None else o["edge_chi2"][:ne],
+                 depth_positive=None if o["edge_depth_positive"] is None else o["edge_depth_positive"][:ne], stats=o["stats"],
+                 lidar_stats=o["lidar_stats"], n_erase=m, erase=np.stack([o["erase_pose"][:m], o["erase_point"][:m]], 1), keep=keep)
+        res.append(r)
+    return res
+
+
 class InertialWindowProblem(C.Structure):
     """tc2li_inertial_window_problem"""
     _fields_ = [(k, C.c_void_p) for k in ("kf_slot", "kf_id", "kf_flags", "prev_kf", "states", "slot_offsets", "slot_point", "point_flags", "positions",

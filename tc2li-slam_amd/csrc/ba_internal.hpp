@@ -16,6 +16,8 @@
 #include <pthread.h>
 #include "common.hpp"
 #include "ba_device.hpp"
+#include "ba_structure.hpp"
+#include "ba_structure_device.hpp"
 #include "balm_host.hpp"
 #include "inertial_host.hpp"
 #include "reduced_solve.hpp"
@@ -132,6 +134,20 @@ struct BaWorkspace {
 // share device buffers
 inline BaWorkspace& ba_ws() { static thread_local BaWorkspace w; return w; }
 
+// A window whose structure the device built (tc2li_ba_window_solve_batch): its sizes, the downloaded numbering of the poses, and where the
+// pieces of its input block lie in device memory -- poses as poses7 rows (the layout of Se3), edges as tc2li_ba_edge (the layout of BaEdge).
+// After the BA the lock-step batch evaluates the outlier rule of OptimizerWithLidar.cc:402-449 for it on the device: erase_pose /
+// erase_point [erase_capacity] and n_erase are pinned host memory.
+struct BaPrepared {
+    BaStructureSizes sizes;
+    const int32_t* pose_var_host = nullptr;
+    const void *poses = nullptr, *points = nullptr, *edges = nullptr, *pose_var = nullptr, *pt_off = nullptr, *pt_edges = nullptr, *pv_off = nullptr,
+               *fl_off = nullptr, *fl_pose = nullptr, *fl_lm = nullptr, *fl_place = nullptr, *slice_off = nullptr, *fl_edge = nullptr, *grp_k0 = nullptr,
+               *grp_l0 = nullptr, *blk_off = nullptr, *blk_rows = nullptr;
+    int32_t *erase_pose = nullptr, *erase_point = nullptr, *n_erase = nullptr;
+    int32_t erase_capacity = 0;
+};
+
 // Structure and device state of the projection-edge part of a local BA (shared by the visual / LiDAR and the inertial
 // entry points): free-pose numbering, CSR of the edges by landmark and by free pose, workspace sizing, uploads, and the
 // BaProblemDev handed to the kernels.  poses7 == NULL: the caller uploads ImuPose states itself (inertial mode).
@@ -155,162 +171,10 @@ struct VisualProblem {
         pb.trial_fused = BaOptions::read().fuse_trial && np <= kBacksubMaxNp && pose_bytes <= (size_t)kTrialPoseBytes && max_group_landmarks <= 256 ? 1 : 0;
     }
 
-    int setup(BaWorkspace& ws, const double* poses7, const uint8_t* fixed, int n_poses, const double* points3, int n_points,
-              const tc2li_ba_edge* edges, int n_edges, const tc2li_camera* cam, const uint8_t* extra_used, hipStream_t st) {
-    // ---- structure: free-pose numbering, CSR by landmark and by free pose ----
-    pose_var.assign(n_poses, -1);
-    n_free = 0;
-    std::vector<uint8_t> used(n_poses, 0);
-    for (int e = 0; e < n_edges; ++e) {
-        if (edges[e].pose < 0 || edges[e].pose >= n_poses || edges[e].point < 0 || edges[e].point >= n_points) {
-            set_error("edge %d references pose %d / point %d out of range", e, edges[e].pose, edges[e].point);
-            return TC2LI_ERR_INVALID;
-        }
-        used[edges[e].pose] = 1;
-    }
-    for (int k = 0; k < n_poses; ++k) if (extra_used && extra_used[k]) used[k] = 1;
-    for (int k = 0; k < n_poses; ++k) if (!fixed[k] && used[k]) pose_var[k] = n_free++;
-    std::vector<int> pt_off(n_points + 1, 0), pt_edges(n_edges), pv_off(n_free + 1, 0);
-    for (int e = 0; e < n_edges; ++e) { pt_off[edges[e].point + 1]++; if (pose_var[edges[e].pose] >= 0) pv_off[pose_var[edges[e].pose] + 1]++; }
-    for (int l = 0; l < n_points; ++l) {
-        if (pt_off[l + 1] == 0) { set_error("point %d has no edge", l); return TC2LI_ERR_INVALID; }
-        pt_off[l + 1] += pt_off[l];
-    }
-    for (int i = 0; i < n_free; ++i) pv_off[i + 1] += pv_off[i];
-    int n_free_edges = pv_off[n_free];  // edges with a free pose; after the slots are made: the SLOTS (duplicates of a (point, pose) pair have none)
-    std::vector<int> pv_edges(std::max(n_free_edges, 1));
-    {
-        std::vector<int> fl(pt_off.begin(), pt_off.end() - 1), fp(pv_off.begin(), pv_off.end() - 1);
-        for (int e = 0; e < n_edges; ++e) {
-            pt_edges[fl[edges[e].point]++] = e;
-            const int i = pose_var[edges[e].pose];
-            if (i >= 0) pv_edges[fp[i]++] = e;
-        }
-    }
-    // the edges with a free pose in landmark-major order: where the W blocks live (the Schur product and the back substitution walk
-    // them by landmark)
-    // fl_off: per landmark [begin, end) of its slots, the landmarks in index order.  (Tried: slots in the order of the poses a landmark
-    // is seen from, so that a chunk of the Schur kernel spans a narrow band of poses and the product's empty tiles can be skipped -- the
-    // windows' covisibility is not banded enough for that, and the linearisation lost its locality: 64 -> 98 us.)
-    // Every window of at most kSchurLeanMaxFree (24) free keyframes runs the lean block-by-block Schur product (ba_device.hpp) -- up to
-    // kSchurBlocksMaxFree (21) with one workgroup per part, above with two (schur_ranges_wide); wider windows the block-sparse MFMA kernels.
-    const bool lean_wide = n_free > kSchurBlocksMaxFree && n_free <= kSchurLeanMaxFree;
-    const bool schur_lean = (6 * n_free + 1 + 15) / 16 <= 8 || lean_wide;
-    struct DupEdge { int pose, edge, slot; };
-    std::vector<DupEdge> dups;
-    std::vector<int> fl_off(2 * (size_t)n_points, 0), fl_pose(std::max(n_free_edges, 1)), fl_lm(std::max(n_free_edges, 1)), fl_place(std::max(n_free_edges, 1)),
-        fl_edge(std::max(n_free_edges, 1)), w_slot(n_edges, -1), slice_off(1, 0);
-    {
-        // slices of the sparse Schur kernel: whole landmarks, at most 256 edges (one per thread) of at most 64 landmarks; a function of
-        // the window alone, so that a window gives the same bits alone and in a batch
-        // (the lean form of the block-by-block product stages half as many slots at a time: kSchurLeanSlots)
-        // Dense windows (more than 21 free keyframes -- the temporal window of LocalInertialBA's bLarge case; round 5, d_ba_schur_units): the
-        // slots follow the landmarks sorted by the first and the last free pose that sees them, and a slice is a CHUNK of 16 landmarks -- a
-        // landmark of a temporal window is seen from a run of consecutive keyframes, so a chunk touches a band of the reduced system and the
-        // product skips the rest.  (The covisibility windows of the sparse path are not banded: see above.)
-        const bool dense_window = (6 * n_free + 1 + 15) / 16 > 8 && !lean_wide;
-        const int kSliceEdges = dense_window ? std::numeric_limits<int>::max() : kSchurLeanSlots;
-        const int kSliceLandmarks = dense_window ? kUnitChunkHost : 64;
-        std::vector<int> order(n_points);
-        for (int l = 0; l < n_points; ++l) order[l] = l;
-        if (dense_window) {
-            std::vector<int> first(n_points, std::numeric_limits<int>::max()), last(n_points, -1);
-            for (int e = 0; e < n_edges; ++e) {
-                const int i = pose_var[edges[e].pose], l = edges[e].point;
-                if (i >= 0) { first[l] = std::min(first[l], i); last[l] = std::max(last[l], i); }
-            }
-            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return first[a] != first[b] ? first[a] < first[b] : last[a] < last[b]; });
-        }
-        std::vector<int> seen(std::max(n_free, 1), -1), seen_slot(std::max(n_free, 1), -1);
-        int at = 0, slice_lms = 0;
-        for (int lo = 0; lo < n_points; ++lo) {
-            const int l = order[lo];
-            const int begin = at;
-            for (int k = pt_off[l]; k < pt_off[l + 1]; ++k) {
-                const int e = pt_edges[k], i = pose_var[edges[e].pose];
-                if (i < 0) continue;
-                // A second edge between the same point and the same free pose: g2o adds the two edges' blocks (BaseBinaryEdge::
-                // constructQuadraticForm on the same Hpl / Hpp blocks, base_binary_edge.hpp:55-137).  The slot arrays hold one W block per
-                // (landmark, pose): the later edge gets no slot -- k_ba_dups adds its W block to the first edge's slot and its pose block to
-                // the pose's sums after the linearisation (round 5; rounds 2-4 refused such a window).  The reference's gather cannot produce
-                // one for a pinhole rig, a two-camera shim can.
-                if (seen[i] == l) { dups.push_back(DupEdge{i, e, seen_slot[i]}); continue; }
-                seen[i] = l; seen_slot[i] = at;
-                w_slot[e] = at; fl_pose[at] = i; fl_lm[at] = l; fl_edge[at] = e; ++at;
-            }
-            fl_off[2 * (size_t)l] = begin; fl_off[2 * (size_t)l + 1] = at;
-            if (at == begin) continue;
-            if (slice_lms == kSliceLandmarks || at - slice_off.back() > kSliceEdges) { slice_off.push_back(begin); slice_lms = 0; }
-            for (int k = begin; k < at; ++k) fl_place[k] = slice_lms;
-            ++slice_lms;
-        }
-        if (at > slice_off.back()) slice_off.push_back(at);
-        n_free_edges = at;
-    }
-    // duplicates (k_ba_dups): by pose, in edge order; the per-pose edge lists of the dense windows' coefficient sums hold the slots' edges only
-    std::vector<int> dup_off(n_free + 1, 0), dup_edge(std::max(dups.size(), (size_t)1)), dup_slot(std::max(dups.size(), (size_t)1));
-    if (!dups.empty()) {
-        std::stable_sort(dups.begin(), dups.end(), [](const DupEdge& a, const DupEdge& b) { return a.pose != b.pose ? a.pose < b.pose : a.edge < b.edge; });
-        for (size_t k = 0; k < dups.size(); ++k) { dup_off[dups[k].pose + 1]++; dup_edge[k] = dups[k].edge; dup_slot[k] = dups[k].slot; }
-        for (int i = 0; i < n_free; ++i) dup_off[i + 1] += dup_off[i];
-        std::fill(pv_off.begin(), pv_off.end(), 0);
-        for (int e = 0; e < n_edges; ++e) if (w_slot[e] >= 0) pv_off[pose_var[edges[e].pose] + 1]++;
-        for (int i = 0; i < n_free; ++i) pv_off[i + 1] += pv_off[i];
-        std::vector<int> fp(pv_off.begin(), pv_off.end() - 1);
-        for (int e = 0; e < n_edges; ++e) if (w_slot[e] >= 0) pv_edges[fp[pose_var[edges[e].pose]]++] = e;
-    }
-    // blocks of 256 free-pose edges (the pose role of the linearisation): the block's rows sorted by pose, for the per-pose sums
-    const int n_blocks = (n_free_edges + 255) / 256;
-    std::vector<int> blk_off((size_t)std::max(n_blocks, 1) * (n_free + 1), 0);
-    std::vector<uint8_t> blk_rows((size_t)std::max(n_blocks, 1) * 256, 0);
-    for (int b = 0; b < n_blocks; ++b) {
-        int* off = blk_off.data() + (size_t)b * (n_free + 1);
-        const int s0 = 256 * b, s1 = std::min(n_free_edges, s0 + 256);
-        for (int s = s0; s < s1; ++s) off[fl_pose[s] + 1]++;
-        for (int i = 0; i < n_free; ++i) off[i + 1] += off[i];
-        std::vector<int> fill(off, off + n_free);
-        for (int s = s0; s < s1; ++s) blk_rows[(size_t)b * 256 + fill[fl_pose[s]]++] = (uint8_t)(s - s0);
-    }
-    // groups of the linearisation: whole landmarks, at most 256 edges (one per thread)
-    std::vector<int> grp_k0(1, 0), grp_l0(1, 0);
-    for (int l = 0; l < n_points; ++l) {
-        if (pt_off[l + 1] - pt_off[l] > 256) { set_error("point %d has more than 256 edges", l); return TC2LI_ERR_INVALID; }
-        if (pt_off[l + 1] - grp_k0.back() > 256) { grp_k0.push_back(pt_off[l]); grp_l0.push_back(l); }
-    }
-    grp_k0.push_back(n_edges); grp_l0.push_back(n_points);
-    const int n_groups = (int)grp_k0.size() - 1;
-    max_group_landmarks = 0;
-    for (int g = 0; g < n_groups; ++g) max_group_landmarks = std::max(max_group_landmarks, grp_l0[g + 1] - grp_l0[g]);
-    if (max_group_landmarks > 256) { set_error("more than 256 landmarks without edges in a row"); return TC2LI_ERR_INVALID; }  // (a landmark-role workgroup has a thread per landmark)
-    np = 6 * n_free;
-    // sparse path: one spare row for W D^-1 b_l (row np of the product); dense path: the operands' width
-    const bool sparse = schur_lean;
-    const int np_pad = sparse ? (np + 1 + 15) / 16 * 16 : std::max(16, (np + 15) / 16 * 16);
-    const int n_schur_slices = (int)slice_off.size() - 1;
-    int schur_group = 1;
-    if (sparse) {
-        schur_group = kSchurGroupLean;  // slices per part
-        n_slices = ba_schur_parts(n_schur_slices, schur_group);  // partial sums in S_part
-        k_per_slice = 0;
-    } else {
-        // dense windows (round 5: d_ba_schur_units): the chunks (slices of slice_off: 16 landmarks each) in at most 8 ranges = partial sums
-        const int want_slices = 8;  // (full-width form, 32 windows per launch beside two other groups: 2 / 4 / 8 slices 0.263 / 0.154 / 0.099 ms)
-        k_per_slice = std::min(64, std::max(1, (n_schur_slices + want_slices - 1) / want_slices));   // chunks per partial sum (at most kUnitMaxChunks: ba_kernels.hip)
-        n_slices = std::max(1, (n_schur_slices + k_per_slice - 1) / k_per_slice);
-    }
-    // which 16-column tiles of the reduced system a chunk of landmarks touches (bit t: a pose with columns in tile t sees one of them)
-    std::vector<uint32_t> chunk_mask;
-    if (!sparse) {
-        if (np_pad / 16 > 32) { set_error("more than 85 free keyframes"); return TC2LI_ERR_INVALID; }
-        chunk_mask.assign((size_t)std::max(n_schur_slices, 1), 0u);
-        for (int c = 0; c < n_schur_slices; ++c)
-            for (int sl = slice_off[c]; sl < slice_off[c + 1]; ++sl) {
-                const int c0 = 6 * fl_pose[sl];
-                chunk_mask[c] |= (1u << (c0 / 16)) | (1u << ((c0 + 5) / 16));
-            }
-    }
-
-    // ---- device memory: a per-thread workspace that only grows (hipMalloc per call would dominate the run time) ----
+    // The workspace of a window of these sizes: a per-thread workspace that only grows (hipMalloc per call would dominate the run time).
+    int reserve(BaWorkspace& ws, const BaStructureSizes& s) {
+    const int n_poses = s.n_poses, n_free_edges = s.n_free_edges, n_blocks = s.n_blocks, n_groups = s.n_groups, np_pad = s.np_pad;
+    const bool sparse = s.sparse != 0;
     auto& d_poses_trial = ws.d_poses_trial;
     auto &d_points_trial = ws.d_points_trial, &d_chi2 = ws.d_chi2, &d_rho0 = ws.d_rho0,
          &d_cp = ws.d_cp, &d_W = ws.d_W, &d_Hll = ws.d_Hll, &d_bl = ws.d_bl, &d_diag_l = ws.d_diag_l, &d_Hpp = ws.d_Hpp,
@@ -318,7 +182,7 @@ struct VisualProblem {
          &d_Spart = ws.d_Spart, &d_scale_part = ws.d_scale_part, &d_chi_part = ws.d_chi_part;
     auto& d_depth = ws.d_depth;
     auto &h_S = ws.h_S, &h_bs = ws.h_bs, &h_xp = ws.h_xp, &h_scal = ws.h_scal;
-    const size_t E = n_edges, P = n_points;
+    const size_t E = s.n_edges, P = s.n_points;
     TC2LI_HIP_CHECK(d_poses_trial.ensure(n_poses));
     TC2LI_HIP_CHECK(d_points_trial.ensure(3 * P));
     TC2LI_HIP_CHECK(d_chi2.ensure(E)); TC2LI_HIP_CHECK(d_rho0.ensure(E)); TC2LI_HIP_CHECK(d_cp.ensure(kContribP * (size_t)std::max(n_blocks * n_free, 1)));
@@ -331,86 +195,126 @@ struct VisualProblem {
     TC2LI_HIP_CHECK(h_S.ensure((size_t)std::max(np * np, 1))); TC2LI_HIP_CHECK(h_bs.ensure(2 * (size_t)std::max(np, 1)));
     TC2LI_HIP_CHECK(h_xp.ensure(std::max(np, 1))); TC2LI_HIP_CHECK(h_scal.ensure(8));
     memset(h_S.p, 0, (size_t)std::max(np * np, 1) * sizeof(double));  // the finish kernel writes the lower triangle only; the rest stays defined
-    // ---- the input block: [poses | points | edges | pose_var | pt_off | pt_edges | pv_off | pv_edges | fl_off | fl_pose | chunk_mask | fl_lm | fl_place | slice_off | fl_edge | grp_k0 | grp_l0 | blk_off | blk_rows | ticket words], every
-    // part 16-byte aligned ----
-    auto align16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_poses = 0, o_points = align16(o_poses + n_poses * sizeof(Se3)), o_edges = align16(o_points + 3 * P * sizeof(double)),
-                 o_pose_var = align16(o_edges + E * sizeof(BaEdge)), o_pt_off = align16(o_pose_var + n_poses * sizeof(int)),
-                 o_pt_edges = align16(o_pt_off + (P + 1) * sizeof(int)), o_pv_off = align16(o_pt_edges + E * sizeof(int)),
-                 o_pv_edges = align16(o_pv_off + (n_free + 1) * sizeof(int)), o_fl_off = align16(o_pv_edges + (sparse ? 0 : pv_edges.size()) * sizeof(int)),
-                 o_fl_pose = align16(o_fl_off + 2 * P * sizeof(int)), o_w_slot = align16(o_fl_pose + fl_pose.size() * sizeof(int)),
-                 o_fl_lm = align16(o_w_slot + chunk_mask.size() * sizeof(uint32_t)), o_fl_place = align16(o_fl_lm + fl_lm.size() * sizeof(int)),
-                 o_slice_off = align16(o_fl_place + fl_place.size() * sizeof(int)), o_fl_edge = align16(o_slice_off + slice_off.size() * sizeof(int)),
-                 o_grp_k0 = align16(o_fl_edge + fl_edge.size() * sizeof(int)), o_grp_l0 = align16(o_grp_k0 + grp_k0.size() * sizeof(int)),
-                 o_blk_off = align16(o_grp_l0 + grp_l0.size() * sizeof(int)), o_blk_rows = align16(o_blk_off + blk_off.size() * sizeof(int)),
-                 o_ticket = align16(o_blk_rows + blk_rows.size()), o_dup_off = align16(o_ticket + 4 * sizeof(int32_t)),
-                 o_dup_edge = align16(o_dup_off + (dups.empty() ? 0 : dup_off.size()) * sizeof(int)),
-                 o_dup_slot = align16(o_dup_edge + (dups.empty() ? 0 : dups.size()) * sizeof(int)),
-                 in_bytes = align16(o_dup_slot + (dups.empty() ? 0 : dups.size()) * sizeof(int));
-    TC2LI_HIP_CHECK(ws.d_in.ensure(in_bytes)); TC2LI_HIP_CHECK(ws.h_in.ensure(in_bytes));
-    uint8_t* const h = ws.h_in.p;
-    if (poses7) {
-        poses.resize(n_poses);
-        for (int k = 0; k < n_poses; ++k) { memcpy(poses[k].q, poses7 + 7 * k, 4 * sizeof(double)); memcpy(poses[k].t, poses7 + 7 * k + 4, 3 * sizeof(double)); }
-        memcpy(h + o_poses, poses.data(), n_poses * sizeof(Se3));
+        return TC2LI_OK;
     }
-    memcpy(h + o_points, points3, 3 * P * sizeof(double));
-    memcpy(h + o_edges, edges, E * sizeof(BaEdge));
-    memcpy(h + o_pose_var, pose_var.data(), n_poses * sizeof(int));
-    memcpy(h + o_pt_off, pt_off.data(), (P + 1) * sizeof(int));
-    memcpy(h + o_pt_edges, pt_edges.data(), E * sizeof(int));
-    memcpy(h + o_pv_off, pv_off.data(), (n_free + 1) * sizeof(int));
-    if (!sparse) memcpy(h + o_pv_edges, pv_edges.data(), pv_edges.size() * sizeof(int));  // pv_edges, w_slot: the dense Schur path's
-    memcpy(h + o_fl_off, fl_off.data(), 2 * P * sizeof(int));
-    memcpy(h + o_fl_pose, fl_pose.data(), fl_pose.size() * sizeof(int));
-    if (!sparse) memcpy(h + o_w_slot, chunk_mask.data(), chunk_mask.size() * sizeof(uint32_t));  // (the region held w_slot for the dense form's prepare kernel)
-    memcpy(h + o_fl_lm, fl_lm.data(), fl_lm.size() * sizeof(int));
-    memcpy(h + o_fl_place, fl_place.data(), fl_place.size() * sizeof(int));
-    memcpy(h + o_slice_off, slice_off.data(), slice_off.size() * sizeof(int));
-    memcpy(h + o_fl_edge, fl_edge.data(), fl_edge.size() * sizeof(int));
-    memcpy(h + o_grp_k0, grp_k0.data(), grp_k0.size() * sizeof(int));
-    memcpy(h + o_grp_l0, grp_l0.data(), grp_l0.size() * sizeof(int));
-    memcpy(h + o_blk_off, blk_off.data(), blk_off.size() * sizeof(int));
-    memcpy(h + o_blk_rows, blk_rows.data(), blk_rows.size());
-    memset(h + o_ticket, 0, 4 * sizeof(int32_t));  // (the kernels that use them leave them at zero again)
-    if (!dups.empty()) {
-        memcpy(h + o_dup_off, dup_off.data(), dup_off.size() * sizeof(int));
-        memcpy(h + o_dup_edge, dup_edge.data(), dups.size() * sizeof(int));
-        memcpy(h + o_dup_slot, dup_slot.data(), dups.size() * sizeof(int));
-    }
-    // inertial mode (poses7 == NULL) uploads ImuPose states itself and does not read the Se3 block
-    const size_t first = poses7 ? 0 : o_points;
-    TC2LI_HIP_CHECK(upload_or_defer(ws.d_in.p + first, h + first, in_bytes - first, st));  // h is pinned
+    // pb: the sizes, the parts of the input block in ws.d_in (lay), the workspace of reserve()
+    void fill_pb(BaWorkspace& ws, const BaStructureSizes& s, const BaInputLayout& lay, const tc2li_camera* cam) {
     uint8_t* const d = ws.d_in.p;
-
+    const bool sparse = s.sparse != 0;
     pb = BaProblemDev{};
-    pb.n_edges = n_edges; pb.n_points = n_points; pb.n_poses = n_poses; pb.n_free = n_free; pb.n_free_edges = n_free_edges; pb.np_pad = np_pad;
+    pb.n_edges = s.n_edges; pb.n_points = s.n_points; pb.n_poses = s.n_poses; pb.n_free = n_free; pb.n_free_edges = s.n_free_edges; pb.np_pad = s.np_pad;
     memcpy(&pb.cam, cam, sizeof(CameraD));
     const float dm = sqrtf(5.991f), ds = sqrtf(7.815f);  // thHuberMono / thHuberStereo are floats (OptimizerWithLidar.cc:219-220)
     pb.delta_mono = dm; pb.delta_stereo = ds;
     pb.dsqr_mono = (float)((double)dm * (double)dm); pb.dsqr_stereo = (float)((double)ds * (double)ds);
-    pb.poses = (Se3*)(d + o_poses); pb.poses_trial = d_poses_trial.p; pb.points = (double*)(d + o_points); pb.points_trial = d_points_trial.p;
-    pb.edges = (const BaEdge*)(d + o_edges); pb.pose_var = (const int*)(d + o_pose_var); pb.pt_off = (const int*)(d + o_pt_off);
-    pb.pt_edges = (const int*)(d + o_pt_edges); pb.pv_off = (const int*)(d + o_pv_off); pb.pv_edges = (const int*)(d + o_pv_edges);
-    pb.fl_off = (const int*)(d + o_fl_off); pb.fl_pose = (const int*)(d + o_fl_pose); pb.chunk_mask = (const uint32_t*)(d + o_w_slot);
-    pb.fl_lm = (const int*)(d + o_fl_lm); pb.fl_place = (const int*)(d + o_fl_place); pb.slice_off = (const int*)(d + o_slice_off); pb.fl_edge = (const int*)(d + o_fl_edge);
-    pb.grp_k0 = (const int*)(d + o_grp_k0); pb.grp_l0 = (const int*)(d + o_grp_l0); pb.n_groups = n_groups;
-    pb.blk_off = (const int*)(d + o_blk_off); pb.blk_rows = (const uint8_t*)(d + o_blk_rows);
-    pb.ticket = (int32_t*)(d + o_ticket);
-    pb.n_dups = (int32_t)dups.size();
-    pb.dup_off = dups.empty() ? nullptr : (const int*)(d + o_dup_off);
-    pb.dup_edge = dups.empty() ? nullptr : (const int*)(d + o_dup_edge);
-    pb.dup_slot = dups.empty() ? nullptr : (const int*)(d + o_dup_slot);
-    pb.sparse_schur = sparse ? 1 : 0; pb.schur_blocks = sparse ? 2 : 0; pb.schur_group = schur_group; pb.n_schur_slices = n_schur_slices;  // (dense windows: the chunks of d_ba_schur_units)
-    pb.schur_rd = pb.schur_ro = 1;
+    pb.poses = (Se3*)(d + lay.o_poses); pb.poses_trial = ws.d_poses_trial.p; pb.points = (double*)(d + lay.o_points); pb.points_trial = ws.d_points_trial.p;
+    pb.edges = (const BaEdge*)(d + lay.o_edges); pb.pose_var = (const int*)(d + lay.o_pose_var); pb.pt_off = (const int*)(d + lay.o_pt_off);
+    pb.pt_edges = (const int*)(d + lay.o_pt_edges); pb.pv_off = (const int*)(d + lay.o_pv_off); pb.pv_edges = (const int*)(d + lay.o_pv_edges);
+    pb.fl_off = (const int*)(d + lay.o_fl_off); pb.fl_pose = (const int*)(d + lay.o_fl_pose); pb.chunk_mask = (const uint32_t*)(d + lay.o_w_slot);
+    pb.fl_lm = (const int*)(d + lay.o_fl_lm); pb.fl_place = (const int*)(d + lay.o_fl_place); pb.slice_off = (const int*)(d + lay.o_slice_off); pb.fl_edge = (const int*)(d + lay.o_fl_edge);
+    pb.grp_k0 = (const int*)(d + lay.o_grp_k0); pb.grp_l0 = (const int*)(d + lay.o_grp_l0); pb.n_groups = s.n_groups;
+    pb.blk_off = (const int*)(d + lay.o_blk_off); pb.blk_rows = (const uint8_t*)(d + lay.o_blk_rows);
+    pb.ticket = (int32_t*)(d + lay.o_ticket);
+    pb.n_dups = s.n_dups;
+    pb.dup_off = !s.n_dups ? nullptr : (const int*)(d + lay.o_dup_off);
+    pb.dup_edge = !s.n_dups ? nullptr : (const int*)(d + lay.o_dup_edge);
+    pb.dup_slot = !s.n_dups ? nullptr : (const int*)(d + lay.o_dup_slot);
+    pb.sparse_schur = sparse ? 1 : 0; pb.schur_blocks = sparse ? 2 : 0; pb.schur_group = s.schur_group; pb.n_schur_slices = s.n_schur_slices;  // (dense windows: the chunks of d_ba_schur_units)
+    pb.schur_rd = s.schur_rd; pb.schur_ro = s.schur_ro;
     decide_trial_fused();
-    if (sparse) {
-        if (lean_wide) schur_ranges_wide(n_free, pb.schur_rd, pb.schur_ro); else schur_ranges(n_free, pb.schur_rd, pb.schur_ro);
+    pb.chi2 = ws.d_chi2.p; pb.rho0 = ws.d_rho0.p; pb.cp_part = ws.d_cp.p; pb.W = ws.d_W.p; pb.Hll = ws.d_Hll.p; pb.bl = ws.d_bl.p;
+    pb.diag_l = ws.d_diag_l.p; pb.Hpp = ws.d_Hpp.p; pb.diag_p = ws.d_diag_p.p; pb.coef_e = ws.d_coef_e.p; pb.coef = ws.d_coef.p; pb.Y = sparse ? nullptr : ws.d_Y.p;
+    pb.S_part = ws.d_Spart.p; pb.scale_part = ws.d_scale_part.p; pb.chi_part = ws.d_chi_part.p;
     }
-    pb.chi2 = d_chi2.p; pb.rho0 = d_rho0.p; pb.cp_part = d_cp.p; pb.W = d_W.p; pb.Hll = d_Hll.p; pb.bl = d_bl.p;
-    pb.diag_l = d_diag_l.p; pb.Hpp = d_Hpp.p; pb.diag_p = d_diag_p.p; pb.coef_e = d_coef_e.p; pb.coef = d_coef.p; pb.Y = sparse ? nullptr : ws.d_Y.p;
-    pb.S_part = d_Spart.p; pb.scale_part = d_scale_part.p; pb.chi_part = d_chi_part.p;
 
+    int setup(BaWorkspace& ws, const double* poses7, const uint8_t* fixed, int n_poses, const double* points3, int n_points,
+              const tc2li_ba_edge* edges, int n_edges, const tc2li_camera* cam, const uint8_t* extra_used, hipStream_t st) {
+    // ---- structure: free-pose numbering, CSR by landmark and by free pose, slots, slices, blocks, groups (ba_structure.hpp) ----
+    BaStructure s;
+    {
+        const int rc = ba_build_structure(fixed, n_poses, n_points, edges, n_edges, extra_used, s);
+        if (rc != TC2LI_OK) return rc;
+    }
+    pose_var = s.pose_var;
+    n_free = s.n_free; np = s.np; n_slices = s.n_slices; k_per_slice = s.k_per_slice; max_group_landmarks = s.max_group_landmarks;
+    const bool sparse = s.sparse != 0;
+    const size_t E = n_edges, P = n_points;
+    // ---- device memory ----
+    {
+        const int rc = reserve(ws, s);
+        if (rc != TC2LI_OK) return rc;
+    }
+    // ---- the input block (ba_input_layout, ba_structure.hpp), every part 16-byte aligned ----
+    const BaInputLayout lay = ba_input_layout(s);
+    TC2LI_HIP_CHECK(ws.d_in.ensure(lay.in_bytes)); TC2LI_HIP_CHECK(ws.h_in.ensure(lay.in_bytes));
+    uint8_t* const h = ws.h_in.p;
+    if (poses7) {
+        poses.resize(n_poses);
+        for (int k = 0; k < n_poses; ++k) { memcpy(poses[k].q, poses7 + 7 * k, 4 * sizeof(double)); memcpy(poses[k].t, poses7 + 7 * k + 4, 3 * sizeof(double)); }
+        memcpy(h + lay.o_poses, poses.data(), n_poses * sizeof(Se3));
+    }
+    memcpy(h + lay.o_points, points3, 3 * P * sizeof(double));
+    memcpy(h + lay.o_edges, edges, E * sizeof(BaEdge));
+    memcpy(h + lay.o_pose_var, pose_var.data(), n_poses * sizeof(int));
+    memcpy(h + lay.o_pt_off, s.pt_off.data(), (P + 1) * sizeof(int));
+    memcpy(h + lay.o_pt_edges, s.pt_edges.data(), E * sizeof(int));
+    memcpy(h + lay.o_pv_off, s.pv_off.data(), (n_free + 1) * sizeof(int));
+    if (!sparse) memcpy(h + lay.o_pv_edges, s.pv_edges.data(), s.pv_edges.size() * sizeof(int));  // pv_edges, w_slot: the dense Schur path's
+    memcpy(h + lay.o_fl_off, s.fl_off.data(), 2 * P * sizeof(int));
+    memcpy(h + lay.o_fl_pose, s.fl_pose.data(), s.fl_pose.size() * sizeof(int));
+    if (!sparse) memcpy(h + lay.o_w_slot, s.chunk_mask.data(), s.chunk_mask.size() * sizeof(uint32_t));  // (the region held w_slot for the dense form's prepare kernel)
+    memcpy(h + lay.o_fl_lm, s.fl_lm.data(), s.fl_lm.size() * sizeof(int));
+    memcpy(h + lay.o_fl_place, s.fl_place.data(), s.fl_place.size() * sizeof(int));
+    memcpy(h + lay.o_slice_off, s.slice_off.data(), s.slice_off.size() * sizeof(int));
+    memcpy(h + lay.o_fl_edge, s.fl_edge.data(), s.fl_edge.size() * sizeof(int));
+    memcpy(h + lay.o_grp_k0, s.grp_k0.data(), s.grp_k0.size() * sizeof(int));
+    memcpy(h + lay.o_grp_l0, s.grp_l0.data(), s.grp_l0.size() * sizeof(int));
+    memcpy(h + lay.o_blk_off, s.blk_off.data(), s.blk_off.size() * sizeof(int));
+    memcpy(h + lay.o_blk_rows, s.blk_rows.data(), s.blk_rows.size());
+    memset(h + lay.o_ticket, 0, 4 * sizeof(int32_t));  // (the kernels that use them leave them at zero again)
+    if (s.n_dups) {
+        memcpy(h + lay.o_dup_off, s.dup_off.data(), s.dup_off.size() * sizeof(int));
+        memcpy(h + lay.o_dup_edge, s.dup_edge.data(), (size_t)s.n_dups * sizeof(int));
+        memcpy(h + lay.o_dup_slot, s.dup_slot.data(), (size_t)s.n_dups * sizeof(int));
+    }
+    // inertial mode (poses7 == NULL) uploads ImuPose states itself and does not read the Se3 block
+    const size_t first = poses7 ? 0 : lay.o_points;
+    TC2LI_HIP_CHECK(upload_or_defer(ws.d_in.p + first, h + first, lay.in_bytes - first, st));  // h is pinned
+    fill_pb(ws, s, lay, cam);
+        return TC2LI_OK;
+    }
+
+    // The same state for a window whose structure was built on the device (ba_structure_kernels.hip): the workspace from the sizes, the
+    // input block filled device to device from the pieces, no structure on the host and no upload.  pose_var_host [n_poses] is the
+    // downloaded numbering (the LiDAR term's host steps read it).
+    int adopt(BaWorkspace& ws, const BaPrepared& pr, const tc2li_camera* cam, hipStream_t st) {
+    const BaStructureSizes& s = pr.sizes;
+    pose_var.assign(pr.pose_var_host, pr.pose_var_host + s.n_poses);
+    poses.resize(s.n_poses);
+    n_free = s.n_free; np = s.np; n_slices = s.n_slices; k_per_slice = s.k_per_slice; max_group_landmarks = s.max_group_landmarks;
+    {
+        const int rc = reserve(ws, s);
+        if (rc != TC2LI_OK) return rc;
+    }
+    const BaInputLayout lay = ba_input_layout(s);
+    TC2LI_HIP_CHECK(ws.d_in.ensure(lay.in_bytes));
+    uint8_t* const d = ws.d_in.p;
+    const size_t K = s.n_poses, P = s.n_points, E = s.n_edges, F = s.n_free_edges;
+    const struct { size_t at; const void* src; size_t bytes; } piece[] = {
+        {lay.o_poses, pr.poses, K * sizeof(Se3)}, {lay.o_points, pr.points, 3 * P * sizeof(double)}, {lay.o_edges, pr.edges, E * sizeof(BaEdge)},
+        {lay.o_pose_var, pr.pose_var, K * 4}, {lay.o_pt_off, pr.pt_off, (P + 1) * 4}, {lay.o_pt_edges, pr.pt_edges, E * 4},
+        {lay.o_pv_off, pr.pv_off, ((size_t)s.n_free + 1) * 4}, {lay.o_fl_off, pr.fl_off, 2 * P * 4}, {lay.o_fl_pose, pr.fl_pose, F * 4},
+        {lay.o_fl_lm, pr.fl_lm, F * 4}, {lay.o_fl_place, pr.fl_place, F * 4}, {lay.o_slice_off, pr.slice_off, lay.n_slice_off * 4},
+        {lay.o_fl_edge, pr.fl_edge, F * 4}, {lay.o_grp_k0, pr.grp_k0, lay.n_grp * 4}, {lay.o_grp_l0, pr.grp_l0, lay.n_grp * 4},
+        {lay.o_blk_off, pr.blk_off, lay.n_blk_off * 4}, {lay.o_blk_rows, pr.blk_rows, lay.n_blk_rows}};
+    for (const auto& q : piece) {
+        if (!q.bytes) continue;
+        // device to device: the batch's copy kernel takes any global pointer; without a batch, the runtime's copy
+        if (copy_sink_active()) { TC2LI_HIP_CHECK(upload_or_defer(d + q.at, q.src, q.bytes, st)); }
+        else { TC2LI_HIP_CHECK(hipMemcpyAsync(d + q.at, q.src, q.bytes, hipMemcpyDeviceToDevice, st)); }
+    }
+    TC2LI_HIP_CHECK(zero_or_defer(d + lay.o_ticket, 4 * sizeof(int32_t), st));
+    fill_pb(ws, s, lay, cam);
         return TC2LI_OK;
     }
 };
@@ -616,6 +520,7 @@ struct LockstepContext {
     DevBuf<uint8_t> d_table;
     PinnedBuf<uint8_t> h_table;
     PinnedBuf<CopyTask> h_tasks;  // the uploads / operand fills of a batch's setup, then its result copies: one launch each (copy_kernels.hip)
+    PinnedBuf<BasOutlierTask> h_outliers;  // prepared windows: the outlier rule after the BA, a task per window (ba_structure_kernels.hip)
     PinnedBuf<CopyTask> h_table_task;  // the steps x_p of a trial phase on their way up: one entry for k_copy_tasks
     // plane extraction of the batch's LiDAR windows on the device (balm_cut_kernels.hip): a task per window, those with points to cut
     // compacted into the list the kernels read, and the uploads the LiDAR tasks deferred (the clouds)
@@ -760,7 +665,9 @@ inline void queue_lm_round(const BaBatchSlot* d_table, const std::vector<Lockste
 }
 
 // the lock-step drivers (ba_lockstep.cpp, lvi_host.cpp): false = the batch goes through the one-window path
-bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_camera* cam, WorkerPool& pool, int32_t* results, int group = 0);
+// prepared: NULL, or one record per window (a window with sizes.n_poses == 0 in it is set up from its host arrays as ever)
+bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_camera* cam, WorkerPool& pool, int32_t* results, int group = 0,
+                       const BaPrepared* prepared = nullptr);
 
 }  // namespace ba_detail
 }  // namespace tc2li

@@ -8,7 +8,8 @@ namespace tc2li {
 namespace ba_detail {
 
 // returns false when the batch has to go through the one-thread-per-window path (a LiDAR window outside the batched kernels' range)
-bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_camera* cam, WorkerPool& pool, int32_t* results, int group) {
+bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_camera* cam, WorkerPool& pool, int32_t* results, int group,
+                       const BaPrepared* prepared) {
     LockstepContext& C = lockstep_ctx(group);
     std::lock_guard<std::mutex> lk(C.mu);
     const BaOptions opt = BaOptions::read();
@@ -53,7 +54,8 @@ bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_came
         const int i = task >> 1;
         LockstepWindow& w = W[i];
         const tc2li_ba_problem& p = problems[i];
-        const bool args_ok = p.poses7 && p.fixed && p.points3 && p.edges && p.n_poses > 0 && p.n_points > 0 && p.n_edges > 0 && p.iterations >= 0;
+        const BaPrepared* const prep = prepared && prepared[i].sizes.n_poses > 0 ? prepared + i : nullptr;  // (its edges may stay on the device)
+        const bool args_ok = p.poses7 && p.fixed && p.points3 && (p.edges || prep) && p.n_poses > 0 && p.n_points > 0 && p.n_edges > 0 && p.iterations >= 0;
         bool lidar_ok = true;
         if (args_ok && p.lidar) {
             if (p.lidar->n_keyframes < 1 || !p.lidar->pose_index) lidar_ok = false;
@@ -71,13 +73,14 @@ bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_came
         if (!lidar_ok) { set_error("lidar window: invalid argument or pose_index out of range"); w.rc = TC2LI_ERR_INVALID; return; }
         if (p.stats) memset(p.stats, 0, sizeof(*p.stats));
         if (p.lidar_stats) memset(p.lidar_stats, 0, sizeof(*p.lidar_stats));
-        if (p.lidar) {
+        if (p.lidar && !prep) {
             w.extra_used.assign(p.n_poses, 0);
             for (int k = 0; k < p.lidar->n_keyframes; ++k) w.extra_used[p.lidar->pose_index[k]] = 1;
         }
         const double ts = now();
-        w.rc = w.vp.setup(*w.ws, p.poses7, p.fixed, p.n_poses, p.points3, p.n_points, p.edges, p.n_edges, cam,
-                          w.extra_used.empty() ? nullptr : w.extra_used.data(), st);
+        if (prep) w.rc = w.vp.adopt(*w.ws, *prep, cam, st);   // the structure is the device's: no host structure, no upload
+        else w.rc = w.vp.setup(*w.ws, p.poses7, p.fixed, p.n_poses, p.points3, p.n_points, p.edges, p.n_edges, cam,
+                               w.extra_used.empty() ? nullptr : w.extra_used.data(), st);
         if (kTiming && i == 0) fprintf(stderr, "  window 0: visual setup %.3f ms\n", now() - ts);
         if (w.rc < 0) return;
         const int np = w.vp.np;
@@ -492,6 +495,17 @@ bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_came
             if (p.edge_depth_positive) add(hc + E * sizeof(double), w.ws->d_depth.p, E);
         }
         if (!failed) launch_copy_tasks(C.h_tasks.p, (int)n_tasks, max_bytes, st);
+        if (!failed && prepared) {   // the outlier rule of the prepared windows, from the chi2 and the depth flags where the kernels left them
+            int m = 0;
+            if (C.h_outliers.ensure(all.size()) != hipSuccess) failed = true;
+            for (int i : all) {
+                if (failed || !(prepared[i].sizes.n_poses > 0) || !prepared[i].n_erase) continue;
+                const BaPrepared& pr = prepared[i];
+                C.h_outliers.p[m++] = BasOutlierTask{(const tc2li_ba_edge*)W[i].vp.pb.edges, W[i].ws->d_chi2.p, W[i].ws->d_depth.p, pr.erase_pose, pr.erase_point,
+                                                     pr.n_erase, W[i].vp.pb.n_edges, pr.erase_capacity};
+            }
+            if (!failed) launch_ba_outliers(C.h_outliers.p, m, st);
+        }
         sync();
         if (!failed)
             pool.parallel_for((int)all.size(), [&](int k) {

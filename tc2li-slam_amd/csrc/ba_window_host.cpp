@@ -1,10 +1,12 @@
 // tc2li_ba_window_batch / tc2li_host_ba_window_batch / tc2li_ba_window_limits / tc2li_ba_window_outliers (include/tc2li_hip.h "local
 // mapping: the window of the local BA"): the gather of OptimizerWithLidar::LocalLVBundleAdjustment (SF/src/OptimizerWithLidar.cc:63-130,
 // :157-187, :226-253, :263-384) and its outlier rule (:402-449) on a flat copy of the graph.  This file validates the problems and either
-// walks them in plain C++ with the reference's mark fields or concatenates them for ba_window_kernels.hip.
+// walks them in plain C++ with the reference's mark fields or concatenates them for ba_window_kernels.hip.  ba_window_batch_run is the
+// device entry with two hooks for what follows the gather on the device (ba_structure_device.hpp: the structure kernels, the BA).
 #include <algorithm>
 #include <cstring>
 
+#include "ba_structure_device.hpp"
 #include "ba_window_device.hpp"
 #include "common.hpp"
 
@@ -27,7 +29,7 @@ struct SlotTable {
 };
 
 // "" or what is wrong with the problem
-const char* validate(const tc2li_ba_window_problem& in, const SlotTable& slots, int n_levels) {
+const char* validate(const tc2li_ba_window_problem& in, const SlotTable& slots, int n_levels, bool edges_optional) {
     if (in.n_keyframes < 0 || in.n_points < 0 || in.n_cov < 0) return "negative size";
     if (in.pose_capacity < 0 || in.point_capacity < 0 || in.edge_capacity < 0) return "negative capacity";
     if (!in.kf_slot || !in.kf_id || !in.kf_flags || !in.poses7 || !in.slot_offsets || !in.obs_offsets || !in.counts || !in.lidar_pose_index)
@@ -36,7 +38,7 @@ const char* validate(const tc2li_ba_window_problem& in, const SlotTable& slots, 
     if ((in.n_cov && !in.cov_kf) || (in.n_points && (!in.point_flags || !in.positions))) return "null cov_kf, point_flags or positions";
     if (in.pose_capacity && (!in.pose_row || !in.poses7_out || !in.fixed)) return "null pose output";
     if (in.point_capacity && (!in.point_row || !in.points3_out)) return "null point output";
-    if (in.edge_capacity && !in.edges) return "null edges";
+    if (in.edge_capacity && !in.edges && !edges_optional) return "null edges";
     if (!ascending(in.slot_offsets, in.n_keyframes)) return "slot_offsets do not ascend from 0";
     if (!ascending(in.obs_offsets, in.n_points)) return "obs_offsets do not ascend from 0";
     const int n_slot = in.slot_offsets[in.n_keyframes], n_obs = in.obs_offsets[in.n_points];
@@ -68,13 +70,13 @@ const char* validate(const tc2li_ba_window_problem& in, const SlotTable& slots, 
 }
 
 int validate_all(const char* entry, const tc2li_ba_window_problem* problems, int n_problems, const SlotTable& slots, const float* inv_level_sigma2,
-                 int n_levels) {
+                 int n_levels, bool edges_optional = false) {
     if (n_problems < 0 || (n_problems && !problems) || !inv_level_sigma2 || n_levels < 1) {
         set_error("%s: null or negative argument", entry);
         return TC2LI_ERR_INVALID;
     }
     std::vector<const char*> what(n_problems, "");
-    tracking_pool().parallel_for(n_problems, [&](int p) { what[p] = validate(problems[p], slots, n_levels); });
+    tracking_pool().parallel_for(n_problems, [&](int p) { what[p] = validate(problems[p], slots, n_levels, edges_optional); });
     for (int p = 0; p < n_problems; ++p)
         if (what[p][0]) {
             set_error("%s: problem %d: %s", entry, p, what[p]);
@@ -83,9 +85,10 @@ int validate_all(const char* entry, const tc2li_ba_window_problem* problems, int
     return 0;
 }
 
-bool fits(const tc2li_ba_window_problem& in, const int32_t* counts) {
+// edges_optional: a problem without an edge array leaves its edges on the device, whatever their number
+bool fits(const tc2li_ba_window_problem& in, const int32_t* counts, bool edges_optional = false) {
     return counts[TC2LI_BA_WINDOW_N_POSES] <= in.pose_capacity && counts[TC2LI_BA_WINDOW_N_POINTS] <= in.point_capacity &&
-           counts[TC2LI_BA_WINDOW_N_EDGES] <= in.edge_capacity;
+           (counts[TC2LI_BA_WINDOW_N_EDGES] <= in.edge_capacity || (edges_optional && !in.edges));
 }
 
 int capacity_error(const char* entry, const tc2li_ba_window_problem* problems, int p) {
@@ -196,6 +199,8 @@ struct BawSpace {
     DevBuf<uint8_t> io, work;
     PinnedBuf<uint8_t> h_io;
 };
+// [0]: tc2li_ba_window_batch's; [1 + group]: a follow-up's that keeps the buffers for the length of a BA on the lock-step context `group`
+struct BawSpaces { BawSpace s[1 + kMaxLockstepGroups]; };
 
 }  // namespace
 }  // namespace tc2li
@@ -284,7 +289,11 @@ extern "C" int tc2li_host_ba_window_batch(const tc2li_keyframe_view* views, int 
 
 extern "C" int tc2li_ba_window_batch(tc2li_keyframe_store* store, const tc2li_ba_window_problem* problems, int n_problems,
                                      const float* inv_level_sigma2, int n_levels, void* stream) {
-    const char* entry = "tc2li_ba_window_batch";
+    return ba_window_batch_run("tc2li_ba_window_batch", store, problems, n_problems, inv_level_sigma2, n_levels, stream, nullptr, 0, false);
+}
+
+int tc2li::ba_window_batch_run(const char* entry, tc2li_keyframe_store* store, const tc2li_ba_window_problem* problems, int n_problems,
+                               const float* inv_level_sigma2, int n_levels, void* stream, BawFollow* follow, int space, bool edges_optional) {
     if (!store) {
         set_error("%s: null store", entry);
         return TC2LI_ERR_INVALID;
@@ -295,7 +304,8 @@ extern "C" int tc2li_ba_window_batch(tc2li_keyframe_store* store, const tc2li_ba
     slots.levels.assign(n_store, 0);
     BawStore where{};
     keyframe_store_baw(store, &where, slots.n.data(), slots.levels.data(), n_store);
-    const int rc = validate_all(entry, problems, n_problems, slots, inv_level_sigma2, n_levels);
+    if (space < 0 || space > kMaxLockstepGroups) { set_error("%s: no such buffer set", entry); return TC2LI_ERR_INVALID; }
+    const int rc = validate_all(entry, problems, n_problems, slots, inv_level_sigma2, n_levels, edges_optional);
     if (rc < 0) return rc;
     if (!device_ready()) return TC2LI_ERR_NO_DEVICE;
     if (n_problems == 0) return 0;
@@ -317,7 +327,7 @@ extern "C" int tc2li_ba_window_batch(tc2li_keyframe_store* store, const tc2li_ba
         // no list is longer than its table: the device arrays need no more room than that, whatever the caller offers
         d.pose_off = (int32_t)n_pose; d.pose_cap = std::min(in.pose_capacity, in.n_keyframes);
         d.pointo_off = (int32_t)n_pointo; d.point_cap = std::min(in.point_capacity, in.n_points);
-        d.edge_off = (int32_t)n_edge; d.edge_cap = std::min(in.edge_capacity, obs_entries);
+        d.edge_off = (int32_t)n_edge; d.edge_cap = edges_optional && !in.edges ? obs_entries : std::min(in.edge_capacity, obs_entries);
         n_kf += in.n_keyframes; n_slot += slot_entries; n_cov += in.n_cov; n_points += in.n_points; n_obs += obs_entries;
         if (d.mark_off >= 0) n_marks += in.n_keyframes;
         if (d.first_off >= 0) n_first += in.n_points;
@@ -343,7 +353,7 @@ extern "C" int tc2li_ba_window_batch(tc2li_keyframe_store* store, const tc2li_ba
     const size_t w_marks = take(n_marks * 4), w_first = take(n_first * 4), w_kfpose = take(n_kf * 4), w_members = take(n_kf * 4),
                  w_lkf = take((n_cov + 2 * np) * 4), w_lstart = take((n_cov + 2 * np) * 4), w_listed = take(n_points * 4), w_estart = take(n_points * 4);
     const size_t work_bytes = off;
-    BawSpace& S = shutdown_owned<BawSpace>();
+    BawSpace& S = shutdown_owned<BawSpaces>().s[space];
     std::lock_guard<std::mutex> lk(S.mu);
     TC2LI_HIP_CHECK(S.io.ensure(io_bytes));
     TC2LI_HIP_CHECK(S.work.ensure(std::max(work_bytes, (size_t)256)));
@@ -386,15 +396,29 @@ extern "C" int tc2li_ba_window_batch(tc2li_keyframe_store* store, const tc2li_ba
     B.edges = (tc2li_ba_edge*)(d + o_edges);
     launch_ba_window(B, st);
     TC2LI_HIP_CHECK(hipGetLastError());
-    TC2LI_HIP_CHECK(hipMemcpyAsync(h + down_from, d + down_from, io_bytes - down_from, hipMemcpyDeviceToHost, st));
+    if (follow) {
+        const int frc = follow->after_gather(B, dev.data(), st);
+        if (frc < 0) { (void)stream_wait_blocking(st); return frc; }
+    }
+    bool edges_wanted = !edges_optional;
+    for (int p = 0; p < n_problems && !edges_wanted; ++p) edges_wanted = problems[p].edges != nullptr;
+    if (edges_wanted) TC2LI_HIP_CHECK(hipMemcpyAsync(h + down_from, d + down_from, io_bytes - down_from, hipMemcpyDeviceToHost, st));
+    else {   // the edges -- five sevenths of the result -- stay where they are
+        TC2LI_HIP_CHECK(hipMemcpyAsync(h + down_from, d + down_from, o_edges - down_from, hipMemcpyDeviceToHost, st));
+        TC2LI_HIP_CHECK(hipMemcpyAsync(h + o_prow, d + o_prow, io_bytes - o_prow, hipMemcpyDeviceToHost, st));
+    }
     TC2LI_HIP_CHECK(stream_wait_blocking(st));
     int short_of_room = -1;
     for (int p = 0; p < n_problems; ++p) {
         const int32_t* counts = (const int32_t*)(h + o_counts) + (size_t)p * TC2LI_BA_WINDOW_COUNTS;
         memcpy(problems[p].counts, counts, TC2LI_BA_WINDOW_COUNTS * 4);
-        if (short_of_room < 0 && !fits(problems[p], counts)) short_of_room = p;
+        if (short_of_room < 0 && !fits(problems[p], counts, edges_optional)) short_of_room = p;
     }
     if (short_of_room >= 0) return capacity_error(entry, problems, short_of_room);
+    if (follow) {
+        const int frc = follow->after_counts();
+        if (frc < 0) return frc;
+    }
     tracking_pool().parallel_for(n_problems, [&](int p) {
         const tc2li_ba_window_problem& in = problems[p];
         const BawProblemDev& D = dev[p];
@@ -407,7 +431,11 @@ extern "C" int tc2li_ba_window_batch(tc2li_keyframe_store* store, const tc2li_ba
         const size_t n_po = (size_t)counts[TC2LI_BA_WINDOW_N_POSES], n_pt = (size_t)counts[TC2LI_BA_WINDOW_N_POINTS];
         get(in.pose_row, o_prow, D.pose_off, n_po, 4); get(in.poses7_out, o_p7, D.pose_off, n_po, 56); get(in.fixed, o_fixed, D.pose_off, n_po, 1);
         get(in.point_row, o_ptrow, D.pointo_off, n_pt, 4); get(in.points3_out, o_p3, D.pointo_off, n_pt, 24);
-        get(in.edges, o_edges, D.edge_off, (size_t)counts[TC2LI_BA_WINDOW_N_EDGES], sizeof(tc2li_ba_edge));
+        if (in.edges) get(in.edges, o_edges, D.edge_off, (size_t)counts[TC2LI_BA_WINDOW_N_EDGES], sizeof(tc2li_ba_edge));
     });
+    if (follow) {
+        const int frc = follow->after_download(B, dev.data(), st);
+        if (frc < 0) return frc;
+    }
     return n_problems;
 }
