@@ -152,7 +152,7 @@ struct StructureBase : BawFollow {
         memcpy(S.h_windows.p, win.data(), (size_t)n * sizeof(BasWindowDev));
         TC2LI_HIP_CHECK(hipMemcpyAsync(S.d_windows.p, S.h_windows.p, (size_t)n * sizeof(BasWindowDev), hipMemcpyHostToDevice, st));
         BasBatch A{};
-        A.n_windows = n; A.max_blocks = max_blocks; A.problems = B.problems; A.counts = B.counts; A.lidar_pose_index = B.lidar_pose_index;
+        A.n_windows = n; A.max_blocks = max_blocks; A.problems = static_cast<const BawProblemDev*>(B.problems); A.counts = B.counts; A.lidar_pose_index = B.lidar_pose_index;
         A.fixed = B.fixed; A.edge_start = B.edge_start; A.edges = B.edges; A.windows = S.d_windows.p;
         A.scratch = reinterpret_cast<int32_t*>(S.scratch.p); A.scratch_rows = S.scratch.p; A.sizes = S.d_sizes.p;
         launch_ba_structure(A, st);

@@ -12,7 +12,7 @@
 //   k_bas_blocks     one workgroup per block of 256 slots: the block's slots sorted by pose, stable.  A slot's place is the number of slots
 //                    with a smaller pose plus the number of earlier slots with the same pose, counted over the 256 poses in LDS (a
 //                    broadcast read each).  The grid is cut from the capacities; a workgroup beyond the window's blocks returns at once.
-// Helpers with a barrier inside (bas_scan_excl, __syncthreads_or) are only called where all 256 threads arrive: every loop around them runs
+// Helpers with a barrier inside (block_scan_excl, __syncthreads_or) are only called where all 256 threads arrive: every loop around them runs
 // to a bound that is the same in all threads, and every early return is taken by the whole workgroup.
 #include <algorithm>
 
@@ -24,29 +24,6 @@ namespace tc2li {
 
 static_assert(kBasMaxFree == kSchurLeanMaxFree, "the device range is the lean sparse path");
 static_assert(kBasThreads == 256 && kBasMaxFree < 255, "a block's rows are bytes; 255 marks a thread past the end");
-
-// Exclusive prefix sum of v over the workgroup's kBasThreads threads, the total in *total.  lds: 4 ints.
-__device__ __forceinline__ int bas_scan_excl(int v, int* lds, int* total) {
-    const int lane = threadIdx.x & 63, w = wave_in_block();
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < kBasThreads / 64; ++k) {
-        const int s = lds[k];
-        if (k < w) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
 
 __global__ __launch_bounds__(kBasThreads) void k_bas_structure(BasBatch B) {
     __shared__ int s_pose[kBasMaxPoses];         // a pose's mark, then its number among the free poses
@@ -109,7 +86,7 @@ __global__ __launch_bounds__(kBasThreads) void k_bas_structure(BasBatch B) {
         const int k = base + tid;
         const bool fr = k < K && !fixed[k] && s_pose[k] != 0;
         int tot;
-        const int at = bas_scan_excl(fr ? 1 : 0, scan, &tot);
+        const int at = block_scan_excl<kBasThreads>(fr ? 1 : 0, scan, &tot);
         if (k < K) {
             const int v = fr ? n_free + at : -1;
             s_pose[k] = v;
@@ -138,7 +115,7 @@ __global__ __launch_bounds__(kBasThreads) void k_bas_structure(BasBatch B) {
             }
         }
         int tot;
-        const int at = bas_scan_excl(nf, scan, &tot);
+        const int at = block_scan_excl<kBasThreads>(nf, scan, &tot);
         if (l < NP) {
             int s = n_slots + at;
             s_pt[l] = e0; s_sb[l] = s;
@@ -245,7 +222,7 @@ __global__ __launch_bounds__(kBasThreads) void k_bas_outliers(const BasOutlierTa
                 erased = ((e.u_right >= 0) == (stereo != 0)) && (T.chi2[i] > limit || !T.depth_positive[i]);
             }
             int tot;
-            const int at = n + bas_scan_excl(erased ? 1 : 0, scan, &tot);
+            const int at = n + block_scan_excl<kBasThreads>(erased ? 1 : 0, scan, &tot);
             if (erased && at < T.capacity) { T.erase_pose[at] = pose; T.erase_point[at] = point; }   // :417, :447
             n += tot;
         }

@@ -2,46 +2,20 @@
 // :157-187, :226-253, :263-384) on the flat graph.  Integer work and copies; no float arithmetic, no MFMA.
 //   k_baw_gather   one workgroup per problem, everything whose order matters:
 //                  local keyframes   cov_kf compacted in its order by a block prefix sum; every keyframe's marks are one int, in LDS up to
-//                                    kBawLdsKeyframes keyframes and in global memory beyond.
-//                  local points      the slots of the local keyframes, concatenated in list order, are numbered q = 0, 1, ...; every slot does
-//                                    an integer atomicMin of q on its point's key (LDS up to kBawLdsPoints points, global memory beyond), the
-//                                    slot whose q is the minimum is the point's first occurrence (:97-101), and a block prefix sum over the
-//                                    flags in q order is the point's place in lLocalMapPoints -- no sort, and minima do not depend on their order.
+//                                    kWinLdsKeyframes keyframes and in global memory beyond.
+//                  local points      window_list_points over the local keyframes (:78-104): first occurrences by an integer atomicMin on the
+//                                    point's key (LDS up to kWinLdsPoints points, global memory beyond) and a block prefix sum.
 //                  fixed cameras     a thread per listed point walks its observations: atomicOr of the fixed bit on every observer that is
 //                                    not marked local (:115-119), and the point's edges counted; a prefix sum gives every point its first edge.
-//                  poses             the marked rows compacted, then ranked by (kf_id, row): a pose's place is the number of smaller keys
-//                                    (a few hundred keyframes at most: members^2 / 256 compares per thread).
-//   k_baw_edges    kBawEdgeBlocks workgroups per problem, a thread per listed point: its row and position, and one edge per observation
-//                  from the first edge on (:277-345), the pixel read from the observer's slot of the keyframe store.
-// Helpers with a barrier inside (block_scan_excl, __syncthreads_count) are only called where all 256 threads arrive: every loop around them
-// runs to a bound that is the same in all threads, and a thread past the end takes part with a zero.
+//                  poses             the marked rows compacted, then ranked by (kf_id, row) (window_compact_members, window_rank_members).
+//   k_window_edges kWinEdgeBlocks workgroups per problem, a thread per listed point: its row and position, and one edge per observation
+//                  from the first edge on (:277-345), the pixel read from the observer's slot of the keyframe store.  The inertial gather
+//                  (inertial_window_kernels.hip) ends with the same kernel.
+// The listing, the compaction, the ranking and the LDS / global dispatch are window_gather_device.hpp's, shared with the inertial gather.
+// Helpers with a barrier inside are only called where all 256 threads arrive (block_scan_excl in launch.hpp says what that takes).
 #include "ba_window_device.hpp"
-#include "launch.hpp"
 
 namespace tc2li {
-
-// Exclusive prefix sum of v over the workgroup's kBawThreads threads, the total in *total.  lds: 4 ints.
-__device__ __forceinline__ int baw_scan_excl(int v, int* lds, int* total) {
-    const int lane = threadIdx.x & 63, w = wave_in_block();
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < kBawThreads / 64; ++k) {
-        const int s = lds[k];
-        if (k < w) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
 
 // marks / first: the problem's keyframe marks and first-occurrence keys, LDS or global (the address space is known after inlining)
 // sh: [0] a local keyframe is the initial one (:85-88), [1 .. 6] vOptKeyFrames of :227-233 as rows
@@ -57,17 +31,16 @@ __device__ __forceinline__ void baw_problem(const BawBatch& B, const BawProblemD
     const int32_t* obs_kf = B.obs_kf + P.obs_off;
     const int32_t* obs_index = B.obs_index + P.obs_off;
     int32_t* list_kf = B.list_kf + P.cov_off + 2 * blockIdx.x;
-    int32_t* list_start = B.list_start + P.cov_off + 2 * blockIdx.x;
     int32_t* listed = B.listed + P.point_off;
     int32_t* edge_start = B.edge_start + P.point_off;
-    int32_t* kf_pose = B.kf_pose + P.kf_off;
+    int32_t* kf_pose = B.vertex_of + P.kf_off;
     int32_t* members = B.members + P.kf_off;
     int32_t* counts = B.counts + (size_t)blockIdx.x * TC2LI_BA_WINDOW_COUNTS;
     const int cur = P.current;
     const int64_t init_id = P.init_kf_id;
 
-    for (int k = tid; k < P.n_kf; k += kBawThreads) marks[k] = 0;
-    for (int p = tid; p < P.n_points; p += kBawThreads) first[p] = 0x7fffffff;
+    for (int k = tid; k < P.n_kf; k += kWinThreads) marks[k] = 0;
+    for (int p = tid; p < P.n_points; p += kWinThreads) first[p] = 0x7fffffff;
     if (tid < 8) sh[tid] = tid == 0 ? 0 : -1;
     __syncthreads();
 
@@ -79,7 +52,7 @@ __device__ __forceinline__ void baw_problem(const BawBatch& B, const BawProblemD
         if (n_cloud) sh[1] = cur;
         if (kf_id[cur] == init_id) atomicOr(&sh[0], 1);
     }
-    for (int base = 0; base < P.n_cov; base += kBawThreads) {
+    for (int base = 0; base < P.n_cov; base += kWinThreads) {
         const int i = base + tid;
         const int k = i < P.n_cov ? cov[i] : -1;
         const int f = k >= 0 ? flags[k] : 3;
@@ -87,7 +60,7 @@ __device__ __forceinline__ void baw_problem(const BawBatch& B, const BawProblemD
         const bool cloud = local && (f & 4);                                         // :231
         if (k >= 0) marks[k] = kBawMarkedLocal | (local ? kBawLocal : 0);            // :73, :75
         int tot;
-        const int at = baw_scan_excl((local ? 1 : 0) | (cloud ? 1 << 16 : 0), scan, &tot);   // at most 256 of each
+        const int at = block_scan_excl<kWinThreads>((local ? 1 : 0) | (cloud ? 1 << 16 : 0), scan, &tot);   // at most 256 of each
         if (local) {
             list_kf[n_local + (at & 0xffff)] = k;
             if (kf_id[k] == init_id) atomicOr(&sh[0], 1);                            // :85-88
@@ -98,49 +71,13 @@ __device__ __forceinline__ void baw_problem(const BawBatch& B, const BawProblemD
     }
     __syncthreads();
 
-    // where the slots of every local keyframe start in the concatenation
-    int n_slots = 0;
-    for (int base = 0; base < n_local; base += kBawThreads) {
-        const int i = base + tid;
-        int len = 0;
-        if (i < n_local) { const int k = list_kf[i]; len = slot_row[k + 1] - slot_row[k]; }
-        int tot;
-        const int at = baw_scan_excl(len, scan, &tot);
-        if (i < n_local) list_start[i] = n_slots + at;
-        n_slots += tot;
-    }
-    __syncthreads();
-
-    // local points (:78-104): the least slot number of every point ...
-    for (int li = 0; li < n_local; ++li) {
-        const int k = list_kf[li];
-        const int s0 = slot_row[k], len = slot_row[k + 1] - s0, q0 = list_start[li];
-        for (int s = tid; s < len; s += kBawThreads) {
-            const int p = slot_point[s0 + s];
-            if (p >= 0 && !(pflags[p] & 3)) atomicMin(&first[p], q0 + s);            // :93-94
-        }
-    }
-    __syncthreads();
-    // ... and the slots that hold it, counted in order (:97-101)
-    int n_listed = 0;
-    for (int li = 0; li < n_local; ++li) {
-        const int k = list_kf[li];
-        const int s0 = slot_row[k], len = slot_row[k + 1] - s0, q0 = list_start[li];
-        for (int base = 0; base < len; base += kBawThreads) {
-            const int s = base + tid;
-            const int p = s < len ? slot_point[s0 + s] : -1;
-            const bool take = p >= 0 && first[p] == q0 + s;                          // only a point that passed :93-94 has a key
-            int tot;
-            const int at = baw_scan_excl(take ? 1 : 0, scan, &tot);
-            if (take) listed[n_listed + at] = p;
-            n_listed += tot;
-        }
-    }
+    // local points (:78-104): a point that is bad or of another map is passed over (:93-94), the others are listed once (:97-101)
+    const int n_listed = window_list_points(list_kf, n_local, slot_row, slot_point, pflags, 3, first, listed, scan);
     __syncthreads();
 
     // fixed cameras (:107-122), and the edges of every listed point counted (:277-345)
     int n_edges = 0, n_without = 0;
-    for (int base = 0; base < n_listed; base += kBawThreads) {
+    for (int base = 0; base < n_listed; base += kWinThreads) {
         const int i = base + tid;
         int ne = 0;
         if (i < n_listed) {
@@ -154,55 +91,36 @@ __device__ __forceinline__ void baw_problem(const BawBatch& B, const BawProblemD
             }
         }
         int tot;
-        const int at = baw_scan_excl(ne, scan, &tot);
+        const int at = block_scan_excl<kWinThreads>(ne, scan, &tot);
         if (i < n_listed) edge_start[i] = n_edges + at;
         n_edges += tot;
         n_without += __syncthreads_count(i < n_listed && ne == 0);
     }
     __syncthreads();
 
-    // the rows that get a pose vertex (:157-187), compacted
-    int n_members = 0, n_fixed = 0;
-    for (int base = 0; base < P.n_kf; base += kBawThreads) {
-        const int k = base + tid;
-        const int m = k < P.n_kf ? marks[k] : 0;
-        const bool member = (m & (kBawLocal | kBawFixed)) != 0, fixed = (m & kBawFixed) != 0;
-        int tot;
-        const int at = baw_scan_excl((member ? 1 : 0) | (fixed ? 1 << 16 : 0), scan, &tot);
-        if (member) members[n_members + (at & 0xffff)] = k;
-        if (k < P.n_kf) kf_pose[k] = -1;
-        n_members += tot & 0xffff;
-        n_fixed += tot >> 16;
-    }
-    __syncthreads();
+    // the rows that get a pose vertex (:157-187), compacted, and the fixed cameras among them counted
+    int n_fixed;
+    const int n_members = window_compact_members(marks, P.n_kf, members, kf_pose, scan, &n_fixed, [](int m) {
+        return ((m & (kBawLocal | kBawFixed)) ? 1 : 0) | ((m & kBawFixed) ? 1 << 16 : 0);
+    });
     const int num_fixed = n_fixed + sh[0];                                           // :123
     if (num_fixed == 0) {                                                            // :126-130
         if (tid < TC2LI_BA_WINDOW_COUNTS) counts[tid] = tid == TC2LI_BA_WINDOW_STATUS ? TC2LI_BA_WINDOW_ABORTED : 0;
         if (tid < TC2LI_BA_WINDOW_MAX_LIDAR) B.lidar_pose_index[(size_t)blockIdx.x * TC2LI_BA_WINDOW_MAX_LIDAR + tid] = -1;
+        if (tid == 0) B.n_emit[blockIdx.x] = 0;
         return;
     }
-    // vertex-id order: a pose's place is the number of members with a smaller (kf_id, row); members ascend by row
+    // vertex-id order
     int32_t* pose_row = B.pose_row + P.pose_off;
     double* poses7_out = B.poses7_out + (size_t)P.pose_off * 7;
     uint8_t* fixed_out = B.fixed + P.pose_off;
     const double* poses7 = B.poses7 + (size_t)P.kf_off * 7;
-    for (int i = tid; i < n_members; i += kBawThreads) {
-        const int k = members[i];
-        const int64_t id = kf_id[k];
-        int r = 0;
-        for (int j = 0; j < n_members; ++j) {
-            const int64_t idj = kf_id[members[j]];
-            r += (idj < id || (idj == id && j < i)) ? 1 : 0;
-        }
-        kf_pose[k] = r;
-        if (r < P.pose_cap) {
-            pose_row[r] = k;
+    window_rank_members(kf_id, members, n_members, kf_pose, P.pose_cap, [&](int k, int r, int64_t id) {
+        pose_row[r] = k;
 #pragma unroll
-            for (int c = 0; c < 7; ++c) poses7_out[(size_t)r * 7 + c] = poses7[(size_t)k * 7 + c];
-            fixed_out[r] = ((marks[k] & kBawFixed) || id == init_id) ? 1 : 0;        // :181, :164
-        }
-    }
-    __syncthreads();   // kf_pose of the BALM keyframes was written by other threads
+        for (int c = 0; c < 7; ++c) poses7_out[(size_t)r * 7 + c] = poses7[(size_t)k * 7 + c];
+        fixed_out[r] = ((marks[k] & kBawFixed) || id == init_id) ? 1 : 0;            // :181, :164
+    });
     const int n_lidar = n_cloud > 2 ? (n_cloud < TC2LI_BA_WINDOW_MAX_LIDAR ? n_cloud : TC2LI_BA_WINDOW_MAX_LIDAR) : 0;   // :235, :244-245
     if (tid < TC2LI_BA_WINDOW_MAX_LIDAR)
         B.lidar_pose_index[(size_t)blockIdx.x * TC2LI_BA_WINDOW_MAX_LIDAR + tid] = tid < n_lidar ? kf_pose[sh[1 + tid]] : -1;   // :249-252
@@ -215,32 +133,32 @@ __device__ __forceinline__ void baw_problem(const BawBatch& B, const BawProblemD
         counts[TC2LI_BA_WINDOW_N_EDGES] = n_edges;
         counts[TC2LI_BA_WINDOW_N_LIDAR] = n_lidar;
         counts[TC2LI_BA_WINDOW_N_POINTS_WITHOUT_EDGE] = n_without;
+        B.n_emit[blockIdx.x] = (n_members <= P.pose_cap && n_listed <= P.point_cap && n_edges <= P.edge_cap) ? n_listed : 0;
     }
 }
 
-__global__ __launch_bounds__(kBawThreads) void k_baw_gather(BawBatch B) {
-    __shared__ int marks[kBawLdsKeyframes];
-    __shared__ int first[kBawLdsPoints];
-    __shared__ int scan[kBawThreads / 64];
+__global__ __launch_bounds__(kWinThreads) void k_baw_gather(BawBatch B) {
+    __shared__ int marks[kWinLdsKeyframes];
+    __shared__ int first[kWinLdsPoints];
+    __shared__ int scan[kWinThreads / 64];
     __shared__ int sh[8];
-    const BawProblemDev& P = B.problems[blockIdx.x];
-    if (P.mark_off < 0 && P.first_off < 0) baw_problem(B, P, marks, first, scan, sh);
-    else if (P.mark_off < 0) baw_problem(B, P, marks, B.first_global + P.first_off, scan, sh);
-    else if (P.first_off < 0) baw_problem(B, P, B.marks_global + P.mark_off, first, scan, sh);
-    else baw_problem(B, P, B.marks_global + P.mark_off, B.first_global + P.first_off, scan, sh);
+    const BawProblemDev& P = window_problem<BawProblemDev>(B, blockIdx.x);
+    window_dispatch(B, P, marks, first, [&](int* m, int* f) __attribute__((always_inline)) { baw_problem(B, P, m, f, scan, sh); });
 }
 
-__global__ __launch_bounds__(kBawThreads) void k_baw_edges(BawBatch B) {
-    const BawProblemDev& P = B.problems[blockIdx.x];
-    const int32_t* counts = B.counts + (size_t)blockIdx.x * TC2LI_BA_WINDOW_COUNTS;
-    const int n_listed = counts[TC2LI_BA_WINDOW_N_POINTS];
-    // nothing to write, or a list of the problem does not fit (the host answers TC2LI_ERR_CAPACITY from the counts)
-    if (counts[TC2LI_BA_WINDOW_STATUS] != TC2LI_BA_WINDOW_OK || counts[TC2LI_BA_WINDOW_N_POSES] > P.pose_cap || n_listed > P.point_cap ||
-        counts[TC2LI_BA_WINDOW_N_EDGES] > P.edge_cap)
-        return;
+// The points and edges of every problem that the gather before it let through (n_emit), for both gathers.  An observation gives an edge
+// when its keyframe has a vertex, is neither bad nor of another map, and sees the point at a keypoint (visual :281, :286, :313; inertial
+// :862, :865, :872, :902).  The first term is the inertial gather's: there a keyframe has a vertex exactly when it carries one of the two
+// marks.  In the visual gather it is always true where the second term lets an observation pass: every observer of a listed point that is
+// neither bad nor of another map is either marked local -- and then in lLocalKeyFrames, because it is not "other" -- or was given the
+// fixed bit by the gather's walk over the same observations; either way it is a member and has its place among the poses.  (A window
+// that ended ABORTED has n_emit 0.)  The tests that compare both device entries byte for byte with their host entries check this.
+__global__ __launch_bounds__(kWinThreads) void k_window_edges(WindowBatch B) {
+    const WindowProblemDev& P = window_problem<WindowProblemDev>(B, blockIdx.x);
+    const int n_listed = B.n_emit[blockIdx.x];
     const uint8_t* flags = B.kf_flags + P.kf_off;
     const int32_t* kf_slot = B.kf_slot + P.kf_off;
-    const int32_t* kf_pose = B.kf_pose + P.kf_off;
+    const int32_t* vertex_of = B.vertex_of + P.kf_off;
     const int32_t* obs_row = B.obs_offsets + P.point_off + blockIdx.x;
     const int32_t* obs_kf = B.obs_kf + P.obs_off;
     const int32_t* obs_index = B.obs_index + P.obs_off;
@@ -250,35 +168,41 @@ __global__ __launch_bounds__(kBawThreads) void k_baw_edges(BawBatch B) {
     int32_t* point_row = B.point_row + P.pointo_off;
     double* points3_out = B.points3_out + (size_t)P.pointo_off * 3;
     tc2li_ba_edge* edges = B.edges + P.edge_off;
-    for (int i = blockIdx.y * kBawThreads + threadIdx.x; i < n_listed; i += kBawEdgeBlocks * kBawThreads) {
+    for (int i = blockIdx.y * kWinThreads + threadIdx.x; i < n_listed; i += kWinEdgeBlocks * kWinThreads) {
         const int p = listed[i];
         point_row[i] = p;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) points3_out[(size_t)i * 3 + c] = positions[(size_t)p * 3 + c];   // :267
+        for (int c = 0; c < 3; ++c) points3_out[(size_t)i * 3 + c] = positions[(size_t)p * 3 + c];   // :267 / :849
         int e = edge_start[i];
         const int o1 = obs_row[p + 1];
         for (int o = obs_row[p]; o < o1; ++o) {
             const int k = obs_kf[o], idx = obs_index[o];
-            if ((flags[k] & 3) || idx < 0) continue;                                 // :281, :286, :313
+            // vertex_of[k] < 0 || (flags[k] & 3) || idx < 0, with both loads in flight before the one branch
+            const int vertex = vertex_of[k], f = flags[k];
+            if ((vertex < 0) | ((f & 3) != 0) | (idx < 0)) continue;
             const uint8_t* slot = B.store.slots + (size_t)kf_slot[k] * B.store.stride;
             const tc2li_keypoint kp = reinterpret_cast<const tc2li_keypoint*>(slot + B.store.keys)[idx];
             const float ur = reinterpret_cast<const float*>(slot + B.store.u_right)[idx];
             tc2li_ba_edge E;
             E.point = i;
-            E.pose = kf_pose[k];
-            E.u = (double)kp.x;                                                      // :290, :318
+            E.pose = vertex;
+            E.u = (double)kp.x;                                                      // :290, :318 / :876-878, :904-909
             E.v = (double)kp.y;
             E.u_right = ur >= 0.f ? (double)ur : -1.0;
-            E.inv_sigma2 = (double)B.inv_level_sigma2[kp.octave];                    // :297, :325
+            E.inv_sigma2 = (double)B.inv_level_sigma2[kp.octave];                    // :297, :325 / :889, :920
             edges[e++] = E;
         }
     }
 }
 
+void launch_window_edges(const WindowBatch& B, hipStream_t st) {
+    TC2LI_LAUNCH(k_window_edges, dim3(B.n_problems, kWinEdgeBlocks), dim3(kWinThreads), 0, st, B);
+}
+
 void launch_ba_window(const BawBatch& B, hipStream_t st) {
     if (B.n_problems <= 0) return;
-    TC2LI_LAUNCH(k_baw_gather, dim3(B.n_problems), dim3(kBawThreads), 0, st, B);
-    TC2LI_LAUNCH(k_baw_edges, dim3(B.n_problems, kBawEdgeBlocks), dim3(kBawThreads), 0, st, B);
+    TC2LI_LAUNCH(k_baw_gather, dim3(B.n_problems), dim3(kWinThreads), 0, st, B);
+    launch_window_edges(B, st);
 }
 
 }  // namespace tc2li

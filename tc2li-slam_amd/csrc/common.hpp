@@ -22,6 +22,15 @@ namespace tc2li {
 
 void set_error(const char* fmt, ...);
 bool device_ready();
+// a CSR offset table of n rows (n + 1 entries): starts at 0 and never falls
+inline bool ascending(const int32_t* off, int n) {
+    if (off[0] != 0) return false;
+    for (int i = 0; i < n; ++i)
+        if (off[i + 1] < off[i]) return false;
+    return true;
+}
+// where the next table of a packed buffer starts: every table on a 256-byte boundary
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // hipStreamSynchronize for waits that last milliseconds (the front-end stages): the calling thread sleeps on an event made with
 // sleeping between looks at an event instead of spinning on the queue -- several host threads wait on the GPU at once and a spinning
 // thread costs a whole core (the GPU boxes give a process 16); see common.cpp.  The host-driven lock-step BA loop (TC2LI_BA_DEVICE_LM=0)

@@ -11,13 +11,6 @@
 namespace tc2li {
 namespace {
 
-bool ascending(const int32_t* off, int n) {
-    if (off[0] != 0) return false;
-    for (int i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return false;
-    return true;
-}
-
 // "" or what is wrong with the rows of a weight map
 const char* validate_rows(const int32_t* offsets, const int32_t* kf, int n_rows, int n_keyframes) {
     for (int r = 0; r < n_rows; ++r)
@@ -192,8 +185,6 @@ int check_covisibles(const char* entry, const int32_t* row_offsets, const int32_
     }
     return 0;
 }
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // the device buffers of a call, kept between calls
 struct ConnSpace {

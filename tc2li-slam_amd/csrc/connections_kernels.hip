@@ -19,29 +19,6 @@
 
 namespace tc2li {
 
-// Exclusive prefix sum of v over the workgroup's kConnThreads threads, the total in *total.  lds: 4 ints.
-__device__ __forceinline__ int block_scan_excl(int v, int* lds, int* total) {
-    const int lane = threadIdx.x & 63, w = wave_in_block();
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < kConnThreads / 64; ++k) {
-        const int s = lds[k];
-        if (k < w) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
 // Orders n entries: entry i has the key key_of(i) (0: not in the list) and goes to the place that is the number of greater keys.
 // wave / n_waves: the wavefronts that share the work, each takes whole groups of 64 places.  Every lane of the wavefront must call it.
 template <class KeyOf>
@@ -113,7 +90,7 @@ __device__ __forceinline__ void conn_problem(const ConnBatch& B, const ConnProbl
         const int k = base + tid;
         const int c = k < P.n_kf ? hist[k] : 0;
         int tot;
-        const int at = block_scan_excl((c > 0 ? 1 : 0) | (c >= TC2LI_CONNECTIONS_TH ? 1 << 16 : 0), scan, &tot);   // at most 256 of each
+        const int at = block_scan_excl<kConnThreads>((c > 0 ? 1 : 0) | (c >= TC2LI_CONNECTIONS_TH ? 1 << 16 : 0), scan, &tot);   // at most 256 of each
         const int a = n_counter + (at & 0xffff), b = n_pairs + (at >> 16);
         if (c > 0 && a < P.counter_cap) { counter_kf[a] = k; counter_weight[a] = c; }
         if (c >= TC2LI_CONNECTIONS_TH && b < P.ordered_cap) { touched_kf[b] = k; touched_weight[b] = c; }
@@ -178,8 +155,8 @@ __device__ __forceinline__ void conn_problem(const ConnBatch& B, const ConnProbl
         const int changed = i < n_pairs ? touched_changed[i] : 0;
         const int len = i < n_pairs ? item_off[i] : 0;
         int tot_c, tot_l;
-        const int c = n_changed + block_scan_excl(changed, scan, &tot_c);
-        const int o = n_entries + block_scan_excl(len, scan, &tot_l);
+        const int c = n_changed + block_scan_excl<kConnThreads>(changed, scan, &tot_c);
+        const int o = n_entries + block_scan_excl<kConnThreads>(len, scan, &tot_l);
         if (i < n_pairs) item_off[i] = changed ? o : -1;
         if (changed) changed_offsets[c] = o;
         n_changed += tot_c;

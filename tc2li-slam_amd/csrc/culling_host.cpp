@@ -12,13 +12,6 @@
 namespace tc2li {
 namespace {
 
-bool ascending(const int32_t* off, int n) {
-    if (off[0] != 0) return false;
-    for (int i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return false;
-    return true;
-}
-
 // "" or what is wrong with problem p
 const char* validate(const tc2li_culling_problem& in) {
     if (in.n_keyframes < 0 || in.n_local < 0 || in.n_points < 0) return "negative size";
@@ -138,8 +131,6 @@ void cull_one(const tc2li_culling_problem& in) {
     if (in.point_bad_after && in.n_points) memcpy(in.point_bad_after, bad.data(), in.n_points);
     if (in.point_nobs_after && in.n_points) memcpy(in.point_nobs_after, nobs.data(), (size_t)in.n_points * 4);
 }
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // the device buffers of a call, kept between calls
 struct CullSpace {

@@ -12,6 +12,33 @@ namespace tc2li {
 // 64 times over; through readfirstlane it is a scalar register, the addresses are scalar arithmetic and the loads take a lane offset
 // (round 6, k_blur7_strips: 78 -> 52 VGPRs from this line alone).
 __device__ __forceinline__ int wave_in_block() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+// Exclusive prefix sum of v over the workgroup's THREADS threads in thread order, the total in *total.  lds: THREADS / 64 ints.
+// There are two barriers inside, so ALL threads of the workgroup must arrive: a loop around a call runs to a bound that is the same in
+// all threads, a thread past the end takes part with a zero, and an early return before a call is taken by the whole workgroup.  After
+// the call lds is free again: two calls in a row may share it.
+template <int THREADS = 256>
+__device__ __forceinline__ int block_scan_excl(int v, int* lds, int* total) {
+    static_assert(THREADS % 64 == 0, "whole wavefronts");
+    const int lane = threadIdx.x & 63, w = wave_in_block();
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(inc, d);
+        if (lane >= d) inc += t;
+    }
+    if (lane == 63) lds[w] = inc;
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < THREADS / 64; ++k) {
+        const int s = lds[k];
+        if (k < w) base += s;
+        tot += s;
+    }
+    __syncthreads();
+    *total = tot;
+    return base + inc - v;
+}
 // Integer sums / minima over a wavefront without the LDS: a __shfl_xor is an LDS permute (10 ns per wavefront instruction per SIMD where a
 // vector instruction is 1.2-2.7, tools/probes/valu_rate.hip), and a butterfly of six of them per value was most of what k_stereo_match's
 // eleven window sums cost.  Four DPP steps inside each row of 16 lanes (quad_perm [1,0,3,2] and [2,3,0,1], row_half_mirror, row_mirror: after

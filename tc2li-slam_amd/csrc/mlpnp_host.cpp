@@ -134,8 +134,6 @@ struct MlpnpSpace {
     PinnedBuf<uint8_t> h_in, h_out;
 };
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 }  // namespace tc2li
 

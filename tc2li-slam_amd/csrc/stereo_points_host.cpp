@@ -127,8 +127,6 @@ void decide_one(const tc2li_stereo_points_frame& f, const tc2li_keyframe_decisio
     points_one(f, u, out.need && !d.create_blocked);
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct StereoPointsSpace {
     std::mutex mu;
     DevBuf<uint8_t> io;

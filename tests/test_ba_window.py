@@ -2,6 +2,9 @@
 tests/ba_window_ref.py, on generated graphs and on hand-made graphs, one per rule, whose expected lists are written out here so that the
 restatement cannot drift.  Every output is an integer or a float widened to double, so the criterion is equality.  No GPU needed."""
 import functools
+import os
+import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -350,3 +353,30 @@ def test_gathered_window_is_a_well_formed_ba_problem(pkg, synthetic):
     theirs = {(int(p), int(k)): (u, v, ur if ur >= 0 else -1.0, s) for p, k, u, v, ur, s in w["edges"].tolist()}   # any negative is monocular (:286)
     listed = set(got["point_row"].tolist())
     assert mine == {k: v for k, v in theirs.items() if k[0] in listed} and len(listed) > 100
+
+
+def test_gather_kernels_keep_their_resources(tmp_path):
+    """The resource report of the compiler for the kernels of the two window gathers and of the structure build: the two gathers, the one
+    edge kernel they share and the three k_bas_* kernels, no private memory in any of them, and no less occupancy than before the gathers
+    were put on one core (3 waves per SIMD for the gathers, whose 41 KB of LDS allow one workgroup per 64 KB; 8 for the edge kernel)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    report = {}
+    for name in ("ba_window_kernels", "inertial_window_kernels", "ba_structure_kernels"):
+        src = os.path.join(root, "tc2li-slam_amd", "csrc", name + ".hip")
+        out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off",
+                              "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", str(tmp_path / (name + ".o"))],
+                             capture_output=True, text=True, check=True).stderr
+        names = re.findall(r"Function Name: (\S+)", out)
+        scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out)]
+        occupancy = [int(v) for v in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", out)]
+        lds = [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", out)]
+        assert len(names) == len(scratch) == len(occupancy) == len(lds), out
+        for n, s, o, l in zip(names, scratch, occupancy, lds):
+            kernel = re.search(r"k_[a-z_]+", n).group(0)
+            assert kernel not in report, names
+            report[kernel] = (s, o, l)
+    print(report)
+    assert sorted(report) == ["k_bas_blocks", "k_bas_outliers", "k_bas_structure", "k_baw_gather", "k_iw_gather", "k_window_edges"], report
+    assert all(s == 0 for s, _, _ in report.values()), report
+    assert report["k_baw_gather"][1] >= 3 and report["k_iw_gather"][1] >= 3 and report["k_window_edges"][1] >= 8, report
+    assert all(l <= 65536 for _, _, l in report.values()), report

@@ -110,6 +110,34 @@ def test_device_slot_shared_by_problems_with_other_flags(pkg, store):
     _check(device_run(pkg, store), batch, want, T.host_run(pkg)(batch), "shared slot")
 
 
+def test_visual_and_inertial_gathers_in_turn(pkg, store):
+    """Both entries list their points with the same code and end with the same edge kernel: on one store and in one process the visual
+    gather, the inertial one and the visual one again -- with a batch of another size -- each give what their host entry gives.  Guards
+    scratch or state that the two paths would share by mistake.  Hand-made graphs of 4 keyframes and 3 points, with flags that make the
+    windows differ."""
+    import ba_window_cases as KV
+    kfs = [dict(slot=0, id=4, prev=1, holds=[0, 1]), dict(slot=0, id=3, prev=2, holds=[1, 2]), dict(slot=0, id=2), dict(slot=0, id=1)]
+    points = [dict(obs={0: 5, 1: 6, 2: 7, 3: 8}), dict(obs={0: 9, 1: -1, 3: 10}), dict(obs={1: 11, 2: 12, 3: 13})]
+    visual, inertial = [], []
+    for vf, nf in (((0, 0, 0, 0), (12, 12, 12, 12)), ((4, 4, 1, 2), (12, 13, 12, 4)), ((0, 2, 4, 0), (8, 12, 13, 12))):
+        vk, nk = [dict(k, flags=f) for k, f in zip(kfs, vf)], [dict(k, flags=f) for k, f in zip(kfs, nf)]
+        visual += [KV.hand(vk, points, 0, [1]), KV.hand(vk, points, 1, [2, 0], init=2)]
+        inertial += [K.hand(nk, points, 0), K.hand(nk, points, 1, in_map=3, rec_init=True)]
+    host_v = pkg.ba_window_batch(visual, K.SIGMA, views=K.WORLD)
+    host_i = T.host_run(pkg)(inertial)
+    assert len({h["edges"].tobytes() for h in host_v}) > 2 and len({h["edges"].tobytes() for h in host_i}) > 2
+    first = pkg.ba_window_batch(visual, K.SIGMA, store=store)
+    second = pkg.inertial_window_batch(inertial, K.SIGMA, store=store)
+    third = pkg.ba_window_batch(visual[2:], K.SIGMA, store=store)
+    for i, (g, h) in enumerate(zip(first, host_v)):
+        KV.assert_equal(g, h, "visual gather, problem %d" % i)
+    for i, (g, h) in enumerate(zip(second, host_i)):
+        K.assert_equal(g, h, "inertial gather after the visual one, problem %d" % i)
+    assert len(third) == 4
+    for i, (g, h) in enumerate(zip(third, host_v[2:])):
+        KV.assert_equal(g, h, "visual gather after the inertial one, problem %d" % i)
+
+
 def test_gathered_window_through_the_inertial_bundle_adjustment(pkg, synthetic):
     """A window gathered on the device goes into tc2li_local_inertial_bundle_adjustment and comes out as the window gathered by the
     restatement does, bit for bit -- and the optimiser accepts the arrays as they are.  The links get their preintegration through

@@ -6,7 +6,7 @@ taken --problems / 16 times each; their flat graphs from tests/ba_window_cases.p
 Per leg: wall time of the whole sequence and CPU seconds of the process (all threads), median and range of --reps after --warmup calls; the
 Python binding's packing of the problem structures is outside the clock.  Every leg runs in a child process of its own under a time limit, so
 that a hang ends that step and nothing more is started on the GPU after it.  The kernels leg repeats the solve calls with
-tc2li_profile_enable(1) and prints the k_bas_* and k_baw_* times of tc2li_profile_report.  The solve leg also checks its poses, points and
+tc2li_profile_enable(1) and prints the k_bas_*, k_baw_* and k_window_* times of tc2li_profile_report.  The solve leg also checks its poses, points and
 outlier pairs against the device leg's arithmetic (the same calls through the Python wrappers) for the first four windows, byte for byte.
 
     python tools/time_ba_window_solve.py [--problems 64] [--reps 20] [--warmup 3] [--json out.json]
@@ -141,7 +141,7 @@ def child(leg, n, reps, warmup):
     res = dict(leg=leg, problems=n, ms=float(np.median(wall)), min_ms=float(min(wall)), max_ms=float(max(wall)), cpu_ms=float(np.median(cpu)),
                cpu_min_ms=float(min(cpu)), cpu_max_ms=float(max(cpu)), iterations=[int(v) for v in results[:N_BASE]])
     if leg == "kernels":
-        res["kernels_ms_per_call"] = {k: v[1] / reps for k, v in capi.profile_report().items() if k.startswith(("k_bas", "k_baw"))}
+        res["kernels_ms_per_call"] = {k: v[1] / reps for k, v in capi.profile_report().items() if k.startswith(("k_bas", "k_baw", "k_window"))}
         capi.profile_enable(False)
     counts = [o["counts"].copy() for o in outs]
     up, down = moved_bytes(problems, counts, "solve" if leg == "kernels" else leg)

@@ -100,7 +100,7 @@ def child(leg, n, reps, warmup):
         assert rc == n
     res = dict(leg=leg, problems=n, ms=float(np.median(times)), min_ms=float(min(times)), max_ms=float(max(times)))
     if leg == "kernels":
-        res["kernels_ms_per_call"] = {k: v[1] / v[0] for k, v in capi.profile_report().items() if k.startswith("k_iw")}
+        res["kernels_ms_per_call"] = {k: v[1] / v[0] for k, v in capi.profile_report().items() if k.startswith(("k_iw", "k_window"))}
         capi.profile_enable(False)
     want = [ref.gather(p, views, sigma) for p in base[:2]]   # the restatement is a Python loop: two windows of the eight
     for i in range(n):
