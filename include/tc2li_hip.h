@@ -2178,6 +2178,62 @@ int tc2li_new_keyframe_batch(const tc2li_stereo_points_frame* frames, const tc2l
 int tc2li_host_new_keyframe_batch(const tc2li_stereo_points_frame* frames, const tc2li_keyframe_decision* decisions,
                                   tc2li_keyframe_verdict* verdicts, int n_frames, const float unproject4[4]);
 
+/* ---- image ingest: what a camera image passes before ORBextractor::operator() sees it -------------------------------------------------
+ * System::TrackStereoLidar (SF/src/System.cc:240-257): with settings_->needToRectify() cv::remap(im, out, M1, M2, INTER_LINEAR) with the
+ * CV_32F maps of SF/src/Settings.cc:523-526 (:241-248), else with needToResize() cv::resize(im, out, newImSize) (:250-252), else a clone
+ * (:254-255).  Tracking::GrabImageStereoLidar (SF/src/Tracking.cc:1646-1671): a 3-channel image through cvtColor RGB2GRAY / BGR2GRAY, a
+ * 4-channel one through RGBA2GRAY / BGRA2GRAY, chosen by mbRGB.  Both steps in one pass: remap or resize first, on the image as delivered,
+ * every channel on its own and rounded to 8 bits; gray is formed from that result (gray first and remap second gives other bytes).
+ * Semantics (a recollection of OpenCV 4.2, parity unpinned: SURVEY.md Appendix B; tests/image_prep_ref.py restates them in numpy):
+ *   gray     (R * 9798 + G * 19235 + B * 3735 + 16384) >> 15;  rgb != 0: channel 0 is R, else B;  a fourth channel is not read.
+ *   remap    INTER_LINEAR, BORDER_CONSTANT 0, maps of the destination's size: sx = cvRound(map_x * 32) (float product, ties to even),
+ *            ix = saturate_cast<short>(sx >> 5), fx = sx & 31, the same in y; taps (iy, ix), (iy, ix + 1), (iy + 1, ix), (iy + 1, ix + 1)
+ *            with weights (32 - fx)(32 - fy) 32, fx (32 - fy) 32, (32 - fx) fy 32, fx fy 32; a tap outside the source reads 0;
+ *            out = (sum + 16384) >> 15.
+ *   resize   INTER_LINEAR as the extractor's pyramid (SF/src/ORBextractor.cc:1156): source coordinate (dx + 0.5) * scale - 0.5, floor and
+ *            clamp, 11-bit weights, (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2; any source and destination size.
+ * Computing the maps (stereoRectify / initUndistortRectifyMap) stays with the caller, and so do 16-bit and float images. */
+enum tc2li_image_prep_mode {
+    TC2LI_IMAGE_PREP_COPY = 0,      /* System.cc:254-255 */
+    TC2LI_IMAGE_PREP_RECTIFY = 1,   /* System.cc:241-248 */
+    TC2LI_IMAGE_PREP_RESIZE = 2     /* System.cc:250-252 */
+};
+typedef struct tc2li_image_prep_params {
+    int32_t src_width, src_height;  /* the image as delivered, 1 .. 16384 */
+    int32_t channels;               /* 1, 3 or 4 interleaved bytes per pixel (Tracking.cc:1646, :1660) */
+    int32_t rgb;                    /* mbRGB (Tracking.cc:1648, :1662) */
+    int32_t mode;                   /* tc2li_image_prep_mode */
+    int32_t dst_width, dst_height;  /* RECTIFY: the maps' size; RESIZE: newImSize; COPY: the source's size.  1 .. 16384 */
+} tc2li_image_prep_params;
+typedef struct tc2li_image_prep tc2li_image_prep;
+/* A handle for calls of up to max_images (1 .. 65535) images.  TC2LI_ERR_INVALID for a channel count other than 1, 3 or 4, a dimension
+ * outside 1 .. 16384, an unknown mode, COPY with a destination size other than the source's; checked before the device is looked for. */
+int tc2li_image_prep_create(const tc2li_image_prep_params* params, int max_images, tc2li_image_prep** out);
+void tc2li_image_prep_destroy(tc2li_image_prep* prep);
+/* The maps of camera 0 (left: M1l, M2l) or 1 (right: M1r, M2r): host memory, dst_height rows of dst_width floats.  They are checked once,
+ * here -- a value that is not finite or has |v| >= 2^24 is TC2LI_ERR_INVALID, cvRound is undefined for it -- and converted once, on the
+ * device, to the fixed-point form above, which stays with the handle; no call converts them again.  The maps are no longer read when
+ * the call returns (stream: NULL = the calling thread's private stream).  The call is ordered behind every tc2li_image_prep_batch queued
+ * on the handle before it: kernels in flight read the maps they were queued with.  TC2LI_ERR_INVALID for a handle whose mode is not
+ * RECTIFY.  A refused call changes nothing: a camera that had no map still has none, one that had an accepted map keeps it. */
+int tc2li_image_prep_set_maps(tc2li_image_prep* prep, int camera, const float* map_x, const float* map_y, void* stream);
+/* n_images images in one launch: image i starts at images + i * image_pitch_bytes, its rows are `stride` bytes apart, and it belongs to
+ * camera i & 1 (the frame convention of tc2li_stereo_match_batch).  images_on_device == 0: host memory, staged and uploaded inside the
+ * call, which then returns when the gray images are complete; != 0: device memory, the call only queues work on `stream` (NULL = the
+ * null stream, as for tc2li_orb_extract_batch).
+ * dev_gray is CALLER-OWNED device memory in exactly the layout tc2li_orb_extract_batch reads (gray image i at dev_gray + i *
+ * gray_pitch_bytes, rows gray_stride bytes apart): pass it on with width = dst_width, height = dst_height, stride = gray_stride,
+ * image_pitch_bytes = gray_pitch_bytes on the same stream.  That call reads level 0 in place, so the buffer must outlive the handle's
+ * pyramids (the stereo matcher and the tracking searches read them), not only the ingest.
+ * TC2LI_ERR_INVALID before any launch for stride < src_width * channels, gray_stride < dst_width, gray images that would overlap, a
+ * RECTIFY call before the maps of both cameras are set; TC2LI_ERR_CAPACITY for n_images > max_images.  Returns n_images. */
+int tc2li_image_prep_batch(tc2li_image_prep* prep, const uint8_t* images, int images_on_device, int n_images, int stride,
+                           size_t image_pitch_bytes, uint8_t* dev_gray, int gray_stride, size_t gray_pitch_bytes, void* stream);
+/* The same contract as plain C++ on the worker pool, every pointer host memory; needs no device.  maps = {x left, y left, x right,
+ * y right} (NULL, or NULL entries, unless the mode is RECTIFY); they are checked as tc2li_image_prep_set_maps checks them, on every call. */
+int tc2li_host_image_prep_batch(const tc2li_image_prep_params* params, const float* const maps[4], const uint8_t* images, int n_images,
+                                int stride, size_t image_pitch_bytes, uint8_t* gray, int gray_stride, size_t gray_pitch_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3292,3 +3292,121 @@ def inertial_window_outliers(edges, edge_chi2, edge_depth_positive, point_bad_no
     n = _check(f(e.ctypes.data, chi2.ctypes.data, dpos.ctypes.data, len(e), bad.ctypes.data, depth.ctypes.data, len(bad), float(initial_chi2),
                  float(final_chi2), int(bool(large)), C.addressof(rejected), pose.ctypes.data, point.ctypes.data, cap))
     return np.stack([pose[:n], point[:n]], 1), bool(rejected.value)
+
+
+# ---- image ingest: clone / remap / resize and colour to gray (System::TrackStereoLidar, Tracking::GrabImageStereoLidar) ------------------
+IMAGE_PREP_COPY, IMAGE_PREP_RECTIFY, IMAGE_PREP_RESIZE = 0, 1, 2
+
+
+class ImagePrepParams(C.Structure):
+    """tc2li_image_prep_params"""
+    _fields_ = [(k, C.c_int32) for k in ("src_width", "src_height", "channels", "rgb", "mode", "dst_width", "dst_height")]
+
+
+def image_prep_params(src_width, src_height, channels=1, rgb=True, mode=IMAGE_PREP_COPY, dst_width=None, dst_height=None):
+    """dst_width / dst_height: the maps' size (RECTIFY) or newImSize (RESIZE); the source's size by default."""
+    return ImagePrepParams(int(src_width), int(src_height), int(channels), int(bool(rgb)), int(mode),
+                           int(src_width if dst_width is None else dst_width), int(src_height if dst_height is None else dst_height))
+
+
+def _image_prep_maps(params, maps):
+    """(xl, yl, xr, yr) -> (the float* [4] the ABI takes, what must stay alive)"""
+    arr = (C.c_void_p * 4)()
+    keep = []
+    for i, m in enumerate(maps or ()):
+        if m is None:
+            continue
+        m = np.ascontiguousarray(m, np.float32)
+        if m.shape != (params.dst_height, params.dst_width):
+            raise ValueError("map %d is %s, the destination is %d x %d" % (i, m.shape, params.dst_height, params.dst_width))
+        keep.append(m)
+        arr[i] = m.ctypes.data
+    return arr, keep
+
+
+class ImagePrep:
+    """tc2li_image_prep: the image ingest on the device.  One handle per image format and mode."""
+
+    def __init__(self, src_width, src_height, channels=1, rgb=True, mode=IMAGE_PREP_COPY, dst_width=None, dst_height=None, max_images=2):
+        self.params = image_prep_params(src_width, src_height, channels, rgb, mode, dst_width, dst_height)
+        self._h = C.c_void_p()
+        f = lib().tc2li_image_prep_create
+        f.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        _check(f(C.addressof(self.params), int(max_images), C.byref(self._h)))
+        self.max_images = int(max_images)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            f = lib().tc2li_image_prep_destroy
+            f.argtypes, f.restype = [C.c_void_p], None
+            f(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_maps(self, camera, map_x, map_y, stream=0):
+        """The CV_32F maps (M1, M2) of camera 0 (left) or 1 (right): checked and converted to fixed point once."""
+        mx, my = np.ascontiguousarray(map_x, np.float32), np.ascontiguousarray(map_y, np.float32)
+        shape = (self.params.dst_height, self.params.dst_width)
+        if mx.shape != shape or my.shape != shape:
+            raise ValueError("maps are %s and %s, the destination is %s" % (mx.shape, my.shape, shape))
+        f = lib().tc2li_image_prep_set_maps
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _check(f(self._h, int(camera), mx.ctypes.data, my.ctypes.data, C.c_void_p(stream)))
+
+    def batch_ptr(self, images_ptr, images_on_device, n_images, stride, image_pitch, gray_ptr, gray_stride, gray_pitch, stream=0):
+        """tc2li_image_prep_batch on plain addresses; gray_ptr is device memory in the layout OrbExtractor.extract_batch_dev reads."""
+        f = lib().tc2li_image_prep_batch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
+        return _check(f(self._h, C.c_void_p(images_ptr), int(bool(images_on_device)), int(n_images), int(stride), int(image_pitch),
+                        C.c_void_p(gray_ptr), int(gray_stride), int(gray_pitch), C.c_void_p(stream)))
+
+
+def host_image_prep_batch_ptr(params, maps, images_ptr, n_images, stride, image_pitch, gray_ptr, gray_stride, gray_pitch):
+    """tc2li_host_image_prep_batch on plain host addresses; maps = (xl, yl, xr, yr) arrays or None."""
+    arr, keep = _image_prep_maps(params, maps)
+    f = lib().tc2li_host_image_prep_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t]
+    rc = _check(f(C.addressof(params), C.addressof(arr) if maps is not None else None, C.c_void_p(images_ptr), int(n_images), int(stride),
+                  int(image_pitch), C.c_void_p(gray_ptr), int(gray_stride), int(gray_pitch)))
+    del keep
+    return rc
+
+
+def image_prep_batch(prep, images, maps=None, host=False, out=None, stream=0):
+    """The images of a step through the ingest; image i belongs to camera i & 1.
+    images: a uint8 array [n, h, w] or [n, h, w, channels] (host memory), or -- host=False only -- a torch uint8 tensor of that shape on
+    the device.
+    host=False: prep is an :class:`ImagePrep` (RECTIFY: after set_maps of both cameras); the gray images go to ``out``, a contiguous torch
+    uint8 device tensor [n, dst_height, dst_width] (made when None), which is returned: hand ``out.data_ptr()`` to
+    ``OrbExtractor.extract_batch_dev`` and keep the tensor alive as long as the extractor's pyramids are read.
+    host=True: prep is an :class:`ImagePrep` or an ImagePrepParams, maps = (xl, yl, xr, yr) for RECTIFY -> numpy [n, dst_height, dst_width]."""
+    p = prep.params if isinstance(prep, ImagePrep) else prep
+    n = int(images.shape[0])
+    want = (n, p.src_height, p.src_width) + ((p.channels,) if p.channels != 1 or len(images.shape) == 4 else ())
+    if tuple(images.shape) != want:
+        raise ValueError("images are %s, expected %s" % (tuple(images.shape), want))
+    row, one = p.src_width * p.channels, p.src_width * p.channels * p.src_height
+    if host:
+        img = np.ascontiguousarray(images, np.uint8)
+        gray = np.empty((n, p.dst_height, p.dst_width), np.uint8)
+        host_image_prep_batch_ptr(p, maps, img.ctypes.data, n, row, one, gray.ctypes.data, p.dst_width, p.dst_width * p.dst_height)
+        return gray
+    import torch
+    if out is None:
+        out = torch.empty((n, p.dst_height, p.dst_width), dtype=torch.uint8, device="cuda")
+    if tuple(out.shape) != (n, p.dst_height, p.dst_width) or out.dtype != torch.uint8 or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("out must be a contiguous uint8 device tensor [%d, %d, %d]" % (n, p.dst_height, p.dst_width))
+    if isinstance(images, torch.Tensor):
+        if images.dtype != torch.uint8 or not images.is_contiguous() or not images.is_cuda:
+            raise ValueError("a torch image batch must be a contiguous uint8 device tensor")
+        ptr, on_device = images.data_ptr(), True
+    else:
+        images = np.ascontiguousarray(images, np.uint8)
+        ptr, on_device = images.ctypes.data, False
+    prep.batch_ptr(ptr, on_device, n, row, one, out.data_ptr(), p.dst_width, p.dst_width * p.dst_height, stream=stream)
+    return out

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace tc2li {
 
 constexpr int kMaxLevels = 12;
@@ -49,6 +51,9 @@ void launch_quadtree_gather(const QuadJob* jobs, const uint32_t* picked, const i
                             int nlevels, int kp_stride, DevKeypoint* kps, DevKeypoint* kps_host, int32_t* n_kp, int32_t* n_kp_host, int32_t* level_counts_host,
                             int32_t* status, hipStream_t st);
 
+// cv::resize(INTER_LINEAR)'s tables for an 8-bit sw x sh -> dw x dh resize: xofs [dw], ialpha [2 dw], yofs [dh], ibeta [2 dh] (orb_host.cpp)
+void build_resize_tables(int sw, int sh, int dw, int dh, std::vector<int>& xofs, std::vector<short>& ialpha, std::vector<int>& yofs,
+                         std::vector<short>& ibeta);
 void launch_resize(const LevelDesc& src, const LevelDesc& dst, const int* xofs, const short* ialpha, const int* yofs,
                    const short* ibeta, int nimg, hipStream_t st);
 // the strip form (and with it the tail) reads the eight taps of four columns out of 8 bytes and stores one destination row per source row

@@ -29,9 +29,9 @@ inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 
-namespace {
+namespace tc2li {
 
-// cv::resize INTER_LINEAR coefficient tables (OpenCV imgproc resize(): 11-bit fixed point)
+// cv::resize INTER_LINEAR coefficient tables (OpenCV imgproc resize(): 11-bit fixed point); shared with the image ingest (orb_device.hpp)
 void build_resize_tables(int sw, int sh, int dw, int dh, std::vector<int>& xofs, std::vector<short>& ialpha,
                          std::vector<int>& yofs, std::vector<short>& ibeta) {
     const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
@@ -56,6 +56,10 @@ void build_resize_tables(int sw, int sh, int dw, int dh, std::vector<int>& xofs,
         ibeta[2 * dy + 1] = sat(fy * 2048);
     }
 }
+
+}  // namespace tc2li
+
+namespace {
 
 int setup_geometry(tc2li_orb* o, int w, int h) {
     if (o->cur_w == w && o->cur_h == h) return TC2LI_OK;
