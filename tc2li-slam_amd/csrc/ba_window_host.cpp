@@ -125,7 +125,7 @@ bool window_one(const tc2li_ba_window_problem& in, const tc2li_keyframe_view* vi
 }
 
 // [0]: tc2li_ba_window_batch's; [1 + group]: a follow-up's that keeps the buffers for the length of a BA on the lock-step context `group`
-struct BawSpaces { WindowSpace s[1 + kMaxLockstepGroups]; };
+struct BawSpaces { PackedSpace s[1 + kMaxLockstepGroups]; };
 
 }  // namespace
 }  // namespace tc2li
@@ -194,7 +194,7 @@ int tc2li::ba_window_batch_run(const char* entry, tc2li_keyframe_store* store, c
         d.cov_off = (int32_t)n_cov; d.n_cov = in.n_cov;
         d.pose_off = (int32_t)n_pose; d.pose_cap = std::min(in.pose_capacity, in.n_keyframes);
         n_cov += in.n_cov; n_pose += d.pose_cap;
-        if (std::max(T.most_rows(p), n_cov + 2 * (size_t)p) > T.kMaxRows) return T.too_many_rows(entry, p);
+        if (std::max(T.most_rows(p), n_cov + 2 * (size_t)p) > kMaxRows) return too_many_rows(entry, p);
     }
     const size_t np = (size_t)n_problems;
     T.take_inputs(n_levels);
@@ -203,19 +203,18 @@ int tc2li::ba_window_batch_run(const char* entry, tc2li_keyframe_store* store, c
     const size_t o_p7 = T.io.take(n_pose * 56), o_prow = T.io.take(n_pose * 4), o_fixed = T.io.take(n_pose);
     T.take_work();
     const size_t w_lkf = T.work.take((n_cov + 2 * np) * 4);
-    WindowSpace& S = shutdown_owned<BawSpaces>().s[space];
+    PackedSpace& S = shutdown_owned<BawSpaces>().s[space];
     std::lock_guard<std::mutex> lk(S.mu);
     TC2LI_HIP_CHECK(T.ensure(S));
-    TC2LI_HIP_CHECK(T.upload(S, inv_level_sigma2, n_levels, st, [&](int, const tc2li_ba_window_problem& in, const BawProblemDev& d) {
+    TC2LI_HIP_CHECK(T.upload_tables(inv_level_sigma2, n_levels, st, [&](int, const tc2li_ba_window_problem& in, const BawProblemDev& d) {
         T.io.put(o_pose, d.kf_off, in.poses7, (size_t)in.n_keyframes, 56);
         T.io.put(o_cov, d.cov_off, in.cov_kf, (size_t)in.n_cov, 4);
     }));
-    uint8_t* d = S.io.p;
-    uint8_t* h = S.h_io.p;
+    uint8_t* d = T.d_io;
     const BawProblemDev* dev = T.dev.data();
     BawBatch B{};
-    T.bind(B, where, d, S.work.p);
-    B.poses7 = (const double*)(d + o_pose); B.cov_kf = (const int32_t*)(d + o_cov); B.list_kf = (int32_t*)(S.work.p + w_lkf);
+    T.bind(B, where);
+    B.poses7 = (const double*)(d + o_pose); B.cov_kf = (const int32_t*)(d + o_cov); B.list_kf = T.dev_work<int32_t>(w_lkf);
     B.counts = (int32_t*)(d + T.o_counts); B.lidar_pose_index = (int32_t*)(d + T.o_lidar); B.pose_row = (int32_t*)(d + o_prow);
     B.poses7_out = (double*)(d + o_p7); B.fixed = d + o_fixed;
     launch_ba_window(B, st);
@@ -226,10 +225,10 @@ int tc2li::ba_window_batch_run(const char* entry, tc2li_keyframe_store* store, c
     }
     bool edges_wanted = !edges_optional;
     for (int p = 0; p < n_problems && !edges_wanted; ++p) edges_wanted = problems[p].edges != nullptr;
-    if (edges_wanted) TC2LI_HIP_CHECK(hipMemcpyAsync(h + T.down_from, d + T.down_from, T.io.off - T.down_from, hipMemcpyDeviceToHost, st));
+    if (edges_wanted) TC2LI_HIP_CHECK(T.download(T.down_from, T.io.off, st));
     else {   // the edges -- five sevenths of the result -- stay where they are
-        TC2LI_HIP_CHECK(hipMemcpyAsync(h + T.down_from, d + T.down_from, T.o_edges - T.down_from, hipMemcpyDeviceToHost, st));
-        TC2LI_HIP_CHECK(hipMemcpyAsync(h + T.o_after_edges, d + T.o_after_edges, T.io.off - T.o_after_edges, hipMemcpyDeviceToHost, st));
+        TC2LI_HIP_CHECK(T.download(T.down_from, T.o_edges, st));
+        TC2LI_HIP_CHECK(T.download(T.o_after_edges, T.io.off, st));
     }
     TC2LI_HIP_CHECK(stream_wait_blocking(st));
     const int short_of_room =

@@ -7,6 +7,7 @@
 
 #include "common.hpp"
 #include "connections_device.hpp"
+#include "packed_batch.hpp"
 
 namespace tc2li {
 namespace {
@@ -50,14 +51,7 @@ int validate_all(const char* entry, const tc2li_connections_problem* problems, i
         set_error("%s: null or negative argument", entry);
         return TC2LI_ERR_INVALID;
     }
-    std::vector<const char*> what(n_problems, "");
-    tracking_pool().parallel_for(n_problems, [&](int p) { what[p] = validate(problems[p]); });
-    for (int p = 0; p < n_problems; ++p)
-        if (what[p][0]) {
-            set_error("%s: problem %d: %s", entry, p, what[p]);
-            return TC2LI_ERR_INVALID;
-        }
-    return 0;
+    return validate_each(entry, "problem", n_problems, invalid_if([&](int p) { return validate(problems[p]); }));
 }
 
 // KeyFrame::UpdateBestCovisibles (:216-238) on keys: sorted ascending (:224), read from the back (:231-232)
@@ -186,18 +180,6 @@ int check_covisibles(const char* entry, const int32_t* row_offsets, const int32_
     return 0;
 }
 
-// the device buffers of a call, kept between calls
-struct ConnSpace {
-    std::mutex mu;
-    DevBuf<uint8_t> io, work;
-    PinnedBuf<uint8_t> h_io;
-};
-struct CovisSpace {
-    std::mutex mu;
-    DevBuf<uint8_t> io;
-    PinnedBuf<uint8_t> h_io;
-};
-
 }  // namespace
 }  // namespace tc2li
 
@@ -216,13 +198,8 @@ extern "C" int tc2li_host_update_connections_batch(const tc2li_connections_probl
     const char* entry = "tc2li_host_update_connections_batch";
     const int rc = validate_all(entry, problems, n_problems);
     if (rc < 0) return rc;
-    // sizes first: on TC2LI_ERR_CAPACITY no list of any problem is written
-    std::vector<uint8_t> ok(n_problems, 1);
-    tracking_pool().parallel_for(n_problems, [&](int p) { ok[p] = connections_one(problems[p], false); });
-    for (int p = 0; p < n_problems; ++p)
-        if (!ok[p]) return capacity_error(entry, problems, p);
-    tracking_pool().parallel_for(n_problems, [&](int p) { connections_one(problems[p], true); });
-    return n_problems;
+    return size_then_write(n_problems, [&](int p, bool write) { return connections_one(problems[p], write); },
+                           [&](int p) { return capacity_error(entry, problems, p); });
 }
 
 extern "C" int tc2li_update_connections_batch(const tc2li_connections_problem* problems, int n_problems, void* stream) {
@@ -252,90 +229,69 @@ extern "C" int tc2li_update_connections_batch(const tc2li_connections_problem* p
         if (d.hist_off >= 0) n_hist += in.n_keyframes;
         n_counter += in.counter_capacity; n_items += in.ordered_capacity; n_changed += in.changed_capacity;
         if (std::max(std::max(std::max(n_kf + p, n_conn), std::max(n_slots, n_points + p)), std::max(std::max(n_obs, n_counter), std::max(n_items + p, n_changed))) >
-            0x7fffff00u) {
-            set_error("%s: the batch up to problem %d has more than 2^31 rows in one table; split it", entry, p);
-            return TC2LI_ERR_INVALID;
-        }
+            kMaxRows)
+            return too_many_rows(entry, p);
     }
     const size_t np = (size_t)n_problems;
     // one buffer: [inputs | outputs]; the upload is the first part, the download the second
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off = align256(off + bytes); return o; };
-    const size_t o_prob = take(np * sizeof(ConnProblemDev)), o_poi = take(n_items * 4), o_flags = take(n_kf), o_crow = take((n_kf + np) * 4),
-                 o_ckf = take(n_conn * 4), o_cw = take(n_conn * 4), o_spt = take(n_slots * 4), o_pbad = take(n_points), o_orow = take((n_points + np) * 4),
-                 o_okf = take(n_obs * 4);
-    const size_t up_bytes = off, down_from = off;
-    const size_t o_counts = take(np * TC2LI_CONNECTIONS_COUNTS * 4), o_cnkf = take(n_counter * 4), o_cnw = take(n_counter * 4), o_okfs = take(n_items * 4),
-                 o_ows = take(n_items * 4), o_tkf = take(n_items * 4), o_tch = take(n_items), o_choff = take((n_items + np) * 4), o_chkf = take(n_changed * 4),
-                 o_chw = take(n_changed * 4);
-    const size_t io_bytes = off;
-    off = 0;
-    const size_t o_hist = take(n_hist * 4), o_tw = take(n_items * 4), o_ioff = take(n_items * 4), o_ifound = take(n_items);
-    const size_t work_bytes = off;
-    ConnSpace& S = shutdown_owned<ConnSpace>();
+    PackedTransfer T;
+    Packer &io = T.io, &work = T.work;
+    const size_t o_prob = io.take(np * sizeof(ConnProblemDev)), o_poi = io.take(n_items * 4), o_flags = io.take(n_kf), o_crow = io.take((n_kf + np) * 4),
+                 o_ckf = io.take(n_conn * 4), o_cw = io.take(n_conn * 4), o_spt = io.take(n_slots * 4), o_pbad = io.take(n_points),
+                 o_orow = io.take((n_points + np) * 4), o_okf = io.take(n_obs * 4);
+    T.outputs_begin();
+    const size_t o_counts = io.take(np * TC2LI_CONNECTIONS_COUNTS * 4), o_cnkf = io.take(n_counter * 4), o_cnw = io.take(n_counter * 4),
+                 o_okfs = io.take(n_items * 4), o_ows = io.take(n_items * 4), o_tkf = io.take(n_items * 4), o_tch = io.take(n_items),
+                 o_choff = io.take((n_items + np) * 4), o_chkf = io.take(n_changed * 4), o_chw = io.take(n_changed * 4);
+    const size_t o_hist = work.take(n_hist * 4), o_tw = work.take(n_items * 4), o_ioff = work.take(n_items * 4), o_ifound = work.take(n_items);
+    PackedSpace& S = shutdown_owned<PackedSpace, kSpaceConnections>();
     std::lock_guard<std::mutex> lk(S.mu);
-    TC2LI_HIP_CHECK(S.io.ensure(io_bytes));
-    TC2LI_HIP_CHECK(S.work.ensure(std::max(work_bytes, (size_t)256)));
-    TC2LI_HIP_CHECK(S.h_io.ensure(io_bytes));
-    uint8_t* h = S.h_io.p;
-    memcpy(h + o_prob, dev.data(), np * sizeof(ConnProblemDev));
+    TC2LI_HIP_CHECK(T.ensure(S));
+    io.put(o_prob, 0, dev.data(), np, sizeof(ConnProblemDev));
     tracking_pool().parallel_for(n_problems, [&](int p) {
         const tc2li_connections_problem& in = problems[p];
         const ConnProblemDev& d = dev[p];
         const size_t nk = (size_t)in.n_keyframes, nc = (size_t)in.conn_offsets[in.n_keyframes], npt = (size_t)in.n_points, no = (size_t)in.obs_offsets[in.n_points];
-        auto put = [h](size_t o, size_t start, const void* src, size_t count, size_t width) {
-            if (count) memcpy(h + o + start * width, src, count * width);
-        };
-        int32_t* poi = (int32_t*)(h + o_poi) + d.ordered_off;
+        int32_t* poi = T.host<int32_t>(o_poi) + d.ordered_off;
         for (int i = 0; i < in.ordered_capacity; ++i) poi[i] = p;
-        put(o_flags, d.kf_off, in.kf_flags, nk, 1);
-        put(o_crow, d.conn_row_off, in.conn_offsets, nk + 1, 4);
-        put(o_ckf, d.conn_off, in.conn_kf, nc, 4); put(o_cw, d.conn_off, in.conn_weight, nc, 4);
-        put(o_spt, d.slot_off, in.slot_point, in.n_slots, 4);
-        put(o_pbad, d.point_off, in.point_bad, npt, 1);
-        put(o_orow, d.obs_row_off, in.obs_offsets, npt + 1, 4);
-        put(o_okf, d.obs_off, in.obs_kf, no, 4);
+        io.put(o_flags, d.kf_off, in.kf_flags, nk, 1);
+        io.put(o_crow, d.conn_row_off, in.conn_offsets, nk + 1, 4);
+        io.put(o_ckf, d.conn_off, in.conn_kf, nc, 4); io.put(o_cw, d.conn_off, in.conn_weight, nc, 4);
+        io.put(o_spt, d.slot_off, in.slot_point, in.n_slots, 4);
+        io.put(o_pbad, d.point_off, in.point_bad, npt, 1);
+        io.put(o_orow, d.obs_row_off, in.obs_offsets, npt + 1, 4);
+        io.put(o_okf, d.obs_off, in.obs_kf, no, 4);
     });
-    TC2LI_HIP_CHECK(hipMemcpyAsync(S.io.p, h, up_bytes, hipMemcpyHostToDevice, st));
-    uint8_t* d = S.io.p;
-    uint8_t* w = S.work.p;
+    TC2LI_HIP_CHECK(T.upload(st));
     ConnBatch B{};
     B.n_problems = n_problems; B.n_items = (int)n_items;
-    B.problems = (const ConnProblemDev*)(d + o_prob); B.problem_of_item = (const int32_t*)(d + o_poi);
-    B.kf_flags = d + o_flags; B.conn_offsets = (const int32_t*)(d + o_crow); B.conn_kf = (const int32_t*)(d + o_ckf);
-    B.conn_weight = (const int32_t*)(d + o_cw); B.slot_point = (const int32_t*)(d + o_spt); B.point_bad = d + o_pbad;
-    B.obs_offsets = (const int32_t*)(d + o_orow); B.obs_kf = (const int32_t*)(d + o_okf);
-    B.hist = (int32_t*)(w + o_hist); B.touched_weight = (int32_t*)(w + o_tw); B.item_off = (int32_t*)(w + o_ioff); B.item_found = w + o_ifound;
-    B.counts = (int32_t*)(d + o_counts); B.counter_kf = (int32_t*)(d + o_cnkf); B.counter_weight = (int32_t*)(d + o_cnw);
-    B.ordered_kf = (int32_t*)(d + o_okfs); B.ordered_weight = (int32_t*)(d + o_ows); B.touched_kf = (int32_t*)(d + o_tkf);
-    B.touched_changed = d + o_tch; B.changed_offsets = (int32_t*)(d + o_choff); B.changed_kf = (int32_t*)(d + o_chkf);
-    B.changed_weight = (int32_t*)(d + o_chw);
+    B.problems = T.dev<const ConnProblemDev>(o_prob); B.problem_of_item = T.dev<const int32_t>(o_poi);
+    B.kf_flags = T.dev<const uint8_t>(o_flags); B.conn_offsets = T.dev<const int32_t>(o_crow); B.conn_kf = T.dev<const int32_t>(o_ckf);
+    B.conn_weight = T.dev<const int32_t>(o_cw); B.slot_point = T.dev<const int32_t>(o_spt); B.point_bad = T.dev<const uint8_t>(o_pbad);
+    B.obs_offsets = T.dev<const int32_t>(o_orow); B.obs_kf = T.dev<const int32_t>(o_okf);
+    B.hist = T.dev_work<int32_t>(o_hist); B.touched_weight = T.dev_work<int32_t>(o_tw); B.item_off = T.dev_work<int32_t>(o_ioff);
+    B.item_found = T.dev_work<uint8_t>(o_ifound);
+    B.counts = T.dev<int32_t>(o_counts); B.counter_kf = T.dev<int32_t>(o_cnkf); B.counter_weight = T.dev<int32_t>(o_cnw);
+    B.ordered_kf = T.dev<int32_t>(o_okfs); B.ordered_weight = T.dev<int32_t>(o_ows); B.touched_kf = T.dev<int32_t>(o_tkf);
+    B.touched_changed = T.dev<uint8_t>(o_tch); B.changed_offsets = T.dev<int32_t>(o_choff); B.changed_kf = T.dev<int32_t>(o_chkf);
+    B.changed_weight = T.dev<int32_t>(o_chw);
     launch_update_connections(B, st);
     TC2LI_HIP_CHECK(hipGetLastError());
-    TC2LI_HIP_CHECK(hipMemcpyAsync(h + down_from, d + down_from, io_bytes - down_from, hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(stream_wait_blocking(st));
-    int short_of_room = -1;
-    for (int p = 0; p < n_problems; ++p) {
-        const int32_t* counts = (const int32_t*)(h + o_counts) + (size_t)p * TC2LI_CONNECTIONS_COUNTS;
-        memcpy(problems[p].counts, counts, TC2LI_CONNECTIONS_COUNTS * 4);
-        if (short_of_room < 0 && !fits(problems[p], counts)) short_of_room = p;
-    }
+    TC2LI_HIP_CHECK(T.download_and_wait(st));
+    const int short_of_room = copy_counts(problems, n_problems, T.host<const int32_t>(o_counts), TC2LI_CONNECTIONS_COUNTS, fits);
     if (short_of_room >= 0) return capacity_error(entry, problems, short_of_room);
     tracking_pool().parallel_for(n_problems, [&](int p) {
         const tc2li_connections_problem& in = problems[p];
         const ConnProblemDev& D = dev[p];
         const int32_t* counts = in.counts;
         if (counts[TC2LI_CONNECTIONS_STATUS] == TC2LI_CONNECTIONS_UNCHANGED) return;
-        auto get = [h](void* dst, size_t o, size_t start, size_t count, size_t width) {
-            if (count) memcpy(dst, h + o + start * width, count * width);
-        };
         const size_t nc = (size_t)counts[TC2LI_CONNECTIONS_N_COUNTER], no = (size_t)counts[TC2LI_CONNECTIONS_N_ORDERED];
-        get(in.counter_kf, o_cnkf, D.counter_off, nc, 4); get(in.counter_weight, o_cnw, D.counter_off, nc, 4);
-        get(in.ordered_kf, o_okfs, D.ordered_off, no, 4); get(in.ordered_weight, o_ows, D.ordered_off, no, 4);
-        get(in.touched_kf, o_tkf, D.ordered_off, no, 4); get(in.touched_changed, o_tch, D.ordered_off, no, 1);
-        get(in.changed_offsets, o_choff, (size_t)D.ordered_off + p, (size_t)counts[TC2LI_CONNECTIONS_N_CHANGED] + 1, 4);
-        get(in.changed_kf, o_chkf, D.changed_off, (size_t)counts[TC2LI_CONNECTIONS_N_CHANGED_ENTRIES], 4);
-        get(in.changed_weight, o_chw, D.changed_off, (size_t)counts[TC2LI_CONNECTIONS_N_CHANGED_ENTRIES], 4);
+        io.get(in.counter_kf, o_cnkf, D.counter_off, nc, 4); io.get(in.counter_weight, o_cnw, D.counter_off, nc, 4);
+        io.get(in.ordered_kf, o_okfs, D.ordered_off, no, 4); io.get(in.ordered_weight, o_ows, D.ordered_off, no, 4);
+        io.get(in.touched_kf, o_tkf, D.ordered_off, no, 4); io.get(in.touched_changed, o_tch, D.ordered_off, no, 1);
+        io.get(in.changed_offsets, o_choff, (size_t)D.ordered_off + p, (size_t)counts[TC2LI_CONNECTIONS_N_CHANGED] + 1, 4);
+        io.get(in.changed_kf, o_chkf, D.changed_off, (size_t)counts[TC2LI_CONNECTIONS_N_CHANGED_ENTRIES], 4);
+        io.get(in.changed_weight, o_chw, D.changed_off, (size_t)counts[TC2LI_CONNECTIONS_N_CHANGED_ENTRIES], 4);
     });
     return n_problems;
 }
@@ -369,38 +325,33 @@ extern "C" int tc2li_update_best_covisibles_batch(const int32_t* row_offsets, co
     if (n_rows == 0) return 0;
     hipStream_t st = stream ? (hipStream_t)stream : private_stream();
     const size_t nr = (size_t)n_rows, ne = (size_t)row_offsets[n_rows], nk = (size_t)n_keyframes;
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off = align256(off + bytes); return o; };
-    const size_t o_row = take((nr + 1) * 4), o_kf = take(ne * 4), o_w = take(ne * 4), o_bad = take(nk);
-    const size_t up_bytes = off, down_from = off;
-    const size_t o_count = take(nr * 4), o_okf = take(ne * 4), o_ow = take(ne * 4);
-    CovisSpace& S = shutdown_owned<CovisSpace>();
+    PackedTransfer T;
+    Packer& io = T.io;
+    const size_t o_row = io.take((nr + 1) * 4), o_kf = io.take(ne * 4), o_w = io.take(ne * 4), o_bad = io.take(nk);
+    T.outputs_begin();
+    const size_t o_count = io.take(nr * 4), o_okf = io.take(ne * 4), o_ow = io.take(ne * 4);
+    PackedSpace& S = shutdown_owned<PackedSpace, kSpaceCovisibles>();
     std::lock_guard<std::mutex> lk(S.mu);
-    TC2LI_HIP_CHECK(S.io.ensure(off));
-    TC2LI_HIP_CHECK(S.h_io.ensure(off));
-    uint8_t* h = S.h_io.p;
-    memcpy(h + o_row, row_offsets, (nr + 1) * 4);
-    if (ne) { memcpy(h + o_kf, row_kf, ne * 4); memcpy(h + o_w, row_weight, ne * 4); }
-    if (nk && bad) memcpy(h + o_bad, bad, nk);
-    TC2LI_HIP_CHECK(hipMemcpyAsync(S.io.p, h, up_bytes, hipMemcpyHostToDevice, st));
-    uint8_t* d = S.io.p;
+    TC2LI_HIP_CHECK(T.ensure(S));
+    io.put(o_row, 0, row_offsets, nr + 1, 4);
+    io.put(o_kf, 0, row_kf, ne, 4); io.put(o_w, 0, row_weight, ne, 4);
+    if (bad) io.put(o_bad, 0, bad, nk, 1);
+    TC2LI_HIP_CHECK(T.upload(st));
     CovisBatch B{};
     B.n_rows = n_rows;
-    B.row_offsets = (const int32_t*)(d + o_row); B.row_kf = (const int32_t*)(d + o_kf); B.row_weight = (const int32_t*)(d + o_w); B.bad = d + o_bad;
-    B.out_count = (int32_t*)(d + o_count); B.out_kf = (int32_t*)(d + o_okf); B.out_weight = (int32_t*)(d + o_ow);
+    B.row_offsets = T.dev<const int32_t>(o_row); B.row_kf = T.dev<const int32_t>(o_kf); B.row_weight = T.dev<const int32_t>(o_w);
+    B.bad = T.dev<const uint8_t>(o_bad);
+    B.out_count = T.dev<int32_t>(o_count); B.out_kf = T.dev<int32_t>(o_okf); B.out_weight = T.dev<int32_t>(o_ow);
     launch_update_best_covisibles(B, st);
     TC2LI_HIP_CHECK(hipGetLastError());
-    TC2LI_HIP_CHECK(hipMemcpyAsync(h + down_from, d + down_from, off - down_from, hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(stream_wait_blocking(st));
+    TC2LI_HIP_CHECK(T.download_and_wait(st));
     // the device wrote every list at its row's start; close the gaps the bad keyframes left
-    const int32_t* count = (const int32_t*)(h + o_count);
+    const int32_t* count = T.host<const int32_t>(o_count);
     int at = 0;
     for (int r = 0; r < n_rows; ++r) {
         out_offsets[r] = at;
-        if (count[r]) {
-            memcpy(out_kf + at, (const int32_t*)(h + o_okf) + row_offsets[r], (size_t)count[r] * 4);
-            memcpy(out_weight + at, (const int32_t*)(h + o_ow) + row_offsets[r], (size_t)count[r] * 4);
-        }
+        io.get(out_kf + at, o_okf, row_offsets[r], (size_t)count[r], 4);
+        io.get(out_weight + at, o_ow, row_offsets[r], (size_t)count[r], 4);
         at += count[r];
     }
     out_offsets[n_rows] = at;

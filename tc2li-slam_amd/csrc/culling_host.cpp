@@ -8,6 +8,7 @@
 
 #include "common.hpp"
 #include "culling_device.hpp"
+#include "packed_batch.hpp"
 
 namespace tc2li {
 namespace {
@@ -42,14 +43,7 @@ int validate_all(const char* entry, const tc2li_culling_problem* problems, int n
         set_error("%s: null or negative argument", entry);
         return TC2LI_ERR_INVALID;
     }
-    std::vector<const char*> what(n_problems, "");
-    tracking_pool().parallel_for(n_problems, [&](int p) { what[p] = validate(problems[p]); });
-    for (int p = 0; p < n_problems; ++p)
-        if (what[p][0]) {
-            set_error("%s: problem %d: %s", entry, p, what[p]);
-            return TC2LI_ERR_INVALID;
-        }
-    return 0;
+    return validate_each(entry, "problem", n_problems, invalid_if([&](int p) { return validate(problems[p]); }));
 }
 
 // nMPs and nRedundantObservations of keyframe kf on the current state (:959-1019)
@@ -132,18 +126,6 @@ void cull_one(const tc2li_culling_problem& in) {
     if (in.point_nobs_after && in.n_points) memcpy(in.point_nobs_after, nobs.data(), (size_t)in.n_points * 4);
 }
 
-// the device buffers of a call, kept between calls
-struct CullSpace {
-    std::mutex mu;
-    DevBuf<uint8_t> io, work;
-    PinnedBuf<uint8_t> h_io;
-};
-struct MpCullSpace {
-    std::mutex mu;
-    DevBuf<uint8_t> io;
-    PinnedBuf<uint8_t> h_io;
-};
-
 }  // namespace
 }  // namespace tc2li
 
@@ -157,7 +139,8 @@ extern "C" int tc2li_host_keyframe_culling_batch(const tc2li_culling_problem* pr
 }
 
 extern "C" int tc2li_keyframe_culling_batch(const tc2li_culling_problem* problems, int n_problems, void* stream) {
-    const int rc = validate_all("tc2li_keyframe_culling_batch", problems, n_problems);
+    const char* entry = "tc2li_keyframe_culling_batch";
+    const int rc = validate_all(entry, problems, n_problems);
     if (rc < 0) return rc;
     if (!device_ready()) return TC2LI_ERR_NO_DEVICE;
     if (n_problems == 0) return 0;
@@ -176,88 +159,75 @@ extern "C" int tc2li_keyframe_culling_batch(const tc2li_culling_problem* problem
         d.current_id = in.current_id; d.last_id = in.last_id;
         n_kf += in.n_keyframes; n_slots += in.slot_offsets[in.n_keyframes]; n_local += in.n_local; n_points += in.n_points;
         n_obs += in.obs_offsets[in.n_points];
-        if (std::max(std::max(n_kf + p, n_slots), std::max(n_points + p, n_obs)) > 0x7fffff00u) {
-            set_error("tc2li_keyframe_culling_batch: the batch up to problem %d has more than 2^31 rows in one table; split it", p);
-            return TC2LI_ERR_INVALID;
-        }
+        if (std::max(std::max(n_kf + p, n_slots), std::max(n_points + p, n_obs)) > kMaxRows) return too_many_rows(entry, p);
     }
     const size_t np = (size_t)n_problems;
     // one buffer: [inputs | state with initial values | outputs]; the upload is the first two parts, the download the last two
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off = align256(off + bytes); return o; };
-    const size_t o_prob = take(np * sizeof(CullProblemDev)), o_pol = take(n_local * 4), o_flags = take(n_kf), o_id = take(n_kf * 8), o_time = take(n_kf * 8),
-                 o_pos = take(n_kf * 12), o_thd = take(n_kf * 4), o_srow = take((n_kf + np) * 4), o_spt = take(n_slots * 4), o_sdep = take(n_slots * 4),
-                 o_soct = take(n_slots), o_local = take(n_local * 4), o_orow = take((n_points + np) * 4), o_okf = take(n_obs * 4), o_ooct = take(n_obs),
-                 o_ow = take(n_obs), o_prev = take(n_kf * 4), o_next = take(n_kf * 4);
-    const size_t o_nobs = take(n_points * 4), o_bad = take(n_points);
-    const size_t up_bytes = off, down_from = o_nobs;
-    const size_t o_verdict = take(n_local * 4), o_nmps = take(n_local * 4), o_nred = take(n_local * 4), o_nvis = take(np * 4);
-    const size_t io_bytes = off;
-    off = 0;
-    const size_t o_kfbad = take(n_kf), o_dead = take(n_obs), o_changed = take(n_points), o_claim = take(n_points * 4);
-    const size_t zero_bytes = off;
-    const size_t o_spec = take(n_local * 8);
-    const size_t work_bytes = off;
-    CullSpace& S = shutdown_owned<CullSpace>();
+    PackedTransfer T;
+    Packer &io = T.io, &work = T.work;
+    const size_t o_prob = io.take(np * sizeof(CullProblemDev)), o_pol = io.take(n_local * 4), o_flags = io.take(n_kf), o_id = io.take(n_kf * 8),
+                 o_time = io.take(n_kf * 8), o_pos = io.take(n_kf * 12), o_thd = io.take(n_kf * 4), o_srow = io.take((n_kf + np) * 4),
+                 o_spt = io.take(n_slots * 4), o_sdep = io.take(n_slots * 4), o_soct = io.take(n_slots), o_local = io.take(n_local * 4),
+                 o_orow = io.take((n_points + np) * 4), o_okf = io.take(n_obs * 4), o_ooct = io.take(n_obs), o_ow = io.take(n_obs),
+                 o_prev = io.take(n_kf * 4), o_next = io.take(n_kf * 4);
+    T.state_begins();
+    const size_t o_nobs = io.take(n_points * 4), o_bad = io.take(n_points);
+    T.outputs_begin();
+    const size_t o_verdict = io.take(n_local * 4), o_nmps = io.take(n_local * 4), o_nred = io.take(n_local * 4), o_nvis = io.take(np * 4);
+    const size_t o_kfbad = work.take(n_kf), o_dead = work.take(n_obs), o_changed = work.take(n_points), o_claim = work.take(n_points * 4);
+    const size_t zero_bytes = work.off;
+    const size_t o_spec = work.take(n_local * 8);
+    PackedSpace& S = shutdown_owned<PackedSpace, kSpaceKeyframeCulling>();
     std::lock_guard<std::mutex> lk(S.mu);
-    TC2LI_HIP_CHECK(S.io.ensure(io_bytes));
-    TC2LI_HIP_CHECK(S.work.ensure(std::max(work_bytes, (size_t)256)));
-    TC2LI_HIP_CHECK(S.h_io.ensure(io_bytes));
-    uint8_t* h = S.h_io.p;
-    memcpy(h + o_prob, dev.data(), np * sizeof(CullProblemDev));
+    TC2LI_HIP_CHECK(T.ensure(S));
+    io.put(o_prob, 0, dev.data(), np, sizeof(CullProblemDev));
     tracking_pool().parallel_for(n_problems, [&](int p) {
         const tc2li_culling_problem& in = problems[p];
         const CullProblemDev& d = dev[p];
         const size_t nk = (size_t)in.n_keyframes, ns = (size_t)in.slot_offsets[in.n_keyframes], npt = (size_t)in.n_points, no = (size_t)in.obs_offsets[in.n_points];
-        auto put = [h](size_t o, size_t start, const void* src, size_t count, size_t width) {
-            if (count) memcpy(h + o + start * width, src, count * width);
-        };
-        int32_t* pol = (int32_t*)(h + o_pol) + d.local_off;
+        int32_t* pol = T.host<int32_t>(o_pol) + d.local_off;
         for (int i = 0; i < in.n_local; ++i) pol[i] = p;
-        put(o_flags, d.kf_off, in.kf_flags, nk, 1); put(o_id, d.kf_off, in.kf_id, nk, 8); put(o_time, d.kf_off, in.kf_time, nk, 8);
-        put(o_pos, d.kf_off, in.kf_imu_pos, nk, 12); put(o_thd, d.kf_off, in.kf_th_depth, nk, 4);
-        put(o_srow, d.slot_row_off, in.slot_offsets, nk + 1, 4);
-        put(o_spt, d.slot_off, in.slot_point, ns, 4); put(o_sdep, d.slot_off, in.slot_depth, ns, 4); put(o_soct, d.slot_off, in.slot_octave, ns, 1);
-        put(o_local, d.local_off, in.local, in.n_local, 4);
-        put(o_orow, d.obs_row_off, in.obs_offsets, npt + 1, 4);
-        put(o_okf, d.obs_off, in.obs_kf, no, 4); put(o_ooct, d.obs_off, in.obs_octave, no, 1); put(o_ow, d.obs_off, in.obs_weight, no, 1);
-        put(o_prev, d.kf_off, in.kf_prev, nk, 4); put(o_next, d.kf_off, in.kf_next, nk, 4);
-        put(o_nobs, d.point_off, in.point_nobs, npt, 4); put(o_bad, d.point_off, in.point_bad, npt, 1);
+        io.put(o_flags, d.kf_off, in.kf_flags, nk, 1); io.put(o_id, d.kf_off, in.kf_id, nk, 8); io.put(o_time, d.kf_off, in.kf_time, nk, 8);
+        io.put(o_pos, d.kf_off, in.kf_imu_pos, nk, 12); io.put(o_thd, d.kf_off, in.kf_th_depth, nk, 4);
+        io.put(o_srow, d.slot_row_off, in.slot_offsets, nk + 1, 4);
+        io.put(o_spt, d.slot_off, in.slot_point, ns, 4); io.put(o_sdep, d.slot_off, in.slot_depth, ns, 4); io.put(o_soct, d.slot_off, in.slot_octave, ns, 1);
+        io.put(o_local, d.local_off, in.local, in.n_local, 4);
+        io.put(o_orow, d.obs_row_off, in.obs_offsets, npt + 1, 4);
+        io.put(o_okf, d.obs_off, in.obs_kf, no, 4); io.put(o_ooct, d.obs_off, in.obs_octave, no, 1); io.put(o_ow, d.obs_off, in.obs_weight, no, 1);
+        io.put(o_prev, d.kf_off, in.kf_prev, nk, 4); io.put(o_next, d.kf_off, in.kf_next, nk, 4);
+        io.put(o_nobs, d.point_off, in.point_nobs, npt, 4); io.put(o_bad, d.point_off, in.point_bad, npt, 1);
     });
-    TC2LI_HIP_CHECK(hipMemcpyAsync(S.io.p, h, up_bytes, hipMemcpyHostToDevice, st));
-    TC2LI_HIP_CHECK(hipMemsetAsync(S.work.p, 0, std::max(zero_bytes, (size_t)256), st));
-    uint8_t* d = S.io.p;
-    uint8_t* w = S.work.p;
+    TC2LI_HIP_CHECK(T.upload(st));
+    TC2LI_HIP_CHECK(T.zero_work(zero_bytes, st));
     CullBatch B{};
     B.n_problems = n_problems; B.n_local = (int)n_local;
-    B.problems = (const CullProblemDev*)(d + o_prob); B.problem_of_local = (const int32_t*)(d + o_pol);
-    B.kf_flags = d + o_flags; B.kf_id = (const int64_t*)(d + o_id); B.kf_time = (const double*)(d + o_time);
-    B.kf_imu_pos = (const float*)(d + o_pos); B.kf_th_depth = (const float*)(d + o_thd);
-    B.slot_offsets = (const int32_t*)(d + o_srow); B.slot_point = (const int32_t*)(d + o_spt); B.slot_depth = (const float*)(d + o_sdep);
-    B.slot_octave = (const int8_t*)(d + o_soct); B.local = (const int32_t*)(d + o_local);
-    B.obs_offsets = (const int32_t*)(d + o_orow); B.obs_kf = (const int32_t*)(d + o_okf); B.obs_octave = (const int8_t*)(d + o_ooct);
-    B.obs_weight = d + o_ow;
-    B.kf_prev = (int32_t*)(d + o_prev); B.kf_next = (int32_t*)(d + o_next); B.point_nobs = (int32_t*)(d + o_nobs); B.point_bad = d + o_bad;
-    B.kf_bad = w + o_kfbad; B.obs_dead = w + o_dead; B.point_changed = w + o_changed; B.point_claim = (int32_t*)(w + o_claim);
-    B.spec = (int32_t*)(w + o_spec);
-    B.verdict = (int32_t*)(d + o_verdict); B.n_mps = (int32_t*)(d + o_nmps); B.n_redundant = (int32_t*)(d + o_nred); B.n_visited = (int32_t*)(d + o_nvis);
+    B.problems = T.dev<const CullProblemDev>(o_prob); B.problem_of_local = T.dev<const int32_t>(o_pol);
+    B.kf_flags = T.dev<const uint8_t>(o_flags); B.kf_id = T.dev<const int64_t>(o_id); B.kf_time = T.dev<const double>(o_time);
+    B.kf_imu_pos = T.dev<const float>(o_pos); B.kf_th_depth = T.dev<const float>(o_thd);
+    B.slot_offsets = T.dev<const int32_t>(o_srow); B.slot_point = T.dev<const int32_t>(o_spt); B.slot_depth = T.dev<const float>(o_sdep);
+    B.slot_octave = T.dev<const int8_t>(o_soct); B.local = T.dev<const int32_t>(o_local);
+    B.obs_offsets = T.dev<const int32_t>(o_orow); B.obs_kf = T.dev<const int32_t>(o_okf); B.obs_octave = T.dev<const int8_t>(o_ooct);
+    B.obs_weight = T.dev<const uint8_t>(o_ow);
+    B.kf_prev = T.dev<int32_t>(o_prev); B.kf_next = T.dev<int32_t>(o_next); B.point_nobs = T.dev<int32_t>(o_nobs); B.point_bad = T.dev<uint8_t>(o_bad);
+    B.kf_bad = T.dev_work<uint8_t>(o_kfbad); B.obs_dead = T.dev_work<uint8_t>(o_dead); B.point_changed = T.dev_work<uint8_t>(o_changed);
+    B.point_claim = T.dev_work<int32_t>(o_claim); B.spec = T.dev_work<int32_t>(o_spec);
+    B.verdict = T.dev<int32_t>(o_verdict); B.n_mps = T.dev<int32_t>(o_nmps); B.n_redundant = T.dev<int32_t>(o_nred); B.n_visited = T.dev<int32_t>(o_nvis);
     launch_keyframe_culling(B, st);
     TC2LI_HIP_CHECK(hipGetLastError());
-    TC2LI_HIP_CHECK(hipMemcpyAsync(h + down_from, d + down_from, io_bytes - down_from, hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(stream_wait_blocking(st));
+    TC2LI_HIP_CHECK(T.download_and_wait(st));
     for (int p = 0; p < n_problems; ++p) {
         const tc2li_culling_problem& in = problems[p];
         const CullProblemDev& D = dev[p];
-        const int32_t* verdict = (const int32_t*)(h + o_verdict) + D.local_off;
-        const int32_t* nmps = (const int32_t*)(h + o_nmps) + D.local_off;
-        const int32_t* nred = (const int32_t*)(h + o_nred) + D.local_off;
+        const int32_t* verdict = T.host<const int32_t>(o_verdict) + D.local_off;
+        const int32_t* nmps = T.host<const int32_t>(o_nmps) + D.local_off;
+        const int32_t* nred = T.host<const int32_t>(o_nred) + D.local_off;
         for (int i = 0; i < in.n_local; ++i) {
             in.verdict[i] = verdict[i];
             if (verdict[i] >= 0) { in.n_mps[i] = nmps[i]; in.n_redundant[i] = nred[i]; }
         }
-        *in.n_visited = ((const int32_t*)(h + o_nvis))[p];
-        if (in.point_bad_after && in.n_points) memcpy(in.point_bad_after, h + o_bad + D.point_off, in.n_points);
-        if (in.point_nobs_after && in.n_points) memcpy(in.point_nobs_after, (const int32_t*)(h + o_nobs) + D.point_off, (size_t)in.n_points * 4);
+        *in.n_visited = T.host<const int32_t>(o_nvis)[p];
+        if (in.point_bad_after) io.get(in.point_bad_after, o_bad, D.point_off, (size_t)in.n_points, 1);
+        if (in.point_nobs_after) io.get(in.point_nobs_after, o_nobs, D.point_off, (size_t)in.n_points, 4);
     }
     return n_problems;
 }
@@ -288,29 +258,25 @@ extern "C" int tc2li_map_point_culling_batch(const uint8_t* bad, const int32_t* 
     if (n_points == 0) return 0;
     hipStream_t st = stream ? (hipStream_t)stream : private_stream();
     const size_t n = (size_t)n_points;
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off = align256(off + bytes); return o; };
-    const size_t o_first = take(n * 8), o_cur = take(n * 8), o_found = take(n * 4), o_vis = take(n * 4), o_obs = take(n * 4), o_bad = take(n);
-    const size_t up_bytes = off;
-    const size_t o_act = take(n);
-    MpCullSpace& S = shutdown_owned<MpCullSpace>();
+    PackedTransfer T;
+    Packer& io = T.io;
+    const size_t o_first = io.take(n * 8), o_cur = io.take(n * 8), o_found = io.take(n * 4), o_vis = io.take(n * 4), o_obs = io.take(n * 4), o_bad = io.take(n);
+    T.outputs_begin();
+    const size_t o_act = io.take(n);
+    PackedSpace& S = shutdown_owned<PackedSpace, kSpaceMapPointCulling>();
     std::lock_guard<std::mutex> lk(S.mu);
-    TC2LI_HIP_CHECK(S.io.ensure(off));
-    TC2LI_HIP_CHECK(S.h_io.ensure(off));
-    uint8_t* h = S.h_io.p;
-    memcpy(h + o_first, first_kf_id, n * 8); memcpy(h + o_cur, current_kf_id, n * 8); memcpy(h + o_found, n_found, n * 4);
-    memcpy(h + o_vis, n_visible, n * 4); memcpy(h + o_obs, n_obs, n * 4); memcpy(h + o_bad, bad, n);
-    TC2LI_HIP_CHECK(hipMemcpyAsync(S.io.p, h, up_bytes, hipMemcpyHostToDevice, st));
-    uint8_t* d = S.io.p;
+    TC2LI_HIP_CHECK(T.ensure(S));
+    io.put(o_first, 0, first_kf_id, n, 8); io.put(o_cur, 0, current_kf_id, n, 8); io.put(o_found, 0, n_found, n, 4);
+    io.put(o_vis, 0, n_visible, n, 4); io.put(o_obs, 0, n_obs, n, 4); io.put(o_bad, 0, bad, n, 1);
+    TC2LI_HIP_CHECK(T.upload(st));
     MpCullBatch B{};
     B.n_points = n_points; B.th_obs = th_obs;
-    B.bad = d + o_bad; B.n_found = (const int32_t*)(d + o_found); B.n_visible = (const int32_t*)(d + o_vis);
-    B.first_kf_id = (const int64_t*)(d + o_first); B.n_obs = (const int32_t*)(d + o_obs); B.current_kf_id = (const int64_t*)(d + o_cur);
-    B.action = d + o_act;
+    B.bad = T.dev<const uint8_t>(o_bad); B.n_found = T.dev<const int32_t>(o_found); B.n_visible = T.dev<const int32_t>(o_vis);
+    B.first_kf_id = T.dev<const int64_t>(o_first); B.n_obs = T.dev<const int32_t>(o_obs); B.current_kf_id = T.dev<const int64_t>(o_cur);
+    B.action = T.dev<uint8_t>(o_act);
     launch_map_point_culling(B, st);
     TC2LI_HIP_CHECK(hipGetLastError());
-    TC2LI_HIP_CHECK(hipMemcpyAsync(h + o_act, d + o_act, n, hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(stream_wait_blocking(st));
-    memcpy(action, h + o_act, n);
+    TC2LI_HIP_CHECK(T.download_and_wait(st));
+    io.get(action, o_act, 0, n, 1);
     return n_points;
 }

@@ -177,9 +177,6 @@ bool window_one(const tc2li_inertial_window_problem& in, const tc2li_keyframe_vi
     return true;
 }
 
-// the buffers of tc2li_inertial_window_batch: its own, whatever the visual gather holds
-struct IwSpace : WindowSpace {};
-
 }  // namespace
 }  // namespace tc2li
 
@@ -254,7 +251,7 @@ extern "C" int tc2li_inertial_window_batch(tc2li_keyframe_store* store, const tc
         d.vertex_off = (int32_t)n_vertex; d.vertex_cap = std::min(std::min(in.kf_capacity, in.n_keyframes), kMaxVertices);
         d.link_cap = std::min(in.link_capacity, kIwMaxOpt);
         n_vertex += d.vertex_cap;
-        if (T.most_rows(p) > T.kMaxRows) return T.too_many_rows(entry, p);
+        if (T.most_rows(p) > kMaxRows) return too_many_rows(entry, p);
     }
     const size_t np = (size_t)n_problems;
     T.take_inputs(n_levels);
@@ -263,24 +260,23 @@ extern "C" int tc2li_inertial_window_batch(tc2li_keyframe_store* store, const tc
     const size_t o_links = T.io.take(np * kIwMaxOpt * kLink), o_lrow = T.io.take(np * kIwMaxOpt * 4), o_kfout = T.io.take(n_vertex * kState),
                  o_krow = T.io.take(n_vertex * 4), o_fixed = T.io.take(n_vertex), o_imu = T.io.take(n_vertex);
     T.take_work();
-    WindowSpace& S = shutdown_owned<IwSpace>();
+    PackedSpace& S = shutdown_owned<PackedSpace, kSpaceInertialWindow>();   // its own, whatever the visual gather holds
     std::lock_guard<std::mutex> lk(S.mu);
     TC2LI_HIP_CHECK(T.ensure(S));
-    TC2LI_HIP_CHECK(T.upload(S, inv_level_sigma2, n_levels, st, [&](int, const tc2li_inertial_window_problem& in, const IwProblemDev& d) {
+    TC2LI_HIP_CHECK(T.upload_tables(inv_level_sigma2, n_levels, st, [&](int, const tc2li_inertial_window_problem& in, const IwProblemDev& d) {
         T.io.put(o_state, d.kf_off, in.states, (size_t)in.n_keyframes, kState);
         T.io.put(o_prev, d.kf_off, in.prev_kf, (size_t)in.n_keyframes, 4);
     }));
-    uint8_t* d = S.io.p;
+    uint8_t* d = T.d_io;
     IwBatch B{};
-    T.bind(B, where, d, S.work.p);
+    T.bind(B, where);
     B.prev_kf = (const int32_t*)(d + o_prev); B.states = (const double*)(d + o_state);
     B.counts = (int32_t*)(d + T.o_counts); B.lidar_pose_index = (int32_t*)(d + T.o_lidar); B.links = (tc2li_inertial_link*)(d + o_links);
     B.link_kf2_row = (int32_t*)(d + o_lrow); B.kf_row = (int32_t*)(d + o_krow); B.keyframes_out = (double*)(d + o_kfout); B.fixed = d + o_fixed;
     B.has_imu = d + o_imu;
     launch_inertial_window(B, st);
     TC2LI_HIP_CHECK(hipGetLastError());
-    TC2LI_HIP_CHECK(hipMemcpyAsync(S.h_io.p + T.down_from, d + T.down_from, T.io.off - T.down_from, hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(stream_wait_blocking(st));
+    TC2LI_HIP_CHECK(T.download_and_wait(st));
     const int short_of_room = T.copy_counts(fits);
     if (short_of_room >= 0) return capacity_error(entry, problems, short_of_room);
     T.copy_out([&](int p, const tc2li_inertial_window_problem& in, const IwProblemDev& D) {

@@ -20,6 +20,7 @@
 #include "mapping_device.hpp"
 #include "mapping_host.hpp"
 #include "matcher_device.hpp"
+#include "packed_batch.hpp"
 
 using namespace tc2li;
 using namespace tc2li::mapping_host;
@@ -30,7 +31,6 @@ static_assert(kNewPointsMaxKeys >= kMaxMatchKeys, "k_new_points_compact holds on
 
 namespace {
 
-inline size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline size_t a16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 struct SlotInfo {
@@ -107,15 +107,13 @@ extern "C" int tc2li_keyframe_store_create(int max_keyframes, int max_keypoints,
     std::unique_ptr<tc2li_keyframe_store> S(new tc2li_keyframe_store());
     S->max_kf = max_keyframes; S->max_kp = max_keypoints;
     const size_t K = (size_t)max_keypoints, F = (size_t)max_keyframes;
-    size_t o = 0;
-    auto take = [&o](size_t bytes) { const size_t at = o; o = a256(o + bytes); return at; };
-    S->s_keys = take(K * sizeof(tc2li_keypoint)); S->s_desc = take(32 * K); S->s_ur = take(4 * K); S->s_depth = take(4 * K);
-    S->s_mkeys = take(K * sizeof(MatchKey)); S->s_node = take(4 * K); S->s_off = take(4 * (K + 1)); S->s_idx = take(4 * K);
-    S->stride = o;
-    o = 0;
-    S->o_cells = take(F * kCellsPlus1 * sizeof(int32_t)); S->o_items = take(F * K * sizeof(uint16_t));
-    S->o_tab = take(F * (a16(sizeof(MatchFrameDev)) + 8)); S->o_slots = take(F * S->stride);
-    TC2LI_HIP_CHECK(hipMalloc((void**)&S->slab, o));
+    Packer slot, slab;
+    S->s_keys = slot.take(K * sizeof(tc2li_keypoint)); S->s_desc = slot.take(32 * K); S->s_ur = slot.take(4 * K); S->s_depth = slot.take(4 * K);
+    S->s_mkeys = slot.take(K * sizeof(MatchKey)); S->s_node = slot.take(4 * K); S->s_off = slot.take(4 * (K + 1)); S->s_idx = slot.take(4 * K);
+    S->stride = slot.off;
+    S->o_cells = slab.take(F * kCellsPlus1 * sizeof(int32_t)); S->o_items = slab.take(F * K * sizeof(uint16_t));
+    S->o_tab = slab.take(F * (a16(sizeof(MatchFrameDev)) + 8)); S->o_slots = slab.take(F * S->stride);
+    TC2LI_HIP_CHECK(hipMalloc((void**)&S->slab, slab.off));
     S->info.assign(F, SlotInfo{});
     *out = S.release();
     return 0;
@@ -283,18 +281,13 @@ extern "C" int tc2li_create_new_map_points_batch(tc2li_keyframe_store* S, const 
     SpaceLease lease;
     BatchSpace& W = *lease.s;
     // ---- layout of the one upload, the work arrays and the one download ----
-    size_t o = 0;
-    auto take = [&o](size_t bytes) { const size_t at = o; o = a256(o + bytes); return at; };
-    const size_t i_prob = take((size_t)n_problems * sizeof(MappingDev)), i_out = take((size_t)n_problems * sizeof(NewPointsOut));
-    const size_t i_neigh = take(n_pairs * sizeof(KfDev)), i_pair = take(n_pairs * sizeof(PairRef));
-    const size_t i_scale = take(4 * (size_t)n_levels), i_sigma = take(4 * (size_t)n_levels), i_hp = take(hp_bytes);
-    const size_t in_bytes = o;
-    o = 0;
-    const size_t w_match = take(4 * n_slots), w_ok = take(n_slots), w_x3D = take(12 * n_slots), w_cnt = take(4 * n_pairs);
-    const size_t work_bytes = o;
-    o = 0;
-    const size_t r_count = take(4 * (size_t)n_problems), r_rec = take(32 * n_records);
-    const size_t out_bytes = o;
+    Packer in, work, out;
+    const size_t i_prob = in.take((size_t)n_problems * sizeof(MappingDev)), i_out = in.take((size_t)n_problems * sizeof(NewPointsOut));
+    const size_t i_neigh = in.take(n_pairs * sizeof(KfDev)), i_pair = in.take(n_pairs * sizeof(PairRef));
+    const size_t i_scale = in.take(4 * (size_t)n_levels), i_sigma = in.take(4 * (size_t)n_levels), i_hp = in.take(hp_bytes);
+    const size_t w_match = work.take(4 * n_slots), w_ok = work.take(n_slots), w_x3D = work.take(12 * n_slots), w_cnt = work.take(4 * n_pairs);
+    const size_t r_count = out.take(4 * (size_t)n_problems), r_rec = out.take(32 * n_records);
+    const size_t in_bytes = in.off, work_bytes = work.off, out_bytes = out.off;
     TC2LI_HIP_CHECK(W.d_in.ensure(in_bytes)); TC2LI_HIP_CHECK(W.h_in.ensure(in_bytes)); TC2LI_HIP_CHECK(W.d_work.ensure(work_bytes));
     TC2LI_HIP_CHECK(W.d_out.ensure(out_bytes)); TC2LI_HIP_CHECK(W.h_out.ensure(out_bytes));
     uint8_t *H = W.h_in.p, *D = W.d_in.p;
@@ -402,14 +395,11 @@ extern "C" int tc2li_fuse_search_batch(tc2li_keyframe_store* S, const tc2li_fuse
     hipStream_t st = stream_ ? (hipStream_t)stream_ : private_stream();
     SpaceLease lease;
     BatchSpace& W = *lease.s;
-    size_t o = 0;
-    auto take = [&o](size_t bytes) { const size_t at = o; o = a256(o + bytes); return at; };
-    const size_t i_item = take((size_t)n_items * sizeof(FuseDev)), i_scale = take(4 * (size_t)n_levels), i_sigma = take(4 * (size_t)n_levels);
-    const size_t i_pts = take(68 * (size_t)n_points_total), i_valid = take((size_t)n_valid_total);
-    const size_t in_bytes = o;
-    o = 0;
-    const size_t r_idx = take(4 * (size_t)n_valid_total), r_dist = take(4 * (size_t)n_valid_total);
-    const size_t out_bytes = o;
+    Packer in, out;
+    const size_t i_item = in.take((size_t)n_items * sizeof(FuseDev)), i_scale = in.take(4 * (size_t)n_levels), i_sigma = in.take(4 * (size_t)n_levels);
+    const size_t i_pts = in.take(68 * (size_t)n_points_total), i_valid = in.take((size_t)n_valid_total);
+    const size_t r_idx = out.take(4 * (size_t)n_valid_total), r_dist = out.take(4 * (size_t)n_valid_total);
+    const size_t in_bytes = in.off, out_bytes = out.off;
     TC2LI_HIP_CHECK(W.d_in.ensure(in_bytes)); TC2LI_HIP_CHECK(W.h_in.ensure(in_bytes)); TC2LI_HIP_CHECK(W.d_out.ensure(out_bytes)); TC2LI_HIP_CHECK(W.h_out.ensure(out_bytes));
     uint8_t *H = W.h_in.p, *D = W.d_in.p;
     memcpy(H + i_scale, scale_factors, 4 * (size_t)n_levels);

@@ -9,6 +9,7 @@
 #include "common.hpp"
 #include "mlpnp_device.hpp"
 #include "mlpnp_math.hpp"
+#include "packed_batch.hpp"
 
 namespace tc2li {
 namespace {
@@ -127,13 +128,6 @@ void write_back(const tc2li_mlpnp_problem* problems, int n_problems, int capacit
     }
 }
 
-// the device buffers of a call, kept between calls
-struct MlpnpSpace {
-    std::mutex mu;
-    DevBuf<uint8_t> in, out, work;
-    PinnedBuf<uint8_t> h_in, h_out;
-};
-
 }  // namespace
 }  // namespace tc2li
 
@@ -219,59 +213,46 @@ extern "C" int tc2li_mlpnp_ransac_batch(const tc2li_mlpnp_problem* problems, int
     hipStream_t st = stream ? (hipStream_t)stream : private_stream();
     const size_t n_solves = K.problem_of_solve.size(), n_corr = K.kp_index.size(), np = (size_t)n_problems, cap = (size_t)capacity;
     const int words = std::max(1, (K.max_corr + 63) / 64);
-    // one staged upload: problems, correspondences, minimal sets, the state's flags
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off = align256(off + bytes); return o; };
-    const size_t o_prob = take(np * sizeof(MlpnpProblemDev)), o_p2d = take(n_corr * 8), o_Xw = take(n_corr * 12), o_err = take(n_corr * 4),
-                 o_kp = take(n_corr * 4), o_idx = take(n_solves * 24), o_pos = take(n_solves * 4);
-    const size_t in_bytes = off;
-    off = 0;
-    const size_t o_res = take(np * 16), o_state = take(np * sizeof(MlpnpStateOut)), o_pose = take(np * 28), o_Rt = take(np * 96),
-                 o_inl = take(np * cap), o_best = take(np * cap);
-    const size_t out_bytes = off;
-    off = 0;
-    const size_t o_wRt = take(n_solves * 96), o_cnt = take(n_solves * 4), o_mask = take(n_solves * words * 8);
-    const size_t work_bytes = off;
-    MlpnpSpace& S = shutdown_owned<MlpnpSpace>();
+    // one buffer: [problems, correspondences, minimal sets | the state's flags, with their values so far | outputs]
+    PackedTransfer T;
+    Packer &io = T.io, &work = T.work;
+    const size_t o_prob = io.take(np * sizeof(MlpnpProblemDev)), o_p2d = io.take(n_corr * 8), o_Xw = io.take(n_corr * 12), o_err = io.take(n_corr * 4),
+                 o_kp = io.take(n_corr * 4), o_idx = io.take(n_solves * 24), o_pos = io.take(n_solves * 4);
+    T.state_begins();
+    const size_t o_best = io.take(np * cap);
+    T.outputs_begin();
+    const size_t o_res = io.take(np * 16), o_state = io.take(np * sizeof(MlpnpStateOut)), o_pose = io.take(np * 28), o_Rt = io.take(np * 96),
+                 o_inl = io.take(np * cap);
+    const size_t o_wRt = work.take(n_solves * 96), o_cnt = work.take(n_solves * 4), o_mask = work.take(n_solves * words * 8);
+    PackedSpace& S = shutdown_owned<PackedSpace, kSpaceMlpnp>();
     std::lock_guard<std::mutex> lk(S.mu);
-    TC2LI_HIP_CHECK(S.in.ensure(in_bytes));
-    TC2LI_HIP_CHECK(S.out.ensure(out_bytes));
-    TC2LI_HIP_CHECK(S.work.ensure(std::max(work_bytes, (size_t)256)));
-    TC2LI_HIP_CHECK(S.h_in.ensure(in_bytes));
-    TC2LI_HIP_CHECK(S.h_out.ensure(out_bytes));
-    uint8_t* h = S.h_in.p;
-    memcpy(h + o_prob, K.problems.data(), np * sizeof(MlpnpProblemDev));
-    if (n_corr) {
-        memcpy(h + o_p2d, K.p2d.data(), n_corr * 8); memcpy(h + o_Xw, K.Xw.data(), n_corr * 12);
-        memcpy(h + o_err, K.max_error.data(), n_corr * 4); memcpy(h + o_kp, K.kp_index.data(), n_corr * 4);
-    }
-    if (n_solves) { memcpy(h + o_idx, K.idx6.data(), n_solves * 24); memcpy(h + o_pos, K.problem_of_solve.data(), n_solves * 4); }
-    uint8_t* hb = S.h_out.p + o_best;
-    memset(hb, 0, np * cap);
-    for (int p = 0; p < n_problems; ++p)
-        if (problems[p].n_keypoints) memcpy(hb + (size_t)p * cap, problems[p].best_inlier, problems[p].n_keypoints);
-    TC2LI_HIP_CHECK(hipMemcpyAsync(S.in.p, h, in_bytes, hipMemcpyHostToDevice, st));
-    if (np * cap) TC2LI_HIP_CHECK(hipMemcpyAsync(S.out.p + o_best, hb, np * cap, hipMemcpyHostToDevice, st));
+    TC2LI_HIP_CHECK(T.ensure(S));
+    io.put(o_prob, 0, K.problems.data(), np, sizeof(MlpnpProblemDev));
+    io.put(o_p2d, 0, K.p2d.data(), n_corr, 8); io.put(o_Xw, 0, K.Xw.data(), n_corr, 12);
+    io.put(o_err, 0, K.max_error.data(), n_corr, 4); io.put(o_kp, 0, K.kp_index.data(), n_corr, 4);
+    io.put(o_idx, 0, K.idx6.data(), n_solves, 24); io.put(o_pos, 0, K.problem_of_solve.data(), n_solves, 4);
+    memset(T.host<void>(o_best), 0, np * cap);
+    for (int p = 0; p < n_problems; ++p) io.put(o_best, (size_t)p * cap, problems[p].best_inlier, (size_t)problems[p].n_keypoints, 1);
+    TC2LI_HIP_CHECK(T.upload(st));
     MlpnpBatch B{};
     B.n_problems = n_problems; B.n_solves = (int)n_solves; B.capacity = capacity; B.mask_words = words;
     B.fx = (float)cam->fx; B.fy = (float)cam->fy; B.cx = (float)cam->cx; B.cy = (float)cam->cy;
-    B.problems = (const MlpnpProblemDev*)(S.in.p + o_prob);
-    B.p2d = (const float*)(S.in.p + o_p2d); B.Xw = (const float*)(S.in.p + o_Xw); B.max_error = (const float*)(S.in.p + o_err);
-    B.kp_index = (const int32_t*)(S.in.p + o_kp); B.idx6 = (const int32_t*)(S.in.p + o_idx); B.problem_of_solve = (const int32_t*)(S.in.p + o_pos);
-    B.Rt = (double*)(S.work.p + o_wRt); B.count = (int32_t*)(S.work.p + o_cnt); B.mask = (unsigned long long*)(S.work.p + o_mask);
-    B.result = (int32_t*)(S.out.p + o_res); B.state = (MlpnpStateOut*)(S.out.p + o_state); B.pose7 = (float*)(S.out.p + o_pose);
-    B.Rt12 = (double*)(S.out.p + o_Rt); B.inlier = S.out.p + o_inl; B.best_inlier = S.out.p + o_best;
+    B.problems = T.dev<const MlpnpProblemDev>(o_prob);
+    B.p2d = T.dev<const float>(o_p2d); B.Xw = T.dev<const float>(o_Xw); B.max_error = T.dev<const float>(o_err);
+    B.kp_index = T.dev<const int32_t>(o_kp); B.idx6 = T.dev<const int32_t>(o_idx); B.problem_of_solve = T.dev<const int32_t>(o_pos);
+    B.Rt = T.dev_work<double>(o_wRt); B.count = T.dev_work<int32_t>(o_cnt); B.mask = T.dev_work<unsigned long long>(o_mask);
+    B.result = T.dev<int32_t>(o_res); B.state = T.dev<MlpnpStateOut>(o_state); B.pose7 = T.dev<float>(o_pose);
+    B.Rt12 = T.dev<double>(o_Rt); B.inlier = T.dev<uint8_t>(o_inl); B.best_inlier = T.dev<uint8_t>(o_best);
     if (!launch_mlpnp(B, st)) {
         set_error("tc2li_mlpnp_ransac_batch: the runtime refused the solve kernel's LDS");
         return TC2LI_ERR_HIP;
     }
     TC2LI_HIP_CHECK(hipGetLastError());
-    TC2LI_HIP_CHECK(hipMemcpyAsync(S.h_out.p, S.out.p, out_bytes, hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(stream_wait_blocking(st));
-    const uint8_t* o = S.h_out.p;
-    memcpy(pose7, o + o_pose, np * 28);
-    if (Rt12) memcpy(Rt12, o + o_Rt, np * 96);
-    if (np * cap) memcpy(inlier, o + o_inl, np * cap);
-    write_back(problems, n_problems, capacity, (const int32_t*)(o + o_res), (const MlpnpStateOut*)(o + o_state), o + o_best, found, no_more, n_inliers);
+    TC2LI_HIP_CHECK(T.download_and_wait(st));
+    io.get(pose7, o_pose, 0, np, 28);
+    if (Rt12) io.get(Rt12, o_Rt, 0, np, 96);
+    io.get(inlier, o_inl, 0, np * cap, 1);
+    write_back(problems, n_problems, capacity, T.host<const int32_t>(o_res), T.host<const MlpnpStateOut>(o_state), T.host<const uint8_t>(o_best), found,
+               no_more, n_inliers);
     return n_problems;
 }

@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "common.hpp"
+#include "packed_batch.hpp"
 #include "stereo_points_device.hpp"
 
 namespace tc2li {
@@ -42,21 +43,12 @@ int validate_all(const char* entry, const tc2li_stereo_points_frame* frames, con
         set_error("%s: null or negative argument", entry);
         return TC2LI_ERR_INVALID;
     }
-    std::vector<const char*> what(n_frames, "");
-    std::vector<int> code(n_frames, 0);
-    tracking_pool().parallel_for(n_frames, [&](int f) {
-        code[f] = validate_frame(frames[f], decide, &what[f]);
-        if (!code[f] && decide) {
-            what[f] = validate_decision(decisions[f]);
-            if (what[f][0]) code[f] = TC2LI_ERR_INVALID;
-        }
+    return validate_each(entry, "frame", n_frames, [&](int f, const char** what) {
+        const int code = validate_frame(frames[f], decide, what);
+        if (code || !decide) return code;
+        *what = validate_decision(decisions[f]);
+        return (*what)[0] ? TC2LI_ERR_INVALID : 0;
     });
-    for (int f = 0; f < n_frames; ++f)
-        if (code[f]) {
-            set_error("%s: frame %d: %s", entry, f, what[f]);
-            return code[f];
-        }
-    return 0;
 }
 
 KeyframeDecisionDev pack_decision(const tc2li_keyframe_decision& d) {
@@ -127,12 +119,6 @@ void decide_one(const tc2li_stereo_points_frame& f, const tc2li_keyframe_decisio
     points_one(f, u, out.need && !d.create_blocked);
 }
 
-struct StereoPointsSpace {
-    std::mutex mu;
-    DevBuf<uint8_t> io;
-    PinnedBuf<uint8_t> h_io;
-};
-
 int device_batch(const char* entry, const tc2li_stereo_points_frame* frames, const tc2li_keyframe_decision* decisions, tc2li_keyframe_verdict* verdicts,
                  bool decide, int n_frames, const float* unproject4, void* stream) {
     const int rc = validate_all(entry, frames, decisions, verdicts, decide, n_frames, unproject4);
@@ -150,66 +136,58 @@ int device_batch(const char* entry, const tc2li_stereo_points_frame* frames, con
         memcpy(d.Rwc, in.Rwc, sizeof d.Rwc); memcpy(d.Ow, in.Ow, sizeof d.Ow);
         total += in.n;
         if (d.n_ref > 0) total_ref += d.n_ref;
-        if (total_ref > 0x7fffff00u) {
+        if (total_ref > kMaxRows) {
             set_error("%s: the batch up to frame %d has more than 2^31 entries of ref_nobs; split it", entry, f);
             return TC2LI_ERR_INVALID;
         }
     }
     const size_t nf = (size_t)n_frames;
     // one buffer: [inputs | outputs]
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off = align256(off + bytes); return o; };
-    const size_t o_frames = take(nf * sizeof(StereoFrameDev)), o_dec = take(decide ? nf * sizeof(KeyframeDecisionDev) : 0), o_depth = take(total * 4),
-                 o_xy = take(total * 8), o_held = take(total), o_outl = take(decide ? total : 0), o_ref = take(total_ref * 4);
-    const size_t up_bytes = off, down_from = off;
-    const size_t o_counts = take(nf * 12), o_verdict = take(decide ? nf * sizeof(tc2li_keyframe_verdict) : 0), o_created = take(total * 4),
-                 o_x3d = take(total * 12);
-    const size_t io_bytes = off;
-    StereoPointsSpace& S = shutdown_owned<StereoPointsSpace>();
+    PackedTransfer T;
+    Packer& io = T.io;
+    const size_t o_frames = io.take(nf * sizeof(StereoFrameDev)), o_dec = io.take(decide ? nf * sizeof(KeyframeDecisionDev) : 0), o_depth = io.take(total * 4),
+                 o_xy = io.take(total * 8), o_held = io.take(total), o_outl = io.take(decide ? total : 0), o_ref = io.take(total_ref * 4);
+    T.outputs_begin();
+    const size_t o_counts = io.take(nf * 12), o_verdict = io.take(decide ? nf * sizeof(tc2li_keyframe_verdict) : 0), o_created = io.take(total * 4),
+                 o_x3d = io.take(total * 12);
+    PackedSpace& S = shutdown_owned<PackedSpace, kSpaceStereoPoints>();
     std::lock_guard<std::mutex> lk(S.mu);
-    TC2LI_HIP_CHECK(S.io.ensure(io_bytes));
-    TC2LI_HIP_CHECK(S.h_io.ensure(io_bytes));
-    uint8_t* h = S.h_io.p;
-    memcpy(h + o_frames, dev.data(), nf * sizeof(StereoFrameDev));
+    TC2LI_HIP_CHECK(T.ensure(S));
+    io.put(o_frames, 0, dev.data(), nf, sizeof(StereoFrameDev));
     tracking_pool().parallel_for(n_frames, [&](int f) {
         const tc2li_stereo_points_frame& in = frames[f];
         const StereoFrameDev& d = dev[f];
         const size_t n = (size_t)in.n;
-        if (n) {
-            memcpy(h + o_depth + 4 * (size_t)d.off, in.depth, n * 4);
-            memcpy(h + o_held + d.off, in.held, n);
-            if (decide) memcpy(h + o_outl + d.off, in.outlier, n);
-            float* xy = (float*)(h + o_xy) + 2 * (size_t)d.off;
-            for (size_t i = 0; i < n; ++i) { xy[2 * i] = in.keys[i].x; xy[2 * i + 1] = in.keys[i].y; }
-        }
+        io.put(o_depth, d.off, in.depth, n, 4); io.put(o_held, d.off, in.held, n, 1);
+        if (decide) io.put(o_outl, d.off, in.outlier, n, 1);
+        float* xy = T.host<float>(o_xy) + 2 * (size_t)d.off;
+        for (size_t i = 0; i < n; ++i) { xy[2 * i] = in.keys[i].x; xy[2 * i + 1] = in.keys[i].y; }
         if (decide) {
-            ((KeyframeDecisionDev*)(h + o_dec))[f] = pack_decision(decisions[f]);
-            if (d.n_ref > 0) memcpy(h + o_ref + 4 * (size_t)d.ref_off, decisions[f].ref_nobs, (size_t)d.n_ref * 4);
+            T.host<KeyframeDecisionDev>(o_dec)[f] = pack_decision(decisions[f]);
+            if (d.n_ref > 0) io.put(o_ref, d.ref_off, decisions[f].ref_nobs, (size_t)d.n_ref, 4);
         }
     });
-    TC2LI_HIP_CHECK(hipMemcpyAsync(S.io.p, h, up_bytes, hipMemcpyHostToDevice, st));
-    uint8_t* d = S.io.p;
+    TC2LI_HIP_CHECK(T.upload(st));
     StereoPointsBatch B{};
     B.n_frames = n_frames; B.decide = decide ? 1 : 0;
     B.cx = unproject4[0]; B.cy = unproject4[1]; B.invfx = unproject4[2]; B.invfy = unproject4[3];
-    B.frames = (const StereoFrameDev*)(d + o_frames); B.decisions = (const KeyframeDecisionDev*)(d + o_dec);
-    B.depth = (const float*)(d + o_depth); B.xy = (const float*)(d + o_xy); B.held = d + o_held; B.outlier = d + o_outl;
-    B.ref_nobs = (const int32_t*)(d + o_ref);
-    B.created_keypoint = (int32_t*)(d + o_created); B.x3D = (float*)(d + o_x3d); B.counts = (int32_t*)(d + o_counts);
-    B.verdicts = (tc2li_keyframe_verdict*)(d + o_verdict);
+    B.frames = T.dev<const StereoFrameDev>(o_frames); B.decisions = T.dev<const KeyframeDecisionDev>(o_dec);
+    B.depth = T.dev<const float>(o_depth); B.xy = T.dev<const float>(o_xy); B.held = T.dev<const uint8_t>(o_held);
+    B.outlier = T.dev<const uint8_t>(o_outl); B.ref_nobs = T.dev<const int32_t>(o_ref);
+    B.created_keypoint = T.dev<int32_t>(o_created); B.x3D = T.dev<float>(o_x3d); B.counts = T.dev<int32_t>(o_counts);
+    B.verdicts = T.dev<tc2li_keyframe_verdict>(o_verdict);
     launch_stereo_points(B, st);
     TC2LI_HIP_CHECK(hipGetLastError());
-    TC2LI_HIP_CHECK(hipMemcpyAsync(h + down_from, d + down_from, io_bytes - down_from, hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(stream_wait_blocking(st));
+    TC2LI_HIP_CHECK(T.download_and_wait(st));
     tracking_pool().parallel_for(n_frames, [&](int f) {
         const tc2li_stereo_points_frame& in = frames[f];
-        const int32_t* counts = (const int32_t*)(h + o_counts) + 3 * (size_t)f;
+        const int32_t* counts = T.host<const int32_t>(o_counts) + 3 * (size_t)f;
         memcpy(in.counts, counts, 12);
         if (counts[0] > 0) {
-            memcpy(in.created_keypoint, (const int32_t*)(h + o_created) + dev[f].off, (size_t)counts[0] * 4);
-            memcpy(in.x3D, (const float*)(h + o_x3d) + 3 * (size_t)dev[f].off, (size_t)counts[0] * 12);
+            io.get(in.created_keypoint, o_created, dev[f].off, (size_t)counts[0], 4);
+            io.get(in.x3D, o_x3d, dev[f].off, (size_t)counts[0], 12);
         }
-        if (decide) verdicts[f] = ((const tc2li_keyframe_verdict*)(h + o_verdict))[f];
+        if (decide) verdicts[f] = T.host<const tc2li_keyframe_verdict>(o_verdict)[f];
     });
     return n_frames;
 }

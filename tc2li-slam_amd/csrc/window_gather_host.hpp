@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "packed_batch.hpp"
 #include "window_gather_device.hpp"
 
 namespace tc2li {
@@ -103,20 +104,12 @@ int validate_all(const char* entry, const Problem* problems, int n_problems, con
         set_error("%s: null or negative argument", entry);
         return TC2LI_ERR_INVALID;
     }
-    std::vector<const char*> what(n_problems, "");
-    tracking_pool().parallel_for(n_problems, [&](int p) { what[p] = validate(problems[p]); });
-    for (int p = 0; p < n_problems; ++p)
-        if (what[p][0]) {
-            set_error("%s: problem %d: %s", entry, p, what[p]);
-            return TC2LI_ERR_INVALID;
-        }
-    return 0;
+    return validate_each(entry, "problem", n_problems, invalid_if([&](int p) { return validate(problems[p]); }));
 }
 
 // ---- the host entries ------------------------------------------------------------------------------------------------------------------
-// The three passes of a host entry: validate, size every problem without writing a list (on TC2LI_ERR_CAPACITY no list of any problem is
-// written), write.  validate(problem, slots) as above; window_one(problem, write) returns whether the lists fit; capacity_error(p) sets
-// the error and returns the code.
+// A host entry: validate, then size_then_write.  validate(problem, slots) as above; window_one(problem, write) returns whether the lists
+// fit; capacity_error(p) sets the error and returns the code.
 template <class Problem, class Validate, class WindowOne, class CapacityError>
 int host_window_batch(const char* entry, const tc2li_keyframe_view* views, int n_views, const Problem* problems, int n_problems,
                       const float* inv_level_sigma2, int n_levels, Validate validate, WindowOne window_one, CapacityError capacity_error) {
@@ -125,12 +118,7 @@ int host_window_batch(const char* entry, const tc2li_keyframe_view* views, int n
     if (rc < 0) return rc;
     rc = validate_all(entry, problems, n_problems, inv_level_sigma2, n_levels, [&](const Problem& in) { return validate(in, slots); });
     if (rc < 0) return rc;
-    std::vector<uint8_t> ok(n_problems, 1);
-    tracking_pool().parallel_for(n_problems, [&](int p) { ok[p] = window_one(problems[p], false); });
-    for (int p = 0; p < n_problems; ++p)
-        if (!ok[p]) return capacity_error(p);
-    tracking_pool().parallel_for(n_problems, [&](int p) { window_one(problems[p], true); });
-    return n_problems;
+    return size_then_write(n_problems, [&](int p, bool write) { return window_one(problems[p], write); }, capacity_error);
 }
 
 // The vertices in id order: `rows` sorted by (kf_id, row); returns every keyframe's place among them, -1: none.
@@ -204,45 +192,22 @@ int outliers_emit(const char* entry, const tc2li_ba_edge* edges, int n_edges, in
 }
 
 // ---- to the device and back ------------------------------------------------------------------------------------------------------------
-// the device buffers of a call, kept between calls
-struct WindowSpace {
-    std::mutex mu;
-    DevBuf<uint8_t> io, work;
-    PinnedBuf<uint8_t> h_io;
-};
-
-// Tables packed into one buffer, each on a 256-byte boundary: take() hands out the places, put() / get() copy `count` entries of `width`
-// bytes to / from entry `start` of the table at o, once base is the buffer.
-struct Packer {
-    uint8_t* base = nullptr;
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off = align256(off + bytes); return o; }
-    void put(size_t o, size_t start, const void* src, size_t count, size_t width) const {
-        if (count) memcpy(base + o + start * width, src, count * width);
-    }
-    void get(void* dst, size_t o, size_t start, size_t count, size_t width) const {
-        if (count) memcpy(dst, base + o + start * width, count * width);
-    }
-};
-
 // The way of a batch through the device, as far as both gathers go it together.  A device entry
 //   add()s every problem (the common part of its device record and the running table sizes), fills in its own part and looks at most_rows();
 //   take_inputs(), then take()s the places of its own input tables from `io`; take_outputs() and take_work() likewise;
-//   ensure()s the buffers, upload()s with its own tables put by `own`, bind()s the batch, adds its own pointers and launches;
-//   downloads io from down_from on, copy_counts() and -- unless a problem was short of room -- copy_out().
-// io is [inputs | outputs]: the upload is the first part, the download the second, in which the edges come last of the common tables
-// (o_edges .. o_after_edges) and the entry's own outputs after them.
+//   ensure()s the buffers, upload_tables() with its own tables put by `own`, bind()s the batch, adds its own pointers and launches;
+//   downloads and waits, copy_counts() and -- unless a problem was short of room -- copy_out().
+// The buffers, the copies and the wait are PackedTransfer's (packed_batch.hpp).  io is [inputs | outputs], in which the edges come last
+// of the common tables (o_edges .. o_after_edges) and the entry's own outputs after them.
 template <class Problem, class Dev>
-struct WindowTransfer {
-    static constexpr size_t kMaxRows = 0x7fffff00u;
+struct WindowTransfer : PackedTransfer {
     const Problem* problems;
     const int n_problems;
     const size_t np;
     std::vector<Dev> dev;
     size_t n_kf = 0, n_slot = 0, n_points = 0, n_obs = 0, n_marks = 0, n_first = 0, n_pointo = 0, n_edge = 0;
-    Packer io, work;
-    size_t o_prob, o_sigma, o_id, o_pos, o_slot, o_srow, o_spt, o_orow, o_okf, o_oidx, o_flags, o_pflags, up_bytes;
-    size_t down_from, o_counts, o_lidar, o_p3, o_ptrow, o_edges, o_after_edges;
+    size_t o_prob, o_sigma, o_id, o_pos, o_slot, o_srow, o_spt, o_orow, o_okf, o_oidx, o_flags, o_pflags;
+    size_t o_counts, o_lidar, o_p3, o_ptrow, o_edges, o_after_edges;
     size_t w_marks, w_first, w_vertex, w_members, w_listed, w_estart, w_emit;
     int n_counts = 0;
 
@@ -269,10 +234,6 @@ struct WindowTransfer {
     }
     // the longest common table up to and with problem p, in rows; the kernels index with 32 bits
     size_t most_rows(int p) const { return std::max(std::max(n_kf + p, n_slot), std::max(n_points + p, n_obs)); }
-    static int too_many_rows(const char* entry, int p) {
-        set_error("%s: the batch up to problem %d has more than 2^31 rows in one table; split it", entry, p);
-        return TC2LI_ERR_INVALID;
-    }
 
     void take_inputs(int n_levels) {
         o_prob = io.take(np * sizeof(Dev)); o_sigma = io.take((size_t)n_levels * 4); o_id = io.take(n_kf * 8); o_pos = io.take(n_points * 24);
@@ -281,7 +242,7 @@ struct WindowTransfer {
     }
     // after the entry's own inputs.  counts_per_problem: TC2LI_*_WINDOW_COUNTS
     void take_outputs(int counts_per_problem) {
-        up_bytes = down_from = io.off;
+        outputs_begin();
         n_counts = counts_per_problem;
         o_counts = io.take(np * n_counts * 4); o_lidar = io.take(np * kWinMaxLidar * 4); o_p3 = io.take(n_pointo * 24); o_ptrow = io.take(n_pointo * 4);
         o_edges = io.take(n_edge * sizeof(tc2li_ba_edge));
@@ -291,16 +252,9 @@ struct WindowTransfer {
         w_marks = work.take(n_marks * 4); w_first = work.take(n_first * 4); w_vertex = work.take(n_kf * 4); w_members = work.take(n_kf * 4);
         w_listed = work.take(n_points * 4); w_estart = work.take(n_points * 4); w_emit = work.take(np * 4);
     }
-    hipError_t ensure(WindowSpace& S) {
-        hipError_t e = S.io.ensure(io.off);
-        if (e == hipSuccess) e = S.work.ensure(work.off);
-        if (e == hipSuccess) e = S.h_io.ensure(io.off);
-        io.base = S.h_io.p;   // put / get work on the host copy
-        return e;
-    }
     // own(p, problem, its device record): the entry's own tables, put into io
     template <class Own>
-    hipError_t upload(WindowSpace& S, const float* inv_level_sigma2, int n_levels, hipStream_t st, Own own) {
+    hipError_t upload_tables(const float* inv_level_sigma2, int n_levels, hipStream_t st, Own own) {
         memcpy(io.base + o_prob, dev.data(), np * sizeof(Dev));
         memcpy(io.base + o_sigma, inv_level_sigma2, (size_t)n_levels * 4);
         tracking_pool().parallel_for(n_problems, [&](int p) {
@@ -315,10 +269,11 @@ struct WindowTransfer {
             io.put(o_okf, d.obs_off, in.obs_kf, n_o, 4); io.put(o_oidx, d.obs_off, in.obs_index, n_o, 4);
             own(p, in, d);
         });
-        return hipMemcpyAsync(S.io.p, io.base, up_bytes, hipMemcpyHostToDevice, st);
+        return upload(st);
     }
-    // the common part of the batch; d, w: the entry's io and work buffers on the device
-    void bind(WindowBatch& B, const BawStore& where, uint8_t* d, uint8_t* w) const {
+    // the common part of the batch
+    void bind(WindowBatch& B, const BawStore& where) const {
+        uint8_t *d = d_io, *w = d_work;
         B.n_problems = n_problems; B.problem_bytes = (int)sizeof(Dev); B.problems = d + o_prob;
         B.store = where; B.inv_level_sigma2 = (const float*)(d + o_sigma);
         B.kf_slot = (const int32_t*)(d + o_slot); B.kf_id = (const int64_t*)(d + o_id); B.kf_flags = d + o_flags;
@@ -333,13 +288,7 @@ struct WindowTransfer {
     // the downloaded counts into the problems' arrays; fits(problem, counts).  Returns the first problem short of room, or -1.
     template <class Fits>
     int copy_counts(Fits fits) const {
-        int short_of_room = -1;
-        for (int p = 0; p < n_problems; ++p) {
-            const int32_t* counts = (const int32_t*)(io.base + o_counts) + (size_t)p * n_counts;
-            memcpy(problems[p].counts, counts, (size_t)n_counts * 4);
-            if (short_of_room < 0 && !fits(problems[p], counts)) short_of_room = p;
-        }
-        return short_of_room;
+        return tc2li::copy_counts(problems, n_problems, host<const int32_t>(o_counts), n_counts, fits);
     }
     // the downloaded lists of every window that came out into the problems' arrays: lidar_pose_index, the points, the edges where the
     // problem has an array for them, and by own(p, problem, its device record) the entry's own lists

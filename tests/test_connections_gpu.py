@@ -107,3 +107,84 @@ def test_device_best_covisibles(pkg):
         assert np.array_equal(got[k], host[k]), k
         assert np.array_equal(got[k], want[k]), k
     assert len(want["kf"]) < len(rows["kf"]) and {0, 1} <= set(np.diff(rows["offsets"]).tolist()) and int(np.diff(want["offsets"]).max()) > 900
+
+
+# ---- the buffers kept between calls -------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _tiny():
+    """Problems of the family's smallest sizes: 12 keyframes and 63 slots, counts on both sides of the threshold."""
+    return [K.make_problem(900 + i, 12, 63, 8, ("high", "mixed")[i % 2], (0, 1, 5), first=bool(i % 3 == 0)) for i in range(16)]
+
+
+def _equals_host(pkg, problems, what):
+    got = pkg.update_connections_batch(problems)
+    host = pkg.update_connections_batch(problems, host=True)
+    assert len(got) == len(host) == len(problems)
+    for i, (g, h) in enumerate(zip(got, host)):
+        K.assert_equal(g, h, "%s: problem %d, device against host" % (what, i))
+    return got
+
+
+def _rows_equal_host(pkg, rows, bad, what):
+    got, host = pkg.update_best_covisibles_batch(rows, bad), pkg.update_best_covisibles_batch(rows, bad, host=True)
+    for k in host:
+        assert np.array_equal(got[k], host[k]), (what, k)
+    return got
+
+
+def test_device_reuses_its_buffers_across_batch_sizes(pkg):
+    """8 problems, then 1 other, then the 8 again through the same buffers: nothing of an earlier call shows in a later one."""
+    tiny = _tiny()
+    eight, one = tiny[:8], [tiny[8]]
+    _equals_host(pkg, tiny, "fill")                                                  # whatever the tests before left, the buffers are larger than the calls below need
+    first = _equals_host(pkg, eight, "8")
+    assert any(g["status"] == ref.UPDATED and len(g["changed_kf"]) for g in first)
+    _equals_host(pkg, one, "1")
+    again = _equals_host(pkg, eight, "8 again")
+    for i, (a, b) in enumerate(zip(first, again)):
+        K.assert_equal(a, b, "problem %d, first against third call" % i)
+    rows, bad = K.random_rows(8, 300, 4000, long_rows=(63, 65))
+    one_row = dict(offsets=rows["offsets"][:2], kf=rows["kf"], weight=rows["weight"])
+    for r, what in ((rows, "300 rows"), (one_row, "1 row"), (rows, "300 rows again")):
+        _rows_equal_host(pkg, r, bad, what)
+
+
+def test_device_empty_problem_inside_a_batch(pkg):
+    """The emptiest problem the validation admits -- the current keyframe alone: no slots, no points, no weight rows -- between two
+    ordinary ones: its tables are empty places in the concatenation.  A problem without any keyframe has no current one and is refused."""
+    tiny = _tiny()
+    alone = K.hand([dict()], [], [], 0)
+    got = _equals_host(pkg, [tiny[0], alone, tiny[1]], "empty in the middle")
+    assert got[1]["status"] == ref.UNCHANGED and len(got[1]["counter_kf"]) == 0
+    _equals_host(pkg, [alone, tiny[0], alone], "empty at both ends")
+    _equals_host(pkg, [alone], "empty alone")
+    for host in (True, False):
+        with pytest.raises(pkg.Tc2liError) as e:
+            pkg.update_connections_batch([tiny[0], K.hand([], [], [], 0), tiny[1]], host=host)
+        assert e.value.code == -2 and "problem 1" in str(e.value) and "current" in str(e.value), e.value
+    # UpdateBestCovisibles: rows without entries between rows with some, and rows without any entry at all
+    got = _rows_equal_host(pkg, dict(offsets=[0, 2, 2, 2, 3], kf=[1, 3, 2], weight=[5, 7, 9]), [0, 0, 1, 0], "empty rows in the middle")
+    assert got["offsets"].tolist() == [0, 2, 2, 2, 2] and got["kf"].tolist() == [3, 1]
+    got = _rows_equal_host(pkg, dict(offsets=[0, 0, 0, 0], kf=[], weight=[]), [], "three empty rows")
+    assert got["offsets"].tolist() == [0, 0, 0, 0] and len(got["kf"]) == 0
+
+
+def test_device_two_callers_at_once(pkg):
+    """Two threads, four calls each on batches of four of their own: each gets its own results."""
+    import two_callers
+    tiny = _tiny()
+    batches = [[[tiny[8 * t + (2 * s + i) % 8] for i in range(4)] for s in range(4)] for t in (0, 1)]
+    want = [[pkg.update_connections_batch(b, host=True) for b in side] for side in batches]
+    got = two_callers.run(pkg.update_connections_batch, batches[0], batches[1])
+    for t in (0, 1):
+        for c, (g, w) in enumerate(zip(got[t], want[t])):
+            assert len(g) == len(w) == 4
+            for i in range(4):
+                K.assert_equal(g[i], w[i], "thread %d, call %d, problem %d" % (t, c, i))
+    rows = [[K.random_rows(50 + 4 * t + c, 100 + 20 * c, 2000, long_rows=(64,)) for c in range(4)] for t in (0, 1)]
+    got = two_callers.run(lambda rb: pkg.update_best_covisibles_batch(*rb), rows[0], rows[1])
+    for t in (0, 1):
+        for c in range(4):
+            host = pkg.update_best_covisibles_batch(*rows[t][c], host=True)
+            for k in host:
+                assert np.array_equal(got[t][c][k], host[k]), (t, c, k)

@@ -96,3 +96,80 @@ def test_device_map_point_culling(pkg):
         got = pkg.map_point_culling_batch(pt, th_obs)
         assert np.array_equal(got, pkg.map_point_culling_batch(pt, th_obs, host=True))
         assert np.array_equal(got, want) and set(want.tolist()) == {0, 1, 2, 3, 4}
+
+
+# ---- the buffers kept between calls -------------------------------------------------------------------------------------------------------
+def _cascade():
+    """test_culling.py's graph on which two culls follow one another: the first leaves point 10 with nObs = 3, the second turns it bad, and
+    the third local keyframe counts no point any more.  The device keeps that state in the zeroed prefix of its work space."""
+    kfs, points = K.star(10, 10)
+    kfs.append(dict(slots=[(10, 5.0, 2)]))
+    points.append(dict(obs=[(0, 2, 2), (1, 2, 1), (2, 2, 1), (6, 2, 1)]))
+    for k in (0, 1, 2):
+        kfs[k]["slots"].append((10, 5.0, 2))
+    for p in points[:10]:
+        p["obs"] += [(5, 2, 2)]
+    return K.hand(kfs, points, [0, 1, 6])
+
+
+@functools.lru_cache(maxsize=None)
+def _tiny():
+    """Problems of the smallest generated size (5 keyframes), the cascade among them."""
+    return [_cascade()] + [K.make_problem(700 + i, 5, 375, inertial=bool(i % 2)) for i in range(15)]
+
+
+def _equals_host(pkg, problems, what):
+    got = pkg.keyframe_culling_batch(problems)
+    host = pkg.keyframe_culling_batch(problems, host=True)
+    assert len(got) == len(host) == len(problems)
+    for i, (g, h) in enumerate(zip(got, host)):
+        K.assert_equal(g, h, "%s: problem %d, device against host" % (what, i))
+    return got
+
+
+def test_device_reuses_its_buffers_across_batch_sizes(pkg):
+    """8 problems, then 1 other, then the 8 again through the same buffers: nothing of an earlier call shows in a later one."""
+    tiny = _tiny()
+    eight, one = tiny[:8], [tiny[8]]
+    # whatever the tests before left, the calls below meet buffers a larger batch has filled, with every point bad
+    _equals_host(pkg, [dict(p, point_bad=np.ones_like(p["point_bad"])) for p in tiny], "fill")
+    first = _equals_host(pkg, eight, "8")
+    assert first[0]["verdict"].tolist() == [3, 3, 0] and first[0]["point_bad_after"][10] == 1 and first[0]["n_mps"][2] == 0
+    _equals_host(pkg, one, "1")
+    again = _equals_host(pkg, eight, "8 again")
+    for i, (a, b) in enumerate(zip(first, again)):
+        K.assert_equal(a, b, "problem %d, first against third call" % i)
+    pt = K.random_points(31, 2000)
+    for n in (2000, 1, 2000):
+        cut = {k: v[:n] for k, v in pt.items()}
+        assert np.array_equal(pkg.map_point_culling_batch(cut), pkg.map_point_culling_batch(cut, host=True)), n
+
+
+def test_device_empty_problem_inside_a_batch(pkg):
+    """A problem without keyframes, points or local list between two ordinary ones: its tables are empty places in the concatenation."""
+    tiny = _tiny()
+    empty = K.hand([], [], [])
+    for middle in (empty, K.hand([dict(slots=[])], [], [])):
+        got = _equals_host(pkg, [tiny[0], middle, tiny[1]], "empty in the middle")
+        assert got[1]["n_visited"] == 0 and len(got[1]["verdict"]) == 0 and len(got[1]["point_bad_after"]) == 0
+    _equals_host(pkg, [empty, tiny[0], empty], "empty at both ends")
+    _equals_host(pkg, [empty], "empty alone")
+
+
+def test_device_two_callers_at_once(pkg):
+    """Two threads, four calls each on batches of four of their own: each gets its own results."""
+    import two_callers
+    tiny = _tiny()
+    batches = [[[tiny[8 * t + (2 * s + i) % 8] for i in range(4)] for s in range(4)] for t in (0, 1)]
+    want = [[pkg.keyframe_culling_batch(b, host=True) for b in side] for side in batches]
+    got = two_callers.run(pkg.keyframe_culling_batch, batches[0], batches[1])
+    for t in (0, 1):
+        for c, (g, w) in enumerate(zip(got[t], want[t])):
+            assert len(g) == len(w) == 4
+            for i in range(4):
+                K.assert_equal(g[i], w[i], "thread %d, call %d, problem %d" % (t, c, i))
+    pts = [[K.random_points(40 + 4 * t + c, 500 + 100 * c) for c in range(4)] for t in (0, 1)]
+    got = two_callers.run(pkg.map_point_culling_batch, pts[0], pts[1])
+    for t in (0, 1):
+        for c in range(4):
+            assert np.array_equal(got[t][c], pkg.map_point_culling_batch(pts[t][c], host=True)), (t, c)

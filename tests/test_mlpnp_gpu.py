@@ -189,3 +189,80 @@ def test_relocalisation_chain(pkg, oracle, synthetic):
         assert np.array_equal(got["kf_keypoint_of_keypoint"][h, :N], want["assign"]) and np.array_equal(got["outlier"][h, :N], want["outlier"]), h
         n_success += bool(want["status"] & R.SUCCESS)
     assert n_success >= len(refs) - 1 and n_success >= 3, n_success
+
+
+# ---- the buffers kept between calls -------------------------------------------------------------------------------------------------------
+import functools
+
+
+@functools.lru_cache(maxsize=None)
+def _tiny(pkg):
+    """-> (problems, bounds): 16 problems of the mixed batch's smallest size, 15 correspondences, every fourth a hard one, with the bound on
+    device against host that the restatement's variants give (mlpnp_cases.compare_call, here on the host entry's result).  Problems 7 and 15 are too small to iterate and come with a
+    state: the solver hands best_inlier, iterations and best_Tcw back as they came, so what went up must be what comes down."""
+    problems = [(K.hard if i % 4 == 1 else K.easy)(41000 + i, 15) for i in range(16)]
+    for i in (7, 15):
+        pr = K.easy(41100 + i, 6)
+        n = len(pr["keys"])
+        problems[i] = dict(pr, iterations=2, best_inliers=3, best_Tcw=np.arange(12, dtype=np.float32), best_inlier=(np.arange(n) % 2).astype(np.uint8))
+    bounds = []
+    for pr in problems:
+        if "best_inlier" in pr:
+            bounds.append(1e-12)
+            continue
+        solvers = K.solvers_for(pr)
+        res = K.compare_call(solvers, pr["n_iterations"], pr["draws"], _run(pkg, [pr], host=True), 0, K.new_report())
+        assert not res["left_out"]
+        bounds.append(res["bound"])
+    return problems, bounds
+
+
+def _equals_host(pkg, problems, bounds, what):
+    dev = _run(pkg, problems, host=False)
+    host = _run(pkg, problems, host=True, capacity=dev["inlier"].shape[1])
+    for p, pr in enumerate(problems):
+        _device_equals_host(dev, host, p, len(pr["keys"]), bounds[p])
+        assert np.array_equal(dev["best_Tcw"][p], host["best_Tcw"][p]) and np.array_equal(dev["pose7"][p], host["pose7"][p]), (what, p)
+        if "best_inlier" in pr:
+            assert np.array_equal(dev["best_inlier"][p][:len(pr["keys"])], pr["best_inlier"]) and dev["iterations"][p] == pr["iterations"], (what, p)
+    return dev
+
+
+def _same(a, b, what):
+    for k in a:
+        assert np.array_equal(a[k], b[k]), (what, k)
+
+
+def test_device_reuses_its_buffer_across_batch_sizes(pkg):
+    """8 problems, then 1 other, then the 8 again through the same buffer: nothing of an earlier call shows in a later one."""
+    problems, bounds = _tiny(pkg)
+    _equals_host(pkg, problems, bounds, "fill")                                      # whatever the tests before left, the buffer is larger than the calls below need
+    first = _equals_host(pkg, problems[:8], bounds[:8], "8")
+    assert first["found"].sum() >= 3 and first["no_more"][7] == 1
+    _equals_host(pkg, problems[8:9], bounds[8:9], "1")
+    _same(first, _equals_host(pkg, problems[:8], bounds[:8], "8 again"), "first against third call")
+
+
+def test_device_empty_problem_inside_a_batch(pkg):
+    """A problem without keypoints, points or draws between two ordinary ones: its tables are empty places in the concatenation, and its
+    row of the inlier flags stays zero."""
+    problems, bounds = _tiny(pkg)
+    empty = dict(keys=np.zeros(0, K.KEYPOINT_DTYPE), match=np.zeros(0, np.int32), Xw=np.zeros((0, 3), np.float32), draws=np.zeros(0, np.uint32))
+    dev = _equals_host(pkg, [problems[0], empty, problems[1]], [bounds[0], 1e-12, bounds[1]], "empty in the middle")
+    assert dev["found"][1] == 0 and dev["no_more"][1] == 1 and not dev["inlier"][1].any() and not dev["best_inlier"][1].any()
+    _equals_host(pkg, [empty, problems[0], empty], [1e-12, bounds[0], 1e-12], "empty at both ends")
+    _equals_host(pkg, [empty], [1e-12], "empty alone")
+
+
+def test_device_two_callers_at_once(pkg):
+    """Two threads, four calls each on batches of four of their own: each gets its own results."""
+    import two_callers
+    problems, bounds = _tiny(pkg)
+    index = [[[8 * t + (2 * s + i) % 8 for i in range(4)] for s in range(4)] for t in (0, 1)]
+    batches = [[[problems[k] for k in b] for b in side] for side in index]
+    got = two_callers.run(lambda b: _run(pkg, b, host=False), batches[0], batches[1])
+    for t in (0, 1):
+        for c in range(4):
+            host = _run(pkg, batches[t][c], host=True, capacity=got[t][c]["inlier"].shape[1])
+            for i, k in enumerate(index[t][c]):
+                _device_equals_host(got[t][c], host, i, len(problems[k]["keys"]), bounds[k])

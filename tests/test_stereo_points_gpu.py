@@ -126,3 +126,69 @@ def test_device_batch_of_noes(pkg):
         assert g["n_with_depth"] == int((f["depth"] > 0).sum())
         close = (f["depth"] > 0) & (f["depth"] < f["th_depth"])
         assert g["n_tracked_close"] + g["n_non_tracked_close"] == int(close.sum())
+
+
+# ---- the buffers kept between calls -------------------------------------------------------------------------------------------------------
+def _tiny():
+    """The family's frames of 63, 64 and 65 keypoints with their decisions, the first 16."""
+    frames, decisions = K.family()
+    pick = [k for k in range(len(frames)) if len(frames[k]["depth"]) <= 65][:16]
+    return [frames[k] for k in pick], [decisions[k] for k in pick]
+
+
+def _equal_host(pkg, frames, decisions, what):
+    got = pkg.stereo_points_batch(frames, U4)
+    host = pkg.stereo_points_batch(frames, U4, host=True)
+    dec = pkg.new_keyframe_batch(frames, decisions, U4)
+    dech = pkg.new_keyframe_batch(frames, decisions, U4, host=True)
+    assert len(got) == len(host) == len(dec) == len(dech) == len(frames)
+    for i in range(len(frames)):
+        K.assert_equal(got[i], host[i], "%s: frame %d, points, device against host" % (what, i))
+        K.assert_equal(dec[i], dech[i], "%s: frame %d, decision, device against host" % (what, i), T.ALL_OUTPUTS)
+    return got, dec
+
+
+def test_device_reuses_its_buffers_across_batch_sizes(pkg):
+    """8 frames, then 1 other, then the 8 again through the same buffers, the two entries in turn: nothing of an earlier call shows in a
+    later one."""
+    frames, decisions = _tiny()
+    _equal_host(pkg, frames, decisions, "fill")                                      # whatever the tests before left, the buffers are larger than the calls below need
+    first = _equal_host(pkg, frames[:8], decisions[:8], "8")
+    assert sum(g["n_created"] for g in first[0]) > 100 and {int(g["need"]) for g in first[1]} == {0, 1}
+    _equal_host(pkg, frames[8:9], decisions[8:9], "1")
+    again = _equal_host(pkg, frames[:8], decisions[:8], "8 again")
+    for i in range(8):
+        K.assert_equal(first[0][i], again[0][i], "frame %d, points, first against third call" % i)
+        K.assert_equal(first[1][i], again[1][i], "frame %d, decision, first against third call" % i, T.ALL_OUTPUTS)
+
+
+def test_device_empty_frame_inside_a_batch(pkg):
+    """A frame without keypoints, decided without ref_nobs, between two ordinary ones: its tables are empty places in the concatenation."""
+    frames, decisions = _tiny()
+    empty, plain = K.frame([]), K.decision(frame_id=120)
+    got, dec = _equal_host(pkg, [frames[0], empty, frames[1]], [decisions[0], plain, decisions[1]], "empty in the middle")
+    assert got[1]["n_created"] == 0 and got[1]["n_with_depth"] == 0 and len(got[1]["created_keypoint"]) == 0 and dec[1]["n_created"] == 0
+    _equal_host(pkg, [empty, frames[0], empty], [plain, decisions[0], plain], "empty at both ends")
+    _equal_host(pkg, [empty], [plain], "empty alone")
+
+
+def test_device_two_callers_at_once(pkg):
+    """Two threads, four calls each on batches of four of their own: each gets its own results.  The two entries share their buffers, so
+    one thread creates points and the other decides."""
+    import two_callers
+    frames, decisions = _tiny()
+    batches = [[[8 * t + (2 * s + i) % 8 for i in range(4)] for s in range(4)] for t in (0, 1)]
+    points = [[frames[k] for k in b] for b in batches[0]]
+    decided = [([frames[k] for k in b], [decisions[k] for k in b]) for b in batches[1]]
+
+    def call(b):
+        return pkg.new_keyframe_batch(b[0], b[1], U4) if isinstance(b, tuple) else pkg.stereo_points_batch(b, U4)
+
+    got = two_callers.run(call, points, decided)
+    for c in range(4):
+        want = pkg.stereo_points_batch(points[c], U4, host=True)
+        wantd = pkg.new_keyframe_batch(decided[c][0], decided[c][1], U4, host=True)
+        assert len(got[0][c]) == len(got[1][c]) == 4
+        for i in range(4):
+            K.assert_equal(got[0][c][i], want[i], "points, call %d, frame %d" % (c, i))
+            K.assert_equal(got[1][c][i], wantd[i], "decision, call %d, frame %d" % (c, i), T.ALL_OUTPUTS)
