@@ -2059,6 +2059,45 @@ int tc2li_inertial_window_outliers(const tc2li_ba_edge* edges, const double* edg
                                    const uint8_t* point_bad_now, const float* track_depth, int n_points, double initial_chi2,
                                    double final_chi2, int large, int32_t* rejected, int32_t* erase_pose, int32_t* erase_point, int capacity);
 
+/* ---- local mapping: the inertial term of local-BA windows ----------------------------------------------------------------------------
+ * The inertial edges of a window -- EdgeInertial, EdgeGyroRW and EdgeAccRW per link (SF/src/G2oTypes.cc:499-601, SF/include/G2oTypes.h:645-714)
+ * -- evaluated at given states for many windows at once: the robust cost and, with linearize, the normal equations.  The values per link
+ * are those the inertial local BA uses (tc2li_local_inertial_bundle_adjustment): information = inverse of C(0:9, 0:9), symmetrised,
+ * eigenvalues below 1e-12 cleared, times info_scale; random-walk informations = the inverses of the two 3 x 3 bias-walk blocks of C; Huber
+ * with sqrtf(16.92f) on the inertial edge where `robust`, never on the random-walk edges.  A building block: the LM loop of the inertial
+ * windows does not call it yet.
+ * Unknowns of a keyframe (15): pose 6 (the body-frame update of VertexPose) | velocity 3 | gyro bias 3 | acc bias 3.
+ *   chi2 [1]: the sum over the links, in link order, of rho(e' Omega e) + the two random-walk costs
+ *   H_diag [n_keyframes][15][15] row-major: per keyframe the sum, in link order, of the diagonal contributions of every link that touches
+ *     it, the random-walk informations on the bias diagonals included.  For kf2 the inertial edge has pose and velocity columns only.
+ *   H_link [n_links][15][15]: link l's off-diagonal block, rows = kf1's unknowns, columns = kf2's; the transpose is implied
+ *   b [n_keyframes][15] = -J' (rho' Omega) e
+ * Rows and columns of a fixed keyframe are zero (so is H_link of a link with a fixed end), and the whole block of a keyframe no link
+ * touches.  With linearize == 0 only chi2 is written and H_diag, H_link, b may be NULL. */
+typedef struct tc2li_inertial_term_problem {
+    const tc2li_inertial_keyframe* keyframes;   /* [n_keyframes] the state the term is evaluated at */
+    const uint8_t* fixed;                       /* [n_keyframes] as tc2li_local_inertial_bundle_adjustment */
+    const uint8_t* has_imu;                     /* [n_keyframes] */
+    const tc2li_inertial_link* links;           /* [n_links] */
+    int32_t n_keyframes, n_links;
+    double* chi2;
+    double* H_diag;
+    double* H_link;
+    double* b;
+} tc2li_inertial_term_problem;
+/* On the device: one upload, the launches, one download; the results are in host memory when the call returns (stream: NULL = the calling
+ * thread's private stream).  The information matrices are prepared on the host, once per link and call.  A window's results are the same
+ * bits alone and anywhere in any batch, and from call to call.  TC2LI_ERR_INVALID before any launch, naming the window and the link, and
+ * with no output written: a link's keyframe index out of range, kf1 == kf2, a link to a keyframe with has_imu == 0, a NULL
+ * pre-integration, a covariance that is not positive definite, NULL arrays, sizes that are negative or beyond
+ * tc2li_inertial_term_limits.  Returns n_problems. */
+int tc2li_inertial_term_batch(const tc2li_inertial_term_problem* problems, int n_problems, int linearize, void* stream);
+/* The same contract on host threads: the same per-link arithmetic and the same sums in the same order (the two differ by the compilers'
+ * contraction and the math libraries only).  Needs no device. */
+int tc2li_host_inertial_term_batch(const tc2li_inertial_term_problem* problems, int n_problems, int linearize);
+/* out[0] = the most keyframes, out[1] = the most links a window may have.  Returns 2.  Needs no device.  No reference counterpart. */
+int tc2li_inertial_term_limits(int32_t* out, int capacity);
+
 /* ---- tracking: stereo map points and the keyframe decision (SF/src/Tracking.cc:2942-3076 NeedNewKeyFrame, :3078-3212 CreateNewKeyFrame,
  * :2676-2734 UpdateLastFrame, :2477-2495 StereoInitialization) ----------------------------------------------------------------------------
  * The step between TrackLocalMap and local mapping: whether the frame becomes a keyframe, and which of its stereo keypoints become new map

@@ -3410,3 +3410,68 @@ def image_prep_batch(prep, images, maps=None, host=False, out=None, stream=0):
         ptr, on_device = images.ctypes.data, False
     prep.batch_ptr(ptr, on_device, n, row, one, out.data_ptr(), p.dst_width, p.dst_width * p.dst_height, stream=stream)
     return out
+
+
+class InertialTermProblem(C.Structure):
+    """tc2li_inertial_term_problem"""
+    _fields_ = [(k, C.c_void_p) for k in ("keyframes", "fixed", "has_imu", "links")] + [("n_keyframes", C.c_int32), ("n_links", C.c_int32)] \
+        + [(k, C.c_void_p) for k in ("chi2", "H_diag", "H_link", "b")]
+
+
+def inertial_term_limits():
+    """tc2li_inertial_term_limits -> {max_keyframes, max_links}: the largest window inertial_term_batch takes."""
+    out = (C.c_int32 * 2)()
+    f = lib().tc2li_inertial_term_limits
+    f.argtypes = [C.c_void_p, C.c_int]
+    _check(f(out, 2))
+    return dict(zip(("max_keyframes", "max_links"), [int(v) for v in out]))
+
+
+def pack_inertial_term_problems(problems, linearize=True, out=None):
+    """The tc2li_inertial_term_problem array of a batch -> (array, the four output arrays per problem, what must stay alive); the arguments
+    are those of :func:`inertial_term_batch`."""
+    n = len(problems)
+    arr, keep, res = (InertialTermProblem * max(n, 1))(), [], []
+    for i, p in enumerate(problems):
+        kf = np.ascontiguousarray(p["kf33"], np.float64).reshape(-1, 33)
+        fixed, has_imu = np.ascontiguousarray(p["fixed"], np.uint8), np.ascontiguousarray(p["has_imu"], np.uint8)
+        link4 = np.ascontiguousarray(p["link4"], np.float64).reshape(-1, 4)
+        K, L = len(kf), len(link4)
+        if len(fixed) != K or len(has_imu) != K or len(p["pre"]) != L:
+            raise ValueError("problem %d: fixed / has_imu need one entry per keyframe, pre one per link" % i)
+        links = (InertialLink * max(L, 1))()
+        for l, row in enumerate(link4):
+            pre = p["pre"][l]
+            links[l] = InertialLink(int(row[0]), int(row[1]), int(row[2] != 0), 0, float(row[3]), C.addressof(pre.p) if pre is not None else None)
+        if out is not None:
+            o = [np.ascontiguousarray(a, np.float64) for a in out[i]]
+            if any(o[j] is not out[i][j] for j in range(4)) or [a.size for a in o] != [1, K * 225, L * 225, K * 15]:
+                raise ValueError("problem %d: out needs contiguous float64 arrays of 1, K * 225, L * 225 and K * 15 entries" % i)
+        elif linearize:
+            o = [np.zeros(1), np.zeros((K, 15, 15)), np.zeros((L, 15, 15)), np.zeros((K, 15))]
+        else:
+            o = [np.zeros(1), None, None, None]
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        arr[i] = InertialTermProblem(ptr(kf), ptr(fixed), ptr(has_imu), C.addressof(links) if L else None, K, L, o[0].ctypes.data, ptr(o[1]), ptr(o[2]), ptr(o[3]))
+        keep.append((kf, fixed, has_imu, links, p["pre"]))
+        res.append(o)
+    return arr, res, keep
+
+
+def inertial_term_batch(problems, linearize=True, host=False, out=None, stream=0):
+    """``tc2li_inertial_term_batch`` (host=True: ``tc2li_host_inertial_term_batch``): the inertial term of many local-BA windows at given
+    states.  problems: dicts in the form of ``synthetic.inertial_window`` -- kf33 [K, 33], fixed [K], has_imu [K], link4 [L, 4] = kf1, kf2,
+    robust, info_scale -- with pre: one ``Preintegrated`` per link (None: a NULL pointer).
+    -> per window (chi2, H_diag [K, 15, 15], H_link [L, 15, 15], b [K, 15]); with linearize=False the three arrays are None and NULL is
+    passed for them.  out: per window the four arrays to write into (tests: prefilled with a sentinel), passed whatever linearize is."""
+    n = len(problems)
+    arr, res, keep = pack_inertial_term_problems(problems, linearize, out)
+    if host:
+        f = lib().tc2li_host_inertial_term_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _check(f(C.addressof(arr), n, int(bool(linearize))))
+    else:
+        f = lib().tc2li_inertial_term_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _check(f(C.addressof(arr), n, int(bool(linearize)), C.c_void_p(stream)))
+    return [(float(o[0].reshape(-1)[0]), o[1], o[2], o[3]) for o in res]

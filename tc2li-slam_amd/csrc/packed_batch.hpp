@@ -33,7 +33,7 @@ struct PackedSpace {
     DevBuf<uint8_t> io, work;
     PinnedBuf<uint8_t> h_io;
 };
-enum PackedSpaceTag { kSpaceKeyframeCulling, kSpaceMapPointCulling, kSpaceConnections, kSpaceCovisibles, kSpaceStereoPoints, kSpaceMlpnp, kSpaceInertialWindow };
+enum PackedSpaceTag { kSpaceKeyframeCulling, kSpaceMapPointCulling, kSpaceConnections, kSpaceCovisibles, kSpaceStereoPoints, kSpaceMlpnp, kSpaceInertialWindow, kSpaceInertialTerm };
 
 // One call's transfer.  The entry take()s its inputs from io, calls state_begins() and takes the tables that go up and come back (an
 // entry without such tables skips this), calls outputs_begin() and takes its outputs; it takes its work tables from work.  Then, under

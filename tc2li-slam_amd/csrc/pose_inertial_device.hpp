@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/tc2li_hip.h"
 #include "inertial_math.hpp"
@@ -36,6 +37,19 @@ struct PiResult {
     double Hv[21];          // sum over the inlier edges of B^T Omega B (upper triangle, row-major)
     int32_t n_bad, n_inliers, solver_failed, pad_;
 };
+
+// the caller's records into the kernels' (the informations of PiPreint are the host's to prepare)
+inline void pi_state_from(const tc2li_inertial_keyframe& k, PiState& s) {
+    memcpy(s.P.Rcw, k.Rcw, 72); memcpy(s.P.tcw, k.tcw, 24); memcpy(s.P.Rwb, k.Rwb, 72); memcpy(s.P.twb, k.twb, 24);
+    s.P.its = 0; s.P.pad_ = 0;  // ImuCamPose(Frame*): its = 0
+    memcpy(s.v, k.velocity, 24); memcpy(s.bg, k.gyro_bias, 24); memcpy(s.ba, k.acc_bias, 24);
+}
+inline void pi_preint_from(const tc2li_preintegrated& q, PiPreint& d) {
+    d.dT = q.dT;
+    memcpy(d.dR, q.dR, 36); memcpy(d.dV, q.dV, 12); memcpy(d.dP, q.dP, 12); memcpy(d.JRg, q.JRg, 36); memcpy(d.JVg, q.JVg, 36);
+    memcpy(d.JVa, q.JVa, 36); memcpy(d.JPg, q.JPg, 36); memcpy(d.JPa, q.JPa, 36);
+    d.bias[0] = q.bias.bax; d.bias[1] = q.bias.bay; d.bias[2] = q.bias.baz; d.bias[3] = q.bias.bwx; d.bias[4] = q.bias.bwy; d.bias[5] = q.bias.bwz;
+}
 
 void launch_pose_inertial(const PiProblem* probs, int n, const double* Xw, const BaEdge* edges, const uint8_t* close, const ImuCalib& cal,
                           const CameraD& cam, uint8_t* outlier, double* chi2_scratch, PiResult* results, hipStream_t st);

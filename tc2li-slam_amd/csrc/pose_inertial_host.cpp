@@ -30,11 +30,6 @@ struct PiWorkspace {
 };
 PiWorkspace& pi_ws() { static thread_local PiWorkspace w; return w; }
 
-void state_from(const tc2li_inertial_keyframe& k, PiState& s) {
-    memcpy(s.P.Rcw, k.Rcw, 72); memcpy(s.P.tcw, k.tcw, 24); memcpy(s.P.Rwb, k.Rwb, 72); memcpy(s.P.twb, k.twb, 24);
-    s.P.its = 0; s.P.pad_ = 0;  // ImuCamPose(Frame*): its = 0
-    memcpy(s.v, k.velocity, 24); memcpy(s.bg, k.gyro_bias, 24); memcpy(s.ba, k.acc_bias, 24);
-}
 void state_to(const PiState& s, tc2li_inertial_keyframe& k) {
     memcpy(k.Rcw, s.P.Rcw, 72); memcpy(k.tcw, s.P.tcw, 24); memcpy(k.Rwb, s.P.Rwb, 72); memcpy(k.twb, s.P.twb, 24);
     memcpy(k.velocity, s.v, 24); memcpy(k.gyro_bias, s.bg, 24); memcpy(k.acc_bias, s.ba, 24);
@@ -151,12 +146,8 @@ extern "C" int tc2li_pose_inertial_optimization_batch(tc2li_pose_inertial_proble
         PiProblem& d = probs[f];
         const int32_t edge_off = d.edge_off;
         memset(&d, 0, sizeof(d));
-        state_from(p.frame, d.cur); state_from(p.other, d.other);
-        const tc2li_preintegrated& q = *p.preintegrated;
-        d.pre.dT = q.dT;
-        memcpy(d.pre.dR, q.dR, 36); memcpy(d.pre.dV, q.dV, 12); memcpy(d.pre.dP, q.dP, 12); memcpy(d.pre.JRg, q.JRg, 36); memcpy(d.pre.JVg, q.JVg, 36);
-        memcpy(d.pre.JVa, q.JVa, 36); memcpy(d.pre.JPg, q.JPg, 36); memcpy(d.pre.JPa, q.JPa, 36);
-        d.pre.bias[0] = q.bias.bax; d.pre.bias[1] = q.bias.bay; d.pre.bias[2] = q.bias.baz; d.pre.bias[3] = q.bias.bwx; d.pre.bias[4] = q.bias.bwy; d.pre.bias[5] = q.bias.bwz;
+        pi_state_from(p.frame, d.cur); pi_state_from(p.other, d.other);
+        pi_preint_from(*p.preintegrated, d.pre);
         InertialLinkHost li, lw;  // the informations: EdgeInertial's from `preintegrated`, the random-walk ones from `preintegrated_rw` (:2645, :3049)
         li.pre = p.preintegrated; lw.pre = p.preintegrated_rw;
         if (!li.prepare(1.0) || !lw.prepare(1.0)) { bad_frame.store(f); return; }
