@@ -143,6 +143,12 @@ int tc2li_orb_last_timings(const tc2li_orb* orb, float ms[8]);
  * chunk before): every device stage is launched once per chunk, and [0]..[5] above are the sums over the chunks.  Returns the chunk
  * count of the last call. */
 int tc2li_orb_last_chunks(const tc2li_orb* orb);
+/* The projection searches on the features of the last tc2li_orb_extract_batch call (tc2li_track_motion_model_batch and its retry pass,
+ * tc2li_track_local_map_batch, tc2li_search_local_points_batch, the refinement ladder of relocalisation) share one feature grid per left
+ * image, as Frame's constructor builds mGrid once: the first search after an extraction builds the grids of all frames, on its stream,
+ * and an extraction drops them.  Returns how many such builds the handle has done.  TC2LI_MATCH_GRID_CACHE=0 (read per call) makes every
+ * search build its own grids and leaves the count alone. */
+int tc2li_orb_match_grid_builds(tc2li_orb* orb);
 
 /* ------------------------------------------------------------------------------------------------
  * Stereo matching -- replaces Frame::ComputeStereoMatches (SF/src/Frame.cc:841-1011; called from the stereo

@@ -376,6 +376,12 @@ class OrbExtractor:
         """Chunks of images the last batch call was pipelined over (every device stage is launched once per chunk)."""
         return _check(lib().tc2li_orb_last_chunks(self._h))
 
+    def match_grid_builds(self):
+        """Feature-grid builds of the handle so far: one per extraction that a projection search followed (tc2li_orb_match_grid_builds)."""
+        f = lib().tc2li_orb_match_grid_builds
+        f.argtypes = [C.c_void_p]
+        return _check(f(self._h))
+
 
 def compute_stereo_matches(ext_left, ext_right, kps_l, desc_l, kps_r, desc_r, bf, b):
     """``Frame::ComputeStereoMatches`` (SF/src/Frame.cc:841): returns (mvuRight, mvDepth, bestSAD)."""

@@ -22,7 +22,7 @@ static_assert(sizeof(MatchQuery) == 64, "layout");
 
 struct MatchFrameDev {
     const MatchKey* keys;
-    const uint8_t* desc;
+    const uint8_t* desc;      // 32 bytes per key, 16-byte aligned (read as two 16-byte loads)
     const float* u_right;
     const uint8_t* occupied;
     const MatchQuery* queries;
@@ -47,8 +47,10 @@ struct MatchLists {
     int32_t* cand_cnt;     // [total queries], bit 30 = has_observations
     uint32_t* pool;
     int32_t* pool_top;     // [0] = entries used, [1] = overflow flag
-    int32_t pool_cap, pad_;
-    const int32_t* cell_row;  // k_match_grid only: frame f writes row cell_row[f] of cell_start; NULL = row f (the keyframe store: row = slot)
+    int32_t pool_cap;
+    int32_t grid_ready;    // launch_match_lists: cell_start / items hold the frames' grids already (frame_grids of projection_search.hpp)
+    const int32_t* cell_row;  // frame f's row of cell_start is cell_row[f]; NULL = row f (the keyframe store: row = slot; a pass over some
+                              // of a handle's frames: row = frame)
 };
 // only the feature grids (cell_start, items) of the frames: used by the fuse search as well
 void launch_match_grid(const MatchFrameDev* frames, int nframes, const MatchLists& L, hipStream_t st);

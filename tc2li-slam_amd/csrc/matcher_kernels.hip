@@ -14,6 +14,9 @@
 #pragma clang fp contract(off)
 #include <stdint.h>
 
+#include <algorithm>
+#include <cstdlib>
+
 #include "matcher_device.hpp"
 
 namespace tc2li {
@@ -162,7 +165,8 @@ __global__ __launch_bounds__(kThreads) void k_match_by_projection(const MatchFra
 // k_match_by_projection recomputes every Hamming distance in every round with one workgroup per frame.  Everything except
 // "claimed by an earlier query" is independent of the rounds, so:
 //   k_match_grid        one workgroup per frame: the 64x48 feature grid (cell starts, keypoint indices ascending per cell) in HBM
-//   k_match_candidates  one thread per query over the whole batch: the candidates that pass the static tests of the loop
+//                       (the frames of an extractor handle: once per extraction, frame_grids of projection_search.hpp)
+//   k_match_candidates  a sub-group of lanes per query over the whole batch: the candidates that pass the static tests of the loop
 //                       body, in scan order, with their descriptor distance (idx | dist << 12 | octave << 21), into a pool
 //   k_match_resolve     one workgroup per frame: the fixed-point rounds walk the short candidate lists only
 
@@ -219,15 +223,22 @@ __global__ __launch_bounds__(kThreads) void k_match_grid(const MatchFrameDev* __
     for (int i = tid; i < n_in; i += kThreads) it[i] = s_items[i];
 }
 
+// what a lane needs of its query for the static tests
+struct QueryWindow {
+    float u, v, r, u_right;
+    int min_level, max_level;
+    bool check_levels;
+};
+
 // the static part of the loop body for one candidate: level window, search window, occupancy, stereo coordinate
-__device__ __forceinline__ bool candidate_ok(const MatchFrameDev& fr, const MatchQuery& Q, bool check_levels, int idx, int& oct) {
+__device__ __forceinline__ bool candidate_ok(const MatchFrameDev& fr, const QueryWindow& Q, int idx, int& oct) {
     const MatchKey k = fr.keys[idx];
     oct = k.octave;
-    if (check_levels) {
+    if (Q.check_levels) {
         if (oct < Q.min_level) return false;
         if (Q.max_level >= 0 && oct > Q.max_level) return false;
     }
-    const float r = Q.radius;
+    const float r = Q.r;
     if (!(fabsf(k.x - Q.u) < r && fabsf(k.y - Q.v) < r)) return false;
     if (fr.occupied && fr.occupied[idx]) return false;
     const float ur = fr.u_right[idx];
@@ -237,62 +248,144 @@ __device__ __forceinline__ bool candidate_ok(const MatchFrameDev& fr, const Matc
     return true;
 }
 
-__global__ __launch_bounds__(256) void k_match_candidates(const MatchFrameDev* __restrict__ frames, int nframes, const int32_t* __restrict__ query_frame,
-                                                          int total_q, MatchLists L) {
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    if (g >= total_q) return;
-    const int f = query_frame[g];
-    if (f < 0) { L.cand_cnt[g] = 0; L.cand_off[g] = 0; return; }
-    const MatchFrameDev fr = global_record(frames[f]);
-    const MatchQuery Q = fr.queries[g - fr.query_off];
-    const int flags = Q.has_observations ? (1 << 30) : 0;
-    if (!Q.valid || fr.n_keys == 0) { L.cand_cnt[g] = flags; L.cand_off[g] = 0; return; }
-    const float invW = (float)kGridCols / (fr.max_x - fr.min_x), invH = (float)kGridRows / (fr.max_y - fr.min_y);
-    const float r = Q.radius;
-    const int minCX = max(0, (int)floorf((Q.u - fr.min_x - r) * invW));
-    const int maxCX = min(kGridCols - 1, (int)ceilf((Q.u - fr.min_x + r) * invW));
-    const int minCY = max(0, (int)floorf((Q.v - fr.min_y - r) * invH));
-    const int maxCY = min(kGridRows - 1, (int)ceilf((Q.v - fr.min_y + r) * invH));
-    const bool any = !(minCX >= kGridCols || maxCX < 0 || minCY >= kGridRows || maxCY < 0);
-    const bool check_levels = (Q.min_level > 0) || (Q.max_level >= 0);
-    const int32_t* cs = L.cell_start + (size_t)f * (kCells + 1);
-    const uint16_t* items = L.items + L.key_base[f];
+constexpr int kCandThreads = 256;
+// candidates a sub-group keeps in LDS until the pool space is reserved (the pool's default: 32 per query); narrow sub-groups are many per
+// workgroup and keep half as many
+constexpr int cand_stage(int lanes) { return lanes >= 8 ? 32 : 16; }
+
+// LDS written by some lanes of a wavefront and read by others of the same wavefront
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the ballot of the W lanes of the caller's sub-group (every lane of a sub-group runs the same loops, so they are active together)
+template <int W>
+__device__ __forceinline__ uint32_t sub_ballot(bool p) {
+    const unsigned long long m = __ballot(p);
+    return (uint32_t)(m >> ((threadIdx.x & 63) / W * W)) & (W == 32 ? 0xffffffffu : (1u << (W & 31)) - 1u);
+}
+
+// One walk over a query's window in the reference's order: ix outer, iy inner, key index ascending.  The cells iy = minCY .. maxCY of a
+// column are neighbours in cell_start, so a column is ONE run of items.  The W lanes of the sub-group take a run W keys at a time -- the
+// gathers of a round (item, key, occupied, u_right, descriptor) are independent of each other -- and a ballot gives every passing key its
+// place in the list.  kStage > 0: the count is not known yet, the first kStage entries go to the sub-group's LDS stage `out`; 0: `out` is
+// the query's pool space.  Returns the number of candidates.
+template <int W, int kStage>
+__device__ __forceinline__ int walk_window(const MatchFrameDev& fr, const QueryWindow& Q, const uint4 qd0, const uint4 qd1, const int32_t* cs,
+                                           const uint16_t* items, int minCX, int maxCX, int minCY, int maxCY, int sl, uint32_t* out) {
+    const uint4* D = reinterpret_cast<const uint4*>(fr.desc);
+    const int span = maxCY - minCY + 1;
+    int c0 = minCX * kGridRows + minCY;
+    int b = cs[c0], e = cs[c0 + span];
     int cnt = 0;
-    if (any)
-        for (int ix = minCX; ix <= maxCX; ++ix)
-            for (int iy = minCY; iy <= maxCY; ++iy) {
-                const int c = ix * kGridRows + iy;
-                for (int k = cs[c]; k < cs[c + 1]; ++k) {
-                    int oct;
-                    cnt += candidate_ok(fr, Q, check_levels, items[k], oct) ? 1 : 0;
-                }
-            }
-    int off = 0;
-    if (cnt) {
-        off = atomicAdd(L.pool_top, cnt);
-        if (off + cnt > L.pool_cap) { L.pool_top[1] = 1; cnt = 0; off = 0; }
-    }
-    L.cand_off[g] = off;
-    L.cand_cnt[g] = cnt | flags;
-    if (!cnt) return;
-    const uint32_t* D = reinterpret_cast<const uint32_t*>(fr.desc);
-    const uint32_t* qd = reinterpret_cast<const uint32_t*>(Q.desc);
-    uint32_t* out = L.pool + off;
-    int w_ = 0;
-    for (int ix = minCX; ix <= maxCX; ++ix)
-        for (int iy = minCY; iy <= maxCY; ++iy) {
-            const int c = ix * kGridRows + iy;
-            for (int k = cs[c]; k < cs[c + 1]; ++k) {
+    for (int ix = minCX; ix <= maxCX; ++ix) {
+        c0 += kGridRows;
+        int nb = 0, ne = 0;
+        if (ix < maxCX) { nb = cs[c0]; ne = cs[c0 + span]; }  // the next column's run: in flight under this column's keys
+        for (int k0 = b; k0 < e; k0 += W) {
+            const int k = k0 + sl;
+            bool ok = false;
+            uint32_t entry = 0;
+            if (k < e) {
                 const int idx = items[k];
                 int oct;
-                if (!candidate_ok(fr, Q, check_levels, idx, oct)) continue;
-                const uint32_t* kd = D + (size_t)idx * 8;
-                int dist = 0;
-#pragma unroll
-                for (int w = 0; w < 8; ++w) dist += __popc(qd[w] ^ kd[w]);
-                out[w_++] = (uint32_t)idx | ((uint32_t)dist << 12) | ((uint32_t)oct << 21);
+                ok = candidate_ok(fr, Q, idx, oct);
+                if (ok) {
+                    const uint4 d0 = D[2 * (size_t)idx], d1 = D[2 * (size_t)idx + 1];
+                    const int dist = __popc(qd0.x ^ d0.x) + __popc(qd0.y ^ d0.y) + __popc(qd0.z ^ d0.z) + __popc(qd0.w ^ d0.w) +
+                                     __popc(qd1.x ^ d1.x) + __popc(qd1.y ^ d1.y) + __popc(qd1.z ^ d1.z) + __popc(qd1.w ^ d1.w);
+                    entry = (uint32_t)idx | ((uint32_t)dist << 12) | ((uint32_t)oct << 21);
+                }
+            }
+            const uint32_t m = sub_ballot<W>(ok);
+            if (ok) {
+                const int at = cnt + __popc(m & ((1u << sl) - 1u));
+                if (kStage == 0 || at < kStage) out[at] = entry;
+            }
+            cnt += __popc(m);
+        }
+        b = nb; e = ne;
+    }
+    return cnt;
+}
+
+// W lanes per query, kCandThreads / W queries per block of queries.  The queries of a pass come frame by frame, and the hardware deals
+// consecutive workgroups to the eight XCDs in turn, each with its own L2: XCD k takes the k-th contiguous eighth of the query blocks (as
+// k_fast_cells does with its cells), so a frame's keys, descriptors, u_right, occupied and grid are fetched into ONE L2, not into eight.
+// A workgroup takes `run` consecutive blocks of its XCD's share.  Every candidate is tested once: the walk keeps the entries in LDS, one
+// atomic per wavefront reserves the pool space of its queries, and the stage is copied out; only a list longer than the stage is walked a
+// second time.
+template <int W>
+__global__ __launch_bounds__(kCandThreads) void k_match_candidates(const MatchFrameDev* __restrict__ frames, int nframes,
+                                                                   const int32_t* __restrict__ query_frame, int total_q, MatchLists L, int run) {
+    static_assert(W >= 2 && W <= 32 && (W & (W - 1)) == 0, "a sub-group lies inside half a wavefront");
+    constexpr int kSub = kCandThreads / W, kCandStage = cand_stage(W);
+    __shared__ uint4 s_query[kSub][4];
+    __shared__ uint32_t s_stage[kSub][kCandStage];
+    const int tid = threadIdx.x, sub = tid / W, sl = tid % W, lane = tid & 63, lead = lane / W * W;
+    const int nblk = (total_q + kSub - 1) / kSub, per_xcd = (nblk + 7) / 8;
+    for (int rep = 0; rep < run; ++rep) {
+        const int in_xcd = ((int)blockIdx.x >> 3) * run + rep;
+        const int logical = ((int)blockIdx.x & 7) * per_xcd + in_xcd;
+        if (in_xcd >= per_xcd || logical >= nblk) break;  // whole workgroup
+        const int g = logical * kSub + sub;
+        const int f = g < total_q ? query_frame[g] : -1;
+        MatchFrameDev fr{};
+        QueryWindow Q{};
+        uint4 qd0 = make_uint4(0, 0, 0, 0), qd1 = qd0;
+        const int32_t* cs = nullptr;
+        const uint16_t* items = nullptr;
+        int minCX = 0, maxCX = -1, minCY = 0, maxCY = -1, cnt = 0, flags = 0;
+        if (f >= 0) {
+            fr = global_record(frames[f]);
+            // the query's record once per sub-group, in 16-byte pieces through LDS
+            for (int i = sl; i < 4; i += W) s_query[sub][i] = reinterpret_cast<const uint4*>(fr.queries + (g - fr.query_off))[i];
+            wave_lds_sync();
+            const uint4 q0 = s_query[sub][0], q1 = s_query[sub][1];
+            qd0 = s_query[sub][2]; qd1 = s_query[sub][3];
+            Q.u = __uint_as_float(q0.x); Q.v = __uint_as_float(q0.y); Q.r = __uint_as_float(q0.z); Q.u_right = __uint_as_float(q0.w);
+            Q.min_level = (int)q1.x; Q.max_level = (int)q1.y;
+            Q.check_levels = (Q.min_level > 0) || (Q.max_level >= 0);
+            const bool valid = (q1.w & 0xffffu) != 0, has_observations = (q1.w >> 16) != 0;  // MatchQuery: int16_t valid, has_observations
+            flags = has_observations ? (1 << 30) : 0;
+            if (valid && fr.n_keys > 0) {
+                const float invW = (float)kGridCols / (fr.max_x - fr.min_x), invH = (float)kGridRows / (fr.max_y - fr.min_y);
+                const float r = Q.r;
+                minCX = max(0, (int)floorf((Q.u - fr.min_x - r) * invW));
+                maxCX = min(kGridCols - 1, (int)ceilf((Q.u - fr.min_x + r) * invW));
+                minCY = max(0, (int)floorf((Q.v - fr.min_y - r) * invH));
+                maxCY = min(kGridRows - 1, (int)ceilf((Q.v - fr.min_y + r) * invH));
+                const bool any = !(minCX >= kGridCols || maxCX < 0 || minCY >= kGridRows || maxCY < 0);
+                if (any) {
+                    cs = L.cell_start + (size_t)(L.cell_row ? L.cell_row[f] : f) * (kCells + 1);
+                    items = L.items + L.key_base[f];
+                    cnt = walk_window<W, kCandStage>(fr, Q, qd0, qd1, cs, items, minCX, maxCX, minCY, maxCY, sl, s_stage[sub]);
+                }
             }
         }
+        wave_lds_sync();
+        // ---- pool space: one atomic per wavefront (every lane of the wavefront is here) ----
+        const int mine = sl == 0 ? cnt : 0;
+        int incl = mine;
+        for (int o = W; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+        const int total = __shfl(incl, 64 - W, 64);
+        int base = 0;
+        if (lane == 0 && total > 0) base = atomicAdd(L.pool_top, total);
+        base = __shfl(base, 0, 64);
+        int off = __shfl(base + incl - mine, lead, 64);
+        // a list the pool cannot hold is dropped whole and reported: projection_search then runs the one-kernel form
+        if (cnt > 0 && off + cnt > L.pool_cap) { if (sl == 0) L.pool_top[1] = 1; cnt = 0; }
+        if (cnt == 0) off = 0;
+        if (sl == 0 && g < total_q) { L.cand_off[g] = off; L.cand_cnt[g] = cnt | flags; }
+        if (cnt > 0) {
+            uint32_t* out = L.pool + off;
+            if (cnt <= kCandStage) for (int i = sl; i < cnt; i += W) out[i] = s_stage[sub][i];
+            else walk_window<W, 0>(fr, Q, qd0, qd1, cs, items, minCX, maxCX, minCY, maxCY, sl, out);
+        }
+        wave_lds_sync();  // the next block of queries rewrites the sub-group's LDS
+    }
 }
 
 __global__ __launch_bounds__(kThreads) void k_match_resolve(const MatchFrameDev* __restrict__ frames, int mode, float nn_ratio, int max_dist, MatchLists L,
@@ -355,12 +448,37 @@ void launch_match_grid(const MatchFrameDev* frames, int nframes, const MatchList
     if (nframes > 0) TC2LI_LAUNCH(k_match_grid, dim3(nframes), dim3(kThreads), 0, st, frames, L);
 }
 
+template <int W>
+static void launch_match_candidates_w(const MatchFrameDev* frames, int nframes, const int32_t* query_frame, int total_q, const MatchLists& L,
+                                      hipStream_t st) {
+    constexpr int kSub = kCandThreads / W;
+    const int nblk = (total_q + kSub - 1) / kSub, per_xcd = (nblk + 7) / 8;
+    // a workgroup covers up to W blocks of 256 / W queries, fewer when that would leave an XCD's 32 CUs short of two workgroups each
+    const int run = std::min(W, std::max(1, per_xcd / 64));
+    TC2LI_LAUNCH(k_match_candidates<W>, dim3(((per_xcd + run - 1) / run) * 8), dim3(kCandThreads), 0, st, frames, nframes, query_frame, total_q, L, run);
+}
+
+static void launch_match_candidates(const MatchFrameDev* frames, int nframes, const int32_t* query_frame, int total_q, const MatchLists& L,
+                                    hipStream_t st) {
+    if (total_q <= 0) return;
+    // Lanes per query, read per call: 2 (default), 4, 8, 16 or 32.  The loop's windows hold a handful of keys, so wide sub-groups are mostly
+    // idle lanes and the kernel's time follows its wavefront count (in the loop, per launch of 512 frames: 0.62 ms with 2 lanes, 0.84 with
+    // 4, 1.17 with 8, 1.79 with 16, 2.42 with 32; one lane per query that walks twice, the form before: 0.96 - 1.10 ms).
+    const char* lanes_env = getenv("TC2LI_MATCH_LANES");
+    const int lanes = lanes_env ? atoi(lanes_env) : 2;
+    if (lanes == 4) launch_match_candidates_w<4>(frames, nframes, query_frame, total_q, L, st);
+    else if (lanes == 8) launch_match_candidates_w<8>(frames, nframes, query_frame, total_q, L, st);
+    else if (lanes == 16) launch_match_candidates_w<16>(frames, nframes, query_frame, total_q, L, st);
+    else if (lanes == 32) launch_match_candidates_w<32>(frames, nframes, query_frame, total_q, L, st);
+    else launch_match_candidates_w<2>(frames, nframes, query_frame, total_q, L, st);
+}
+
 void launch_match_lists(const MatchFrameDev* frames, int nframes, const int32_t* query_frame, int total_q, const MatchLists& L, int mode,
                         float nn_ratio, int32_t* match_of_query, int32_t* prev_claim, int32_t* rounds_out, hipStream_t st, int max_dist) {
     if (nframes <= 0) return;
     (void)hipMemsetAsync(L.pool_top, 0, 2 * sizeof(int32_t), st);
-    TC2LI_LAUNCH(k_match_grid, dim3(nframes), dim3(kThreads), 0, st, frames, L);
-    TC2LI_LAUNCH(k_match_candidates, dim3((total_q + 255) / 256), dim3(256), 0, st, frames, nframes, query_frame, total_q, L);
+    if (!L.grid_ready) TC2LI_LAUNCH(k_match_grid, dim3(nframes), dim3(kThreads), 0, st, frames, L);
+    launch_match_candidates(frames, nframes, query_frame, total_q, L, st);
     TC2LI_LAUNCH(k_match_resolve, dim3(nframes), dim3(kThreads), 0, st, frames, mode, nn_ratio, max_dist, L, match_of_query, prev_claim, rounds_out);
 }
 

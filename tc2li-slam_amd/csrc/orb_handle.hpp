@@ -1,5 +1,6 @@
 // The extractor handle behind tc2li_orb_* (shared by the ORB and stereo translation units).
 #pragma once
+#include <mutex>
 #include <vector>
 
 #include "common.hpp"
@@ -67,6 +68,18 @@ struct tc2li_orb {
     std::vector<int> last_kp_off, last_kp_cnt;  // [nimg] first slot and number of each image's keypoints in d_mkeys / d_desc
     bool last_plain_order = false;  // true when the device order equals the output order
     tc2li::ScaleTable scale_tab{};
+    // The feature grids (k_match_grid, bounds 0, cur_w, 0, cur_h) of the left images of the last extraction, frame f = image 2 f.  Every
+    // projection search on these features walks the same grid -- as Frame's constructor builds mGrid once -- so the first search after an
+    // extraction builds the grids of all frames on its stream (frame_grids, projection_search.cpp) and every extraction drops them.
+    tc2li::DevBuf<int32_t> d_grid_cells;   // [frames][kCellsPlus1]
+    tc2li::DevBuf<uint16_t> d_grid_items;  // beside d_mkeys: the items of frame f start at last_kp_off[2 f]
+    tc2li::DevBuf<uint8_t> d_grid_tab;     // the build's frame records and item bases
+    tc2li::PinnedBuf<uint8_t> h_grid_tab;
+    std::mutex grid_mutex;                 // guards the fields below and the build
+    bool grid_valid = false;
+    hipStream_t grid_stream = nullptr;     // the stream of the build; a search on another stream waits for grid_event
+    hipEvent_t grid_event = nullptr;
+    int grid_builds = 0;                   // tc2li_orb_match_grid_builds
 
     hipStream_t side_stream = nullptr;
     hipStream_t chunk_stream = nullptr;  // the odd chunks of a chunked batch call (round 4): their kernels overlap the even chunks' bus-bound tails
@@ -87,6 +100,7 @@ struct tc2li_orb {
         if (side_stream) (void)hipStreamDestroy(side_stream);
         if (chunk_stream) (void)hipStreamDestroy(chunk_stream);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (grid_event) (void)hipEventDestroy(grid_event);
     }
 };
 

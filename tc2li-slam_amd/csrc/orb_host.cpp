@@ -330,6 +330,12 @@ int tc2li_orb_scale_factors(const tc2li_orb* o, float* s, float* is, float* s2, 
 
 int tc2li_orb_last_chunks(const tc2li_orb* o) { return o ? o->last_chunks : TC2LI_ERR_INVALID; }
 
+int tc2li_orb_match_grid_builds(tc2li_orb* o) {
+    if (!o) { set_error("tc2li_orb_match_grid_builds: invalid argument"); return TC2LI_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(o->grid_mutex);
+    return o->grid_builds;
+}
+
 int tc2li_orb_features_per_level(const tc2li_orb* o, int32_t* per_level) {
     if (!o || !per_level) return TC2LI_ERR_INVALID;
     memcpy(per_level, o->features_per_level.data(), o->features_per_level.size() * sizeof(int32_t));
@@ -377,6 +383,7 @@ int tc2li_orb_extract_batch(tc2li_orb* o, const uint8_t* dev_images, int n_image
         blur.lv[l] = LevelDesc{o->d_blur[l].p, g.img_stride, g.pitch, g.w, g.h, 0};
     }
     o->last_nimg = M;
+    { std::lock_guard<std::mutex> lk(o->grid_mutex); o->grid_valid = false; }  // the feature grids belong to the features this call replaces
 
     // The whole call is queued at once (pyramid, FAST, compaction, keypoint distribution, then orientation + descriptors once the blur
     // -- on the side stream -- is done) and the host waits once, at the end.  TC2LI_ORB_CHUNKS > 1 queues the images in that many

@@ -38,8 +38,45 @@ int resolve_ambiguous_levels(SearchScratch& s, const TrackConst& C, PatchLaunche
     return TC2LI_OK;
 }
 
+int frame_grids(tc2li_orb* o, hipStream_t st, FrameGrids* out) {
+    *out = FrameGrids{};
+    const char* cache = getenv("TC2LI_MATCH_GRID_CACHE");  // read per call: 0 = every search builds its own grids (the A/B runs, a test)
+    if (cache && atoi(cache) == 0) return TC2LI_OK;
+    const int nf = o->last_nimg / 2;
+    if (nf <= 0) return TC2LI_OK;
+    std::lock_guard<std::mutex> lk(o->grid_mutex);
+    if (!o->grid_valid) {
+        const size_t o_base = up256(sizeof(MatchFrameDev) * (size_t)nf), bytes = up256(o_base + 4 * (size_t)nf);
+        TC2LI_HIP_CHECK(o->d_grid_cells.ensure((size_t)nf * kCellsPlus1)); TC2LI_HIP_CHECK(o->d_grid_items.ensure(o->d_mkeys.n));
+        TC2LI_HIP_CHECK(o->d_grid_tab.ensure(bytes)); TC2LI_HIP_CHECK(o->h_grid_tab.ensure(bytes));
+        if (!o->grid_event) TC2LI_HIP_CHECK(hipEventCreateWithFlags(&o->grid_event, hipEventDisableTiming));
+        MatchFrameDev* hm = reinterpret_cast<MatchFrameDev*>(o->h_grid_tab.p);
+        int32_t* hb = reinterpret_cast<int32_t*>(o->h_grid_tab.p + o_base);
+        for (int f = 0; f < nf; ++f) {
+            const int off = o->last_kp_off[2 * f], n = o->last_kp_cnt[2 * f];
+            // a frame with more keys than the matcher takes is refused by every search (check_match_keys): its grid stays empty
+            hm[f] = MatchFrameDev{o->d_mkeys.p + off, nullptr, nullptr, nullptr, nullptr, n <= kMaxMatchKeys ? n : 0, 0, 0, 0,
+                                  0.0f, (float)o->cur_w, 0.0f, (float)o->cur_h};
+            hb[f] = off;
+        }
+        TC2LI_HIP_CHECK(hipMemcpyAsync(o->d_grid_tab.p, o->h_grid_tab.p, bytes, hipMemcpyHostToDevice, st));
+        MatchLists L{};
+        L.cell_start = o->d_grid_cells.p; L.items = o->d_grid_items.p; L.key_base = reinterpret_cast<const int32_t*>(o->d_grid_tab.p + o_base);
+        launch_match_grid(reinterpret_cast<const MatchFrameDev*>(o->d_grid_tab.p), nf, L, st);
+        TC2LI_HIP_CHECK(hipGetLastError());
+        TC2LI_HIP_CHECK(hipEventRecord(o->grid_event, st));
+        o->grid_valid = true; o->grid_stream = st; ++o->grid_builds;
+    } else if (st != o->grid_stream) {
+        TC2LI_HIP_CHECK(hipStreamWaitEvent(st, o->grid_event, 0));
+    }
+    out->cell_start = o->d_grid_cells.p; out->items = o->d_grid_items.p;
+    return TC2LI_OK;
+}
+
 int projection_search(SearchScratch& s, const SearchPass& P, hipStream_t st, const std::function<int()>& behind) {
-    const MatchLists L{s.d_cell_start.p, s.d_items.p, P.d_key_base, s.d_cand_off.p, s.d_cand_cnt.p, s.d_pool.p, s.pool_top(), s.pool_cap, 0, nullptr};
+    const bool cached = P.grid_cells != nullptr;
+    const MatchLists L{cached ? P.grid_cells : s.d_cell_start.p, cached ? P.grid_items : s.d_items.p, P.d_key_base, s.d_cand_off.p, s.d_cand_cnt.p,
+                       s.d_pool.p, s.pool_top(), s.pool_cap, cached ? 1 : 0, cached ? P.d_cell_row : nullptr};
     launch_match_lists(P.d_mframes, P.n_pass, s.d_query_frame.p, P.total_q, L, P.mode, P.nn_ratio, s.d_match.p, s.d_prev.p, s.d_rounds.p, st, P.orb_dist);
     TC2LI_HIP_CHECK(hipGetLastError());
     TC2LI_HIP_CHECK(hipMemcpyAsync(s.h_small.p, s.pool_top(), 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));

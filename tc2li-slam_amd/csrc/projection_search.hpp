@@ -115,7 +115,21 @@ struct SearchPass {
     int mode;
     float nn_ratio;
     int orb_dist;
+    // frame_grids of the handle the pass searches, or NULL: the search builds the grids of its frames itself.  With them d_key_base[k] is
+    // where frame k's items start in grid_items and d_cell_row[k] its row of grid_cells (the frame's index in the handle's extraction).
+    int32_t* grid_cells = nullptr;
+    uint16_t* grid_items = nullptr;
+    const int32_t* d_cell_row = nullptr;
 };
+
+// The feature grids of the handle's last extraction for a search on stream st: built on st by the first call after the extraction, later
+// calls on other streams wait for that build.  Row f of cell_start is frame f (image 2 f), its items start at last_kp_off[2 f].
+// TC2LI_MATCH_GRID_CACHE=0 (read per call): cell_start comes back NULL and the search builds its own grids, as before.
+struct FrameGrids {
+    int32_t* cell_start = nullptr;
+    uint16_t* items = nullptr;
+};
+int frame_grids(tc2li_orb* o, hipStream_t st, FrameGrids* out);
 // The search of one pass into s.d_match: queues the list form, then `behind` (what the caller wants queued before the single wait; may be
 // empty), waits, and when the candidate pool overflowed resets the pass's matches and queues the one-kernel form -- same result -- and
 // `behind` again with a second wait.  Without `behind` the fall-back is left queued: the caller's follow-up kernels go behind it.

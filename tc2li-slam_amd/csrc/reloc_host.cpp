@@ -596,6 +596,8 @@ extern "C" int tc2li_relocalization_refine_batch(tc2li_orb* o, const tc2li_reloc
     SearchScratch& S = w.s;
     const size_t nh = n_hyps, cap1 = std::max(capacity, 1), q1 = std::max<size_t>(nq, 1), ne = nh * cap1, nfr = std::max(n_frames, 1);
     const int total_q = (int)nq;
+    FrameGrids G;  // the handle's grids: hypothesis k reads the row of its frame (frame_of_hyp), the items start where the frame's keys start
+    if (int rc = frame_grids(o, st, &G)) return rc;
     const KeyframePointStage pts(0, q1);
     const size_t o_match = pts.end, o_inl = up256(o_match + 4 * ne), o_ur = up256(o_inl + ne), o_neg = up256(o_ur + 4 * nfr * cap1),
                  o_frames = up256(o_neg + 4 * cap1), o_bounds = up256(o_frames + sizeof(TrackFrameDev) * nh), o_mframes = up256(o_bounds + 16 * nh),
@@ -633,7 +635,7 @@ extern "C" int tc2li_relocalization_refine_batch(tc2li_orb* o, const tc2li_reloc
         memcpy(h + o_bounds + 16 * (size_t)k, B, 16);
         hm[k] = MatchFrameDev{o->d_mkeys.p + key_off, o->d_desc.p + (size_t)key_off * 32, reinterpret_cast<const float*>(d + o_neg), d_occ + (size_t)k * cap1,
                               S.d_queries.p + q, n, Hy.n_points, (int32_t)q, 0, B[0], B[1], B[2], B[3]};
-        reinterpret_cast<int32_t*>(h + o_kbase)[k] = (int32_t)(k * cap1);
+        reinterpret_cast<int32_t*>(h + o_kbase)[k] = G.cell_start ? key_off : (int32_t)(k * cap1);
         reinterpret_cast<int32_t*>(h + o_foh)[k] = Hy.frame_index;
         q += Hy.n_points;
     }
@@ -663,7 +665,7 @@ extern "C" int tc2li_relocalization_refine_batch(tc2li_orb* o, const tc2li_reloc
                                       S.d_match.p, S.amb_count(), S.d_amb_ids.p, S.d_amb_ratio.p, S.d_amb_r.p, st);
         if (int rc = resolve_ambiguous_levels(S, C, launch_track_patch_levels_keyframe, st)) return rc;
         const SearchPass P{reinterpret_cast<const MatchFrameDev*>(d + o_mframes), reinterpret_cast<const int32_t*>(d + o_kbase), n_hyps, total_q, hf, nullptr,
-                           0, 0.0f, orb_dist};
+                           0, 0.0f, orb_dist, G.cell_start, G.items, G.cell_start ? L.frame_of_hyp : nullptr};
         if (int rc = projection_search(S, P, st)) return rc;  // the follow-up waits for the overflow decision: assign scatters
         launch_track_count(w.d_frames.p, nullptr, n_hyps, S.d_queries.p, o->d_angles.p, 1, S.d_match.p, d_nm, st);
         launch_track_assign_keyframe(w.d_frames.p, n_hyps, (int)cap1, total_q, S.d_match.p, d_assign, st);

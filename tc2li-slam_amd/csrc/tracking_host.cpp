@@ -64,18 +64,21 @@ struct Pass {
     // frames of the pass are in w.h_pass[0 .. n_pass); their TrackFrameDev (slot set) are on the device already.  Returns with the
     // stream drained and w.h_nmatch holding every frame's count (the pass rewrote its own): the count rides behind the list form.
     int search(int n_pass) {
+        FrameGrids G;  // the handle's grids: frame k of the pass reads row h_pass[k], its items start where its keys start
+        if (int rc = frame_grids(o, st, &G)) return rc;
         for (int k = 0; k < n_pass; ++k) {
             const int f = w.h_pass.p[k];
             const TrackFrameDev& F = w.h_frames.p[f];
             w.h_mframes.p[k] = MatchFrameDev{o->d_mkeys.p + F.key_off, o->d_desc.p + (size_t)F.key_off * 32, d_ur + (size_t)f * capacity,
                                              d_occ ? d_occ + (size_t)f * capacity : nullptr, w.s.d_queries.p + F.q_off, F.n_keys, F.n_q, F.q_off, 0,
                                              0.0f, (float)o->cur_w, 0.0f, (float)o->cur_h};
-            w.h_key_base.p[k] = f * capacity;
+            w.h_key_base.p[k] = G.cell_start ? F.key_off : f * capacity;
         }
         TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_mframes.p, w.h_mframes.p, n_pass * sizeof(MatchFrameDev), hipMemcpyHostToDevice, st));
         TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_key_base.p, w.h_key_base.p, n_pass * sizeof(int32_t), hipMemcpyHostToDevice, st));
         TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_pass.p, w.h_pass.p, n_pass * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        const SearchPass P{w.d_mframes.p, w.d_key_base.p, n_pass, total_q, w.h_frames.p, w.h_pass.p, mode, nn_ratio, kMatchThHigh};
+        const SearchPass P{w.d_mframes.p, w.d_key_base.p, n_pass, total_q, w.h_frames.p, w.h_pass.p, mode, nn_ratio, kMatchThHigh,
+                           G.cell_start, G.items, G.cell_start ? w.d_pass.p : nullptr};
         return projection_search(w.s, P, st, [&]() -> int {
             launch_track_count(w.d_frames.p, w.d_pass.p, n_pass, w.s.d_queries.p, o->d_angles.p, check_orientation ? 1 : 0, w.s.d_match.p, w.s.d_nmatch.p, st);
             TC2LI_HIP_CHECK(hipGetLastError());
