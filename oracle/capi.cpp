@@ -1180,9 +1180,14 @@ int oracle_local_inertial_ba(double* kf33, const uint8_t* fixed, const uint8_t* 
 // prior246: ConstraintPoseImu of the previous frame = Rwb 9, twb 3, vwb 3, bg 3, ba 3, H 225 (NULL for the keyframe form);
 // edges6[e] = (index into Xw, unused, u, v, uR, invSigma2); prior_out246: the frame's new mpcpi; stats3: n_initial, n_bad, n_inliers.
 // Returns nInitialCorrespondences - nBad.
-int oracle_pose_inertial(double* cur33, double* other33, int last_frame, const double* prior246, const double* calib24, const float* pre298,
-                         const float* pre_rw298, const double* Xw, const double* edges6, int n_edges, const uint8_t* close, const double* cam5,
-                         int rec_init, uint8_t* outlier, double* prior_out246, int* stats3) {
+// oracle_pose_inertial_details: the same run, and what the directed tests need to know of it (any pointer may be NULL): solver_failed;
+// rounds4: Gauss-Newton iterations per round, -1 for a round not entered; pivots [40][4]: per factorisation the deciding pivot, the
+// largest term it was formed from, the smallest |pivot| / largest term up to it and the pivot's unknown (PoseInertialResult), n_fact
+// of them; prior_chi2 [40]: EdgePriorPoseImu's chi2 per iteration (previous-frame form, else untouched); chi2 [n_edges]: the chi2 each edge's last test read.
+int oracle_pose_inertial_details(double* cur33, double* other33, int last_frame, const double* prior246, const double* calib24, const float* pre298,
+                                 const float* pre_rw298, const double* Xw, const double* edges6, int n_edges, const uint8_t* close, const double* cam5,
+                                 int rec_init, uint8_t* outlier, double* prior_out246, int* stats3, int* solver_failed, int* rounds4, double* pivots,
+                                 int* n_fact, double* prior_chi2, double* chi2) {
     InertialKeyFrame cur = kf_from(cur33, 0, 1), other = kf_from(other33, last_frame ? 0 : 1, 1);
     PoseImuPrior prior;
     if (prior246) {
@@ -1204,7 +1209,22 @@ int oracle_pose_inertial(double* cur33, double* other33, int last_frame, const d
         std::memcpy(prior_out246 + 15, r.prior.bg, 24); std::memcpy(prior_out246 + 18, r.prior.ba, 24); std::memcpy(prior_out246 + 21, r.prior.H, 225 * sizeof(double));
     }
     if (stats3) { stats3[0] = r.n_initial; stats3[1] = r.n_bad; stats3[2] = r.n_inliers; }
+    if (solver_failed) *solver_failed = r.solver_failed ? 1 : 0;
+    if (rounds4) for (int k = 0; k < 4; ++k) rounds4[k] = r.round_iterations[k];
+    if (n_fact) *n_fact = (int)r.pivot.size();
+    if (pivots)
+        for (size_t k = 0; k < r.pivot.size() && k < 40; ++k) {
+            pivots[4 * k] = r.pivot[k]; pivots[4 * k + 1] = r.pivot_scale[k]; pivots[4 * k + 2] = r.pivot_clearance[k]; pivots[4 * k + 3] = r.pivot_index[k];
+        }
+    if (prior_chi2) for (size_t k = 0; k < r.prior_chi2.size() && k < 40; ++k) prior_chi2[k] = r.prior_chi2[k];
+    if (chi2) for (int e = 0; e < n_edges; ++e) chi2[e] = r.chi2[e];
     return r.n_initial - r.n_bad;
+}
+int oracle_pose_inertial(double* cur33, double* other33, int last_frame, const double* prior246, const double* calib24, const float* pre298,
+                         const float* pre_rw298, const double* Xw, const double* edges6, int n_edges, const uint8_t* close, const double* cam5,
+                         int rec_init, uint8_t* outlier, double* prior_out246, int* stats3) {
+    return oracle_pose_inertial_details(cur33, other33, last_frame, prior246, calib24, pre298, pre_rw298, Xw, edges6, n_edges, close, cam5, rec_init, outlier,
+                                        prior_out246, stats3, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 // Optimizer::InertialOptimization (IMU initialisation): kf33 rows in temporal order (Rwb, twb, v read; v written), pre298[i] = row i's
 // pre-integration from row i - 1 (row 0 unused); state17 = Rwg 9 | scale | bg 3 | ba 3 | (pad).  Returns the iterations.

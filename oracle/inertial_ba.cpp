@@ -592,6 +592,30 @@ void constraint_clamp(double H[225]) {
     for (double& x : w) if (x < 1e-12) x = 0;
     for (int r = 0; r < 15; ++r) for (int c = 0; c < 15; ++c) { double s = 0; for (int k = 0; k < 15; ++k) s += V[15 * r + k] * w[k] * V[15 * c + k]; H[15 * r + c] = s; }
 }
+// The pivots of ldlt() once more, with the sizes of what they are made of: a report for the tests, read by nobody else.
+void pivot_report(std::vector<double> H, int n, double& pivot, double& scale, double& clearance, int& index) {
+    std::vector<double> D(n);
+    pivot = scale = clearance = std::numeric_limits<double>::infinity();
+    index = -1;
+    for (int j = 0; j < n; ++j) {
+        double d = H[(size_t)j * n + j], big = std::fabs(d);
+        for (int k = 0; k < j; ++k) {
+            const double t = H[(size_t)j * n + k] * H[(size_t)j * n + k] * D[k];
+            d -= t;
+            big = std::max(big, std::fabs(t));
+        }
+        const bool positive = std::isfinite(d) && d > 0.0;
+        if (!positive || d < pivot) { pivot = d; scale = big; index = j; }
+        clearance = std::min(clearance, std::fabs(d) / big);
+        if (!positive) return;
+        D[j] = d;
+        for (int i = j + 1; i < n; ++i) {
+            double s = H[(size_t)i * n + j];
+            for (int k = 0; k < j; ++k) s -= H[(size_t)i * n + k] * H[(size_t)j * n + k] * D[k];
+            H[(size_t)i * n + j] = s / d;
+        }
+    }
+}
 }  // namespace
 
 PoseInertialResult PoseInertialOptimization(InertialKeyFrame& cur, InertialKeyFrame& other, bool last_frame, const PoseImuPrior* prior_prev,
@@ -644,7 +668,9 @@ PoseInertialResult PoseInertialOptimization(InertialKeyFrame& cur, InertialKeyFr
     int nBad = 0, nInliers = 0;
     for (int round = 0; round < 4; ++round) {
         bool ok = true;
+        res.round_iterations[round] = 0;
         for (int it = 0; it < 10 && ok; ++it) {
+            ++res.round_iterations[round];
             std::fill(H.begin(), H.end(), 0.0);
             std::fill(b.begin(), b.end(), 0.0);
             // visual edges of level 0 -> pose block of the frame
@@ -718,6 +744,7 @@ PoseInertialResult PoseInertialOptimization(InertialKeyFrame& cur, InertialKeyFr
                 for (int r = 0; r < 15; ++r) { double s = 0; for (int k = 0; k < 15; ++k) s += prior_prev->H[15 * r + k] * e15[k]; Oe[r] = s; c += e15[r] * s; }
                 double r0, r1;
                 hub_prior.rho(c, r0, r1);
+                res.prior_chi2.push_back(c);
                 for (int i = 0; i < 15; ++i) {
                     double g = 0;
                     for (int r = 0; r < 15; ++r) g += J[15 * r + i] * Oe[r];
@@ -732,6 +759,12 @@ PoseInertialResult PoseInertialOptimization(InertialKeyFrame& cur, InertialKeyFr
             // LinearSolverDense: LDLT, usable only when no pivot is negative (Eigen::LDLT::isPositive)
             std::vector<double> Hw = H;
             std::vector<double> xn(n);
+            {
+                double piv, scale, clearance;
+                int index;
+                pivot_report(H, n, piv, scale, clearance, index);
+                res.pivot.push_back(piv); res.pivot_scale.push_back(scale); res.pivot_clearance.push_back(clearance); res.pivot_index.push_back(index);
+            }
             bool pos = ldlt(Hw, n, b.data(), xn.data());
             if (pos) {  // the sign of D: recompute the pivots (ldlt() leaves the unit lower factor in Hw, D is not kept)
                 std::vector<double> D(n);
@@ -791,6 +824,7 @@ PoseInertialResult PoseInertialOptimization(InertialKeyFrame& cur, InertialKeyFr
     }
     res.n_bad = nBad;
     res.n_inliers = nInliers;
+    res.chi2 = chi2;
     // ---- the new prior: Hessian at the final estimate (GetHessian* call linearizeOplus(), no robust weights) ----
     double e9[9], J[9 * 24];
     inertial_edge(other, cur, pint, e9, J);

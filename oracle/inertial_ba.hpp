@@ -70,6 +70,15 @@ struct PoseInertialResult {
     std::vector<uint8_t> outlier;                   // mvbOutlier per edge
     PoseImuPrior prior;                             // pFrame->mpcpi
     bool solver_failed = false;
+    // What the directed tests must know of the run (tests/pose_inertial_cases.py); none of it feeds back into the optimisation.
+    int round_iterations[4] = {-1, -1, -1, -1};     // Gauss-Newton iterations of each round, -1: round not entered
+    // Per factorisation, in order: the deciding pivot of the LDL^T -- the smallest one when all are positive, else the first that is
+    // not -- and the largest magnitude among the terms it is the sum of (H_jj and the (L_jk L_jk) D_k); pivot_clearance is the smallest
+    // |D_j| / (largest term of D_j) over the pivots up to and including the deciding one.
+    std::vector<double> pivot, pivot_scale, pivot_clearance;
+    std::vector<int> pivot_index;                   // which unknown the deciding pivot belongs to
+    std::vector<double> prior_chi2;                 // per iteration (previous-frame form): chi2 of EdgePriorPoseImu, what its Huber weight sees
+    std::vector<double> chi2;                       // per edge: the chi2 the last test of the edge read (classification or recovery)
 };
 // cur: the frame (updated in place); other: the last keyframe (fixed) or, when last_frame, the previous frame (free, updated too).
 // pint: the pre-integration of EdgeInertial (mpImuPreintegrated / mpImuPreintegratedFrame); pint_rw: the one whose bias-walk covariance

@@ -890,21 +890,38 @@ def pack_preintegrated(fields, bias6):
     return np.concatenate(out)
 
 
-def pose_inertial(cur33, other33, last_frame, prior246, calib24, pre298, pre_rw298, Xw, edges6, close, cam5, rec_init=False):
+def pose_inertial(cur33, other33, last_frame, prior246, calib24, pre298, pre_rw298, Xw, edges6, close, cam5, rec_init=False, details=False):
     """Optimizer::PoseInertialOptimizationLastKeyFrame (last_frame False) / LastFrame (True)
-    -> (cur33, other33, outlier [E], prior246 of the frame, return value, (n_initial, n_bad, n_inliers))."""
+    -> (cur33, other33, outlier [E], prior246 of the frame, return value, (n_initial, n_bad, n_inliers)).
+    details=True: one more element, a dict of what the run did -- solver_failed; rounds: Gauss-Newton iterations of each of the four
+    rounds (-1: not entered); pivot, pivot_scale, pivot_clearance: per factorisation the deciding pivot (the smallest when all are
+    positive, else the first that is not), the largest term it was formed from, the smallest |pivot| / largest term among the
+    pivots up to it, and the unknown the deciding pivot belongs to (pivot_index); prior_chi2: chi2 of the prior edge per iteration
+    (previous-frame form); chi2: per edge, what its last test read."""
     cur, oth = _f64(cur33).copy(), _f64(other33).copy()
     e6, X = _f64(edges6).reshape(-1, 6), _f64(Xw).reshape(-1, 3)
     cl = np.ascontiguousarray(close, np.uint8)
     pre, prw = np.ascontiguousarray(pre298, np.float32), np.ascontiguousarray(pre_rw298, np.float32)
     pr = _f64(prior246) if prior246 is not None else None
     out, outlier, st = np.zeros(246), np.zeros(len(e6), np.uint8), np.zeros(3, np.int32)
-    f = lib().oracle_pose_inertial
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    rv = f(cur.ctypes.data, oth.ctypes.data, int(last_frame), pr.ctypes.data if pr is not None else None, _f64(calib24).ctypes.data, pre.ctypes.data,
-           prw.ctypes.data, X.ctypes.data, e6.ctypes.data, len(e6), cl.ctypes.data, _f64(cam5).ctypes.data, int(rec_init), outlier.ctypes.data,
-           out.ctypes.data, st.ctypes.data)
-    return cur, oth, outlier, out, rv, tuple(int(v) for v in st)
+    args = (cur.ctypes.data, oth.ctypes.data, int(last_frame), pr.ctypes.data if pr is not None else None, _f64(calib24).ctypes.data, pre.ctypes.data,
+            prw.ctypes.data, X.ctypes.data, e6.ctypes.data, len(e6), cl.ctypes.data, _f64(cam5).ctypes.data, int(rec_init), outlier.ctypes.data,
+            out.ctypes.data, st.ctypes.data)
+    argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    if not details:
+        f = lib().oracle_pose_inertial
+        f.argtypes = argtypes
+        rv = f(*args)
+        return cur, oth, outlier, out, rv, tuple(int(v) for v in st)
+    failed, nf, rounds, piv, pc, chi2 = C.c_int(0), C.c_int(0), np.zeros(4, np.int32), np.zeros((40, 4)), np.zeros(40), np.zeros(max(len(e6), 1))
+    f = lib().oracle_pose_inertial_details
+    f.argtypes = argtypes + [C.c_void_p] * 6
+    rv = f(*args, C.addressof(failed), rounds.ctypes.data, piv.ctypes.data, C.addressof(nf), pc.ctypes.data, chi2.ctypes.data)
+    n = nf.value
+    d = dict(solver_failed=bool(failed.value), rounds=tuple(int(v) for v in rounds), pivot=piv[:n, 0].copy(), pivot_scale=piv[:n, 1].copy(),
+             pivot_clearance=piv[:n, 2].copy(), pivot_index=piv[:n, 3].astype(int), prior_chi2=pc[:n].copy() if last_frame else np.zeros(0),
+             chi2=chi2[:len(e6)].copy())
+    return cur, oth, outlier, out, rv, tuple(int(v) for v in st), d
 
 
 def inertial_optimization(kf33, pre298, Rwg, scale, bg, ba, mono=False, fixed_vel=False, priorG=1e2, priorA=1e6, its=200):

@@ -4,36 +4,9 @@ prior's Hessian within 1e-4 of its scale.  Both sides get the product's pre-inte
 import numpy as np
 import pytest
 
+from pose_inertial_cases import RTOL, check, problem, rel  # shared with the directed tests (test_pose_inertial_gates_gpu.py)
+
 pytestmark = pytest.mark.gpu
-RTOL = 1e-4
-
-
-def problem(pkg, oracle, synthetic, seed, last_frame, **kw):
-    w = synthetic.pose_inertial_problem(seed, last_frame=last_frame, **kw)
-    p = pkg.capi.Preintegrated(w["bias6"], *synthetic.IMU_NOISE)
-    p.preintegrate(w["samples"], w["t1"], w["t2"])
-    w["pre"], w["pre298"] = p, oracle.pack_preintegrated(p.fields(), w["bias6"])
-    w["last_frame"] = last_frame
-    w["packed_edges"] = pkg.pack_ba_edges(w["edges"])
-    return w
-
-
-def rel(a, b):
-    return np.abs(a - b).max() / max(1.0, np.abs(b).max())
-
-
-def check(got, want, n_flag_slack=0):
-    cur, oth, outlier, prior, rv, counts, failed = got
-    wcur, woth, woutlier, wprior, wrv, wcounts = want
-    assert not failed
-    assert np.sum(outlier != woutlier) <= n_flag_slack
-    if n_flag_slack == 0:
-        assert rv == wrv and counts == wcounts
-    assert rel(cur[:24], wcur[:24]) < RTOL and np.allclose(cur[24:], wcur[24:], rtol=RTOL, atol=1e-6)
-    assert rel(oth[:24], woth[:24]) < RTOL and np.allclose(oth[24:], woth[24:], rtol=RTOL, atol=1e-6)
-    H, wH = prior[21:].reshape(15, 15), wprior[21:].reshape(15, 15)
-    assert np.allclose(prior[:21], wprior[:21], rtol=RTOL, atol=1e-6)
-    assert np.abs(H - wH).max() <= 1e-4 * np.abs(wH).max()
 
 
 @pytest.mark.parametrize("last_frame", [False, True])
