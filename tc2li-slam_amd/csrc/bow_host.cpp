@@ -120,52 +120,44 @@ BowVocDev voc_dev(const tc2li_vocabulary* v) {
     return BowVocDev{v->d_rows.p, v->d_nodes.p, v->d_weight.p, v->n_nodes(), v->n_words};
 }
 
-struct BowWs {
-    DevBuf<uint8_t> d_desc;
-    DevBuf<BowFrameDev> d_frames;
-    DevBuf<int32_t> d_i32;
-    DevBuf<double> d_val;
-    // search
-    PinnedBuf<uint8_t> h_stage;
-    DevBuf<uint8_t> d_stage;
-    DevBuf<int32_t> d_match;
-    // TrackReferenceKeyFrame
-    DevBuf<int32_t> d_ref_i32;
-    DevBuf<PoseProblem> d_probs;
-    DevBuf<BaEdge> d_edges;
-    DevBuf<double> d_Xw, d_poses, d_chi2;
-    DevBuf<uint8_t> d_outlier;
-};
-BowWs& bws() { static thread_local BowWs w; return w; }
+// the buffers of the entries below, per host thread
+PackedBuffers& bws() { static thread_local PackedBuffers w; return w; }
 
 bool out_ok(const tc2li_bow_out* o) {
     return o && o->word && o->node && o->n_words && o->bow_word && o->bow_value && o->n_nodes && o->fv_node && o->fv_offset && o->fv_index;
 }
 
-// frames[f] set, descriptors on the device at `desc` (rows src_row ..): queues the descent and the assembly into the work space's arrays (O)
-int queue_transform(tc2li_vocabulary* v, const uint8_t* desc, std::vector<BowFrameDev>& frames, size_t total, int levelsup, BowOutDev& O,
-                    hipStream_t st) {
-    BowWs& w = bws();
-    const int nf = (int)frames.size();
-    const size_t nt = std::max<size_t>(total, 1);
-    TC2LI_HIP_CHECK(w.d_frames.ensure(nf));
-    // int32 arrays: word, node, bow_word, fv_node, fv_index, rank, flags [nt] each; fv_offset [nt + nf]; n_words, n_nodes, n_valid [nf]
-    TC2LI_HIP_CHECK(w.d_i32.ensure(8 * nt + 4 * (size_t)nf));
-    TC2LI_HIP_CHECK(w.d_val.ensure(nt));
-    int32_t* p = w.d_i32.p;
+// The tables of a transform of nf frames over `total` descriptor rows, taken from the caller's transfer: the frame records go up in its
+// block, the rest is device-only.  The int32 arrays are one table, filled in one go: word, node, bow_word, fv_node, fv_index, rank,
+// flags [nt] each; fv_offset [nt + nf]; n_words, n_nodes, n_valid [nf].
+struct BowTransform {
+    int nf;
+    size_t nt;
+    Table<BowFrameDev> frames;
+    Table<int32_t> i32;
+    Table<double> bow_value;
+    BowTransform(PackedTransfer& T, int n_frames, size_t total) : nf(n_frames), nt(std::max<size_t>(total, 1)) {
+        frames = T.io.take<BowFrameDev>(nf); i32 = T.work.take<int32_t>(8 * nt + 4 * (size_t)nf); bow_value = T.work.take<double>(nt);
+    }
+};
+
+// after T.ensure(): the frame records into the block.  After T.upload(), descriptors on the device at `desc` (rows src_row ..): queues the
+// descent and the assembly into the transform's arrays (O)
+int queue_transform(tc2li_vocabulary* v, const PackedTransfer& T, const BowTransform& B, const uint8_t* desc, int levelsup, BowOutDev& O, hipStream_t st) {
+    const size_t nt = B.nt, nf = B.nf;
+    int32_t* p = T.dev_work(B.i32);
     O.word = p; O.node = p + nt; O.bow_word = p + 2 * nt; O.fv_node = p + 3 * nt; O.fv_index = p + 4 * nt;
     O.rank = reinterpret_cast<uint32_t*>(p + 5 * nt); O.flags = p + 6 * nt; O.fv_offset = p + 7 * nt;
     O.n_words = p + 8 * nt + nf; O.n_nodes = O.n_words + nf; O.n_valid = O.n_nodes + nf;
-    O.bow_value = w.d_val.p;
+    O.bow_value = T.dev_work(B.bow_value);
     int max_n = 0;
-    for (const BowFrameDev& F : frames) max_n = std::max(max_n, F.n);
-    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_frames.p, frames.data(), nf * sizeof(BowFrameDev), hipMemcpyHostToDevice, st));
+    for (size_t f = 0; f < nf; ++f) max_n = std::max(max_n, T.host(B.frames)[f].n);
     // entries beyond a frame's counts read back as -1 / 0 on every call
-    TC2LI_HIP_CHECK(hipMemsetAsync(p, 0xff, (8 * nt + 4 * (size_t)nf) * sizeof(int32_t), st));
+    TC2LI_HIP_CHECK(hipMemsetAsync(p, 0xff, (8 * nt + 4 * nf) * sizeof(int32_t), st));
     TC2LI_HIP_CHECK(hipMemsetAsync(O.bow_value, 0, nt * sizeof(double), st));
     const BowVocDev V = voc_dev(v);
-    launch_bow_descend(V, desc, w.d_frames.p, nf, max_n, v->L - levelsup, O, st);
-    launch_bow_assemble(V, v->d_word_weight.p, w.d_frames.p, nf, v->scoring, v->weighting, O, st);
+    launch_bow_descend(V, desc, T.dev(B.frames), B.nf, max_n, v->L - levelsup, O, st);
+    launch_bow_assemble(V, v->d_word_weight.p, T.dev(B.frames), B.nf, v->scoring, v->weighting, O, st);
     TC2LI_HIP_CHECK(hipGetLastError());
     return TC2LI_OK;
 }
@@ -185,13 +177,26 @@ int queue_transform_download(const BowOutDev& O, size_t total, int nf, const tc2
     return TC2LI_OK;
 }
 
-int run_transform(tc2li_vocabulary* v, const uint8_t* desc, std::vector<BowFrameDev>& frames, size_t total, int levelsup,
+// The transform alone.  The descriptors are on the device at dev_desc, or, dev_desc NULL, `total` rows of the caller's at host_desc, which go
+// up to a table of the call.
+int run_transform(tc2li_vocabulary* v, const uint8_t* dev_desc, const uint8_t* host_desc, const std::vector<BowFrameDev>& frames, size_t total, int levelsup,
                   const tc2li_bow_out* out, hipStream_t st) {
+    PackedTransfer T;
+    const BowTransform B(T, (int)frames.size(), total);
+    T.outputs_begin();
+    const Table<OrbDescriptor> t_desc = T.work.take<OrbDescriptor>(dev_desc ? 0 : B.nt);
+    TC2LI_HIP_CHECK(T.ensure(bws()));
+    T.io.put(B.frames, 0, frames.data(), frames.size());
+    TC2LI_HIP_CHECK(T.upload(st));
+    if (!dev_desc) {
+        if (total) TC2LI_HIP_CHECK(hipMemcpyAsync(T.dev_work(t_desc), host_desc, total * sizeof(OrbDescriptor), hipMemcpyHostToDevice, st));
+        dev_desc = T.dev_work(t_desc)->b;
+    }
     BowOutDev O;
-    if (int rc = queue_transform(v, desc, frames, total, levelsup, O, st)) return rc;
-    if (int rc = queue_transform_download(O, total, (int)frames.size(), out, st)) return rc;
+    if (int rc = queue_transform(v, T, B, dev_desc, levelsup, O, st)) return rc;
+    if (int rc = queue_transform_download(O, total, B.nf, out, st)) return rc;
     TC2LI_HIP_CHECK(stream_wait_blocking(st));
-    return (int)frames.size();
+    return B.nf;
 }
 
 // a FeatureVector as tc2li_search_for_triangulation checks it (mapping_host.cpp): offsets from 0, not decreasing, nodes strictly ascending,
@@ -330,10 +335,7 @@ extern "C" int tc2li_vocabulary_transform_batch(tc2li_vocabulary* v, int n_frame
     if (n_frames == 0) return 0;
     if (int rc = ensure_device(v)) return rc;
     hipStream_t st = stream_ ? (hipStream_t)stream_ : private_stream();
-    BowWs& w = bws();
-    TC2LI_HIP_CHECK(w.d_desc.ensure(std::max<size_t>(total, 1) * 32));
-    if (total) TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_desc.p, descriptors, total * 32, hipMemcpyHostToDevice, st));
-    return run_transform(v, w.d_desc.p, frames, total, levelsup, out, st);
+    return run_transform(v, nullptr, descriptors, frames, total, levelsup, out, st);
 }
 
 extern "C" int tc2li_orb_compute_bow_batch(tc2li_orb* o, tc2li_vocabulary* v, int n_frames, int levelsup, int capacity, const tc2li_bow_out* out,
@@ -350,7 +352,7 @@ extern "C" int tc2li_orb_compute_bow_batch(tc2li_orb* o, tc2li_vocabulary* v, in
     }
     if (int rc = ensure_device(v)) return rc;
     hipStream_t st = stream_ ? (hipStream_t)stream_ : private_stream();
-    return run_transform(v, o->d_desc.p, frames, (size_t)n_frames * capacity, levelsup, out, st);
+    return run_transform(v, o->d_desc.p, nullptr, frames, (size_t)n_frames * capacity, levelsup, out, st);
 }
 
 extern "C" int tc2li_search_by_bow_batch(const tc2li_bow_pair* pairs, int n_pairs, int capacity, int32_t* kf_keypoint_of_keypoint, int32_t* n_matches,
@@ -398,22 +400,27 @@ extern "C" int tc2li_search_by_bow_batch(const tc2li_bow_pair* pairs, int n_pair
     }
     if (n_pairs == 0) return 0;
     hipStream_t st = stream_ ? (hipStream_t)stream_ : private_stream();
-    BowWs& w = bws();
-    const size_t nk = std::max<size_t>(n_keys, 1), ni = std::max<size_t>(n_idx, 1);
-    const size_t o_desc = 0, o_ang = up256(o_desc + 32 * nk), o_hp = up256(o_ang + 4 * nk), o_idx = up256(o_hp + nk), o_pairs = up256(o_idx + 4 * ni),
-                 o_tasks = up256(o_pairs + sizeof(BowPairDev) * n_pairs), bytes = up256(o_tasks + sizeof(BowTaskDev) * std::max<size_t>(tasks.size(), 1));
-    TC2LI_HIP_CHECK(w.h_stage.ensure(bytes)); TC2LI_HIP_CHECK(w.d_stage.ensure(bytes));
-    uint8_t* h = w.h_stage.p;
-    float* ang = reinterpret_cast<float*>(h + o_ang);
-    int32_t* fi = reinterpret_cast<int32_t*>(h + o_idx);
+    const size_t nk = std::max<size_t>(n_keys, 1), ni = std::max<size_t>(n_idx, 1), cap1 = std::max(capacity, 1);
+    PackedTransfer T;
+    const auto t_desc = T.io.take<OrbDescriptor>(nk);
+    const auto t_ang = T.io.take<float>(nk);
+    const auto t_hp = T.io.take<uint8_t>(nk);
+    const auto t_idx = T.io.take<int32_t>(ni), t_match = T.work.take<int32_t>((size_t)n_pairs * cap1), t_nm = T.work.take<int32_t>(n_pairs);
+    const auto t_pairs = T.io.take<BowPairDev>(n_pairs);
+    const auto t_tasks = T.io.take<BowTaskDev>(std::max<size_t>(tasks.size(), 1));
+    T.outputs_begin();
+    TC2LI_HIP_CHECK(T.ensure(bws()));
+    float* ang = T.host(t_ang);
+    uint8_t* hp = T.host(t_hp);
+    int32_t* fi = T.host(t_idx);
     size_t row = 0, idx = 0;  // the same running layout as above: per pair the keyframe, then the frame
     for (int p = 0; p < n_pairs; ++p) {
         for (int s = 0; s < 2; ++s) {
             const tc2li_keyframe_view& V = s ? pairs[p].frame : pairs[p].keyframe;
-            if (V.n) memcpy(h + o_desc + 32 * row, V.descriptors, (size_t)V.n * 32);
+            T.io.put(t_desc, row, V.descriptors, V.n);
             for (int i = 0; i < V.n; ++i) {
                 ang[row + i] = V.keys[i].angle;
-                h[o_hp + row + i] = (s == 0 && V.has_point[i]) ? 1 : 0;
+                hp[row + i] = (s == 0 && V.has_point[i]) ? 1 : 0;
             }
             const int m = V.n_nodes ? V.fv_offset[V.n_nodes] : 0;
             for (int i = 0; i < m; ++i) {
@@ -425,16 +432,12 @@ extern "C" int tc2li_search_by_bow_batch(const tc2li_bow_pair* pairs, int n_pair
             row += V.n;
         }
     }
-    memcpy(h + o_pairs, P.data(), sizeof(BowPairDev) * n_pairs);
-    if (!tasks.empty()) memcpy(h + o_tasks, tasks.data(), sizeof(BowTaskDev) * tasks.size());
-    TC2LI_HIP_CHECK(w.d_match.ensure((size_t)n_pairs * std::max(capacity, 1) + n_pairs));
-    uint8_t* d = w.d_stage.p;
-    TC2LI_HIP_CHECK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
-    int32_t* d_match = w.d_match.p;
-    int32_t* d_nm = d_match + (size_t)n_pairs * std::max(capacity, 1);
-    TC2LI_HIP_CHECK(hipMemsetAsync(d_match, 0xff, (size_t)n_pairs * std::max(capacity, 1) * 4, st));
-    launch_bow_search(reinterpret_cast<const BowTaskDev*>(d + o_tasks), (int)tasks.size(), reinterpret_cast<const BowPairDev*>(d + o_pairs), n_pairs,
-                      d + o_desc, reinterpret_cast<const float*>(d + o_ang), d + o_hp, reinterpret_cast<const int32_t*>(d + o_idx), d_match, d_nm, st);
+    T.io.put(t_pairs, 0, P.data(), n_pairs);
+    T.io.put(t_tasks, 0, tasks.data(), tasks.size());
+    TC2LI_HIP_CHECK(T.upload(st));
+    int32_t *d_match = T.dev_work(t_match), *d_nm = T.dev_work(t_nm);
+    TC2LI_HIP_CHECK(hipMemsetAsync(d_match, 0xff, (size_t)n_pairs * cap1 * sizeof(int32_t), st));
+    launch_bow_search(T.dev(t_tasks), (int)tasks.size(), T.dev(t_pairs), n_pairs, T.dev(t_desc)->b, T.dev(t_ang), T.dev(t_hp), T.dev(t_idx), d_match, d_nm, st);
     TC2LI_HIP_CHECK(hipGetLastError());
     TC2LI_HIP_CHECK(hipMemcpyAsync(kf_keypoint_of_keypoint, d_match, (size_t)n_pairs * capacity * 4, hipMemcpyDeviceToHost, st));
     TC2LI_HIP_CHECK(hipMemcpyAsync(n_matches, d_nm, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, st));
@@ -479,81 +482,74 @@ extern "C" int tc2li_track_reference_keyframe_batch(tc2li_orb* o, tc2li_vocabula
     }
     if (int rc = ensure_device(v)) return rc;
     hipStream_t st = stream_ ? (hipStream_t)stream_ : private_stream();
-    BowWs& w = bws();
     const size_t nf = n_frames, ne = nf * std::max(capacity, 1);
     const size_t k1 = std::max<size_t>(nk, 1), i1 = std::max<size_t>(ni, 1), t1 = std::max<size_t>(nt, 1);
-    const size_t o_desc = 0, o_ang = up256(o_desc + 32 * k1), o_hp = up256(o_ang + 4 * k1), o_obs = up256(o_hp + k1), o_Xw = up256(o_obs + k1),
-                 o_idx = up256(o_Xw + 12 * k1), o_node = up256(o_idx + 4 * i1), o_tasks = up256(o_node + 4 * t1),
-                 o_pairs = up256(o_tasks + sizeof(BowTaskDev) * t1), o_pose = up256(o_pairs + sizeof(BowPairDev) * nf), o_ur = up256(o_pose + 28 * nf),
-                 bytes = up256(o_ur + 4 * ne);
-    TC2LI_HIP_CHECK(w.h_stage.ensure(bytes)); TC2LI_HIP_CHECK(w.d_stage.ensure(bytes));
-    uint8_t* h = w.h_stage.p;
-    float* ang = reinterpret_cast<float*>(h + o_ang);
-    float* Xw = reinterpret_cast<float*>(h + o_Xw);
-    int32_t* fi = reinterpret_cast<int32_t*>(h + o_idx);
-    int32_t* node = reinterpret_cast<int32_t*>(h + o_node);
-    BowTaskDev* tasks = reinterpret_cast<BowTaskDev*>(h + o_tasks);
-    float* pose = reinterpret_cast<float*>(h + o_pose);
+    // the upload block: the reference keyframes' arrays, their nodes as tasks, the pairs, the last poses, mvuRight and the transform's frame
+    // records; device-only: the matches, the counts per frame, PoseOptimization's tables and the transform's
+    PackedTransfer T;
+    const auto t_desc = T.io.take<OrbDescriptor>(k1);
+    const auto t_hp = T.io.take<uint8_t>(k1), t_obs = T.io.take<uint8_t>(k1);
+    const auto t_ang = T.io.take<float>(k1), t_Xw = T.io.take<float>(3 * k1), t_pose = T.io.take<float>(7 * nf), t_ur = T.io.take<float>(ne);
+    const auto t_idx = T.io.take<int32_t>(i1), t_node = T.io.take<int32_t>(t1);
+    const auto t_tasks = T.io.take<BowTaskDev>(t1);
+    const auto t_pairs = T.io.take<BowPairDev>(nf);
+    const BowTransform B(T, n_frames, ne);  // Frame::ComputeBoW
+    T.outputs_begin();
+    const auto t_match = T.work.take<int32_t>(ne), t_nmatch = T.work.take<int32_t>(nf), t_ninl = T.work.take<int32_t>(nf), t_nmap = T.work.take<int32_t>(nf);
+    const PoseTail pose(T.work, nf, ne);
+    TC2LI_HIP_CHECK(T.ensure(bws()));
+    float* ang = T.host(t_ang);
+    uint8_t *hp = T.host(t_hp), *obs = T.host(t_obs);
     size_t row = 0, idx = 0;
     int n_tasks = 0;
     for (int f = 0; f < n_frames; ++f) {
         const tc2li_keyframe_view& K = refs[f].kf;
-        if (K.n) {
-            memcpy(h + o_desc + 32 * row, K.descriptors, (size_t)K.n * 32);
-            memcpy(Xw + 3 * row, refs[f].Xw, (size_t)K.n * 12);
-        }
+        T.io.put(t_desc, row, K.descriptors, K.n);
+        T.io.put(t_Xw, 3 * row, refs[f].Xw, 3 * (size_t)K.n);
         for (int i = 0; i < K.n; ++i) {
             ang[row + i] = K.keys[i].angle;
-            h[o_hp + row + i] = K.has_point[i] ? 1 : 0;
-            h[o_obs + row + i] = refs[f].observed[i] ? 1 : 0;
+            hp[row + i] = K.has_point[i] ? 1 : 0;
+            obs[row + i] = refs[f].observed[i] ? 1 : 0;
         }
         for (int a = 0; a < K.n_nodes; ++a) {
             const int c = K.fv_offset[a + 1] - K.fv_offset[a];
             if (c == 0) continue;
             BowTaskDev t{};
             t.pair = f; t.kf_pos = (int32_t)idx + K.fv_offset[a]; t.kf_n = c;
-            node[n_tasks] = K.fv_node[a];
-            tasks[n_tasks++] = t;
+            T.host(t_node)[n_tasks] = K.fv_node[a];
+            T.host(t_tasks)[n_tasks++] = t;
         }
         const int m = K.n_nodes ? K.fv_offset[K.n_nodes] : 0;
-        if (m) memcpy(fi + idx, K.fv_index, (size_t)m * 4);
-        memcpy(pose + 7 * f, refs[f].last_pose7, 28);
+        T.io.put(t_idx, idx, K.fv_index, m);
+        T.io.put(t_pose, 7 * (size_t)f, refs[f].last_pose7, 7);
         idx += m;
         row += K.n;
     }
-    memcpy(h + o_pairs, P.data(), sizeof(BowPairDev) * nf);
-    memcpy(h + o_ur, u_right, 4 * nf * capacity);
-    // device work space
-    TC2LI_HIP_CHECK(w.d_ref_i32.ensure(ne + 4 * nf)); TC2LI_HIP_CHECK(w.d_probs.ensure(nf)); TC2LI_HIP_CHECK(w.d_edges.ensure(ne));
-    TC2LI_HIP_CHECK(w.d_Xw.ensure(3 * ne)); TC2LI_HIP_CHECK(w.d_poses.ensure(7 * nf)); TC2LI_HIP_CHECK(w.d_chi2.ensure(ne));
-    TC2LI_HIP_CHECK(w.d_outlier.ensure(ne)); TC2LI_HIP_CHECK(w.d_match.ensure(ne));
+    T.io.put(t_pairs, 0, P.data(), nf);
+    T.io.put(t_ur, 0, u_right, nf * capacity);
+    T.io.put(B.frames, 0, frames.data(), nf);
+    TC2LI_HIP_CHECK(T.upload(st));
     BowOutDev O;
-    if (int rc = queue_transform(v, o->d_desc.p, frames, ne, 4, O, st)) return rc;  // Frame::ComputeBoW (levelsup 4)
-    uint8_t* d = w.d_stage.p;
-    TC2LI_HIP_CHECK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
-    TC2LI_HIP_CHECK(hipMemsetAsync(w.d_match.p, 0xff, ne * sizeof(int32_t), st));
+    if (int rc = queue_transform(v, T, B, o->d_desc.p, 4, O, st)) return rc;  // levelsup 4
+    auto W = [&](auto t) { return T.dev_work(t); };
+    TC2LI_HIP_CHECK(hipMemsetAsync(W(t_match), 0xff, ne * sizeof(int32_t), st));
     BowRefArgs A{};
     A.n_frames = n_frames; A.n_tasks = n_tasks;
-    A.tasks = reinterpret_cast<const BowTaskDev*>(d + o_tasks); A.kf_node = reinterpret_cast<const int32_t*>(d + o_node);
-    A.pairs = reinterpret_cast<const BowPairDev*>(d + o_pairs);
-    A.kf_desc = d + o_desc; A.kf_has_point = d + o_hp; A.kf_observed = d + o_obs; A.kf_angle = reinterpret_cast<const float*>(d + o_ang);
-    A.kf_Xw = reinterpret_cast<const float*>(d + o_Xw); A.kf_fv_index = reinterpret_cast<const int32_t*>(d + o_idx);
-    A.last_pose7 = reinterpret_cast<const float*>(d + o_pose);
-    A.f_desc = o->d_desc.p; A.f_angle = o->d_angles.p; A.keys = o->d_mkeys.p; A.u_right = reinterpret_cast<const float*>(d + o_ur);
+    A.tasks = T.dev(t_tasks); A.kf_node = T.dev(t_node); A.pairs = T.dev(t_pairs);
+    A.kf_desc = T.dev(t_desc)->b; A.kf_has_point = T.dev(t_hp); A.kf_observed = T.dev(t_obs); A.kf_angle = T.dev(t_ang);
+    A.kf_Xw = T.dev(t_Xw); A.kf_fv_index = T.dev(t_idx); A.last_pose7 = T.dev(t_pose);
+    A.f_desc = o->d_desc.p; A.f_angle = o->d_angles.p; A.keys = o->d_mkeys.p; A.u_right = T.dev(t_ur);
     A.O = O;
     for (int l = 0; l < o->prm.nlevels; ++l) A.C.inv_sigma2[l] = o->inv_sigma2[l];
-    A.match = w.d_match.p;
-    int32_t* small = w.d_ref_i32.p;
-    A.n_matches = small; A.inliers = small + nf; A.n_inliers = small + 2 * nf; A.n_matches_map = small + 3 * nf;
-    A.probs = w.d_probs.p; A.edges = w.d_edges.p; A.Xw = w.d_Xw.p; A.edge_kp = small + 4 * nf; A.poses = w.d_poses.p; A.outlier = w.d_outlier.p;
+    A.match = W(t_match);
+    A.n_matches = W(t_nmatch); A.inliers = W(pose.inliers); A.n_inliers = W(t_ninl); A.n_matches_map = W(t_nmap);
+    A.probs = W(pose.probs); A.edges = W(pose.edges); A.Xw = W(pose.Xw); A.edge_kp = W(pose.edge_kp); A.poses = W(pose.poses); A.outlier = W(pose.outlier);
     launch_bow_reference(A, st);
-    CameraD cd;
-    memcpy(&cd, cam, sizeof(cd));
-    launch_pose_optimization(w.d_probs.p, n_frames, w.d_Xw.p, w.d_edges.p, cd, w.d_poses.p, w.d_outlier.p, w.d_chi2.p, A.inliers, capacity, st);
+    pose.launch(T, n_frames, cam, capacity, st);
     launch_bow_reference_finish(A, st);
     TC2LI_HIP_CHECK(hipGetLastError());
-    TC2LI_HIP_CHECK(hipMemcpyAsync(poses7, w.d_poses.p, 7 * nf * sizeof(double), hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(kf_keypoint_of_keypoint, w.d_match.p, nf * capacity * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(poses7, A.poses, 7 * nf * sizeof(double), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(kf_keypoint_of_keypoint, A.match, nf * capacity * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     TC2LI_HIP_CHECK(hipMemcpyAsync(n_matches, A.n_matches, nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     TC2LI_HIP_CHECK(hipMemcpyAsync(n_inliers, A.n_inliers, nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     TC2LI_HIP_CHECK(hipMemcpyAsync(n_matches_map, A.n_matches_map, nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));

@@ -5,6 +5,7 @@
 
 #include "common.hpp"
 #include "orb_device.hpp"
+#include "packed_batch.hpp"
 #include "quadtree.hpp"
 
 namespace tc2li {
@@ -73,8 +74,7 @@ struct tc2li_orb {
     // extraction builds the grids of all frames on its stream (frame_grids, projection_search.cpp) and every extraction drops them.
     tc2li::DevBuf<int32_t> d_grid_cells;   // [frames][kCellsPlus1]
     tc2li::DevBuf<uint16_t> d_grid_items;  // beside d_mkeys: the items of frame f start at last_kp_off[2 f]
-    tc2li::DevBuf<uint8_t> d_grid_tab;     // the build's frame records and item bases
-    tc2li::PinnedBuf<uint8_t> h_grid_tab;
+    tc2li::PackedBuffers grid_tab;         // the build's frame records and item bases
     std::mutex grid_mutex;                 // guards the fields below and the build
     bool grid_valid = false;
     hipStream_t grid_stream = nullptr;     // the stream of the build; a search on another stream waits for grid_event

@@ -1,7 +1,7 @@
 // The way of a problem batch through the device, as every batched entry goes it: the caller's per-problem tables are concatenated into
 // one pinned buffer [inputs | state with initial values | outputs], each table on a 256-byte boundary; parts one and two go up in one
 // copy, the kernels run, parts two and three come down in one copy, the stream is waited on and the entry scatters the results into the
-// problems' arrays.  Here: the layout (Packer), the buffers kept between calls (PackedSpace), the copies and the wait (PackedTransfer),
+// problems' arrays.  Here: the layout (Packer), the buffers kept between calls (PackedBuffers, PackedSpace), the copies and the wait (PackedTransfer),
 // the per-problem validation, the row limit of the 32-bit kernels, and what the entries with capacities share.  An entry writes its
 // sizes, its tables, its batch structure and its scatter back.
 #pragma once
@@ -13,32 +13,40 @@
 namespace tc2li {
 
 // Tables packed into one buffer, each on a 256-byte boundary: take() hands out the places, put() / get() copy `count` entries of `width`
-// bytes to / from entry `start` of the table at o, once base is the buffer.
+// bytes to / from entry `start` of the table at o, once base is the buffer.  take<T>(count) gives the place of `count` entries of T as a
+// Table<T>: the pointers and copies made from it need no type or width again.
+template <class T> struct Table { size_t o = 0; };
 struct Packer {
     uint8_t* base = nullptr;
     size_t off = 0;
     size_t take(size_t bytes) { const size_t o = off; off = align256(off + bytes); return o; }
+    template <class T> Table<T> take(size_t count) { return Table<T>{take(count * sizeof(T))}; }
     void put(size_t o, size_t start, const void* src, size_t count, size_t width) const {
         if (count) memcpy(base + o + start * width, src, count * width);
     }
     void get(void* dst, size_t o, size_t start, size_t count, size_t width) const {
         if (count) memcpy(dst, base + o + start * width, count * width);
     }
+    template <class T> void put(Table<T> t, size_t start, const void* src, size_t count) const { put(t.o, start, src, count, sizeof(T)); }
+    template <class T> void get(void* dst, Table<T> t, size_t start, size_t count) const { get(dst, t.o, start, count, sizeof(T)); }
 };
 
-// The device buffers of an entry, kept between calls; mu is held for the length of a call.  Every entry has its own through
-// shutdown_owned<PackedSpace, tag>, so none waits for another.
-struct PackedSpace {
-    std::mutex mu;
+// The buffers of an entry, kept between calls: a work space of one host thread (thread_local) holds them as they are.  PackedSpace adds
+// the mutex of a process-wide one, held for the length of a call; every such entry has its own through shutdown_owned<PackedSpace, tag>,
+// so none waits for another.
+struct PackedBuffers {
     DevBuf<uint8_t> io, work;
     PinnedBuf<uint8_t> h_io;
+};
+struct PackedSpace : PackedBuffers {
+    std::mutex mu;
 };
 enum PackedSpaceTag { kSpaceKeyframeCulling, kSpaceMapPointCulling, kSpaceConnections, kSpaceCovisibles, kSpaceStereoPoints, kSpaceMlpnp, kSpaceInertialWindow, kSpaceInertialTerm };
 
 // One call's transfer.  The entry take()s its inputs from io, calls state_begins() and takes the tables that go up and come back (an
-// entry without such tables skips this), calls outputs_begin() and takes its outputs; it takes its work tables from work.  Then, under
-// the space's lock: ensure(), the tables put into io, upload(), zero_work() where the kernels expect zeros, the launch, and
-// download_and_wait().
+// entry without such tables skips this), calls outputs_begin() and takes what does not go up with the block -- its outputs, or tables it
+// uploads later by themselves; it takes its work tables from work.  Then (a process-wide space: under its lock): ensure(), the tables
+// put into io, upload(), zero_work() where the kernels expect zeros, the launch, and download_and_wait() or the entry's own downloads.
 struct PackedTransfer {
     Packer io, work;
     size_t up_bytes = 0, down_from = ~(size_t)0;
@@ -47,7 +55,7 @@ struct PackedTransfer {
     void state_begins() { down_from = io.off; }
     void outputs_begin() { up_bytes = io.off; down_from = std::min(down_from, io.off); }
     // the work buffer is never empty: an entry may zero or point into it whatever its sizes are
-    hipError_t ensure(PackedSpace& S) {
+    hipError_t ensure(PackedBuffers& S) {
         hipError_t e = S.io.ensure(io.off);
         if (e == hipSuccess) e = S.work.ensure(std::max(work.off, (size_t)256));
         if (e == hipSuccess) e = S.h_io.ensure(io.off);
@@ -69,6 +77,13 @@ struct PackedTransfer {
     template <class T> T* dev(size_t o) const { return (T*)(d_io + o); }
     template <class T> T* dev_work(size_t o) const { return (T*)(d_work + o); }
     template <class T> T* host(size_t o) const { return (T*)(io.base + o); }
+    template <class T> T* dev(Table<T> t) const { return (T*)(d_io + t.o); }
+    template <class T> T* dev_work(Table<T> t) const { return (T*)(d_work + t.o); }
+    template <class T> T* host(Table<T> t) const { return (T*)(io.base + t.o); }
+    // entries start .. start + count of one table up again: what the host rewrote after a wait
+    template <class T> hipError_t upload(Table<T> t, size_t start, size_t count, hipStream_t st) const {
+        return hipMemcpyAsync(dev(t) + start, host(t) + start, count * sizeof(T), hipMemcpyHostToDevice, st);
+    }
 };
 
 // ---- validation ------------------------------------------------------------------------------------------------------------------------

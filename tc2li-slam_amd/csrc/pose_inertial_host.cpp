@@ -12,23 +12,15 @@
 
 #include "common.hpp"
 #include "inertial_host.hpp"
+#include "packed_batch.hpp"
 #include "pose_inertial_device.hpp"
 
 using namespace tc2li;
 
 namespace {
 
-struct PiWorkspace {
-    DevBuf<PiProblem> d_probs;
-    DevBuf<PiResult> d_results;
-    DevBuf<double> d_Xw, d_chi2;
-    DevBuf<BaEdge> d_edges;
-    DevBuf<uint8_t> d_close, d_outlier;
-    PinnedBuf<PiResult> h_results;
-    PinnedBuf<uint8_t> h_stage;  // [Xw | edges | close flags] of all frames on their way up, then the outlier flags on their way back
-    std::mutex mu;
-};
-PiWorkspace& pi_ws() { static thread_local PiWorkspace w; return w; }
+// one work space per host thread
+PackedBuffers& pi_ws() { static thread_local PackedBuffers w; return w; }
 
 void state_to(const PiState& s, tc2li_inertial_keyframe& k) {
     memcpy(k.Rcw, s.P.Rcw, 72); memcpy(k.tcw, s.P.tcw, 24); memcpy(k.Rwb, s.P.Rwb, 72); memcpy(k.twb, s.P.twb, 24);
@@ -113,7 +105,7 @@ extern "C" int tc2li_pose_inertial_optimization_batch(tc2li_pose_inertial_proble
     if (n_frames == 0) return 0;
     if (!device_ready()) return TC2LI_ERR_NO_DEVICE;
     hipStream_t st = (hipStream_t)stream_;
-    std::vector<PiProblem> probs(n_frames);
+    std::vector<int32_t> edge_off(n_frames);
     size_t total = 0;
     for (int f = 0; f < n_frames; ++f) {
         const tc2li_pose_inertial_problem& p = problems[f];
@@ -122,29 +114,28 @@ extern "C" int tc2li_pose_inertial_optimization_batch(tc2li_pose_inertial_proble
             set_error("tc2li_pose_inertial_optimization_batch: frame %d: invalid argument", f);
             return TC2LI_ERR_INVALID;
         }
-        probs[f].edge_off = (int32_t)total;
+        edge_off[f] = (int32_t)total;
         total += (size_t)p.n_edges;
     }
-    PiWorkspace& w = pi_ws();
-    std::lock_guard<std::mutex> lk(w.mu);
-    const size_t T1 = std::max<size_t>(total, 1);
-    TC2LI_HIP_CHECK(w.d_probs.ensure(n_frames)); TC2LI_HIP_CHECK(w.d_results.ensure(n_frames)); TC2LI_HIP_CHECK(w.h_results.ensure(n_frames));
-    TC2LI_HIP_CHECK(w.d_Xw.ensure(3 * T1)); TC2LI_HIP_CHECK(w.d_chi2.ensure(T1));
-    TC2LI_HIP_CHECK(w.d_edges.ensure(T1)); TC2LI_HIP_CHECK(w.d_close.ensure(T1));
-    TC2LI_HIP_CHECK(w.d_outlier.ensure(T1));
     static_assert(sizeof(BaEdge) == sizeof(tc2li_ba_edge), "ABI layout");
-    // the frames' arrays go up as three copies from one pinned block (a copy per frame and array costs more than the kernel at hundreds of
-    // frames); the per-frame host work -- information matrices of the inertial edge, later the marginalisation -- runs on the pool threads
-    const size_t o_edges = 3 * T1 * sizeof(double), o_close = o_edges + T1 * sizeof(BaEdge), stage_bytes = o_close + T1;
-    TC2LI_HIP_CHECK(w.h_stage.ensure(stage_bytes));
-    double* const h_Xw = reinterpret_cast<double*>(w.h_stage.p);
-    BaEdge* const h_edges = reinterpret_cast<BaEdge*>(w.h_stage.p + o_edges);
-    uint8_t* const h_close = w.h_stage.p + o_close;
+    // the frames' arrays and the problem records go up in one copy from the pinned block (a copy per frame and array costs more than the
+    // kernel at hundreds of frames), the results and the outlier flags come down in one; the per-frame host work -- information matrices of
+    // the inertial edge, later the marginalisation -- runs on the pool threads
+    const size_t T1 = std::max<size_t>(total, 1);
+    PackedTransfer T;
+    const auto t_Xw = T.io.take<double>(3 * T1), t_chi2 = T.work.take<double>(T1);
+    const auto t_edges = T.io.take<BaEdge>(T1);
+    const auto t_close = T.io.take<uint8_t>(T1);
+    const auto t_probs = T.io.take<PiProblem>(n_frames);
+    T.outputs_begin();
+    const auto t_results = T.io.take<PiResult>(n_frames);
+    const auto t_outlier = T.io.take<uint8_t>(T1);
+    TC2LI_HIP_CHECK(T.ensure(pi_ws()));
+    PiProblem* const probs = T.host(t_probs);
     std::atomic<int> bad_frame{-1};
     tracking_pool().parallel_for(n_frames, [&](int f) {
         const tc2li_pose_inertial_problem& p = problems[f];
         PiProblem& d = probs[f];
-        const int32_t edge_off = d.edge_off;
         memset(&d, 0, sizeof(d));
         pi_state_from(p.frame, d.cur); pi_state_from(p.other, d.other);
         pi_preint_from(*p.preintegrated, d.pre);
@@ -156,38 +147,28 @@ extern "C" int tc2li_pose_inertial_optimization_batch(tc2li_pose_inertial_proble
             memcpy(d.prior.Rwb, p.prior->Rwb, 72); memcpy(d.prior.twb, p.prior->twb, 24); memcpy(d.prior.vwb, p.prior->vwb, 24);
             memcpy(d.prior.bg, p.prior->bg, 24); memcpy(d.prior.ba, p.prior->ba, 24); memcpy(d.prior.H, p.prior->H, sizeof(d.prior.H));
         }
-        d.edge_off = edge_off; d.n_edges = p.n_edges; d.last_frame = p.last_frame ? 1 : 0; d.rec_init = p.rec_init ? 1 : 0;
-        if (p.n_edges) {
-            memcpy(h_Xw + 3 * (size_t)edge_off, p.Xw, 3 * (size_t)p.n_edges * sizeof(double));
-            memcpy(h_edges + edge_off, p.edges, (size_t)p.n_edges * sizeof(BaEdge));
-            memcpy(h_close + edge_off, p.close_point, (size_t)p.n_edges);
-        }
+        d.edge_off = edge_off[f]; d.n_edges = p.n_edges; d.last_frame = p.last_frame ? 1 : 0; d.rec_init = p.rec_init ? 1 : 0;
+        T.io.put(t_Xw, 3 * (size_t)d.edge_off, p.Xw, 3 * (size_t)p.n_edges);
+        T.io.put(t_edges, d.edge_off, p.edges, p.n_edges);
+        T.io.put(t_close, d.edge_off, p.close_point, p.n_edges);
     });
     if (bad_frame.load() >= 0) { set_error("frame %d: the pre-integration covariance is not positive definite", bad_frame.load()); return TC2LI_ERR_INVALID; }
-    if (total) {
-        TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_Xw.p, h_Xw, 3 * total * sizeof(double), hipMemcpyHostToDevice, st));
-        TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_edges.p, h_edges, total * sizeof(BaEdge), hipMemcpyHostToDevice, st));
-        TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_close.p, h_close, total, hipMemcpyHostToDevice, st));
-    }
-    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_probs.p, probs.data(), n_frames * sizeof(PiProblem), hipMemcpyHostToDevice, st));
+    TC2LI_HIP_CHECK(T.upload(st));
     ImuCalib cal;
     CameraD c;
     static_assert(sizeof(ImuCalib) == sizeof(tc2li_imu_calib), "ABI layout");
     memcpy(&cal, calib, sizeof(cal));
     memcpy(&c, cam, sizeof(c));
-    launch_pose_inertial(w.d_probs.p, n_frames, w.d_Xw.p, w.d_edges.p, w.d_close.p, cal, c, w.d_outlier.p, w.d_chi2.p, w.d_results.p, st);
+    launch_pose_inertial(T.dev(t_probs), n_frames, T.dev(t_Xw), T.dev(t_edges), T.dev(t_close), cal, c, T.dev(t_outlier), T.dev_work(t_chi2), T.dev(t_results), st);
     TC2LI_HIP_CHECK(hipGetLastError());
-    TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_results.p, w.d_results.p, n_frames * sizeof(PiResult), hipMemcpyDeviceToHost, st));
-    uint8_t* const h_outlier = w.h_stage.p;  // the uploads above have completed when this copy runs (same stream)
-    if (total) TC2LI_HIP_CHECK(hipMemcpyAsync(h_outlier, w.d_outlier.p, total, hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(stream_wait_blocking(st));
+    TC2LI_HIP_CHECK(T.download_and_wait(st));
     tracking_pool().parallel_for(n_frames, [&](int f) {
         tc2li_pose_inertial_problem& p = problems[f];
-        const PiResult& R = w.h_results.p[f];
+        const PiResult& R = T.host(t_results)[f];
         state_to(R.cur, p.frame);
         if (p.last_frame) state_to(R.other, p.other);
         p.n_initial = p.n_edges; p.n_bad = R.n_bad; p.n_inliers = R.n_inliers; p.solver_failed = R.solver_failed;
-        if (p.n_edges) memcpy(p.outlier, h_outlier + probs[f].edge_off, (size_t)p.n_edges);
+        T.io.get(p.outlier, t_outlier, edge_off[f], p.n_edges);
         if (p.prior_out) {
             tc2li_pose_imu_prior& o = *p.prior_out;
             memcpy(o.Rwb, R.cur.P.Rwb, 72); memcpy(o.twb, R.cur.P.twb, 24); memcpy(o.vwb, R.cur.v, 24); memcpy(o.bg, R.cur.bg, 24); memcpy(o.ba, R.cur.ba, 24);

@@ -46,23 +46,24 @@ int frame_grids(tc2li_orb* o, hipStream_t st, FrameGrids* out) {
     if (nf <= 0) return TC2LI_OK;
     std::lock_guard<std::mutex> lk(o->grid_mutex);
     if (!o->grid_valid) {
-        const size_t o_base = up256(sizeof(MatchFrameDev) * (size_t)nf), bytes = up256(o_base + 4 * (size_t)nf);
+        PackedTransfer T;
+        const Table<MatchFrameDev> frames = T.io.take<MatchFrameDev>(nf);
+        const Table<int32_t> key_base = T.io.take<int32_t>(nf);
+        T.outputs_begin();
         TC2LI_HIP_CHECK(o->d_grid_cells.ensure((size_t)nf * kCellsPlus1)); TC2LI_HIP_CHECK(o->d_grid_items.ensure(o->d_mkeys.n));
-        TC2LI_HIP_CHECK(o->d_grid_tab.ensure(bytes)); TC2LI_HIP_CHECK(o->h_grid_tab.ensure(bytes));
+        TC2LI_HIP_CHECK(T.ensure(o->grid_tab));
         if (!o->grid_event) TC2LI_HIP_CHECK(hipEventCreateWithFlags(&o->grid_event, hipEventDisableTiming));
-        MatchFrameDev* hm = reinterpret_cast<MatchFrameDev*>(o->h_grid_tab.p);
-        int32_t* hb = reinterpret_cast<int32_t*>(o->h_grid_tab.p + o_base);
         for (int f = 0; f < nf; ++f) {
             const int off = o->last_kp_off[2 * f], n = o->last_kp_cnt[2 * f];
             // a frame with more keys than the matcher takes is refused by every search (check_match_keys): its grid stays empty
-            hm[f] = MatchFrameDev{o->d_mkeys.p + off, nullptr, nullptr, nullptr, nullptr, n <= kMaxMatchKeys ? n : 0, 0, 0, 0,
-                                  0.0f, (float)o->cur_w, 0.0f, (float)o->cur_h};
-            hb[f] = off;
+            T.host(frames)[f] = MatchFrameDev{o->d_mkeys.p + off, nullptr, nullptr, nullptr, nullptr, n <= kMaxMatchKeys ? n : 0, 0, 0, 0,
+                                              0.0f, (float)o->cur_w, 0.0f, (float)o->cur_h};
+            T.host(key_base)[f] = off;
         }
-        TC2LI_HIP_CHECK(hipMemcpyAsync(o->d_grid_tab.p, o->h_grid_tab.p, bytes, hipMemcpyHostToDevice, st));
+        TC2LI_HIP_CHECK(T.upload(st));
         MatchLists L{};
-        L.cell_start = o->d_grid_cells.p; L.items = o->d_grid_items.p; L.key_base = reinterpret_cast<const int32_t*>(o->d_grid_tab.p + o_base);
-        launch_match_grid(reinterpret_cast<const MatchFrameDev*>(o->d_grid_tab.p), nf, L, st);
+        L.cell_start = o->d_grid_cells.p; L.items = o->d_grid_items.p; L.key_base = T.dev(key_base);
+        launch_match_grid(T.dev(frames), nf, L, st);
         TC2LI_HIP_CHECK(hipGetLastError());
         TC2LI_HIP_CHECK(hipEventRecord(o->grid_event, st));
         o->grid_valid = true; o->grid_stream = st; ++o->grid_builds;

@@ -1,6 +1,7 @@
 // The host driver every projection search shares (tracking_host.cpp: TrackWithMotionModel / TrackLocalMap; reloc_host.cpp: the keyframe
 // overload and the refinement ladder): the scratch buffers of a search, MapPoint::PredictScale on the host for ratios on a level boundary,
-// the list-form matcher with its fall-back to the one-kernel form, and the small helpers those entry points had a copy of each.
+// the list-form matcher with its fall-back to the one-kernel form, the keyframe points' tables, the pose-optimisation tail (also bow_host.cpp's)
+// and the small helpers those entry points had a copy of each.  Every table of a call has its place from a Packer (packed_batch.hpp).
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -9,11 +10,11 @@
 #include "common.hpp"
 #include "matcher_device.hpp"
 #include "orb_handle.hpp"
+#include "packed_batch.hpp"
+#include "pose_opt_device.hpp"
 #include "tracking_device.hpp"
 
 namespace tc2li {
-
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // MapPoint::PredictScale (SF/src/MapPoint.cc:540-555) with the host library's logf: the one definition
 inline int predict_scale_level(float ratio, float log_scale, int n_levels) {
@@ -57,29 +58,53 @@ inline TrackConst track_const(const tc2li_orb* o, const tc2li_camera* cam, float
 }
 
 // ---- the keyframe's points of the keyframe overload (tc2li_projection_keyframe_item / tc2li_reloc_hypothesis), query-indexed ----
-struct KeyframePointStage {  // offsets in the caller's staging block, q1 points
-    size_t o_hp, o_Xw, o_pd, o_min, o_max, o_raw, o_pang, end;
-    KeyframePointStage(size_t begin, size_t q1)
-        : o_hp(begin), o_Xw(up256(o_hp + q1)), o_pd(up256(o_Xw + 12 * q1)), o_min(up256(o_pd + 32 * q1)), o_max(up256(o_min + 4 * q1)),
-          o_raw(up256(o_max + 4 * q1)), o_pang(up256(o_raw + 4 * q1)), end(up256(o_pang + 4 * q1)) {}
-    KeyframePointArrays arrays(const uint8_t* d, const uint8_t* d_found) const {
-        auto f = [&](size_t off) { return reinterpret_cast<const float*>(d + off); };
-        return KeyframePointArrays{d + o_hp, d_found, f(o_Xw), d + o_pd, f(o_min), f(o_max), f(o_raw), f(o_pang)};
+struct OrbDescriptor { uint8_t b[32]; };
+struct KeyframePointTables {
+    Table<uint8_t> has_point;
+    Table<float> Xw, min_distance, max_distance, max_distance_raw, angle;  // Xw: [3] each
+    Table<OrbDescriptor> desc;
+};
+// the places of q1 points in the caller's upload block
+inline KeyframePointTables take_keyframe_points(Packer& io, size_t q1) {
+    KeyframePointTables S;
+    S.has_point = io.take<uint8_t>(q1); S.Xw = io.take<float>(3 * q1); S.desc = io.take<OrbDescriptor>(q1); S.min_distance = io.take<float>(q1);
+    S.max_distance = io.take<float>(q1); S.max_distance_raw = io.take<float>(q1); S.angle = io.take<float>(q1);
+    return S;
+}
+// packs the points of `it` at query offset q
+template <typename Item>
+void stage_keyframe_points(const PackedTransfer& T, const KeyframePointTables& S, size_t q, const Item& it) {
+    const size_t n = (size_t)it.n_points;
+    uint8_t* hp = T.host(S.has_point) + q;
+    for (size_t i = 0; i < n; ++i) hp[i] = it.has_point[i] ? 1 : 0;
+    T.io.put(S.Xw, 3 * q, it.Xw, 3 * n); T.io.put(S.desc, q, it.point_descriptors, n); T.io.put(S.min_distance, q, it.min_distance, n);
+    T.io.put(S.max_distance, q, it.max_distance, n); T.io.put(S.max_distance_raw, q, it.max_distance_raw, n); T.io.put(S.angle, q, it.angle, n);
+}
+inline KeyframePointArrays keyframe_point_arrays(const PackedTransfer& T, const KeyframePointTables& S, const uint8_t* d_found) {
+    return KeyframePointArrays{T.dev(S.has_point), d_found, T.dev(S.Xw), T.dev(S.desc)->b, T.dev(S.min_distance), T.dev(S.max_distance),
+                               T.dev(S.max_distance_raw), T.dev(S.angle)};
+}
+
+// ---- Optimizer::PoseOptimization behind a search: its eight device tables for (n_frames, n_edges), taken from the work Packer, and the
+// launch over them.  A caller's kernels write probs, edges, Xw, edge_kp and poses before and read outlier and inliers after. ----
+struct PoseTail {
+    Table<PoseProblem> probs;
+    Table<BaEdge> edges;
+    Table<double> Xw, poses, chi2;
+    Table<int32_t> edge_kp, inliers;
+    Table<uint8_t> outlier;
+    PoseTail(Packer& work, size_t n_frames, size_t n_edges) {
+        probs = work.take<PoseProblem>(n_frames); edges = work.take<BaEdge>(n_edges); Xw = work.take<double>(3 * n_edges);
+        edge_kp = work.take<int32_t>(n_edges); poses = work.take<double>(7 * n_frames); outlier = work.take<uint8_t>(n_edges);
+        chi2 = work.take<double>(n_edges); inliers = work.take<int32_t>(n_frames);
+    }
+    void launch(const PackedTransfer& T, int n_frames, const tc2li_camera* cam, int max_edges, hipStream_t st) const {
+        CameraD cd;
+        memcpy(&cd, cam, sizeof(cd));
+        launch_pose_optimization(T.dev_work(probs), n_frames, T.dev_work(Xw), T.dev_work(edges), cd, T.dev_work(poses), T.dev_work(outlier),
+                                 T.dev_work(chi2), T.dev_work(inliers), max_edges, st);
     }
 };
-// packs the points of `it` at query offset q of the host block h
-template <typename Item>
-void stage_keyframe_points(const KeyframePointStage& S, uint8_t* h, size_t q, const Item& it) {
-    const size_t n = (size_t)it.n_points;
-    for (size_t i = 0; i < n; ++i) h[S.o_hp + q + i] = it.has_point[i] ? 1 : 0;
-    if (!n) return;
-    memcpy(h + S.o_Xw + 12 * q, it.Xw, 12 * n);
-    memcpy(h + S.o_pd + 32 * q, it.point_descriptors, 32 * n);
-    memcpy(h + S.o_min + 4 * q, it.min_distance, 4 * n);
-    memcpy(h + S.o_max + 4 * q, it.max_distance, 4 * n);
-    memcpy(h + S.o_raw + 4 * q, it.max_distance_raw, 4 * n);
-    memcpy(h + S.o_pang + 4 * q, it.angle, 4 * n);
-}
 
 // ---- the buffers of a search: one per work space (TrackWs, KfSearchWs, LadderWs) ----
 struct SearchScratch {

@@ -135,14 +135,8 @@ int sync_device(tc2li_keyframe_db* db, std::vector<RelocRowDev>& stage, std::vec
     return TC2LI_OK;
 }
 
-struct RelocWs {
-    DevBuf<int32_t> d_word, d_i32;
-    DevBuf<double> d_value, d_out;
-    DevBuf<float> d_f32;
-    DevBuf<RelocPairDev> d_pairs;
-    DevBuf<RelocQueryDev> d_queries;
-};
-RelocWs& rws() { static thread_local RelocWs w; return w; }
+// the buffers of tc2li_vocabulary_score_batch and tc2li_detect_relocalization_candidates_batch, per host thread
+PackedBuffers& rws() { static thread_local PackedBuffers w; return w; }
 
 const char* kKlText = "scoring type KL is not supported on the device (it calls log(), whose device result is not the host library's to the last bit)";
 
@@ -268,22 +262,23 @@ extern "C" int tc2li_vocabulary_score_batch(tc2li_vocabulary* voc, int n_pairs, 
         total += (size_t)v1[p].n + v2[p].n;
     }
     if (n_pairs == 0) return 0;
-    std::vector<int32_t> word(std::max<size_t>(total, 1));
-    std::vector<double> value(std::max<size_t>(total, 1));
-    for (int p = 0; p < n_pairs; ++p) {
-        if (v1[p].n) { memcpy(&word[P[p].off1], v1[p].word, v1[p].n * sizeof(int32_t)); memcpy(&value[P[p].off1], v1[p].value, v1[p].n * sizeof(double)); }
-        if (v2[p].n) { memcpy(&word[P[p].off2], v2[p].word, v2[p].n * sizeof(int32_t)); memcpy(&value[P[p].off2], v2[p].value, v2[p].n * sizeof(double)); }
-    }
     hipStream_t st = stream_ ? (hipStream_t)stream_ : private_stream();
-    RelocWs& w = rws();
-    TC2LI_HIP_CHECK(w.d_word.ensure(word.size())); TC2LI_HIP_CHECK(w.d_value.ensure(value.size()));
-    TC2LI_HIP_CHECK(w.d_pairs.ensure(n_pairs)); TC2LI_HIP_CHECK(w.d_out.ensure(n_pairs));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_word.p, word.data(), word.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_value.p, value.data(), value.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_pairs.p, P.data(), n_pairs * sizeof(RelocPairDev), hipMemcpyHostToDevice, st));
-    launch_bow_score(w.d_pairs.p, n_pairs, w.d_word.p, w.d_value.p, sc, w.d_out.p, st);
+    PackedTransfer T;
+    const size_t t1 = std::max<size_t>(total, 1);
+    const auto t_pairs = T.io.take<RelocPairDev>(n_pairs);
+    const auto t_word = T.io.take<int32_t>(t1);
+    const auto t_value = T.io.take<double>(t1), t_out = T.work.take<double>(n_pairs);
+    T.outputs_begin();
+    TC2LI_HIP_CHECK(T.ensure(rws()));
+    T.io.put(t_pairs, 0, P.data(), n_pairs);
+    for (int p = 0; p < n_pairs; ++p) {
+        T.io.put(t_word, P[p].off1, v1[p].word, v1[p].n); T.io.put(t_value, P[p].off1, v1[p].value, v1[p].n);
+        T.io.put(t_word, P[p].off2, v2[p].word, v2[p].n); T.io.put(t_value, P[p].off2, v2[p].value, v2[p].n);
+    }
+    TC2LI_HIP_CHECK(T.upload(st));
+    launch_bow_score(T.dev(t_pairs), n_pairs, T.dev(t_word), T.dev(t_value), sc, T.dev_work(t_out), st);
     TC2LI_HIP_CHECK(hipGetLastError());
-    TC2LI_HIP_CHECK(hipMemcpyAsync(scores, w.d_out.p, n_pairs * sizeof(double), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(scores, T.dev_work(t_out), n_pairs * sizeof(double), hipMemcpyDeviceToHost, st));
     TC2LI_HIP_CHECK(stream_wait_blocking(st));
     return n_pairs;
 }
@@ -329,46 +324,51 @@ extern "C" int tc2li_detect_relocalization_candidates_batch(const tc2li_reloc_qu
     for (tc2li_keyframe_db* d : order) locks.emplace_back(d->mu);
 
     hipStream_t st = stream_ ? (hipStream_t)stream_ : private_stream();
-    RelocWs& w = rws();
-    // the frames' BowVectors, one upload
-    std::vector<int32_t> f_word(std::max<size_t>(n_f, 1));
-    std::vector<double> f_value(std::max<size_t>(n_f, 1));
-    std::vector<RelocQueryDev> QD(n_queries);
+    size_t n_rows = 0;
+    int max_rows = 0;
+    for (int q = 0; q < n_queries; ++q) {
+        const int n = (int)queries[q].db->rows.size();
+        if (n > 2 * kRelocMaxLive) { set_error("%s: query %d: the pool holds %d rows", fn, q, n); return TC2LI_ERR_CAPACITY; }
+        n_rows += n;
+        max_rows = std::max(max_rows, n);
+    }
+    const size_t nq = n_queries, nr = std::max<size_t>(n_rows, 1), cap = std::max(capacity, 1), f1 = std::max<size_t>(n_f, 1);
+    const size_t lc = std::min<size_t>(kRelocMaxLive, std::max(max_rows, 1));
+    // the upload block: the frames' BowVectors and the query records; device-only: per pool row, per query, the candidate and scored lists
+    PackedTransfer T;
+    const auto t_word = T.io.take<int32_t>(f1);
+    const auto t_value = T.io.take<double>(f1);
+    const auto t_queries = T.io.take<RelocQueryDev>(nq);
+    T.outputs_begin();
+    const auto t_common = T.work.take<int32_t>(nr), t_first_word = T.work.take<int32_t>(nr), t_ncand = T.work.take<int32_t>(nq),
+               t_nscored = T.work.take<int32_t>(nq), t_cand = T.work.take<int32_t>(nq * cap), t_sc_row = T.work.take<int32_t>(nq * lc),
+               t_sc_kf_words = T.work.take<int32_t>(2 * nq * lc),  // sc_kf, sc_words: one download
+               t_sc_best_row = T.work.take<int32_t>(nq * lc), t_sc_best = T.work.take<int32_t>(nq * lc);
+    const auto t_si = T.work.take<float>(nr), t_sc_si_acc = T.work.take<float>(2 * nq * lc);  // sc_si, sc_acc: one download
+    TC2LI_HIP_CHECK(T.ensure(rws()));
     std::vector<std::vector<RelocRowDev>> stage(n_queries);
     std::vector<std::vector<float>> stage_score(n_queries);
     size_t pos = 0, row_off = 0;
-    int max_rows = 0;
     for (int q = 0; q < n_queries; ++q) {
         const tc2li_reloc_query& Q = queries[q];
         tc2li_keyframe_db* db = Q.db;
         if (int rc = sync_device(db, stage[q], stage_score[q], st)) return rc;
-        if (Q.n_words) { memcpy(&f_word[pos], Q.bow_word, Q.n_words * sizeof(int32_t)); memcpy(&f_value[pos], Q.bow_value, Q.n_words * sizeof(double)); }
-        RelocQueryDev& D = QD[q];
+        T.io.put(t_word, pos, Q.bow_word, Q.n_words); T.io.put(t_value, pos, Q.bow_value, Q.n_words);
+        RelocQueryDev& D = T.host(t_queries)[q];
         D.kf_word = db->d_word.p; D.kf_value = db->d_value.p; D.rows = db->d_rows.p; D.score = db->d_score.p;
         D.n_rows = (int32_t)db->rows.size();
         D.f_off = (int32_t)pos; D.f_n = Q.n_words; D.map_id = Q.map_id; D.row_off = (int32_t)row_off; D.pad_ = 0;
-        if (D.n_rows > 2 * kRelocMaxLive) { set_error("%s: query %d: the pool holds %d rows", fn, q, D.n_rows); return TC2LI_ERR_CAPACITY; }
         pos += Q.n_words;
         row_off += D.n_rows;
-        max_rows = std::max(max_rows, D.n_rows);
     }
-    const size_t nq = n_queries, nr = std::max<size_t>(row_off, 1), cap = std::max(capacity, 1);
-    const size_t lc = std::min<size_t>(kRelocMaxLive, std::max(max_rows, 1));
-    TC2LI_HIP_CHECK(w.d_word.ensure(f_word.size())); TC2LI_HIP_CHECK(w.d_value.ensure(f_value.size())); TC2LI_HIP_CHECK(w.d_queries.ensure(nq));
-    // int32: common, first_word [nr]; n_candidates, n_scored [nq]; candidates [nq][cap]; sc_row, sc_kf, sc_words, sc_best_row, sc_best [nq][lc]
-    TC2LI_HIP_CHECK(w.d_i32.ensure(2 * nr + 2 * nq + nq * cap + 5 * nq * lc));
-    TC2LI_HIP_CHECK(w.d_f32.ensure(nr + 2 * nq * lc));  // si [nr]; sc_si, sc_acc [nq][lc]
-    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_word.p, f_word.data(), f_word.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_value.p, f_value.data(), f_value.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_queries.p, QD.data(), nq * sizeof(RelocQueryDev), hipMemcpyHostToDevice, st));
+    TC2LI_HIP_CHECK(T.upload(st));
+    auto W = [&](auto t) { return T.dev_work(t); };
     RelocArgs A{};
-    A.queries = w.d_queries.p; A.n_queries = n_queries; A.max_rows = max_rows; A.scoring = scoring;
-    A.f_word = w.d_word.p; A.f_value = w.d_value.p;
-    int32_t* ip = w.d_i32.p;
-    A.common = ip; A.first_word = ip + nr; A.n_candidates = ip + 2 * nr; A.n_scored = A.n_candidates + nq; A.candidates = A.n_scored + nq;
-    A.sc_row = A.candidates + nq * cap; A.sc_kf = A.sc_row + nq * lc; A.sc_words = A.sc_kf + nq * lc; A.sc_best_row = A.sc_words + nq * lc;
-    A.sc_best = A.sc_best_row + nq * lc;
-    A.si = w.d_f32.p; A.sc_si = A.si + nr; A.sc_acc = A.sc_si + nq * lc;
+    A.queries = T.dev(t_queries); A.n_queries = n_queries; A.max_rows = max_rows; A.scoring = scoring;
+    A.f_word = T.dev(t_word); A.f_value = T.dev(t_value);
+    A.common = W(t_common); A.first_word = W(t_first_word); A.n_candidates = W(t_ncand); A.n_scored = W(t_nscored); A.candidates = W(t_cand);
+    A.sc_row = W(t_sc_row); A.sc_kf = W(t_sc_kf_words); A.sc_words = A.sc_kf + nq * lc; A.sc_best_row = W(t_sc_best_row); A.sc_best = W(t_sc_best);
+    A.si = W(t_si); A.sc_si = W(t_sc_si_acc); A.sc_acc = A.sc_si + nq * lc;
     A.capacity = capacity; A.list_cap = (int)lc;
     TC2LI_HIP_CHECK(hipMemsetAsync(A.candidates, 0xff, nq * cap * sizeof(int32_t), st));
     launch_reloc_candidates(A, st);
@@ -431,10 +431,8 @@ extern "C" int tc2li_detect_relocalization_candidates_batch(const tc2li_reloc_qu
 namespace {
 
 struct KfSearchWs {
-    PinnedBuf<uint8_t> h_stage;
-    DevBuf<uint8_t> d_stage;
+    PackedBuffers b;
     SearchScratch s;
-    DevBuf<int32_t> d_of_key;
 };
 KfSearchWs& kws() { static thread_local KfSearchWs w; return w; }
 
@@ -470,25 +468,25 @@ extern "C" int tc2li_search_by_projection_keyframe_batch(const tc2li_projection_
     SearchScratch& S = w.s;
     const size_t nf = n_items, k1 = std::max<size_t>(nk, 1), q1 = std::max<size_t>(nq, 1), cap1 = std::max(capacity, 1);
     const int total_q = (int)nq;
-    // one staging block: per frame keypoint the matcher's key, descriptor, angle, held flag and a u_right of -1 (the overload has no stereo
-    // test); per keyframe keypoint the point; per frame the records
-    const size_t o_keys = 0, o_desc = up256(o_keys + sizeof(MatchKey) * k1), o_ang = up256(o_desc + 32 * k1), o_ur = up256(o_ang + 4 * k1),
-                 o_held = up256(o_ur + 4 * k1);
-    const KeyframePointStage pts(up256(o_held + k1), q1);
-    const size_t o_found = pts.end, o_frames = up256(o_found + q1), o_bounds = up256(o_frames + sizeof(TrackFrameDev) * nf),
-                 o_mframes = up256(o_bounds + 16 * nf), o_kbase = up256(o_mframes + sizeof(MatchFrameDev) * nf), bytes = up256(o_kbase + 4 * nf);
-    TC2LI_HIP_CHECK(w.h_stage.ensure(bytes)); TC2LI_HIP_CHECK(w.d_stage.ensure(bytes));
+    // the upload block: per frame keypoint the matcher's key, descriptor, angle, held flag and a u_right of -1 (the overload has no stereo
+    // test); per keyframe keypoint the point; per frame the records.  Device-only: the keypoints' keyframe keypoints.
+    PackedTransfer T;
+    const auto t_keys = T.io.take<MatchKey>(k1);
+    const auto t_desc = T.io.take<OrbDescriptor>(k1);
+    const auto t_ang = T.io.take<float>(k1), t_ur = T.io.take<float>(k1);
+    const auto t_held = T.io.take<uint8_t>(k1), t_found = T.io.take<uint8_t>(q1);
+    const KeyframePointTables pts = take_keyframe_points(T.io, q1);
+    const auto t_frames = T.io.take<TrackFrameDev>(nf);
+    const auto t_bounds = T.io.take<float4>(nf);
+    const auto t_mframes = T.io.take<MatchFrameDev>(nf);
+    const auto t_kbase = T.io.take<int32_t>(nf), t_of_key = T.work.take<int32_t>(nf * cap1);
+    T.outputs_begin();
+    TC2LI_HIP_CHECK(T.ensure(w.b));
     if (int rc = S.ensure(n_items, total_q, capacity)) return rc;
-    TC2LI_HIP_CHECK(w.d_of_key.ensure(nf * cap1));
-    uint8_t* h = w.h_stage.p;
-    uint8_t* d = w.d_stage.p;
-    MatchKey* hk = reinterpret_cast<MatchKey*>(h + o_keys);
-    float* hang = reinterpret_cast<float*>(h + o_ang);
-    float* hur = reinterpret_cast<float*>(h + o_ur);
-    TrackFrameDev* hf = reinterpret_cast<TrackFrameDev*>(h + o_frames);
-    float* hb = reinterpret_cast<float*>(h + o_bounds);
-    MatchFrameDev* hm = reinterpret_cast<MatchFrameDev*>(h + o_mframes);
-    int32_t* hkb = reinterpret_cast<int32_t*>(h + o_kbase);
+    MatchKey* hk = T.host(t_keys);
+    float *hang = T.host(t_ang), *hur = T.host(t_ur);
+    uint8_t *hheld = T.host(t_held), *hfound = T.host(t_found);
+    TrackFrameDev* hf = T.host(t_frames);
     size_t key = 0, q = 0;
     for (int f = 0; f < n_items; ++f) {
         const tc2li_projection_keyframe_item& I = items[f];
@@ -496,42 +494,41 @@ extern "C" int tc2li_search_by_projection_keyframe_batch(const tc2li_projection_
             hk[key + i] = MatchKey{I.keys[i].x, I.keys[i].y, I.keys[i].octave};
             hang[key + i] = I.keys[i].angle;
             hur[key + i] = -1.0f;
-            h[o_held + key + i] = I.held[i] ? 1 : 0;
+            hheld[key + i] = I.held[i] ? 1 : 0;
         }
-        if (I.n) memcpy(h + o_desc + 32 * key, I.descriptors, 32 * (size_t)I.n);
-        stage_keyframe_points(pts, h, q, I);
-        for (int i = 0; i < I.n_points; ++i) h[o_found + q + i] = I.found[i] ? 1 : 0;
+        T.io.put(t_desc, key, I.descriptors, I.n);
+        stage_keyframe_points(T, pts, q, I);
+        for (int i = 0; i < I.n_points; ++i) hfound[q + i] = I.found[i] ? 1 : 0;
         TrackFrameDev& F = hf[f];
         memset(&F, 0, sizeof(F));
         memcpy(F.pose7, I.pose7, 7 * sizeof(float));
         F.th = th; F.q_off = (int32_t)q; F.n_q = I.n_points; F.key_off = (int32_t)key; F.n_keys = I.n; F.slot = f;
-        memcpy(hb + 4 * f, I.bounds, 16);
-        hm[f] = MatchFrameDev{reinterpret_cast<const MatchKey*>(d + o_keys) + key, d + o_desc + 32 * key, reinterpret_cast<const float*>(d + o_ur) + key,
-                              d + o_held + key, S.d_queries.p + q, I.n, I.n_points, (int32_t)q, 0, I.bounds[0], I.bounds[1], I.bounds[2], I.bounds[3]};
-        hkb[f] = (int32_t)key;
+        T.io.put(t_bounds, f, I.bounds, 1);
+        T.host(t_mframes)[f] = MatchFrameDev{T.dev(t_keys) + key, T.dev(t_desc)[key].b, T.dev(t_ur) + key, T.dev(t_held) + key, S.d_queries.p + q,
+                                             I.n, I.n_points, (int32_t)q, 0, I.bounds[0], I.bounds[1], I.bounds[2], I.bounds[3]};
+        T.host(t_kbase)[f] = (int32_t)key;
         key += I.n; q += I.n_points;
     }
     const TrackConst C = track_const(cam4, scale_factors, n_levels, log_scale_factor, capacity);
-    TC2LI_HIP_CHECK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
-    const TrackFrameDev* d_frames = reinterpret_cast<const TrackFrameDev*>(d + o_frames);
-    const KeyframePointArrays A = pts.arrays(d, d + o_found);
-    TC2LI_HIP_CHECK(hipMemsetAsync(w.d_of_key.p, 0xff, nf * cap1 * sizeof(int32_t), st));
+    TC2LI_HIP_CHECK(T.upload(st));
+    const TrackFrameDev* d_frames = T.dev(t_frames);
+    const KeyframePointArrays A = keyframe_point_arrays(T, pts, T.dev(t_found));
+    int32_t* d_of_key = T.dev_work(t_of_key);
+    TC2LI_HIP_CHECK(hipMemsetAsync(d_of_key, 0xff, nf * cap1 * sizeof(int32_t), st));
     TC2LI_HIP_CHECK(hipMemsetAsync(S.d_nmatch.p, 0, nf * sizeof(int32_t), st));
     if (total_q > 0) {
         TC2LI_HIP_CHECK(hipMemsetAsync(S.amb_count(), 0, sizeof(int32_t), st));
-        launch_track_queries_keyframe(d_frames, n_items, reinterpret_cast<const float4*>(d + o_bounds), C, A, total_q, S.d_queries.p, S.d_query_frame.p,
+        launch_track_queries_keyframe(d_frames, n_items, T.dev(t_bounds), C, A, total_q, S.d_queries.p, S.d_query_frame.p,
                                       S.d_match.p, S.amb_count(), S.d_amb_ids.p, S.d_amb_ratio.p, S.d_amb_r.p, st);
         if (int rc = resolve_ambiguous_levels(S, C, launch_track_patch_levels_keyframe, st)) return rc;
         // the follow-up kernels go behind the overflow decision: k_track_assign_keyframe scatters into of_key and must not see a partial list
-        const SearchPass P{reinterpret_cast<const MatchFrameDev*>(d + o_mframes), reinterpret_cast<const int32_t*>(d + o_kbase), n_items, total_q, hf, nullptr,
-                           0, 0.0f, orb_dist};
+        const SearchPass P{T.dev(t_mframes), T.dev(t_kbase), n_items, total_q, hf, nullptr, 0, 0.0f, orb_dist};
         if (int rc = projection_search(S, P, st)) return rc;
-        launch_track_count(d_frames, nullptr, n_items, S.d_queries.p, reinterpret_cast<const float*>(d + o_ang), check_orientation ? 1 : 0, S.d_match.p,
-                           S.d_nmatch.p, st);
-        launch_track_assign_keyframe(d_frames, n_items, capacity, total_q, S.d_match.p, w.d_of_key.p, st);
+        launch_track_count(d_frames, nullptr, n_items, S.d_queries.p, T.dev(t_ang), check_orientation ? 1 : 0, S.d_match.p, S.d_nmatch.p, st);
+        launch_track_assign_keyframe(d_frames, n_items, capacity, total_q, S.d_match.p, d_of_key, st);
         TC2LI_HIP_CHECK(hipGetLastError());
     }
-    if (capacity > 0) TC2LI_HIP_CHECK(hipMemcpyAsync(kf_keypoint_of_keypoint, w.d_of_key.p, nf * cap1 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (capacity > 0) TC2LI_HIP_CHECK(hipMemcpyAsync(kf_keypoint_of_keypoint, d_of_key, nf * cap1 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     TC2LI_HIP_CHECK(hipMemcpyAsync(n_matches, S.d_nmatch.p, nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     TC2LI_HIP_CHECK(stream_wait_blocking(st));
     return n_items;
@@ -545,14 +542,8 @@ extern "C" int tc2li_search_by_projection_keyframe_batch(const tc2li_projection_
 namespace {
 
 struct LadderWs {
-    PinnedBuf<uint8_t> h_stage;
-    DevBuf<uint8_t> d_stage, d_u8;
-    DevBuf<TrackFrameDev> d_frames;
+    PackedBuffers b;
     SearchScratch s;
-    DevBuf<int32_t> d_i32;
-    DevBuf<PoseProblem> d_probs;
-    DevBuf<BaEdge> d_edges;
-    DevBuf<double> d_f64;
 };
 LadderWs& lws() { static thread_local LadderWs w; return w; }
 
@@ -596,97 +587,96 @@ extern "C" int tc2li_relocalization_refine_batch(tc2li_orb* o, const tc2li_reloc
     SearchScratch& S = w.s;
     const size_t nh = n_hyps, cap1 = std::max(capacity, 1), q1 = std::max<size_t>(nq, 1), ne = nh * cap1, nfr = std::max(n_frames, 1);
     const int total_q = (int)nq;
+    // the upload block: the keyframes' points, the hypotheses' matches and inlier flags, mvuRight, a row of -1 (the search has no stereo
+    // test), the records per hypothesis
+    PackedTransfer T;
+    const KeyframePointTables pts = take_keyframe_points(T.io, q1);
+    const auto t_match = T.io.take<int32_t>(ne), t_kbase = T.io.take<int32_t>(nh), t_foh = T.io.take<int32_t>(nh);
+    const auto t_inl = T.io.take<uint8_t>(ne);
+    const auto t_ur = T.io.take<float>(nfr * cap1), t_neg = T.io.take<float>(cap1);
+    const auto t_frames = T.io.take<TrackFrameDev>(nh);
+    const auto t_bounds = T.io.take<float4>(nh);
+    const auto t_mframes = T.io.take<MatchFrameDev>(nh);
+    T.outputs_begin();
+    // device-only: the ladder's state per hypothesis, per keypoint and per keyframe point, PoseOptimization's tables
+    const auto t_active = T.work.take<int32_t>(nh), t_status = T.work.take<int32_t>(nh), t_ngood = T.work.take<int32_t>(nh),
+               t_nadd = T.work.take<int32_t>(2 * nh), t_assign = T.work.take<int32_t>(ne);
+    const auto t_found = T.work.take<uint8_t>(q1), t_occ = T.work.take<uint8_t>(ne), t_outl_key = T.work.take<uint8_t>(ne);
+    const auto t_stage_poses = T.work.take<double>(21 * nh);
+    const PoseTail pose(T.work, nh, ne);
+    TC2LI_HIP_CHECK(T.ensure(w.b));
+    if (int rc = S.ensure(n_hyps, total_q, capacity)) return rc;
     FrameGrids G;  // the handle's grids: hypothesis k reads the row of its frame (frame_of_hyp), the items start where the frame's keys start
     if (int rc = frame_grids(o, st, &G)) return rc;
-    const KeyframePointStage pts(0, q1);
-    const size_t o_match = pts.end, o_inl = up256(o_match + 4 * ne), o_ur = up256(o_inl + ne), o_neg = up256(o_ur + 4 * nfr * cap1),
-                 o_frames = up256(o_neg + 4 * cap1), o_bounds = up256(o_frames + sizeof(TrackFrameDev) * nh), o_mframes = up256(o_bounds + 16 * nh),
-                 o_kbase = up256(o_mframes + sizeof(MatchFrameDev) * nh), o_foh = up256(o_kbase + 4 * nh), bytes = up256(o_foh + 4 * nh);
-    TC2LI_HIP_CHECK(w.h_stage.ensure(bytes)); TC2LI_HIP_CHECK(w.d_stage.ensure(bytes));
-    TC2LI_HIP_CHECK(w.d_frames.ensure(nh));
-    if (int rc = S.ensure(n_hyps, total_q, capacity)) return rc;
-    // int32: active, status, n_good, inliers [nh]; n_additional [nh][2]; assign, edge_kp [nh][capacity]
-    TC2LI_HIP_CHECK(w.d_i32.ensure(6 * nh + 2 * ne));
-    TC2LI_HIP_CHECK(w.d_u8.ensure(q1 + 3 * ne));  // found [q1]; occupied, outlier_of_key, outlier [nh][capacity]
-    TC2LI_HIP_CHECK(w.d_probs.ensure(nh)); TC2LI_HIP_CHECK(w.d_edges.ensure(ne));
-    TC2LI_HIP_CHECK(w.d_f64.ensure(3 * ne + 7 * nh + 21 * nh + ne));  // Xw, poses, stage_poses, chi2
-    uint8_t* h = w.h_stage.p;
-    uint8_t* d = w.d_stage.p;
-    memset(h + o_match, 0xff, 4 * ne);
-    memset(h + o_inl, 0, ne);
-    memcpy(h + o_ur, u_right, 4 * (size_t)n_frames * capacity);
-    for (size_t i = 0; i < cap1; ++i) reinterpret_cast<float*>(h + o_neg)[i] = -1.0f;  // the overload has no stereo test
-    TrackFrameDev* hf = reinterpret_cast<TrackFrameDev*>(h + o_frames);
-    MatchFrameDev* hm = reinterpret_cast<MatchFrameDev*>(h + o_mframes);
-    uint8_t* d_u8 = w.d_u8.p;
-    uint8_t *d_found = d_u8, *d_occ = d_u8 + q1, *d_outl_key = d_occ + ne, *d_outl = d_outl_key + ne;
+    auto W = [&](auto t) { return T.dev_work(t); };
+    memset(T.host(t_match), 0xff, ne * sizeof(int32_t));
+    memset(T.host(t_inl), 0, ne);
+    T.io.put(t_ur, 0, u_right, (size_t)n_frames * capacity);
+    for (size_t i = 0; i < cap1; ++i) T.host(t_neg)[i] = -1.0f;  // the overload has no stereo test
+    TrackFrameDev* hf = T.host(t_frames);
     size_t q = 0;
     for (int k = 0; k < n_hyps; ++k) {
         const tc2li_reloc_hypothesis& Hy = hyps[k];
         const int n = o->last_kp_cnt[2 * Hy.frame_index], key_off = o->last_kp_off[2 * Hy.frame_index];
-        stage_keyframe_points(pts, h, q, Hy);
-        memcpy(h + o_match + 4 * (size_t)k * cap1, Hy.match, 4 * (size_t)n);
-        for (int i = 0; i < n; ++i) h[o_inl + (size_t)k * cap1 + i] = Hy.inlier[i] ? 1 : 0;
+        stage_keyframe_points(T, pts, q, Hy);
+        T.io.put(t_match, (size_t)k * cap1, Hy.match, n);
+        for (int i = 0; i < n; ++i) T.host(t_inl)[(size_t)k * cap1 + i] = Hy.inlier[i] ? 1 : 0;
         TrackFrameDev& F = hf[k];
         memset(&F, 0, sizeof(F));
         memcpy(F.pose7, Hy.pose7, 7 * sizeof(float));
         F.th = 10.0f; F.q_off = (int32_t)q; F.n_q = Hy.n_points; F.key_off = key_off; F.n_keys = n; F.slot = -1;
         const float B[4] = {0.0f, (float)o->cur_w, 0.0f, (float)o->cur_h};
-        memcpy(h + o_bounds + 16 * (size_t)k, B, 16);
-        hm[k] = MatchFrameDev{o->d_mkeys.p + key_off, o->d_desc.p + (size_t)key_off * 32, reinterpret_cast<const float*>(d + o_neg), d_occ + (size_t)k * cap1,
-                              S.d_queries.p + q, n, Hy.n_points, (int32_t)q, 0, B[0], B[1], B[2], B[3]};
-        reinterpret_cast<int32_t*>(h + o_kbase)[k] = G.cell_start ? key_off : (int32_t)(k * cap1);
-        reinterpret_cast<int32_t*>(h + o_foh)[k] = Hy.frame_index;
+        T.io.put(t_bounds, k, B, 1);
+        T.host(t_mframes)[k] = MatchFrameDev{o->d_mkeys.p + key_off, o->d_desc.p + (size_t)key_off * 32, T.dev(t_neg), W(t_occ) + (size_t)k * cap1,
+                                             S.d_queries.p + q, n, Hy.n_points, (int32_t)q, 0, B[0], B[1], B[2], B[3]};
+        T.host(t_kbase)[k] = G.cell_start ? key_off : (int32_t)(k * cap1);
+        T.host(t_foh)[k] = Hy.frame_index;
         q += Hy.n_points;
     }
     const TrackConst C = track_const(o, cam, 0.f, capacity);
-    TC2LI_HIP_CHECK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_frames.p, hf, nh * sizeof(TrackFrameDev), hipMemcpyHostToDevice, st));
-    int32_t* ip = w.d_i32.p;
-    int32_t *d_nm = S.d_nmatch.p, *d_active = ip, *d_status = d_active + nh, *d_ngood = d_status + nh, *d_inl = d_ngood + nh, *d_nadd = d_inl + nh,
-            *d_assign = d_nadd + 2 * nh, *d_edge_kp = d_assign + ne;
-    double *d_Xw = w.d_f64.p, *d_poses = d_Xw + 3 * ne, *d_stage_poses = d_poses + 7 * nh, *d_chi2 = d_stage_poses + 21 * nh;
-    const KeyframePointArrays A = pts.arrays(d, d_found);
+    TC2LI_HIP_CHECK(T.upload(st));
+    TrackFrameDev* d_frames = T.dev(t_frames);  // the ladder rewrites pose, window and slot on the device; the host records stay as sent
+    int32_t *d_nm = S.d_nmatch.p, *d_assign = W(t_assign);
+    const KeyframePointArrays A = keyframe_point_arrays(T, pts, W(t_found));
     RelocLadder L{};
-    L.n_hyps = n_hyps; L.capacity = (int)cap1; L.frames = w.d_frames.p; L.frame_of_hyp = reinterpret_cast<const int32_t*>(d + o_foh);
-    L.keys = o->d_mkeys.p; L.u_right = reinterpret_cast<const float*>(d + o_ur);
+    L.n_hyps = n_hyps; L.capacity = (int)cap1; L.frames = d_frames; L.frame_of_hyp = T.dev(t_foh);
+    L.keys = o->d_mkeys.p; L.u_right = T.dev(t_ur);
     for (int l = 0; l < n_levels; ++l) L.inv_sigma2[l] = o->inv_sigma2[l];
-    L.kf_Xw = A.Xw; L.in_match = reinterpret_cast<const int32_t*>(d + o_match); L.in_inlier = d + o_inl;
-    L.found = d_found; L.occupied = d_occ; L.assign = d_assign; L.outlier_of_key = d_outl_key; L.n_matches = d_nm; L.active = d_active;
-    L.status = d_status; L.n_good = d_ngood; L.n_additional = d_nadd; L.stage_poses = d_stage_poses;
-    L.probs = w.d_probs.p; L.edges = w.d_edges.p; L.Xw = d_Xw; L.edge_kp = d_edge_kp; L.poses = d_poses; L.outlier = d_outl; L.inliers = d_inl;
-    CameraD cd;
-    memcpy(&cd, cam, sizeof(cd));
+    L.kf_Xw = A.Xw; L.in_match = T.dev(t_match); L.in_inlier = T.dev(t_inl);
+    L.found = W(t_found); L.occupied = W(t_occ); L.assign = d_assign; L.outlier_of_key = W(t_outl_key); L.n_matches = d_nm; L.active = W(t_active);
+    L.status = W(t_status); L.n_good = W(t_ngood); L.n_additional = W(t_nadd); L.stage_poses = W(t_stage_poses);
+    L.probs = W(pose.probs); L.edges = W(pose.edges); L.Xw = W(pose.Xw); L.edge_kp = W(pose.edge_kp); L.poses = W(pose.poses);
+    L.outlier = W(pose.outlier); L.inliers = W(pose.inliers);
     // ORBmatcher matcher2(0.9, true).SearchByProjection(mCurrentFrame, pKF, sFound, th, orb_dist) for the hypotheses k_reloc_ladder_after chose
     auto search = [&](int orb_dist) -> int {
         if (total_q == 0) return TC2LI_OK;
         TC2LI_HIP_CHECK(hipMemsetAsync(S.amb_count(), 0, sizeof(int32_t), st));
-        launch_track_queries_keyframe(w.d_frames.p, n_hyps, reinterpret_cast<const float4*>(d + o_bounds), C, A, total_q, S.d_queries.p, S.d_query_frame.p,
+        launch_track_queries_keyframe(d_frames, n_hyps, T.dev(t_bounds), C, A, total_q, S.d_queries.p, S.d_query_frame.p,
                                       S.d_match.p, S.amb_count(), S.d_amb_ids.p, S.d_amb_ratio.p, S.d_amb_r.p, st);
         if (int rc = resolve_ambiguous_levels(S, C, launch_track_patch_levels_keyframe, st)) return rc;
-        const SearchPass P{reinterpret_cast<const MatchFrameDev*>(d + o_mframes), reinterpret_cast<const int32_t*>(d + o_kbase), n_hyps, total_q, hf, nullptr,
+        const SearchPass P{T.dev(t_mframes), T.dev(t_kbase), n_hyps, total_q, hf, nullptr,
                            0, 0.0f, orb_dist, G.cell_start, G.items, G.cell_start ? L.frame_of_hyp : nullptr};
         if (int rc = projection_search(S, P, st)) return rc;  // the follow-up waits for the overflow decision: assign scatters
-        launch_track_count(w.d_frames.p, nullptr, n_hyps, S.d_queries.p, o->d_angles.p, 1, S.d_match.p, d_nm, st);
-        launch_track_assign_keyframe(w.d_frames.p, n_hyps, (int)cap1, total_q, S.d_match.p, d_assign, st);
+        launch_track_count(d_frames, nullptr, n_hyps, S.d_queries.p, o->d_angles.p, 1, S.d_match.p, d_nm, st);
+        launch_track_assign_keyframe(d_frames, n_hyps, (int)cap1, total_q, S.d_match.p, d_assign, st);
         TC2LI_HIP_CHECK(hipGetLastError());
         return TC2LI_OK;
     };
     launch_reloc_ladder_init(L, st);
     for (int stage = 0; stage < 3; ++stage) {
         launch_reloc_ladder_edges(L, stage, st);
-        launch_pose_optimization(w.d_probs.p, n_hyps, d_Xw, w.d_edges.p, cd, d_poses, d_outl, d_chi2, d_inl, (int)cap1, st);
+        pose.launch(T, n_hyps, cam, (int)cap1, st);
         launch_reloc_ladder_after(L, stage, st);
         TC2LI_HIP_CHECK(hipGetLastError());
         if (stage < 2) { if (int rc = search(stage == 0 ? 100 : 64)) return rc; }
     }
-    TC2LI_HIP_CHECK(hipMemcpyAsync(status, d_status, nh * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(n_good, d_ngood, nh * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(n_additional, d_nadd, 2 * nh * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(poses7, d_stage_poses, 21 * nh * sizeof(double), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(status, L.status, nh * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(n_good, L.n_good, nh * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(n_additional, L.n_additional, 2 * nh * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(poses7, L.stage_poses, 21 * nh * sizeof(double), hipMemcpyDeviceToHost, st));
     if (capacity > 0) {
         TC2LI_HIP_CHECK(hipMemcpyAsync(kf_keypoint_of_keypoint, d_assign, ne * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        TC2LI_HIP_CHECK(hipMemcpyAsync(outlier, d_outl_key, ne, hipMemcpyDeviceToHost, st));
+        TC2LI_HIP_CHECK(hipMemcpyAsync(outlier, L.outlier_of_key, ne, hipMemcpyDeviceToHost, st));
     }
     TC2LI_HIP_CHECK(stream_wait_blocking(st));
     return n_hyps;

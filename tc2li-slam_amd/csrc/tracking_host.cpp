@@ -15,6 +15,7 @@
 #include "common.hpp"
 #include "matcher_device.hpp"
 #include "orb_handle.hpp"
+#include "packed_batch.hpp"
 #include "pose_opt_device.hpp"
 #include "projection_search.hpp"
 #include "tracking_device.hpp"
@@ -24,20 +25,9 @@ using namespace tc2li;
 namespace {
 
 struct TrackWs {
-    PinnedBuf<uint8_t> h_stage;
-    DevBuf<uint8_t> d_stage;
-    PinnedBuf<TrackFrameDev> h_frames;
-    DevBuf<TrackFrameDev> d_frames;
-    PinnedBuf<MatchFrameDev> h_mframes;
-    DevBuf<MatchFrameDev> d_mframes;
-    PinnedBuf<int32_t> h_pass, h_key_base, h_nmatch;
-    DevBuf<int32_t> d_pass, d_key_base;
+    PackedBuffers b;             // the call's upload block and its device-only tables
+    PinnedBuf<int32_t> h_nmatch;
     SearchScratch s;
-    DevBuf<PoseProblem> d_probs;
-    DevBuf<BaEdge> d_edges;
-    DevBuf<double> d_Xw, d_poses, d_chi2;
-    DevBuf<uint8_t> d_outlier, d_occ, d_outlier_key;
-    DevBuf<int32_t> d_edge_kp, d_inliers, d_ninl, d_of_key;
 };
 // one work space per host thread: TrackWithMotionModel and TrackLocalMap of different batches run side by side
 TrackWs& tws() { static thread_local TrackWs w; return w; }
@@ -45,42 +35,49 @@ TrackWs& tws() { static thread_local TrackWs w; return w; }
 // The searches of one call: SearchByProjection for the frames of a pass, the rotation filter and the match counts.
 struct Pass {
     TrackWs& w;
+    PackedTransfer& T;
     tc2li_orb* o;
     int n_frames, total_q, capacity;
-    const float* d_ur;       // [n_frames][capacity]
-    const uint8_t* d_occ;    // [n_frames][capacity] or NULL
     int mode;
     float nn_ratio;
     bool check_orientation;
     hipStream_t st;
+    const float* d_ur = nullptr;     // [n_frames][capacity]
+    const uint8_t* d_occ = nullptr;  // [n_frames][capacity] or NULL
+    Table<TrackFrameDev> frames;     // [n_frames], the last table of the block's one upload
+    Table<MatchFrameDev> mframes;    // [n_pass], this and the next two: rewritten and uploaded per pass
+    Table<int32_t> key_base, pass;
 
+    // after the caller's tables: the passes' own, and every buffer of the call, once; the first pass holds every frame
     int prepare() {
-        TC2LI_HIP_CHECK(w.d_mframes.ensure(n_frames)); TC2LI_HIP_CHECK(w.h_mframes.ensure(n_frames));
-        TC2LI_HIP_CHECK(w.d_pass.ensure(n_frames)); TC2LI_HIP_CHECK(w.h_pass.ensure(n_frames));
-        TC2LI_HIP_CHECK(w.d_key_base.ensure(n_frames)); TC2LI_HIP_CHECK(w.h_key_base.ensure(n_frames));
-        TC2LI_HIP_CHECK(w.h_nmatch.ensure(n_frames));
-        return w.s.ensure(n_frames, total_q, capacity);
+        frames = T.io.take<TrackFrameDev>(n_frames);
+        T.outputs_begin();
+        mframes = T.io.take<MatchFrameDev>(n_frames); key_base = T.io.take<int32_t>(n_frames); pass = T.io.take<int32_t>(n_frames);
+        TC2LI_HIP_CHECK(T.ensure(w.b)); TC2LI_HIP_CHECK(w.h_nmatch.ensure(n_frames));
+        if (int rc = w.s.ensure(n_frames, total_q, capacity)) return rc;
+        for (int f = 0; f < n_frames; ++f) T.host(pass)[f] = f;
+        return TC2LI_OK;
     }
-    // frames of the pass are in w.h_pass[0 .. n_pass); their TrackFrameDev (slot set) are on the device already.  Returns with the
+    // frames of the pass are in host(pass)[0 .. n_pass); their TrackFrameDev (slot set) are on the device already.  Returns with the
     // stream drained and w.h_nmatch holding every frame's count (the pass rewrote its own): the count rides behind the list form.
     int search(int n_pass) {
-        FrameGrids G;  // the handle's grids: frame k of the pass reads row h_pass[k], its items start where its keys start
+        FrameGrids G;  // the handle's grids: frame k of the pass reads row pass[k], its items start where its keys start
         if (int rc = frame_grids(o, st, &G)) return rc;
+        const TrackFrameDev* h_frames = T.host(frames);
+        const int32_t* h_pass = T.host(pass);
         for (int k = 0; k < n_pass; ++k) {
-            const int f = w.h_pass.p[k];
-            const TrackFrameDev& F = w.h_frames.p[f];
-            w.h_mframes.p[k] = MatchFrameDev{o->d_mkeys.p + F.key_off, o->d_desc.p + (size_t)F.key_off * 32, d_ur + (size_t)f * capacity,
-                                             d_occ ? d_occ + (size_t)f * capacity : nullptr, w.s.d_queries.p + F.q_off, F.n_keys, F.n_q, F.q_off, 0,
-                                             0.0f, (float)o->cur_w, 0.0f, (float)o->cur_h};
-            w.h_key_base.p[k] = G.cell_start ? F.key_off : f * capacity;
+            const int f = h_pass[k];
+            const TrackFrameDev& F = h_frames[f];
+            T.host(mframes)[k] = MatchFrameDev{o->d_mkeys.p + F.key_off, o->d_desc.p + (size_t)F.key_off * 32, d_ur + (size_t)f * capacity,
+                                               d_occ ? d_occ + (size_t)f * capacity : nullptr, w.s.d_queries.p + F.q_off, F.n_keys, F.n_q, F.q_off, 0,
+                                               0.0f, (float)o->cur_w, 0.0f, (float)o->cur_h};
+            T.host(key_base)[k] = G.cell_start ? F.key_off : f * capacity;
         }
-        TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_mframes.p, w.h_mframes.p, n_pass * sizeof(MatchFrameDev), hipMemcpyHostToDevice, st));
-        TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_key_base.p, w.h_key_base.p, n_pass * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_pass.p, w.h_pass.p, n_pass * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        const SearchPass P{w.d_mframes.p, w.d_key_base.p, n_pass, total_q, w.h_frames.p, w.h_pass.p, mode, nn_ratio, kMatchThHigh,
-                           G.cell_start, G.items, G.cell_start ? w.d_pass.p : nullptr};
+        TC2LI_HIP_CHECK(T.upload(mframes, 0, n_pass, st)); TC2LI_HIP_CHECK(T.upload(key_base, 0, n_pass, st)); TC2LI_HIP_CHECK(T.upload(pass, 0, n_pass, st));
+        const SearchPass P{T.dev(mframes), T.dev(key_base), n_pass, total_q, h_frames, h_pass, mode, nn_ratio, kMatchThHigh,
+                           G.cell_start, G.items, G.cell_start ? T.dev(pass) : nullptr};
         return projection_search(w.s, P, st, [&]() -> int {
-            launch_track_count(w.d_frames.p, w.d_pass.p, n_pass, w.s.d_queries.p, o->d_angles.p, check_orientation ? 1 : 0, w.s.d_match.p, w.s.d_nmatch.p, st);
+            launch_track_count(T.dev(frames), T.dev(pass), n_pass, w.s.d_queries.p, o->d_angles.p, check_orientation ? 1 : 0, w.s.d_match.p, w.s.d_nmatch.p, st);
             TC2LI_HIP_CHECK(hipGetLastError());
             TC2LI_HIP_CHECK(hipMemcpyAsync(w.h_nmatch.p, w.s.d_nmatch.p, n_frames * sizeof(int32_t), hipMemcpyDeviceToHost, st));
             return TC2LI_OK;
@@ -112,10 +109,10 @@ extern "C" int tc2li_track_motion_model_batch(tc2li_orb* o, int n_frames, const 
     const TrackConst C = track_const(o, cam, b, capacity);
     const int L = C.n_levels;
 
-    TC2LI_HIP_CHECK(w.h_frames.ensure(n_frames)); TC2LI_HIP_CHECK(w.d_frames.ensure(n_frames));
+    std::vector<TrackFrameDev> frames(n_frames);
     int total_q = 0;
     for (int f = 0; f < n_frames; ++f) {
-        TrackFrameDev& F = w.h_frames.p[f];
+        TrackFrameDev& F = frames[f];
         memset(&F, 0, sizeof(F));
         F.key_off = o->last_kp_off[2 * f];
         F.n_keys = o->last_kp_cnt[2 * f];
@@ -139,45 +136,46 @@ extern "C" int tc2li_track_motion_model_batch(tc2li_orb* o, int n_frames, const 
         for (int c = 0; c < 3; ++c) tlc[c] += F.last_pose7[4 + c];
         F.forward = tlc[2] > b; F.backward = -tlc[2] > b;
     }
-    // ---- one staging block: the last frames' points (structure of arrays) and mvuRight of the current frames ----
-    const size_t nq = (size_t)std::max(total_q, 1), nk = (size_t)n_frames * std::max(capacity, 1);
-    const size_t o_flags = 0, o_Xw = up256(o_flags + nq), o_ang = up256(o_Xw + 12 * nq), o_oct = up256(o_ang + 4 * nq), o_desc = up256(o_oct + 4 * nq),
-                 o_ur = up256(o_desc + 32 * nq), stage_bytes = up256(o_ur + 4 * nk);
-    TC2LI_HIP_CHECK(w.h_stage.ensure(stage_bytes)); TC2LI_HIP_CHECK(w.d_stage.ensure(stage_bytes));
+    // ---- the upload block: the last frames' points (structure of arrays), mvuRight of the current frames, the frame records; the
+    // device-only tables: the keypoints' map points, the inlier counts, PoseOptimization's ----
+    const size_t nq = (size_t)std::max(total_q, 1), nk = (size_t)n_frames * std::max(capacity, 1), ne = nk;
+    PackedTransfer T;
+    const auto t_flags = T.io.take<uint8_t>(nq);
+    const auto t_Xw = T.io.take<float>(3 * nq), t_ang = T.io.take<float>(nq), t_ur = T.io.take<float>(nk);
+    const auto t_oct = T.io.take<int32_t>(nq);
+    const auto t_desc = T.io.take<OrbDescriptor>(nq);
+    const auto t_of_key = T.work.take<int32_t>(ne), t_ninl = T.work.take<int32_t>(n_frames);
+    const PoseTail pose(T.work, n_frames, ne);
+    Pass pass{w, T, o, n_frames, total_q, capacity, 0, 0.9f, true, st};
+    int rc = pass.prepare();
+    if (rc != TC2LI_OK) return rc;
+    T.io.put(pass.frames, 0, frames.data(), n_frames);
+    TrackFrameDev* const h_frames = T.host(pass.frames);
     std::vector<int> bad(n_frames, 0);
     tracking_pool().parallel_for(n_frames, [&](int f) {
-        const TrackFrameDev& F = w.h_frames.p[f];
+        const TrackFrameDev& F = h_frames[f];
         const tc2li_last_frame& lf = last[f];
-        uint8_t* hs = w.h_stage.p;
-        uint8_t* fl = hs + o_flags + F.q_off;
-        float* ang = reinterpret_cast<float*>(hs + o_ang) + F.q_off;
-        int32_t* oct = reinterpret_cast<int32_t*>(hs + o_oct) + F.q_off;
+        uint8_t* fl = T.host(t_flags) + F.q_off;
+        float* ang = T.host(t_ang) + F.q_off;
+        int32_t* oct = T.host(t_oct) + F.q_off;
         for (int i = 0; i < lf.n; ++i) {
             fl[i] = (uint8_t)((lf.has_point[i] ? 1 : 0) | (lf.outlier[i] ? 2 : 0));
             ang[i] = lf.keys[i].angle;
             oct[i] = lf.keys[i].octave;
             if (fl[i] == 1 && (oct[i] < 0 || oct[i] >= L)) bad[f] = 1;
         }
-        if (lf.n) {
-            memcpy(hs + o_Xw + 12 * (size_t)F.q_off, lf.Xw, 12 * (size_t)lf.n);
-            memcpy(hs + o_desc + 32 * (size_t)F.q_off, lf.descriptors, 32 * (size_t)lf.n);
-        }
-        memcpy(hs + o_ur + 4 * (size_t)f * capacity, u_right + (size_t)f * capacity, 4 * (size_t)F.n_keys);
+        T.io.put(t_Xw, 3 * (size_t)F.q_off, lf.Xw, 3 * (size_t)lf.n);
+        T.io.put(t_desc, F.q_off, lf.descriptors, lf.n);
+        T.io.put(t_ur, (size_t)f * capacity, u_right + (size_t)f * capacity, F.n_keys);
     });
     for (int f = 0; f < n_frames; ++f) if (bad[f]) { set_error("octave out of range"); return TC2LI_ERR_INVALID; }
     tm[0] = now() - t0; t0 = now();
-    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_stage.p, w.h_stage.p, stage_bytes, hipMemcpyHostToDevice, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_frames.p, w.h_frames.p, n_frames * sizeof(TrackFrameDev), hipMemcpyHostToDevice, st));
-    const uint8_t* ds = w.d_stage.p;
-    const LastFrameArrays A{ds + o_flags, reinterpret_cast<const float*>(ds + o_Xw), reinterpret_cast<const float*>(ds + o_ang),
-                            reinterpret_cast<const int32_t*>(ds + o_oct), ds + o_desc};
-    const float* d_ur = reinterpret_cast<const float*>(ds + o_ur);
-    Pass pass{w, o, n_frames, total_q, capacity, d_ur, nullptr, 0, 0.9f, true, st};
-    int rc = pass.prepare();
-    if (rc != TC2LI_OK) return rc;
-    for (int f = 0; f < n_frames; ++f) w.h_pass.p[f] = f;
+    TC2LI_HIP_CHECK(T.upload(st));
+    const TrackFrameDev* d_frames = T.dev(pass.frames);
+    const LastFrameArrays A{T.dev(t_flags), T.dev(t_Xw), T.dev(t_ang), T.dev(t_oct), T.dev(t_desc)->b};
+    const float* d_ur = pass.d_ur = T.dev(t_ur);
     if (total_q > 0) {
-        launch_track_queries_last(w.d_frames.p, n_frames, C, A, total_q, S.d_queries.p, S.d_query_frame.p, S.d_match.p, st);
+        launch_track_queries_last(d_frames, n_frames, C, A, total_q, S.d_queries.p, S.d_query_frame.p, S.d_match.p, st);
         rc = pass.search(n_frames);
         if (rc != TC2LI_OK) return rc;
         memcpy(n_matches, w.h_nmatch.p, n_frames * sizeof(int32_t));
@@ -189,34 +187,29 @@ extern "C" int tc2li_track_motion_model_batch(tc2li_orb* o, int n_frames, const 
     // fewer than 20 matches: wider window (Tracking.cc:2774-2783), those frames only
     int n_retry = 0;
     for (int f = 0; f < n_frames; ++f) {
-        TrackFrameDev& F = w.h_frames.p[f];
-        if (n_matches[f] < 20 && F.n_q > 0) { F.slot = n_retry; F.th = 2 * th; w.h_pass.p[n_retry++] = f; }
+        TrackFrameDev& F = h_frames[f];
+        if (n_matches[f] < 20 && F.n_q > 0) { F.slot = n_retry; F.th = 2 * th; T.host(pass.pass)[n_retry++] = f; }
         else F.slot = -1;
     }
     if (n_retry > 0) {
-        TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_frames.p, w.h_frames.p, n_frames * sizeof(TrackFrameDev), hipMemcpyHostToDevice, st));
-        launch_track_queries_last(w.d_frames.p, n_frames, C, A, total_q, S.d_queries.p, S.d_query_frame.p, S.d_match.p, st);
+        TC2LI_HIP_CHECK(T.upload(pass.frames, 0, n_frames, st));
+        launch_track_queries_last(d_frames, n_frames, C, A, total_q, S.d_queries.p, S.d_query_frame.p, S.d_match.p, st);
         rc = pass.search(n_retry);
         if (rc != TC2LI_OK) return rc;
         memcpy(n_matches, w.h_nmatch.p, n_frames * sizeof(int32_t));  // d_nmatch holds every frame: the pass rewrote its own
     }
     tm[2] = now() - t0; t0 = now();
     // ---- Optimizer::PoseOptimization: one edge per keypoint that now holds a map point, in keypoint order ----
-    const size_t ne = (size_t)n_frames * std::max(capacity, 1);
-    TC2LI_HIP_CHECK(w.d_of_key.ensure(ne)); TC2LI_HIP_CHECK(w.d_probs.ensure(n_frames)); TC2LI_HIP_CHECK(w.d_edges.ensure(ne)); TC2LI_HIP_CHECK(w.d_Xw.ensure(3 * ne));
-    TC2LI_HIP_CHECK(w.d_edge_kp.ensure(ne)); TC2LI_HIP_CHECK(w.d_poses.ensure(7 * (size_t)n_frames)); TC2LI_HIP_CHECK(w.d_outlier.ensure(ne));
-    TC2LI_HIP_CHECK(w.d_chi2.ensure(ne)); TC2LI_HIP_CHECK(w.d_inliers.ensure(n_frames)); TC2LI_HIP_CHECK(w.d_ninl.ensure(n_frames));
-    launch_track_edges_last(w.d_frames.p, n_frames, C, o->d_mkeys.p, d_ur, S.d_match.p, S.d_nmatch.p, A.Xw, w.d_of_key.p, w.d_probs.p, w.d_edges.p, w.d_Xw.p,
-                            w.d_edge_kp.p, w.d_poses.p, st);
-    CameraD cd;
-    memcpy(&cd, cam, sizeof(cd));
-    launch_pose_optimization(w.d_probs.p, n_frames, w.d_Xw.p, w.d_edges.p, cd, w.d_poses.p, w.d_outlier.p, w.d_chi2.p, w.d_inliers.p, capacity, st);
-    launch_track_finish_last(w.d_frames.p, n_frames, capacity, S.d_nmatch.p, w.d_probs.p, w.d_outlier.p, w.d_edge_kp.p, w.d_inliers.p, w.d_of_key.p, w.d_poses.p,
-                             w.d_ninl.p, st);
+    auto W = [&](auto t) { return T.dev_work(t); };
+    launch_track_edges_last(d_frames, n_frames, C, o->d_mkeys.p, d_ur, S.d_match.p, S.d_nmatch.p, A.Xw, W(t_of_key), W(pose.probs), W(pose.edges), W(pose.Xw),
+                            W(pose.edge_kp), W(pose.poses), st);
+    pose.launch(T, n_frames, cam, capacity, st);
+    launch_track_finish_last(d_frames, n_frames, capacity, S.d_nmatch.p, W(pose.probs), W(pose.outlier), W(pose.edge_kp), W(pose.inliers), W(t_of_key),
+                             W(pose.poses), W(t_ninl), st);
     TC2LI_HIP_CHECK(hipGetLastError());
-    TC2LI_HIP_CHECK(hipMemcpyAsync(map_point_of_keypoint, w.d_of_key.p, ne * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(poses7, w.d_poses.p, 7 * (size_t)n_frames * sizeof(double), hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(n_inliers, w.d_ninl.p, n_frames * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(map_point_of_keypoint, W(t_of_key), ne * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(poses7, W(pose.poses), 7 * (size_t)n_frames * sizeof(double), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(n_inliers, W(t_ninl), n_frames * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     TC2LI_HIP_CHECK(stream_wait_blocking(st));
     tm[3] = now() - t0;
     if (kTiming) fprintf(stderr, "track timing ms: stage %.3f search %.3f retry %.3f edges+pose-opt+results %.3f\n", tm[0], tm[1], tm[2], tm[3]);
@@ -255,9 +248,9 @@ static int track_local_map_impl(tc2li_orb* o, int n_frames, const tc2li_keypoint
     TrackConst C = track_const(o, cam, 0.f, capacity);
     C.far_points = far_points; C.th_far = th_far_points; C.view_cos_limit = 0.5f;
 
-    TC2LI_HIP_CHECK(w.h_frames.ensure(n_frames)); TC2LI_HIP_CHECK(w.d_frames.ensure(n_frames));
+    std::vector<TrackFrameDev> frames(n_frames);
     for (int f = 0; f < n_frames; ++f) {
-        TrackFrameDev& F = w.h_frames.p[f];
+        TrackFrameDev& F = frames[f];
         memset(&F, 0, sizeof(F));
         F.key_off = o->last_kp_off[2 * f];
         F.n_keys = o->last_kp_cnt[2 * f];
@@ -268,40 +261,45 @@ static int track_local_map_impl(tc2li_orb* o, int n_frames, const tc2li_keypoint
         memcpy(F.pose7, poses7 + 7 * (size_t)f, 7 * sizeof(float));
         F.th = th; F.slot = f;
     }
-    // ---- one staging block: the local points, mvuRight, the held flags and positions ----
-    const size_t nq = (size_t)std::max(total_q, 1), nk = (size_t)n_frames * std::max(capacity, 1);
-    const size_t o_pts = 0, o_ur = up256(o_pts + sizeof(LocalPointDev) * nq), o_held = up256(o_ur + 4 * nk), o_hx = up256(o_held + nk),
-                 stage_bytes = up256(o_hx + 12 * nk);
-    TC2LI_HIP_CHECK(w.h_stage.ensure(stage_bytes)); TC2LI_HIP_CHECK(w.d_stage.ensure(stage_bytes));
+    // ---- the upload block: the local points, mvuRight, the held flags and positions, the frame records; the device-only tables: the
+    // occupied flags, the keypoints' local points and outlier flags, the inlier counts, PoseOptimization's ----
+    const size_t nq = (size_t)std::max(total_q, 1), nk = (size_t)n_frames * std::max(capacity, 1), ne = nk;
+    PackedTransfer T;
+    const auto t_pts = T.io.take<LocalPointDev>(nq);
+    const auto t_ur = T.io.take<float>(nk), t_hx = T.io.take<float>(3 * nk);
+    const auto t_held = T.io.take<uint8_t>(nk);
+    const auto t_occ = T.work.take<uint8_t>(nk), t_outlier_key = T.work.take<uint8_t>(ne);
+    const auto t_of_key = T.work.take<int32_t>(ne), t_ninl = T.work.take<int32_t>(n_frames);
+    const PoseTail pose(T.work, n_frames, ne);
+    Pass pass{w, T, o, n_frames, total_q, capacity, 1, 0.8f, false, st};
+    int rc = pass.prepare();
+    if (rc != TC2LI_OK) return rc;
+    T.io.put(pass.frames, 0, frames.data(), n_frames);
     {
         // the callers' arrays are contiguous: copied in 1 MiB pieces by the pool
         struct Piece { uint8_t* dst; const uint8_t* src; size_t n; };
         std::vector<Piece> pieces;
-        auto add = [&](size_t off, const void* src, size_t bytes) {
+        auto add = [&](auto t, const void* src, size_t count) {
+            const size_t bytes = count * sizeof(*T.host(t));
             for (size_t at = 0; at < bytes; at += (size_t)1 << 20)
-                pieces.push_back(Piece{w.h_stage.p + off + at, static_cast<const uint8_t*>(src) + at, std::min((size_t)1 << 20, bytes - at)});
+                pieces.push_back(Piece{(uint8_t*)T.host(t) + at, static_cast<const uint8_t*>(src) + at, std::min((size_t)1 << 20, bytes - at)});
         };
-        if (total_q) add(o_pts, local_points, sizeof(LocalPointDev) * (size_t)total_q);
-        add(o_ur, u_right, 4 * nk); add(o_held, held, nk); add(o_hx, held_Xw, 12 * nk);
+        add(t_pts, local_points, total_q);
+        add(t_ur, u_right, nk); add(t_held, held, nk); add(t_hx, held_Xw, 3 * nk);
         tracking_pool().parallel_for((int)pieces.size(), [&](int k) { memcpy(pieces[k].dst, pieces[k].src, pieces[k].n); });
     }
     tm[0] = now() - t0; t0 = now();
-    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_stage.p, w.h_stage.p, stage_bytes, hipMemcpyHostToDevice, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_frames.p, w.h_frames.p, n_frames * sizeof(TrackFrameDev), hipMemcpyHostToDevice, st));
-    const uint8_t* ds = w.d_stage.p;
-    const LocalPointDev* d_pts = reinterpret_cast<const LocalPointDev*>(ds + o_pts);
-    const float* d_ur = reinterpret_cast<const float*>(ds + o_ur);
-    const uint8_t* d_held = ds + o_held;
-    const float* d_hx = reinterpret_cast<const float*>(ds + o_hx);
-    TC2LI_HIP_CHECK(w.d_occ.ensure(nk));
-    Pass pass{w, o, n_frames, total_q, capacity, d_ur, w.d_occ.p, 1, 0.8f, false, st};
-    int rc = pass.prepare();
-    if (rc != TC2LI_OK) return rc;
-    for (int f = 0; f < n_frames; ++f) w.h_pass.p[f] = f;
-    launch_track_occupied(d_held, nk, w.d_occ.p, st);
+    TC2LI_HIP_CHECK(T.upload(st));
+    auto W = [&](auto t) { return T.dev_work(t); };
+    const TrackFrameDev* d_frames = T.dev(pass.frames);
+    const LocalPointDev* d_pts = T.dev(t_pts);
+    const float *d_ur = T.dev(t_ur), *d_hx = T.dev(t_hx);
+    const uint8_t* d_held = T.dev(t_held);
+    pass.d_ur = d_ur; pass.d_occ = W(t_occ);
+    launch_track_occupied(d_held, nk, W(t_occ), st);
     if (total_q > 0) {
         TC2LI_HIP_CHECK(hipMemsetAsync(S.amb_count(), 0, sizeof(int32_t), st));
-        launch_track_queries_local(w.d_frames.p, n_frames, C, d_pts, total_q, S.d_queries.p, S.d_query_frame.p, S.d_match.p, S.amb_count(), S.d_amb_ids.p,
+        launch_track_queries_local(d_frames, n_frames, C, d_pts, total_q, S.d_queries.p, S.d_query_frame.p, S.d_match.p, S.amb_count(), S.d_amb_ids.p,
                                    S.d_amb_ratio.p, S.d_amb_r.p, st);
         // MapPoint::PredictScale on a level boundary: the host's logf decides (see k_track_queries_local).  One count comes back; the
         // listed ratios get their level on the host and a patch kernel writes level and window before the search starts.
@@ -316,30 +314,23 @@ static int track_local_map_impl(tc2li_orb* o, int n_frames, const tc2li_keypoint
     }
     tm[2] = now() - t0; t0 = now();
     // ---- Optimizer::PoseOptimization over every map point the frame now holds, in keypoint order ----
-    const size_t ne = nk;
-    TC2LI_HIP_CHECK(w.d_of_key.ensure(ne)); TC2LI_HIP_CHECK(w.d_probs.ensure(n_frames)); TC2LI_HIP_CHECK(w.d_edges.ensure(ne)); TC2LI_HIP_CHECK(w.d_Xw.ensure(3 * ne));
-    TC2LI_HIP_CHECK(w.d_edge_kp.ensure(ne)); TC2LI_HIP_CHECK(w.d_poses.ensure(7 * (size_t)n_frames)); TC2LI_HIP_CHECK(w.d_outlier.ensure(ne));
-    TC2LI_HIP_CHECK(w.d_chi2.ensure(ne)); TC2LI_HIP_CHECK(w.d_inliers.ensure(n_frames)); TC2LI_HIP_CHECK(w.d_ninl.ensure(n_frames));
-    TC2LI_HIP_CHECK(w.d_outlier_key.ensure(ne));
-    launch_track_edges_local(w.d_frames.p, n_frames, C, o->d_mkeys.p, d_ur, S.d_match.p, d_held, d_hx, d_pts, w.d_of_key.p, w.d_probs.p, w.d_edges.p, w.d_Xw.p,
-                             w.d_edge_kp.p, w.d_poses.p, st);
+    launch_track_edges_local(d_frames, n_frames, C, o->d_mkeys.p, d_ur, S.d_match.p, d_held, d_hx, d_pts, W(t_of_key), W(pose.probs), W(pose.edges), W(pose.Xw),
+                             W(pose.edge_kp), W(pose.poses), st);
     if (!optimise) {  // the keypoints' new map points are what the caller wants; the optimisation is the pose-inertial one, elsewhere
         TC2LI_HIP_CHECK(hipGetLastError());
-        TC2LI_HIP_CHECK(hipMemcpyAsync(local_of_keypoint, w.d_of_key.p, ne * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        TC2LI_HIP_CHECK(hipMemcpyAsync(local_of_keypoint, W(t_of_key), ne * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         TC2LI_HIP_CHECK(stream_wait_blocking(st));
         tm[3] = now() - t0;
         if (kTiming) fprintf(stderr, "search-local-points timing ms: stage %.3f queries %.3f search %.3f results %.3f\n", tm[0], tm[1], tm[2], tm[3]);
         return n_frames;
     }
-    CameraD cd;
-    memcpy(&cd, cam, sizeof(cd));
-    launch_pose_optimization(w.d_probs.p, n_frames, w.d_Xw.p, w.d_edges.p, cd, w.d_poses.p, w.d_outlier.p, w.d_chi2.p, w.d_inliers.p, capacity, st);
-    launch_track_finish_local(w.d_frames.p, n_frames, capacity, w.d_probs.p, w.d_outlier.p, w.d_edge_kp.p, d_held, w.d_of_key.p, w.d_outlier_key.p, w.d_ninl.p, st);
+    pose.launch(T, n_frames, cam, capacity, st);
+    launch_track_finish_local(d_frames, n_frames, capacity, W(pose.probs), W(pose.outlier), W(pose.edge_kp), d_held, W(t_of_key), W(t_outlier_key), W(t_ninl), st);
     TC2LI_HIP_CHECK(hipGetLastError());
-    TC2LI_HIP_CHECK(hipMemcpyAsync(local_of_keypoint, w.d_of_key.p, ne * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(outlier, w.d_outlier_key.p, ne, hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(poses7_out, w.d_poses.p, 7 * (size_t)n_frames * sizeof(double), hipMemcpyDeviceToHost, st));
-    TC2LI_HIP_CHECK(hipMemcpyAsync(n_inliers, w.d_ninl.p, n_frames * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(local_of_keypoint, W(t_of_key), ne * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(outlier, W(t_outlier_key), ne, hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(poses7_out, W(pose.poses), 7 * (size_t)n_frames * sizeof(double), hipMemcpyDeviceToHost, st));
+    TC2LI_HIP_CHECK(hipMemcpyAsync(n_inliers, W(t_ninl), n_frames * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     TC2LI_HIP_CHECK(stream_wait_blocking(st));
     tm[3] = now() - t0;
     if (kTiming) fprintf(stderr, "track-local-map timing ms: stage %.3f queries %.3f search %.3f edges+pose-opt+results %.3f\n", tm[0], tm[1], tm[2], tm[3]);

@@ -201,14 +201,13 @@ def test_search_by_bow_rejects_malformed_feature_vectors(pkg, drive, trained):
         assert e.value.code == -2
 
 
-def test_track_reference_keyframe_batch(pkg, oracle, synthetic):
-    """The batch against 'restatement ComputeBoW -> SearchByBoW(0.7, true) -> oracle.pose_optimization -> discard', frames above and below
-    15 matches in one batch."""
-    import torch
+@pytest.fixture(scope="module")
+def reference_scene(pkg, synthetic):
+    """Four frames and their reference keyframes: 0.1 m behind every frame, own extractor, depth from the stereo match; the third keyframe
+    with so few points that the search finds fewer than 15 matches."""
     xs = [0.0, 0.2, 0.4, 0.6]
     bf = np.float32(synthetic.BF); b = np.float32(bf / np.float32(synthetic.FX))
     fx, fy, cx, cy = [np.float32(v) for v in (synthetic.FX, synthetic.FY, synthetic.CX, synthetic.CY)]
-    # reference keyframes: 0.1 m behind every frame, own extractor, depth from the stereo match
     ext_kf, dev_kf, kfs, kcounts = _drive(pkg, synthetic, [x - 0.1 for x in xs], seed=8)
     _, kdepth, _ = pkg.stereo_match_batch(ext_kf, len(xs), float(bf), float(b))
     ext, dev, frames, counts = _drive(pkg, synthetic, xs, seed=8)
@@ -236,16 +235,29 @@ def test_track_reference_keyframe_batch(pkg, oracle, synthetic):
                          fv_offset=kbows[f]["fv_offset"], fv_index=kbows[f]["fv_index"], Xw=Xw,
                          observed=(rng.random(n) < 0.9).astype(np.uint8), last_pose7=last))
     cam5 = np.float32([fx, fy, cx, cy, bf]).astype(np.float64)
-    poses, mp, nm, inl, nmap, braw = pkg.capi.track_reference_keyframe_batch(ext, h, keypoints, u_right, refs, cam5, with_bow=True)
+    return dict(ext=ext, dev=dev, keep=(ext_kf, dev_kf), frames=frames, keypoints=keypoints, u_right=u_right, refs=refs, cam5=cam5, voc=h, voc_ref=voc_ref)
+
+
+def _track_reference(pkg, sc, refs, with_bow=True):
+    """the first len(refs) frames of the scene against `refs`"""
+    F = len(refs)
+    return pkg.capi.track_reference_keyframe_batch(sc["ext"], sc["voc"], sc["keypoints"][:2 * F], sc["u_right"][:F], refs, sc["cam5"], with_bow=with_bow)
+
+
+def _check_track_reference(pkg, oracle, sc, refs, got):
+    """The outputs of _track_reference(sc, refs) against 'restatement ComputeBoW -> SearchByBoW(0.7, true) -> oracle.pose_optimization ->
+    discard' -> per frame the inliers, None below 15 matches."""
+    poses, mp, nm, inl, nmap, braw = got
+    ext, u_right, cam5 = sc["ext"], sc["u_right"], sc["cam5"]
     inv_sigma2 = ext.GetInverseScaleSigmaSquares()
     cap = ext.capacity
     results = []
-    for f, fr in enumerate(frames):
+    for f, r in enumerate(refs):
+        fr = sc["frames"][f]
         n = len(fr["keys"])
-        fb = R.transform(voc_ref, fr["descriptors"], 4)
+        fb = R.transform(sc["voc_ref"], fr["descriptors"], 4)
         assert np.array_equal(braw["fv_node"][f * cap:f * cap + braw["n_nodes"][f]], fb["fv_node"])
         assert braw["bow_value"][f * cap:f * cap + braw["n_words"][f]].tobytes() == fb["bow_value"].tobytes()
-        r = refs[f]
         m, nmatch = R.search_by_bow(dict(angle=r["keys"]["angle"], descriptors=r["descriptors"], has_point=r["has_point"], fv_node=r["fv_node"],
                                          fv_offset=r["fv_offset"], fv_index=r["fv_index"]),
                                     dict(angle=fr["keys"]["angle"], descriptors=fr["descriptors"], **{k: fb[k] for k in ("fv_node", "fv_offset", "fv_index")}),
@@ -269,4 +281,72 @@ def test_track_reference_keyframe_batch(pkg, oracle, synthetic):
         assert nmap[f] == int(sum(r["observed"][want[i]] for i in np.flatnonzero(want >= 0)))
         assert np.allclose(poses[f], pose, rtol=1e-4, atol=1e-6), (poses[f], pose)
         results.append(ninl)
-    assert results[2] is None and sum(x is not None and x > 50 for x in results) >= 2, (nm, inl)
+    return results
+
+
+def test_track_reference_keyframe_batch(pkg, oracle, reference_scene):
+    """The batch against 'restatement ComputeBoW -> SearchByBoW(0.7, true) -> oracle.pose_optimization -> discard', frames above and below
+    15 matches in one batch."""
+    sc = reference_scene
+    got = _track_reference(pkg, sc, sc["refs"])
+    results = _check_track_reference(pkg, oracle, sc, sc["refs"], got)
+    assert results[2] is None and sum(x is not None and x > 50 for x in results) >= 2, (got[2], got[3])
+
+
+# ---- the tables of a call: every one has its place in the call's block, whatever the call before left there -----------------------------
+def _same_outputs(a, b, rows=None):
+    """two results of _track_reference, `rows` of b; the bow arrays only where both have them"""
+    for x, y in zip(a[:5], b[:5]):
+        assert np.array_equal(x, y if rows is None else y[rows])
+    if rows is None and len(a) > 5 and len(b) > 5:
+        for k in a[5]:
+            assert a[5][k].tobytes() == b[5][k].tobytes(), k
+
+
+def test_track_reference_grows_shrinks_and_reuses_its_buffers(pkg, oracle, reference_scene):
+    """Four frames (checked against the reference), the first alone, the four again, through the same per-thread buffers; the call without
+    the bow output; and a reference keyframe without keypoints and without nodes between two ordinary ones."""
+    sc = reference_scene
+    refs = sc["refs"]
+    got = _track_reference(pkg, sc, refs)
+    _check_track_reference(pkg, oracle, sc, refs, got)
+    _same_outputs(_track_reference(pkg, sc, refs[:1]), got, rows=[0])
+    _same_outputs(_track_reference(pkg, sc, refs), got)
+    _same_outputs(_track_reference(pkg, sc, refs, with_bow=False), got)
+    none = dict(refs[1], keys=refs[1]["keys"][:0], descriptors=refs[1]["descriptors"][:0], has_point=refs[1]["has_point"][:0], Xw=refs[1]["Xw"][:0],
+                observed=refs[1]["observed"][:0], fv_node=refs[1]["fv_node"][:0], fv_offset=np.zeros(1, np.int32), fv_index=refs[1]["fv_index"][:0])
+    three = [refs[0], none, refs[2]]
+    got3 = _track_reference(pkg, sc, three)
+    results = _check_track_reference(pkg, oracle, sc, three, got3)
+    assert results[1] is None and got3[2][1] == 0 and results[0] is not None
+    for x, y in zip(got3[:5], got[:5]):
+        assert np.array_equal(x[[0, 2]], y[[0, 2]])
+
+
+def test_search_by_bow_with_an_empty_frame_between_two(pkg, drive, trained):
+    ext, _, frames, counts = drive
+    p, lf, d, w = trained
+    h = pkg.Vocabulary.from_arrays(5, 3, R.L1_NORM, R.TF_IDF, p, lf, d, w)
+    bows = h.transform_orb(ext, counts, levelsup=1)
+    hp = [np.ones(len(fr["keys"]), np.uint8) for fr in frames]
+    nothing = dict(keys=frames[0]["keys"][:0], descriptors=frames[0]["descriptors"][:0])
+    no_bow = dict(fv_node=np.zeros(0, np.int32), fv_offset=np.zeros(1, np.int32), fv_index=np.zeros(0, np.int32))
+    sides = [((frames[0], bows[0]), (frames[1], bows[1])), ((frames[2], bows[2]), (nothing, no_bow)), ((frames[1], bows[1]), (frames[3], bows[3]))]
+    pairs = [dict(keyframe=_view(*kf, has_point=hp[k] if len(kf[0]["keys"]) else None), frame=_view(*fr), nn_ratio=0.7, check_orientation=True)
+             for k, (kf, fr) in zip((0, 2, 1), sides)]
+    match, nm = pkg.search_by_bow_batch(pairs, capacity=ext.capacity)
+    for i, (k, (kf, fr)) in enumerate(zip((0, 2, 1), sides)):
+        m, n = R.search_by_bow(_ref_view(*kf, has_point=hp[k]), _ref_view(*fr), 0.7, True)
+        assert np.array_equal(match[i][:len(m)], m) and (match[i][len(m):] == -1).all() and nm[i] == n, i
+    assert nm[1] == 0 and nm[0] > 20 and nm[2] > 20
+
+
+def test_transform_with_a_frame_of_no_descriptors_between_two(pkg, drive, full_voc):
+    _, _, frames, _ = drive
+    ref, h = full_voc
+    descs = [frames[0]["descriptors"], np.zeros((0, 32), np.uint8), frames[1]["descriptors"][:65]]
+    for n in (3, 1, 3):   # and through the same buffers: three frames, one, three
+        got = h.transform(descs[:n], levelsup=4)
+        for f in range(n):
+            _same(got[f], R.transform(ref, descs[f], 4), "frame %d of %d" % (f, n))
+    assert len(got[1]["bow_word"]) == 0 and got[1]["fv_offset"].tolist() == [0]

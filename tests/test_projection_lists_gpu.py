@@ -14,6 +14,7 @@ import pytest
 
 import reloc_ref as R
 import test_tracking_gpu as T
+import two_callers
 
 pytestmark = pytest.mark.gpu
 
@@ -317,3 +318,62 @@ def test_retry_pass_reads_its_frames_grid_rows(pkg, oracle, synthetic):
         alone = pkg.capi.track_motion_model_batch(ext, 1, kps, sc["u_right"][f:f + 1], pkg.capi.pack_last_frames(sc["lasts"][f:f + 1]),
                                                   sc["preds"][f:f + 1], cam5, sc["b"])
         assert np.array_equal(alone[1][0], mp[f]) and alone[2][0] == nm[f] and alone[3][0] == inl[f] and np.array_equal(alone[0][0], poses[f])
+
+
+# ---- 8. the tables of a call: every one has its place in the call's block, whatever the call before left there -------------------------
+def test_keyframe_overload_grows_shrinks_and_reuses_its_buffers(pkg, oracle, ragged):
+    """On one thread, through the same per-thread buffers: the 17 items, an item of 1 key and 1 query alone, the 17 again."""
+    items, refs = ragged
+    one = _random_item(pkg, np.random.default_rng(12), 1, 1)
+    first, _ = _same(pkg, oracle, items, 10.0, refs)
+    _same(pkg, oracle, [one], 10.0)
+    again, _ = _same(pkg, oracle, items, 10.0, refs)
+    assert np.array_equal(first, again)
+
+
+def test_keyframe_overload_with_empty_and_with_full_tables(pkg, oracle):
+    """A call whose items all have no keys and no points: every table of the block has no row.  And one whose tables are all full and none
+    a multiple of 256 bytes long: 65 keys (capacity 65), 33 points."""
+    rng = np.random.default_rng(13)
+    match, nm = _search(pkg, [_random_item(pkg, rng, 0, 0) for _ in range(3)], 10.0)
+    assert (match == -1).all() and (nm == 0).all()
+    items = [_random_item(pkg, rng, 65, 33) for _ in range(2)]
+    for width in (12, 32, 4, 1):   # MatchKey, descriptor, float / int32, flag: bytes per key and per point
+        assert (65 * width) % 256 and (33 * width) % 256 and (2 * 65 * width) % 256 and (2 * 33 * width) % 256
+    match, _ = _same(pkg, oracle, items, 10.0)
+    assert match.shape == (2, 65)
+    for f, it in enumerate(items):   # the items alone: what a neighbour's table could have overwritten
+        alone, _ = _search(pkg, [it], 10.0)
+        assert np.array_equal(alone[0], match[f])
+
+
+@pytest.fixture(scope="module")
+def one_frame_tracking(pkg, oracle, synthetic):
+    return T.local_map_scenario(pkg, oracle, synthetic, [37], nfeatures=1000, w=640, h=240)
+
+
+def _track_both(pkg, synthetic, sc, streams=(0, 0)):
+    return list(T.run_motion_model(pkg, synthetic, sc, stream=streams[0])) + list(T.run_local_map(pkg, synthetic, sc, 1.0, False, stream=streams[1]))
+
+
+def test_tracking_grows_shrinks_and_reuses_its_buffers(pkg, oracle, synthetic, small_tracking, one_frame_tracking):
+    """Two frames of 1242 x 375, one frame of 640 x 240 on a handle of its own, the two frames again: on one thread, through both entries
+    and the same per-thread buffers.  The first two runs equal the oracle, the third the first."""
+    runs = [_track_both(pkg, synthetic, sc) for sc in (small_tracking, one_frame_tracking, small_tracking)]
+    for sc, got in ((small_tracking, runs[0]), (one_frame_tracking, runs[1])):
+        T.check(pkg, oracle, synthetic, sc, got=got[:4])
+        T.check_local_map(pkg, oracle, synthetic, sc, 1.0, False, got=got[4:], at_least=(20, 20))
+    assert _equal(runs[2], runs[0])
+
+
+def test_two_threads_in_track_local_map(pkg, synthetic, small_tracking, one_frame_tracking):
+    """Two host threads in tc2li_track_local_map_batch at once, each with its own extractor and stream, three calls each: the work spaces
+    are per thread, so each thread's results are the single-threaded ones."""
+    import torch
+    scs = (small_tracking, one_frame_tracking)
+    alone = [T.run_local_map(pkg, synthetic, sc, 1.0, False) for sc in scs]
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    torch.cuda.synchronize()
+    call = lambda k: T.run_local_map(pkg, synthetic, scs[k], 1.0, False, stream=streams[k].cuda_stream)
+    a, b = two_callers.run(call, [0] * 3, [1] * 3)
+    assert all(_equal(got, alone[0]) for got in a) and all(_equal(got, alone[1]) for got in b)

@@ -445,13 +445,14 @@ def _restrict(kf, keep):
     return dict(kf, has_point=hp)
 
 
-def _check_relocalization_refine(pkg, oracle, synthetic, S, dense=False):
+def _check_relocalization_refine(pkg, oracle, synthetic, S, dense=False, batch=None):
     """Hypotheses from SearchByBoW matches (ratio 0.75), a true pose a few centimetres off and only the first k matches flagged as inliers;
     candidates with few points steer the searches, so that the batch reaches every exit of the ladder.  Every stage is checked from the
     device's own pose of the previous stage: searches byte for byte, each PoseOptimization against the oracle on the same edges.  `dense`
     keeps only hypotheses whose candidate has all its points, so that nearly every query of the batch is a live one.  Returns the batch's
     outputs and, per search, (its window candidates over all hypotheses, the queries of the batch): with one pool entry per query a
-    search overflows the pool when it has more candidates than queries."""
+    search overflows the pool when it has more candidates than queries.  batch: a dict that receives the call's inputs (hyps, u_right,
+    cam5) and check(hyps, refs, got), the comparison below for any list of these hypotheses and the outputs of a call on it."""
     sf = S["scale_factors"]
     log_sf = float(np.log(np.float32(sf[1])))
     ext = S["ext"]
@@ -513,32 +514,37 @@ def _check_relocalization_refine(pkg, oracle, synthetic, S, dense=False):
     got = pkg.relocalization_refine_batch(ext, hyps, u_right, cam5)
     seen = set()
     by_hand = {0: [], 1: []}
-    for h, (f, cand, inl) in enumerate(refs):
-        fr = S["frames"][f]
-        N = len(fr["keys"])
-        frame = dict(keys=fr["keys"], descriptors=fr["descriptors"], u_right=u_right[f, :N], cols=W, rows=H)
-        ref = R.relocalization_refine(oracle, frame, cand, hyps[h]["pose7"], hyps[h]["match"], inl, cam5, inv_sigma2, sf, log_sf, device_poses=got["poses7"][h])
-        print("hypothesis %d (frame %d): status %d (want %d), nGood %d (%d), nadditional %s (%s)" % (
-            h, f, got["status"][h], ref["status"], got["n_good"][h], ref["n_good"], got["n_additional"][h].tolist(), ref["n_additional"]))
-        assert got["status"][h] == ref["status"], h
-        assert got["n_good"][h] == ref["n_good"] and got["n_additional"][h].tolist() == ref["n_additional"], h
-        for stage in range(3):
-            if ref["outliers"][stage] is None:
-                assert not got["poses7"][h, stage].any()
-            else:   # the tolerance test_track_reference_keyframe_batch uses for this kernel against this oracle
-                assert np.allclose(got["poses7"][h, stage], ref["poses"][stage], rtol=1e-4, atol=1e-6), (h, stage, got["poses7"][h, stage], ref["poses"][stage])
-        assert np.array_equal(got["kf_keypoint_of_keypoint"][h, :N], ref["assign"]), h
-        assert (got["kf_keypoint_of_keypoint"][h, N:] == -1).all()
-        assert np.array_equal(got["outlier"][h, :N], ref["outlier"]), h
-        for which in range(2):
-            if ref["searches"][which] is not None:
-                by_hand[which].append((h, f, cand, ref["searches"][which]))
-        st = int(got["status"][h])
-        seen.add("rejected" if st & R.REJECTED else "success without search" if st == R.OPT1 | R.SUCCESS else
-                 "first search not enough" if st == R.OPT1 | R.SEARCH1 else "second optimisation" if st == R.OPT1 | R.SEARCH1 | R.OPT2 | R.SUCCESS else
-                 "third optimisation" if st & R.OPT3 else "final failure" if not st & R.SUCCESS else "other")
-        if st & R.OPT3 and not st & R.SUCCESS:
-            seen.add("final failure")
+
+    def check(hyps, refs, got, seen, by_hand):
+        for h, (f, cand, inl) in enumerate(refs):
+            fr = S["frames"][f]
+            N = len(fr["keys"])
+            frame = dict(keys=fr["keys"], descriptors=fr["descriptors"], u_right=u_right[f, :N], cols=W, rows=H)
+            ref = R.relocalization_refine(oracle, frame, cand, hyps[h]["pose7"], hyps[h]["match"], inl, cam5, inv_sigma2, sf, log_sf, device_poses=got["poses7"][h])
+            print("hypothesis %d (frame %d): status %d (want %d), nGood %d (%d), nadditional %s (%s)" % (
+                h, f, got["status"][h], ref["status"], got["n_good"][h], ref["n_good"], got["n_additional"][h].tolist(), ref["n_additional"]))
+            assert got["status"][h] == ref["status"], h
+            assert got["n_good"][h] == ref["n_good"] and got["n_additional"][h].tolist() == ref["n_additional"], h
+            for stage in range(3):
+                if ref["outliers"][stage] is None:
+                    assert not got["poses7"][h, stage].any()
+                else:   # the tolerance test_track_reference_keyframe_batch uses for this kernel against this oracle
+                    assert np.allclose(got["poses7"][h, stage], ref["poses"][stage], rtol=1e-4, atol=1e-6), (h, stage, got["poses7"][h, stage], ref["poses"][stage])
+            assert np.array_equal(got["kf_keypoint_of_keypoint"][h, :N], ref["assign"]), h
+            assert (got["kf_keypoint_of_keypoint"][h, N:] == -1).all()
+            assert np.array_equal(got["outlier"][h, :N], ref["outlier"]), h
+            for which in range(2):
+                if ref["searches"][which] is not None:
+                    by_hand[which].append((h, f, cand, ref["searches"][which]))
+            st = int(got["status"][h])
+            seen.add("rejected" if st & R.REJECTED else "success without search" if st == R.OPT1 | R.SUCCESS else
+                     "first search not enough" if st == R.OPT1 | R.SEARCH1 else "second optimisation" if st == R.OPT1 | R.SEARCH1 | R.OPT2 | R.SUCCESS else
+                     "third optimisation" if st & R.OPT3 else "final failure" if not st & R.SUCCESS else "other")
+            if st & R.OPT3 and not st & R.SUCCESS:
+                seen.add("final failure")
+    check(hyps, refs, got, seen, by_hand)
+    if batch is not None:
+        batch.update(hyps=hyps, refs=refs, u_right=u_right, cam5=cam5, check=lambda hy, rf, gt: check(hy, rf, gt, set(), {0: [], 1: []}))
     assert dense or {"rejected", "success without search", "first search not enough", "second optimisation", "third optimisation", "final failure"} <= seen, seen
     queries = sum(len(h["has_point"]) for h in hyps)
     pool = [(sum(s[5] for _, _, _, s in by_hand[which]), queries) for which in range(2)]
@@ -570,3 +576,77 @@ def test_relocalization_refine_pool_overflow_takes_the_one_kernel_path(pkg, orac
     print("(window candidates, queries) of the two searches:", pool)
     assert pool[0][0] > pool[0][1], pool
     assert sorted(got) == sorted(ref) and all(np.array_equal(got[k], ref[k]) for k in ref)
+
+
+# ---- the tables of a call: every one has its place in the call's block, whatever the call before left there -----------------------------
+def _rows(got, rows):
+    return {k: v[rows] for k, v in got.items()}
+
+
+def _same_outputs(a, b):
+    return sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+
+
+def test_refine_grows_shrinks_and_reuses_its_buffers(pkg, oracle, synthetic, reloc_scene):
+    """All hypotheses (checked against the reference inside the helper), one of them alone, all again, through the same per-thread buffers;
+    then a hypothesis whose keyframe has no point between two ordinary ones.  The hypotheses are independent: a hypothesis' rows are the
+    same in every batch, and the pointless one is checked against the reference as the others were."""
+    B_ = {}
+    got, _ = _check_relocalization_refine(pkg, oracle, synthetic, reloc_scene, batch=B_)
+    hyps, refs, run = B_["hyps"], B_["refs"], lambda hy: pkg.relocalization_refine_batch(reloc_scene["ext"], hy, B_["u_right"], B_["cam5"])
+    k = 3                                                                         # "the second optimisation reaches 50": both searches run
+    assert _same_outputs(run([hyps[k]]), _rows(got, [k]))
+    assert _same_outputs(run(hyps), got)
+    f, cand, inl = refs[1]
+    none = {n: np.zeros((0,) + np.asarray(cand[n]).shape[1:], np.asarray(cand[n]).dtype) for n in (
+        "has_point", "Xw", "point_descriptors", "min_distance", "max_distance", "max_distance_raw", "angle")}
+    empty = dict(hyps[1], match=np.full_like(hyps[1]["match"], -1), inlier=np.zeros_like(hyps[1]["inlier"]), **none)
+    three = run([hyps[k], empty, hyps[-1]])
+    assert _same_outputs(_rows(three, [0, 2]), _rows(got, [k, len(hyps) - 1]))
+    B_["check"]([empty], [(f, none, empty["inlier"])], _rows(three, [1]))
+    assert three["status"][1] & R.REJECTED and (three["kf_keypoint_of_keypoint"][1] == -1).all()
+
+
+def test_three_databases_whose_scored_lists_end_off_a_boundary(pkg, tree):
+    """Databases of 5, 70 and 9 keyframes in one call with a scored list: 3 queries x 70 list entries x 4 bytes = 840, no multiple of 256,
+    so the scored tables lie off the boundaries a table starts on.  Against the restatement and against the three one-database calls on
+    fresh copies."""
+    voc = _voc(pkg, tree, R.L1_NORM)
+
+    def make():
+        rng = np.random.default_rng(78)
+        ms, frames = [], []
+        for n_kf in (5, 70, 9):
+            places = _places(rng, 2, 80)
+            m = Mirror(pkg, voc)
+            _fill(m, rng, places, n_kf, n_words=100)
+            ms.append(m)
+            frames.append(R.random_bow(rng, N_VOC, 100, places[0], 0.9))
+        return ms, frames
+
+    a, frames = make()
+    b, _ = make()
+    for rounds in range(2):   # the second round meets stored scores
+        cands, scored = pkg.detect_relocalization_candidates_batch([(m.dev, 0, *f) for m, f in zip(a, frames)], capacity=70, scored_capacity=70)
+        for d in range(3):
+            c1, s1 = pkg.detect_relocalization_candidates_batch([(b[d].dev, 0, *frames[d])], capacity=70, scored_capacity=70)
+            assert c1[0].tolist() == cands[d].tolist(), d
+            for key in s1[0]:
+                assert s1[0][key].tobytes() == scored[d][key].tobytes(), (d, key)
+            _same_result(cands[d], scored[d], a[d].ref.detect_relocalization_candidates(0, *frames[d]), d)
+            a[d].check_entries()
+        assert all(len(s["kf_id"]) > 0 for s in scored) and len(scored[1]["kf_id"]) > 9
+
+
+def test_score_pairs_of_0_1_and_200_words(pkg, tree):
+    voc = _voc(pkg, tree, R.L1_NORM)
+    rng = np.random.default_rng(6)
+    base = R.random_bow(rng, N_VOC, 200)[0]
+    big = [R.random_bow(rng, N_VOC, 200, base, 0.8) for _ in range(2)]
+    empty = (np.zeros(0, np.int32), np.zeros(0))
+    one = (np.array([big[0][0][5]], np.int32), np.array([0.5]))
+    pairs = [(empty, empty), (one, one), (big[0], big[1]), (one, big[0]), (empty, big[1]), (big[1], one)]
+    assert all(len(w) == 200 for w, _ in big)
+    got = voc.score(pairs)
+    want = np.array([R.score(R.L1_NORM, p[0], p[1]) for p in pairs])
+    assert _bits(got, np.float64) == _bits(want, np.float64) and len(set(want.tolist())) >= 4

@@ -51,12 +51,18 @@ def scenario(pkg, synthetic, seeds, w=1242, h=375, variants=None, nfeatures=2000
                 w=w, h=h)
 
 
-def check(pkg, oracle, synthetic, sc, th=7.0):
+def run_motion_model(pkg, synthetic, sc, th=7.0, stream=0):
+    cam5 = np.float32([synthetic.FX, synthetic.FY, synthetic.CX, synthetic.CY, sc["bf"]]).astype(np.float64)  # the frame's intrinsics are floats
+    return pkg.capi.track_motion_model_batch(sc["ext"], len(sc["lasts"]), sc["kps"], sc["u_right"], pkg.capi.pack_last_frames(sc["lasts"]), sc["preds"], cam5,
+                                             sc["b"], th, stream=stream)
+
+
+def check(pkg, oracle, synthetic, sc, th=7.0, got=None):
+    """got: the outputs of a run_motion_model(sc, th) made before, else the call is made here"""
     F = len(sc["lasts"])
     cam5 = np.array([synthetic.FX, synthetic.FY, synthetic.CX, synthetic.CY, sc["bf"]], np.float64)
     cam5 = np.float32(cam5).astype(np.float64)  # the frame's intrinsics are floats
-    packed = pkg.capi.pack_last_frames(sc["lasts"])
-    poses, mp, nm, inl = pkg.capi.track_motion_model_batch(sc["ext"], F, sc["kps"], sc["u_right"], packed, sc["preds"], cam5, sc["b"], th)
+    poses, mp, nm, inl = got if got is not None else run_motion_model(pkg, synthetic, sc, th)
     scales, inv_sigma2 = sc["ext"].GetScaleFactors(), sc["ext"].GetInverseScaleSigmaSquares()
     out = []
     for f in range(F):
@@ -99,8 +105,8 @@ def test_track_motion_model_argument_errors(pkg, synthetic):
 
 
 # ---- Tracking::TrackLocalMap --------------------------------------------------------------------------------------------------
-def local_map_scenario(pkg, oracle, synthetic, seeds, nfeatures=2000):
-    sc = scenario(pkg, synthetic, seeds, nfeatures=nfeatures)
+def local_map_scenario(pkg, oracle, synthetic, seeds, nfeatures=2000, w=1242, h=375):
+    sc = scenario(pkg, synthetic, seeds, w=w, h=h, nfeatures=nfeatures)
     F = len(seeds)
     cap = sc["kps"].shape[1]
     fx, fy, cx, cy = [np.float32(v) for v in (synthetic.FX, synthetic.FY, synthetic.CX, synthetic.CY)]
@@ -138,11 +144,19 @@ def local_map_scenario(pkg, oracle, synthetic, seeds, nfeatures=2000):
     return sc
 
 
-def check_local_map(pkg, oracle, synthetic, sc, th, far):
+def run_local_map(pkg, synthetic, sc, th, far, stream=0):
+    cam5 = np.float32([synthetic.FX, synthetic.FY, synthetic.CX, synthetic.CY, sc["bf"]]).astype(np.float64)
+    return pkg.capi.track_local_map_batch(sc["ext"], len(sc["poses"]), sc["kps"], sc["u_right"], sc["poses"], sc["held"], sc["held_Xw"], sc["local"],
+                                          sc["local_off"], cam5, th=th, far_points=far, th_far=30.0, stream=stream)
+
+
+def check_local_map(pkg, oracle, synthetic, sc, th, far, got=None, at_least=(100, 200)):
+    """got: the outputs of a run_local_map(sc, th, far) made before, else the call is made here.  at_least: the matches and inliers every
+    frame of the scenario must pass, so that the comparison is one of full frames."""
     F = len(sc["poses"])
     cam5 = np.float32([synthetic.FX, synthetic.FY, synthetic.CX, synthetic.CY, sc["bf"]]).astype(np.float64)
-    got = pkg.capi.track_local_map_batch(sc["ext"], F, sc["kps"], sc["u_right"], sc["poses"], sc["held"], sc["held_Xw"], sc["local"], sc["local_off"], cam5,
-                                         th=th, far_points=far, th_far=30.0)
+    if got is None:
+        got = run_local_map(pkg, synthetic, sc, th, far)
     scales, inv_sigma2 = sc["ext"].GetScaleFactors(), sc["ext"].GetInverseScaleSigmaSquares()
     log_scale = float(np.log(np.float32(1.2)))
     for f in range(F):
@@ -150,10 +164,10 @@ def check_local_map(pkg, oracle, synthetic, sc, th, far):
         pts = sc["local"][sc["local_off"][f]:sc["local_off"][f + 1]]
         want = oracle.track_local_map(sc["kps"][2 * f, :n], sc["desc"][2 * f, :n], sc["u_right"][f, :n], sc["w"], sc["h"], scales, inv_sigma2, log_scale,
                                       sc["poses"][f], cam5, sc["held"][f, :n], sc["held_Xw"][f, :n], pts, th=th, far_points=far, th_far=30.0)
-        assert got[3][f] == want[3] and want[3] > 100
+        assert got[3][f] == want[3] and want[3] > at_least[0]
         assert np.array_equal(got[1][f, :n], want[1]) and np.all(got[1][f, n:] == -1)
         assert np.array_equal(got[2][f, :n], want[2])
-        assert got[4][f] == want[4] and want[4] > 200
+        assert got[4][f] == want[4] and want[4] > at_least[1]
         assert np.allclose(got[0][f], want[0], rtol=1e-4, atol=1e-6)
         # a keypoint that holds a point with observations keeps it
         assert np.all(got[1][f, :n][sc["held"][f, :n] == 1] == -1)

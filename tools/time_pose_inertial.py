@@ -17,6 +17,10 @@ for last in (True, False):
         items = [ws[k % 4] for k in range(n)]
         f = lambda: pkg.capi.pose_inertial_optimization_batch(items, ws[0]["calib24"], ws[0]["cam"])
         for _ in range(3): f()
+        ts = []
+        for _ in range(9):
+            t0 = time.perf_counter(); f(); ts.append(1e3 * (time.perf_counter() - t0))
+        print("last_frame=%d, %3d frames: %-24s %.3f ms per call (median of 9, host memory to host memory)" % (last, n, "call", float(np.median(ts))))
         pkg.capi.profile_enable(True)
         for _ in range(5): f()
         pkg.capi.profile_enable(False)
