@@ -582,7 +582,8 @@ int tc2li_imu_predict_state(const tc2li_preintegrated* p, const tc2li_imu_bias* 
  * g2o's stop rules) over the keyframe velocities (in / out, double), one gyro and one accelerometer bias (in: the first keyframe's; out:
  * the estimate), the gravity direction Rwg (in / out) and, when mono, the scale (in / out); fixed_vel freezes velocities and biases.
  * The pre-integrations are evaluated at the estimated biases through their bias Jacobians (SetNewBias + GetDelta*(b)).  What the
- * reference does with the result on its objects (SetVelocity / SetNewBias / Reintegrate, ApplyScaledRotation) stays with the caller.
+ * reference does with the result on its objects (SetVelocity / SetNewBias / Reintegrate) stays with the caller; Map::ApplyScaledRotation
+ * on the flat map is tc2li_apply_scaled_rotation_batch ("IMU initialisation: the map update" below).
  * Returns the iterations run. */
 typedef struct tc2li_inertial_init_stats { int32_t iterations, trials; double initial_chi2, final_chi2, final_lambda; } tc2li_inertial_init_stats;
 int tc2li_imu_init_gravity(int n_kfs, const float* Rwb9, const float* twb3, const tc2li_preintegrated* const* pre, float* vel3, float Rwg9[9]);
@@ -2278,6 +2279,137 @@ int tc2li_image_prep_batch(tc2li_image_prep* prep, const uint8_t* images, int im
  * y right} (NULL, or NULL entries, unless the mode is RECTIFY); they are checked as tc2li_image_prep_set_maps checks them, on every call. */
 int tc2li_host_image_prep_batch(const tc2li_image_prep_params* params, const float* const maps[4], const uint8_t* images, int n_images,
                                 int stride, size_t image_pitch_bytes, uint8_t* gray, int gray_stride, size_t gray_pitch_bytes);
+
+/* ---- IMU initialisation: the map update (SF/src/Map.cc:256-287 Map::ApplyScaledRotation, called at SF/src/LocalMapping.cc:1299 and :1494;
+ * SF/src/LocalMapping.cc:1346-1425, the update of the map after FullInertialBA, which is the reference's update after any global BA) ------
+ * The two steps of LocalMapping::InitializeIMU (:1184-1445) and ScaleRefinement (:1447-1512) that rewrite every keyframe and every map
+ * point, on a flat copy of the map, one problem per sequence.  The library returns the new poses, velocities, biases and positions; the
+ * caller writes them into its objects (INTEGRATION.md "InitializeIMU / ScaleRefinement").  Rig: pinhole stereo, NLeft == -1, no
+ * mpCamera2: an observation contributes its left camera centre only.  All pointers are host memory, the arrays are copied by the call,
+ * indices are rows of the problem's own tables, outputs must not overlap inputs.  A pose is seven floats, the unit quaternion x, y, z, w
+ * and the translation, as Sophus::SE3f holds it.
+ * Arithmetic: float, every product and sum rounded (no contraction), the Sophus operations in the order Sophus writes them
+ * (csrc/se3f_math.hpp):
+ *   unit(q)      len = sqrt(x*x + y*y + z*z + w*w) summed left to right, then four divisions (SO3::normalize)
+ *   spin(q, p)   uv = q.vec x p; uv += uv; p + w * uv + q.vec x uv, summed left to right (so3.hpp:358-367)
+ *   inverse(T)   q' = unit(conj(q)) -- the conjugate passes the SO3(Quaternion) constructor --, t' = spin(q', t * -1) (se3.hpp:208-211)
+ *   compose(A,B) q = unit(a * b) with the product of so3.hpp:325-339, t = t_a + spin(q_a, t_b) (se3.hpp:304-308)
+ *   rotation_of  Eigen's toRotationMatrix
+ * Where Eigen leaves a summation order to its build, THESE CHOICES DEFINE PARITY: a 3-term row sum is ((a*x + b*y) + c*z), a translation
+ * is added after it; a vector norm is sqrtf((x*x + y*y) + z*z), the order of tc2li_map_points_refresh.
+ *
+ * One call of Map::ApplyScaledRotation(T, s, bScaledVel):
+ *   T7 Tyw as the caller's Sophus::SE3f holds it;  s;  scaled_vel bScaledVel;  has_tcb mImuCalib.mbIsSet and tcb3 mImuCalib.mTcb.translation();
+ *   keyframes (n_keyframes rows): kf_pose7 mTcw;  kf_vel [n][3] mVw
+ *   points (n_points rows): point_pos [n][3];  point_bad isBad();  CSR obs_offsets [n_points + 1];  obs_kf the observing keyframe, IN THE
+ *     ITERATION ORDER OF mObservations -- the normal is a float sum in that order --;  point_ref_kf mpRefKF (-1 only where the point is bad
+ *     or has no observations);  point_ref_level_scale mvScaleFactors[octave of the reference observation];  last_level_scale
+ *     mvScaleFactors[nLevels - 1]
+ * Per keyframe (Map.cc:268-277, KeyFrame::SetPose SF/src/KeyFrame.cc:121-134): Twc = inverse(Tcw); Twc.t *= s componentwise; Tyc =
+ *   compose(Tyw, Twc); Tcw' = inverse(Tyc); Twc' = inverse(Tcw'); with has_tcb Owb' = rotation_of(Twc'.q) * tcb + Twc'.t; V' = Ryw * V,
+ *   then * s with scaled_vel, Ryw = rotation_of(Tyw.q).
+ * Per point (Map.cc:283-284): M = s * Ryw with every entry rounded; pos' = ((M[r][0]*x + M[r][1]*y) + M[r][2]*z) + tyw[r] -- a bad point
+ *   is moved too, SetWorldPos does not look at the flag --; then MapPoint::UpdateNormalAndDepth (SF/src/MapPoint.cc:444-503) against the
+ *   new camera centres Twc'.t, which does nothing for a bad point or one without observations: normal = the sum over the observations, in
+ *   order, of (pos' - Ow) / |pos' - Ow|, divided by their number; max_distance = |pos' - Ow_ref| * point_ref_level_scale; min_distance =
+ *   max_distance / last_level_scale.  The arithmetic of tc2li_map_points_refresh, without its cap on the observations of a point.
+ * Out: kf_pose7_out mTcw;  kf_inv_pose7_out mTwc (its translation is the camera centre);  kf_imu_pos_out [n][3] mOwb (may be NULL;
+ * written when has_tcb);  kf_vel_out;  point_pos_out;  point_normal [n][3], point_min_distance, point_max_distance: left untouched where
+ * the reference returns early. */
+typedef struct tc2li_scaled_rotation_problem {
+    const float* kf_pose7;
+    const float* kf_vel;
+    const float* point_pos;
+    const uint8_t* point_bad;
+    const int32_t* obs_offsets;
+    const int32_t* obs_kf;
+    const int32_t* point_ref_kf;
+    const float* point_ref_level_scale;
+    float* kf_pose7_out;
+    float* kf_inv_pose7_out;
+    float* kf_imu_pos_out;
+    float* kf_vel_out;
+    float* point_pos_out;
+    float* point_normal;
+    float* point_min_distance;
+    float* point_max_distance;
+    float T7[7];
+    float s;
+    float tcb3[3];
+    float last_level_scale;
+    int32_t n_keyframes, n_points;
+    uint8_t scaled_vel, has_tcb;
+    uint8_t pad_[6];
+} tc2li_scaled_rotation_problem;
+/* Map::ApplyScaledRotation for n_problems maps at once on the device: one lane per keyframe, then one lane per point with the point's
+ * observations walked in order.  One upload, two launches, one download; the results are in host memory when the call returns (stream:
+ * NULL = the calling thread's private stream).  Before any device work: TC2LI_ERR_INVALID for negative sizes, NULL required arrays,
+ * offsets that do not ascend from 0, obs_kf or point_ref_kf out of range.  A refused call writes nothing.  Returns n_problems. */
+int tc2li_apply_scaled_rotation_batch(const tc2li_scaled_rotation_problem* problems, int n_problems, void* stream);
+/* The same contract as plain sequential C++ with the same arithmetic (one problem per worker thread); needs no device. */
+int tc2li_host_apply_scaled_rotation_batch(const tc2li_scaled_rotation_problem* problems, int n_problems);
+
+/* One map update after a global BA with nLoopId != 0 (LocalMapping.cc:1346-1425), on what Optimizer.cc:734-810 left on the objects.
+ *   keyframes (n_keyframes rows, at most 4096): kf_parent mpParent (-1 = none);  kf_origin member of mvpKeyFrameOrigins (an origin has no
+ *     parent);  kf_bad isBad();  kf_in_gba mnBAGlobalForKF == GBAid on entry;  kf_imu bImu;  kf_vel_set isVelocitySet();  kf_pose7 mTcw;
+ *     kf_gba_pose7 mTcwGBA as stored;  kf_bef_gba_pose7 mTcwBefGBA as stored (read only for keyframes the walk does not reach);  kf_vel /
+ *     kf_gba_vel [n][3] mVw / mVwbGBA;  kf_bias / kf_gba_bias [n][6] GetImuBias() / mBiasGBA
+ *   points (n_points rows): point_bad;  point_in_gba mnBAGlobalForKF == GBAid;  point_pos;  point_gba_pos mPosGBA;  point_ref_kf (-1 only
+ *     where the point is bad or in the GBA)
+ * The walk (:1347-1394) starts at the origins and goes down the children.  A bad child is skipped with everything below it; an origin is
+ * not asked.  A visited child with !kf_in_gba gets TcwGBA = compose(compose(Tcw_child, Twc_parent), TcwGBA_parent), where Twc_parent is
+ * the parent's mTwc when the parent is popped, inverse() of its pose before its own SetPose; VwbGBA = spin(compose_q(inverse_q(TcwGBA.q),
+ * Tcw_child.q), V) when kf_vel_set (inverse_q = unit(conj), SO3::inverse), else its stored kf_gba_vel; BiasGBA = its bias; and the flag.
+ * Every visited keyframe then gets TcwBefGBA = Tcw, Tcw = TcwGBA and, with kf_imu, V = VwbGBA and bias = BiasGBA.  EVERY KEYFRAME HAS ONE
+ * PARENT, SO THE ORDER AMONG SIBLINGS REACHES NO RESULT.
+ * Points (:1399-1425): a bad point is untouched; point_in_gba: pos = gba_pos; otherwise, only if the reference keyframe's flag is set
+ * after the walk: Xc = spin(TcwBef.q, pos) + TcwBef.t, pos = spin(Twc'.q, Xc) + Twc'.t with Twc' = inverse() of that keyframe's pose
+ * after the walk.  UpdateNormalAndDepth is not called here in the reference.
+ * Out: kf_visited;  kf_in_gba_out;  kf_pose7_out;  kf_bef_gba_pose7_out;  kf_vel_out;  kf_bias_out (all rows are written: a keyframe the
+ * walk did not reach gets its inputs back);  point_pos_out;  point_moved: 0 untouched, 1 took the GBA position, 2 followed its reference
+ * keyframe. */
+typedef struct tc2li_gba_correction_problem {
+    const int32_t* kf_parent;
+    const uint8_t* kf_origin;
+    const uint8_t* kf_bad;
+    const uint8_t* kf_in_gba;
+    const uint8_t* kf_imu;
+    const uint8_t* kf_vel_set;
+    const float* kf_pose7;
+    const float* kf_gba_pose7;
+    const float* kf_bef_gba_pose7;
+    const float* kf_vel;
+    const float* kf_gba_vel;
+    const float* kf_bias;
+    const float* kf_gba_bias;
+    const uint8_t* point_bad;
+    const uint8_t* point_in_gba;
+    const float* point_pos;
+    const float* point_gba_pos;
+    const int32_t* point_ref_kf;
+    uint8_t* kf_visited;
+    uint8_t* kf_in_gba_out;
+    float* kf_pose7_out;
+    float* kf_bef_gba_pose7_out;
+    float* kf_vel_out;
+    float* kf_bias_out;
+    float* point_pos_out;
+    uint8_t* point_moved;
+    int32_t n_keyframes, n_points;
+} tc2li_gba_correction_problem;
+/* The map update of n_problems maps at once on the device: one workgroup per problem walks the tree in rounds (a round resolves every
+ * keyframe whose parent is resolved; a chain of depth d takes d rounds), then one lane per point.  One upload, two launches, one
+ * download; the results are in host memory when the call returns (stream: NULL = the calling thread's private stream).  Before any device
+ * work: TC2LI_ERR_INVALID for negative sizes, NULL arrays, kf_parent or point_ref_kf out of range, an origin with a parent, a parent
+ * chain that does not end (a cycle); TC2LI_ERR_CAPACITY for more than 4096 keyframes in a problem.  A refused call writes nothing.
+ * Returns n_problems. */
+int tc2li_gba_map_correction_batch(const tc2li_gba_correction_problem* problems, int n_problems, void* stream);
+/* The same contract as plain sequential C++ (the list of :1347 as a queue, one problem per worker thread); needs no device. */
+int tc2li_host_gba_map_correction_batch(const tc2li_gba_correction_problem* problems, int n_problems);
+/* out[0] = the most keyframes of a tc2li_gba_correction_problem (the walk's state bytes live in LDS), out[1] = threads per problem in the
+ * walk, out[2] = keyframes and out[3] = points per workgroup of the per-row kernels.  Returns 4.  Needs no device.  No reference
+ * counterpart. */
+int tc2li_map_update_limits(int32_t* out, int capacity);
 
 #ifdef __cplusplus
 }

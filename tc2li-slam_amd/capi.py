@@ -2665,6 +2665,151 @@ def map_point_culling_batch(points, th_obs=3, host=False, stream=0):
     return action
 
 
+class ScaledRotationProblem(C.Structure):
+    """tc2li_scaled_rotation_problem"""
+    _fields_ = [(k, C.c_void_p) for k in ("kf_pose7", "kf_vel", "point_pos", "point_bad", "obs_offsets", "obs_kf", "point_ref_kf",
+                                          "point_ref_level_scale", "kf_pose7_out", "kf_inv_pose7_out", "kf_imu_pos_out", "kf_vel_out",
+                                          "point_pos_out", "point_normal", "point_min_distance", "point_max_distance")] \
+        + [("T7", C.c_float * 7), ("s", C.c_float), ("tcb3", C.c_float * 3), ("last_level_scale", C.c_float), ("n_keyframes", C.c_int32),
+           ("n_points", C.c_int32), ("scaled_vel", C.c_uint8), ("has_tcb", C.c_uint8), ("pad_", C.c_uint8 * 6)]
+
+
+_SCALED_ROTATION_ARRAYS = (("kf_pose7", np.float32, 7), ("kf_vel", np.float32, 3), ("point_pos", np.float32, 3), ("point_bad", np.uint8, 0),
+                           ("obs_offsets", np.int32, 0), ("obs_kf", np.int32, 0), ("point_ref_kf", np.int32, 0), ("point_ref_level_scale", np.float32, 0))
+_SCALED_ROTATION_OUTPUTS = (("kf_pose7_out", np.float32, "k", 7), ("kf_inv_pose7_out", np.float32, "k", 7), ("kf_imu_pos_out", np.float32, "k", 3),
+                            ("kf_vel_out", np.float32, "k", 3), ("point_pos_out", np.float32, "p", 3), ("point_normal", np.float32, "p", 3),
+                            ("point_min_distance", np.float32, "p", 0), ("point_max_distance", np.float32, "p", 0))
+
+
+def _rows(a, width):
+    """A flat table as rows of `width` entries (0: a plain array)."""
+    return a.reshape(-1, width) if width else a.reshape(-1)
+
+
+def _fill_outputs(spec, sizes, fill):
+    """The output arrays of a problem: spec entries (name, dtype, which size, width), every array filled with `fill` reinterpreted as its
+    type, so that a test sees what a call left untouched."""
+    out = {}
+    for k, t, which, width in spec:
+        a = np.empty((sizes[which], width) if width else (sizes[which],), t)
+        a.view(np.uint8)[...] = fill
+        out[k] = a
+    return out
+
+
+def pack_scaled_rotation_problems(problems, fill=0):
+    """The tc2li_scaled_rotation_problem array of a batch with its output arrays (every byte prefilled with `fill`) -> (array, outputs per
+    problem, what must stay alive)."""
+    P = len(problems)
+    arr, outs, keep = (ScaledRotationProblem * max(P, 1))(), [], []
+    for i, p in enumerate(problems):
+        a = {k: _rows(np.ascontiguousarray(p[k], t), w) for k, t, w in _SCALED_ROTATION_ARRAYS}
+        nk, npts = len(a["kf_pose7"]), len(a["point_pos"])
+        if len(a["kf_vel"]) != nk or any(len(a[k]) != npts for k in ("point_bad", "point_ref_kf", "point_ref_level_scale")) or len(a["obs_offsets"]) != npts + 1:
+            raise ValueError("problem %d: the tables do not fit n_keyframes = %d, n_points = %d" % (i, nk, npts))
+        if len(a["obs_kf"]) < int(a["obs_offsets"][-1]):
+            raise ValueError("problem %d: obs_kf is shorter than obs_offsets say" % i)
+        o = _fill_outputs(_SCALED_ROTATION_OUTPUTS, dict(k=nk, p=npts), fill)
+        for k, v in list(a.items()) + list(o.items()):
+            setattr(arr[i], k, v.ctypes.data)
+        arr[i].T7 = (C.c_float * 7)(*[float(v) for v in np.asarray(p["T7"], np.float32)])
+        arr[i].tcb3 = (C.c_float * 3)(*[float(v) for v in np.asarray(p.get("tcb3", (0, 0, 0)), np.float32)])
+        arr[i].s, arr[i].last_level_scale = float(np.float32(p["s"])), float(np.float32(p["last_level_scale"]))
+        arr[i].scaled_vel, arr[i].has_tcb = int(bool(p.get("scaled_vel", 0))), int(bool(p.get("has_tcb", 0)))
+        arr[i].n_keyframes, arr[i].n_points = nk, npts
+        keep.append(a)
+        outs.append(o)
+    return arr, outs, keep
+
+
+def apply_scaled_rotation_batch(problems, host=False, stream=0, fill=0):
+    """One ``Map::ApplyScaledRotation(T, s, bScaledVel)`` per problem.  problems: dicts with T7 (quaternion x, y, z, w, then translation), s,
+    scaled_vel, has_tcb, tcb3, last_level_scale and the arrays of tc2li_scaled_rotation_problem (kf_pose7 [n, 7], kf_vel [n, 3], point_pos
+    [m, 3], point_bad, obs_offsets [m + 1], obs_kf, point_ref_kf, point_ref_level_scale) -> one dict per problem: kf_pose7_out,
+    kf_inv_pose7_out, kf_imu_pos_out, kf_vel_out, point_pos_out, point_normal, point_min_distance, point_max_distance.  What the reference
+    leaves untouched (normal and distances of bad points and of points without observations, kf_imu_pos_out without has_tcb) keeps the
+    `fill` bytes.  host=True runs the same arithmetic on the CPU."""
+    arr, outs, keep = pack_scaled_rotation_problems(problems, fill)
+    if host:
+        f = lib().tc2li_host_apply_scaled_rotation_batch
+        f.argtypes = [C.c_void_p, C.c_int]
+        _check(f(C.addressof(arr), len(problems)))
+    else:
+        f = lib().tc2li_apply_scaled_rotation_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _check(f(C.addressof(arr), len(problems), C.c_void_p(stream)))
+    del keep
+    return outs
+
+
+class GbaCorrectionProblem(C.Structure):
+    """tc2li_gba_correction_problem"""
+    _fields_ = [(k, C.c_void_p) for k in ("kf_parent", "kf_origin", "kf_bad", "kf_in_gba", "kf_imu", "kf_vel_set", "kf_pose7", "kf_gba_pose7",
+                                          "kf_bef_gba_pose7", "kf_vel", "kf_gba_vel", "kf_bias", "kf_gba_bias", "point_bad", "point_in_gba", "point_pos",
+                                          "point_gba_pos", "point_ref_kf", "kf_visited", "kf_in_gba_out", "kf_pose7_out", "kf_bef_gba_pose7_out",
+                                          "kf_vel_out", "kf_bias_out", "point_pos_out", "point_moved")] \
+        + [("n_keyframes", C.c_int32), ("n_points", C.c_int32)]
+
+
+_GBA_CORRECTION_ARRAYS = (("kf_parent", np.int32, 0, "k"), ("kf_origin", np.uint8, 0, "k"), ("kf_bad", np.uint8, 0, "k"), ("kf_in_gba", np.uint8, 0, "k"),
+                          ("kf_imu", np.uint8, 0, "k"), ("kf_vel_set", np.uint8, 0, "k"), ("kf_pose7", np.float32, 7, "k"), ("kf_gba_pose7", np.float32, 7, "k"),
+                          ("kf_bef_gba_pose7", np.float32, 7, "k"), ("kf_vel", np.float32, 3, "k"), ("kf_gba_vel", np.float32, 3, "k"),
+                          ("kf_bias", np.float32, 6, "k"), ("kf_gba_bias", np.float32, 6, "k"), ("point_bad", np.uint8, 0, "p"),
+                          ("point_in_gba", np.uint8, 0, "p"), ("point_pos", np.float32, 3, "p"), ("point_gba_pos", np.float32, 3, "p"),
+                          ("point_ref_kf", np.int32, 0, "p"))
+_GBA_CORRECTION_OUTPUTS = (("kf_visited", np.uint8, "k", 0), ("kf_in_gba_out", np.uint8, "k", 0), ("kf_pose7_out", np.float32, "k", 7),
+                           ("kf_bef_gba_pose7_out", np.float32, "k", 7), ("kf_vel_out", np.float32, "k", 3), ("kf_bias_out", np.float32, "k", 6),
+                           ("point_pos_out", np.float32, "p", 3), ("point_moved", np.uint8, "p", 0))
+
+
+def pack_gba_correction_problems(problems, fill=0):
+    """The tc2li_gba_correction_problem array of a batch with its output arrays (every byte prefilled with `fill`) -> (array, outputs per
+    problem, what must stay alive)."""
+    P = len(problems)
+    arr, outs, keep = (GbaCorrectionProblem * max(P, 1))(), [], []
+    for i, p in enumerate(problems):
+        a = {k: _rows(np.ascontiguousarray(p[k], t), w) for k, t, w, _ in _GBA_CORRECTION_ARRAYS}
+        sizes = dict(k=len(a["kf_parent"]), p=len(a["point_bad"]))
+        for k, _, _, which in _GBA_CORRECTION_ARRAYS:
+            if len(a[k]) != sizes[which]:
+                raise ValueError("problem %d: %s has %d rows, not %d" % (i, k, len(a[k]), sizes[which]))
+        o = _fill_outputs(_GBA_CORRECTION_OUTPUTS, sizes, fill)
+        for k, v in list(a.items()) + list(o.items()):
+            setattr(arr[i], k, v.ctypes.data)
+        arr[i].n_keyframes, arr[i].n_points = sizes["k"], sizes["p"]
+        keep.append(a)
+        outs.append(o)
+    return arr, outs, keep
+
+
+def gba_map_correction_batch(problems, host=False, stream=0, fill=0):
+    """The map update that follows a global BA (``LocalMapping::InitializeIMU`` after ``FullInertialBA``), one per problem.  problems: dicts
+    with the arrays of tc2li_gba_correction_problem (kf_parent, kf_origin, kf_bad, kf_in_gba, kf_imu, kf_vel_set, kf_pose7, kf_gba_pose7,
+    kf_bef_gba_pose7 [n, 7], kf_vel, kf_gba_vel [n, 3], kf_bias, kf_gba_bias [n, 6], point_bad, point_in_gba, point_pos, point_gba_pos [m, 3],
+    point_ref_kf) -> one dict per problem: kf_visited, kf_in_gba_out, kf_pose7_out, kf_bef_gba_pose7_out, kf_vel_out, kf_bias_out,
+    point_pos_out, point_moved (0 untouched, 1 the GBA position, 2 followed its reference keyframe).  host=True walks the tree on the CPU."""
+    arr, outs, keep = pack_gba_correction_problems(problems, fill)
+    if host:
+        f = lib().tc2li_host_gba_map_correction_batch
+        f.argtypes = [C.c_void_p, C.c_int]
+        _check(f(C.addressof(arr), len(problems)))
+    else:
+        f = lib().tc2li_gba_map_correction_batch
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _check(f(C.addressof(arr), len(problems), C.c_void_p(stream)))
+    del keep
+    return outs
+
+
+def map_update_limits():
+    """tc2li_map_update_limits -> {max_keyframes, walk_threads, keyframe_tile, point_tile}."""
+    out = (C.c_int32 * 4)()
+    f = lib().tc2li_map_update_limits
+    f.argtypes = [C.c_void_p, C.c_int]
+    _check(f(out, 4))
+    return dict(zip(("max_keyframes", "walk_threads", "keyframe_tile", "point_tile"), [int(v) for v in out]))
+
+
 class StereoPointsFrame(C.Structure):
     """tc2li_stereo_points_frame"""
     _fields_ = [(k, C.c_void_p) for k in ("depth", "keys", "held", "outlier", "created_keypoint", "x3D", "counts")] \
