@@ -573,7 +573,8 @@ int tc2li_imu_delta(const tc2li_preintegrated* p, const tc2li_imu_bias* bias, fl
 int tc2li_imu_predict_state(const tc2li_preintegrated* p, const tc2li_imu_bias* bias, const float Rwb1[9], const float twb1[3],
                             const float Vwb1[3], float Rwb2[9], float twb2[3], float Vwb2[3]);
 
-/* IMU initialisation (host code by design: tens of keyframes, one 9-d edge per consecutive pair).
+/* IMU initialisation (one problem on the host: tens of keyframes, one 9-d edge per consecutive pair.  Many
+ * maps at once, on the device or on the host's pool: "IMU initialisation: the inertial optimisation, batched" below).
  * tc2li_imu_init_gravity = the first estimate of LocalMapping::InitializeIMU (SF/src/LocalMapping.cc:1241-1270): keyframes in temporal
  * order (Rwb [n][9] row-major, twb [n][3], float), pre[i] = keyframe i's pre-integration from keyframe i - 1 (pre[0] ignored, NULL
  * entries skipped) -> the finite-difference velocities vel3 [n][3] and Rwg (gravity direction of the IMU world).  Returns the links used.
@@ -2410,6 +2411,65 @@ int tc2li_host_gba_map_correction_batch(const tc2li_gba_correction_problem* prob
  * walk, out[2] = keyframes and out[3] = points per workgroup of the per-row kernels.  Returns 4.  Needs no device.  No reference
  * counterpart. */
 int tc2li_map_update_limits(int32_t* out, int capacity);
+
+/* ---- IMU initialisation: the inertial optimisation, batched (SF/src/Optimizer.cc:2169-2356 Optimizer::InertialOptimization(pMap, Rwg,
+ * scale, bg, ba, bMono, covInertial, bFixedVel, bGauss, priorG, priorA), called at SF/src/LocalMapping.cc:1283; SF/src/Optimizer.cc:2359-2466
+ * Optimizer::InertialOptimization(pMap, Rwg, scale), called at SF/src/LocalMapping.cc:1491) --------------------------------------------------
+ * tc2li_inertial_optimization and tc2li_inertial_scale_refinement ("IMU initialisation" above) for many maps at once: when many sequences
+ * start together they reach the 1 s, 5 s and 15 s initialisations (SF/src/LocalMapping.cc:204-240) and every 10 s scale refinement (:253)
+ * in the same step.  One problem per map; it carries exactly the arguments of the two single-problem entries, with their meaning:
+ *   n_keyframes;  Rwb9 [n][9], twb3 [n][3] the keyframes in temporal order;  vel3 [n][3] the velocities: in / out in the first form, read
+ *   only in the refinement form;  pre [n]: pre[i] = keyframe i's pre-integration from keyframe i - 1, pre[0] is ignored and a NULL entry
+ *   is a link that is skipped;  Rwg9 [9], scale: in / out;  bg [3], ba [3]: in / out, first form;  bg3, ba3 [n][3]: the keyframes' fixed
+ *   biases, refinement form -- edge i takes keyframe i - 1's;  mono, fixed_vel, prior_g, prior_a: first form;  iterations: 200 / 10 in the
+ *   reference;  refine: 0 = the first overload, otherwise the second.
+ *   Out: stats (may be NULL): the first form's iterations, trials, chi2 before and after and the last lambda;  chi2 [2] (may be NULL): the
+ *   refinement form's activeRobustChi2 before and after;  iterations_run (may be NULL): the iterations either form ran.
+ * ONE STRUCT, TWO ENTRIES: tc2li_inertial_optimization_batch takes each problem in the form its `refine` says, so one call serves a step
+ * in which some maps initialise and others refine; tc2li_inertial_scale_refinement_batch takes every problem in the refinement form
+ * whatever `refine` says -- LocalMapping::ScaleRefinement's call needs no flag.  All pointers are host memory. */
+typedef struct tc2li_inertial_init_problem {
+    const double* Rwb9;
+    const double* twb3;
+    double* vel3;
+    const tc2li_preintegrated* const* pre;
+    double* Rwg9;
+    double* scale;
+    double* bg;
+    double* ba;
+    const double* bg3;
+    const double* ba3;
+    tc2li_inertial_init_stats* stats;
+    double* chi2;
+    int32_t* iterations_run;
+    int32_t n_keyframes, mono, fixed_vel, iterations, refine;
+    float prior_g, prior_a;
+    int32_t pad_;
+} tc2li_inertial_init_problem;
+/* On the device, one workgroup per map with the whole optimisation inside the launch: Levenberg-Marquardt with g2o's control, trials,
+ * backup and restore and stop rules (first form, SF/src/Optimizer.cc:2169-2356), Gauss-Newton with Huber(1) (refinement form, :2359-2466).
+ * The links' informations are prepared on the host as the single-problem entries prepare them; the 15 x 15 covariances are not uploaded.
+ * One upload, one launch per form present, one download; the results are in host memory when the call returns (stream: NULL = the
+ * calling thread's private stream).  A map's results are the same bits alone, anywhere in any batch, and from call to call.  They differ
+ * from the host entries' by rounding: the sums over links are formed in another (fixed) order and the pre-integration at the new bias
+ * normalises its rotation as tc2li_pose_inertial_optimization_batch does.  Before any device work: TC2LI_ERR_INVALID, naming the problem,
+ * for n_keyframes < 2, NULL required arrays, negative iterations, a link covariance that is not positive definite, sizes or iterations
+ * beyond tc2li_inertial_init_limits.  A refused call writes nothing.  Returns n_problems. */
+int tc2li_inertial_optimization_batch(const tc2li_inertial_init_problem* problems, int n_problems, void* stream);
+int tc2li_inertial_scale_refinement_batch(const tc2li_inertial_init_problem* problems, int n_problems, void* stream);
+/* The same contract through tc2li_inertial_optimization / tc2li_inertial_scale_refinement, one problem per worker thread under the host
+ * thread budget: their results, bit for bit; no limits on sizes or iterations; needs no device. */
+int tc2li_host_inertial_optimization_batch(const tc2li_inertial_init_problem* problems, int n_problems);
+int tc2li_host_inertial_scale_refinement_batch(const tc2li_inertial_init_problem* problems, int n_problems);
+/* out[0] = the most keyframes of a first-form problem in a device call (its solver state is per keyframe), out[1] = of a refinement-form
+ * problem, out[2] = the most iterations of either (so that no launch is unbounded).  Returns 3.  Needs no device.  No reference
+ * counterpart. */
+int tc2li_inertial_init_limits(int32_t* out, int capacity);
+/* One step of the block factorisation of the first form's velocity part, the function the kernel's chain runs (csrc/imu_init_device.hpp):
+ * S = D + lambda I - L Sinv_prev L' (Sinv_prev NULL: the first block, L is not read), Sinv = S^-1.  Returns 1, or 0 when S is singular or
+ * not finite -- the trial then fails and Sinv is not written.  Needs no device.  No reference counterpart (g2o hands the system to a sparse
+ * Cholesky). */
+int tc2li_inertial_init_arrow_pivot(const double D[9], const double L[9], const double Sinv_prev[9], double lambda, double Sinv[9]);
 
 #ifdef __cplusplus
 }

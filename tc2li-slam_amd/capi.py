@@ -2810,6 +2810,110 @@ def map_update_limits():
     return dict(zip(("max_keyframes", "walk_threads", "keyframe_tile", "point_tile"), [int(v) for v in out]))
 
 
+class InertialInitProblem(C.Structure):
+    """tc2li_inertial_init_problem"""
+    _fields_ = [(k, C.c_void_p) for k in ("Rwb9", "twb3", "vel3", "pre", "Rwg9", "scale", "bg", "ba", "bg3", "ba3", "stats", "chi2", "iterations_run")] \
+        + [(k, C.c_int32) for k in ("n_keyframes", "mono", "fixed_vel", "iterations", "refine")] \
+        + [("prior_g", C.c_float), ("prior_a", C.c_float), ("pad_", C.c_int32)]
+
+
+def pack_inertial_init_problems(problems, all_refine=False):
+    """The tc2li_inertial_init_problem array of a batch -> (array, per problem the arrays the call writes, what must stay alive).  problems:
+    dicts with Rwb [n, 3, 3], twb [n, 3], vel [n, 3], pres (``Preintegrated`` or None per keyframe, pres[0] ignored), Rwg, scale and, first
+    form: bg, ba, mono, fixed_vel, prior_g (1e2), prior_a (1e6), iterations (200); refinement form (refine=True): bg3, ba3 [n, 3], iterations
+    (10).  A key given as None reaches the library as a NULL pointer; n_keyframes overrides the count taken from Rwb.  all_refine: for the
+    entry that takes every problem in the refinement form (the flag is passed on as the problem has it)."""
+    P = len(problems)
+    arr, outs, keep = (InertialInitProblem * max(P, 1))(), [], []
+    for i, p in enumerate(problems):
+        flag = bool(p.get("refine", False))
+        refine = flag or all_refine
+        n = int(p.get("n_keyframes", 0 if p.get("Rwb") is None else len(np.asarray(p["Rwb"]).reshape(-1, 9))))
+
+        def table(key, width, must=True):
+            v = p.get(key)
+            if v is None:
+                if must and key not in p:
+                    raise ValueError("problem %d lacks %s" % (i, key))
+                return None
+            return np.ascontiguousarray(v, np.float64).reshape(-1, width).copy()
+        a = dict(Rwb9=table("Rwb", 9), twb3=table("twb", 3), vel3=table("vel", 3), Rwg9=table("Rwg", 9), bg=table("bg", 3, not refine), ba=table("ba", 3, not refine),
+                 bg3=table("bg3", 3, refine), ba3=table("ba3", 3, refine))
+        a["scale"] = None if p.get("scale", 1.0) is None else np.array([p.get("scale", 1.0)], np.float64)
+        pres = p.get("pres")
+        ptrs = None
+        if pres is not None:
+            ptrs = (C.c_void_p * max(len(pres), 1))(*[None if (k == 0 or q is None) else C.addressof(q.p) for k, q in enumerate(pres)])
+        o = dict(stats=InertialInitStats(), chi2=np.zeros(2), iterations_run=np.zeros(1, np.int32))
+        for k, v in a.items():
+            setattr(arr[i], k, None if v is None else v.ctypes.data)
+        arr[i].pre = None if ptrs is None else C.addressof(ptrs)
+        arr[i].stats, arr[i].chi2, arr[i].iterations_run = C.addressof(o["stats"]), o["chi2"].ctypes.data, o["iterations_run"].ctypes.data
+        arr[i].n_keyframes, arr[i].mono, arr[i].fixed_vel = n, int(bool(p.get("mono", False))), int(bool(p.get("fixed_vel", False)))
+        arr[i].iterations, arr[i].refine = int(p.get("iterations", 10 if refine else 200)), int(flag)
+        arr[i].prior_g, arr[i].prior_a = float(p.get("prior_g", 1e2)), float(p.get("prior_a", 1e6))
+        o.update(a)
+        keep.append((a, ptrs, pres))
+        outs.append(o)
+    return arr, outs, keep
+
+
+def _inertial_init_batch(name, problems, host, stream):
+    arr, outs, keep = pack_inertial_init_problems(problems, name == "inertial_scale_refinement_batch")
+    f = getattr(lib(), ("tc2li_host_" if host else "tc2li_") + name)
+    if host:
+        f.argtypes = [C.c_void_p, C.c_int]
+        _check(f(C.addressof(arr), len(problems)))
+    else:
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _check(f(C.addressof(arr), len(problems), C.c_void_p(stream)))
+    del keep
+    res = []
+    for p, o in zip(problems, outs):
+        r = dict(Rwg=o["Rwg9"].reshape(3, 3), scale=float(o["scale"][0]), iterations=int(o["iterations_run"][0]))
+        if p.get("refine", False) or name == "inertial_scale_refinement_batch":
+            r.update(chi2=(float(o["chi2"][0]), float(o["chi2"][1])))
+        else:
+            r.update(vel=o["vel3"], bg=o["bg"].reshape(3), ba=o["ba"].reshape(3), stats=o["stats"])
+        res.append(r)
+    return res
+
+
+def inertial_optimization_batch(problems, host=False, stream=0):
+    """``Optimizer::InertialOptimization`` for many maps at once (tc2li_inertial_optimization_batch; host=True: the single-problem entries on the
+    pool).  problems: see pack_inertial_init_problems; each is taken in the form its ``refine`` says -> one dict per problem: Rwg, scale,
+    iterations and vel, bg, ba, stats (first form) or chi2 (refinement form)."""
+    return _inertial_init_batch("inertial_optimization_batch", problems, host, stream)
+
+
+def inertial_scale_refinement_batch(problems, host=False, stream=0):
+    """The second overload (``LocalMapping::ScaleRefinement``) for many maps at once: every problem in the refinement form -> one dict per
+    problem: Rwg, scale, iterations, chi2."""
+    return _inertial_init_batch("inertial_scale_refinement_batch", problems, host, stream)
+
+
+def inertial_init_limits():
+    """tc2li_inertial_init_limits -> {max_keyframes, max_refine_keyframes, max_iterations}."""
+    out = (C.c_int32 * 3)()
+    f = lib().tc2li_inertial_init_limits
+    f.argtypes = [C.c_void_p, C.c_int]
+    _check(f(out, 3))
+    return dict(zip(("max_keyframes", "max_refine_keyframes", "max_iterations"), [int(v) for v in out]))
+
+
+def inertial_init_arrow_pivot(D, L, Sinv_prev, lam):
+    """tc2li_inertial_init_arrow_pivot -> S^-1 [3, 3] of S = D + lam I - L Sinv_prev L' (Sinv_prev None: the first block), or None when S is
+    singular."""
+    D = np.ascontiguousarray(D, np.float64).reshape(9)
+    L = None if L is None else np.ascontiguousarray(L, np.float64).reshape(9)
+    Sp = None if Sinv_prev is None else np.ascontiguousarray(Sinv_prev, np.float64).reshape(9)
+    out = np.full(9, np.nan)
+    f = lib().tc2li_inertial_init_arrow_pivot
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+    rc = _check(f(D.ctypes.data, None if L is None else L.ctypes.data, None if Sp is None else Sp.ctypes.data, float(lam), out.ctypes.data))
+    return out.reshape(3, 3) if rc == 1 else None
+
+
 class StereoPointsFrame(C.Structure):
     """tc2li_stereo_points_frame"""
     _fields_ = [(k, C.c_void_p) for k in ("depth", "keys", "held", "outlier", "created_keypoint", "x3D", "counts")] \

@@ -8,7 +8,8 @@
 // 9-dimensional edge per consecutive pair.  The normal equations have an arrow shape -- the velocities only couple to their neighbours in
 // time and to the nine shared unknowns (biases, gravity direction, scale) -- and are solved as such: the block-tridiagonal velocity part
 // is factorised in O(N) 3 x 3 steps, the shared part through its Schur complement (g2o hands the reference the same system as a
-// sparse Cholesky; the results agree to rounding).
+// sparse Cholesky; the results agree to rounding).  The edge and the step of the block factorisation are imu_init_device.hpp's, shared with
+// the kernels that run many maps at once (imu_init_kernels.hip, imu_init_batch_host.cpp); one problem stays here.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "imu_init_device.hpp"
 #include "inertial_host.hpp"
 
 using namespace tc2li;
@@ -23,70 +25,24 @@ using namespace tc2li::inertial_detail;
 
 namespace {
 
-constexpr double kG = (double)9.81f;  // IMU::GRAVITY_VALUE is a float constant
-
 struct InitVars {
     std::vector<double> v;  // [3 N]
     double bg[3], ba[3], Rwg[9], s;
 };
 
-// EdgeInertialGS between keyframes i - 1 and i: error and the Jacobian columns V1 3 | bg 3 | ba 3 | V2 3 | gdir 2 | scale 1 (9 x 15, row-major)
+// EdgeInertialGS between keyframes i - 1 and i: error and the Jacobian columns V1 3 | bg 3 | ba 3 | V2 3 | gdir 2 | scale 1 (9 x 15, row-major).
+// The pre-integration at the current bias here, the edge in imu_init_device.hpp (the kernels run the same).
 void gs_edge(const double* Rwb1, const double* twb1, const double* v1, const double* Rwb2, const double* twb2, const double* v2, const InitVars& x,
              const tc2li_preintegrated* pre, double err[9], double* J) {
     const tc2li_imu_bias b{(float)x.ba[0], (float)x.ba[1], (float)x.ba[2], (float)x.bg[0], (float)x.bg[1], (float)x.bg[2]};
     float dRf[9], dVf[3], dPf[3];
     tc2li_imu_delta(pre, &b, dRf, dVf, dPf);
-    double dR[9], g[3], Rbw1[9], dRt[9], t1[9], eR[9], er[3], dv[3], dp[3], rv[3], rp[3];
+    double dR[9], dV[3], dP[3];
     for (int k = 0; k < 9; ++k) dR[k] = dRf[k];
-    const double gI[3] = {0, 0, -kG}, dt = pre->dT, s = x.s;
-    r3_vec(x.Rwg, gI, g);
-    tr3(Rwb1, Rbw1); tr3(dR, dRt);
-    r3_mul(dRt, Rbw1, t1); r3_mul(t1, Rwb2, eR);
-    log_so3(eR, er);
-    for (int k = 0; k < 3; ++k) {
-        dv[k] = s * (v2[k] - v1[k]) - g[k] * dt;
-        dp[k] = s * (twb2[k] - twb1[k] - v1[k] * dt) - g[k] * dt * dt / 2;
-    }
-    r3_vec(Rbw1, dv, rv); r3_vec(Rbw1, dp, rp);
-    for (int k = 0; k < 3; ++k) { err[k] = er[k]; err[3 + k] = rv[k] - (double)dVf[k]; err[6 + k] = rp[k] - (double)dPf[k]; }
-    if (!J) return;
-    memset(J, 0, 9 * 15 * sizeof(double));
-    auto put = [&](int r0, int c0, const double* m, double f) { for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) J[15 * (r0 + r) + c0 + c] = f * m[3 * r + c]; };
-    put(3, 0, Rbw1, -s); put(6, 0, Rbw1, -s * dt);
-    double invJr[9], JRg[9], JVg[9], JPg[9], JVa[9], JPa[9], Jd[3], RJ[9], eRt[9], a1[9], a2[9], a3[9];
-    jr_so3(er, true, invJr);
-    for (int k = 0; k < 9; ++k) { JRg[k] = pre->JRg[k]; JVg[k] = pre->JVg[k]; JPg[k] = pre->JPg[k]; JVa[k] = pre->JVa[k]; JPa[k] = pre->JPa[k]; }
+    for (int k = 0; k < 3; ++k) { dV[k] = (double)dVf[k]; dP[k] = (double)dPf[k]; }
     const double dbg[3] = {(double)(b.bwx - pre->bias.bwx), (double)(b.bwy - pre->bias.bwy), (double)(b.bwz - pre->bias.bwz)};
-    r3_vec(JRg, dbg, Jd);
-    jr_so3(Jd, false, RJ);
-    tr3(eR, eRt);
-    r3_mul(invJr, eRt, a1); r3_mul(a1, RJ, a2); r3_mul(a2, JRg, a3);
-    put(0, 3, a3, -1.0); put(3, 3, JVg, -1.0); put(6, 3, JPg, -1.0);
-    put(3, 6, JVa, -1.0); put(6, 6, JPa, -1.0);
-    put(3, 9, Rbw1, s);
-    // dGdTheta = Rwg * [0 -G; G 0; 0 0]
-    for (int r = 0; r < 3; ++r) {
-        double c0 = 0, c1 = 0;
-        for (int k = 0; k < 3; ++k) { c0 += Rbw1[3 * r + k] * (x.Rwg[3 * k + 1] * kG); c1 += Rbw1[3 * r + k] * (x.Rwg[3 * k] * -kG); }
-        J[15 * (3 + r) + 12] = -c0 * dt; J[15 * (3 + r) + 13] = -c1 * dt;
-        J[15 * (6 + r) + 12] = -0.5 * c0 * dt * dt; J[15 * (6 + r) + 13] = -0.5 * c1 * dt * dt;
-    }
-    double d1[3], d2[3], s1[3], s2[3];
-    for (int k = 0; k < 3; ++k) { d1[k] = v2[k] - v1[k]; d2[k] = twb2[k] - twb1[k] - v1[k] * dt; }
-    r3_vec(Rbw1, d1, s1); r3_vec(Rbw1, d2, s2);
-    for (int r = 0; r < 3; ++r) { J[15 * (3 + r) + 14] = s1[r]; J[15 * (6 + r) + 14] = s2[r]; }
-}
-
-// 3 x 3 helpers of the arrow solver
-inline bool inv3(const double* a, double* o) {
-    const double c0 = a[4] * a[8] - a[5] * a[7], c1 = a[5] * a[6] - a[3] * a[8], c2 = a[3] * a[7] - a[4] * a[6];
-    const double det = a[0] * c0 + a[1] * c1 + a[2] * c2;
-    if (!(std::fabs(det) > 0) || !std::isfinite(det)) return false;
-    const double id = 1.0 / det;
-    o[0] = c0 * id; o[1] = (a[2] * a[7] - a[1] * a[8]) * id; o[2] = (a[1] * a[5] - a[2] * a[4]) * id;
-    o[3] = c1 * id; o[4] = (a[0] * a[8] - a[2] * a[6]) * id; o[5] = (a[2] * a[3] - a[0] * a[5]) * id;
-    o[6] = c2 * id; o[7] = (a[1] * a[6] - a[0] * a[7]) * id; o[8] = (a[0] * a[4] - a[1] * a[3]) * id;
-    return true;
+    if (J) ii_gs_edge_at<1>(*pre, dR, dV, dP, dbg, Rwb1, twb1, v1, Rwb2, twb2, v2, x.Rwg, x.s, err, J);
+    else ii_gs_edge_at<0>(*pre, dR, dV, dP, dbg, Rwb1, twb1, v1, Rwb2, twb2, v2, x.Rwg, x.s, err, nullptr);
 }
 
 // The system  [ T  B ] [xv]   [bv]     T: block tridiagonal (N blocks of 3 x 3: diagonal D_i, sub-diagonal L_i = T(i, i-1)),
@@ -105,20 +61,17 @@ struct ArrowSystem {
         const int w = m + 1;
         std::vector<double> Sinv((size_t)9 * N), Y((size_t)3 * N * w);  // Y_i = rows of (B | bv) after the elimination
         for (int i = 0; i < N; ++i) {
-            double S[9];
-            for (int k = 0; k < 9; ++k) S[k] = D[9 * (size_t)i + k];
-            S[0] += lambda; S[4] += lambda; S[8] += lambda;
             for (int r = 0; r < 3; ++r) { for (int c = 0; c < m; ++c) Y[(size_t)(3 * i + r) * w + c] = B[(size_t)(3 * i + r) * m + c]; Y[(size_t)(3 * i + r) * w + m] = bv[3 * (size_t)i + r]; }
-            if (i > 0) {
-                // G = L_i S_{i-1}^-1;  S -= G L_i';  Y_i -= G Y_{i-1}
-                double G[9];
-                r3_mul(&L[9 * (size_t)i], &Sinv[9 * (size_t)(i - 1)], G);
-                for (int r = 0; r < 3; ++r)
-                    for (int c = 0; c < 3; ++c) { double t = 0; for (int k = 0; k < 3; ++k) t += G[3 * r + k] * L[9 * (size_t)i + 3 * c + k]; S[3 * r + c] -= t; }
-                for (int r = 0; r < 3; ++r)
-                    for (int c = 0; c < w; ++c) { double t = 0; for (int k = 0; k < 3; ++k) t += G[3 * r + k] * Y[(size_t)(3 * (i - 1) + k) * w + c]; Y[(size_t)(3 * i + r) * w + c] -= t; }
-            }
-            if (!inv3(S, &Sinv[9 * (size_t)i])) return false;
+            // G = L_i S_{i-1}^-1;  S -= G L_i';  Y_i -= G Y_{i-1}: the chain step the kernel runs too (imu_init_device.hpp)
+            double G[9];
+            if (!ii_arrow_pivot(&D[9 * (size_t)i], &L[9 * (size_t)i], i > 0 ? &Sinv[9 * (size_t)(i - 1)] : nullptr, i == 0, lambda, G, &Sinv[9 * (size_t)i])) return false;
+            if (i > 0)
+                for (int c = 0; c < w; ++c) {
+                    double yp[3], y[3];
+                    for (int r = 0; r < 3; ++r) { yp[r] = Y[(size_t)(3 * (i - 1) + r) * w + c]; y[r] = Y[(size_t)(3 * i + r) * w + c]; }
+                    ii_arrow_eliminate(G, yp, y);
+                    for (int r = 0; r < 3; ++r) Y[(size_t)(3 * i + r) * w + c] = y[r];
+                }
         }
         // Schur complement of the border: Cs = C + lambda I - sum_i Y_i' S_i^-1 Y_i(:, :m),  rhs = bc - sum_i Y_i(:, :m)' S_i^-1 Y_i(:, m)
         std::vector<double> Cs((size_t)m * m), rhs(m), Z((size_t)3 * N * w);
