@@ -1021,6 +1021,46 @@ int tc2li_local_map_update(tc2li_local_map* map, const int32_t* frame_points, in
                            void* stream);
 const int32_t* tc2li_local_map_device_points(const tc2li_local_map* map);
 
+/* UpdateLocalMap for many sequences in one call: one problem per sequence, each with the semantics of tc2li_local_map_update, line for
+ * line against Tracking.cc:3296-3476.  Problems are independent: a problem's result does not depend on the batch's size or order.
+ * counts [TC2LI_LOCAL_MAP_COUNTS] is always written on success and on TC2LI_ERR_CAPACITY; local_keyframes / local_points /
+ * frame_point_cleared get their first N_KEYFRAMES / N_POINTS / n_frame_points entries, what lies beyond stays untouched.
+ * Refused before any work with TC2LI_ERR_INVALID and the problem's number in the message, nothing written: NULL map (device entry) /
+ * graph (host entry) / counts, NULL frame_points or frame_point_cleared with n_frame_points > 0, a NULL list with a capacity > 0,
+ * negative sizes or capacities, a map without a graph, a frame point outside [-1, n_points), temporal_last_kf outside
+ * [-1, n_keyframes), and (device entry) the same map named by two problems of one call.
+ * TC2LI_ERR_CAPACITY when a list of some problem does not fit: counts holds the sizes needed for EVERY problem, no list of any
+ * problem is written, and the call repeated with those capacities succeeds.  Returns n_problems (0 for an empty batch).
+ * The device entry issues a number of launches, memsets, copies and stream waits that does not depend on n_problems: one upload, five
+ * kernels, one download of the counts, one of the lists at the sizes found (never at capacity).  The host entry walks problem.graph in
+ * plain C++ on the tracking pool, one problem per thread, validates the graph as tc2li_local_map_set_graph does, and needs no device.
+ * After a batch call tc2li_local_map_device_points(map) is unspecified: the batch keeps its lists in its own buffers. */
+enum tc2li_local_map_count {
+    TC2LI_LOCAL_MAP_N_KEYFRAMES = 0,   /* entries of local_keyframes (mvpLocalKeyFrames) */
+    TC2LI_LOCAL_MAP_N_VOTED = 1,       /* how many of them came from the vote (:3383-3398) */
+    TC2LI_LOCAL_MAP_REFERENCE_KF = 2,  /* pKFmax, -1: mpReferenceKF stays */
+    TC2LI_LOCAL_MAP_N_POINTS = 3,      /* entries of local_points (mvpLocalMapPoints) */
+    TC2LI_LOCAL_MAP_N_CLEARED = 4,     /* frame points set to NULL because they are bad (:3345, :3369) */
+    TC2LI_LOCAL_MAP_COUNTS = 8         /* ints in the block, the rest 0 */
+};
+typedef struct tc2li_local_map_update_problem {
+    tc2li_local_map* map;              /* device entry: the sequence's mirror; the host entry does not read it */
+    const tc2li_map_graph* graph;      /* host entry: the graph itself; the device entry does not read it */
+    const int32_t* frame_points;       /* as tc2li_local_map_update */
+    int32_t n_frame_points, temporal_last_kf;
+    int32_t* counts;                   /* [TC2LI_LOCAL_MAP_COUNTS], always written */
+    int32_t* local_keyframes; int32_t* local_points; uint8_t* frame_point_cleared;
+    int32_t keyframe_capacity, point_capacity;
+} tc2li_local_map_update_problem;
+int tc2li_local_map_update_batch(const tc2li_local_map_update_problem* problems, int n_problems, void* stream);
+int tc2li_host_local_map_update_batch(const tc2li_local_map_update_problem* problems, int n_problems);  /* needs no device */
+/* tc2li_local_map_set_graph for n_maps mirrors: every graph is validated first (one invalid graph, or a map named twice: TC2LI_ERR_INVALID
+ * with the map's number and no mirror changes), then all copies go on the stream and one wait ends the call.  Returns n_maps. */
+int tc2li_local_map_set_graph_batch(tc2li_local_map* const* maps, const tc2li_map_graph* graphs, int n_maps, void* stream);
+/* The sizes at which the kernels of tc2li_local_map_update_batch change path, for tests: out[0] keyframes up to which the vote counters
+ * live in LDS, out[1] workgroups per problem of the point phase, out[2] threads per workgroup.  Returns 3.  Needs no device. */
+int tc2li_local_map_limits(int32_t* out, int capacity);
+
 /* The LiDAR term alone at the poses poses7 (Tcw of the window keyframes are rows lidar->pose_index): planes from the
  * window, then *residual = LidarCovisRes::ComputeError() and JacT [6W] / Hessian [(6W)^2, row-major] =
  * LidarCovisRes::ComputeJandHSE3 (SF/src/LidarRes.cc:136-186, with respect to the camera se3 increments).  JacT and

@@ -2026,6 +2026,15 @@ class MapGraph(C.Structure):
                 ("match_offsets", C.c_void_p), ("matches", C.c_void_p), ("point_bad", C.c_void_p), ("obs_offsets", C.c_void_p), ("obs_kf", C.c_void_p)]
 
 
+def map_graph(graph):
+    """dict of flat arrays (see LocalMap) -> (MapGraph, the arrays it points into: keep them alive as long as it is used)"""
+    g = {k: np.ascontiguousarray(v, np.uint8 if k in ("kf_bad", "point_bad") else np.int32) for k, v in graph.items()}
+    ptr = lambda k: g[k].ctypes.data if g[k].size else None
+    mg = MapGraph(len(g["kf_bad"]), len(g["point_bad"]), ptr("kf_bad"), ptr("covis_off"), ptr("covis"), ptr("child_off"), ptr("children"),
+                  ptr("parent"), ptr("prev_kf"), ptr("match_off"), ptr("matches"), ptr("point_bad"), ptr("obs_off"), ptr("obs_kf"))
+    return mg, g
+
+
 class LocalMap:
     """Device-resident mirror of the keyframe graph (``tc2li_local_map``) and ``Tracking::UpdateLocalMap`` on it.  graph: dict of flat
     arrays kf_bad, covis_off, covis, child_off, children, parent, prev_kf, match_off, matches, point_bad, obs_off, obs_kf."""
@@ -2036,11 +2045,9 @@ class LocalMap:
         self.n_keyframes = self.n_points = 0
 
     def set_graph(self, graph, stream=0):
-        g = {k: np.ascontiguousarray(v, np.uint8 if k in ("kf_bad", "point_bad") else np.int32) for k, v in graph.items()}
-        ptr = lambda k: g[k].ctypes.data if g[k].size else None
-        mg = MapGraph(len(g["kf_bad"]), len(g["point_bad"]), ptr("kf_bad"), ptr("covis_off"), ptr("covis"), ptr("child_off"), ptr("children"),
-                      ptr("parent"), ptr("prev_kf"), ptr("match_off"), ptr("matches"), ptr("point_bad"), ptr("obs_off"), ptr("obs_kf"))
+        mg, keep = map_graph(graph)
         _check(lib().tc2li_local_map_set_graph(self.h, C.addressof(mg), C.c_void_p(stream)))
+        del keep
         self.n_keyframes, self.n_points = mg.n_keyframes, mg.n_points
 
     def update(self, frame_points, temporal_last_kf=-1, stream=0, keyframe_capacity=None, point_capacity=None):
@@ -2066,6 +2073,109 @@ class LocalMap:
             self.close()
         except Exception:
             pass
+
+
+class LocalMapUpdateProblem(C.Structure):
+    """tc2li_local_map_update_problem"""
+    _fields_ = [("map", C.c_void_p), ("graph", C.c_void_p), ("frame_points", C.c_void_p), ("n_frame_points", C.c_int32), ("temporal_last_kf", C.c_int32),
+                ("counts", C.c_void_p), ("local_keyframes", C.c_void_p), ("local_points", C.c_void_p), ("frame_point_cleared", C.c_void_p),
+                ("keyframe_capacity", C.c_int32), ("point_capacity", C.c_int32)]
+
+
+_LOCAL_MAP_COUNTS = ("n_keyframes", "n_voted", "reference_kf", "n_points", "n_cleared")
+
+
+def local_map_limits():
+    """tc2li_local_map_limits -> {lds_keyframes, point_workgroups, threads}: the sizes at which the device path of local_map_update_batch
+    changes (the vote counters and marks leave LDS above lds_keyframes keyframes; a problem's point phase is cut into point_workgroups slices)."""
+    out = (C.c_int32 * 3)()
+    f = lib().tc2li_local_map_limits
+    f.argtypes = [C.c_void_p, C.c_int]
+    _check(f(out, 3))
+    return dict(zip(("lds_keyframes", "point_workgroups", "threads"), [int(v) for v in out]))
+
+
+def pack_local_map_problems(problems, fill=0):
+    """The tc2li_local_map_update_problem array of a batch with its output arrays (prefilled with `fill`) -> (array, outputs per problem, what
+    must stay alive).  A problem is a dict with frame_points, optionally temporal_last_kf (-1), keyframe_capacity / point_capacity (by default
+    the graph's sizes, which can never be too small) and ``map`` (a LocalMap with its graph set: the device entry) and / or ``graph`` (the dict
+    of flat arrays LocalMap.set_graph takes: the host entry)."""
+    P = len(problems)
+    arr, outs, keep = (LocalMapUpdateProblem * max(P, 1))(), [], []
+    for i, p in enumerate(problems):
+        fp = np.ascontiguousarray(p["frame_points"], np.int32).reshape(-1)
+        lm, mg, nk, npts = p.get("map"), None, 0, 0
+        if lm is not None:
+            arr[i].map, nk, npts = lm.h, lm.n_keyframes, lm.n_points
+        if p.get("graph") is not None:
+            mg, g = map_graph(p["graph"])
+            keep.append((mg, g))
+            arr[i].graph, nk, npts = C.addressof(mg), mg.n_keyframes, mg.n_points
+        kc, pc = int(p.get("keyframe_capacity", nk)), int(p.get("point_capacity", npts))
+        full = lambda n, t: np.full(max(n, 1), fill, np.int64).astype(t)
+        o = dict(counts=full(8, np.int32), local_keyframes=full(kc, np.int32), local_points=full(pc, np.int32), frame_point_cleared=full(len(fp), np.uint8))
+        arr[i].frame_points = fp.ctypes.data if len(fp) else None
+        arr[i].n_frame_points, arr[i].temporal_last_kf = len(fp), int(p.get("temporal_last_kf", -1))
+        arr[i].counts, arr[i].local_keyframes, arr[i].local_points = o["counts"].ctypes.data, o["local_keyframes"].ctypes.data, o["local_points"].ctypes.data
+        arr[i].frame_point_cleared = o["frame_point_cleared"].ctypes.data if len(fp) else None
+        arr[i].keyframe_capacity, arr[i].point_capacity = kc, pc
+        keep.append(fp)
+        outs.append(o)
+    return arr, outs, keep
+
+
+def run_local_map_update_batch(arr, n_problems, host=False, stream=0):
+    """tc2li_local_map_update_batch / tc2li_host_local_map_update_batch on a packed array -> the call's return value; raises Tc2liError"""
+    if host:
+        f = lib().tc2li_host_local_map_update_batch
+        f.argtypes = [C.c_void_p, C.c_int]
+        return _check(f(C.addressof(arr), n_problems))
+    f = lib().tc2li_local_map_update_batch
+    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    return _check(f(C.addressof(arr), n_problems, C.c_void_p(stream)))
+
+
+def _local_map_results(problems, outs):
+    res = []
+    for p, o in zip(problems, outs):
+        c = dict(zip(_LOCAL_MAP_COUNTS, [int(v) for v in o["counts"][:5]]))
+        n = len(np.asarray(p["frame_points"]).reshape(-1))
+        res.append(dict(c, keyframes=o["local_keyframes"][:c["n_keyframes"]], points=o["local_points"][:c["n_points"]],
+                        cleared=o["frame_point_cleared"][:n].astype(bool)))
+    return res
+
+
+def local_map_update_batch(problems, stream=0, host=False):
+    """One ``Tracking::UpdateLocalMap`` per problem in one device call (``tc2li_local_map_update_batch``).  problems: dicts with ``map`` (a
+    LocalMap), frame_points and optionally temporal_last_kf, keyframe_capacity, point_capacity -> one dict per problem: keyframes, points,
+    cleared (cut to their counts), reference_kf, n_voted, n_keyframes, n_points, n_cleared."""
+    arr, outs, keep = pack_local_map_problems(problems)
+    run_local_map_update_batch(arr, len(problems), host, stream)
+    del keep
+    return _local_map_results(problems, outs)
+
+
+def host_local_map_update_batch(problems):
+    """``tc2li_host_local_map_update_batch``: the same on the CPU over each problem's ``graph`` (dict of flat arrays); needs no device."""
+    return local_map_update_batch(problems, host=True)
+
+
+def local_map_set_graph_batch(maps, graphs, stream=0):
+    """``tc2li_local_map_set_graph_batch``: LocalMap.set_graph for every (map, graph) pair with one wait; no mirror changes if a graph is
+    refused."""
+    n = len(maps)
+    if len(graphs) != n:
+        raise ValueError("as many graphs as maps are needed")
+    packed = [map_graph(g) for g in graphs]
+    mgs, hs = (MapGraph * max(n, 1))(), (C.c_void_p * max(n, 1))()
+    for i, (mg, _) in enumerate(packed):
+        mgs[i], hs[i] = mg, maps[i].h
+    f = lib().tc2li_local_map_set_graph_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    _check(f(C.addressof(hs), C.addressof(mgs), n, C.c_void_p(stream)))
+    for m, (mg, _) in zip(maps, packed):
+        m.n_keyframes, m.n_points = mg.n_keyframes, mg.n_points
+    del packed
 
 
 # ---- ORB vocabulary (DBoW2): Frame::ComputeBoW / KeyFrame::ComputeBoW, ORBmatcher::SearchByBoW(KeyFrame*, Frame&) ----------------------
