@@ -1,5 +1,5 @@
 // tc2li_ba_engine: running lock-step queues that windows join and leave one at a time (include/tc2li_hip.h).
-#include "ba_internal.hpp"
+#include "lockstep_host.hpp"
 
 using namespace tc2li;
 using namespace tc2li::ba_detail;
@@ -123,12 +123,8 @@ void tc2li_ba_engine::setup_task(int task) {
     EngineSlot& sl = slots[s];
     LockstepWindow& w = W[s];
     const tc2li_ba_problem& p = sl.ticket->problems[sl.index];
-    const bool args_ok = p.poses7 && p.fixed && p.points3 && p.edges && p.n_poses > 0 && p.n_points > 0 && p.n_edges > 0 && p.iterations >= 0;
-    bool lidar_ok = true;
-    if (args_ok && p.lidar) {
-        if (p.lidar->n_keyframes < 1 || p.lidar->n_keyframes > 7 || !p.lidar->pose_index) lidar_ok = false;
-        else for (int k = 0; k < p.lidar->n_keyframes; ++k) if (p.lidar->pose_index[k] < 0 || p.lidar->pose_index[k] >= p.n_poses) lidar_ok = false;
-    }
+    const bool args_ok = lv_window_args_ok(p, false);
+    const bool lidar_ok = !(args_ok && p.lidar) || lidar_window_ok(p.lidar, p.n_poses, kLockstepMaxLidarKeyframes);
     if (task & 1) {
         if (!args_ok || !lidar_ok || !p.lidar) return;
         CopySink sink(&sl.deferred_lidar);
@@ -136,26 +132,14 @@ void tc2li_ba_engine::setup_task(int task) {
         return;
     }
     CopySink sink(&sl.deferred_vis);
-    w.p = &p; w.ws = C.ws[s].get();
+    w.bind(p, C.ws[s].get());
     if (!args_ok) { set_error("tc2li_ba_engine: invalid window"); w.rc = TC2LI_ERR_INVALID; return; }
     if (!lidar_ok) { set_error("tc2li_ba_engine: a LiDAR window of 1 .. 7 keyframes with pose_index in range"); w.rc = TC2LI_ERR_INVALID; return; }
     if (p.stats) memset(p.stats, 0, sizeof(*p.stats));
     if (p.lidar_stats) memset(p.lidar_stats, 0, sizeof(*p.lidar_stats));
-    if (p.lidar) {
-        w.extra_used.assign(p.n_poses, 0);
-        for (int k = 0; k < p.lidar->n_keyframes; ++k) w.extra_used[p.lidar->pose_index[k]] = 1;
-    }
-    w.rc = w.vp.setup(*w.ws, p.poses7, p.fixed, p.n_poses, p.points3, p.n_points, p.edges, p.n_edges, &cam, w.extra_used.empty() ? nullptr : w.extra_used.data(), st);
+    w.rc = lv_window_structure(w, nullptr, &cam, st);
     if (w.rc < 0) return;
-    BaWorkspace& ws = *w.ws;
-    const size_t nn = (size_t)std::max(w.vp.np * w.vp.np, 1), n1 = (size_t)std::max(w.vp.np, 1), E = p.n_edges, P = p.n_points;
-    bool ok = ws.d_S.ensure(nn) == hipSuccess && ws.d_bs.ensure(2 * n1) == hipSuccess && ws.d_xp.ensure(n1) == hipSuccess && ws.d_scal.ensure(8) == hipSuccess &&
-              ws.h_result.ensure(p.n_poses * sizeof(Se3) + 3 * P * sizeof(double) + E * sizeof(double) + E) == hipSuccess;
-    if (ok && p.lidar) {
-        const size_t nl = 6 * (size_t)p.lidar->n_keyframes;
-        ok = ws.d_Hl.ensure(nn + n1) == hipSuccess && ws.d_balm_out.ensure((size_t)balm_out_size(p.lidar->n_keyframes)) == hipSuccess && ws.d_lidar_JH.ensure(nl + nl * nl) == hipSuccess;
-    }
-    if (!ok) w.rc = TC2LI_ERR_HIP;
+    if (!lv_window_device_buffers(w) || w.ws->h_result.ensure(result_bytes(w.vp.pb, true)) != hipSuccess) w.rc = TC2LI_ERR_HIP;
 }
 void tc2li_ba_engine::setup_loop() {
     (void)pthread_setname_np(pthread_self(), "tc2li-ba-setup");
@@ -182,13 +166,11 @@ void tc2li_ba_engine::run() {
     (void)hipSetDevice(device);
     BufferCacheScope cached(&cache);
     {
-        int lo = 0, hi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        if (hipStreamCreateWithPriority(&C.st, hipStreamNonBlocking, hi) != hipSuccess && hipStreamCreateWithFlags(&C.st, hipStreamNonBlocking) != hipSuccess) { C.st = nullptr; failed = 1; }
+        if (!create_priority_stream(&C.st)) failed = 1;
         for (hipEvent_t& e : C.round_done) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { e = nullptr; failed = 1; }
         use_side = getenv("TC2LI_BA_ENGINE_SIDE") && atoi(getenv("TC2LI_BA_ENGINE_SIDE")) != 0;
         if (const char* e = getenv("TC2LI_BA_ENGINE_STAGE")) { int a = 0, b = 0; if (sscanf(e, "%d,%d", &a, &b) == 2 && a >= 1 && b >= 0) { stage_min = a; stage_wait = b; } }
-        if (use_side && hipStreamCreateWithPriority(&side, hipStreamNonBlocking, hi) != hipSuccess && hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess) { side = nullptr; failed = 1; }
+        if (use_side && !create_priority_stream(&side)) failed = 1;
         for (hipEvent_t& e : side_ev) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { e = nullptr; failed = 1; }
     }
     hipStream_t st = C.st;
@@ -229,15 +211,8 @@ void tc2li_ba_engine::run() {
             if (!done.empty()) {
                 pool->parallel_for((int)done.size(), [&](int k) {
                     LockstepWindow& w = W[done[k]];
-                    const tc2li_ba_problem& p = *w.p;
-                    const size_t E = p.n_edges, P = p.n_points;
-                    const uint8_t* h = w.ws->h_result.p;
-                    memcpy(w.vp.poses.data(), h, p.n_poses * sizeof(Se3));
-                    for (int q = 0; q < p.n_poses; ++q) { memcpy(p.poses7 + 7 * q, w.vp.poses[q].q, 4 * sizeof(double)); memcpy(p.poses7 + 7 * q + 4, w.vp.poses[q].t, 3 * sizeof(double)); }
-                    memcpy(p.points3, h + p.n_poses * sizeof(Se3), 3 * P * sizeof(double));
-                    const uint8_t* hc = h + p.n_poses * sizeof(Se3) + 3 * P * sizeof(double);
-                    if (p.edge_chi2) memcpy(p.edge_chi2, hc, E * sizeof(double));
-                    if (p.edge_depth_positive) memcpy(p.edge_depth_positive, hc + E * sizeof(double), E);
+                    scatter_results(w, true);
+                    write_poses7(w.vp.poses, w.p->poses7);
                 });
                 for (int s : done) {
                     LockstepWindow& w = W[s];
@@ -427,18 +402,9 @@ void tc2li_ba_engine::run() {
             for (int s : retire) {
                 if (failed) break;
                 LockstepWindow& w = W[s];
-                const tc2li_ba_problem& p = *w.p;
-                const BaLmState& m = C.h_lm.p[s];
                 BaProblemDev pb = w.vp.pb;
-                if (m.parity) { std::swap(pb.poses, pb.poses_trial); std::swap(pb.points, pb.points_trial); }
-                const size_t E = p.n_edges, P = p.n_points;
-                uint8_t* h = w.ws->h_result.p;
-                uint8_t* hc = h + p.n_poses * sizeof(Se3) + 3 * P * sizeof(double);
-                auto add = [&](void* dst, const void* src, size_t nbytes) { G.h_copies_r.p[n_tasks++] = CopyTask{dst, src, nbytes}; max_bytes = std::max(max_bytes, nbytes); };
-                add(h, pb.poses, p.n_poses * sizeof(Se3));
-                add(h + p.n_poses * sizeof(Se3), pb.points, 3 * P * sizeof(double));
-                if (p.edge_chi2) add(hc, w.ws->d_chi2.p, E * sizeof(double));
-                if (p.edge_depth_positive) add(hc + E * sizeof(double), w.ws->d_depth.p, E);
+                if (C.h_lm.p[s].parity) { std::swap(pb.poses, pb.poses_trial); std::swap(pb.points, pb.points_trial); }
+                queue_result_copies(w, pb, true, [&](void* dst, const void* src, size_t nbytes) { G.h_copies_r.p[n_tasks++] = CopyTask{dst, src, nbytes}; max_bytes = std::max(max_bytes, nbytes); });
                 slots[s].state = kSlotRetiring; slots[s].seq = tick; if (kTiming) slots[s].t_retire = now();
             }
             if (!failed && n_tasks) { launch_copy_tasks(G.h_copies_r.p, (int)n_tasks, max_bytes, st); queued_any = true; }

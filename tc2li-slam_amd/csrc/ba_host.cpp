@@ -1,6 +1,6 @@
 // Host side of the optimisation entry points (include/tc2li_hip.h): tc2li_pose_optimization[_batch] replaces
 // Optimizer::PoseOptimization (SF/src/Optimizer.cc:816-1116).
-#include "ba_internal.hpp"
+#include "lockstep_host.hpp"
 
 using namespace tc2li;
 using namespace tc2li::ba_detail;
@@ -216,14 +216,12 @@ static int lv_ba_impl(double* poses7, const uint8_t* fixed, int n_poses, double*
     bool stop_agreed = false;
     const Collective kTrialSystem{d_red, (size_t)np * np + 2 * (size_t)np, TC2LI_REDUCE_SUM}, kTrialScalars{d_red, 3, TC2LI_REDUCE_SUM};
     auto stopped = [&] { return sharded ? stop_agreed : (stop_flag && *stop_flag); };
-    double lambda = -1, ni = 2;
-    int n_bad = 0, done = 0, trials_total = 0;
-    bool ok = true;
+    LmHost lm;
     std::vector<double> Swork((size_t)std::max(np * np, 1)), x(std::max(np, 1));
     std::vector<double> Hl, bl_;  // dense pose-pose contribution of the LiDAR edge
     if (lidar) { Hl.assign((size_t)np * np, 0.0); bl_.assign(np, 0.0); }
     tm[0] = now() - t_begin;
-    for (int it = 0; it < iterations && !stopped() && ok; ++it) {
+    for (int it = 0; it < iterations && !stopped() && lm.ok; ++it) {
         double t0 = now();
         const bool want_maxdiag = it == 0 && !(lambda_init > 0);
         if (sharded) next = Collective{d_red, 1, TC2LI_REDUCE_SUM};
@@ -275,34 +273,15 @@ static int lv_ba_impl(double* poses7, const uint8_t* fixed, int n_poses, double*
         TC2LI_SH_CHECK(hipStreamSynchronize(st));
         if (sharded && peer_failed()) return (int)TC2LI_ERR_COMM;
         tm[1] += now() - t0; t0 = now();
-        double currentChi = h_scal.p[0];
+        double chi = h_scal.p[0];
         double max_pose_diag = h_scal.p[2];
-        if (lidar) {
-            lidar->finish_error();
-            currentChi = lidar->chi2() + currentChi;
-            lidar->finish_linearization();  // constructQuadraticForm uses the stored Jacobian / Hessian when the cost grew
-            std::fill(Hl.begin(), Hl.end(), 0.0);
-            std::fill(bl_.begin(), bl_.end(), 0.0);
-            lidar->add_quadratic_form(pose_var.data(), np, Hl.data(), bl_.data());
-        }
-        if (need_diag) {
-            static const int dpos[6] = {0, 6, 11, 15, 18, 20};  // diagonal of the packed upper triangle
-            max_pose_diag = 0;
-            for (int j = 0; j < np; ++j)
-                max_pose_diag = std::max(max_pose_diag, std::fabs(ws.h_Hpp.p[27 * (size_t)(j / 6) + dpos[j % 6]] + (lidar ? Hl[(size_t)j * np + j] : 0.0)));
-        }
+        if (lidar) chi = lidar_after_linearize(*lidar, chi, pose_var.data(), np, Hl.data(), bl_.data());
+        if (need_diag) max_pose_diag = max_pose_diagonal(ws.h_Hpp.p, lidar ? Hl.data() : nullptr, np);
         tm[2] += now() - t0;
-        double tempChi = currentChi;
-        const double iniChi = currentChi;
-        if (it == 0) {
-            if (stats) stats->initial_chi2 = currentChi;
-            lambda = lambda_init > 0 ? lambda_init : 1e-5 * std::max(h_scal.p[1], max_pose_diag);
-            ni = 2;
-            n_bad = 0;
-        }
-        double rho = 0;
-        int qmax = 0;
+        if (it == 0 && stats) stats->initial_chi2 = chi;
+        lm.begin_iteration(chi, it == 0, lambda_init > 0 ? lambda_init : 1e-5 * std::max(h_scal.p[1], max_pose_diag));
         do {
+            const double lambda = lm.lambda;   // of this trial (decide() moves it on)
             bool ok2 = true;
             t0 = now();
             // a rank's part of the reduced camera system: its edges' Hpp and b_p, minus its landmarks' W Hll^-1 W^T and
@@ -330,7 +309,7 @@ static int lv_ba_impl(double* poses7, const uint8_t* fixed, int n_poses, double*
                 memcpy(h_xp.p, x.data(), np * sizeof(double));
                 tm[4] += now() - t0; t0 = now();
             }
-            double scale = 0;
+            double scale = 0, tempChi = 0;
             // pose part of computeScale(): b_p is what the finish kernel left in h_bs[np .. 2 np)
             for (int j = 0; j < np; ++j) scale += x[j] * (lambda * x[j] + h_bs.p[np + j]);
             if (ok2) {
@@ -364,40 +343,21 @@ static int lv_ba_impl(double* poses7, const uint8_t* fixed, int n_poses, double*
                     tempChi = lidar->chi2() + tempChi;
                     tm[6] += now() - t0;
                 }
-            } else {
-                tempChi = std::numeric_limits<double>::max();
             }
             if (sharded) next = np > 0 ? kTrialSystem : kTrialScalars;  // another trial (corrected below when the loops end)
-            rho = currentChi - tempChi;
-            scale += 1e-3;
-            rho /= scale;
-            if (rho > 0 && std::isfinite(tempChi)) {
-                lambda = lm_lambda_accepted(lambda, rho);
-                ni = 2;
-                currentChi = tempChi;
+            if (lm.decide(ok2, tempChi, scale)) {
                 std::swap(pb.poses, pb.poses_trial);
                 std::swap(pb.points, pb.points_trial);
-            } else {
-                lambda *= ni;
-                ni *= 2;
             }
-            qmax++;
-            trials_total++;
-        } while (rho < 0 && qmax < 10 && !stopped());
-        ++done;
-        if (stats) { stats->final_chi2 = currentChi; stats->final_lambda = lambda; }
-        if (qmax == 10 || rho == 0) { ok = false; continue; }
-        if ((iniChi - currentChi) * 1e3 < iniChi) n_bad++; else n_bad = 0;
-        if (n_bad >= 3) ok = false;
+        } while (lm.try_again(stopped()));
+        lm.end_iteration();
+        if (stats) { stats->final_chi2 = lm.currentChi; stats->final_lambda = lm.lambda; }
     }
     next = Collective{};  // the wrapper's result sum is the next collective: it tells the peers itself
     result_sum_next = true;
     if (sharded && shard_exit) *shard_exit = kShardResultSumNext;  // also for the plain HIP checks of the result copies below
-    if (stats) { stats->iterations = done; stats->trials = trials_total; stats->n_free_poses = n_free; }
-    if (lidar && lidar_stats) {
-        lidar_stats->n_planes = lidar->n_planes; lidar_stats->hessian_evaluations = lidar->hessian_evaluations;
-        lidar_stats->residual = lidar->error; lidar_stats->chi2 = lidar->chi2();
-    }
+    if (stats) { stats->iterations = lm.done; stats->trials = lm.trials_total; stats->n_free_poses = n_free; }
+    if (lidar && lidar_stats) write_lidar_stats(*lidar, lidar_stats);
     // ---- results ----
     ba_launch_depth(pb, d_depth.p, st);
     TC2LI_HIP_CHECK(hipGetLastError());
@@ -406,9 +366,9 @@ static int lv_ba_impl(double* poses7, const uint8_t* fixed, int n_poses, double*
     if (edge_chi2) TC2LI_HIP_CHECK(hipMemcpyAsync(edge_chi2, d_chi2.p, E * sizeof(double), hipMemcpyDeviceToHost, st));
     if (edge_depth_positive) TC2LI_HIP_CHECK(hipMemcpyAsync(edge_depth_positive, d_depth.p, E, hipMemcpyDeviceToHost, st));
     TC2LI_HIP_CHECK(hipStreamSynchronize(st));
-    for (int k = 0; k < n_poses; ++k) { memcpy(poses7 + 7 * k, poses[k].q, 4 * sizeof(double)); memcpy(poses7 + 7 * k + 4, poses[k].t, 3 * sizeof(double)); }
+    write_poses7(poses, poses7);
     if (kTiming) fprintf(stderr, "BA timing ms: setup %.3f linearize %.3f lidar-lin %.3f schur %.3f solve %.3f trial %.3f lidar-err %.3f total %.3f\n", tm[0], tm[1], tm[2], tm[3], tm[4], tm[5], tm[6], now() - t_begin);
-    return done;
+    return lm.done;
 #undef TC2LI_SH_CHECK
 }
 

@@ -1,5 +1,5 @@
 // Internal to the bundle-adjustment host code (ba_host.cpp, ba_lockstep.cpp, ba_engine.cpp, lvi_host.cpp): the options, the per-thread and
-// per-window work spaces, the visual problem's structure, the inertial term, and what the lock-step drivers share.  Not part of the C ABI.
+// per-window work spaces, the visual problem's structure and the inertial term (what the lock-step drivers share: lockstep_host.hpp).  Not part of the C ABI.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -457,217 +457,6 @@ struct InertialTerm {
     }
 };
 
-
-// ---- lock-step batch -----------------------------------------------------------------------------------------------------
-// All windows advance through the phases of the Levenberg-Marquardt loop together: one launch per kernel and one stream
-// synchronisation per phase for the whole batch (a window alone is bound by launch and synchronisation latency: its kernels take
-// 5-20 us each).  The arithmetic of a window is the one of tc2li_local_lv_bundle_adjustment (same kernel bodies, same host
-// steps), so the results are identical to optimising the windows one by one.
-struct LockstepWindow {
-    const tc2li_ba_problem* p = nullptr;
-    BaWorkspace* ws = nullptr;
-    VisualProblem vp;
-    BalmTerm* lidar = nullptr;
-    std::vector<uint8_t> extra_used;
-    std::vector<double> Swork, x;
-    double *Hl = nullptr, *bl_ = nullptr;  // the LiDAR term's (6K)^2 Hessian and 6K gradient (pinned: ws->h_Hl)
-    double lambda = -1, ni = 2, currentChi = 0, tempChi = 0, iniChi = 0, rho = 0, scale = 0, max_pose_diag = 0;
-    int n_bad = 0, done = 0, trials_total = 0, qmax = 0, it = 0, rc = 0;
-    int parity = 0;  // 1: the accepted estimate lives in the trial buffers of the slot (an odd number of accepted steps)
-    bool ok = true, ok2 = true, need_diag = false, want_maxdiag = false;
-    bool wants_hpp() const { return need_diag; }
-    bool stopped() const { return p->stop_flag && *p->stop_flag; }
-    bool wants_iteration() const { return rc >= 0 && it < p->iterations && !stopped() && ok; }
-};
-
-// The windows `list[c0 .. c1)` of a phase as kernel arguments (ba_device.hpp BaPhase): table index, parity / request bits, lambda --
-// and, beside them on the host, each window's own sizes, from which a launch wrapper cuts the compact grid of its kernel.
-template <typename Win>
-BaPhaseHost make_phase(const BaBatchSlot* d_table, const double* d_xp_area, const std::vector<Win>& W, const std::vector<int>& list, size_t c0, size_t c1, int expect = 0) {
-    BaPhaseHost ph;
-    ph.table = d_table; ph.xp_area = d_xp_area; ph.first = (int32_t)c0; ph.pad_ = 0; ph.expect = expect; ph.n = (int32_t)(c1 - c0);
-    ph.first_block[0] = 0;
-    for (size_t k = c0; k < c1; ++k) {
-        const Win& w = W[list[k]];
-        ph.win[k - c0] = (uint16_t)list[k];
-        ph.flags[k - c0] = (uint8_t)((w.parity ? kBaAcceptedInTrial : 0u) | (w.want_maxdiag ? kBaWantMaxdiag : 0u) | (w.wants_hpp() ? kBaWantHpp : 0u));
-        ph.lambda[k - c0] = w.lambda;
-        BaWindowExtent& e = ph.own[k - c0];
-        e = BaWindowExtent{};
-        if (w.rc < 0) continue;  // (its slot is empty: no kernel has work for it)
-        const BaProblemDev& pb = w.vp.pb;
-        e.n_groups = pb.n_groups; e.n_free_edges = pb.n_free_edges; e.n_edges = pb.n_edges; e.n_points = pb.n_points; e.n_poses = pb.n_poses; e.n_free = pb.n_free;
-        if (pb.sparse_schur && pb.n_free > 0) e.schur_lean_blocks = w.vp.n_slices * (pb.n_free > kSchurBlocksMaxFree ? 2 : 1);
-        e.trial_fused = pb.trial_fused;
-        if (w.lidar) { e.has_lidar = 1; e.lidar_chunks = w.lidar->dev.n_chunks; e.lidar_W = w.lidar->W; }
-    }
-    return ph;
-}
-// fn(phase, windows in it) for every piece of at most kBaPhaseMax windows of `list`
-template <typename Win, typename Fn>
-void for_phase_pieces(const BaBatchSlot* d_table, const double* d_xp_area, const std::vector<Win>& W, const std::vector<int>& list, Fn&& fn, int expect = 0) {
-    for (size_t c0 = 0; c0 < list.size(); c0 += kBaPhaseMax) {
-        const size_t c1 = std::min(list.size(), c0 + (size_t)kBaPhaseMax);
-        const BaPhaseHost ph = make_phase(d_table, d_xp_area, W, list, c0, c1, expect);
-        fn(ph, (int)(c1 - c0));
-    }
-}
-
-struct LockstepContext {
-    std::mutex mu;
-    std::vector<std::unique_ptr<BaWorkspace>> ws;
-    // slot table and, behind it, the two index lists of a phase: one host buffer, one device buffer, one copy per phase
-    DevBuf<uint8_t> d_table;
-    PinnedBuf<uint8_t> h_table;
-    PinnedBuf<CopyTask> h_tasks;  // the uploads / operand fills of a batch's setup, then its result copies: one launch each (copy_kernels.hip)
-    PinnedBuf<BasOutlierTask> h_outliers;  // prepared windows: the outlier rule after the BA, a task per window (ba_structure_kernels.hip)
-    PinnedBuf<CopyTask> h_table_task;  // the steps x_p of a trial phase on their way up: one entry for k_copy_tasks
-    // plane extraction of the batch's LiDAR windows on the device (balm_cut_kernels.hip): a task per window, those with points to cut
-    // compacted into the list the kernels read, and the uploads the LiDAR tasks deferred (the clouds)
-    PinnedBuf<BalmCutTask> h_cut, h_cut_list;
-    DevBuf<BalmCutTask> d_cut_list;
-    PinnedBuf<CopyTask> h_cut_copies;
-    // device-side LM: the windows' states (device), their initial values and the mirror the decide kernel writes (pinned), the stop words
-    DevBuf<BaLmState> d_lm;
-    PinnedBuf<BaLmState> h_lm_init, h_lm;
-    PinnedBuf<int32_t> h_stop;
-    hipEvent_t round_done[2] = {nullptr, nullptr};
-    hipStream_t st = nullptr;
-    ~LockstepContext() {
-        for (hipEvent_t e : round_done) if (e) (void)hipEventDestroy(e);
-        if (st) (void)hipStreamDestroy(st);
-    }
-};
-struct LockstepContexts { LockstepContext c[kMaxLockstepGroups]; };
-inline LockstepContext& lockstep_ctx(int group) { return shutdown_owned<LockstepContexts, 0>().c[group]; }
-
-
-// The LiDAR half of a lock-step batch's setup, after its tasks (the odd entries of `deferred`) have staged the clouds and described the
-// extractions in C.h_cut[0..n): the uploads and the extraction kernels of all windows are queued in one go, so that they run while the
-// host builds the visual structure.  plane_extraction_finish (after that) waits for them and gives every window its planes.
-inline bool plane_extraction_begin(LockstepContext& C, std::vector<std::vector<CopyTask>>& deferred, int n, hipStream_t st) {
-    int m = 0, max_points = 0, max_table = 0;
-    if (C.h_cut_list.ensure(std::max(n, 1)) != hipSuccess || C.d_cut_list.ensure(std::max(n, 1)) != hipSuccess) return false;
-    for (int i = 0; i < n; ++i) {
-        const BalmCutTask& t = C.h_cut.p[i];
-        if (t.n_points <= 0) continue;
-        C.h_cut_list.p[m++] = t;
-        max_points = std::max(max_points, t.n_points);
-        max_table = std::max(max_table, 1 << t.table_bits);
-    }
-    if (!m) return true;
-    size_t n_copies = 1, max_bytes = (size_t)m * sizeof(BalmCutTask);
-    for (int i = 0; i < n; ++i) n_copies += deferred[2 * (size_t)i + 1].size();
-    if (C.h_cut_copies.ensure(n_copies) != hipSuccess) return false;
-    size_t at = 0;
-    C.h_cut_copies.p[at++] = CopyTask{C.d_cut_list.p, C.h_cut_list.p, (size_t)m * sizeof(BalmCutTask)};
-    for (int i = 0; i < n; ++i) {
-        for (const CopyTask& t : deferred[2 * (size_t)i + 1]) { C.h_cut_copies.p[at++] = t; max_bytes = std::max(max_bytes, t.bytes); }
-        deferred[2 * (size_t)i + 1].clear();
-    }
-    launch_copy_tasks(C.h_cut_copies.p, (int)n_copies, max_bytes, st);
-    launch_balm_cut(C.d_cut_list.p, m, max_points, max_table, st);
-    return hipGetLastError() == hipSuccess;
-}
-// rc per window (0, or the error of a window whose planes could not be set up)
-inline bool plane_extraction_finish(LockstepContext& C, int n, std::vector<int>& rc_lidar, hipStream_t st) {
-    bool any = false;
-    for (int i = 0; i < n; ++i) any |= C.h_cut.p[i].n_points > 0;
-    if (!any) return true;
-    if (stream_wait_blocking(st) != hipSuccess) return false;
-    for (int i = 0; i < n; ++i) {
-        if (C.h_cut.p[i].n_points <= 0 || rc_lidar[i] < 0) continue;
-        rc_lidar[i] = C.ws[i]->lidar.finish_cut(st);
-    }
-    return true;
-}
-
-// What the launches of a phase have to cover: the largest sizes among the listed windows and which kernel families they need.  Taken over
-// the whole batch once (the fusion switches follow from it) and, with the device-side LM loop, again over the windows still alive whenever that
-// list shrinks: the rounds a few stragglers need after the bulk has finished are launched for THEIR sizes and families only (no dense-path
-// kernels once the last window of more than 21 free keyframes is done, the narrow solve kernel for narrow systems).
-template <typename Win>
-BaBatchExtent batch_extent(const std::vector<Win>& W, const std::vector<int>& list, bool* all_block_parts_out = nullptr) {
-    BaBatchExtent X{};
-    bool all_block_parts = true;
-    for (int i : list) {
-        if (W[i].rc < 0) continue;
-        const BaProblemDev& pb = W[i].vp.pb;
-        X.max_edges = std::max(X.max_edges, pb.n_edges); X.max_points = std::max(X.max_points, pb.n_points); X.max_poses = std::max(X.max_poses, pb.n_poses);
-        X.max_free = std::max(X.max_free, pb.n_free); X.max_free_edges = std::max(X.max_free_edges, pb.n_free_edges); X.max_groups = std::max(X.max_groups, pb.n_groups);
-        if (!(pb.sparse_schur && pb.schur_blocks && pb.n_free > 0 && W[i].vp.n_slices > 0)) all_block_parts = false;
-        if (pb.trial_fused) X.any_trial_fused = 1; else X.any_trial_unfused = 1;
-        if (pb.n_dups) X.any_dups = 1;
-        if (pb.sparse_schur && pb.schur_blocks) {
-            if (pb.n_free > 0 && W[i].vp.n_slices > 0) {
-                X.min_block_free = X.max_block_parts ? std::min(X.min_block_free, pb.n_free) : pb.n_free;
-                X.max_block_parts = std::max(X.max_block_parts, W[i].vp.n_slices); X.max_block_free = std::max(X.max_block_free, pb.n_free);
-                X.any_block_lean = 1;
-                if (pb.n_free > kSchurBlocksMaxFree) X.any_block_wide = 1;
-            }
-        } else if (!pb.sparse_schur) {
-            X.any_dense = 1; X.max_np_pad = std::max(X.max_np_pad, pb.np_pad); X.max_slices = std::max(X.max_slices, W[i].vp.n_slices);
-        }
-        if (W[i].lidar) {
-            X.max_planes = std::max(X.max_planes, W[i].lidar->n_planes); X.max_chunks = std::max(X.max_chunks, W[i].lidar->dev.n_chunks);
-            X.max_W = std::max(X.max_W, W[i].lidar->W);
-        }
-    }
-    if (all_block_parts_out) *all_block_parts_out = all_block_parts;
-    return X;
-}
-
-
-// ---- what the device-side Levenberg-Marquardt loop's two drivers share (ba_batch_lockstep's device-LM form, tc2li_ba_engine) ----
-// The table entry and the initial optimiser state of window w in slot i of context C: everything a phase leaves for the next one stays in
-// device memory, the decide kernel mirrors the window's state into C.h_lm[i].  The entry goes up with the caller's next copy launch
-// (C.d_table + i), the state from C.h_lm_init[i] to C.d_lm[i].
-inline void fill_device_lm_slot(BaBatchSlot& s, const LockstepWindow& w, LockstepContext& C, int i) {
-    s = BaBatchSlot{};
-    s.pb = w.vp.pb;
-    s.lambda_init = w.p->lambda_init; s.iterations = w.p->iterations;
-    s.n_slices = w.vp.n_slices; s.k_per_slice = w.vp.k_per_slice; s.has_lidar = w.lidar != nullptr;
-    const size_t nn = (size_t)w.vp.np * w.vp.np;
-    double* sc = w.ws->d_scal.p;
-    s.chi_out = sc; s.maxdiag_out = sc + 1; s.scale_out = sc + 3; s.chi_trial_out = sc + 4;
-    s.S_out = w.ws->d_S.p; s.bs_out = w.ws->d_bs.p; s.xp = s.x_dev = w.ws->d_xp.p; s.depth_out = w.ws->d_depth.p;
-    s.lm = C.d_lm.p + i; s.lm_host = C.h_lm.p + i; s.stop_host = C.h_stop.p + i; s.ok_host = &s.lm->solve_ok;
-    if (w.lidar) {
-        s.balm = w.lidar->dev;
-        s.Hl = w.ws->d_Hl.p; s.bl_lidar = w.ws->d_Hl.p + nn; s.balm.out = w.ws->d_balm_out.p; s.lidar_JH = w.ws->d_lidar_JH.p;
-        s.lidar_information = w.lidar->information;
-    }
-    BaLmState& m = C.h_lm_init.p[i];
-    m = BaLmState{};
-    m.lambda = -1; m.ni = 2; m.r1 = 1000; m.r2 = 1000; m.is_calc_hess = 1; m.ok = 1; m.solve_ok = 1;
-    m.status = w.wants_iteration() ? kLmIterate : kLmDone;
-    C.h_lm.p[i] = m;
-    C.h_stop.p[i] = 0;
-}
-// One round of the windows in `live` queued on st as ONE sequence without a host decision in it: linearise (windows whose status is
-// kLmIterate) + the plane term + begin, then Schur + solve + trial estimate + errors + decide (windows in kLmTrial).  live_lidar: those of
-// `live` with a LiDAR edge; lidar_first: those of them whose plane residual at the current estimate is not in place yet (their first
-// linearisation: later the accepted estimate is the last trial, whose residual and decompositions are).
-inline void queue_lm_round(const BaBatchSlot* d_table, const std::vector<LockstepWindow>& W, const std::vector<int>& live, const std::vector<int>& live_lidar,
-                           const std::vector<int>& lidar_first, const BaBatchExtent& XL, bool want_maxdiag, hipStream_t st) {
-    auto pieces_for = [&](const std::vector<int>& list, int expect, auto&& fn) { for_phase_pieces(d_table, (const double*)nullptr, W, list, fn, expect); };
-    pieces_for(live, kLmIterate, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_linearize(ph, cnt, XL, want_maxdiag, st); });
-    pieces_for(lidar_first, kLmIterate, [&](const BaPhaseHost& ph, int cnt) { balm_batch_launch_residual(ph, cnt, false, st); });
-    pieces_for(live_lidar, kLmIterate, [&](const BaPhaseHost& ph, int cnt) { balm_batch_launch_hessian(ph, cnt, XL, st); });
-    pieces_for(live, kLmIterate, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_lm_begin(ph, cnt, st); });
-    pieces_for(live, kLmTrial, [&](const BaPhaseHost& ph, int cnt) {
-        ba_batch_launch_schur(ph, cnt, XL, st);
-        ba_batch_launch_solve(ph, cnt, XL, st);
-        ba_batch_launch_trial(ph, cnt, XL, st);
-    });
-    if (XL.any_trial_unfused) pieces_for(live_lidar, kLmTrial, [&](const BaPhaseHost& ph, int cnt) { balm_batch_launch_residual(ph, cnt, true, st); });  // (windows with pb.trial_fused: inside the trial kernel)
-    pieces_for(live, kLmTrial, [&](const BaPhaseHost& ph, int cnt) { ba_batch_launch_lm_decide(ph, cnt, st); });
-}
-
-// the lock-step drivers (ba_lockstep.cpp, lvi_host.cpp): false = the batch goes through the one-window path
-// prepared: NULL, or one record per window (a window with sizes.n_poses == 0 in it is set up from its host arrays as ever)
-bool ba_batch_lockstep(const tc2li_ba_problem* problems, int n, const tc2li_camera* cam, WorkerPool& pool, int32_t* results, int group = 0,
-                       const BaPrepared* prepared = nullptr);
 
 }  // namespace ba_detail
 }  // namespace tc2li

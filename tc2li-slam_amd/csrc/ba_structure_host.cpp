@@ -5,7 +5,7 @@
 #include <cstring>
 #include <mutex>
 
-#include "ba_internal.hpp"
+#include "lockstep_host.hpp"
 
 namespace tc2li {
 namespace ba_detail {

@@ -19,6 +19,7 @@
 #include "common.hpp"
 #include "imu_init_device.hpp"
 #include "inertial_host.hpp"
+#include "lm_host.hpp"
 
 using namespace tc2li;
 using namespace tc2li::inertial_detail;
@@ -201,61 +202,47 @@ int tc2li_inertial_optimization(int n_kfs, const double* Rwb9, const double* twb
         memcpy(y.Rwg, R, sizeof(R));
         if (mono) y.s *= std::exp(xc[o_s]);
     };
-    double lambda = 0, ni = 2;
-    int n_bad = 0, done = 0, trials = 0;
+    // lambda after an accepted step with libm's pow, as this loop has always computed it and as its device twin (imu_init_kernels.hip)
+    // does with the device library's.  The local BA's loops use lm_lambda_accepted's correctly rounded cube so that host and device agree
+    // to the bit; pow differs from it in the last bit now and then, so taking it here would change results this entry has given so far.
+    auto accepted = [](double lambda, double rho) {
+        double alpha = 1. - std::pow((2 * rho - 1), 3);
+        alpha = std::min(alpha, 2. / 3.);
+        return lambda * std::max(1. / 3., alpha);
+    };
+    LmHost lm;
+    lm.lambda = 0;
     const double err0 = chi2_of(x);
     std::vector<double> xv, xc;
-    for (int it = 0; it < iterations; ++it) {
-        double currentChi = chi2_of(x), tempChi = currentChi;
-        const double iniChi = currentChi;
+    for (int it = 0; it < iterations && lm.ok; ++it) {
+        const double chi = chi2_of(x);
         build(x);
-        if (it == 0) {
-            if (prior_g != 0.f) lambda = 1e3;
-            else {
-                double md = 0;
-                for (int i = 0; i < Nv; ++i) for (int k = 0; k < 3; ++k) md = std::max(md, std::fabs(A.D[9 * (size_t)i + 4 * k]));
-                for (int k = 0; k < m; ++k) md = std::max(md, std::fabs(A.C[(size_t)k * m + k]));
-                lambda = 1e-5 * md;
-            }
-            ni = 2; n_bad = 0;
+        double lambda0 = 1e3;
+        if (it == 0 && prior_g == 0.f) {
+            double md = 0;
+            for (int i = 0; i < Nv; ++i) for (int k = 0; k < 3; ++k) md = std::max(md, std::fabs(A.D[9 * (size_t)i + 4 * k]));
+            for (int k = 0; k < m; ++k) md = std::max(md, std::fabs(A.C[(size_t)k * m + k]));
+            lambda0 = 1e-5 * md;
         }
-        double rho = 0;
-        int qmax = 0;
+        lm.begin_iteration(chi, it == 0, lambda0);
         do {
             const InitVars backup = x;
-            const bool ok2 = A.solve(lambda, xv, xc);
+            const bool ok2 = A.solve(lm.lambda, xv, xc);
             if (ok2) apply(x, xv, xc);
-            tempChi = ok2 ? chi2_of(x) : std::numeric_limits<double>::max();
-            rho = currentChi - tempChi;
+            const double trial_chi = ok2 ? chi2_of(x) : 0.0;
             double sc = 0;
             if (ok2) {
-                for (size_t k = 0; k < xv.size(); ++k) sc += xv[k] * (lambda * xv[k] + A.bv[k]);
-                for (int k = 0; k < m; ++k) sc += xc[k] * (lambda * xc[k] + A.bc[k]);
+                for (size_t k = 0; k < xv.size(); ++k) sc += xv[k] * (lm.lambda * xv[k] + A.bv[k]);
+                for (int k = 0; k < m; ++k) sc += xc[k] * (lm.lambda * xc[k] + A.bc[k]);
             }
-            sc += 1e-3;
-            rho /= sc;
-            if (rho > 0 && std::isfinite(tempChi)) {
-                double alpha = 1. - std::pow((2 * rho - 1), 3);
-                alpha = std::min(alpha, 2. / 3.);
-                lambda *= std::max(1. / 3., alpha);
-                ni = 2;
-                currentChi = tempChi;
-            } else {
-                lambda *= ni;
-                ni *= 2;
-                x = backup;
-            }
-            ++qmax; ++trials;
-        } while (rho < 0 && qmax < 10);
-        ++done;
-        if (qmax == 10 || rho == 0) break;
-        if ((iniChi - currentChi) * 1e3 < iniChi) n_bad++; else n_bad = 0;
-        if (n_bad >= 3) break;
+            if (!lm.decide(ok2, trial_chi, sc, accepted)) x = backup;
+        } while (lm.try_again(false));
+        lm.end_iteration();
     }
     memcpy(vel3, x.v.data(), 3 * (size_t)N * sizeof(double));
     memcpy(bg, x.bg, 24); memcpy(ba, x.ba, 24); memcpy(Rwg9, x.Rwg, 72); *scale = x.s;
-    if (stats) { stats->iterations = done; stats->trials = trials; stats->initial_chi2 = err0; stats->final_chi2 = chi2_of(x); stats->final_lambda = lambda; }
-    return done;
+    if (stats) { stats->iterations = lm.done; stats->trials = lm.trials_total; stats->initial_chi2 = err0; stats->final_chi2 = chi2_of(x); stats->final_lambda = lm.lambda; }
+    return lm.done;
 }
 
 int tc2li_inertial_scale_refinement(int n_kfs, const double* Rwb9, const double* twb3, const double* vel3, const double* bg3, const double* ba3,

@@ -273,6 +273,37 @@ def test_inertial_batch_on_the_device_and_on_the_host(pkg, cases, alone, monkeyp
         assert np.allclose(a["state"], b["state"], rtol=1e-9, atol=1e-10) and np.allclose(a["points"], b["points"], rtol=1e-9, atol=1e-9)
 
 
+def test_a_slot_carries_nothing_over_from_the_call_before(pkg, cases, alone, monkeypatch):
+    """A group's slot table is pinned memory that stays from call to call, and the forms of the loop use different fields of a slot: the
+    device-side LM its state pointers and stop word (lm, lm_host, stop_host), the host-driven forms none of them.  A slot that kept a
+    pointer of the call before sends a host-driven window through the device's decisions (the inertial batch did once).  In one process
+    and on one group: two LiDAR windows under the device-side LM, then two inertial windows, each of which must have the bits of its own
+    one-window call; then the other way round, the LiDAR windows checked.  The two drivers keep a context each, so the same LiDAR batch
+    also follows itself with the decisions on the host (TC2LI_BA_DEVICE_LM=0): there the table's memory is the same for certain.
+    Windows of at most 6 keyframes."""
+    group = 5
+    c0 = cases["inertial_converged"]
+    lidar = {"lidar_converged": cases["lidar_converged"], "lidar_first": cases["lidar_converged"]["first"]}
+    names = tuple(lidar)
+    assert all(len(c["window"]["poses"]) <= 6 and "win_pose" in c["window"] for c in lidar.values())
+    assert all(len(cases[n]["window"]["kf33"]) <= 6 for n in INERTIAL_ORDER)
+    set_env(monkeypatch, {})
+    assert pkg.capi.ba_options()["device_lm"] == 1
+    wanted = {n: run_alone(pkg, c["window"], c["cam"]) for n, c in lidar.items()}
+    wanted.update({n: alone[(), n] for n in INERTIAL_ORDER})
+    all_cases = dict(cases, **lidar)
+    lv = pkg.capi.BaBatch([lidar[n]["window"] for n in names], lidar["lidar_converged"]["cam"])
+    lvi = pkg.capi.LviBatch([cases[n]["window"] for n in INERTIAL_ORDER], c0["calib24"], c0["cam"])
+    for first, second in (((lv, names), (lvi, INERTIAL_ORDER)), ((lvi, INERTIAL_ORDER), (lv, names))):
+        for batch, which in (first, second):
+            assert batch.run_group(group) == len(which)
+        assert_batch_equals(second[0], second[1], wanted, "after the other driver's batch on group %d" % group, all_cases)
+    assert lv.run_group(group) == len(names)
+    set_env(monkeypatch, {"TC2LI_BA_DEVICE_LM": "0"})
+    assert lv.run_group(group) == len(names)
+    assert_batch_equals(lv, names, wanted, "host LM after device LM on group %d" % group, all_cases)
+
+
 # ---- the fused forms ------------------------------------------------------------------------------------------------------------
 FUSE_TRIAL_RTOL = 1e-9
 
