@@ -969,6 +969,143 @@ int tc2li_fuse_search_batch(tc2li_keyframe_store* store, const tc2li_fuse_item* 
                             const tc2li_map_point* points, int n_points_total, const uint8_t* valid, int n_valid_total,
                             int32_t* best_idx, int32_t* best_dist, int32_t* n_fused, void* stream);
 
+/* ---- LocalMapping::SearchInNeighbors (SF/src/LocalMapping.cc:728-837) in the reference's order, for many sequences in one call ----
+ * The reference fuses target by target: after target k a point that absorbed another (MapPoint::Replace, SF/src/MapPoint.cc:257-309)
+ * carries a new descriptor (ComputeDistinctiveDescriptors at :306), more observations and is "in" more keyframes, the loser is bad, and
+ * target k + 1 is searched with that state (ORBmatcher.cc:1311, :1323, :1328 read it).  One tc2li_fuse_search_batch call over all
+ * targets searches every target with the entry state and departs from the reference wherever a point absorbs another before a later
+ * target.  Here the whole function runs on the flat graph with the side effects simulated, as tc2li_keyframe_culling_batch simulates
+ * SetBadFlag.  Rig: pinhole stereo, NLeft == -1, mpCamera2 == nullptr, mbMonocular == false (nn = 10 at :731); the bRight calls of
+ * :787 and :817 are not covered.  One problem is one mpCurrentKeyFrame; all pointers are host memory and the call copies the arrays;
+ * indices are rows of the problem's own tables; row order stands in for the address order of the reference's
+ * std::map<KeyFrame*, tuple<int,int>> mObservations (as in tc2li_ba_window_problem).  The problems of a batch are independent and one
+ * store slot may appear in several problems.
+ *
+ * Keyframes (n_keyframes rows): the current keyframe, everything its covisibility lists and mPrevKF chain can reach within rule 1, and
+ * every observer of every point listed.
+ *   kf_slot        the keyframe's store slot; in the host entry an index into views
+ *   kf_flags       bit 0 isBad(); bit 1 mnFuseTargetForKF == mpCurrentKeyFrame->mnId on entry (:739)
+ *   prev_kf        mPrevKF (:765), -1 = NULL
+ *   poses7         [n][7] GetPose()
+ *   covis_offsets / covis   CSR of mvpOrderedConnectedKeyFrames (GetBestCovisibilityKeyFrames, :734, :749); only the rows of the current
+ *                  keyframe and of its first-ring targets are read
+ *   slot_offsets / slot_point   CSR of GetMapPointMatches() (:781, :802, :821), -1 = NULL; every row has the keyframe's stored keypoint count
+ * Points (n_points rows):
+ *   points         position, normal, the two invariance distances, max_distance_raw, mDescriptor: what tc2li_fuse_search_batch takes
+ *   point_flags    bit 0 isBad(); bit 1 mnFuseCandidateForKF == mpCurrentKeyFrame->mnId on entry (:809)
+ *   point_nobs     nObs (MapPoint.cc:171-174);  point_found / point_visible  mnFound / mnVisible (:304-305)
+ *   point_ref_kf   mpRefKF (:477);  point_ref_level_scale  as in tc2li_map_points_refresh (:494)
+ *   obs_offsets / obs_kf / obs_index   CSR of mObservations; a row ascends strictly by keyframe row; obs_index is the left index
+ * Scalars: current = row of mpCurrentKeyFrame; inertial = mbInertial (:763); abort = mbAbortBA AS IT IS WHEN THE CALL IS MADE -- the
+ * reference reads it live at :758 and :791; the snapshot is a stated deviation, as abort_ba is in tc2li_culling_problem;
+ * last_level_scale = mvScaleFactors[nLevels - 1] (MapPoint.cc:500).  The search radius factor is Fuse's default th = 3.0.
+ *
+ * Rule 1, targets (:731-777).  The first 10 entries of the current keyframe's covisibility row (:734), skipping a keyframe that is bad
+ *   or marked (:739); each keyframe taken is marked (:742).  For i over the targets gathered by that first loop (imax is fixed before
+ *   the loop, :747) the first 20 of target i's row (:749), skipping a keyframe that is bad, marked or the current one (:753), marking
+ *   what is taken (:756).  With abort the loop breaks after i = 0 has been processed (:758).  With inertial, mPrevKF is walked from the
+ *   current keyframe while the targets number fewer than 20 (:765-776): bad or marked keyframes are passed over, the others taken and
+ *   marked.  At most 10 + 10 * 20 = 210 targets.
+ * Rule 2, stage 1 (:781-788).  vpMapPointMatches is the current keyframe's slot row as it is BEFORE stage 1 (:781 copies it): later
+ *   replacements in that row do not change the list.  For every target in order: Fuse(target, list) (:786).
+ * Rule 3, Fuse (ORBmatcher.cc:1186-1344) walks the list in order.  An entry is skipped when it is NULL (:1190), bad NOW (:1196), or in
+ *   the target keyframe NOW -- its observation list holds the target's row (:1201).  Otherwise the search runs (:1207-1318): exactly
+ *   the arithmetic of tc2li_fuse_search with the point's CURRENT descriptor (:1265).  With bestDist <= 50 (:1321) let q be the live
+ *   occupant of slot bestIdx of the target (:1323).  No occupant: AddObservation(target, bestIdx) (:1336; MapPoint.cc:150-175: nObs += 2
+ *   if u_right[bestIdx] >= 0, else += 1) and AddMapPoint (:1337).  Occupant not bad (:1326): nObs(q) > nObs(p) ? p.Replace(q) :
+ *   q.Replace(p) (:1328-1331).  Occupant bad: nothing happens.  nFused counts all three outcomes (:1339).
+ * Rule 4, x.Replace(w) (MapPoint.cc:257-309).  x == w: nothing (:259).  Otherwise, for x's observations in row order (:275): w not in that
+ *   keyframe (:283) -- the keyframe's slot takes w (:286) and w gains the observation with its nObs weight (:287); w already in that
+ *   keyframe -- the slot becomes NULL (:297).  x is bad, holds no observations and replaced[x] = w (:267-272); w.found += x.found,
+ *   w.visible += x.visible (:304-305); w.ComputeDistinctiveDescriptors() (:306; :338-412): the descriptors of w's observations in
+ *   keyframes that are not bad (:361), in row order, the Hamming matrix (:381-390), per row the sorted row's entry (int)(0.5 * (N - 1))
+ *   (:399), the first row with the least such median becomes mDescriptor (:401-410).  mpRefKF, position, normal and the distances do
+ *   not change here.
+ * Rule 5, abort (:791).  With abort the call returns after stage 1: no stage 2, no refresh, no candidate marks.
+ * Rule 6, stage 2 (:795-817).  The targets in order and their slot rows AS THEY ARE AFTER STAGE 1 (:802), slots ascending: a point is
+ *   taken if it is not NULL (:807), not bad and not marked (:809), and is then marked (:811).  This is vpFuseCandidates (:812).  Then
+ *   Fuse(current keyframe, candidates) (:816) by rule 3.
+ * Rule 7, refresh (:821-833).  For every slot of the current keyframe's row as it is now (:821) that holds a point that is not bad
+ *   (:825-827): ComputeDistinctiveDescriptors (:829) and UpdateNormalAndDepth (:830; MapPoint.cc:435-503), the arithmetic of
+ *   tc2li_map_points_refresh with the camera centres of poses7; a point without observations is left alone (:352, :450).
+ * UpdateConnections (:836) stays tc2li_update_connections_batch; the end state below is what it needs.
+ *
+ * Why a target's list entries may be searched side by side (the device path), for a graph in which every slot's point has the matching
+ * observation: (a) an entry that is skipped when the target starts stays skipped, because NULL and bad are final and a point leaves a
+ * keyframe only by becoming bad (rule 4); (b) an earlier entry of the same target changes another point only through Replace, whose
+ * loser is bad and whose winner afterwards holds the target's row -- an occupant with the matching observation held it already, the
+ * list point gains it at :286-287 from such an occupant -- so every point whose descriptor or observations changed during the target
+ * is skipped by rule 3 when its turn comes; (c) hence the search of an entry that is not skipped at its turn reads exactly the state
+ * the point had when the target started, and only the occupant of the slot and the nObs comparison are read live.
+ * The entries do NOT require that consistency: the rules above are applied as written to a slot that holds a point without the
+ * matching observation.  There (b) can fail -- the winner may stay outside the target and still have an entry ahead in the list, which
+ * the reference then searches with the winner's new descriptor -- so the device path checks every Replace for exactly that (winner
+ * not in the target, winner ahead in the list) and hands such a problem to the host twin (TC2LI_NEIGHBORS_ON_HOST).
+ *
+ * Outputs; the capacities are the caller's and an array of capacity 0 may be NULL.
+ *   counts [TC2LI_NEIGHBORS_COUNTS], always written: status (TC2LI_NEIGHBORS_ON_DEVICE / _ON_HOST), targets, candidates, ops, entries
+ *                  of the observation CSR out, points refreshed, nFused summed over stage 1, nFused of stage 2 (fused_current, :816)
+ *   targets, target_fused [target_capacity]   vpTargetKFs in order and Fuse's return value per target (:786)
+ *   candidates [candidate_capacity]           vpFuseCandidates in order (:812)
+ *   ops [op_capacity]   every state change in execution order: kind ADD_OBSERVATION (:1336) or REPLACE (:1329, :1331), stage_target =
+ *                  the target's ordinal (n_targets for stage 2), point = the list's point, occupant (or -1), winner (REPLACE: the
+ *                  survivor; else -1), kf, idx = the keyframe row and keypoint searched.  x == w and a bad occupant change nothing and
+ *                  give no op.  A shim replays these on its objects.
+ *   slot_point_out (the shape of slot_point), point_bad_out, point_replaced (-1 or mpReplaced, :272), point_nobs_out, point_found_out,
+ *   point_visible_out, obs_offsets_out [n_points + 1], obs_kf_out, obs_index_out [obs_capacity]: the end state
+ *   desc_kf, desc_index [n_points]   the observation whose descriptor is mDescriptor at the end (:410) of a point that is not bad then;
+ *                  -1 where ComputeDistinctiveDescriptors did not run or returned early (:347, :352, :374) and for points that are bad
+ *   refreshed [n_points] and, where it is set, normals_out [n][3], min_distance_out, max_distance_out (MapPoint.cc:499-501)
+ * Errors.  TC2LI_ERR_INVALID before any device work and with nothing written: sizes, NULLs, offsets that do not ascend, indices out of
+ *   range, observation rows that do not ascend strictly, a slot that is empty or out of range, a slot-row length that is not the stored
+ *   keypoint count, a prev_kf chain that returns to itself within the walk of rule 1.  TC2LI_ERR_CAPACITY: counts is written for every
+ *   problem with the sizes needed and no list of any problem; the call repeated with those capacities succeeds (the contract of
+ *   tc2li_local_map_update_batch).
+ * The device entry: one workgroup owns one problem from the targets to the refresh; one upload, one launch whatever n_problems, one
+ * download.  A problem beyond a limit of tc2li_search_in_neighbors_limits -- the observations of a point are only known while running --
+ * or one that the check of the paragraph above catches, is finished inside the call by the host twin, reports TC2LI_NEIGHBORS_ON_HOST
+ * in counts[0] (so a caller sees how often that happens) and has the same outputs.  Both entries
+ * return n_problems. */
+#define TC2LI_NEIGHBORS_COUNTS 8
+#define TC2LI_NEIGHBORS_ON_DEVICE 0
+#define TC2LI_NEIGHBORS_ON_HOST 1
+#define TC2LI_NEIGHBORS_ADD_OBSERVATION 1
+#define TC2LI_NEIGHBORS_REPLACE 2
+#define TC2LI_NEIGHBORS_MAX_TARGETS 210
+typedef struct tc2li_neighbors_op {
+    int32_t kind, stage_target, point, occupant, winner, kf, idx, pad_;
+} tc2li_neighbors_op;
+typedef struct tc2li_neighbors_problem {
+    const int32_t* kf_slot; const uint8_t* kf_flags; const int32_t* prev_kf; const float* poses7;
+    const int32_t *covis_offsets, *covis, *slot_offsets, *slot_point;
+    const tc2li_map_point* points; const uint8_t* point_flags;
+    const int32_t *point_nobs, *point_found, *point_visible, *point_ref_kf; const float* point_ref_level_scale;
+    const int32_t *obs_offsets, *obs_kf, *obs_index;
+    int32_t* counts; int32_t *targets, *target_fused, *candidates; tc2li_neighbors_op* ops;
+    int32_t* slot_point_out; uint8_t* point_bad_out;
+    int32_t *point_replaced, *point_nobs_out, *point_found_out, *point_visible_out;
+    int32_t *obs_offsets_out, *obs_kf_out, *obs_index_out, *desc_kf, *desc_index;
+    uint8_t* refreshed; float *normals_out, *min_distance_out, *max_distance_out;
+    int32_t n_keyframes, n_points, current;
+    int32_t target_capacity, candidate_capacity, op_capacity, obs_capacity;
+    float last_level_scale;
+    uint8_t inertial, abort, pad_[6];
+} tc2li_neighbors_problem;
+int tc2li_search_in_neighbors_batch(tc2li_keyframe_store* store, const tc2li_neighbors_problem* problems, int n_problems,
+                                    const float cam4[4], float bf, const float* scale_factors, const float* inv_level_sigma2,
+                                    int n_levels, float log_scale_factor, void* stream);
+/* The host twin: plain sequential C++, one problem per worker thread under the host thread budget; kf_slot indexes views (keys,
+ * descriptors, u_right are read; bounds4[k] = mnMinX, mnMaxX, mnMinY, mnMaxY of view k), whose feature grids (KeyFrame.cc:716-760) are
+ * built on the host.  counts[0] is TC2LI_NEIGHBORS_ON_HOST.  Needs no device. */
+int tc2li_host_search_in_neighbors_batch(const tc2li_keyframe_view* views, const float* bounds4, int n_views,
+                                         const tc2li_neighbors_problem* problems, int n_problems, const float cam4[4], float bf,
+                                         const float* scale_factors, const float* inv_level_sigma2, int n_levels,
+                                         float log_scale_factor);
+/* The limits of the device path: out[0] the most observations a point may reach (those of tc2li_map_points_refresh's descriptor step),
+ * out[1] the most keypoints of a keyframe, out[2] / out[3] the most points / keyframes of a problem whose marks live in LDS, out[4]
+ * threads per problem.  Returns how many values there are; needs no device. */
+int tc2li_search_in_neighbors_limits(int32_t* out, int capacity);
+
 /* Per-map-point refresh of local mapping after a local BA / after creating or fusing points (LocalMapping.cc, Optimizer.cc:1506,
  * OptimizerWithLidar.cc:484 `pMP->UpdateNormalAndDepth()`; `ComputeDistinctiveDescriptors` in CreateNewMapPoints / Fuse):
  * MapPoint::ComputeDistinctiveDescriptors (SF/src/MapPoint.cc:338-412) and MapPoint::UpdateNormalAndDepth (:444-503) for a flat

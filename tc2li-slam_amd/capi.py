@@ -1301,6 +1301,134 @@ def fuse_search_batch(store, items, cam4, bf, scale_factors, inv_level_sigma2, l
     return nf[:len(items)], bi[:m], bd[:m]
 
 
+# ---- LocalMapping::SearchInNeighbors in the reference's order (tc2li_search_in_neighbors_batch) ------------------------------------------
+_NEIGHBORS_INPUTS = (("kf_slot", np.int32), ("kf_flags", np.uint8), ("prev_kf", np.int32), ("poses7", np.float32), ("covis_offsets", np.int32),
+                     ("covis", np.int32), ("slot_offsets", np.int32), ("slot_point", np.int32), ("points", None), ("point_flags", np.uint8),
+                     ("point_nobs", np.int32), ("point_found", np.int32), ("point_visible", np.int32), ("point_ref_kf", np.int32),
+                     ("point_ref_level_scale", np.float32), ("obs_offsets", np.int32), ("obs_kf", np.int32), ("obs_index", np.int32))
+_NEIGHBORS_OUTPUTS = ("counts", "targets", "target_fused", "candidates", "ops", "slot_point_out", "point_bad_out", "point_replaced", "point_nobs_out",
+                      "point_found_out", "point_visible_out", "obs_offsets_out", "obs_kf_out", "obs_index_out", "desc_kf", "desc_index", "refreshed",
+                      "normals_out", "min_distance_out", "max_distance_out")
+NEIGHBORS_OP_DTYPE = np.dtype([(k, "<i4") for k in ("kind", "stage_target", "point", "occupant", "winner", "kf", "idx", "pad_")])
+NEIGHBORS_COUNTS = ("status", "targets", "candidates", "ops", "observations", "refreshed", "fused_stage1", "fused_current")
+NEIGHBORS_ON_DEVICE, NEIGHBORS_ON_HOST, NEIGHBORS_ADD_OBSERVATION, NEIGHBORS_REPLACE, NEIGHBORS_MAX_TARGETS = 0, 1, 1, 2, 210
+
+
+class NeighborsProblem(C.Structure):
+    """tc2li_neighbors_problem"""
+    _fields_ = [(k, C.c_void_p) for k, _ in _NEIGHBORS_INPUTS] + [(k, C.c_void_p) for k in _NEIGHBORS_OUTPUTS] \
+        + [(k, C.c_int32) for k in ("n_keyframes", "n_points", "current", "target_capacity", "candidate_capacity", "op_capacity", "obs_capacity")] \
+        + [("last_level_scale", C.c_float), ("inertial", C.c_uint8), ("abort", C.c_uint8), ("pad_", C.c_uint8 * 6)]
+
+
+def search_in_neighbors_limits():
+    """tc2li_search_in_neighbors_limits -> {observations, keypoints, lds_points, lds_keyframes, threads}: beyond the first four a problem
+    of ``search_in_neighbors_batch`` is computed by the host twin inside the call."""
+    out = np.zeros(8, np.int32)
+    f = lib().tc2li_search_in_neighbors_limits
+    f.argtypes = [C.c_void_p, C.c_int]
+    n = _check(f(out.ctypes.data, len(out)))
+    return dict(zip(("observations", "keypoints", "lds_points", "lds_keyframes", "threads"), [int(v) for v in out[:n]]))
+
+
+def pack_neighbors_problems(problems, capacities=None):
+    """The tc2li_neighbors_problem array of a batch with its output arrays -> (array, outputs per problem, what must stay alive).
+    problems: dicts with the input arrays of tc2li_neighbors_problem (points: MAP_POINT_DTYPE; poses7 [n, 7]) and current, inertial, abort,
+    last_level_scale.  capacities: per problem a dict with targets / candidates / ops / observations; default: what always suffices for
+    targets (210) and candidates (n_points), and for ops and observations a guess that the caller enlarges from ``counts`` on
+    TC2LI_ERR_CAPACITY (``search_in_neighbors_batch`` does)."""
+    P = len(problems)
+    arr, outs, keep = (NeighborsProblem * max(P, 1))(), [], []
+    for i, p in enumerate(problems):
+        a = {k: np.ascontiguousarray(p[k], MAP_POINT_DTYPE if t is None else t) for k, t in _NEIGHBORS_INPUTS}
+        nk, npts = len(a["kf_slot"]), len(a["points"])
+        if len(a["covis_offsets"]) != nk + 1 or len(a["slot_offsets"]) != nk + 1 or len(a["obs_offsets"]) != npts + 1 or a["poses7"].size != 7 * nk:
+            raise ValueError("problem %d: offsets or poses do not fit the tables" % i)
+        for k in ("kf_flags", "prev_kf"):
+            if len(a[k]) != nk:
+                raise ValueError("problem %d: %s has %d rows for %d keyframes" % (i, k, len(a[k]), nk))
+        for k in ("point_flags", "point_nobs", "point_found", "point_visible", "point_ref_kf", "point_ref_level_scale"):
+            if len(a[k]) != npts:
+                raise ValueError("problem %d: %s has %d rows for %d points" % (i, k, len(a[k]), npts))
+        ns, no = int(a["slot_offsets"][-1]), int(a["obs_offsets"][-1])
+        if len(a["slot_point"]) < ns or len(a["covis"]) < int(a["covis_offsets"][-1]) or len(a["obs_kf"]) < no or len(a["obs_index"]) < no:
+            raise ValueError("problem %d: slot, covisibility or observation arrays are shorter than their offsets say" % i)
+        cap = dict(targets=NEIGHBORS_MAX_TARGETS, candidates=npts, ops=max(64, ns // 4), observations=2 * no + 64)
+        cap.update((capacities[i] if capacities is not None else None) or {})
+        o = dict(counts=np.zeros(len(NEIGHBORS_COUNTS), np.int32), targets=np.full(cap["targets"], -1, np.int32), target_fused=np.zeros(cap["targets"], np.int32),
+                 candidates=np.full(cap["candidates"], -1, np.int32), ops=np.zeros(cap["ops"], NEIGHBORS_OP_DTYPE), slot_point_out=np.full(ns, -2, np.int32),
+                 point_bad_out=np.zeros(npts, np.uint8), point_replaced=np.full(npts, -2, np.int32), point_nobs_out=np.zeros(npts, np.int32),
+                 point_found_out=np.zeros(npts, np.int32), point_visible_out=np.zeros(npts, np.int32), obs_offsets_out=np.zeros(npts + 1, np.int32),
+                 obs_kf_out=np.full(cap["observations"], -1, np.int32), obs_index_out=np.full(cap["observations"], -1, np.int32),
+                 desc_kf=np.full(npts, -2, np.int32), desc_index=np.full(npts, -2, np.int32), refreshed=np.zeros(npts, np.uint8),
+                 normals_out=np.zeros((npts, 3), np.float32), min_distance_out=np.zeros(npts, np.float32), max_distance_out=np.zeros(npts, np.float32))
+        for k, v in list(a.items()) + list(o.items()):
+            setattr(arr[i], k, v.ctypes.data if v.size else None)
+        arr[i].n_keyframes, arr[i].n_points, arr[i].current = nk, npts, int(p["current"])
+        arr[i].target_capacity, arr[i].candidate_capacity, arr[i].op_capacity, arr[i].obs_capacity = cap["targets"], cap["candidates"], cap["ops"], cap["observations"]
+        arr[i].last_level_scale = float(p["last_level_scale"])
+        arr[i].inertial, arr[i].abort = int(bool(p.get("inertial", False))), int(bool(p.get("abort", False)))
+        keep.append(a)
+        outs.append(o)
+    return arr, outs, keep
+
+
+def run_search_in_neighbors_batch(arr, n_problems, cam4, bf, scale_factors, inv_level_sigma2, log_scale_factor, store=None, views=None, bounds=None,
+                                  stream=0):
+    """tc2li_search_in_neighbors_batch on ``store`` or, with ``views`` (the dicts ``pack_keyframe_views`` takes) and ``bounds``,
+    tc2li_host_search_in_neighbors_batch -> the call's return value (no exception: the caller reads the code)."""
+    c4 = np.ascontiguousarray(cam4, np.float32)
+    sf, isg = np.ascontiguousarray(scale_factors, np.float32), np.ascontiguousarray(inv_level_sigma2, np.float32)
+    tail = [C.addressof(arr), int(n_problems), c4.ctypes.data, float(bf), sf.ctypes.data, isg.ctypes.data, len(sf), float(log_scale_factor)]
+    if store is not None:
+        f = lib().tc2li_search_in_neighbors_batch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]
+        return f(store._handle(), *tail, C.c_void_p(stream))
+    items = []
+    for kf in views:
+        it = dict(kf)
+        it.setdefault("has_point", np.zeros(len(kf["keys"]), np.uint8))
+        it.setdefault("pose7", np.float32([0, 0, 0, 1, 0, 0, 0]))
+        items.append(it)
+    b = np.ascontiguousarray(np.broadcast_to(np.asarray(bounds, np.float32).reshape(-1, 4), (len(items), 4)), np.float32)
+    varr, keep = pack_keyframe_views(items)
+    f = lib().tc2li_host_search_in_neighbors_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_float]
+    rc = f(C.addressof(varr), b.ctypes.data, len(items), *tail)
+    del keep
+    return rc
+
+
+def _neighbors_results(outs):
+    res = []
+    for o in outs:
+        c = dict(zip(NEIGHBORS_COUNTS, [int(v) for v in o["counts"]]))
+        r = dict(o, counts=c, status=c["status"], targets=o["targets"][:c["targets"]], target_fused=o["target_fused"][:c["targets"]],
+                 candidates=o["candidates"][:c["candidates"]], ops=o["ops"][:c["ops"]], obs_kf_out=o["obs_kf_out"][:c["observations"]],
+                 obs_index_out=o["obs_index_out"][:c["observations"]], fused_current=c["fused_current"])
+        res.append(r)
+    return res
+
+
+def search_in_neighbors_batch(problems, cam4, bf, scale_factors, inv_level_sigma2, log_scale_factor, store=None, views=None, bounds=None, stream=0,
+                              capacities=None):
+    """One ``LocalMapping::SearchInNeighbors`` per problem in the reference's order (``tc2li_search_in_neighbors_batch``; with ``views`` and
+    ``bounds`` in place of ``store`` the host twin) -> one dict per problem: counts (dict), status, targets, target_fused, candidates, ops
+    (NEIGHBORS_OP_DTYPE), fused_current and the end state (slot_point_out, point_bad_out, point_replaced, point_nobs_out, point_found_out,
+    point_visible_out, obs_offsets_out, obs_kf_out, obs_index_out, desc_kf, desc_index, refreshed, normals_out, min_distance_out,
+    max_distance_out).  On TC2LI_ERR_CAPACITY the call is repeated once with the sizes ``counts`` reports."""
+    for attempt in range(2):
+        arr, outs, keep = pack_neighbors_problems(problems, capacities)
+        rc = run_search_in_neighbors_batch(arr, len(problems), cam4, bf, scale_factors, inv_level_sigma2, log_scale_factor, store, views, bounds, stream)
+        del keep
+        if rc == -5 and attempt == 0 and capacities is None:   # TC2LI_ERR_CAPACITY
+            capacities = [dict(targets=max(int(o["counts"][1]), 1), candidates=max(int(o["counts"][2]), 1), ops=max(int(o["counts"][3]), 1),
+                               observations=max(int(o["counts"][4]), 1)) for o in outs]
+            continue
+        _check(rc)
+        return _neighbors_results(outs)
+
+
 def map_points_refresh(obs_off, descriptors, centres, positions, ref_centres, level_scale, last_scale, stream=0):
     """``MapPoint::ComputeDistinctiveDescriptors`` + ``UpdateNormalAndDepth`` for a flat list of points ->
     (best_obs, normals [n, 3], min_distance, max_distance)."""

@@ -20,6 +20,7 @@
 #include "mapping_device.hpp"
 #include "mapping_host.hpp"
 #include "matcher_device.hpp"
+#include "neighbors_device.hpp"
 #include "packed_batch.hpp"
 
 using namespace tc2li;
@@ -147,6 +148,20 @@ void tc2li::keyframe_store_baw(tc2li_keyframe_store* S, BawStore* where, int32_t
     *where = BawStore{S->slab + S->o_slots, S->stride, S->s_keys, S->s_ur};
     std::lock_guard<std::mutex> lk(S->info_mu);
     for (int s = 0; s < capacity && s < S->max_kf; ++s) { n_keypoints[s] = S->info[s].n < 0 ? -1 : S->info[s].n; n_levels[s] = S->info[s].n_levels; }
+}
+
+// what tc2li_search_in_neighbors_batch reads of the store (neighbors_host.cpp)
+bool tc2li::keyframe_store_neighbors(tc2li_keyframe_store* S, int s, NbKf* out, int32_t* n_levels) {
+    if (!slot_in_range(S, s)) return false;
+    std::lock_guard<std::mutex> lk(S->info_mu);
+    const SlotInfo& si = S->info[s];
+    if (si.n < 0) return false;
+    const KfDev d = S->view(s, si);
+    out->keys = d.keys; out->desc = d.desc; out->u_right = d.u_right; out->cell_start = S->cell_start(s); out->items = S->items(s);
+    out->n = si.n;
+    memcpy(out->bounds, si.bounds, 16);
+    *n_levels = si.n_levels;
+    return true;
 }
 
 extern "C" int tc2li_keyframe_store_put_batch(tc2li_keyframe_store* S, int n, const int32_t* slots, const tc2li_keyframe_view* views,

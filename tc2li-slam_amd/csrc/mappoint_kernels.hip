@@ -5,6 +5,7 @@
 // 16-bit values) and finds the row's median -- the value sorted[(int)(0.5 (N - 1))] of the reference -- by bisection on the
 // value range 0..256 (the smallest v with at least k + 1 entries <= v); the first row with the least median wins, as in the
 // reference's loop.  The mean viewing direction is accumulated by one lane in observation order (float, like the reference).
+// row_median of fuse_search.hpp is the same bisection without the table (SearchInNeighbors, both sides): keep the two in step.
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
