@@ -1856,6 +1856,95 @@ int tc2li_host_update_best_covisibles_batch(const int32_t* row_offsets, const in
  * kernel.  Returns 3.  No reference counterpart. */
 int tc2li_connections_limits(int32_t* out, int capacity);
 
+/* ---- LocalMapping::ProcessNewKeyFrame (SF/src/LocalMapping.cc:312-352) for many sequences in one call ----
+ * The first stage of LocalMapping::Run: the new keyframe's tracked points gain their observation (:326-345), mlpRecentAddedMapPoints is
+ * filled (:341) and the first KeyFrame::UpdateConnections is made (:348), on the flat graph.  ComputeBoW (:321) is
+ * tc2li_orb_compute_bow_batch; the queue (:314-318), mpAtlas->AddKeyFrame (:351) and mbFirstConnection stay the caller's.  Rig: that of
+ * tc2li_search_in_neighbors_batch (pinhole stereo, NLeft == -1, mpCamera2 == nullptr, every observation index is a left index >= 0).
+ * One problem is one mpCurrentKeyFrame; all pointers are host memory and the call copies the arrays; indices are rows of the problem's own
+ * tables; row order stands in for the address order of std::map<KeyFrame*, ...> (as in tc2li_neighbors_problem).  Problems of a batch are
+ * independent: two problems over one graph both see the input state, and one store slot may appear in several problems.
+ *
+ * Inputs.  `conn` is a tc2li_connections_problem and is read as that entry reads it -- kf_flags, conn_offsets / conn_kf / conn_weight,
+ * current, slot_point [n_slots] (GetMapPointMatches() at :324, -1 = NULL; n_slots must equal the stored keypoint count of the current
+ * keyframe's slot), point_bad, first_connection, is_init_kf, the capacities and the outputs -- except that its obs_offsets / obs_kf are the
+ * observation rows ON ENTRY (a row ascends strictly by keyframe row) while the votes of rule 4 are taken on the END state.  Beside it:
+ *   keyframes (conn.n_keyframes rows: the current keyframe, every observer of every point in its slot row, whatever the connection rows name):
+ *     kf_slot   the store slot (host entry: an index into views); -1 is allowed only for a row that observes no point of the slot row
+ *     centres   [n][3] GetCameraCenter()
+ *   points (conn.n_points rows): positions [n][3]; point_nobs nObs; point_ref_kf the row of mpRefKF and point_ref_level_scale as in
+ *     tc2li_map_points_refresh; obs_index, parallel to conn.obs_kf: the left index
+ *   last_level_scale = mvScaleFactors[nLevels - 1] (MapPoint.cc:500)
+ *
+ * Rule 1, association (:326-345).  Slots ascend.  A NULL slot (:329) and a bad point (:331) are skipped.  If the current keyframe's row is
+ *   not in the point's observation row NOW (IsInKeyFrame, MapPoint.cc:429-433): AddObservation(current, i) (MapPoint.cc:150-175) inserts
+ *   the pair at its place in row order and adds 2 to nObs if u_right[i] >= 0, else 1; UpdateNormalAndDepth (:336) and
+ *   ComputeDistinctiveDescriptors (:337) then run on the new state.  Otherwise the point is pushed to the recent list (:341), which is in
+ *   slot order; a point held by two observed slots is pushed twice.  A point held by two slots and not yet observed is associated by the
+ *   lower slot and pushed by the higher one.  A point observed from the current keyframe at an index other than its slot is simply "in":
+ *   recent list, nothing changes.
+ * Rule 2, UpdateNormalAndDepth (MapPoint.cc:435-503).  The normal is the float sum of (pos - centre) / |pos - centre| over every observation
+ *   in row order, BAD KEYFRAMES INCLUDED (:456-475 has no isBad() test), divided by their number; max_distance = |pos - centres[point_ref_kf]|
+ *   * point_ref_level_scale (:499), min_distance = max_distance / last_level_scale (:500).  The arithmetic and evaluation order of
+ *   tc2li_map_points_refresh, bit for bit.
+ * Rule 3, ComputeDistinctiveDescriptors (MapPoint.cc:338-412): rule 4 of tc2li_search_in_neighbors_batch -- the descriptors of the
+ *   observations in keyframes that are NOT bad (:361), in row order, read from the store; per row the sorted row's entry
+ *   (int)(0.5 * (N - 1)); the first row with the least such median wins.
+ * Rule 4, UpdateConnections (:348): every output of `conn` equals what tc2li_update_connections_batch returns for the same kf_flags,
+ *   connection rows, slot_point and point_bad with the observation CSR AFTER rule 1.
+ *
+ * Why the device may work on a slot row side by side: a point is associated at most once per call, and nothing else in the loop changes
+ * any point's observations, any position or any centre; so the refresh of an associated point reads the same state whether it runs at
+ * its slot's turn or after the loop.  The only sequential fact is which of several slots holding one unobserved point comes first: a
+ * first-occurrence minimum over slot indices, taken with an integer atomicMin.
+ *
+ * Outputs (capacities are the caller's; an array of capacity 0 may be NULL):
+ *   counts [TC2LI_PROCESS_KEYFRAME_COUNTS], always written: status (TC2LI_PROCESS_KEYFRAME_ON_DEVICE / _ON_HOST), associated, recent
+ *                  pushes, entries of the observation CSR out
+ *   associated_slot / associated_point [associated_capacity]   in slot order: the shim replays AddObservation from these
+ *   recent [recent_capacity]                                   the pushes of :341 in order
+ *   point_nobs_out [n_points]; obs_offsets_out [n_points + 1], obs_kf_out / obs_index_out [obs_capacity]: the end state
+ *   desc_kf / desc_index [n_points]   the observation whose descriptor is mDescriptor afterwards, -1 where the step did not run or left early
+ *   refreshed [n_points] and, where it is set, normals_out [n][3], min_distance_out, max_distance_out
+ *   conn.counts and the lists of conn, exactly as tc2li_connections_problem defines them
+ * Errors.  TC2LI_ERR_INVALID before any device work and with nothing written: sizes and NULLs, offsets that do not ascend from 0, indices
+ *   out of range, observation or connection rows that do not ascend strictly, an empty or out-of-range slot where one is needed (the
+ *   current keyframe and the observers of the slot row's points), n_slots different from the stored keypoint count, an observation index
+ *   beyond the observer's keypoints, a point_ref_kf out of range for a point that can be associated (in the slot row, not bad, not yet
+ *   observed from the current keyframe).  TC2LI_ERR_CAPACITY as tc2li_search_in_neighbors_batch: counts and conn.counts are written for
+ *   every problem with the sizes needed and no list for any; the call repeated with those capacities succeeds.  conn.counts keeps its own
+ *   rule: N_CHANGED and N_CHANGED_ENTRIES are the sizes needed once counter_capacity and ordered_capacity suffice, and 0 until then.
+ * The device entry: one upload, four launches whatever the batch (classification and the end-state CSR, one workgroup per problem; the
+ * refresh, one wavefront per associated point over the whole batch; the two connection kernels on the CSR the first launch wrote), one
+ * download, no host wait between launches.  A problem in which a point would pass the observation limit of
+ * tc2li_process_new_keyframe_limits is finished inside the call by the host twin, reports TC2LI_PROCESS_KEYFRAME_ON_HOST and has the same
+ * outputs.  Both entries return n_problems. */
+#define TC2LI_PROCESS_KEYFRAME_COUNTS 4
+#define TC2LI_PROCESS_KEYFRAME_ON_DEVICE 0
+#define TC2LI_PROCESS_KEYFRAME_ON_HOST 1
+typedef struct tc2li_process_keyframe_problem {
+    tc2li_connections_problem conn;
+    const int32_t* kf_slot; const float* centres;
+    const float* positions; const int32_t *point_nobs, *point_ref_kf; const float* point_ref_level_scale; const int32_t* obs_index;
+    int32_t* counts; int32_t *associated_slot, *associated_point, *recent;
+    int32_t *point_nobs_out, *obs_offsets_out, *obs_kf_out, *obs_index_out, *desc_kf, *desc_index;
+    uint8_t* refreshed; float *normals_out, *min_distance_out, *max_distance_out;
+    int32_t associated_capacity, recent_capacity, obs_capacity;
+    float last_level_scale;
+} tc2li_process_keyframe_problem;
+int tc2li_process_new_keyframe_batch(tc2li_keyframe_store* store, const tc2li_process_keyframe_problem* problems, int n_problems,
+                                     void* stream);
+/* The host twin: plain sequential C++ in the reference's order, the refresh at the slot's turn; one problem per worker thread under the
+ * host thread budget; kf_slot indexes views (n, descriptors and u_right are read; n < 0 = an empty slot).  No observation limit; needs
+ * no device.  counts[0] is TC2LI_PROCESS_KEYFRAME_ON_HOST. */
+int tc2li_host_process_new_keyframe_batch(const tc2li_keyframe_view* views, int n_views, const tc2li_process_keyframe_problem* problems,
+                                          int n_problems);
+/* The limits of the device path: out[0] the most observations a point may reach (tc2li_map_points_refresh's), out[1] the most keypoints
+ * of a keyframe, out[2] threads per problem of the classification kernel, out[3] wavefronts per workgroup of the refresh kernel.  The
+ * per-point and per-keyframe marks live in global memory, so there is no limit on the points or keyframes of a problem.  Returns how
+ * many values there are; needs no device. */
+int tc2li_process_new_keyframe_limits(int32_t* out, int capacity);
+
 /* ---- local mapping: the window of the local BA (SF/src/OptimizerWithLidar.cc:63-130 the gather, :157-187 the pose vertices, :226-253 the
  * keyframes of the BALM edge, :263-384 the point vertices and edges; the identical gather of Optimizer::LocalBundleAdjustment,
  * SF/src/Optimizer.cc:1124-1190) -----------------------------------------------------------------------------------------------------------

@@ -3357,6 +3357,141 @@ def update_connections_batch(problems, host=False, stream=0, raw=False, fill=0):
     return res
 
 
+# ---- LocalMapping::ProcessNewKeyFrame (tc2li_process_new_keyframe_batch) -------------------------------------------------------------------
+_PROCESS_KEYFRAME_INPUTS = (("kf_slot", np.int32), ("centres", np.float32), ("positions", np.float32), ("point_nobs", np.int32), ("point_ref_kf", np.int32),
+                            ("point_ref_level_scale", np.float32), ("obs_index", np.int32))
+_PROCESS_KEYFRAME_OUTPUTS = ("counts", "associated_slot", "associated_point", "recent", "point_nobs_out", "obs_offsets_out", "obs_kf_out", "obs_index_out",
+                             "desc_kf", "desc_index", "refreshed", "normals_out", "min_distance_out", "max_distance_out")
+PROCESS_KEYFRAME_COUNTS = ("status", "associated", "recent", "observations")
+PROCESS_KEYFRAME_ON_DEVICE, PROCESS_KEYFRAME_ON_HOST = 0, 1
+_PROCESS_KEYFRAME_CAPACITIES = ("associated", "recent", "observations", "counter", "ordered", "changed")
+
+
+class ProcessKeyframeProblem(C.Structure):
+    """tc2li_process_keyframe_problem"""
+    _fields_ = [("conn", ConnectionsProblem)] + [(k, C.c_void_p) for k, _ in _PROCESS_KEYFRAME_INPUTS] + [(k, C.c_void_p) for k in _PROCESS_KEYFRAME_OUTPUTS] \
+        + [(k, C.c_int32) for k in ("associated_capacity", "recent_capacity", "obs_capacity")] + [("last_level_scale", C.c_float)]
+
+
+def process_new_keyframe_limits():
+    """tc2li_process_new_keyframe_limits -> {observations, keypoints, threads, refresh_waves}: a problem in which a point would pass
+    ``observations`` is computed by the host twin inside ``process_new_keyframe_batch``."""
+    out = np.zeros(8, np.int32)
+    f = lib().tc2li_process_new_keyframe_limits
+    f.argtypes = [C.c_void_p, C.c_int]
+    n = _check(f(out.ctypes.data, len(out)))
+    return dict(zip(("observations", "keypoints", "threads", "refresh_waves"), [int(v) for v in out[:n]]))
+
+
+def pack_process_keyframe_problems(problems, capacities=None):
+    """The tc2li_process_keyframe_problem array of a batch with its output arrays -> (array, outputs per problem, what must stay alive).
+    problems: dicts with the input arrays of tc2li_connections_problem (kf_flags, conn_offsets, conn_kf, conn_weight, slot_point, point_bad,
+    obs_offsets, obs_kf: the observation rows on entry), kf_slot, centres [n, 3], positions [n, 3], point_nobs, point_ref_kf,
+    point_ref_level_scale, obs_index, and current, last_level_scale, optionally first_connection, is_init_kf.  capacities: per problem a dict
+    with associated / recent / observations / counter / ordered / changed; default: what always suffices.  The outputs of the connection
+    half are in the dict under conn_counts and tc2li_connections_problem's names."""
+    P = len(problems)
+    arr, outs, keep = (ProcessKeyframeProblem * max(P, 1))(), [], []
+    for i, p in enumerate(problems):
+        a = {k: np.ascontiguousarray(p[k], t).reshape(-1) for k, t in _CONNECTIONS_ARRAYS + _PROCESS_KEYFRAME_INPUTS}
+        nk, ns, npts = len(a["kf_flags"]), len(a["slot_point"]), len(a["point_bad"])
+        if len(a["conn_offsets"]) != nk + 1 or len(a["obs_offsets"]) != npts + 1:
+            raise ValueError("problem %d: conn_offsets or obs_offsets do not fit the tables" % i)
+        nc, no = int(a["conn_offsets"][-1]), int(a["obs_offsets"][-1])
+        if min(len(a["conn_kf"]), len(a["conn_weight"])) < nc or min(len(a["obs_kf"]), len(a["obs_index"])) < no:
+            raise ValueError("problem %d: conn or observation arrays are shorter than their offsets say" % i)
+        if len(a["kf_slot"]) != nk or len(a["centres"]) != 3 * nk:
+            raise ValueError("problem %d: kf_slot or centres do not have %d rows" % (i, nk))
+        for k, w in (("positions", 3), ("point_nobs", 1), ("point_ref_kf", 1), ("point_ref_level_scale", 1)):
+            if len(a[k]) != w * npts:
+                raise ValueError("problem %d: %s does not have %d rows" % (i, k, npts))
+        occupied = int((a["slot_point"] >= 0).sum())
+        cap = dict(associated=occupied, recent=occupied, observations=no + occupied, counter=nk, ordered=nk, changed=nc + nk)
+        cap.update((capacities[i] if capacities is not None else None) or {})
+        o = dict(counts=np.zeros(len(PROCESS_KEYFRAME_COUNTS), np.int32), associated_slot=np.full(cap["associated"], -2, np.int32),
+                 associated_point=np.full(cap["associated"], -2, np.int32), recent=np.full(cap["recent"], -2, np.int32), point_nobs_out=np.full(npts, -2, np.int32),
+                 obs_offsets_out=np.full(npts + 1, -2, np.int32), obs_kf_out=np.full(cap["observations"], -2, np.int32),
+                 obs_index_out=np.full(cap["observations"], -2, np.int32), desc_kf=np.full(npts, -2, np.int32), desc_index=np.full(npts, -2, np.int32),
+                 refreshed=np.zeros(npts, np.uint8), normals_out=np.zeros((npts, 3), np.float32), min_distance_out=np.zeros(npts, np.float32),
+                 max_distance_out=np.zeros(npts, np.float32))
+        co = dict(conn_counts=np.full(8, -2, np.int32), counter_kf=np.full(cap["counter"], -2, np.int32), counter_weight=np.full(cap["counter"], -2, np.int32),
+                  ordered_kf=np.full(cap["ordered"], -2, np.int32), ordered_weight=np.full(cap["ordered"], -2, np.int32), touched_kf=np.full(cap["ordered"], -2, np.int32),
+                  touched_changed=np.full(cap["ordered"], 254, np.uint8), changed_offsets=np.full(cap["ordered"] + 1, -2, np.int32),
+                  changed_kf=np.full(cap["changed"], -2, np.int32), changed_weight=np.full(cap["changed"], -2, np.int32))
+        for k, _ in _CONNECTIONS_ARRAYS:
+            setattr(arr[i].conn, k, a[k].ctypes.data)
+        for k, v in co.items():
+            setattr(arr[i].conn, "counts" if k == "conn_counts" else k, v.ctypes.data if v.size else None)
+        arr[i].conn.n_keyframes, arr[i].conn.n_slots, arr[i].conn.n_points, arr[i].conn.current = nk, ns, npts, int(p["current"])
+        arr[i].conn.counter_capacity, arr[i].conn.ordered_capacity, arr[i].conn.changed_capacity = cap["counter"], cap["ordered"], cap["changed"]
+        arr[i].conn.first_connection, arr[i].conn.is_init_kf = int(bool(p.get("first_connection", 0))), int(bool(p.get("is_init_kf", 0)))
+        for k, _ in _PROCESS_KEYFRAME_INPUTS:
+            setattr(arr[i], k, a[k].ctypes.data if a[k].size else None)
+        for k, v in o.items():
+            setattr(arr[i], k, v.ctypes.data if v.size else None)
+        arr[i].associated_capacity, arr[i].recent_capacity, arr[i].obs_capacity = cap["associated"], cap["recent"], cap["observations"]
+        arr[i].last_level_scale = float(p["last_level_scale"])
+        keep.append(a)
+        outs.append(dict(o, **co))
+    return arr, outs, keep
+
+
+def run_process_new_keyframe_batch(arr, n_problems, store=None, views=None, stream=0):
+    """tc2li_process_new_keyframe_batch on ``store`` or, with ``views`` (per slot None or a dict with descriptors and u_right),
+    tc2li_host_process_new_keyframe_batch -> the call's return value (no exception: the caller reads the code)."""
+    if store is not None:
+        f = lib().tc2li_process_new_keyframe_batch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        return f(store._handle(), C.addressof(arr), int(n_problems), C.c_void_p(stream))
+    varr, keep = (KeyframeView * max(len(views), 1))(), []
+    for i, v in enumerate(views):
+        if v is None:
+            varr[i].n = -1
+            continue
+        d, ur = np.ascontiguousarray(v["descriptors"], np.uint8).reshape(-1, 32), np.ascontiguousarray(v["u_right"], np.float32)
+        if len(d) != len(ur):
+            raise ValueError("view %d: one u_right per descriptor" % i)
+        keep.append((d, ur))
+        varr[i].n, varr[i].descriptors, varr[i].u_right = len(d), d.ctypes.data, ur.ctypes.data
+    f = lib().tc2li_host_process_new_keyframe_batch
+    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    rc = f(C.addressof(varr), len(views), C.addressof(arr), int(n_problems))
+    del keep
+    return rc
+
+
+def _process_keyframe_results(outs):
+    res = []
+    for o in outs:
+        c = dict(zip(PROCESS_KEYFRAME_COUNTS, [int(v) for v in o["counts"]]))
+        k = dict(zip(_CONNECTIONS_COUNTS, [int(v) for v in o["conn_counts"][:6]]))
+        r = dict(o, counts=c, status=c["status"], associated_slot=o["associated_slot"][:c["associated"]], associated_point=o["associated_point"][:c["associated"]],
+                 recent=o["recent"][:c["recent"]], obs_kf_out=o["obs_kf_out"][:c["observations"]], obs_index_out=o["obs_index_out"][:c["observations"]])
+        conn = dict(status=k["status"], parent=k["parent"])
+        for name, n in (("counter_kf", "n_counter"), ("counter_weight", "n_counter"), ("ordered_kf", "n_ordered"), ("ordered_weight", "n_ordered"),
+                        ("touched_kf", "n_ordered"), ("touched_changed", "n_ordered"), ("changed_kf", "n_changed_entries"), ("changed_weight", "n_changed_entries")):
+            conn[name] = o[name][:k[n]]
+            del r[name]
+        conn["changed_offsets"] = o["changed_offsets"][:k["n_changed"] + 1] if k["status"] else np.zeros(1, np.int32)
+        del r["changed_offsets"], r["conn_counts"]
+        r["connections"] = conn
+        res.append(r)
+    return res
+
+
+def process_new_keyframe_batch(problems, store=None, views=None, stream=0, capacities=None):
+    """One ``LocalMapping::ProcessNewKeyFrame`` per problem (``tc2li_process_new_keyframe_batch``; with ``views`` in place of ``store`` the
+    host twin) -> one dict per problem: counts (dict), status, associated_slot, associated_point, recent, point_nobs_out, obs_offsets_out,
+    obs_kf_out, obs_index_out, desc_kf, desc_index, refreshed, normals_out, min_distance_out, max_distance_out, and connections: the dict
+    ``update_connections_batch`` returns."""
+    if (store is None) == (views is None):
+        raise ValueError("either a store (the device entry) or views (the host entry)")
+    arr, outs, keep = pack_process_keyframe_problems(problems, capacities)
+    _check(run_process_new_keyframe_batch(arr, len(problems), store, views, stream))
+    del keep
+    return _process_keyframe_results(outs)
+
+
 def update_best_covisibles_batch(rows, bad, host=False, stream=0):
     """``KeyFrame::UpdateBestCovisibles`` for a flat list of keyframes of any number of sequences.  rows: dict with the CSR offsets, kf, weight of
     their mConnectedKeyFrameWeights (a row ascends by kf); bad [n_keyframes]: isBad() of every keyframe the rows name -> dict offsets, kf,

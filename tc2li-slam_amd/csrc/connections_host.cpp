@@ -181,6 +181,18 @@ int check_covisibles(const char* entry, const int32_t* row_offsets, const int32_
 }
 
 }  // namespace
+
+// for tc2li_process_new_keyframe_batch (process_keyframe_device.hpp), which votes on the observation rows it has just written
+const char* connections_what_is_wrong(const tc2li_connections_problem& in) { return validate(in); }
+int host_connections(const char* entry, const tc2li_connections_problem* problems, int n_problems, bool write) {
+    if (write)
+        return size_then_write(n_problems, [&](int p, bool w) { return connections_one(problems[p], w); }, [&](int p) { return capacity_error(entry, problems, p); });
+    std::vector<uint8_t> ok(n_problems, 1);
+    tracking_pool().parallel_for(n_problems, [&](int p) { ok[p] = connections_one(problems[p], false); });
+    for (int p = 0; p < n_problems; ++p)
+        if (!ok[p]) return capacity_error(entry, problems, p);
+    return n_problems;
+}
 }  // namespace tc2li
 
 using namespace tc2li;

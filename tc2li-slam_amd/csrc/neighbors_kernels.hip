@@ -23,13 +23,16 @@
 
 #include "fuse_search.hpp"
 #include "neighbors_device.hpp"
+#include "point_refresh_device.hpp"
 
 namespace tc2li {
 
 namespace {
 
 constexpr int F_BAD = 1, F_MARK = 2, F_DIRTY = 4, F_REFRESH = 8;
-constexpr int kDescStride = 9;  // words per descriptor row in LDS: 8 + 1, so that lanes reading their own rows meet no bank twice
+using refresh::kDescStride;
+using refresh::lane_rank;
+using refresh::wave_sync_lds;
 enum { S_STATUS = 0, S_NTARGETS, S_NHITS, S_POOL, S_NOPS, S_NCAND, S_FUSED1, S_FUSED2, S_NREFRESHED, S_FUSED, S_COUNT };
 
 struct Ctx {  // the tables of this workgroup's problem
@@ -46,21 +49,10 @@ struct Ctx {  // the tables of this workgroup's problem
     int32_t* s;              // LDS scalars
 };
 
-__device__ __forceinline__ void wave_sync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ int lane_rank(unsigned long long mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
 // MapPoint::IsInKeyFrame: the row ascends by keyframe
 __device__ __forceinline__ bool in_kf(const Ctx& c, int p, int kf) {
     const NbObs* o = c.pool + c.p_start[p];
-    int lo = 0, hi = c.p_len[p];
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (o[mid].kf < kf) lo = mid + 1; else hi = mid; }
-    return lo < c.p_len[p] && o[lo].kf == kf;
+    return refresh::in_kf(c.p_len[p], [=](int k) { return o[k].kf; }, kf);
 }
 
 // room for `need` observations of point w: a list that outgrows its room moves to a fresh piece of the pool, half as long again as
@@ -141,37 +133,16 @@ __device__ __forceinline__ FuseDev fuse_of(const NbKf& k, const NbConsts& cc) {
 // MapPoint::ComputeDistinctiveDescriptors of point w by the calling wavefront; desc: its kNbMaxObs x kDescStride words, rows: which
 // observation each row is.  A bad point or one without a descriptor to take is left as it is.
 __device__ void describe_point(const Ctx& c, int w, uint32_t* desc, uint8_t* rows, int32_t* desc_kf, int32_t* desc_index, int lane) {
-    const int st = c.p_start[w], len = c.p_len[w];
-    int N = 0;
-    for (int o0 = 0; o0 < len; o0 += 64) {
-        const int o = o0 + lane;
-        NbObs ob{0, 0};
-        bool ok = false;
-        if (o < len) { ob = c.pool[st + o]; ok = !(c.kflag[ob.kf] & 1); }
-        const unsigned long long mask = __ballot(ok);
-        if (ok) {
-            const int r = N + lane_rank(mask);
-            rows[r] = (uint8_t)o;
-            const uint32_t* d = reinterpret_cast<const uint32_t*>(c.kfs[ob.kf].desc) + 8 * (size_t)ob.idx;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) desc[r * kDescStride + k] = d[k];
-        }
-        N += __popcll(mask);
-    }
-    if (N == 0) return;
-    wave_sync_lds();
-    int best_median = 0x7fffffff, best_row = 0x7fffffff;
-    for (int i = lane; i < N; i += 64) {
-        const int m = row_median(desc, kDescStride, N, i);
-        if (m < best_median) { best_median = m; best_row = i; }  // rows of a lane ascend: the first minimum is kept
-    }
-    for (int o = 32; o >= 1; o >>= 1) {
-        const int m = __shfl_xor(best_median, o, 64), r = __shfl_xor(best_row, o, 64);
-        if (m < best_median || (m == best_median && r < best_row)) { best_median = m; best_row = r; }
-    }
+    const int len = c.p_len[w];
+    const NbObs* obs = c.pool + c.p_start[w];
+    int best_row;
+    const int best = refresh::describe_rows(
+        len, [=](int o) { return obs[o].kf; }, [&](int kf) { return (c.kflag[kf] & 1) != 0; },
+        [&](int o) { return reinterpret_cast<const uint32_t*>(c.kfs[obs[o].kf].desc) + 8 * (size_t)obs[o].idx; }, desc, rows, lane, &best_row);
+    if (best < 0) return;
     if (lane < 8) reinterpret_cast<uint32_t*>(c.points + 68 * (size_t)w + 36)[lane] = desc[best_row * kDescStride + lane];
     if (lane == 0) {
-        const NbObs ob = c.pool[st + rows[best_row]];
+        const NbObs ob = obs[best];
         desc_kf[w] = ob.kf; desc_index[w] = ob.idx;
     }
     wave_sync_lds();  // the rows are free for the wavefront's next point
@@ -401,23 +372,10 @@ __global__ __launch_bounds__(kNbThreads) void k_search_in_neighbors(NbBatch B) {
                 const int N = c.p_len[p];
                 if (lane == 0 && N > 0) {  // MapPoint::UpdateNormalAndDepth in the order of k_map_points_refresh
                     const float* X = reinterpret_cast<const float*>(c.points + 68 * (size_t)p);
-                    const float px = X[0], py = X[1], pz = X[2];
                     const NbObs* ob = c.pool + c.p_start[p];
-                    float nx = 0, ny = 0, nz = 0;
-                    for (int o = 0; o < N; ++o) {
-                        const float* C = c.kfs[ob[o].kf].Ow;
-                        const float vx = px - C[0], vy = py - C[1], vz = pz - C[2];
-                        const float nr = sqrtf(vx * vx + vy * vy + vz * vz);
-                        nx = nx + vx / nr; ny = ny + vy / nr; nz = nz + vz / nr;
-                    }
-                    const float* R = c.kfs[B.ref_kf[P.point_off + p]].Ow;
-                    const float rx = px - R[0], ry = py - R[1], rz = pz - R[2];
-                    const float dist = sqrtf(rx * rx + ry * ry + rz * rz);
-                    const float mx = dist * B.ref_scale[P.point_off + p];
                     const size_t g = (size_t)P.point_off + p;
-                    B.max_dist[g] = mx;
-                    B.min_dist[g] = mx / P.last_level_scale;
-                    B.normals[3 * g] = nx / (float)N; B.normals[3 * g + 1] = ny / (float)N; B.normals[3 * g + 2] = nz / (float)N;
+                    refresh::normal_and_depth(X, N, [&](int o) { return c.kfs[ob[o].kf].Ow; }, c.kfs[B.ref_kf[g]].Ow, B.ref_scale[g], P.last_level_scale,
+                                              B.normals + 3 * g, B.min_dist + g, B.max_dist + g);
                     B.refreshed[g] = 1;
                     atomicAdd(&s_s[S_NREFRESHED], 1);
                 }

@@ -42,7 +42,7 @@ struct PackedSpace : PackedBuffers {
     std::mutex mu;
 };
 enum PackedSpaceTag { kSpaceKeyframeCulling, kSpaceMapPointCulling, kSpaceConnections, kSpaceCovisibles, kSpaceStereoPoints, kSpaceMlpnp, kSpaceInertialWindow, kSpaceInertialTerm,
-                      kSpaceScaledRotation, kSpaceGbaCorrection, kSpaceInertialInit, kSpaceLocalMap, kSpaceNeighbors };
+                      kSpaceScaledRotation, kSpaceGbaCorrection, kSpaceInertialInit, kSpaceLocalMap, kSpaceNeighbors, kSpaceProcessKeyframe };
 
 // One call's transfer.  The entry take()s its inputs from io, calls state_begins() and takes the tables that go up and come back (an
 // entry without such tables skips this), calls outputs_begin() and takes what does not go up with the block -- its outputs, or tables it
