@@ -2194,6 +2194,151 @@ typedef struct tc2li_ba_window_solve_problem {
 int tc2li_ba_window_solve_batch(tc2li_keyframe_store* store, const tc2li_ba_window_solve_problem* problems, int n_problems,
                                 const float* inv_level_sigma2, int n_levels, const tc2li_camera* cam, int group, int32_t* results);
 
+/* ---- local mapping: the map graph resident on the device, and the local-BA gather reading from it (no reference counterpart as a
+ * whole: the reference keeps the graph in KeyFrame / MapPoint objects; every edit below names the call it stands for) --------------------
+ * The input half of tc2li_ba_window_problem -- kf_slot, kf_id, kf_flags, poses7, slot_offsets / slot_point, point_flags, positions,
+ * obs_offsets / obs_kf / obs_index -- of n_sequences sequences in one slab allocated at create, in the dense CSR layout the gather kernels
+ * read.  After tc2li_map_graph_set_batch only edit logs cross the bus (tc2li_map_graph_apply_batch), and tc2li_ba_window_graph_batch /
+ * tc2li_ba_window_solve_graph_batch gather from the resident tables.  One lock per handle: calls on one graph run one after the other.
+ * The graph is bound to one keyframe store for life: kf_slot names that store's slots, and an observation's index is checked against the
+ * keypoints the slot holds when the edit arrives.  (tc2li_map_graph, without a suffix, is the host-array graph of tc2li_local_map.) */
+typedef struct tc2li_map_graph_handle tc2li_map_graph_handle;
+enum tc2li_map_graph_capacity {       /* per sequence */
+    TC2LI_MAP_GRAPH_KEYFRAMES = 0,    /* keyframe rows */
+    TC2LI_MAP_GRAPH_SLOTS = 1,        /* entries of slot_point */
+    TC2LI_MAP_GRAPH_POINTS = 2,       /* point rows */
+    TC2LI_MAP_GRAPH_OBSERVATIONS = 3, /* entries of obs_kf / obs_index */
+    TC2LI_MAP_GRAPH_CAPACITIES = 4
+};
+/* The tables of one sequence as host arrays, the members named as in tc2li_ba_window_problem.  Read by set_batch and the host twin,
+ * written by download and the host twin. */
+typedef struct tc2li_map_graph_tables {
+    int32_t* kf_slot;
+    int64_t* kf_id;
+    uint8_t* kf_flags;
+    double* poses7;
+    int32_t* slot_offsets;
+    int32_t* slot_point;
+    uint8_t* point_flags;
+    double* positions;
+    int32_t* obs_offsets;
+    int32_t* obs_kf;
+    int32_t* obs_index;
+    int32_t n_keyframes, n_points;
+} tc2li_map_graph_tables;
+/* One edit: 16 bytes.  Operands that carry doubles name an offset into the log's `values`.
+ *   op                  a          b          c            reference                                         effect
+ *   ADD_KEYFRAME        store slot n_slots    values off   new KeyFrame, SF/src/Tracking.cc:3078             appends a keyframe row whose n_slots slots are -1;
+ *                                                                                                            values: id, flags, pose7 (9 doubles; id and flags
+ *                                                                                                            integral).  Its row is n_keyframes + the appends
+ *                                                                                                            before it in this log
+ *   SET_KEYFRAME_FLAGS  row        flags      -            KeyFrame::SetBadFlag SF/src/KeyFrame.cc:585,      overwrites
+ *                                                          the LiDAR cloud bit
+ *   SET_POSE            row        values off -            KeyFrame::SetPose SF/src/KeyFrame.cc:121          overwrites poses7 (7 doubles)
+ *   ADD_POINT           flags      values off -            new MapPoint                                      appends a point row (3 doubles) with an empty
+ *                                                                                                            observation row
+ *   SET_POINT_FLAGS     row        flags      -            MapPoint::SetBadFlag SF/src/MapPoint.cc:225       overwrites
+ *   SET_POSITION        row        values off -            MapPoint::SetWorldPos                             overwrites (3 doubles)
+ *   SET_SLOT            kf row     slot       point or -1  KeyFrame::AddMapPoint / EraseMapPointMatch /      overwrites one slot
+ *                                                          ReplaceMapPointMatch SF/src/KeyFrame.cc:309-340
+ *   ADD_OBSERVATION     point      kf row     index        MapPoint::AddObservation SF/src/MapPoint.cc:150-175  inserts the pair at its place in row order; a
+ *                                                                                                            keyframe already in the row gets its index
+ *                                                                                                            OVERWRITTEN (mObservations[pKF] = indexes, :155-169)
+ *   ERASE_OBSERVATION   point      kf row     -            MapPoint::EraseObservation SF/src/MapPoint.cc:177-210  removes the pair; a no-op if absent (:182)
+ *   CLEAR_OBSERVATIONS  point      -          -            mObservations.clear() in MapPoint::SetBadFlag     empties the row
+ * The graph stores literal edits: what the reference chains onto one (EraseObservation turning a point bad at nObs <= 2, SetBadFlag
+ * erasing the slots of every observer, Replace) the caller spells out as further edits.  The result is what applying the log one edit
+ * after the other gives; an edit may name a row the same log appended earlier. */
+enum tc2li_map_graph_op {
+    TC2LI_MAP_GRAPH_ADD_KEYFRAME = 0,
+    TC2LI_MAP_GRAPH_SET_KEYFRAME_FLAGS = 1,
+    TC2LI_MAP_GRAPH_SET_POSE = 2,
+    TC2LI_MAP_GRAPH_ADD_POINT = 3,
+    TC2LI_MAP_GRAPH_SET_POINT_FLAGS = 4,
+    TC2LI_MAP_GRAPH_SET_POSITION = 5,
+    TC2LI_MAP_GRAPH_SET_SLOT = 6,
+    TC2LI_MAP_GRAPH_ADD_OBSERVATION = 7,
+    TC2LI_MAP_GRAPH_ERASE_OBSERVATION = 8,
+    TC2LI_MAP_GRAPH_CLEAR_OBSERVATIONS = 9,
+    TC2LI_MAP_GRAPH_OPS = 10
+};
+typedef struct tc2li_map_graph_edit {
+    int32_t op, a, b, c;
+} tc2li_map_graph_edit;
+/* The ordered edit log of one sequence. */
+typedef struct tc2li_map_graph_delta {
+    const tc2li_map_graph_edit* edits;
+    const double* values;
+    int32_t sequence, n_edits, n_values, pad_;
+} tc2li_map_graph_delta;
+enum tc2li_map_graph_info_field {
+    TC2LI_MAP_GRAPH_INFO_KEYFRAMES = 0,
+    TC2LI_MAP_GRAPH_INFO_POINTS = 1,
+    TC2LI_MAP_GRAPH_INFO_SLOTS = 2,          /* entries of slot_point */
+    TC2LI_MAP_GRAPH_INFO_OBSERVATIONS = 3,   /* entries of obs_kf */
+    TC2LI_MAP_GRAPH_INFO_APPLIES = 4,        /* applies since the last set; -1: the sequence was never set */
+    TC2LI_MAP_GRAPH_INFO_APPLY_BYTES = 5,    /* host-to-device bytes of the last apply that named the sequence, the sequence's share: its
+                                              * record, its edits, the values they use */
+    TC2LI_MAP_GRAPH_INFO_GATHER_BYTES = 6,   /* host-to-device bytes of the last graph-reading gather that named the sequence, the whole call's:
+                                              * problem records, level table, cov_kf.  NOT counted: what the BA after the gather of
+                                              * tc2li_ba_window_solve_graph_batch uploads of its own -- the clouds of LiDAR windows, and the
+                                              * whole window where one is finished on the host path -- exactly as in tc2li_ba_window_solve_batch */
+    TC2LI_MAP_GRAPH_INFO_FIELDS = 7
+};
+/* capacities [TC2LI_MAP_GRAPH_CAPACITIES], per sequence, fixed for life.  TC2LI_ERR_INVALID for a capacity below 1 or a table of all
+ * sequences beyond 2^31 rows; TC2LI_ERR_NO_DEVICE without one. */
+int tc2li_map_graph_create(tc2li_keyframe_store* store, int n_sequences, const int32_t* capacities, tc2li_map_graph_handle** out);
+int tc2li_map_graph_destroy(tc2li_map_graph_handle* graph);
+/* The full state of n sequences (no sequence twice).  The validation is tc2li_ba_window_batch's of the same tables: offsets ascending
+ * from 0, slot_point, obs_kf and obs_index in range, observation rows ascending strictly by keyframe row, every kf_slot occupied in the
+ * store; kf_flags and point_flags are bytes and kept as given.  TC2LI_ERR_CAPACITY for tables beyond a capacity.  A refused call leaves the
+ * graph unchanged.  One upload per call; resident when the call returns. */
+int tc2li_map_graph_set_batch(tc2li_map_graph_handle* graph, const int32_t* sequences, const tc2li_map_graph_tables* tables, int n, void* stream);
+/* One edit log per named sequence (none twice: TC2LI_ERR_INVALID).  Every edit is checked on the host before any device work, against the
+ * row counts, the slot count and store slot of every keyframe row and the observation total -- the host mirrors no table.
+ * TC2LI_ERR_INVALID, graph unchanged: an unknown op; a row, slot or values offset out of range; a row named before its append; a point
+ * below -1; flags outside a byte; an observation index below -1 or at or beyond the keypoints of the observer's store slot; a store slot
+ * that is empty or out of range; a sequence that was never set.  TC2LI_ERR_CAPACITY, graph unchanged: appends beyond a row capacity, slot
+ * entries beyond theirs, or observation entries resident now + ADD_OBSERVATION edits in the log > the observation capacity (the host
+ * cannot know whether an ADD grows a row; the resident total is exact, each apply downloads 4 bytes per sequence); or a log whose
+ * observation edits are too scattered: a touched row finds its edits by walking the log from its first to its last edit, and the sum of
+ * those stretches over the points of one log may not exceed tc2li_map_graph_limits' out[5] (one keyframe's worth of edits, one per point,
+ * sums to their number; keep a point's edits together, or split the log).
+ * Crossing the bus: one 64-byte record per sequence, the edits, the values.  Two kernel launches whatever the number of edits and
+ * sequences.  Returns n. */
+int tc2li_map_graph_apply_batch(tc2li_map_graph_handle* graph, const tc2li_map_graph_delta* deltas, int n, void* stream);
+/* The resident tables of one sequence as host arrays (for tests and tools).  capacities [4] are the caller's arrays' (keyframe rows, slot
+ * entries, point rows, observation entries; the offset arrays hold one more than their rows), counts [4] is always written;
+ * TC2LI_ERR_CAPACITY when an array is too small. */
+int tc2li_map_graph_download(tc2li_map_graph_handle* graph, int sequence, tc2li_map_graph_tables* tables_out, const int32_t* capacities, int32_t* counts);
+/* out [TC2LI_MAP_GRAPH_INFO_FIELDS] of one sequence; returns the number written. */
+int tc2li_map_graph_info(tc2li_map_graph_handle* graph, int sequence, int64_t* out, int capacity);
+/* The sizes at which the apply kernel changes path (for tests): out[0] = the longest observation row (old entries + the row's edits) that
+ * is merged in LDS (beyond: in global memory), out[1] = edits per step of the workgroup, out[2] = threads per sequence, out[3] = bytes of
+ * the per-sequence record of an apply, out[4] = bytes of the per-problem record of a graph-reading gather, out[5] = the most edit reads
+ * the walks of one log's touched rows may sum to.  Returns 6.  Needs no device. */
+int tc2li_map_graph_limits(int32_t* out, int capacity);
+/* The host twin: the same log applied by plain sequential C++ to host arrays; it defines the result.  tables_out's arrays have
+ * capacities [4]; counts [4] receives the sizes.  The checks of tc2li_map_graph_apply_batch except those that need the store (a store
+ * slot is only required to be >= 0, an observation index to be >= -1); on an error nothing is written.  Needs no device. */
+int tc2li_host_map_graph_apply(const tc2li_map_graph_tables* tables_in, const tc2li_map_graph_edit* edits, int n_edits, const double* values,
+                               int n_values, tc2li_map_graph_tables* tables_out, const int32_t* capacities, int32_t* counts);
+/* tc2li_ba_window_batch with the tables of problem p taken from sequence sequences[p] of the graph.
+ * NOTE: of a problem only current, cov_kf / n_cov, init_kf_id, the outputs and the capacities are read.  ITS TABLE POINTERS, n_keyframes
+ * AND n_points ARE IGNORED WITHOUT AN ERROR: a caller who also passes tables gets the graph's, never its own, however stale they are.
+ * Pass NULL and 0 there.  Every output, count,
+ * status and error is bit for bit that of tc2li_ba_window_batch given the tables tc2li_map_graph_download returns -- the same kernels read
+ * the same layout.  Several problems may name one sequence.  Uploaded: the problem records, cov_kf and the level table; no table.  Per
+ * call the host checks in O(n_keyframes) that the store slots of the sequence's keyframe rows are occupied and hold no octave beyond
+ * n_levels and hold no fewer keypoints than when the rows' observation indices were checked (a slot put again with fewer is refused:
+ * TC2LI_ERR_INVALID), and current and cov_kf. */
+int tc2li_ba_window_graph_batch(tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences, const tc2li_ba_window_problem* problems,
+                                int n_problems, const float* inv_level_sigma2, int n_levels, void* stream);
+/* The same step for tc2li_ba_window_solve_batch: stop flag, stats, clouds, erase lists as there. */
+int tc2li_ba_window_solve_graph_batch(tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences,
+                                      const tc2li_ba_window_solve_problem* problems, int n_problems, const float* inv_level_sigma2, int n_levels,
+                                      const tc2li_camera* cam, int group, int32_t* results);
+
 /* ---- local mapping: the window of the inertial local BA (OptimizerWithLidar::LocalLVIBA, SF/src/OptimizerWithLidar.cc:489-607 the gather,
  * :632-727 the vertices and the keyframes of the LiDAR edge, :729-800 the inertial links, :832-969 the point vertices and edges, :985-1045
  * the outlier rule; the twin Optimizer::LocalInertialBA, SF/src/Optimizer.cc:1512-1631 and on) -------------------------------------------

@@ -3796,6 +3796,230 @@ def ba_window_solve_batch(problems, inv_level_sigma2, store, cam5, group=0, fill
     return res
 
 
+MAP_GRAPH_EDIT_DTYPE = np.dtype([("op", "<i4"), ("a", "<i4"), ("b", "<i4"), ("c", "<i4")])
+MAP_GRAPH_OPS = ("ADD_KEYFRAME", "SET_KEYFRAME_FLAGS", "SET_POSE", "ADD_POINT", "SET_POINT_FLAGS", "SET_POSITION", "SET_SLOT", "ADD_OBSERVATION",
+                 "ERASE_OBSERVATION", "CLEAR_OBSERVATIONS")
+MAP_GRAPH_OP = {k: i for i, k in enumerate(MAP_GRAPH_OPS)}
+_MAP_GRAPH_ARRAYS = (("kf_slot", np.int32, 0, 1), ("kf_id", np.int64, 0, 1), ("kf_flags", np.uint8, 0, 1), ("poses7", np.float64, 0, 7),
+                     ("slot_offsets", np.int32, 0, 1), ("slot_point", np.int32, 1, 1), ("point_flags", np.uint8, 2, 1), ("positions", np.float64, 2, 3),
+                     ("obs_offsets", np.int32, 2, 1), ("obs_kf", np.int32, 3, 1), ("obs_index", np.int32, 3, 1))   # name, type, capacity, width
+_MAP_GRAPH_INFO = ("n_keyframes", "n_points", "n_slots", "n_observations", "applies", "apply_bytes", "gather_bytes")
+
+
+class MapGraphTables(C.Structure):
+    """tc2li_map_graph_tables"""
+    _fields_ = [(k, C.c_void_p) for k, _, _, _ in _MAP_GRAPH_ARRAYS] + [("n_keyframes", C.c_int32), ("n_points", C.c_int32)]
+
+
+class MapGraphDelta(C.Structure):
+    """tc2li_map_graph_delta"""
+    _fields_ = [("edits", C.c_void_p), ("values", C.c_void_p)] + [(k, C.c_int32) for k in ("sequence", "n_edits", "n_values", "pad_")]
+
+
+def _pack_map_graph_tables(t, into):
+    """The tables of one sequence (a dict with the arrays of tc2li_ba_window_problem; further keys are ignored) into a MapGraphTables."""
+    a = {k: np.ascontiguousarray(t[k], ty).reshape(-1) for k, ty, _, _ in _MAP_GRAPH_ARRAYS}
+    nk, npts = len(a["kf_slot"]), len(a["point_flags"])
+    if len(a["kf_id"]) != nk or len(a["kf_flags"]) != nk or len(a["poses7"]) != 7 * nk or len(a["slot_offsets"]) != nk + 1:
+        raise ValueError("the keyframe arrays do not have one row per keyframe")
+    if len(a["positions"]) != 3 * npts or len(a["obs_offsets"]) != npts + 1:
+        raise ValueError("the point arrays do not have one row per point")
+    if len(a["slot_point"]) < int(a["slot_offsets"][-1]) or min(len(a["obs_kf"]), len(a["obs_index"])) < int(a["obs_offsets"][-1]):
+        raise ValueError("slot or observation arrays are shorter than their offsets say")
+    for k, v in a.items():
+        setattr(into, k, v.ctypes.data)
+    into.n_keyframes, into.n_points = nk, npts
+    return a
+
+
+def _room_for_map_graph_tables(capacities, fill=0):
+    """-> (MapGraphTables over fresh arrays with room for `capacities` (keyframes, slots, points, observations), the arrays)"""
+    t, a = MapGraphTables(), {}
+    for k, ty, c, w in _MAP_GRAPH_ARRAYS:
+        a[k] = np.full((int(capacities[c]) + (1 if k.endswith("offsets") else 0)) * w, fill, np.int64).astype(ty)
+        setattr(t, k, a[k].ctypes.data)
+    return t, a
+
+
+def _cut_map_graph_tables(a, counts):
+    nk, ns, npts, no = [int(c) for c in counts]
+    return dict(kf_slot=a["kf_slot"][:nk], kf_id=a["kf_id"][:nk], kf_flags=a["kf_flags"][:nk], poses7=a["poses7"][:7 * nk].reshape(-1, 7),
+                slot_offsets=a["slot_offsets"][:nk + 1], slot_point=a["slot_point"][:ns], point_flags=a["point_flags"][:npts],
+                positions=a["positions"][:3 * npts].reshape(-1, 3), obs_offsets=a["obs_offsets"][:npts + 1], obs_kf=a["obs_kf"][:no],
+                obs_index=a["obs_index"][:no])
+
+
+def map_graph_limits():
+    """tc2li_map_graph_limits -> {lds_row, edits_per_step, threads, apply_record_bytes, gather_record_bytes, max_walk}"""
+    out = (C.c_int32 * 6)()
+    f = lib().tc2li_map_graph_limits
+    f.argtypes = [C.c_void_p, C.c_int]
+    _check(f(out, 6))
+    return dict(zip(("lds_row", "edits_per_step", "threads", "apply_record_bytes", "gather_record_bytes", "max_walk"), [int(v) for v in out]))
+
+
+def _pack_map_graph_log(edits, values):
+    e = np.ascontiguousarray(edits, MAP_GRAPH_EDIT_DTYPE).reshape(-1)
+    v = np.ascontiguousarray(values if values is not None else [], np.float64).reshape(-1)
+    return e, v
+
+
+def host_map_graph_apply(tables, edits, values, capacities):
+    """tc2li_host_map_graph_apply, the host twin: the log (edits: MAP_GRAPH_EDIT_DTYPE, values: float64) applied one edit after the other to
+    the tables (a dict as for ResidentMapGraph.set_batch) -> the tables after it.  capacities: keyframes, slots, points, observations."""
+    tin = MapGraphTables()
+    keep = _pack_map_graph_tables(tables, tin)
+    e, v = _pack_map_graph_log(edits, values)
+    caps = np.ascontiguousarray(capacities, np.int32)
+    tout, a = _room_for_map_graph_tables(caps)
+    counts = np.zeros(4, np.int32)
+    f = lib().tc2li_host_map_graph_apply
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(f(C.addressof(tin), e.ctypes.data, len(e), v.ctypes.data, len(v), C.addressof(tout), caps.ctypes.data, counts.ctypes.data))
+    del keep
+    return _cut_map_graph_tables(a, counts)
+
+
+class ResidentMapGraph:
+    """``tc2li_map_graph_*``: the input half of the local-BA window problems of n_sequences sequences, resident on the device and edited by
+    logs.  capacities: per sequence keyframe rows, slot entries, point rows, observation entries.  Bound to one :class:`KeyframeStore`."""
+
+    def __init__(self, store, n_sequences, capacities):
+        self._h = C.c_void_p()
+        self.store, self.n_sequences = store, int(n_sequences)
+        self.capacities = np.ascontiguousarray(capacities, np.int32).copy()
+        if self.capacities.shape != (4,):
+            raise ValueError("four capacities: keyframes, slots, points, observations")
+        f = lib().tc2li_map_graph_create
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _check(f(store._handle(), self.n_sequences, self.capacities.ctypes.data, C.byref(self._h)))
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the map graph is closed")
+        return self._h
+
+    def set_batch(self, sequences, tables, stream=0):
+        """tc2li_map_graph_set_batch: the full state of the named sequences (tables: dicts with the arrays of tc2li_ba_window_problem)."""
+        seq = np.ascontiguousarray(sequences, np.int32).reshape(-1)
+        arr = (MapGraphTables * max(len(tables), 1))()
+        keep = [_pack_map_graph_tables(t, arr[i]) for i, t in enumerate(tables)]
+        f = lib().tc2li_map_graph_set_batch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _check(f(self._handle(), seq.ctypes.data, C.addressof(arr), len(tables), C.c_void_p(stream)))
+        del keep
+
+    def apply_batch(self, deltas, stream=0):
+        """tc2li_map_graph_apply_batch.  deltas: (sequence, edits (MAP_GRAPH_EDIT_DTYPE), values (float64 or None)) per named sequence."""
+        arr, keep = (MapGraphDelta * max(len(deltas), 1))(), []
+        for i, (s, edits, values) in enumerate(deltas):
+            e, v = _pack_map_graph_log(edits, values)
+            keep.append((e, v))
+            arr[i].edits, arr[i].values, arr[i].sequence, arr[i].n_edits, arr[i].n_values = e.ctypes.data, v.ctypes.data, int(s), len(e), len(v)
+        f = lib().tc2li_map_graph_apply_batch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _check(f(self._handle(), C.addressof(arr), len(deltas), C.c_void_p(stream)))
+        del keep
+
+    def download(self, sequence, fill=0):
+        """tc2li_map_graph_download -> the resident tables of the sequence as a dict of arrays"""
+        i = self.info(sequence)
+        caps = np.array([i["n_keyframes"], i["n_slots"], i["n_points"], i["n_observations"]], np.int32)
+        t, a = _room_for_map_graph_tables(caps, fill)
+        counts = np.zeros(4, np.int32)
+        f = lib().tc2li_map_graph_download
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _check(f(self._handle(), int(sequence), C.addressof(t), caps.ctypes.data, counts.ctypes.data))
+        return _cut_map_graph_tables(a, counts)
+
+    def info(self, sequence):
+        """tc2li_map_graph_info -> {n_keyframes, n_points, n_slots, n_observations, applies, apply_bytes, gather_bytes}"""
+        out = (C.c_int64 * len(_MAP_GRAPH_INFO))()
+        f = lib().tc2li_map_graph_info
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        _check(f(self._handle(), int(sequence), out, len(_MAP_GRAPH_INFO)))
+        return dict(zip(_MAP_GRAPH_INFO, [int(v) for v in out]))
+
+    def close(self):
+        if self._h:
+            f = lib().tc2li_map_graph_destroy
+            f.argtypes = [C.c_void_p]
+            f(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _without_tables(window):
+    """A tc2li_ba_window_problem as the graph-reading entries take it: the table pointers NULL and the sizes 0 -- they are not read."""
+    for k, _ in _BA_WINDOW_ARRAYS:
+        if k != "cov_kf":
+            setattr(window, k, None)
+    window.n_keyframes = window.n_points = 0
+
+
+def ba_window_graph_batch(problems, sequences, inv_level_sigma2, store, graph, stream=0, raw=False, fill=0):
+    """tc2li_ba_window_graph_batch: ba_window_batch with the tables of problem i taken from sequence sequences[i] of `graph` (a
+    :class:`ResidentMapGraph`).  problems: the dicts of ba_window_batch; of them current, cov_kf, init_kf_id and the capacities reach the library (the
+    tables only size the default capacities).  -> as ba_window_batch."""
+    arr, outs, keep = pack_ba_window_problems(problems, fill)
+    for i in range(len(problems)):
+        _without_tables(arr[i])
+    seq = np.ascontiguousarray(sequences, np.int32).reshape(-1)
+    if len(seq) != len(problems):
+        raise ValueError("one sequence per problem")
+    sg = np.ascontiguousarray(inv_level_sigma2, np.float32).reshape(-1)
+    f = lib().tc2li_ba_window_graph_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    _check(f(store._handle(), graph._handle(), seq.ctypes.data, C.addressof(arr), len(problems), sg.ctypes.data, len(sg), C.c_void_p(stream)))
+    del keep
+    if raw:
+        return outs
+    res = []
+    for o in outs:
+        r, c = _cut_ba_window_outputs(o)
+        r.update({k: c[k] for k in ("status", "num_fixed_kf", "num_opt_kf", "n_lidar", "n_points_without_edge")})
+        res.append(r)
+    return res
+
+
+def ba_window_solve_graph_batch(problems, sequences, inv_level_sigma2, store, graph, cam5, group=0, fill=0):
+    """tc2li_ba_window_solve_graph_batch: ba_window_solve_batch with the tables of problem i taken from sequence sequences[i] of `graph`.
+    -> as ba_window_solve_batch."""
+    arr, outs, keep = pack_ba_window_solve_problems(problems, fill)
+    for i in range(len(problems)):
+        _without_tables(arr[i].window)
+    seq = np.ascontiguousarray(sequences, np.int32).reshape(-1)
+    if len(seq) != len(problems):
+        raise ValueError("one sequence per problem")
+    sg = np.ascontiguousarray(inv_level_sigma2, np.float32).reshape(-1)
+    cam = np.ascontiguousarray(cam5, np.float64)
+    n = len(problems)
+    results = np.zeros(max(n, 1), np.int32)
+    f = lib().tc2li_ba_window_solve_graph_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    _check(f(store._handle(), graph._handle(), seq.ctypes.data, C.addressof(arr), n, sg.ctypes.data, len(sg), cam.ctypes.data, int(group), results.ctypes.data))
+    res = []
+    for i, o in enumerate(outs):
+        r, c = _cut_ba_window_outputs(o)
+        ne, m = c["n_edges"], int(o["n_erase"][0])
+        r.update(result=int(results[i]), chi2=None if o["edge_chi2"] is None else o["edge_chi2"][:ne],
+                 depth_positive=None if o["edge_depth_positive"] is None else o["edge_depth_positive"][:ne], stats=o["stats"],
+                 lidar_stats=o["lidar_stats"], n_erase=m, erase=np.stack([o["erase_pose"][:m], o["erase_point"][:m]], 1), keep=keep)
+        res.append(r)
+    return res
+
+
 class InertialWindowProblem(C.Structure):
     """tc2li_inertial_window_problem"""
     _fields_ = [(k, C.c_void_p) for k in ("kf_slot", "kf_id", "kf_flags", "prev_kf", "states", "slot_offsets", "slot_point", "point_flags", "positions",

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "ba_window_device.hpp"
 
 namespace tc2li {
@@ -73,7 +75,13 @@ struct BawFollow {
 };
 // space: which set of buffers (0: tc2li_ba_window_batch's own; 1 + g: the one that goes with lock-step context g).  edges_optional: a
 // problem whose `edges` is NULL keeps its edges on the device (they are gathered into room for every observation, and not downloaded).
+struct MgLease;   // map_graph_host.hpp
 int ba_window_batch_run(const char* entry, tc2li_keyframe_store* store, const tc2li_ba_window_problem* problems, int n_problems,
-                        const float* inv_level_sigma2, int n_levels, void* stream, BawFollow* follow, int space, bool edges_optional);
+                        const float* inv_level_sigma2, int n_levels, void* stream, BawFollow* follow, int space, bool edges_optional,
+                        MgLease* resident = nullptr);
+// resident: the problems carry no table; problem p reads sequence resident->seq[p] of the map graph, whose lock the lease holds.
+// resident_windows makes such problems of a graph-reading entry's (windows: a copy of them) and takes the lease.
+int resident_windows(const char* entry, MgLease* lease, tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences, int n_problems,
+                     std::vector<tc2li_ba_window_problem>* windows);
 
 }  // namespace tc2li

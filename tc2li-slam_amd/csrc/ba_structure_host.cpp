@@ -6,6 +6,7 @@
 #include <mutex>
 
 #include "lockstep_host.hpp"
+#include "map_graph_host.hpp"
 
 namespace tc2li {
 namespace ba_detail {
@@ -428,9 +429,11 @@ extern "C" int tc2li_ba_window_structure_batch(tc2li_keyframe_store* store, cons
     return ba_window_batch_run(entry, store, problems, n_problems, inv_level_sigma2, n_levels, stream, &F, 0, false);
 }
 
-extern "C" int tc2li_ba_window_solve_batch(tc2li_keyframe_store* store, const tc2li_ba_window_solve_problem* problems, int n_problems,
-                                           const float* inv_level_sigma2, int n_levels, const tc2li_camera* cam, int group, int32_t* results) {
-    const char* entry = "tc2li_ba_window_solve_batch";
+namespace {
+// tc2li_ba_window_solve_batch, or with a graph tc2li_ba_window_solve_graph_batch: the windows' tables from the sequences of the map graph
+int solve_batch(const char* entry, tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences,
+                const tc2li_ba_window_solve_problem* problems, int n_problems, const float* inv_level_sigma2, int n_levels, const tc2li_camera* cam,
+                int group, int32_t* results) {
     if (n_problems < 0 || (n_problems > 0 && (!problems || !results)) || !cam || group < 0 || group >= kMaxLockstepGroups) {
         set_error("%s: invalid argument (group 0 .. %d)", entry, kMaxLockstepGroups - 1);
         return TC2LI_ERR_INVALID;
@@ -445,12 +448,29 @@ extern "C" int tc2li_ba_window_solve_batch(tc2li_keyframe_store* store, const tc
         }
         windows[p] = q.window;
     }
+    MgLease lease;
+    if (graph) {
+        const int lrc = resident_windows(entry, &lease, store, graph, sequences, n_problems, &windows);
+        if (lrc < 0) return lrc;
+    }
     BasSpace& S = shutdown_owned<BasSpaces>().s[1 + group];
     std::lock_guard<std::mutex> lk(S.mu);
     SolveFollow F(S);
     F.problems = windows.data(); F.n = n_problems; F.solve = problems; F.cam = cam; F.group = group; F.results = results;
     F.use_lidar.assign(std::max(n_problems, 0), 0);
     for (int p = 0; p < n_problems; ++p) F.use_lidar[p] = problems[p].cloud_xyz ? 1 : 0;
-    const int rc = ba_window_batch_run(entry, store, windows.data(), n_problems, inv_level_sigma2, n_levels, nullptr, &F, 1 + group, true);
-    return rc;
+    return ba_window_batch_run(entry, store, windows.data(), n_problems, inv_level_sigma2, n_levels, nullptr, &F, 1 + group, true, graph ? &lease : nullptr);
+}
+}  // namespace
+
+extern "C" int tc2li_ba_window_solve_batch(tc2li_keyframe_store* store, const tc2li_ba_window_solve_problem* problems, int n_problems,
+                                           const float* inv_level_sigma2, int n_levels, const tc2li_camera* cam, int group, int32_t* results) {
+    return solve_batch("tc2li_ba_window_solve_batch", store, nullptr, nullptr, problems, n_problems, inv_level_sigma2, n_levels, cam, group, results);
+}
+
+extern "C" int tc2li_ba_window_solve_graph_batch(tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences,
+                                                 const tc2li_ba_window_solve_problem* problems, int n_problems, const float* inv_level_sigma2, int n_levels,
+                                                 const tc2li_camera* cam, int group, int32_t* results) {
+    if (!graph) { set_error("tc2li_ba_window_solve_graph_batch: null graph"); return TC2LI_ERR_INVALID; }
+    return solve_batch("tc2li_ba_window_solve_graph_batch", store, graph, sequences, problems, n_problems, inv_level_sigma2, n_levels, cam, group, results);
 }

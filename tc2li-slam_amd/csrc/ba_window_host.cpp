@@ -10,6 +10,7 @@
 
 #include "ba_structure_device.hpp"
 #include "ba_window_device.hpp"
+#include "map_graph_host.hpp"
 #include "window_gather_host.hpp"
 
 namespace tc2li {
@@ -37,6 +38,37 @@ const char* validate(const tc2li_ba_window_problem& in, const SlotTable& slots, 
         }
         return "";
     });
+}
+
+// The same for a problem whose tables are a sequence of the resident map graph: the tables were checked when they were set and edited, so
+// what is left is the problem's own -- sizes, outputs, current, cov_kf -- and, in O(n_keyframes), that the store still holds the slots of
+// the sequence's keyframe rows with no octave beyond n_levels.
+const char* validate_resident(const tc2li_ba_window_problem& in, const MgSequenceView& seq, const SlotTable& slots, int n_levels, bool edges_optional) {
+    if (in.n_cov < 0) return "negative size";
+    if (in.pose_capacity < 0 || in.point_capacity < 0 || in.edge_capacity < 0) return "negative capacity";
+    if (!in.counts || !in.lidar_pose_index) return "null counts or lidar_pose_index";
+    if (in.current < 0 || in.current >= in.n_keyframes) return "current out of range";
+    if (in.n_cov && !in.cov_kf) return "null cov_kf";
+    if (in.pose_capacity && (!in.pose_row || !in.poses7_out || !in.fixed)) return "null pose output";
+    if (in.point_capacity && (!in.point_row || !in.points3_out)) return "null point output";
+    if (in.edge_capacity && !in.edges && !edges_optional) return "null edges";
+    const int n_store = (int)slots.n.size();
+    for (int k = 0; k < in.n_keyframes; ++k) {
+        const int s = seq.kf_store_slot[k];
+        if (s < 0 || s >= n_store || slots.n[s] < 0) return "a kf_slot is empty or out of range";
+        if (slots.levels[s] > n_levels) return "a slot holds an octave outside [0, n_levels)";
+        // the resident obs_index were checked against the keypoints the slot held then: a slot put again with fewer would be read beyond its end
+        if (slots.n[s] < seq.kf_keys[k]) return "a kf_slot holds fewer keypoints than when the row's observations were checked";
+    }
+    std::vector<uint8_t> named(in.n_keyframes, 0);
+    named[in.current] = 1;
+    for (int i = 0; i < in.n_cov; ++i) {
+        const int k = in.cov_kf[i];
+        if (k < 0 || k >= in.n_keyframes) return "cov_kf out of range";
+        if (named[k]) return "cov_kf names a row twice or the current keyframe";
+        named[k] = 1;
+    }
+    return "";
 }
 
 // edges_optional: a problem without an edge array leaves its edges on the device, whatever their number
@@ -169,8 +201,34 @@ extern "C" int tc2li_ba_window_batch(tc2li_keyframe_store* store, const tc2li_ba
     return ba_window_batch_run("tc2li_ba_window_batch", store, problems, n_problems, inv_level_sigma2, n_levels, stream, nullptr, 0, false);
 }
 
+// The problems of a graph-reading entry as ba_window_batch_run takes them: no table, the sizes of the problem's sequence.
+int tc2li::resident_windows(const char* entry, MgLease* lease, tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences, int n_problems,
+                            std::vector<tc2li_ba_window_problem>* windows) {
+    if (!store || n_problems < 0) { set_error("%s: null store or negative size", entry); return TC2LI_ERR_INVALID; }
+    const int rc = lease->acquire(entry, graph, store, sequences, n_problems);
+    if (rc < 0) return rc;
+    for (int p = 0; p < n_problems; ++p) {
+        tc2li_ba_window_problem& w = (*windows)[p];
+        w.kf_slot = nullptr; w.kf_id = nullptr; w.kf_flags = nullptr; w.poses7 = nullptr; w.slot_offsets = nullptr; w.slot_point = nullptr;
+        w.point_flags = nullptr; w.positions = nullptr; w.obs_offsets = nullptr; w.obs_kf = nullptr; w.obs_index = nullptr;
+        w.n_keyframes = lease->seq[p].n_kf; w.n_points = lease->seq[p].n_points;
+    }
+    return 0;
+}
+
+extern "C" int tc2li_ba_window_graph_batch(tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences, const tc2li_ba_window_problem* problems,
+                                           int n_problems, const float* inv_level_sigma2, int n_levels, void* stream) {
+    const char* entry = "tc2li_ba_window_graph_batch";
+    if (n_problems > 0 && !problems) { set_error("%s: null problems", entry); return TC2LI_ERR_INVALID; }
+    std::vector<tc2li_ba_window_problem> windows(problems, problems + std::max(n_problems, 0));
+    MgLease lease;
+    const int rc = resident_windows(entry, &lease, store, graph, sequences, n_problems, &windows);
+    if (rc < 0) return rc;
+    return ba_window_batch_run(entry, store, windows.data(), n_problems, inv_level_sigma2, n_levels, stream, nullptr, 0, false, &lease);
+}
+
 int tc2li::ba_window_batch_run(const char* entry, tc2li_keyframe_store* store, const tc2li_ba_window_problem* problems, int n_problems,
-                               const float* inv_level_sigma2, int n_levels, void* stream, BawFollow* follow, int space, bool edges_optional) {
+                               const float* inv_level_sigma2, int n_levels, void* stream, BawFollow* follow, int space, bool edges_optional, MgLease* resident) {
     if (!store) {
         set_error("%s: null store", entry);
         return TC2LI_ERR_INVALID;
@@ -180,16 +238,25 @@ int tc2li::ba_window_batch_run(const char* entry, tc2li_keyframe_store* store, c
     slot_table_from_store(store, &slots, &where);
     if (space < 0 || space > kMaxLockstepGroups) { set_error("%s: no such buffer set", entry); return TC2LI_ERR_INVALID; }
     const int rc = validate_all(entry, problems, n_problems, inv_level_sigma2, n_levels,
-                                [&](const tc2li_ba_window_problem& in) { return validate(in, slots, n_levels, edges_optional); });
+                                [&](const tc2li_ba_window_problem& in) {
+                                    return resident ? validate_resident(in, resident->seq[&in - problems], slots, n_levels, edges_optional)
+                                                    : validate(in, slots, n_levels, edges_optional);
+                                });
     if (rc < 0) return rc;
     if (!device_ready()) return TC2LI_ERR_NO_DEVICE;
     if (n_problems == 0) return 0;
     hipStream_t st = stream ? (hipStream_t)stream : private_stream();
     WindowTransfer<tc2li_ba_window_problem, BawProblemDev> T(problems, n_problems);
     size_t n_cov = 0, n_pose = 0;
+    T.resident = resident != nullptr;
     for (int p = 0; p < n_problems; ++p) {
         const tc2li_ba_window_problem& in = problems[p];
-        BawProblemDev& d = T.add(p, edges_optional && !in.edges ? INT_MAX : in.edge_capacity);
+        const int edge_room = edges_optional && !in.edges ? INT_MAX : in.edge_capacity;
+        BawProblemDev& d = resident ? T.add(p, edge_room, resident->seq[p].n_slot, resident->seq[p].n_obs) : T.add(p, edge_room);
+        if (resident) {
+            const MgSequenceView& s = resident->seq[p];
+            d.t_kf = s.t_kf; d.t_slot = s.t_slot; d.t_point = s.t_point; d.t_obs = s.t_obs; d.slot_row = s.slot_row; d.obs_row = s.obs_row;
+        }
         d.init_kf_id = in.init_kf_id;
         d.cov_off = (int32_t)n_cov; d.n_cov = in.n_cov;
         d.pose_off = (int32_t)n_pose; d.pose_cap = std::min(in.pose_capacity, in.n_keyframes);
@@ -198,7 +265,9 @@ int tc2li::ba_window_batch_run(const char* entry, tc2li_keyframe_store* store, c
     }
     const size_t np = (size_t)n_problems;
     T.take_inputs(n_levels);
-    const size_t o_pose = T.io.take(T.n_kf * 56), o_cov = T.io.take(n_cov * 4);
+    size_t o_pose, o_cov;
+    if (resident) { o_pose = o_cov = T.io.off; T.io.off += n_cov * 4; }   // the poses are resident; cov_kf follows the level table
+    else { o_pose = T.io.take(T.n_kf * 56); o_cov = T.io.take(n_cov * 4); }
     T.take_outputs(TC2LI_BA_WINDOW_COUNTS);
     const size_t o_p7 = T.io.take(n_pose * 56), o_prow = T.io.take(n_pose * 4), o_fixed = T.io.take(n_pose);
     T.take_work();
@@ -207,14 +276,22 @@ int tc2li::ba_window_batch_run(const char* entry, tc2li_keyframe_store* store, c
     std::lock_guard<std::mutex> lk(S.mu);
     TC2LI_HIP_CHECK(T.ensure(S));
     TC2LI_HIP_CHECK(T.upload_tables(inv_level_sigma2, n_levels, st, [&](int, const tc2li_ba_window_problem& in, const BawProblemDev& d) {
-        T.io.put(o_pose, d.kf_off, in.poses7, (size_t)in.n_keyframes, 56);
+        if (!resident) T.io.put(o_pose, d.kf_off, in.poses7, (size_t)in.n_keyframes, 56);
         T.io.put(o_cov, d.cov_off, in.cov_kf, (size_t)in.n_cov, 4);
     }));
+    if (resident) resident->uploaded = (int64_t)T.up_bytes;
     uint8_t* d = T.d_io;
     const BawProblemDev* dev = T.dev.data();
     BawBatch B{};
     T.bind(B, where);
-    B.poses7 = (const double*)(d + o_pose); B.cov_kf = (const int32_t*)(d + o_cov); B.list_kf = T.dev_work<int32_t>(w_lkf);
+    B.poses7 = (const double*)(d + o_pose);
+    if (resident) {   // the tables of the slab in place of the uploaded ones
+        const MgTables& G = resident->T;
+        B.kf_slot = G.kf_slot; B.kf_id = G.kf_id; B.kf_flags = G.kf_flags; B.slot_offsets = G.slot_offsets; B.slot_point = G.slot_point;
+        B.point_flags = G.point_flags; B.positions = G.positions; B.obs_offsets = G.obs_offsets; B.obs_kf = G.obs_kf; B.obs_index = G.obs_index;
+        B.poses7 = G.poses7;
+    }
+    B.cov_kf = (const int32_t*)(d + o_cov); B.list_kf = T.dev_work<int32_t>(w_lkf);
     B.counts = (int32_t*)(d + T.o_counts); B.lidar_pose_index = (int32_t*)(d + T.o_lidar); B.pose_row = (int32_t*)(d + o_prow);
     B.poses7_out = (double*)(d + o_p7); B.fixed = d + o_fixed;
     launch_ba_window(B, st);

@@ -21,15 +21,15 @@ namespace tc2li {
 // sh: [0] a local keyframe is the initial one (:85-88), [1 .. 6] vOptKeyFrames of :227-233 as rows
 __device__ __forceinline__ void baw_problem(const BawBatch& B, const BawProblemDev& P, int* marks, int* first, int* scan, int* sh) {
     const int tid = threadIdx.x;
-    const uint8_t* flags = B.kf_flags + P.kf_off;
-    const int64_t* kf_id = B.kf_id + P.kf_off;
-    const int32_t* slot_row = B.slot_offsets + P.kf_off + blockIdx.x;
-    const int32_t* slot_point = B.slot_point + P.slot_off;
+    const uint8_t* flags = B.kf_flags + P.t_kf;
+    const int64_t* kf_id = B.kf_id + P.t_kf;
+    const int32_t* slot_row = B.slot_offsets + P.slot_row;
+    const int32_t* slot_point = B.slot_point + P.t_slot;
     const int32_t* cov = B.cov_kf + P.cov_off;
-    const uint8_t* pflags = B.point_flags + P.point_off;
-    const int32_t* obs_row = B.obs_offsets + P.point_off + blockIdx.x;
-    const int32_t* obs_kf = B.obs_kf + P.obs_off;
-    const int32_t* obs_index = B.obs_index + P.obs_off;
+    const uint8_t* pflags = B.point_flags + P.t_point;
+    const int32_t* obs_row = B.obs_offsets + P.obs_row;
+    const int32_t* obs_kf = B.obs_kf + P.t_obs;
+    const int32_t* obs_index = B.obs_index + P.t_obs;
     int32_t* list_kf = B.list_kf + P.cov_off + 2 * blockIdx.x;
     int32_t* listed = B.listed + P.point_off;
     int32_t* edge_start = B.edge_start + P.point_off;
@@ -114,7 +114,7 @@ __device__ __forceinline__ void baw_problem(const BawBatch& B, const BawProblemD
     int32_t* pose_row = B.pose_row + P.pose_off;
     double* poses7_out = B.poses7_out + (size_t)P.pose_off * 7;
     uint8_t* fixed_out = B.fixed + P.pose_off;
-    const double* poses7 = B.poses7 + (size_t)P.kf_off * 7;
+    const double* poses7 = B.poses7 + (size_t)P.t_kf * 7;
     window_rank_members(kf_id, members, n_members, kf_pose, P.pose_cap, [&](int k, int r, int64_t id) {
         pose_row[r] = k;
 #pragma unroll
@@ -156,15 +156,15 @@ __global__ __launch_bounds__(kWinThreads) void k_baw_gather(BawBatch B) {
 __global__ __launch_bounds__(kWinThreads) void k_window_edges(WindowBatch B) {
     const WindowProblemDev& P = window_problem<WindowProblemDev>(B, blockIdx.x);
     const int n_listed = B.n_emit[blockIdx.x];
-    const uint8_t* flags = B.kf_flags + P.kf_off;
-    const int32_t* kf_slot = B.kf_slot + P.kf_off;
+    const uint8_t* flags = B.kf_flags + P.t_kf;
+    const int32_t* kf_slot = B.kf_slot + P.t_kf;
     const int32_t* vertex_of = B.vertex_of + P.kf_off;
-    const int32_t* obs_row = B.obs_offsets + P.point_off + blockIdx.x;
-    const int32_t* obs_kf = B.obs_kf + P.obs_off;
-    const int32_t* obs_index = B.obs_index + P.obs_off;
+    const int32_t* obs_row = B.obs_offsets + P.obs_row;
+    const int32_t* obs_kf = B.obs_kf + P.t_obs;
+    const int32_t* obs_index = B.obs_index + P.t_obs;
     const int32_t* listed = B.listed + P.point_off;
     const int32_t* edge_start = B.edge_start + P.point_off;
-    const double* positions = B.positions + (size_t)P.point_off * 3;
+    const double* positions = B.positions + (size_t)P.t_point * 3;
     int32_t* point_row = B.point_row + P.pointo_off;
     double* points3_out = B.points3_out + (size_t)P.pointo_off * 3;
     tc2li_ba_edge* edges = B.edges + P.edge_off;

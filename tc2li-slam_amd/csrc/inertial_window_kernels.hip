@@ -80,15 +80,15 @@ __device__ __forceinline__ int iw_fixed_observers(int* marks, const uint8_t* fla
 // sh: [0 .. 25) vpOptimizableKFs as rows, [25] its size before :553, [26] N after, [27] lFixedKeyFrames.size()
 __device__ __forceinline__ void iw_problem(const IwBatch& B, const IwProblemDev& P, int* marks, int* first, int* scan, int* sh) {
     const int tid = threadIdx.x;
-    const uint8_t* flags = B.kf_flags + P.kf_off;
-    const int64_t* kf_id = B.kf_id + P.kf_off;
+    const uint8_t* flags = B.kf_flags + P.t_kf;
+    const int64_t* kf_id = B.kf_id + P.t_kf;
     const int32_t* prev = B.prev_kf + P.kf_off;
-    const int32_t* slot_row = B.slot_offsets + P.kf_off + blockIdx.x;
-    const int32_t* slot_point = B.slot_point + P.slot_off;
-    const uint8_t* pflags = B.point_flags + P.point_off;
-    const int32_t* obs_row = B.obs_offsets + P.point_off + blockIdx.x;
-    const int32_t* obs_kf = B.obs_kf + P.obs_off;
-    const int32_t* obs_index = B.obs_index + P.obs_off;
+    const int32_t* slot_row = B.slot_offsets + P.slot_row;
+    const int32_t* slot_point = B.slot_point + P.t_slot;
+    const uint8_t* pflags = B.point_flags + P.t_point;
+    const int32_t* obs_row = B.obs_offsets + P.obs_row;
+    const int32_t* obs_kf = B.obs_kf + P.t_obs;
+    const int32_t* obs_index = B.obs_index + P.t_obs;
     int32_t* listed = B.listed + P.point_off;
     int32_t* edge_start = B.edge_start + P.point_off;
     int32_t* kf_vertex = B.vertex_of + P.kf_off;

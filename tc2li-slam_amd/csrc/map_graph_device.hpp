@@ -1,0 +1,74 @@
+// Device side of the resident map graph (include/tc2li_hip.h "the map graph resident on the device"): map_graph_host.cpp keeps the slab,
+// the per-row metadata and the checks, map_graph_kernels.hip applies an edit log.  The slab is table-major -- every table holds all
+// sequences, a sequence's part at sequence * capacity -- so that a gather (ba_window_kernels.hip) reads a sequence's tables at 32-bit
+// starts from one base pointer per table, as it reads the concatenated tables of a batch of host arrays.  The observation CSR cannot be
+// edited in place: it has two generations per sequence, an apply reads the one and writes the other, and the host remembers which is
+// current.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/tc2li_hip.h"
+
+namespace tc2li {
+
+constexpr int kMgThreads = 256;            // per sequence in k_mg_apply, per block in k_mg_write
+constexpr int kMgLdsRow = 256;             // up to here (old entries + the ADD edits of the row) a touched observation row is merged in LDS, beyond in global memory
+constexpr int kMgWriteBlocks = 8;          // workgroups per sequence in k_mg_write
+// A touched observation row finds its edits by walking the log from its first to its last edit.  The sum of those stretches over the
+// touched rows of one log is the work of one workgroup; the host refuses a log beyond this many edit reads (a few milliseconds of one
+// workgroup), so that no log can hold a shared card for long.  One keyframe's worth of edits -- one edit per point -- reads one each.
+constexpr int64_t kMgMaxWalk = 1 << 22;
+
+struct MgTables {
+    int32_t* kf_slot;                      // [S][cap_kf]
+    int64_t* kf_id;
+    uint8_t* kf_flags;
+    double* poses7;                        // [S][cap_kf][7]
+    int32_t* slot_offsets;                 // [S][cap_kf + 1]
+    int32_t* slot_point;                   // [S][cap_slot]
+    uint8_t* point_flags;                  // [S][cap_pt]
+    double* positions;                     // [S][cap_pt][3]
+    int32_t* obs_offsets;                  // [S][2][cap_pt + 1]
+    int32_t* obs_kf;                       // [S][2][cap_obs]
+    int32_t* obs_index;
+    // scratch of an apply, per sequence
+    int32_t* pt_head;                      // [S][cap_pt] the first edit of the log on the point's observation row, 0x7fffffff: untouched
+    int32_t* pt_last;                      // the last one
+    int32_t* pt_len;                       // the row's new length
+    int32_t* pt_stage;                     // first the row's ADD edits counted, then where its merged row is staged
+    int32_t* touched;                      // the touched rows, compacted
+    int32_t* stage_kf;                     // [S][cap_obs] the merged rows until the new offsets are known
+    int32_t* stage_index;
+    int32_t cap_kf, cap_slot, cap_pt, cap_obs;
+};
+
+// One sequence of an apply: 64 bytes.  The sizes are the resident ones before the log; the host has checked every edit against them.
+struct MgApplyDev {
+    int32_t sequence, generation;          // the observation CSR that is current
+    int32_t n_kf, n_points, n_slot, n_obs;
+    int32_t edit_off, n_edits, value_off;  // the sequence's part of the batch's edits and values
+    int32_t n_points_new;                  // n_points + the ADD_POINT edits of the log
+    int32_t pad_[6];
+};
+static_assert(sizeof(MgApplyDev) == 64, "an apply moves 64 bytes per sequence beside its edits and values");
+
+struct MgApplyBatch {
+    MgTables T;
+    int n;
+    const MgApplyDev* deltas;
+    const tc2li_map_graph_edit* edits;
+    const double* values;
+    int32_t* totals;                       // [n] the observation entries of every sequence after its log
+};
+void launch_map_graph_apply(const MgApplyBatch& B, hipStream_t st);
+
+// A sequence as a gather reads it: the sizes, and where its tables start in the slab's tables (WindowProblemDev::t_*, slot_row, obs_row).
+struct MgSequenceView {
+    int32_t n_kf, n_points, n_slot, n_obs;
+    int32_t t_kf, t_slot, t_point, t_obs, slot_row, obs_row;
+    const int32_t* kf_store_slot;          // host: the store slot of every keyframe row
+    const int32_t* kf_keys;                // host: the keypoints that slot held when the row's observation indices were checked
+};
+
+}  // namespace tc2li

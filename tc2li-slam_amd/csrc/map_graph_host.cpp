@@ -1,0 +1,506 @@
+// tc2li_map_graph_* / tc2li_host_map_graph_apply (include/tc2li_hip.h "the map graph resident on the device"): the slab and its layout,
+// the host's mirror of per-row metadata (row counts, the store slot and the slot row of every keyframe row, the observation total -- no
+// table), the check of an edit log against it, the log's way to the device (map_graph_kernels.hip) and the plain sequential twin that
+// defines the result.  MgLease (map_graph_host.hpp) is how a gather reads the graph (ba_window_host.cpp).
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <utility>
+#include <vector>
+
+#include "common.hpp"
+#include "map_graph_host.hpp"
+#include "packed_batch.hpp"
+#include "window_gather_host.hpp"
+
+using namespace tc2li;
+
+namespace {
+
+struct SeqMeta {
+    bool set = false;
+    int generation = 0;                      // the observation CSR that is current
+    int n_kf = 0, n_pt = 0, n_obs = 0;
+    int applies = -1;
+    int64_t apply_bytes = 0, gather_bytes = 0;
+    std::vector<int32_t> store_slot;         // [n_kf]
+    std::vector<int32_t> n_keys;             // [n_kf] the most keypoints the row's store slot held at a set or an apply: every resident obs_index is below it
+    std::vector<int32_t> slot_off{0};        // [n_kf + 1] slot_offsets
+};
+
+}  // namespace
+
+struct tc2li_map_graph_handle {
+    tc2li_keyframe_store* store = nullptr;
+    int n_seq = 0;
+    int32_t cap[TC2LI_MAP_GRAPH_CAPACITIES] = {0, 0, 0, 0};
+    uint8_t* slab = nullptr;
+    MgTables T{};
+    std::vector<SeqMeta> seq;
+    std::mutex mu;                           // one call at a time on a graph
+    PinnedBuf<uint8_t> h_up;                 // what a call stages: the tables of a set, the records, edits and values of an apply
+    PinnedBuf<CopyTask> tasks;
+    DevBuf<uint8_t> d_up;
+    DevBuf<int32_t> d_totals;
+    PinnedBuf<int32_t> h_totals;
+};
+
+namespace {
+
+// ---- the check of a log ----------------------------------------------------------------------------------------------------------------
+// The sizes a log meets and what they are after it.  store_slot / slot_off: of the rows resident now.
+struct LogSizes {
+    int n_kf, n_pt, n_obs;
+    const int32_t* store_slot;
+    const int32_t* slot_off;
+};
+struct LogAfter {
+    int n_kf = 0, n_pt = 0, n_slot = 0, n_adds = 0;
+    std::vector<int32_t> new_store_slot, new_slots;   // of the rows the log appends
+};
+
+bool is_byte(double v) { return v >= 0 && v <= 255 && v == std::floor(v); }
+
+// 0, or the code with *what set.  The first edit in log order that fails decides; the observation bound comes after all edits.
+// store_n: the keypoints of every store slot (-1: empty), or NULL for the host twin, which has no store.
+int check_log(const LogSizes& m, const tc2li_map_graph_edit* edits, int n_edits, const double* values, int n_values, const int32_t* cap,
+              const std::vector<int32_t>* store_n, LogAfter* r, const char** what) {
+    r->n_kf = m.n_kf; r->n_pt = m.n_pt; r->n_slot = m.slot_off[m.n_kf]; r->n_adds = 0;
+    auto fail = [&](int code, const char* w) { *what = w; return code; };
+    auto has_values = [&](int32_t off, int count) { return off >= 0 && (int64_t)off + count <= n_values; };
+    auto slots_of = [&](int row) { return row < m.n_kf ? m.slot_off[row + 1] - m.slot_off[row] : r->new_slots[row - m.n_kf]; };
+    auto store_slot_of = [&](int row) { return row < m.n_kf ? m.store_slot[row] : r->new_store_slot[row - m.n_kf]; };
+    if (n_edits < 0 || n_values < 0 || (n_edits && !edits) || (n_values && !values)) return fail(TC2LI_ERR_INVALID, "null or negative log");
+    for (int e = 0; e < n_edits; ++e) {
+        const tc2li_map_graph_edit& ed = edits[e];
+        switch (ed.op) {
+            case TC2LI_MAP_GRAPH_ADD_KEYFRAME: {
+                if (ed.a < 0 || (store_n && (ed.a >= (int)store_n->size() || (*store_n)[ed.a] < 0))) return fail(TC2LI_ERR_INVALID, "a store slot is empty or out of range");
+                if (ed.b < 0) return fail(TC2LI_ERR_INVALID, "a negative slot count");
+                if (!has_values(ed.c, 9)) return fail(TC2LI_ERR_INVALID, "a values offset out of range");
+                const double id = values[ed.c];
+                if (!(std::fabs(id) <= 9007199254740992.0) || id != std::floor(id) || !is_byte(values[ed.c + 1])) return fail(TC2LI_ERR_INVALID, "a keyframe id or flags that is no integer");
+                if (r->n_kf + 1 > cap[TC2LI_MAP_GRAPH_KEYFRAMES]) return fail(TC2LI_ERR_CAPACITY, "keyframe rows beyond the capacity");
+                if ((int64_t)r->n_slot + ed.b > cap[TC2LI_MAP_GRAPH_SLOTS]) return fail(TC2LI_ERR_CAPACITY, "slot entries beyond the capacity");
+                r->new_store_slot.push_back(ed.a); r->new_slots.push_back(ed.b);
+                ++r->n_kf; r->n_slot += ed.b;
+                break;
+            }
+            case TC2LI_MAP_GRAPH_SET_KEYFRAME_FLAGS:
+                if (ed.a < 0 || ed.a >= r->n_kf) return fail(TC2LI_ERR_INVALID, "a keyframe row out of range or named before its append");
+                if (ed.b < 0 || ed.b > 255) return fail(TC2LI_ERR_INVALID, "flags outside a byte");
+                break;
+            case TC2LI_MAP_GRAPH_SET_POSE:
+                if (ed.a < 0 || ed.a >= r->n_kf) return fail(TC2LI_ERR_INVALID, "a keyframe row out of range or named before its append");
+                if (!has_values(ed.b, 7)) return fail(TC2LI_ERR_INVALID, "a values offset out of range");
+                break;
+            case TC2LI_MAP_GRAPH_ADD_POINT:
+                if (ed.a < 0 || ed.a > 255) return fail(TC2LI_ERR_INVALID, "flags outside a byte");
+                if (!has_values(ed.b, 3)) return fail(TC2LI_ERR_INVALID, "a values offset out of range");
+                if (r->n_pt + 1 > cap[TC2LI_MAP_GRAPH_POINTS]) return fail(TC2LI_ERR_CAPACITY, "point rows beyond the capacity");
+                ++r->n_pt;
+                break;
+            case TC2LI_MAP_GRAPH_SET_POINT_FLAGS:
+                if (ed.a < 0 || ed.a >= r->n_pt) return fail(TC2LI_ERR_INVALID, "a point row out of range or named before its append");
+                if (ed.b < 0 || ed.b > 255) return fail(TC2LI_ERR_INVALID, "flags outside a byte");
+                break;
+            case TC2LI_MAP_GRAPH_SET_POSITION:
+                if (ed.a < 0 || ed.a >= r->n_pt) return fail(TC2LI_ERR_INVALID, "a point row out of range or named before its append");
+                if (!has_values(ed.b, 3)) return fail(TC2LI_ERR_INVALID, "a values offset out of range");
+                break;
+            case TC2LI_MAP_GRAPH_SET_SLOT:
+                if (ed.a < 0 || ed.a >= r->n_kf) return fail(TC2LI_ERR_INVALID, "a keyframe row out of range or named before its append");
+                if (ed.b < 0 || ed.b >= slots_of(ed.a)) return fail(TC2LI_ERR_INVALID, "a slot out of range");
+                if (ed.c < -1 || ed.c >= r->n_pt) return fail(TC2LI_ERR_INVALID, "a point below -1, out of range or named before its append");
+                break;
+            case TC2LI_MAP_GRAPH_ADD_OBSERVATION:
+                if (ed.a < 0 || ed.a >= r->n_pt) return fail(TC2LI_ERR_INVALID, "a point row out of range or named before its append");
+                if (ed.b < 0 || ed.b >= r->n_kf) return fail(TC2LI_ERR_INVALID, "a keyframe row out of range or named before its append");
+                if (ed.c < -1 || (store_n && ed.c >= (*store_n)[store_slot_of(ed.b)])) return fail(TC2LI_ERR_INVALID, "an observation index outside the keypoints of the observer's slot");
+                ++r->n_adds;
+                break;
+            case TC2LI_MAP_GRAPH_ERASE_OBSERVATION:
+                if (ed.a < 0 || ed.a >= r->n_pt) return fail(TC2LI_ERR_INVALID, "a point row out of range or named before its append");
+                if (ed.b < 0 || ed.b >= r->n_kf) return fail(TC2LI_ERR_INVALID, "a keyframe row out of range or named before its append");
+                break;
+            case TC2LI_MAP_GRAPH_CLEAR_OBSERVATIONS:
+                if (ed.a < 0 || ed.a >= r->n_pt) return fail(TC2LI_ERR_INVALID, "a point row out of range or named before its append");
+                break;
+            default: return fail(TC2LI_ERR_INVALID, "an unknown op");
+        }
+    }
+    // the host cannot know whether an ADD grows a row: conservative, and exact to state
+    if ((int64_t)m.n_obs + r->n_adds > cap[TC2LI_MAP_GRAPH_OBSERVATIONS]) return fail(TC2LI_ERR_CAPACITY, "observation entries resident + ADD_OBSERVATION edits beyond the capacity");
+    return 0;
+}
+
+const char* tables_fault(const tc2li_map_graph_tables& t) {
+    if (t.n_keyframes < 0 || t.n_points < 0) return "negative size";
+    if (!t.slot_offsets || !t.obs_offsets) return "null slot_offsets or obs_offsets";
+    if ((t.n_keyframes && (!t.kf_slot || !t.kf_id || !t.kf_flags || !t.poses7)) || (t.n_points && (!t.point_flags || !t.positions)))
+        return "null kf_slot, kf_id, kf_flags, poses7, point_flags or positions";
+    return "";
+}
+
+bool sequence_ok(const tc2li_map_graph_handle* g, int s) { return s >= 0 && s < g->n_seq; }
+
+MgSequenceView view_of(const tc2li_map_graph_handle* g, int s) {
+    const SeqMeta& m = g->seq[s];
+    MgSequenceView v{};
+    v.n_kf = m.n_kf; v.n_points = m.n_pt; v.n_slot = m.slot_off[m.n_kf]; v.n_obs = m.n_obs;
+    v.t_kf = s * g->cap[0]; v.t_slot = s * g->cap[1]; v.t_point = s * g->cap[2];
+    v.t_obs = (2 * s + m.generation) * g->cap[3];
+    v.slot_row = s * (g->cap[0] + 1); v.obs_row = (2 * s + m.generation) * (g->cap[2] + 1);
+    v.kf_store_slot = m.store_slot.data(); v.kf_keys = m.n_keys.data();
+    return v;
+}
+
+}  // namespace
+
+// ---- handle ----------------------------------------------------------------------------------------------------------------------------
+extern "C" int tc2li_map_graph_limits(int32_t* out, int capacity) {
+    if (!out || capacity < 6) {
+        set_error("tc2li_map_graph_limits: room for 6 values is needed");
+        return TC2LI_ERR_INVALID;
+    }
+    out[0] = kMgLdsRow; out[1] = kMgThreads; out[2] = kMgThreads; out[3] = (int32_t)sizeof(MgApplyDev); out[4] = (int32_t)sizeof(BawProblemDev); out[5] = (int32_t)kMgMaxWalk;
+    return 6;
+}
+
+extern "C" int tc2li_map_graph_create(tc2li_keyframe_store* store, int n_sequences, const int32_t* capacities, tc2li_map_graph_handle** out) {
+    const char* me = "tc2li_map_graph_create";
+    if (!out || !store || !capacities || n_sequences < 1) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    *out = nullptr;
+    for (int c = 0; c < TC2LI_MAP_GRAPH_CAPACITIES; ++c)
+        if (capacities[c] < 1 || 2 * (int64_t)n_sequences * ((int64_t)capacities[c] + 1) > (int64_t)kMaxRows) {
+            set_error("%s: a capacity below 1, or a table of all sequences beyond 2^31 rows", me);
+            return TC2LI_ERR_INVALID;
+        }
+    if (!device_ready()) return TC2LI_ERR_NO_DEVICE;
+    std::unique_ptr<tc2li_map_graph_handle> G(new tc2li_map_graph_handle());
+    G->store = store; G->n_seq = n_sequences;
+    memcpy(G->cap, capacities, sizeof(G->cap));
+    const size_t S = (size_t)n_sequences, K = (size_t)capacities[0], L = (size_t)capacities[1], P = (size_t)capacities[2], O = (size_t)capacities[3];
+    Packer slab;
+    const size_t o_slot = slab.take(S * K * 4), o_id = slab.take(S * K * 8), o_flags = slab.take(S * K), o_pose = slab.take(S * K * 56);
+    const size_t o_srow = slab.take(S * (K + 1) * 4), o_spt = slab.take(S * L * 4), o_pflags = slab.take(S * P), o_pos = slab.take(S * P * 24);
+    const size_t o_orow = slab.take(2 * S * (P + 1) * 4), o_okf = slab.take(2 * S * O * 4), o_oidx = slab.take(2 * S * O * 4);
+    const size_t o_head = slab.take(S * P * 4), o_last = slab.take(S * P * 4), o_len = slab.take(S * P * 4), o_stage = slab.take(S * P * 4);
+    const size_t o_touched = slab.take(S * P * 4), o_skf = slab.take(S * O * 4), o_sidx = slab.take(S * O * 4);
+    TC2LI_HIP_CHECK(hipMalloc((void**)&G->slab, slab.off));
+    uint8_t* b = G->slab;
+    MgTables& T = G->T;
+    T.kf_slot = (int32_t*)(b + o_slot); T.kf_id = (int64_t*)(b + o_id); T.kf_flags = b + o_flags; T.poses7 = (double*)(b + o_pose);
+    T.slot_offsets = (int32_t*)(b + o_srow); T.slot_point = (int32_t*)(b + o_spt); T.point_flags = b + o_pflags; T.positions = (double*)(b + o_pos);
+    T.obs_offsets = (int32_t*)(b + o_orow); T.obs_kf = (int32_t*)(b + o_okf); T.obs_index = (int32_t*)(b + o_oidx);
+    T.pt_head = (int32_t*)(b + o_head); T.pt_last = (int32_t*)(b + o_last); T.pt_len = (int32_t*)(b + o_len); T.pt_stage = (int32_t*)(b + o_stage);
+    T.touched = (int32_t*)(b + o_touched); T.stage_kf = (int32_t*)(b + o_skf); T.stage_index = (int32_t*)(b + o_sidx);
+    T.cap_kf = capacities[0]; T.cap_slot = capacities[1]; T.cap_pt = capacities[2]; T.cap_obs = capacities[3];
+    G->seq.assign(S, SeqMeta{});
+    *out = G.release();
+    return 0;
+}
+
+extern "C" int tc2li_map_graph_destroy(tc2li_map_graph_handle* g) {
+    if (!g) return 0;
+    if (g->slab) (void)hipFree(g->slab);
+    delete g;
+    return 0;
+}
+
+extern "C" int tc2li_map_graph_info(tc2li_map_graph_handle* g, int sequence, int64_t* out, int capacity) {
+    if (!g || !sequence_ok(g, sequence) || !out || capacity < TC2LI_MAP_GRAPH_INFO_FIELDS) { set_error("tc2li_map_graph_info: invalid argument"); return TC2LI_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(g->mu);
+    const SeqMeta& m = g->seq[sequence];
+    out[TC2LI_MAP_GRAPH_INFO_KEYFRAMES] = m.n_kf; out[TC2LI_MAP_GRAPH_INFO_POINTS] = m.n_pt; out[TC2LI_MAP_GRAPH_INFO_SLOTS] = m.slot_off[m.n_kf];
+    out[TC2LI_MAP_GRAPH_INFO_OBSERVATIONS] = m.n_obs; out[TC2LI_MAP_GRAPH_INFO_APPLIES] = m.applies;
+    out[TC2LI_MAP_GRAPH_INFO_APPLY_BYTES] = m.apply_bytes; out[TC2LI_MAP_GRAPH_INFO_GATHER_BYTES] = m.gather_bytes;
+    return TC2LI_MAP_GRAPH_INFO_FIELDS;
+}
+
+// ---- set -------------------------------------------------------------------------------------------------------------------------------
+extern "C" int tc2li_map_graph_set_batch(tc2li_map_graph_handle* g, const int32_t* sequences, const tc2li_map_graph_tables* tables, int n, void* stream) {
+    const char* me = "tc2li_map_graph_set_batch";
+    if (!g || n < 0 || (n && (!sequences || !tables))) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    if (n == 0) return 0;
+    std::lock_guard<std::mutex> lk(g->mu);
+    SlotTable slots;
+    BawStore where{};
+    slot_table_from_store(g->store, &slots, &where);
+    std::vector<uint8_t> named(g->n_seq, 0);
+    size_t bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        const tc2li_map_graph_tables& t = tables[i];
+        if (!sequence_ok(g, sequences[i]) || named[sequences[i]]) { set_error("%s: sequence %d out of range or named twice", me, sequences[i]); return TC2LI_ERR_INVALID; }
+        named[sequences[i]] = 1;
+        const char* what = tables_fault(t);
+        if (!what[0]) what = validate_graph(t, slots, INT_MAX, [](int) { return ""; }, [] { return ""; });
+        if (what[0]) { set_error("%s: sequence %d: %s", me, sequences[i], what); return TC2LI_ERR_INVALID; }
+        const int n_slot = t.slot_offsets[t.n_keyframes], n_obs = t.obs_offsets[t.n_points];
+        if (t.n_keyframes > g->cap[0] || n_slot > g->cap[1] || t.n_points > g->cap[2] || n_obs > g->cap[3]) {
+            set_error("%s: sequence %d has %d keyframes, %d slots, %d points and %d observations; the capacities are %d, %d, %d and %d", me, sequences[i],
+                      t.n_keyframes, n_slot, t.n_points, n_obs, g->cap[0], g->cap[1], g->cap[2], g->cap[3]);
+            return TC2LI_ERR_CAPACITY;
+        }
+        bytes += 16 * 11 + (size_t)t.n_keyframes * (4 + 8 + 1 + 56 + 4) + 4 + (size_t)n_slot * 4 + (size_t)t.n_points * (1 + 24 + 4) + 4 + (size_t)n_obs * 8;
+    }
+    if (!device_ready()) return TC2LI_ERR_NO_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : private_stream();
+    TC2LI_HIP_CHECK(g->h_up.ensure(bytes));
+    TC2LI_HIP_CHECK(g->tasks.ensure(11 * (size_t)n));
+    size_t at = 0, n_tasks = 0, max_bytes = 0;
+    auto stage = [&](void* dst, const void* src, size_t b) {
+        if (!b) return;
+        memcpy(g->h_up.p + at, src, b);
+        g->tasks.p[n_tasks++] = CopyTask{dst, g->h_up.p + at, b};
+        max_bytes = std::max(max_bytes, b);
+        at += (b + 15) & ~(size_t)15;
+    };
+    const MgTables& T = g->T;
+    for (int i = 0; i < n; ++i) {
+        const tc2li_map_graph_tables& t = tables[i];
+        const size_t s = (size_t)sequences[i], nk = (size_t)t.n_keyframes, np = (size_t)t.n_points;
+        const size_t n_slot = (size_t)t.slot_offsets[nk], n_obs = (size_t)t.obs_offsets[np];
+        stage(T.kf_slot + s * T.cap_kf, t.kf_slot, nk * 4); stage(T.kf_id + s * T.cap_kf, t.kf_id, nk * 8); stage(T.kf_flags + s * T.cap_kf, t.kf_flags, nk);
+        stage(T.poses7 + s * T.cap_kf * 7, t.poses7, nk * 56); stage(T.slot_offsets + s * ((size_t)T.cap_kf + 1), t.slot_offsets, (nk + 1) * 4);
+        stage(T.slot_point + s * T.cap_slot, t.slot_point, n_slot * 4); stage(T.point_flags + s * T.cap_pt, t.point_flags, np);
+        stage(T.positions + s * T.cap_pt * 3, t.positions, np * 24);
+        stage(T.obs_offsets + 2 * s * ((size_t)T.cap_pt + 1), t.obs_offsets, (np + 1) * 4);   // generation 0
+        stage(T.obs_kf + 2 * s * T.cap_obs, t.obs_kf, n_obs * 4); stage(T.obs_index + 2 * s * T.cap_obs, t.obs_index, n_obs * 4);
+    }
+    launch_copy_tasks(g->tasks.p, (int)n_tasks, max_bytes, st);
+    TC2LI_HIP_CHECK(hipGetLastError());
+    TC2LI_HIP_CHECK(stream_wait_blocking(st));   // resident on return: a gather on any stream may follow
+    for (int i = 0; i < n; ++i) {
+        const tc2li_map_graph_tables& t = tables[i];
+        SeqMeta& m = g->seq[sequences[i]];
+        m.set = true; m.generation = 0; m.n_kf = t.n_keyframes; m.n_pt = t.n_points; m.n_obs = t.obs_offsets[t.n_points];
+        m.applies = 0; m.apply_bytes = 0; m.gather_bytes = 0;
+        m.store_slot.assign(t.kf_slot, t.kf_slot + t.n_keyframes);
+        m.n_keys.resize(t.n_keyframes);
+        for (int k = 0; k < t.n_keyframes; ++k) m.n_keys[k] = slots.n[t.kf_slot[k]];
+        m.slot_off.assign(t.slot_offsets, t.slot_offsets + t.n_keyframes + 1);
+    }
+    return n;
+}
+
+// ---- apply -----------------------------------------------------------------------------------------------------------------------------
+extern "C" int tc2li_map_graph_apply_batch(tc2li_map_graph_handle* g, const tc2li_map_graph_delta* deltas, int n, void* stream) {
+    const char* me = "tc2li_map_graph_apply_batch";
+    if (!g || n < 0 || (n && !deltas)) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    if (n == 0) return 0;
+    std::lock_guard<std::mutex> lk(g->mu);
+    SlotTable slots;
+    BawStore where{};
+    slot_table_from_store(g->store, &slots, &where);
+    // ---- every check before any device work: a refused call leaves the graph as it was ----
+    std::vector<uint8_t> named(g->n_seq, 0);
+    std::vector<LogAfter> after(n);
+    size_t n_edits = 0, n_values = 0;
+    for (int i = 0; i < n; ++i) {
+        const tc2li_map_graph_delta& d = deltas[i];
+        if (!sequence_ok(g, d.sequence) || named[d.sequence]) { set_error("%s: sequence %d out of range or named twice", me, d.sequence); return TC2LI_ERR_INVALID; }
+        named[d.sequence] = 1;
+        const SeqMeta& m = g->seq[d.sequence];
+        if (!m.set) { set_error("%s: sequence %d was never set", me, d.sequence); return TC2LI_ERR_INVALID; }
+        const LogSizes sizes{m.n_kf, m.n_pt, m.n_obs, m.store_slot.data(), m.slot_off.data()};
+        const char* what = "";
+        const int rc = check_log(sizes, d.edits, d.n_edits, d.values, d.n_values, g->cap, &slots.n, &after[i], &what);
+        if (rc < 0) { set_error("%s: sequence %d: %s", me, d.sequence, what); return rc; }
+        // what the workgroup of this log will read to find every touched row's edits (map_graph_device.hpp, kMgMaxWalk)
+        std::vector<int32_t> first(after[i].n_pt, -1), last(after[i].n_pt, -1);
+        for (int e = 0; e < d.n_edits; ++e) {
+            const int op = d.edits[e].op;
+            if (op != TC2LI_MAP_GRAPH_ADD_OBSERVATION && op != TC2LI_MAP_GRAPH_ERASE_OBSERVATION && op != TC2LI_MAP_GRAPH_CLEAR_OBSERVATIONS) continue;
+            if (first[d.edits[e].a] < 0) first[d.edits[e].a] = e;
+            last[d.edits[e].a] = e;
+        }
+        int64_t walk = 0;
+        for (int p = 0; p < after[i].n_pt; ++p) walk += first[p] < 0 ? 0 : last[p] - first[p] + 1;
+        if (walk > kMgMaxWalk) {
+            set_error("%s: sequence %d: the observation edits of single points lie %lld log entries apart in sum, the limit is %lld; split the log or keep a point's edits together", me,
+                      d.sequence, (long long)walk, (long long)kMgMaxWalk);
+            return TC2LI_ERR_CAPACITY;
+        }
+        n_edits += (size_t)d.n_edits; n_values += (size_t)d.n_values;
+        if (n_edits > kMaxRows || n_values > kMaxRows) return too_many_rows(me, i);
+    }
+    if (!device_ready()) return TC2LI_ERR_NO_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : private_stream();
+    // ---- one upload: [records | edits | values], nothing else ----
+    const size_t o_edits = (size_t)n * sizeof(MgApplyDev), o_values = o_edits + n_edits * sizeof(tc2li_map_graph_edit), bytes = o_values + n_values * 8;
+    TC2LI_HIP_CHECK(g->h_up.ensure(bytes)); TC2LI_HIP_CHECK(g->d_up.ensure(bytes));
+    TC2LI_HIP_CHECK(g->d_totals.ensure(n)); TC2LI_HIP_CHECK(g->h_totals.ensure(n));
+    MgApplyDev* rec = reinterpret_cast<MgApplyDev*>(g->h_up.p);
+    size_t e_at = 0, v_at = 0;
+    for (int i = 0; i < n; ++i) {
+        const tc2li_map_graph_delta& d = deltas[i];
+        const SeqMeta& m = g->seq[d.sequence];
+        MgApplyDev r{};
+        r.sequence = d.sequence; r.generation = m.generation; r.n_kf = m.n_kf; r.n_points = m.n_pt; r.n_slot = m.slot_off[m.n_kf]; r.n_obs = m.n_obs;
+        r.edit_off = (int32_t)e_at; r.n_edits = d.n_edits; r.value_off = (int32_t)v_at; r.n_points_new = after[i].n_pt;
+        rec[i] = r;
+        if (d.n_edits) memcpy(g->h_up.p + o_edits + e_at * sizeof(tc2li_map_graph_edit), d.edits, (size_t)d.n_edits * sizeof(tc2li_map_graph_edit));
+        if (d.n_values) memcpy(g->h_up.p + o_values + v_at * 8, d.values, (size_t)d.n_values * 8);
+        e_at += (size_t)d.n_edits; v_at += (size_t)d.n_values;
+    }
+    TC2LI_HIP_CHECK(hipMemcpyAsync(g->d_up.p, g->h_up.p, bytes, hipMemcpyHostToDevice, st));
+    MgApplyBatch B{};
+    B.T = g->T; B.n = n; B.deltas = reinterpret_cast<const MgApplyDev*>(g->d_up.p);
+    B.edits = reinterpret_cast<const tc2li_map_graph_edit*>(g->d_up.p + o_edits); B.values = reinterpret_cast<const double*>(g->d_up.p + o_values);
+    B.totals = g->d_totals.p;
+    launch_map_graph_apply(B, st);
+    TC2LI_HIP_CHECK(hipGetLastError());
+    TC2LI_HIP_CHECK(hipMemcpyAsync(g->h_totals.p, g->d_totals.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));   // 4 bytes per sequence
+    TC2LI_HIP_CHECK(stream_wait_blocking(st));
+    for (int i = 0; i < n; ++i) {
+        const tc2li_map_graph_delta& d = deltas[i];
+        SeqMeta& m = g->seq[d.sequence];
+        const LogAfter& a = after[i];
+        m.generation ^= 1; m.n_kf = a.n_kf; m.n_pt = a.n_pt; m.n_obs = g->h_totals.p[i];
+        m.store_slot.insert(m.store_slot.end(), a.new_store_slot.begin(), a.new_store_slot.end());
+        m.n_keys.resize(m.store_slot.size(), 0);
+        for (size_t k = 0; k < m.store_slot.size(); ++k) m.n_keys[k] = std::max(m.n_keys[k], slots.n[m.store_slot[k]]);   // what this log's indices were checked against
+        for (int32_t s : a.new_slots) m.slot_off.push_back(m.slot_off.back() + s);
+        ++m.applies;
+        m.apply_bytes = (int64_t)(sizeof(MgApplyDev) + (size_t)d.n_edits * sizeof(tc2li_map_graph_edit) + (size_t)d.n_values * 8);
+    }
+    return n;
+}
+
+// ---- download --------------------------------------------------------------------------------------------------------------------------
+extern "C" int tc2li_map_graph_download(tc2li_map_graph_handle* g, int sequence, tc2li_map_graph_tables* out, const int32_t* capacities, int32_t* counts) {
+    const char* me = "tc2li_map_graph_download";
+    if (!g || !sequence_ok(g, sequence) || !out || !capacities || !counts) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(g->mu);
+    const SeqMeta& m = g->seq[sequence];
+    const MgSequenceView v = view_of(g, sequence);
+    counts[0] = v.n_kf; counts[1] = v.n_slot; counts[2] = v.n_points; counts[3] = v.n_obs;
+    for (int c = 0; c < 4; ++c)
+        if (capacities[c] < counts[c]) { set_error("%s: the arrays are too small", me); return TC2LI_ERR_CAPACITY; }
+    if (!out->slot_offsets || !out->obs_offsets || (v.n_kf && (!out->kf_slot || !out->kf_id || !out->kf_flags || !out->poses7)) || (v.n_slot && !out->slot_point) ||
+        (v.n_points && (!out->point_flags || !out->positions)) || (v.n_obs && (!out->obs_kf || !out->obs_index))) {
+        set_error("%s: null array", me);
+        return TC2LI_ERR_INVALID;
+    }
+    out->n_keyframes = v.n_kf; out->n_points = v.n_points;
+    if (!m.set) { out->slot_offsets[0] = 0; out->obs_offsets[0] = 0; return 0; }
+    if (!device_ready()) return TC2LI_ERR_NO_DEVICE;
+    const MgTables& T = g->T;
+    auto get = [](void* dst, const void* src, size_t b) { return b ? hipMemcpy(dst, src, b, hipMemcpyDeviceToHost) : hipSuccess; };
+    const size_t nk = (size_t)v.n_kf, np = (size_t)v.n_points;
+    TC2LI_HIP_CHECK(get(out->kf_slot, T.kf_slot + v.t_kf, nk * 4)); TC2LI_HIP_CHECK(get(out->kf_id, T.kf_id + v.t_kf, nk * 8));
+    TC2LI_HIP_CHECK(get(out->kf_flags, T.kf_flags + v.t_kf, nk)); TC2LI_HIP_CHECK(get(out->poses7, T.poses7 + (size_t)v.t_kf * 7, nk * 56));
+    TC2LI_HIP_CHECK(get(out->slot_offsets, T.slot_offsets + v.slot_row, (nk + 1) * 4)); TC2LI_HIP_CHECK(get(out->slot_point, T.slot_point + v.t_slot, (size_t)v.n_slot * 4));
+    TC2LI_HIP_CHECK(get(out->point_flags, T.point_flags + v.t_point, np)); TC2LI_HIP_CHECK(get(out->positions, T.positions + (size_t)v.t_point * 3, np * 24));
+    TC2LI_HIP_CHECK(get(out->obs_offsets, T.obs_offsets + v.obs_row, (np + 1) * 4)); TC2LI_HIP_CHECK(get(out->obs_kf, T.obs_kf + v.t_obs, (size_t)v.n_obs * 4));
+    TC2LI_HIP_CHECK(get(out->obs_index, T.obs_index + v.t_obs, (size_t)v.n_obs * 4));
+    return 0;
+}
+
+// ---- what a gather reads ---------------------------------------------------------------------------------------------------------------
+int tc2li::MgLease::acquire(const char* entry, tc2li_map_graph_handle* g, tc2li_keyframe_store* store, const int32_t* sequences_, int n_) {
+    if (!g || n_ < 0 || (n_ && !sequences_)) { set_error("%s: null graph or sequences", entry); return TC2LI_ERR_INVALID; }
+    if (store != g->store) { set_error("%s: the graph was created on another keyframe store", entry); return TC2LI_ERR_INVALID; }
+    g->mu.lock();
+    graph = g; sequences = sequences_; n = n_;
+    T = g->T;
+    seq.resize(n);
+    for (int p = 0; p < n; ++p) {
+        if (!sequence_ok(g, sequences[p]) || !g->seq[sequences[p]].set) { set_error("%s: problem %d names sequence %d, which is out of range or was never set", entry, p, sequences[p]); return TC2LI_ERR_INVALID; }
+        seq[p] = view_of(g, sequences[p]);
+    }
+    return 0;
+}
+tc2li::MgLease::~MgLease() {
+    if (!graph) return;
+    if (uploaded >= 0)
+        for (int p = 0; p < n; ++p) graph->seq[sequences[p]].gather_bytes = uploaded;
+    graph->mu.unlock();
+}
+
+// ---- the host twin ---------------------------------------------------------------------------------------------------------------------
+extern "C" int tc2li_host_map_graph_apply(const tc2li_map_graph_tables* in, const tc2li_map_graph_edit* edits, int n_edits, const double* values,
+                                          int n_values, tc2li_map_graph_tables* out, const int32_t* capacities, int32_t* counts) {
+    const char* me = "tc2li_host_map_graph_apply";
+    if (!in || !out || !capacities || !counts) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    const char* what = tables_fault(*in);
+    if (!what[0] && (!ascending(in->slot_offsets, in->n_keyframes) || !ascending(in->obs_offsets, in->n_points))) what = "offsets do not ascend from 0";
+    if (what[0]) { set_error("%s: %s", me, what); return TC2LI_ERR_INVALID; }
+    const int n_kf = in->n_keyframes, n_pt = in->n_points, n_slot = in->slot_offsets[n_kf], n_obs = in->obs_offsets[n_pt];
+    if ((n_slot && !in->slot_point) || (n_obs && (!in->obs_kf || !in->obs_index))) { set_error("%s: null slot_point, obs_kf or obs_index", me); return TC2LI_ERR_INVALID; }
+    if (n_kf > capacities[0] || n_slot > capacities[1] || n_pt > capacities[2] || n_obs > capacities[3]) { set_error("%s: the tables are beyond the capacities", me); return TC2LI_ERR_CAPACITY; }
+    LogAfter after;
+    const LogSizes sizes{n_kf, n_pt, n_obs, in->kf_slot, in->slot_offsets};
+    const int rc = check_log(sizes, edits, n_edits, values, n_values, capacities, nullptr, &after, &what);
+    if (rc < 0) { set_error("%s: %s", me, what); return rc; }
+    // the state, then the log one edit after the other
+    std::vector<int32_t> kf_slot(in->kf_slot, in->kf_slot + n_kf), slot_off(in->slot_offsets, in->slot_offsets + n_kf + 1), slot_point(in->slot_point, in->slot_point + n_slot);
+    std::vector<int64_t> kf_id(in->kf_id, in->kf_id + n_kf);
+    std::vector<uint8_t> kf_flags(in->kf_flags, in->kf_flags + n_kf), point_flags(in->point_flags, in->point_flags + n_pt);
+    std::vector<double> poses7(in->poses7, in->poses7 + 7 * (size_t)n_kf), positions(in->positions, in->positions + 3 * (size_t)n_pt);
+    std::vector<std::vector<std::pair<int32_t, int32_t>>> obs(n_pt);
+    for (int p = 0; p < n_pt; ++p)
+        for (int o = in->obs_offsets[p]; o < in->obs_offsets[p + 1]; ++o) obs[p].emplace_back(in->obs_kf[o], in->obs_index[o]);
+    for (int e = 0; e < n_edits; ++e) {
+        const tc2li_map_graph_edit& ed = edits[e];
+        switch (ed.op) {
+            case TC2LI_MAP_GRAPH_ADD_KEYFRAME: {                                          // new KeyFrame (Tracking.cc:3078)
+                const double* v = values + ed.c;
+                kf_slot.push_back(ed.a); kf_id.push_back((int64_t)v[0]); kf_flags.push_back((uint8_t)(int)v[1]);
+                poses7.insert(poses7.end(), v + 2, v + 9);
+                slot_point.insert(slot_point.end(), (size_t)ed.b, -1);
+                slot_off.push_back(slot_off.back() + ed.b);
+                break;
+            }
+            case TC2LI_MAP_GRAPH_SET_KEYFRAME_FLAGS: kf_flags[ed.a] = (uint8_t)ed.b; break;          // KeyFrame.cc:585
+            case TC2LI_MAP_GRAPH_SET_POSE: std::copy(values + ed.b, values + ed.b + 7, poses7.begin() + 7 * (size_t)ed.a); break;   // KeyFrame.cc:121
+            case TC2LI_MAP_GRAPH_ADD_POINT:                                                          // new MapPoint
+                point_flags.push_back((uint8_t)ed.a);
+                positions.insert(positions.end(), values + ed.b, values + ed.b + 3);
+                obs.emplace_back();
+                break;
+            case TC2LI_MAP_GRAPH_SET_POINT_FLAGS: point_flags[ed.a] = (uint8_t)ed.b; break;          // MapPoint.cc:225
+            case TC2LI_MAP_GRAPH_SET_POSITION: std::copy(values + ed.b, values + ed.b + 3, positions.begin() + 3 * (size_t)ed.a); break;
+            case TC2LI_MAP_GRAPH_SET_SLOT: slot_point[slot_off[ed.a] + ed.b] = ed.c; break;          // KeyFrame.cc:309-340
+            case TC2LI_MAP_GRAPH_ADD_OBSERVATION: {                                                  // MapPoint.cc:150-175
+                auto& row = obs[ed.a];
+                auto it = std::lower_bound(row.begin(), row.end(), ed.b, [](const std::pair<int32_t, int32_t>& x, int32_t k) { return x.first < k; });
+                if (it != row.end() && it->first == ed.b) it->second = ed.c;                         // mObservations[pKF] = indexes (:155-169)
+                else row.insert(it, std::make_pair(ed.b, ed.c));
+                break;
+            }
+            case TC2LI_MAP_GRAPH_ERASE_OBSERVATION: {                                                // MapPoint.cc:177-210
+                auto& row = obs[ed.a];
+                auto it = std::lower_bound(row.begin(), row.end(), ed.b, [](const std::pair<int32_t, int32_t>& x, int32_t k) { return x.first < k; });
+                if (it != row.end() && it->first == ed.b) row.erase(it);                             // absent: nothing (:182)
+                break;
+            }
+            default: obs[ed.a].clear(); break;                                                       // mObservations.clear()
+        }
+    }
+    size_t total = 0;
+    for (const auto& row : obs) total += row.size();
+    counts[0] = (int32_t)kf_slot.size(); counts[1] = slot_off.back(); counts[2] = (int32_t)point_flags.size(); counts[3] = (int32_t)total;
+    const size_t nk = kf_slot.size(), np = point_flags.size();
+    if (!out->slot_offsets || !out->obs_offsets || (nk && (!out->kf_slot || !out->kf_id || !out->kf_flags || !out->poses7)) || (slot_point.size() && !out->slot_point) ||
+        (np && (!out->point_flags || !out->positions)) || (total && (!out->obs_kf || !out->obs_index))) {
+        set_error("%s: null output array", me);
+        return TC2LI_ERR_INVALID;
+    }
+    auto put = [](void* dst, const void* src, size_t b) { if (b) memcpy(dst, src, b); };
+    put(out->kf_slot, kf_slot.data(), nk * 4); put(out->kf_id, kf_id.data(), nk * 8); put(out->kf_flags, kf_flags.data(), nk); put(out->poses7, poses7.data(), nk * 56);
+    put(out->slot_offsets, slot_off.data(), (nk + 1) * 4); put(out->slot_point, slot_point.data(), slot_point.size() * 4);
+    put(out->point_flags, point_flags.data(), np); put(out->positions, positions.data(), np * 24);
+    int32_t o = 0;
+    for (size_t p = 0; p < np; ++p) {
+        out->obs_offsets[p] = o;
+        for (const auto& kv : obs[p]) { out->obs_kf[o] = kv.first; out->obs_index[o++] = kv.second; }
+    }
+    out->obs_offsets[np] = o;
+    out->n_keyframes = (int32_t)nk; out->n_points = (int32_t)np;
+    return 0;
+}

@@ -28,12 +28,17 @@ void keyframe_store_baw(tc2li_keyframe_store* store, BawStore* where, int32_t* n
 int keyframe_store_slots(const tc2li_keyframe_store* store);
 
 // One problem = one gather.  The tables of all problems are concatenated; indices stay problem-local and the kernels add the problem's
-// offsets.  The CSR offset tables have one more row than their table per problem, hence their own starts.
+// offsets.  The CSR offset tables have one more row than their table per problem, hence their own starts.  The graph tables have starts
+// of their own (t_*, slot_row, obs_row) beside those of the scratch and of the gather's own tables (kf_off, point_off): a batch of host
+// arrays fills them with the same places (WindowTransfer::add), a batch that reads the resident map graph (map_graph_device.hpp) with
+// the places of the problem's sequence in the slab, which two problems may share.
 struct WindowProblemDev {
-    int32_t kf_off, n_kf;                  // kf_slot, kf_id, kf_flags, the gather's own keyframe tables, vertex_of / members; slot_offsets rows start at kf_off + problem index
-    int32_t slot_off;                      // slot_point
-    int32_t point_off, n_points;           // point_flags, positions, per-point scratch; obs_offsets rows start at point_off + problem index
-    int32_t obs_off;                       // obs_kf, obs_index
+    int32_t kf_off, n_kf;                  // the gather's own keyframe tables (cov-independent inputs it uploads per problem), vertex_of / members
+    int32_t slot_off;                      // slot_point of a batch of host arrays (= t_slot there)
+    int32_t point_off, n_points;           // per-point scratch: listed, edge_start
+    int32_t obs_off;                       // obs_kf, obs_index of a batch of host arrays (= t_obs there)
+    int32_t t_kf, t_slot, t_point, t_obs;  // kf_slot, kf_id, kf_flags, poses7 | slot_point | point_flags, positions | obs_kf, obs_index
+    int32_t slot_row, obs_row;             // the first row of the problem's slot_offsets / obs_offsets
     int32_t current;
     int32_t mark_off;                      // start of the problem's marks in the global scratch, -1: they fit in LDS
     int32_t first_off;                     // start of the problem's first-occurrence keys in the global scratch, -1: they fit in LDS

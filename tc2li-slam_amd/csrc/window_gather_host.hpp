@@ -210,6 +210,9 @@ struct WindowTransfer : PackedTransfer {
     size_t o_counts, o_lidar, o_p3, o_ptrow, o_edges, o_after_edges;
     size_t w_marks, w_first, w_vertex, w_members, w_listed, w_estart, w_emit;
     int n_counts = 0;
+    // the graph tables are resident on the device (map_graph_device.hpp): none is laid out or uploaded, the inputs that do go up lie back
+    // to back so that the upload is exactly as long as they are, and the entry binds the tables and fills t_* / slot_row / obs_row itself
+    bool resident = false;
 
     WindowTransfer(const Problem* problems_, int n) : problems(problems_), n_problems(n), np((size_t)n), dev(n) {}
 
@@ -217,10 +220,16 @@ struct WindowTransfer : PackedTransfer {
     // table, so the device arrays need no more room than that, whatever the caller offers.
     Dev& add(int p, int edge_room) {
         const Problem& in = problems[p];
+        return add(p, edge_room, in.slot_offsets[in.n_keyframes], in.obs_offsets[in.n_points]);
+    }
+    // the same with the entries of the two CSR tables given: the problems of a resident batch carry no table
+    Dev& add(int p, int edge_room, int slot_entries, int obs_entries) {
+        const Problem& in = problems[p];
         Dev& d = dev[p];
-        const int slot_entries = in.slot_offsets[in.n_keyframes], obs_entries = in.obs_offsets[in.n_points];
         d.kf_off = (int32_t)n_kf; d.n_kf = in.n_keyframes; d.slot_off = (int32_t)n_slot;
         d.point_off = (int32_t)n_points; d.n_points = in.n_points; d.obs_off = (int32_t)n_obs;
+        d.t_kf = d.kf_off; d.t_slot = d.slot_off; d.t_point = d.point_off; d.t_obs = d.obs_off;
+        d.slot_row = d.kf_off + p; d.obs_row = d.point_off + p;
         d.current = in.current;
         d.mark_off = in.n_keyframes > kWinLdsKeyframes ? (int32_t)n_marks : -1;
         d.first_off = in.n_points > kWinLdsPoints ? (int32_t)n_first : -1;
@@ -236,6 +245,13 @@ struct WindowTransfer : PackedTransfer {
     size_t most_rows(int p) const { return std::max(std::max(n_kf + p, n_slot), std::max(n_points + p, n_obs)); }
 
     void take_inputs(int n_levels) {
+        if (resident) {
+            static_assert(sizeof(Dev) % 4 == 0, "the level table and cov_kf follow the records without padding");
+            o_prob = io.off; io.off += np * sizeof(Dev);
+            o_sigma = io.off; io.off += (size_t)n_levels * 4;
+            o_id = o_pos = o_slot = o_srow = o_spt = o_orow = o_okf = o_oidx = o_flags = o_pflags = io.off;
+            return;
+        }
         o_prob = io.take(np * sizeof(Dev)); o_sigma = io.take((size_t)n_levels * 4); o_id = io.take(n_kf * 8); o_pos = io.take(n_points * 24);
         o_slot = io.take(n_kf * 4); o_srow = io.take((n_kf + np) * 4); o_spt = io.take(n_slot * 4); o_orow = io.take((n_points + np) * 4);
         o_okf = io.take(n_obs * 4); o_oidx = io.take(n_obs * 4); o_flags = io.take(n_kf); o_pflags = io.take(n_points);
@@ -243,6 +259,7 @@ struct WindowTransfer : PackedTransfer {
     // after the entry's own inputs.  counts_per_problem: TC2LI_*_WINDOW_COUNTS
     void take_outputs(int counts_per_problem) {
         outputs_begin();
+        io.off = align256(io.off);   // a resident batch's inputs end where they end
         n_counts = counts_per_problem;
         o_counts = io.take(np * n_counts * 4); o_lidar = io.take(np * kWinMaxLidar * 4); o_p3 = io.take(n_pointo * 24); o_ptrow = io.take(n_pointo * 4);
         o_edges = io.take(n_edge * sizeof(tc2li_ba_edge));
@@ -260,6 +277,7 @@ struct WindowTransfer : PackedTransfer {
         tracking_pool().parallel_for(n_problems, [&](int p) {
             const Problem& in = problems[p];
             const Dev& d = dev[p];
+            if (resident) { own(p, in, d); return; }
             const size_t nk = (size_t)in.n_keyframes, npt = (size_t)in.n_points, n_o = (size_t)in.obs_offsets[in.n_points];
             io.put(o_id, d.kf_off, in.kf_id, nk, 8); io.put(o_slot, d.kf_off, in.kf_slot, nk, 4); io.put(o_flags, d.kf_off, in.kf_flags, nk, 1);
             io.put(o_srow, (size_t)d.kf_off + p, in.slot_offsets, nk + 1, 4);
