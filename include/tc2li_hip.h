@@ -2339,6 +2339,62 @@ int tc2li_ba_window_solve_graph_batch(tc2li_keyframe_store* store, tc2li_map_gra
                                       const tc2li_ba_window_solve_problem* problems, int n_problems, const float* inv_level_sigma2, int n_levels,
                                       const tc2li_camera* cam, int group, int32_t* results);
 
+/* ---- local mapping: the closing step of LocalLVBundleAdjustment, "Recover optimized data" (SF/src/OptimizerWithLidar.cc:455-485), on the
+ * resident graph -----------------------------------------------------------------------------------------------------------------------
+ * The reference ends its local BA by writing into the map: EraseMapPointMatch / EraseObservation for every pair of vToErase (:458-465),
+ * SetPose for every local keyframe (:468-475), SetWorldPos for every local point (:478-484).  tc2li_host_ba_window_commit_log states that
+ * step as an edit log of the map graph and so defines it; tc2li_ba_window_solve_graph_commit_batch is tc2li_ba_window_solve_graph_batch
+ * followed by that log on the resident tables, the optimised values never leaving the device for it.
+ *
+ * The log of one solved window, applied by tc2li_host_map_graph_apply to the sequence's tables as they were before the solve:
+ *   1. for every erase pair i in the order of erase_pose / erase_point: SET_SLOT(kf row, index, -1), then ERASE_OBSERVATION(point row,
+ *      kf row), with kf row = pose_row[erase_pose[i]], point row = point_row[erase_point[i]] and index the obs_index stored for that
+ *      keyframe row in the point's observation row (KeyFrame::EraseMapPointMatch(MapPoint*) goes through GetIndexInKeyFrame, :461-462).
+ *      Where the keyframe row holds no slot of that index -- a row whose matches are not resident: the gather reads the slots of the
+ *      current keyframe and of cov_kf only, and a graph may leave the others empty -- there is nothing to clear and the SET_SLOT is left out;
+ *   2. SET_POSE(pose_row[i], poses7_out[i]) for every pose with fixed[i] == 0, in pose order (:468-475);
+ *   3. SET_POSITION(point_row[j], points3_out[j]) for every listed point, in order (:478-484).
+ * The values are those of the arrays bit for bit, except under TC2LI_BA_COMMIT_POSITIONS_F32, where every position component is
+ * (double)(float)x, the cast<float>() of :482.  Poses are never rounded: Sophus::SE3f's constructor renormalises, which stays with the
+ * caller, who may send a SET_POSE of its own.
+ * A window is committed when its status is TC2LI_BA_WINDOW_OK and its result is >= 0 -- also with result 0 because iterations == 0 or
+ * the stop flag was raised: the reference recovers the data then too.  An ABORTED window and a window with a negative result give no
+ * edit.
+ * NOT part of the step (the graph stores literal edits, as its contract says): what the reference chains onto an erase -- nObs <= 2
+ * turning the point bad (MapPoint.cc:203-209), a changed mpRefKF, UpdateNormalAndDepth, IncreaseChangeIndex.  The caller spells these out
+ * in its next log from the erase lists, which are returned as before.  The inertial windows and the other readers of the graph have no
+ * such entry yet. */
+#define TC2LI_BA_COMMIT_POSITIONS_F32 1u
+/* Host only, needs no device.  tables: the sequence's tables before the solve; problem: a problem of tc2li_ba_window_solve_batch after
+ * the call, of which window.counts, pose_row, fixed, poses7_out, point_row, points3_out, erase_pose, erase_point, n_erase and
+ * erase_capacity are read; result: the call's results[] entry of the problem.  edits [edit_capacity], values [value_capacity].
+ * n_edits and n_values receive the sizes of the log (n_edits may be NULL); returns the number of edits.  TC2LI_ERR_CAPACITY, the sizes
+ * written and nothing else, when an array is too small or *n_erase exceeds erase_capacity (the lists are then cut).  TC2LI_ERR_INVALID,
+ * nothing written: unknown flag bits, NULL n_erase, a pose_row / point_row outside the tables, an erase index outside the counts, an
+ * erase pair whose keyframe row is not in the point's observation row. */
+int tc2li_host_ba_window_commit_log(const tc2li_map_graph_tables* tables, const tc2li_ba_window_solve_problem* problem, int32_t result,
+                                    uint32_t flags, tc2li_map_graph_edit* edits, int edit_capacity, double* values, int value_capacity,
+                                    int32_t* n_edits, int32_t* n_values);
+/* tc2li_ba_window_solve_graph_batch -- every output, count, result and error as there, bit for bit; poses, points and erase lists are
+ * downloaded as there -- and then, for every committed window p, the log above on sequence sequences[p].
+ *   n_erase must be non-NULL in every problem (the commit is defined by the outlier rule) and no sequence may be named twice (the local
+ *   mapping of a map is one thread): TC2LI_ERR_INVALID.  So are unknown bits of flags.
+ *   On any error of the whole call no sequence is changed, the late TC2LI_ERR_CAPACITY of an erase_capacity that turns out too small
+ *   included.  The graph's lock is held for the whole call.
+ *   Windows the lock-step group solved on the device: a scatter kernel writes poses and positions from the device copy of the final
+ *   estimate, a second kernel turns the device copy of the erase pairs into an edit log in device memory (one wavefront per window, the
+ *   index by bisection of the point's observation row) and the kernels of tc2li_map_graph_apply_batch apply it.  Host to device: one
+ *   64-byte record per sequence, no value, no table, no edit.  A window without erase pairs gets no rebuild of the observation CSR.
+ *   Should the erase pairs of one window name single points so far apart that tc2li_map_graph_apply_batch would refuse the log
+ *   (tc2li_map_graph_limits' out[5]), the call returns TC2LI_ERR_CAPACITY with no sequence changed; the outputs are written.
+ *   Windows finished on the host path (see tc2li_ba_window_solve_batch): their sequence's tables are downloaded, the log is built by
+ *   tc2li_host_ba_window_commit_log and goes through the apply.
+ *   tc2li_map_graph_info: APPLIES goes up by one per committed sequence; APPLY_BYTES is what the commit moved host to device for the
+ *   sequence (64, or the record and the log of a host-path window); GATHER_BYTES as tc2li_ba_window_solve_graph_batch counts it. */
+int tc2li_ba_window_solve_graph_commit_batch(tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences,
+                                             const tc2li_ba_window_solve_problem* problems, int n_problems, const float* inv_level_sigma2,
+                                             int n_levels, const tc2li_camera* cam, int group, uint32_t flags, int32_t* results);
+
 /* ---- local mapping: the window of the inertial local BA (OptimizerWithLidar::LocalLVIBA, SF/src/OptimizerWithLidar.cc:489-607 the gather,
  * :632-727 the vertices and the keyframes of the LiDAR edge, :729-800 the inertial links, :832-969 the point vertices and edges, :985-1045
  * the outlier rule; the twin Optimizer::LocalInertialBA, SF/src/Optimizer.cc:1512-1631 and on) -------------------------------------------

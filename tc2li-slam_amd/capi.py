@@ -4020,6 +4020,76 @@ def ba_window_solve_graph_batch(problems, sequences, inv_level_sigma2, store, gr
     return res
 
 
+BA_COMMIT_POSITIONS_F32 = 1
+
+
+def ba_window_solve_graph_commit_batch(problems, sequences, inv_level_sigma2, store, graph, cam5, group=0, fill=0, flags=0):
+    """tc2li_ba_window_solve_graph_commit_batch: ba_window_solve_graph_batch, and every solved window written into its sequence of `graph`
+    -- the erase pairs, the free poses and the points, the closing step of LocalLVBundleAdjustment -- without the values leaving the device.
+    flags: 0 or BA_COMMIT_POSITIONS_F32.  No sequence twice.  -> as ba_window_solve_batch."""
+    arr, outs, keep = pack_ba_window_solve_problems(problems, fill)
+    for i in range(len(problems)):
+        _without_tables(arr[i].window)
+    seq = np.ascontiguousarray(sequences, np.int32).reshape(-1)
+    if len(seq) != len(problems):
+        raise ValueError("one sequence per problem")
+    sg = np.ascontiguousarray(inv_level_sigma2, np.float32).reshape(-1)
+    cam = np.ascontiguousarray(cam5, np.float64)
+    n = len(problems)
+    results = np.zeros(max(n, 1), np.int32)
+    f = lib().tc2li_ba_window_solve_graph_commit_batch
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
+    _check(f(store._handle(), graph._handle(), seq.ctypes.data, C.addressof(arr), n, sg.ctypes.data, len(sg), cam.ctypes.data, int(group), int(flags),
+             results.ctypes.data))
+    res = []
+    for i, o in enumerate(outs):
+        r, c = _cut_ba_window_outputs(o)
+        ne, m = c["n_edges"], int(o["n_erase"][0])
+        r.update(result=int(results[i]), chi2=None if o["edge_chi2"] is None else o["edge_chi2"][:ne],
+                 depth_positive=None if o["edge_depth_positive"] is None else o["edge_depth_positive"][:ne], stats=o["stats"],
+                 lidar_stats=o["lidar_stats"], n_erase=m, erase=np.stack([o["erase_pose"][:m], o["erase_point"][:m]], 1), keep=keep)
+        res.append(r)
+    return res
+
+
+def host_ba_window_commit_log(tables, solved, flags=0, edit_capacity=None, value_capacity=None, into=None, sizes=None):
+    """tc2li_host_ba_window_commit_log: the closing step of LocalLVBundleAdjustment as an edit log of the map graph.  tables: the sequence's
+    tables before the solve; solved: a result of ba_window_solve_batch (result, status, pose_row, fixed, poses7, point_row, points3, erase)
+    -- n_erase and erase_capacity, if given, stand for the pairs the rule found and the room the erase lists had.  into: (edits, values)
+    arrays to write instead of fresh ones; sizes: an int32 [2] that receives the edits and values of the log, also when the call is
+    refused for want of room.  -> (edits as MAP_GRAPH_EDIT_DTYPE, values)."""
+    t = MapGraphTables()
+    keep = _pack_map_graph_tables(tables, t)
+    pose_row = np.ascontiguousarray(solved["pose_row"], np.int32).reshape(-1)
+    fixed = np.ascontiguousarray(solved["fixed"], np.uint8).reshape(-1)
+    poses7 = np.ascontiguousarray(solved["poses7"], np.float64).reshape(-1)
+    point_row = np.ascontiguousarray(solved["point_row"], np.int32).reshape(-1)
+    points3 = np.ascontiguousarray(solved["points3"], np.float64).reshape(-1)
+    erase = np.asarray(solved["erase"], np.int32).reshape(-1, 2)
+    erase_pose, erase_point = np.ascontiguousarray(erase[:, 0]), np.ascontiguousarray(erase[:, 1])
+    n_erase = np.array([solved.get("n_erase", len(erase))], np.int32)
+    counts = np.zeros(len(_BA_WINDOW_COUNTS), np.int32)
+    counts[0], counts[3], counts[4] = int(solved["status"]), len(pose_row), len(point_row)
+    q = BaWindowSolveProblem()
+    w = q.window
+    w.counts, w.pose_row, w.fixed, w.poses7_out, w.point_row, w.points3_out = (counts.ctypes.data, pose_row.ctypes.data, fixed.ctypes.data, poses7.ctypes.data,
+                                                                              point_row.ctypes.data, points3.ctypes.data)
+    q.erase_pose, q.erase_point, q.n_erase = erase_pose.ctypes.data, erase_point.ctypes.data, n_erase.ctypes.data
+    q.erase_capacity = int(solved.get("erase_capacity", len(erase)))
+    ne = 2 * len(erase) + len(pose_row) + len(point_row) if edit_capacity is None else int(edit_capacity)
+    nv = 7 * len(pose_row) + 3 * len(point_row) if value_capacity is None else int(value_capacity)
+    edits, values = (np.zeros(max(ne, 1), MAP_GRAPH_EDIT_DTYPE), np.zeros(max(nv, 1), np.float64)) if into is None else into
+    if len(edits) < ne or len(values) < nv or edits.dtype != MAP_GRAPH_EDIT_DTYPE or values.dtype != np.float64:
+        raise ValueError("into: arrays of MAP_GRAPH_EDIT_DTYPE and float64 with the stated room")
+    sizes = np.zeros(2, np.int32) if sizes is None else sizes
+    f = lib().tc2li_host_ba_window_commit_log
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    n = _check(f(C.addressof(t), C.addressof(q), int(solved["result"]), int(flags), edits.ctypes.data, ne, values.ctypes.data, nv, sizes.ctypes.data,
+                 sizes.ctypes.data + 4))
+    del keep
+    return edits[:n], values[:int(sizes[1])]
+
+
 class InertialWindowProblem(C.Structure):
     """tc2li_inertial_window_problem"""
     _fields_ = [(k, C.c_void_p) for k in ("kf_slot", "kf_id", "kf_flags", "prev_kf", "states", "slot_offsets", "slot_point", "point_flags", "positions",

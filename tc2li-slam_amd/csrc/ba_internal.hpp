@@ -146,6 +146,12 @@ struct BaPrepared {
                *grp_l0 = nullptr, *blk_off = nullptr, *blk_rows = nullptr;
     int32_t *erase_pose = nullptr, *erase_point = nullptr, *n_erase = nullptr;
     int32_t erase_capacity = 0;
+    // tc2li_ba_window_solve_graph_commit_batch, which goes on from the device copy of the result after the batch has returned and the
+    // windows' workspaces belong to the next caller of the group: with write_back the final estimate is also copied over `poses` and
+    // `points` (device to device; they are the caller's to write), and with erase_dev the outlier rule is evaluated a second time into
+    // device memory, laid out as the pinned block: [n_erase | 3 words | erase_pose | erase_point], each list erase_capacity long.
+    bool write_back = false;
+    int32_t* erase_dev = nullptr;
 };
 
 // Structure and device state of the projection-edge part of a local BA (shared by the visual / LiDAR and the inertial

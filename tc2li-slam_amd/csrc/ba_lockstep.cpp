@@ -339,16 +339,28 @@ bool lv_host_iteration(LvRun& R) {
 void lv_results(LvRun& R, int32_t* results) {
     auto outliers = [&](const std::vector<int>& all) {   // the outlier rule of the prepared windows, from the chi2 and the depth flags where the kernels left them
         if (!R.prepared) return;
-        int m = 0;
-        if (R.C.h_outliers.ensure(all.size()) != hipSuccess) { R.failed = true; return; }
+        int m = 0, n_back = 0;
+        size_t max_bytes = 0;
+        if (R.C.h_outliers.ensure(2 * all.size()) != hipSuccess || R.C.h_write_back.ensure(2 * all.size()) != hipSuccess) { R.failed = true; return; }
         for (int i : all) {
             const BaPrepared& pr = R.prepared[i];
-            if (!(pr.sizes.n_poses > 0) || !pr.n_erase) continue;
+            if (!(pr.sizes.n_poses > 0)) continue;
             const LockstepWindow& w = R.W[i];
+            if (pr.write_back) {   // the accepted estimate back over the gather's copy of the window, for a caller that goes on from it on the device
+                const size_t pose_bytes = (size_t)w.vp.pb.n_poses * sizeof(Se3), point_bytes = 3 * (size_t)w.vp.pb.n_points * sizeof(double);
+                R.C.h_write_back.p[n_back++] = CopyTask{const_cast<void*>(pr.poses), w.vp.pb.poses, pose_bytes};
+                R.C.h_write_back.p[n_back++] = CopyTask{const_cast<void*>(pr.points), w.vp.pb.points, point_bytes};
+                max_bytes = std::max(max_bytes, std::max(pose_bytes, point_bytes));
+            }
+            if (!pr.n_erase) continue;
             R.C.h_outliers.p[m++] = BasOutlierTask{(const tc2li_ba_edge*)w.vp.pb.edges, w.ws->d_chi2.p, w.ws->d_depth.p, pr.erase_pose, pr.erase_point,
                                                    pr.n_erase, w.vp.pb.n_edges, pr.erase_capacity};
+            if (pr.erase_dev)
+                R.C.h_outliers.p[m++] = BasOutlierTask{(const tc2li_ba_edge*)w.vp.pb.edges, w.ws->d_chi2.p, w.ws->d_depth.p, pr.erase_dev + 4, pr.erase_dev + 4 + pr.erase_capacity,
+                                                       pr.erase_dev, w.vp.pb.n_edges, pr.erase_capacity};
         }
         launch_ba_outliers(R.C.h_outliers.p, m, R.st);
+        launch_copy_tasks(R.C.h_write_back.p, n_back, max_bytes, R.st);
     };
     lockstep_results(R, R.W, true, outliers, [](LockstepWindow& w) { write_poses7(w.vp.poses, w.p->poses7); });
     lockstep_write_stats(R, R.W, "tc2li_local_bundle_adjustment_batch", results, [](LockstepWindow&) {});

@@ -2,6 +2,7 @@
 // (ba_structure.hpp) in the header's flat form.  tc2li_ba_window_structure_batch and tc2li_ba_window_solve_batch: the gather of
 // ba_window_host.cpp followed by the structure kernels (ba_structure_kernels.hip) and, for the second, by the lock-step batch that adopts the
 // windows where they are (ba_lockstep.cpp, VisualProblem::adopt).
+#include <algorithm>
 #include <cstring>
 #include <mutex>
 
@@ -105,6 +106,7 @@ struct BasSpace {
     PinnedBuf<CopyTask> h_tasks;
     PinnedBuf<uint8_t> h_blocks;
     PinnedBuf<int32_t> h_erase;      // per window [n_erase | pad | erase_pose cap | erase_point cap]
+    DevBuf<int32_t> d_erase;         // the same blocks in device memory: what a commit reads (tc2li_ba_window_solve_graph_commit_batch)
 };
 // [0]: tc2li_ba_window_structure_batch's; [1 + group]: tc2li_ba_window_solve_batch's on the lock-step context `group`
 struct BasSpaces { BasSpace s[1 + kMaxLockstepGroups]; };
@@ -273,6 +275,10 @@ struct SolveFollow : StructureBase {
     const tc2li_camera* cam = nullptr;
     int group = 0;
     int32_t* results = nullptr;
+    // tc2li_ba_window_solve_graph_commit_batch: the lease of the gather, under whose lock the solved windows are written into their sequences
+    MgLease* commit = nullptr;
+    uint32_t commit_flags = 0;
+    const char* entry = "tc2li_ba_window_solve_batch";
     using StructureBase::StructureBase;
 
     int after_counts() override {
@@ -334,6 +340,7 @@ struct SolveFollow : StructureBase {
         for (int p : built) { erase_at[p] = erase_ints; erase_ints += 4 + 2 * (size_t)std::max(std::min(solve[p].erase_capacity, prob[p].n_edges), 0); }
         if (lockstep && !built.empty()) {
             TC2LI_HIP_CHECK(S.h_erase.ensure(std::max<size_t>(erase_ints, 4)));
+            if (commit) TC2LI_HIP_CHECK(S.d_erase.ensure(std::max<size_t>(erase_ints, 4)));
             std::vector<tc2li_ba_problem> bp(built.size());
             std::vector<BaPrepared> prep(built.size());
             std::vector<int32_t> rc(built.size(), 0);
@@ -347,6 +354,7 @@ struct SolveFollow : StructureBase {
                     int32_t* e = S.h_erase.p + erase_at[p];
                     e[0] = 0;
                     prep[k].n_erase = e; prep[k].erase_pose = e + 4; prep[k].erase_point = e + 4 + cap; prep[k].erase_capacity = cap;
+                    if (commit) { prep[k].write_back = true; prep[k].erase_dev = S.d_erase.p + erase_at[p]; }
                 }
             }
             if (ba_batch_lockstep(bp.data(), (int)bp.size(), cam, named_pool(kPoolBaGroup0 + group), rc.data(), group, prep.data())) {
@@ -396,7 +404,41 @@ struct SolveFollow : StructureBase {
                 set_error("tc2li_ba_window_solve_batch: problem %d has %d outlier pairs and room for %d", p, *solve[p].n_erase, solve[p].erase_capacity);
                 return TC2LI_ERR_CAPACITY;
             }
-        return 0;
+        if (!commit) return 0;
+        // ---- "Recover optimized data" (OptimizerWithLidar.cc:455-485) into the resident tables: no error can follow that would have to undo it ----
+        std::vector<MgCommitWindow> on_device;
+        std::vector<int> on_host;
+        for (int p : alive) {
+            if (results[p] < 0) continue;
+            if (!done[p]) { on_host.push_back(p); continue; }
+            const int32_t* c = solve[p].window.counts;
+            MgCommitWindow w{};
+            w.sequence = commit->sequences[p];
+            w.pose_off = dev[p].pose_off; w.point_off = dev[p].pointo_off; w.n_poses = c[TC2LI_BA_WINDOW_N_POSES]; w.n_points = c[TC2LI_BA_WINDOW_N_POINTS];
+            w.n_erase = *solve[p].n_erase; w.erase_at = (int32_t)erase_at[p] + 4; w.erase_cap = std::max(std::min(solve[p].erase_capacity, prob[p].n_edges), 0);
+            w.erase_point = solve[p].erase_point;
+            on_device.push_back(w);
+        }
+        // a window finished on the host path: its log from the sequence's tables and its host arrays (tc2li_host_ba_window_commit_log)
+        std::vector<MgHostTables> tables(on_host.size());
+        std::vector<std::vector<tc2li_map_graph_edit>> log_edits(on_host.size());
+        std::vector<std::vector<double>> log_values(on_host.size());
+        std::vector<tc2li_map_graph_delta> logs(on_host.size());
+        for (size_t k = 0; k < on_host.size(); ++k) {
+            const int p = on_host[k];
+            const int32_t* c = solve[p].window.counts;
+            const int rrc = map_graph_read(entry, *commit, commit->sequences[p], &tables[k]);
+            if (rrc < 0) return rrc;
+            log_edits[k].resize(2 * (size_t)std::max(*solve[p].n_erase, 0) + c[TC2LI_BA_WINDOW_N_POSES] + c[TC2LI_BA_WINDOW_N_POINTS] + 1);
+            log_values[k].resize(7 * (size_t)c[TC2LI_BA_WINDOW_N_POSES] + 3 * (size_t)c[TC2LI_BA_WINDOW_N_POINTS] + 1);
+            int32_t n_values = 0;
+            const int n_edits = tc2li_host_ba_window_commit_log(&tables[k].tables, &solve[p], results[p], commit_flags, log_edits[k].data(), (int)log_edits[k].size(),
+                                                                log_values[k].data(), (int)log_values[k].size(), nullptr, &n_values);
+            if (n_edits < 0) return n_edits;
+            logs[k] = tc2li_map_graph_delta{log_edits[k].data(), log_values[k].data(), commit->sequences[p], n_edits, n_values, 0};
+        }
+        const MgCommitSource src{B.pose_row, B.fixed, B.poses7_out, B.point_row, B.points3_out, S.d_erase.p};
+        return map_graph_commit(entry, *commit, src, on_device, logs.data(), (int)logs.size(), commit_flags, st);
     }
 };
 
@@ -431,9 +473,10 @@ extern "C" int tc2li_ba_window_structure_batch(tc2li_keyframe_store* store, cons
 
 namespace {
 // tc2li_ba_window_solve_batch, or with a graph tc2li_ba_window_solve_graph_batch: the windows' tables from the sequences of the map graph
+// commit: the solved windows are then written into their sequences (tc2li_ba_window_solve_graph_commit_batch)
 int solve_batch(const char* entry, tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences,
                 const tc2li_ba_window_solve_problem* problems, int n_problems, const float* inv_level_sigma2, int n_levels, const tc2li_camera* cam,
-                int group, int32_t* results) {
+                int group, int32_t* results, bool commit = false, uint32_t flags = 0) {
     if (n_problems < 0 || (n_problems > 0 && (!problems || !results)) || !cam || group < 0 || group >= kMaxLockstepGroups) {
         set_error("%s: invalid argument (group 0 .. %d)", entry, kMaxLockstepGroups - 1);
         return TC2LI_ERR_INVALID;
@@ -446,7 +489,15 @@ int solve_batch(const char* entry, tc2li_keyframe_store* store, tc2li_map_graph_
             set_error("%s: problem %d: negative iterations or capacity, clouds without offsets, or null erase arrays", entry, p);
             return TC2LI_ERR_INVALID;
         }
+        if (commit && !q.n_erase) { set_error("%s: problem %d: n_erase is NULL: the commit is defined by the outlier rule", entry, p); return TC2LI_ERR_INVALID; }
         windows[p] = q.window;
+    }
+    if (commit) {
+        if (flags & ~(uint32_t)TC2LI_BA_COMMIT_POSITIONS_F32) { set_error("%s: unknown flag bits", entry); return TC2LI_ERR_INVALID; }
+        if (n_problems > 0 && !sequences) { set_error("%s: null sequences", entry); return TC2LI_ERR_INVALID; }
+        std::vector<int32_t> named(sequences, sequences + n_problems);   // the local mapping of a map is one thread
+        std::sort(named.begin(), named.end());
+        if (std::adjacent_find(named.begin(), named.end()) != named.end()) { set_error("%s: a sequence is named by two problems", entry); return TC2LI_ERR_INVALID; }
     }
     MgLease lease;
     if (graph) {
@@ -457,6 +508,7 @@ int solve_batch(const char* entry, tc2li_keyframe_store* store, tc2li_map_graph_
     std::lock_guard<std::mutex> lk(S.mu);
     SolveFollow F(S);
     F.problems = windows.data(); F.n = n_problems; F.solve = problems; F.cam = cam; F.group = group; F.results = results;
+    F.entry = entry; F.commit = commit ? &lease : nullptr; F.commit_flags = flags;
     F.use_lidar.assign(std::max(n_problems, 0), 0);
     for (int p = 0; p < n_problems; ++p) F.use_lidar[p] = problems[p].cloud_xyz ? 1 : 0;
     return ba_window_batch_run(entry, store, windows.data(), n_problems, inv_level_sigma2, n_levels, nullptr, &F, 1 + group, true, graph ? &lease : nullptr);
@@ -473,4 +525,12 @@ extern "C" int tc2li_ba_window_solve_graph_batch(tc2li_keyframe_store* store, tc
                                                  const tc2li_camera* cam, int group, int32_t* results) {
     if (!graph) { set_error("tc2li_ba_window_solve_graph_batch: null graph"); return TC2LI_ERR_INVALID; }
     return solve_batch("tc2li_ba_window_solve_graph_batch", store, graph, sequences, problems, n_problems, inv_level_sigma2, n_levels, cam, group, results);
+}
+
+extern "C" int tc2li_ba_window_solve_graph_commit_batch(tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences,
+                                                        const tc2li_ba_window_solve_problem* problems, int n_problems, const float* inv_level_sigma2,
+                                                        int n_levels, const tc2li_camera* cam, int group, uint32_t flags, int32_t* results) {
+    const char* entry = "tc2li_ba_window_solve_graph_commit_batch";
+    if (!graph) { set_error("%s: null graph", entry); return TC2LI_ERR_INVALID; }
+    return solve_batch(entry, store, graph, sequences, problems, n_problems, inv_level_sigma2, n_levels, cam, group, results, true, flags);
 }

@@ -134,7 +134,8 @@ struct LockstepContext {
     DevBuf<uint8_t> d_table;
     PinnedBuf<uint8_t> h_table;
     PinnedBuf<CopyTask> h_tasks;  // the uploads / operand fills of a batch's setup, then its result copies: one launch each (copy_kernels.hip)
-    PinnedBuf<BasOutlierTask> h_outliers;  // prepared windows: the outlier rule after the BA, a task per window (ba_structure_kernels.hip)
+    PinnedBuf<BasOutlierTask> h_outliers;  // prepared windows: the outlier rule after the BA, a task per window (ba_structure_kernels.hip), two where a device copy is asked for
+    PinnedBuf<CopyTask> h_write_back;      // prepared windows with BaPrepared::write_back: the final estimate back over the caller's device arrays (h_tasks is still being read)
     // plane extraction of the batch's LiDAR windows on the device (balm_cut_kernels.hip): a task per window, those with points to cut
     // compacted into the list the kernels read, and the uploads the LiDAR tasks deferred (the clouds)
     PinnedBuf<BalmCutTask> h_cut, h_cut_list;

@@ -63,6 +63,35 @@ struct MgApplyBatch {
 };
 void launch_map_graph_apply(const MgApplyBatch& B, hipStream_t st);
 
+// ---- the commit of solved local-BA windows (map_graph_commit_kernels.hip; include/tc2li_hip.h "the closing step of
+// LocalLVBundleAdjustment") ----
+// A committed window is one MgApplyDev record and nothing else from the host: the first six members as an apply has them (n_edits = two per
+// erase pair, value_off 0, n_points_new = n_points), and in pad_ where the window lies in the gather's device output and in the device
+// copy of the erase lists.
+enum MgCommitPad { kMgcPoseOff = 0, kMgcPointOff = 1, kMgcPoses = 2, kMgcPoints = 3, kMgcEraseAt = 4, kMgcEraseCap = 5 };
+constexpr int kMgcThreads = 256;           // per block of the scatter kernel
+constexpr int kMgcNoEdit = -1;             // no op: k_mg_apply passes over it.  In place of a SET_SLOT whose keyframe row holds no such slot, and of both
+                                           // edits of an erase pair the erase-log kernel could not resolve: the host then sees the window's status word
+                                           // and drops the whole commit before any table is written
+struct MgCommitBatch {
+    MgTables T;
+    int n, n_erasing;                      // records; the first n_erasing of them have erase pairs
+    int max_rows;                          // the largest n_poses + n_points among the records (the scatter's grid)
+    uint32_t flags;                        // TC2LI_BA_COMMIT_*
+    const MgApplyDev* records;
+    // the gather's device output with the final estimate written back over it, and the outlier kernel's device output
+    const int32_t* pose_row;
+    const uint8_t* fixed;
+    const double* poses7;
+    const int32_t* point_row;
+    const double* points3;
+    const int32_t* erase;                  // a window's pairs: the pose indices at erase_at, the point indices at erase_at + erase_cap
+    tc2li_map_graph_edit* edits;           // out: the erase log of record r at records[r].edit_off
+    int32_t* status;                       // out [n_erasing]: 0, or 1 when a pair was not resolved
+};
+void launch_map_graph_commit_erase_log(const MgCommitBatch& B, hipStream_t st);
+void launch_map_graph_commit_scatter(const MgCommitBatch& B, hipStream_t st);
+
 // A sequence as a gather reads it: the sizes, and where its tables start in the slab's tables (WindowProblemDev::t_*, slot_row, obs_row).
 struct MgSequenceView {
     int32_t n_kf, n_points, n_slot, n_obs;

@@ -46,6 +46,12 @@ struct tc2li_map_graph_handle {
     DevBuf<uint8_t> d_up;
     DevBuf<int32_t> d_totals;
     PinnedBuf<int32_t> h_totals;
+    // a commit: [records | the erase logs the device writes] and [totals | status words]; its own, because the logs of host-path windows
+    // go through the apply's buffers in the same call
+    PinnedBuf<uint8_t> h_commit;
+    DevBuf<uint8_t> d_commit;
+    DevBuf<int32_t> d_commit_words;
+    PinnedBuf<int32_t> h_commit_words;
 };
 
 namespace {
@@ -288,11 +294,9 @@ extern "C" int tc2li_map_graph_set_batch(tc2li_map_graph_handle* g, const int32_
 }
 
 // ---- apply -----------------------------------------------------------------------------------------------------------------------------
-extern "C" int tc2li_map_graph_apply_batch(tc2li_map_graph_handle* g, const tc2li_map_graph_delta* deltas, int n, void* stream) {
-    const char* me = "tc2li_map_graph_apply_batch";
-    if (!g || n < 0 || (n && !deltas)) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
-    if (n == 0) return 0;
-    std::lock_guard<std::mutex> lk(g->mu);
+namespace {
+// the caller holds g->mu
+int apply_locked(const char* me, tc2li_map_graph_handle* g, const tc2li_map_graph_delta* deltas, int n, void* stream) {
     SlotTable slots;
     BawStore where{};
     slot_table_from_store(g->store, &slots, &where);
@@ -370,12 +374,20 @@ extern "C" int tc2li_map_graph_apply_batch(tc2li_map_graph_handle* g, const tc2l
     }
     return n;
 }
+}  // namespace
+
+extern "C" int tc2li_map_graph_apply_batch(tc2li_map_graph_handle* g, const tc2li_map_graph_delta* deltas, int n, void* stream) {
+    const char* me = "tc2li_map_graph_apply_batch";
+    if (!g || n < 0 || (n && !deltas)) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    if (n == 0) return 0;
+    std::lock_guard<std::mutex> lk(g->mu);
+    return apply_locked(me, g, deltas, n, stream);
+}
 
 // ---- download --------------------------------------------------------------------------------------------------------------------------
-extern "C" int tc2li_map_graph_download(tc2li_map_graph_handle* g, int sequence, tc2li_map_graph_tables* out, const int32_t* capacities, int32_t* counts) {
-    const char* me = "tc2li_map_graph_download";
-    if (!g || !sequence_ok(g, sequence) || !out || !capacities || !counts) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(g->mu);
+namespace {
+// the caller holds g->mu
+int download_locked(const char* me, tc2li_map_graph_handle* g, int sequence, tc2li_map_graph_tables* out, const int32_t* capacities, int32_t* counts) {
     const SeqMeta& m = g->seq[sequence];
     const MgSequenceView v = view_of(g, sequence);
     counts[0] = v.n_kf; counts[1] = v.n_slot; counts[2] = v.n_points; counts[3] = v.n_obs;
@@ -400,6 +412,14 @@ extern "C" int tc2li_map_graph_download(tc2li_map_graph_handle* g, int sequence,
     TC2LI_HIP_CHECK(get(out->obs_index, T.obs_index + v.t_obs, (size_t)v.n_obs * 4));
     return 0;
 }
+}  // namespace
+
+extern "C" int tc2li_map_graph_download(tc2li_map_graph_handle* g, int sequence, tc2li_map_graph_tables* out, const int32_t* capacities, int32_t* counts) {
+    const char* me = "tc2li_map_graph_download";
+    if (!g || !sequence_ok(g, sequence) || !out || !capacities || !counts) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(g->mu);
+    return download_locked(me, g, sequence, out, capacities, counts);
+}
 
 // ---- what a gather reads ---------------------------------------------------------------------------------------------------------------
 int tc2li::MgLease::acquire(const char* entry, tc2li_map_graph_handle* g, tc2li_keyframe_store* store, const int32_t* sequences_, int n_) {
@@ -420,6 +440,197 @@ tc2li::MgLease::~MgLease() {
     if (uploaded >= 0)
         for (int p = 0; p < n; ++p) graph->seq[sequences[p]].gather_bytes = uploaded;
     graph->mu.unlock();
+}
+
+// ---- the commit of solved windows ------------------------------------------------------------------------------------------------------
+int tc2li::map_graph_read(const char* entry, const MgLease& lease, int sequence, MgHostTables* out) {
+    tc2li_map_graph_handle* g = lease.graph;
+    const SeqMeta& m = g->seq[sequence];
+    const int32_t caps[4] = {m.n_kf, m.slot_off[m.n_kf], m.n_pt, m.n_obs};
+    const size_t nk = (size_t)caps[0], ns = (size_t)caps[1], np = (size_t)caps[2], no = (size_t)caps[3];
+    out->kf_slot.assign(nk + 1, 0); out->kf_id.assign(nk + 1, 0); out->kf_flags.assign(nk + 1, 0); out->poses7.assign(7 * nk + 1, 0.0);
+    out->slot_offsets.assign(nk + 1, 0); out->slot_point.assign(ns + 1, 0); out->point_flags.assign(np + 1, 0); out->positions.assign(3 * np + 1, 0.0);
+    out->obs_offsets.assign(np + 1, 0); out->obs_kf.assign(no + 1, 0); out->obs_index.assign(no + 1, 0);
+    tc2li_map_graph_tables& t = out->tables;
+    t.kf_slot = out->kf_slot.data(); t.kf_id = out->kf_id.data(); t.kf_flags = out->kf_flags.data(); t.poses7 = out->poses7.data();
+    t.slot_offsets = out->slot_offsets.data(); t.slot_point = out->slot_point.data(); t.point_flags = out->point_flags.data(); t.positions = out->positions.data();
+    t.obs_offsets = out->obs_offsets.data(); t.obs_kf = out->obs_kf.data(); t.obs_index = out->obs_index.data();
+    int32_t counts[4];
+    return download_locked(entry, g, sequence, &t, caps, counts);
+}
+
+int tc2li::map_graph_commit(const char* entry, const MgLease& lease, const MgCommitSource& src, const std::vector<MgCommitWindow>& wins,
+                            const tc2li_map_graph_delta* host_logs, int n_host_logs, uint32_t flags, hipStream_t st) {
+    tc2li_map_graph_handle* g = lease.graph;
+    const int n = (int)wins.size();
+    std::vector<int> order;                  // the windows with erase pairs first: their records are the apply kernels' batch
+    for (int k = 0; k < n; ++k) if (wins[k].n_erase > 0) order.push_back(k);
+    const int n_erasing = (int)order.size();
+    for (int k = 0; k < n; ++k) if (wins[k].n_erase <= 0) order.push_back(k);
+    // what k_mg_apply will read to find every touched row's edits (kMgMaxWalk): pair i erases its observation with edit 2 i + 1, and the
+    // pairs of a point are together within the monocular and within the stereo stretch, so a point has at most two stretches
+    size_t n_edits = 0;
+    int max_rows = 0;
+    for (int k = 0; k < n_erasing; ++k) {
+        const MgCommitWindow& w = wins[order[k]];
+        std::vector<int32_t> first(w.n_points, -1), last(w.n_points, -1);
+        for (int i = 0; i < w.n_erase; ++i) {
+            const int pt = w.erase_point[i];
+            if (pt < 0 || pt >= w.n_points) { set_error("%s: sequence %d: an erase pair names a point outside the window", entry, w.sequence); return TC2LI_ERR_INVALID; }
+            if (first[pt] < 0) first[pt] = 2 * i + 1;
+            last[pt] = 2 * i + 1;
+        }
+        int64_t walk = 0;
+        for (int p = 0; p < w.n_points; ++p) walk += first[p] < 0 ? 0 : last[p] - first[p] + 1;
+        if (walk > kMgMaxWalk) {
+            set_error("%s: sequence %d: the erase pairs of single points lie %lld log entries apart in sum, the limit is %lld; solve without the commit and split the log", entry,
+                      w.sequence, (long long)walk, (long long)kMgMaxWalk);
+            return TC2LI_ERR_CAPACITY;
+        }
+        n_edits += 2 * (size_t)w.n_erase;
+        if (n_edits > kMaxRows) return too_many_rows(entry, order[k]);
+    }
+    MgCommitBatch C{};
+    if (n) {
+        if (!device_ready()) return TC2LI_ERR_NO_DEVICE;
+        const size_t o_edits = (size_t)n * sizeof(MgApplyDev), bytes = o_edits + n_edits * sizeof(tc2li_map_graph_edit);
+        TC2LI_HIP_CHECK(g->h_commit.ensure(o_edits)); TC2LI_HIP_CHECK(g->d_commit.ensure(bytes));
+        TC2LI_HIP_CHECK(g->d_commit_words.ensure(2 * (size_t)n)); TC2LI_HIP_CHECK(g->h_commit_words.ensure(2 * (size_t)n));
+        MgApplyDev* rec = reinterpret_cast<MgApplyDev*>(g->h_commit.p);
+        size_t e_at = 0;
+        for (int k = 0; k < n; ++k) {
+            const MgCommitWindow& w = wins[order[k]];
+            const SeqMeta& m = g->seq[w.sequence];
+            MgApplyDev r{};
+            r.sequence = w.sequence; r.generation = m.generation; r.n_kf = m.n_kf; r.n_points = m.n_pt; r.n_slot = m.slot_off[m.n_kf]; r.n_obs = m.n_obs;
+            r.edit_off = (int32_t)e_at; r.n_edits = 2 * std::max(w.n_erase, 0); r.value_off = 0; r.n_points_new = m.n_pt;
+            r.pad_[kMgcPoseOff] = w.pose_off; r.pad_[kMgcPointOff] = w.point_off; r.pad_[kMgcPoses] = w.n_poses; r.pad_[kMgcPoints] = w.n_points;
+            r.pad_[kMgcEraseAt] = w.erase_at; r.pad_[kMgcEraseCap] = w.erase_cap;
+            rec[k] = r;
+            e_at += (size_t)r.n_edits;
+            max_rows = std::max(max_rows, w.n_poses + w.n_points);
+        }
+        TC2LI_HIP_CHECK(hipMemcpyAsync(g->d_commit.p, g->h_commit.p, o_edits, hipMemcpyHostToDevice, st));   // all that goes up: 64 bytes per sequence
+        C.T = g->T; C.n = n; C.n_erasing = n_erasing; C.max_rows = max_rows; C.flags = flags;
+        C.records = reinterpret_cast<const MgApplyDev*>(g->d_commit.p);
+        C.pose_row = src.pose_row; C.fixed = src.fixed; C.poses7 = src.poses7; C.point_row = src.point_row; C.points3 = src.points3; C.erase = src.erase;
+        C.edits = reinterpret_cast<tc2li_map_graph_edit*>(g->d_commit.p + o_edits);
+        C.status = g->d_commit_words.p + n;
+        if (n_erasing) {   // the erase logs first: they read the tables and write none, and the host sees whether every pair was resolved
+            launch_map_graph_commit_erase_log(C, st);
+            TC2LI_HIP_CHECK(hipGetLastError());
+            TC2LI_HIP_CHECK(hipMemcpyAsync(g->h_commit_words.p + n, C.status, (size_t)n_erasing * 4, hipMemcpyDeviceToHost, st));
+            TC2LI_HIP_CHECK(stream_wait_blocking(st));
+            for (int k = 0; k < n_erasing; ++k)
+                if (g->h_commit_words.p[n + k]) {
+                    set_error("%s: sequence %d: an erase pair names a keyframe that is not in the point's observation row", entry,
+                              wins[order[k]].sequence);
+                    return TC2LI_ERR_INVALID;
+                }
+        }
+    }
+    // the logs of the windows finished on the host: checked as any log before anything is written
+    if (n_host_logs > 0) {
+        const int rc = apply_locked(entry, g, host_logs, n_host_logs, st);
+        if (rc < 0) return rc;
+    }
+    if (!n) return 0;
+    launch_map_graph_commit_scatter(C, st);
+    TC2LI_HIP_CHECK(hipGetLastError());
+    if (n_erasing) {   // a window without erase pairs keeps its observation CSR and its generation
+        MgApplyBatch A{};
+        A.T = g->T; A.n = n_erasing; A.deltas = C.records; A.edits = C.edits; A.values = nullptr; A.totals = g->d_commit_words.p;
+        launch_map_graph_apply(A, st);
+        TC2LI_HIP_CHECK(hipGetLastError());
+        TC2LI_HIP_CHECK(hipMemcpyAsync(g->h_commit_words.p, g->d_commit_words.p, (size_t)n_erasing * 4, hipMemcpyDeviceToHost, st));
+    }
+    TC2LI_HIP_CHECK(stream_wait_blocking(st));
+    for (int k = 0; k < n; ++k) {
+        SeqMeta& m = g->seq[wins[order[k]].sequence];
+        if (k < n_erasing) { m.generation ^= 1; m.n_obs = g->h_commit_words.p[k]; }
+        ++m.applies;
+        m.apply_bytes = (int64_t)sizeof(MgApplyDev);
+    }
+    return 0;
+}
+
+// the host's statement of the step: it defines what map_graph_commit leaves
+extern "C" int tc2li_host_ba_window_commit_log(const tc2li_map_graph_tables* t, const tc2li_ba_window_solve_problem* q, int32_t result, uint32_t flags,
+                                               tc2li_map_graph_edit* edits, int edit_capacity, double* values, int value_capacity, int32_t* n_edits_out,
+                                               int32_t* n_values_out) {
+    const char* me = "tc2li_host_ba_window_commit_log";
+    if (!t || !q || !n_values_out || edit_capacity < 0 || value_capacity < 0 || !q->window.counts) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    if (flags & ~(uint32_t)TC2LI_BA_COMMIT_POSITIONS_F32) { set_error("%s: unknown flag bits", me); return TC2LI_ERR_INVALID; }
+    if (!q->n_erase) { set_error("%s: n_erase is NULL: the commit is defined by the outlier rule", me); return TC2LI_ERR_INVALID; }
+    const tc2li_ba_window_problem& w = q->window;
+    if (w.counts[TC2LI_BA_WINDOW_STATUS] != TC2LI_BA_WINDOW_OK || result < 0) {   // ABORTED, refused or failed: nothing to recover
+        if (n_edits_out) *n_edits_out = 0;
+        *n_values_out = 0;
+        return 0;
+    }
+    const char* what = tables_fault(*t);
+    if (!what[0] && (!ascending(t->slot_offsets, t->n_keyframes) || !ascending(t->obs_offsets, t->n_points))) what = "offsets do not ascend from 0";
+    if (what[0]) { set_error("%s: %s", me, what); return TC2LI_ERR_INVALID; }
+    const int n_poses = w.counts[TC2LI_BA_WINDOW_N_POSES], n_points = w.counts[TC2LI_BA_WINDOW_N_POINTS], n_erase = *q->n_erase;
+    if (n_poses < 0 || n_points < 0 || n_erase < 0 || (n_poses && (!w.pose_row || !w.fixed || !w.poses7_out)) || (n_points && (!w.point_row || !w.points3_out)) ||
+        (n_erase && (!q->erase_pose || !q->erase_point)) || (t->obs_offsets[t->n_points] && (!t->obs_kf || !t->obs_index))) {
+        set_error("%s: negative count or null array", me);
+        return TC2LI_ERR_INVALID;
+    }
+    int n_free = 0;
+    for (int i = 0; i < n_poses; ++i) {
+        if (w.pose_row[i] < 0 || w.pose_row[i] >= t->n_keyframes) { set_error("%s: pose_row[%d] is outside the tables", me, i); return TC2LI_ERR_INVALID; }
+        n_free += w.fixed[i] ? 0 : 1;
+    }
+    for (int j = 0; j < n_points; ++j)
+        if (w.point_row[j] < 0 || w.point_row[j] >= t->n_points) { set_error("%s: point_row[%d] is outside the tables", me, j); return TC2LI_ERR_INVALID; }
+    int64_t need_edits = 2 * (int64_t)n_erase + n_free + n_points;   // (fewer where a keyframe row holds no slot to clear: known after the look-up)
+    const int64_t need_values = 7 * (int64_t)n_free + 3 * (int64_t)n_points;
+    if (need_edits > INT_MAX || need_values > INT_MAX) { set_error("%s: the log is beyond 2^31 entries", me); return TC2LI_ERR_INVALID; }
+    if (n_erase > q->erase_capacity) {
+        if (n_edits_out) *n_edits_out = (int32_t)need_edits;
+        *n_values_out = (int32_t)need_values;
+        set_error("%s: %d erase pairs and erase_capacity %d: the lists are cut", me, n_erase, q->erase_capacity);
+        return TC2LI_ERR_CAPACITY;
+    }
+    std::vector<int32_t> index(n_erase, 0);
+    for (int i = 0; i < n_erase; ++i) {
+        const int ep = q->erase_pose[i], et = q->erase_point[i];
+        if (ep < 0 || ep >= n_poses || et < 0 || et >= n_points) { set_error("%s: erase pair %d is outside the counts", me, i); return TC2LI_ERR_INVALID; }
+        const int kf = w.pose_row[ep], pt = w.point_row[et];
+        const int32_t *b = t->obs_kf + t->obs_offsets[pt], *e = t->obs_kf + t->obs_offsets[pt + 1];
+        const int32_t* it = std::lower_bound(b, e, kf);
+        if (it == e || *it != kf) { set_error("%s: erase pair %d: keyframe row %d is not in the observation row of point %d", me, i, kf, pt); return TC2LI_ERR_INVALID; }
+        index[i] = t->obs_index[it - t->obs_kf];                                            // GetIndexInKeyFrame (KeyFrame::EraseMapPointMatch(MapPoint*))
+        if (index[i] < 0 || index[i] >= t->slot_offsets[kf + 1] - t->slot_offsets[kf]) { index[i] = -1; --need_edits; }   // the row's matches are not resident: no slot to clear
+    }
+    if (n_edits_out) *n_edits_out = (int32_t)need_edits;
+    *n_values_out = (int32_t)need_values;
+    if (need_edits > edit_capacity || need_values > value_capacity) {
+        set_error("%s: the log has %lld edits and %lld values, the arrays hold %d and %d", me, (long long)need_edits, (long long)need_values, edit_capacity, value_capacity);
+        return TC2LI_ERR_CAPACITY;
+    }
+    if ((need_edits && !edits) || (need_values && !values)) { set_error("%s: null edits or values", me); return TC2LI_ERR_INVALID; }
+    int e_at = 0, v_at = 0;
+    for (int i = 0; i < n_erase; ++i) {                                                     // OptimizerWithLidar.cc:457-463
+        const int kf = w.pose_row[q->erase_pose[i]], pt = w.point_row[q->erase_point[i]];
+        if (index[i] >= 0) edits[e_at++] = tc2li_map_graph_edit{TC2LI_MAP_GRAPH_SET_SLOT, kf, index[i], -1};
+        edits[e_at++] = tc2li_map_graph_edit{TC2LI_MAP_GRAPH_ERASE_OBSERVATION, pt, kf, 0};
+    }
+    for (int i = 0; i < n_poses; ++i) {                                                     // :468-475
+        if (w.fixed[i]) continue;
+        edits[e_at++] = tc2li_map_graph_edit{TC2LI_MAP_GRAPH_SET_POSE, w.pose_row[i], v_at, 0};
+        memcpy(values + v_at, w.poses7_out + 7 * (size_t)i, 7 * sizeof(double));
+        v_at += 7;
+    }
+    for (int j = 0; j < n_points; ++j) {                                                    // :478-484
+        edits[e_at++] = tc2li_map_graph_edit{TC2LI_MAP_GRAPH_SET_POSITION, w.point_row[j], v_at, 0};
+        for (int c = 0; c < 3; ++c) {
+            const double x = w.points3_out[3 * (size_t)j + c];
+            values[v_at++] = (flags & TC2LI_BA_COMMIT_POSITIONS_F32) ? (double)(float)x : x;   // cast<float>() (:482)
+        }
+    }
+    return e_at;
 }
 
 // ---- the host twin ---------------------------------------------------------------------------------------------------------------------

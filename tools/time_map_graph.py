@@ -1,9 +1,13 @@
 """Timings of the local-BA gather from the resident map graph beside the gather from host arrays, for 512 sequences of the bundle
 adjustment's own window shape (synthetic.ba_window: 10 free and 30 fixed keyframes, 2 000 points; 32 different windows, each sequence one
-of them).  Two pairs of legs:
+of them).  Two pairs of legs and a fifth:
 
     gather   tc2li_ba_window_batch on host arrays          against   tc2li_map_graph_apply_batch + tc2li_ba_window_graph_batch
     solve    tc2li_ba_window_solve_batch, edges == NULL     against   tc2li_map_graph_apply_batch + tc2li_ba_window_solve_graph_batch
+    resident_commit   tc2li_map_graph_apply_batch of the delta WITHOUT its SET_POSE / SET_POSITION edits, then
+                      tc2li_ba_window_solve_graph_commit_batch, which writes the BA's result into the resident tables itself.  Its graph
+                      changes from cycle to cycle (the solved poses and points stay, the outlier pairs go), so from the second cycle on
+                      its BA starts from a converged map: the mean iterations and trials of the last cycle are printed for every solve leg.
 
 The delta of every apply is one keyframe's worth per sequence: one new keyframe row, 400 slots set and 400 observations added on it, 40
 poses and 2 000 positions overwritten.  The host-array legs gather the graph as it was set (the resident one grows by a row per call; 400
@@ -47,8 +51,9 @@ def world(pkg):
     return views, problems, sigma, cam
 
 
-def delta_of(pr, n_keys, call, rng):
-    """one keyframe's worth of edits for the graph of `pr` after `call` earlier ones -> (edits, values)"""
+def delta_of(pr, n_keys, call, rng, with_results=True):
+    """one keyframe's worth of edits for the graph of `pr` after `call` earlier ones -> (edits, values).  with_results: the BA's result
+    sent back as SET_POSE / SET_POSITION edits, which a committing solve makes unnecessary."""
     import map_graph_cases as M
     L = M.Log(pr)
     for _ in range(call):                                                               # the rows the earlier calls appended
@@ -60,9 +65,9 @@ def delta_of(pr, n_keys, call, rng):
     for i, p in enumerate(pts):
         L.set_slot(k, i, int(p))
         L.add_observation(int(p), k, i % n_keys[slot])
-    for r in rng.choice(n_kf, min(N_POSES, n_kf), replace=False):
+    for r in rng.choice(n_kf, min(N_POSES, n_kf), replace=False) if with_results else ():
         L.set_pose(int(r), pr["poses7"][r])
-    for p in rng.choice(n_pt, min(N_POSITIONS, n_pt), replace=False):
+    for p in rng.choice(n_pt, min(N_POSITIONS, n_pt), replace=False) if with_results else ():
         L.set_position(int(p), pr["positions"][p])
     return L.done()
 
@@ -83,7 +88,8 @@ def child(leg, n, reps, warmup):
     import ba_window_cases as K
     views, base, sigma, cam = world(pkg)
     sg = np.ascontiguousarray(sigma, np.float32)
-    solve, resident = leg.endswith("solve"), leg.startswith("resident")
+    commit = leg == "resident_commit"
+    solve, resident = leg.endswith("solve") or commit, leg.startswith("resident")
     calls = warmup + reps
     # room for what the resident graph grows to: every call's new keyframe sees 400 points and so becomes a fixed camera with 400 edges
     base = [dict(p, pose_capacity=len(p["kf_slot"]) + calls, edge_capacity=len(p["obs_kf"]) + N_OBS * calls, erase_capacity=len(p["obs_kf"]) + N_OBS * calls)
@@ -107,7 +113,7 @@ def child(leg, n, reps, warmup):
             graph.set_batch(seq, problems)
             rng = np.random.default_rng(1)
             for c in range(calls):                                                      # the logs of every call, packed outside the clock
-                per_base = [delta_of(p, n_keys, c, rng) for p in base]
+                per_base = [delta_of(p, n_keys, c, rng, with_results=not commit) for p in base]
                 darr, dkeep = (capi.MapGraphDelta * n)(), per_base
                 for i in range(n):
                     e, v = per_base[i % N_BASE]
@@ -119,7 +125,10 @@ def child(leg, n, reps, warmup):
         L.tc2li_ba_window_graph_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.tc2li_ba_window_solve_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.tc2li_ba_window_solve_graph_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.tc2li_ba_window_solve_graph_commit_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                               C.c_uint32, C.c_void_p]
         a, s, h = C.addressof(arr), store._handle(), graph._handle() if resident else None
+        bytes_of_apply = [0]
 
         def call(c):
             t_apply = 0.0
@@ -128,8 +137,12 @@ def child(leg, n, reps, warmup):
                 rc = L.tc2li_map_graph_apply_batch(h, C.addressof(deltas[c][0]), n, None)
                 t_apply = (time.perf_counter() - t) * 1e3
                 assert rc == n, (rc, L.tc2li_last_error())
+                if commit and c == calls - 1:                                           # (the commit overwrites the counter; outside the clocks)
+                    bytes_of_apply[0] = int(sum(graph.info(i)["apply_bytes"] for i in range(n)))
             t = time.perf_counter()
-            if solve and resident:
+            if commit:
+                rc = L.tc2li_ba_window_solve_graph_commit_batch(s, h, seq.ctypes.data, a, n, sg.ctypes.data, len(sg), cam.ctypes.data, 0, 0, results.ctypes.data)
+            elif solve and resident:
                 rc = L.tc2li_ba_window_solve_graph_batch(s, h, seq.ctypes.data, a, n, sg.ctypes.data, len(sg), cam.ctypes.data, 0, results.ctypes.data)
             elif solve:
                 rc = L.tc2li_ba_window_solve_batch(s, a, n, sg.ctypes.data, len(sg), cam.ctypes.data, 0, results.ctypes.data)
@@ -146,9 +159,14 @@ def child(leg, n, reps, warmup):
         res = dict(leg=leg, sequences=n, reps=reps, pair=stat(total), apply=stat([x for x, _ in times]), gather=stat([y for _, y in times]),
                    n_keyframes=float(np.mean([len(p["kf_slot"]) for p in base])), n_points=float(np.mean([len(p["point_flags"]) for p in base])),
                    n_observations=float(np.mean([len(p["obs_kf"]) for p in base])), windows_ok=int(sum(int(o["counts"][0]) == 0 for o in outs)))
+        if solve:
+            res.update(windows_solved=int((results > 0).sum()), iterations=float(np.mean([o["stats"].iterations for o in outs])),
+                       trials=float(np.mean([o["stats"].trials for o in outs])), erase_pairs=float(np.mean([int(o["n_erase"][0]) for o in outs])))
         if resident:
             info = [graph.info(i) for i in range(n)]
-            res.update(apply_bytes=int(sum(i["apply_bytes"] for i in info)), gather_bytes=int(info[0]["gather_bytes"]),
+            if commit:
+                res.update(commit_bytes=int(sum(i["apply_bytes"] for i in info)), applies=int(info[0]["applies"]))
+            res.update(apply_bytes=bytes_of_apply[0] if commit else int(sum(i["apply_bytes"] for i in info)), gather_bytes=int(info[0]["gather_bytes"]),
                        edits_per_sequence=float(np.mean([len(e) for e, _ in deltas[-1][1]])))
             graph.close()
         else:
@@ -166,14 +184,14 @@ def main():
     ap.add_argument("--timeout", type=int, default=240)
     ap.add_argument("--legs", default="host_gather,resident_gather,host_solve,resident_solve")
     ap.add_argument("--json")
-    ap.add_argument("--child", help="one leg in this process: host_gather, resident_gather, host_solve or resident_solve")
+    ap.add_argument("--child", help="one leg in this process: host_gather, resident_gather, host_solve, resident_solve or resident_commit")
     a = ap.parse_args()
     if a.child:
         child(a.child, a.sequences, a.reps, a.warmup)
         return
     rows = {}
     for leg in a.legs.split(","):
-        reps = a.solve_reps if leg.endswith("solve") else a.reps
+        reps = a.solve_reps if leg.endswith("solve") or leg == "resident_commit" else a.reps
         cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", leg, "--sequences", str(a.sequences),
                "--reps", str(reps), "--warmup", str(a.warmup)]
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -187,6 +205,11 @@ def main():
             print("%s, %d sequences: host arrays %.2f ms (%.2f-%.2f), %.1f MB up; resident apply %.2f + %s %.2f = %.2f ms (%.2f-%.2f), %.2f + %.3f MB up"
                   % (kind, b["sequences"], b["pair"]["ms"], b["pair"]["min_ms"], b["pair"]["max_ms"], b["gather_bytes"] / 1e6, r["apply"]["ms"], kind,
                      r["gather"]["ms"], r["pair"]["ms"], r["pair"]["min_ms"], r["pair"]["max_ms"], r["apply_bytes"] / 1e6, r["gather_bytes"] / 1e6))
+    if "resident_commit" in rows:
+        r = rows["resident_commit"]
+        print("committed cycle, %d sequences: apply %.2f + solve and commit %.2f = %.2f ms (%.2f-%.2f), %.2f + %.3f + %.3f MB up (apply, gather, commit); %.1f iterations, %.1f trials, %.1f erase pairs per window"
+              % (r["sequences"], r["apply"]["ms"], r["gather"]["ms"], r["pair"]["ms"], r["pair"]["min_ms"], r["pair"]["max_ms"], r["apply_bytes"] / 1e6, r["gather_bytes"] / 1e6,
+                 r["commit_bytes"] / 1e6, r["iterations"], r["trials"], r["erase_pairs"]))
     if a.json:
         json.dump(rows, open(a.json, "w"), indent=1)
 
