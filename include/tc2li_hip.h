@@ -514,7 +514,11 @@ int tc2li_pose_optimization_batch(int n_frames, double* poses7, const int32_t* e
  * kernel, and which kernel ran last (for tests): out[0] = the largest number of correspondences of a batch's largest frame at which the
  * frames are staged in LDS (beyond: every frame of the batch works in global memory), out[1] = the step in correspondences by which the
  * LDS block grows, out[2] = threads per frame, out[3] = what the most recent pose optimisation of this process launched: 0 nothing yet,
- * 1 the LDS kernel, 2 the global-memory kernel.  Returns 4.  Needs no device.  No reference counterpart. */
+ * 1 the LDS kernel (61 bytes per correspondence), 2 the global-memory kernel, 3 the LDS kernel in its compact form (33 bytes per
+ * correspondence: map points and observations held as floats; launched only when every one of them is a float's value, so the results are
+ * the same bits; reported by the two entries above, which have the device check the staged values.  The tracking batches make their
+ * values from floats and take the compact layout without a check; their launches report 1, "staged in LDS", in either layout).
+ * TC2LI_PO_COMPACT=0, read per call, keeps the 61-byte layout everywhere.  Returns 4.  Needs no device.  No reference counterpart. */
 int tc2li_pose_optimization_limits(int32_t* out, int capacity);
 
 /* Statistics of one bundle adjustment (all optional). */

@@ -864,7 +864,8 @@ def pose_optimization_batch(poses7, edge_offsets, Xw, edges, cam5, stream=0):
 
 def pose_optimization_limits():
     """tc2li_pose_optimization_limits -> {lds_max_edges, lds_granule, threads, last_form}: a batch whose largest frame has more than lds_max_edges
-    correspondences runs the global-memory kernel; last_form is what the most recent pose optimisation launched (0 none, 1 LDS, 2 global)."""
+    correspondences runs the global-memory kernel; last_form is what the most recent pose optimisation launched (0 none, 1 LDS, 2 global,
+    3 LDS in the compact layout after the public entries' device-side check; TC2LI_PO_COMPACT=0 keeps the 61-byte layout)."""
     out = (C.c_int32 * 4)()
     f = lib().tc2li_pose_optimization_limits
     f.argtypes = [C.c_void_p, C.c_int]

@@ -43,7 +43,19 @@ int tc2li_pose_optimization_batch(int n_frames, double* poses7, const int32_t* e
     memcpy(&c, cam, sizeof(c));
     int max_edges = 0;
     for (int f = 0; f < n_frames; ++f) max_edges = std::max(max_edges, probs[f].n);
-    launch_pose_optimization(w.d_probs.p, n_frames, w.d_Xw.p, w.d_edges.p, c, w.d_poses.p, w.d_outlier.p, w.d_chi2.p, w.d_inliers.p, max_edges, st);
+    // the caller's doubles: the compact LDS form only after the device has looked at every staged value (one small kernel and a 4-byte
+    // read-back; this entry waits for its results anyway)
+    int exact = 0;
+    if (total) {
+        static const int one = 1;
+        TC2LI_HIP_CHECK(w.d_exact.ensure(1));
+        TC2LI_HIP_CHECK(hipMemcpyAsync(w.d_exact.p, &one, sizeof(int), hipMemcpyHostToDevice, st));
+        launch_pose_inputs_float_exact(w.d_Xw.p, w.d_edges.p, total, w.d_exact.p, st);
+        TC2LI_HIP_CHECK(hipMemcpyAsync(&exact, w.d_exact.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        TC2LI_HIP_CHECK(stream_wait_blocking(st));
+    }
+    launch_pose_optimization(w.d_probs.p, n_frames, w.d_Xw.p, w.d_edges.p, c, w.d_poses.p, w.d_outlier.p, w.d_chi2.p, w.d_inliers.p, max_edges, st,
+                             exact ? PoseFloats::kChecked : PoseFloats::kUnknown);
     TC2LI_HIP_CHECK(hipGetLastError());
     TC2LI_HIP_CHECK(hipMemcpyAsync(poses7, w.d_poses.p, (size_t)7 * n_frames * sizeof(double), hipMemcpyDeviceToHost, st));
     TC2LI_HIP_CHECK(hipMemcpyAsync(n_inliers, w.d_inliers.p, n_frames * sizeof(int), hipMemcpyDeviceToHost, st));

@@ -64,7 +64,7 @@ struct PoseOptWorkspace {
     DevBuf<double> d_Xw, d_poses, d_chi2;
     DevBuf<BaEdge> d_edges;
     DevBuf<uint8_t> d_outlier;
-    DevBuf<int> d_inliers;
+    DevBuf<int> d_inliers, d_exact;  // d_exact [1]: launch_pose_inputs_float_exact's answer
     std::mutex mu;
 };
 inline PoseOptWorkspace& po_ws() { static thread_local PoseOptWorkspace w; return w; }

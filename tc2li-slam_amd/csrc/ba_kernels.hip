@@ -1402,8 +1402,7 @@ __global__ __launch_bounds__(256) void k_ba_schur_finish_b(const BaPhase ph) {
 // workgroup per window, lane i = row i.  Every element is formed by the same operations in the same order as on the host -- a row's
 // sums run over k ascending, one column after the other; the forward substitution subtracts column by column (k ascending per row); the
 // backward substitution is the host's row loop, one lane at a time -- so a window gives the same step here and in the one-window path.
-// The lower triangle lives packed in LDS (row i at i (i + 1) / 2).  A pivot that is zero or not finite: ok = 0 and a zero step (the
-// host treats the trial as failed).
+// A pivot that is zero or not finite: ok = 0 and a zero step (the host treats the trial as failed).
 // The reduced system of a window solved on the device (TC2LI_BA_DEVICE_SOLVE=1): ldlt_solve_small's factorisation and substitutions, the same
 // operations on the same operands in the same order per entry -- so the step is the host's bit for bit -- carried out by a workgroup:
 //   * factorisation RIGHT-LOOKING (round 5): after column k has its pivot and L_ik = a_ik / D_k, every remaining entry (i, j), j > k, takes its
@@ -1421,10 +1420,17 @@ constexpr int kSolveThreads = 256;
 // entries into LDS, one thread per row divides by the pivot, and every thread takes its entries' terms (l_i l_j) d from
 // the two short LDS vectors -- two barriers per column, no index arithmetic (the tile loops are unrolled, a tile left of the column is a
 // scalar branch).  The operations per entry are the old kernel's and ldlt_solve_small's, in their order: the step is the same bit for bit.
-// Then L goes to LDS once and wavefront 0 runs the backward sweep with the solution in its registers (x_k by v_readlane).
+// Then wavefront 0 runs the backward sweep with the solution in its registers (x_k by v_readlane).  The sweep needs row k of L only while it
+// handles row k, so L goes to LDS one tile row at a time, from the last tile row up: its 16 rows into s_L ([16][16 NT] doubles: 18 KB
+// in the widest variant), barrier, the sweep over those rows with k descending, barrier.  (Until then the whole packed triangle went to LDS
+// first -- 26 / 66 / 83 KB of dynamic LDS for 5 / 8 / 9 tile rows, for every window of the launch: such a workgroup starts only on a CU
+// with half its LDS free.)  Per entry the operations and their order are unchanged.
+// A window narrower than its variant (n <= 16 (NT - 1)) skips the tile rows at or beyond ceil(n / 16) in the elimination's update loop and
+// in the sweep, on a scalar branch: those registers hold zeros that never reach a result.
 template <int NT>
 __device__ __forceinline__ void d_ba_solve_tiles(const BaBatchSlot& sl, const int n, double* s_L) {
     constexpr int kTiles = NT * (NT + 1) / 2;
+    const int nt_live = __builtin_amdgcn_readfirstlane((n + 15) >> 4);   // tile rows that hold a row of the window
     constexpr int kRows = 16 * 9;   // the widest variant: 24 free keyframes
     __shared__ double s_colA[kRows], s_colL[kRows], s_dg[kRows], s_xs[kRows], s_y;
     __shared__ int s_bad;
@@ -1479,7 +1485,8 @@ __device__ __forceinline__ void d_ba_solve_tiles(const BaBatchSlot& sl, const in
             if (tx == kr) {
                 if (ty >= kr) s_colA[16 * kt + ty] = a[kt * (kt + 1) / 2 + kt];
 #pragma unroll
-                for (int ti = kt + 1; ti < NT; ++ti) s_colA[16 * ti + ty] = a[ti * (ti + 1) / 2 + kt];
+                for (int ti = kt + 1; ti < NT; ++ti)
+                    if (ti < nt_live) s_colA[16 * ti + ty] = a[ti * (ti + 1) / 2 + kt];
             }
             if (tx == 0 && ty == kr) s_y = rhs[kt];
             __syncthreads();
@@ -1500,6 +1507,7 @@ __device__ __forceinline__ void d_ba_solve_tiles(const BaBatchSlot& sl, const in
             }
 #pragma unroll
             for (int ti = kt + 1; ti < NT; ++ti) {
+                if (ti >= nt_live) break;
                 {   // the tile in the column's own tile column: its entries right of the column take their term, the column's become L
                     const int q = ti * (ti + 1) / 2 + kt;
                     const double upd = a[q] - li[ti] * lj[kt] * d;
@@ -1511,30 +1519,43 @@ __device__ __forceinline__ void d_ba_solve_tiles(const BaBatchSlot& sl, const in
             }
         }
     }
-    // L (strictly lower) and y to LDS; z = y / D; backward sweep x_i = z_i - sum_{k > i} L_ki x_k, k descending, by wavefront 0
+    // y to LDS; z = y / D; backward sweep x_i = z_i - sum_{k > i} L_ki x_k, k descending, by wavefront 0, a tile row of L at a time
 #pragma unroll
     for (int ti = 0; ti < NT; ++ti) {
         const int i = 16 * ti + ty;
-#pragma unroll
-        for (int tj = 0; tj <= ti; ++tj) { const int j = 16 * tj + tx; if (i < n && j < i) s_L[i * (i + 1) / 2 + j] = a[ti * (ti + 1) / 2 + tj]; }  // (packed: 24 free keyframes are 83 KB)
         if (tx == 0 && i < n) s_xs[i] = rhs[ti];
     }
     __syncthreads();
+    const int lane = tid & 63;
+    double x0 = 0.0, x1 = 0.0, x2 = 0.0;
     if (tid < 64) {
-        const int lane = tid;
-        double x0 = lane < n ? s_xs[lane] / s_dg[lane] : 0.0, x1 = lane + 64 < n ? s_xs[lane + 64] / s_dg[lane + 64] : 0.0,
-               x2 = lane + 128 < n ? s_xs[lane + 128] / s_dg[lane + 128] : 0.0;
-        for (int k = n - 1; k >= 1; --k) {
-            union { double d; int w[2]; } xk;
-            xk.d = k >= 128 ? x2 : k >= 64 ? x1 : x0;
-            xk.w[0] = __builtin_amdgcn_readlane(xk.w[0], k & 63);
-            xk.w[1] = __builtin_amdgcn_readlane(xk.w[1], k & 63);
-            const double* row = s_L + k * (k + 1) / 2;
-            const double l0 = row[min(lane, k - 1)], l1 = row[min(lane + 64, k - 1)], l2 = row[min(lane + 128, k - 1)];
-            x0 = lane < k ? x0 - l0 * xk.d : x0;
-            x1 = lane + 64 < k ? x1 - l1 * xk.d : x1;
-            x2 = lane + 128 < k ? x2 - l2 * xk.d : x2;
+        x0 = lane < n ? s_xs[lane] / s_dg[lane] : 0.0; x1 = lane + 64 < n ? s_xs[lane + 64] / s_dg[lane + 64] : 0.0;
+        x2 = lane + 128 < n ? s_xs[lane + 128] / s_dg[lane + 128] : 0.0;
+    }
+#pragma unroll
+    for (int ti = NT - 1; ti >= 0; --ti) {
+        if (ti >= nt_live) continue;   // (uniform: every thread of the workgroup passes the same barriers)
+        // row 16 ti + ty, columns 0 .. 16 ti + 15, as the registers hold them: what lies on or above the diagonal, or beyond row n, is
+        // written but never read (the sweep reads columns below k of the rows k < n)
+#pragma unroll
+        for (int tj = 0; tj <= ti; ++tj) s_L[ty * (16 * NT) + 16 * tj + tx] = a[ti * (ti + 1) / 2 + tj];
+        __syncthreads();
+        if (tid < 64) {
+            for (int k = min(16 * ti + 15, n - 1); k >= max(16 * ti, 1); --k) {
+                union { double d; int w[2]; } xk;
+                xk.d = k >= 128 ? x2 : k >= 64 ? x1 : x0;
+                xk.w[0] = __builtin_amdgcn_readlane(xk.w[0], k & 63);
+                xk.w[1] = __builtin_amdgcn_readlane(xk.w[1], k & 63);
+                const double* row = s_L + (k - 16 * ti) * (16 * NT);
+                const double l0 = row[min(lane, k - 1)], l1 = row[min(lane + 64, k - 1)], l2 = row[min(lane + 128, k - 1)];
+                x0 = lane < k ? x0 - l0 * xk.d : x0;
+                x1 = lane + 64 < k ? x1 - l1 * xk.d : x1;
+                x2 = lane + 128 < k ? x2 - l2 * xk.d : x2;
+            }
         }
+        if (ti > 0) __syncthreads();   // the sweep has read the tile row before the next one up takes its place
+    }
+    if (tid < 64) {
         const bool bad = s_bad != 0;
         double* x_dev = global_ptr(load_uniform(&sl.x_dev));
         double* x_host = global_ptr(load_uniform(&sl.x_host));
@@ -2132,15 +2153,14 @@ void ba_batch_launch_schur(const BaPhaseHost& ph, int n_active, const BaBatchExt
 void ba_batch_launch_solve(const BaPhase& ph, int n_active, const BaBatchExtent& x, hipStream_t st) {
     if (!n_active || !x.max_free) return;
     const int n = 6 * x.max_free;   // (the callers send no window beyond kSolveMaxFree free keyframes here)
-    const size_t lds = (size_t)n * (n + 1) / 2 * sizeof(double);  // L, packed, for the backward sweep: 12 free keyframes 21 KB, 24: 83 KB
+    // one tile row of L at a time for the backward sweep, [16][16 NT] doubles: 10 / 16 / 18 KB -- below the default limit of a kernel
+    const auto lds = [](int nt) { return (size_t)16 * 16 * nt * sizeof(double); };
     if (n <= 80) {
-        TC2LI_LAUNCH(k_ba_solve5_b, dim3(n_active), dim3(kSolveThreads), lds, st, ph);
+        TC2LI_LAUNCH(k_ba_solve5_b, dim3(n_active), dim3(kSolveThreads), lds(5), st, ph);
     } else if (n <= 128) {
-        (void)ensure_dynamic_lds((const void*)k_ba_solve_b, 96 * 1024);
-        TC2LI_LAUNCH(k_ba_solve_b, dim3(n_active), dim3(kSolveThreads), lds, st, ph);
+        TC2LI_LAUNCH(k_ba_solve_b, dim3(n_active), dim3(kSolveThreads), lds(8), st, ph);
     } else {
-        (void)ensure_dynamic_lds((const void*)k_ba_solve9_b, 96 * 1024);
-        TC2LI_LAUNCH(k_ba_solve9_b, dim3(n_active), dim3(kSolveThreads), lds, st, ph);
+        TC2LI_LAUNCH(k_ba_solve9_b, dim3(n_active), dim3(kSolveThreads), lds(9), st, ph);
     }
 }
 // whether the two kernels get the LDS of their largest window (25 free keyframes: 160 KB, all a CU has); asked once, before a window is promised

@@ -53,8 +53,9 @@ __device__ __forceinline__ double block_sum(double x, double* s_red, double* s_o
 // LDS by the caller (k_pose_optimization_lds)
 // (edge_at(i): the i-th correspondence as a BaEdge -- out of global memory, or rebuilt from the four doubles the LDS form keeps of it; Chi2T: double
 // in global memory, float in LDS -- the only reader of the stored chi2 is the classification, which compares it as a float: Optimizer.cc:1018-1102)
-template <typename EdgeAt, typename Chi2T>
-__device__ __forceinline__ void pose_optimization_body(const int N, const EdgeAt edge_at, const double* __restrict__ X, Chi2T* __restrict__ chi2,
+// (point_at(i, x): the i-th map point as three doubles -- the compact LDS form keeps floats and widens them here, before any arithmetic)
+template <typename EdgeAt, typename PointAt, typename Chi2T>
+__device__ __forceinline__ void pose_optimization_body(const int N, const EdgeAt edge_at, const PointAt point_at, Chi2T* __restrict__ chi2,
                                                        uint8_t* __restrict__ out, const CameraD& cam, double* __restrict__ pose_io, int* __restrict__ inliers) {
     __shared__ double s_red[4 * kRed], s_sum[kRed];
     __shared__ Se3 s_pose, s_trial;
@@ -90,8 +91,9 @@ __device__ __forceinline__ void pose_optimization_body(const int N, const EdgeAt
             for (int i = tid; i < N; i += kPoThreads) {
                 if (out[i]) continue;  // level 1
                 const BaEdge e = edge_at(i);
-                double p[3], err[3], B[18];
-                se3_map(T, X + 3 * i, p);
+                double X[3], p[3], err[3], B[18];
+                point_at(i, X);
+                se3_map(T, X, p);
                 const bool stereo = e.ur >= 0;
                 const int dim = edge_error(p, e, cam, err);
                 double c2 = 0;
@@ -155,8 +157,9 @@ __device__ __forceinline__ void pose_optimization_body(const int N, const EdgeAt
                 for (int i = tid; i < N; i += kPoThreads) {
                     if (out[i]) continue;
                     const BaEdge e = edge_at(i);
-                    double p[3], err[3];
-                    se3_map(Tt, X + 3 * i, p);
+                    double X[3], p[3], err[3];
+                    point_at(i, X);
+                    se3_map(Tt, X, p);
                     const bool stereo = e.ur >= 0;
                     const int dim = edge_error(p, e, cam, err);
                     double c2 = 0;
@@ -213,8 +216,9 @@ __device__ __forceinline__ void pose_optimization_body(const int N, const EdgeAt
         for (int i = tid; i < N; i += kPoThreads) {
             const BaEdge e = edge_at(i);
             if (out[i]) {
-                double p[3], err[3];
-                se3_map(T, X + 3 * i, p);
+                double X[3], p[3], err[3];
+                point_at(i, X);
+                se3_map(T, X, p);
                 const int dim = edge_error(p, e, cam, err);
                 double c2 = 0;
                 for (int d = 0; d < dim; ++d) c2 += err[d] * e.info * err[d];
@@ -245,8 +249,9 @@ __global__ __launch_bounds__(kPoThreads) void k_pose_optimization(const PoseProb
                                                                  double* __restrict__ chi2_scratch, int* __restrict__ inliers) {
     const PoseProblem pr = probs[blockIdx.x];
     const BaEdge* E = edges + pr.edge_off;
-    pose_optimization_body(pr.n, [E](int i) { return E[i]; }, Xw + 3 * (size_t)pr.edge_off, chi2_scratch + pr.edge_off, outlier + pr.edge_off, cam,
-                           poses7 + 7 * (size_t)blockIdx.x, inliers + blockIdx.x);
+    const double* X = Xw + 3 * (size_t)pr.edge_off;
+    pose_optimization_body(pr.n, [E](int i) { return E[i]; }, [X](int i, double (&x)[3]) { x[0] = X[3 * i]; x[1] = X[3 * i + 1]; x[2] = X[3 * i + 2]; },
+                           chi2_scratch + pr.edge_off, outlier + pr.edge_off, cam, poses7 + 7 * (size_t)blockIdx.x, inliers + blockIdx.x);
 }
 
 // The same with the frame's correspondences staged in LDS for the whole optimisation: HBM sees each edge and map point once and one outlier
@@ -255,7 +260,15 @@ __global__ __launch_bounds__(kPoThreads) void k_pose_optimization(const PoseProb
 // Round 5: 61 bytes per correspondence instead of 73 -- observation and information as four doubles (the edge's two indices are not used here),
 // the chi2 as the float the classification compares -- so that a frame of up to 1 311 correspondences leaves room for a second workgroup on its CU
 // (the batched frames hold ~1 200: one workgroup per CU at 73 bytes, i.e. two rounds of 256 for 512 frames).
+// The compact form: 33 bytes per correspondence -- map point and observation (u, v, ur, info) as seven FLOATS, field-major ([7][cap]: the lanes of a
+// wavefront read neighbouring words), the chi2 float and the outlier byte.  Every read widens to double before any arithmetic, and the form
+// is only launched when every one of the seven values of every correspondence is a float's value ((double)(float)x == x): the tracking
+// callers widen floats themselves (k_track_edges_last / _local), the public entry asks k_pose_inputs_float_exact.  So the operands, the
+// operations and their order are the 61-byte form's and the results are the same bits, while a frame of 1 216 correspondences holds 40 KB
+// of its CU's 160 KB through the four rounds instead of 74 KB: what it leaves is room for the LDS kernels of the other stages beside it.
 constexpr int kPoLdsPerEdge = 4 * sizeof(double) + 3 * sizeof(double) + sizeof(float) + 1;  // 61 B
+constexpr int kPoLdsPerEdgeCompact = 7 * sizeof(float) + sizeof(float) + 1;                 // 33 B
+template <bool kCompact>
 __global__ __launch_bounds__(kPoThreads) void k_pose_optimization_lds(const PoseProblem* __restrict__ probs, const double* __restrict__ Xw,
                                                                      const BaEdge* __restrict__ edges, CameraD cam,
                                                                      double* __restrict__ poses7, uint8_t* __restrict__ outlier,
@@ -263,39 +276,79 @@ __global__ __launch_bounds__(kPoThreads) void k_pose_optimization_lds(const Pose
     extern __shared__ double s_po[];
     const PoseProblem pr = probs[blockIdx.x];
     const int N = pr.n, tid = threadIdx.x;
-    double* const s_X = s_po;                                  // [cap][3]
-    double* const s_E = s_X + 3 * (size_t)cap;                 // [cap][4]: u, v, ur, info
-    float* const s_chi2 = reinterpret_cast<float*>(s_E + 4 * (size_t)cap);  // [cap]
-    uint8_t* const s_out = reinterpret_cast<uint8_t*>(s_chi2 + cap);
-    {
-        const double* gx = Xw + 3 * (size_t)pr.edge_off;
+    const double* gx = Xw + 3 * (size_t)pr.edge_off;
+    const double* ge = reinterpret_cast<const double*>(edges + pr.edge_off);   // 5 doubles per edge: (point, pose), u, v, ur, info
+    uint8_t* s_out;
+    if constexpr (kCompact) {
+        float* const s_F = reinterpret_cast<float*>(s_po);     // [7][cap]: X, Y, Z, u, v, ur, info
+        float* const s_chi2 = s_F + 7 * (size_t)cap;           // [cap]
+        s_out = reinterpret_cast<uint8_t*>(s_chi2 + cap);
+        for (int i = tid; i < N; i += kPoThreads) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s_F[k * cap + i] = (float)gx[3 * i + k];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s_F[(3 + k) * cap + i] = (float)ge[5 * i + 1 + k];
+        }
+        __syncthreads();
+        pose_optimization_body(
+            N, [s_F, cap](int i) { return BaEdge{0, 0, (double)s_F[3 * cap + i], (double)s_F[4 * cap + i], (double)s_F[5 * cap + i], (double)s_F[6 * cap + i]}; },
+            [s_F, cap](int i, double (&x)[3]) { x[0] = (double)s_F[i]; x[1] = (double)s_F[cap + i]; x[2] = (double)s_F[2 * cap + i]; }, s_chi2, s_out, cam,
+            poses7 + 7 * (size_t)blockIdx.x, inliers + blockIdx.x);
+    } else {
+        double* const s_X = s_po;                                  // [cap][3]
+        double* const s_E = s_X + 3 * (size_t)cap;                 // [cap][4]: u, v, ur, info
+        float* const s_chi2 = reinterpret_cast<float*>(s_E + 4 * (size_t)cap);  // [cap]
+        s_out = reinterpret_cast<uint8_t*>(s_chi2 + cap);
         for (int k = tid; k < 3 * N; k += kPoThreads) s_X[k] = gx[k];
-        const double* ge = reinterpret_cast<const double*>(edges + pr.edge_off);   // 5 doubles per edge: (point, pose), u, v, ur, info
         for (int k = tid; k < 4 * N; k += kPoThreads) s_E[k] = ge[5 * (k >> 2) + 1 + (k & 3)];
+        __syncthreads();
+        pose_optimization_body(N, [s_E](int i) { return BaEdge{0, 0, s_E[4 * i], s_E[4 * i + 1], s_E[4 * i + 2], s_E[4 * i + 3]}; },
+                               [s_X](int i, double (&x)[3]) { x[0] = s_X[3 * i]; x[1] = s_X[3 * i + 1]; x[2] = s_X[3 * i + 2]; }, s_chi2, s_out, cam,
+                               poses7 + 7 * (size_t)blockIdx.x, inliers + blockIdx.x);
     }
-    __syncthreads();
-    pose_optimization_body(N, [s_E](int i) { return BaEdge{0, 0, s_E[4 * i], s_E[4 * i + 1], s_E[4 * i + 2], s_E[4 * i + 3]}; }, s_X, s_chi2, s_out, cam,
-                           poses7 + 7 * (size_t)blockIdx.x, inliers + blockIdx.x);
     __syncthreads();
     uint8_t* out = outlier + pr.edge_off;
     for (int i = tid; i < N; i += kPoThreads) out[i] = s_out[i];
 }
 
+// *exact (set to 1 by the caller before) becomes 0 when a map point coordinate or one of u, v, ur, info of the n staged correspondences is
+// not a float's value (a NaN is not: it compares unequal to itself)
+__global__ __launch_bounds__(256) void k_pose_inputs_float_exact(const double* __restrict__ Xw, const BaEdge* __restrict__ edges, int n, int* __restrict__ exact) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double* e = reinterpret_cast<const double*>(edges + i);
+    bool ok = true;
+    for (int k = 0; k < 3; ++k) ok = ok && (double)(float)Xw[3 * (size_t)i + k] == Xw[3 * (size_t)i + k];
+    for (int k = 1; k < 5; ++k) ok = ok && (double)(float)e[k] == e[k];
+    if (!ok) *exact = 0;
+}
+void launch_pose_inputs_float_exact(const double* Xw, const BaEdge* edges, int n, int* exact, hipStream_t st) {
+    if (n > 0) TC2LI_LAUNCH(k_pose_inputs_float_exact, dim3((n + 255) / 256), dim3(256), 0, st, Xw, edges, n, exact);
+}
+
 // what the most recent launch_pose_optimization of this process launched (tc2li_pose_optimization_limits): 0 nothing yet, 1 the LDS form, 2 the
-// global-memory form
+// global-memory form, 3 the compact LDS form after the device-side check of a public entry.  A tracking batch's launch reports 1 in either
+// layout: "staged in LDS" is what the value has meant to its callers since it was added, and there the layout is not a property of the inputs.
 static std::atomic<int> g_po_last_form{0};
 
 void launch_pose_optimization(const PoseProblem* probs, int nprobs, const double* Xw, const BaEdge* edges, const CameraD& cam,
-                              double* poses7, uint8_t* outlier, double* chi2_scratch, int* inliers, int max_edges, hipStream_t st) {
+                              double* poses7, uint8_t* outlier, double* chi2_scratch, int* inliers, int max_edges, hipStream_t st, PoseFloats floats) {
     if (nprobs <= 0) return;
-    // the correspondences of a frame in LDS when they fit (2048: 125 KB).  The block is sized from the batch's largest frame, not in two
-    // classes: a workgroup lives for the whole optimisation (milliseconds), and what it does not take of its CU's 160 KB the other stages'
-    // kernels can (1200 correspondences: 73 KB; <= 1311: two workgroups per CU).  TC2LI_PO_LDS_CLASSES=1: the two classes (A/B).
+    // the correspondences of a frame in LDS when they fit (2048: 125 KB, 66 KB compact).  The block is sized from the batch's largest frame, not
+    // in two classes: a workgroup lives for the whole optimisation (milliseconds), and what it does not take of its CU's 160 KB the other stages'
+    // kernels can (1200 correspondences: 73 KB, 40 KB compact).  TC2LI_PO_LDS_CLASSES=1: the two classes (A/B).
+    // TC2LI_PO_COMPACT=0 (read per call): the 61-byte form also where the compact one would do (A/B runs, the tests).
     static const bool kClasses = getenv("TC2LI_PO_LDS_CLASSES") && atoi(getenv("TC2LI_PO_LDS_CLASSES")) != 0;
+    const char* const compact_env = getenv("TC2LI_PO_COMPACT");
+    const bool compact = floats != PoseFloats::kUnknown && (compact_env ? atoi(compact_env) != 0 : true);
     const int cap = kClasses ? (max_edges <= kPoLdsMaxEdges / 2 ? kPoLdsMaxEdges / 2 : kPoLdsMaxEdges)
                              : std::max(kPoLdsGranule, (max_edges + kPoLdsGranule - 1) / kPoLdsGranule * kPoLdsGranule);
-    if (max_edges <= kPoLdsMaxEdges && ensure_dynamic_lds((const void*)k_pose_optimization_lds, kPoLdsMaxEdges * kPoLdsPerEdge + 64)) {
-        TC2LI_LAUNCH(k_pose_optimization_lds, dim3(nprobs), dim3(kPoThreads), (size_t)cap * kPoLdsPerEdge + 64, st, probs, Xw, edges, cam, poses7, outlier,
+    if (compact && max_edges <= kPoLdsMaxEdges && ensure_dynamic_lds((const void*)k_pose_optimization_lds<true>, kPoLdsMaxEdges * kPoLdsPerEdgeCompact + 64)) {
+        TC2LI_LAUNCH(k_pose_optimization_lds<true>, dim3(nprobs), dim3(kPoThreads), (size_t)cap * kPoLdsPerEdgeCompact + 64, st, probs, Xw, edges, cam, poses7,
+                     outlier, inliers, cap);
+        g_po_last_form.store(floats == PoseFloats::kChecked ? 3 : 1, std::memory_order_relaxed);
+    } else if (max_edges <= kPoLdsMaxEdges && ensure_dynamic_lds((const void*)k_pose_optimization_lds<false>, kPoLdsMaxEdges * kPoLdsPerEdge + 64)) {
+        TC2LI_LAUNCH(k_pose_optimization_lds<false>, dim3(nprobs), dim3(kPoThreads), (size_t)cap * kPoLdsPerEdge + 64, st, probs, Xw, edges, cam, poses7, outlier,
                      inliers, cap);
         g_po_last_form.store(1, std::memory_order_relaxed);
     } else {

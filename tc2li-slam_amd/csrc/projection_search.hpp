@@ -98,11 +98,11 @@ struct PoseTail {
         edge_kp = work.take<int32_t>(n_edges); poses = work.take<double>(7 * n_frames); outlier = work.take<uint8_t>(n_edges);
         chi2 = work.take<double>(n_edges); inliers = work.take<int32_t>(n_frames);
     }
-    void launch(const PackedTransfer& T, int n_frames, const tc2li_camera* cam, int max_edges, hipStream_t st) const {
+    void launch(const PackedTransfer& T, int n_frames, const tc2li_camera* cam, int max_edges, hipStream_t st, PoseFloats floats = PoseFloats::kUnknown) const {
         CameraD cd;
         memcpy(&cd, cam, sizeof(cd));
         launch_pose_optimization(T.dev_work(probs), n_frames, T.dev_work(Xw), T.dev_work(edges), cd, T.dev_work(poses), T.dev_work(outlier),
-                                 T.dev_work(chi2), T.dev_work(inliers), max_edges, st);
+                                 T.dev_work(chi2), T.dev_work(inliers), max_edges, st, floats);
     }
 };
 

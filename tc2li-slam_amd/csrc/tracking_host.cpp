@@ -203,7 +203,7 @@ extern "C" int tc2li_track_motion_model_batch(tc2li_orb* o, int n_frames, const 
     auto W = [&](auto t) { return T.dev_work(t); };
     launch_track_edges_last(d_frames, n_frames, C, o->d_mkeys.p, d_ur, S.d_match.p, S.d_nmatch.p, A.Xw, W(t_of_key), W(pose.probs), W(pose.edges), W(pose.Xw),
                             W(pose.edge_kp), W(pose.poses), st);
-    pose.launch(T, n_frames, cam, capacity, st);
+    pose.launch(T, n_frames, cam, capacity, st, PoseFloats::kByConstruction);  // (the edge kernel widened floats)
     launch_track_finish_last(d_frames, n_frames, capacity, S.d_nmatch.p, W(pose.probs), W(pose.outlier), W(pose.edge_kp), W(pose.inliers), W(t_of_key),
                              W(pose.poses), W(t_ninl), st);
     TC2LI_HIP_CHECK(hipGetLastError());
@@ -324,7 +324,7 @@ static int track_local_map_impl(tc2li_orb* o, int n_frames, const tc2li_keypoint
         if (kTiming) fprintf(stderr, "search-local-points timing ms: stage %.3f queries %.3f search %.3f results %.3f\n", tm[0], tm[1], tm[2], tm[3]);
         return n_frames;
     }
-    pose.launch(T, n_frames, cam, capacity, st);
+    pose.launch(T, n_frames, cam, capacity, st, PoseFloats::kByConstruction);  // (the edge kernel widened floats)
     launch_track_finish_local(d_frames, n_frames, capacity, W(pose.probs), W(pose.outlier), W(pose.edge_kp), d_held, W(t_of_key), W(t_outlier_key), W(t_ninl), st);
     TC2LI_HIP_CHECK(hipGetLastError());
     TC2LI_HIP_CHECK(hipMemcpyAsync(local_of_keypoint, W(t_of_key), ne * sizeof(int32_t), hipMemcpyDeviceToHost, st));
