@@ -2327,6 +2327,97 @@ int tc2li_map_graph_limits(int32_t* out, int capacity);
  * slot is only required to be >= 0, an observation index to be >= -1); on an error nothing is written.  Needs no device. */
 int tc2li_host_map_graph_apply(const tc2li_map_graph_tables* tables_in, const tc2li_map_graph_edit* edits, int n_edits, const double* values,
                                int n_values, tc2li_map_graph_tables* tables_out, const int32_t* capacities, int32_t* counts);
+/* ---- the covisibility graph on the resident map graph (SF/src/KeyFrame.cc:391-486 UpdateConnections, :201-238 AddConnection and
+ * UpdateBestCovisibles, :600-603 and :617-618 the covisibility part of SetBadFlag, :699-713 EraseConnection) ------------------------------
+ * mConnectedKeyFrameWeights and mvpOrderedConnectedKeyFrames / mvOrderedWeights of every keyframe row as two CSRs per sequence, resident
+ * beside the tables above and updated on the device from them:
+ *   weights  conn_offsets [n_keyframes + 1], conn_kf, conn_weight: a row ascends strictly by keyframe row, the map order of
+ *            tc2li_connections_problem;
+ *   ordered  ord_offsets [n_keyframes + 1], ord_kf, ord_weight: the lists as the reference last wrote them.  They are stored, not derived:
+ *            the reference leaves a list stale when AddConnection returns at :209-210, and leaves bad keyframes out of it at :229.
+ * The spanning tree (mpParent, mspChildrens, mbFirstConnection) stays with the caller, as for tc2li_update_connections_batch.
+ * Keyframe rows that ADD_KEYFRAME appends after the connections were set have empty rows in both CSRs, with no further call;
+ * tc2li_map_graph_set_batch on a sequence empties its connections.  Until tc2li_map_graph_connections_reserve has been called every entry
+ * of this section returns TC2LI_ERR_INVALID and the graph behaves as without it. */
+typedef struct tc2li_map_graph_connections {
+    int32_t* conn_offsets;
+    int32_t* conn_kf;
+    int32_t* conn_weight;
+    int32_t* ord_offsets;
+    int32_t* ord_kf;
+    int32_t* ord_weight;
+    int32_t n_keyframes, pad_;
+} tc2li_map_graph_connections;
+enum tc2li_map_graph_connections_info_field {
+    TC2LI_MAP_GRAPH_CONNECTIONS_WEIGHT_ENTRIES = 0,   /* entries of conn_kf */
+    TC2LI_MAP_GRAPH_CONNECTIONS_ORDERED_ENTRIES = 1,  /* entries of ord_kf */
+    TC2LI_MAP_GRAPH_CONNECTIONS_UPDATES = 2,          /* update and erase calls that named the sequence and succeeded, since its last set */
+    TC2LI_MAP_GRAPH_CONNECTIONS_UPDATE_BYTES = 3,     /* host-to-device bytes of the last update or erase that named the sequence, its share */
+    TC2LI_MAP_GRAPH_CONNECTIONS_INFO_FIELDS = 4
+};
+/* Once per graph: allocates both CSRs (two generations each, see tc2li_map_graph_update_connections_batch) with room for
+ * entries_per_sequence entries per sequence and CSR.  TC2LI_ERR_INVALID for a second call, a capacity below 1 or tables of all sequences
+ * beyond 2^31 entries. */
+int tc2li_map_graph_connections_reserve(tc2li_map_graph_handle* graph, int entries_per_sequence);
+/* The full connection state of n sequences (none twice; each must have been set by tc2li_map_graph_set_batch).  TC2LI_ERR_INVALID, the
+ * graph unchanged: n_keyframes negative or beyond the sequence's resident keyframe rows (rows beyond n_keyframes are empty); offsets that
+ * do not ascend from 0; a keyframe out of [0, n_keyframes); a weight row that does not ascend strictly; an ordered row that names a
+ * keyframe twice; a row of either CSR that names its own keyframe.  TC2LI_ERR_CAPACITY, the graph unchanged: a CSR beyond the reserve.
+ * One upload per call; resident when the call returns.  Returns n. */
+int tc2li_map_graph_set_connections_batch(tc2li_map_graph_handle* graph, const int32_t* sequences, const tc2li_map_graph_connections* tables, int n,
+                                          void* stream);
+/* The resident connections of one sequence as host arrays (for tests and tools), n_keyframes = the sequence's resident keyframe rows.
+ * capacities [2]: weight entries, ordered entries of the caller's arrays (the offset arrays hold the keyframe rows + 1); counts [2] is
+ * always written; TC2LI_ERR_CAPACITY when an array is too small. */
+int tc2li_map_graph_download_connections(tc2li_map_graph_handle* graph, int sequence, tc2li_map_graph_connections* out, const int32_t* capacities,
+                                         int32_t* counts);
+/* out [TC2LI_MAP_GRAPH_CONNECTIONS_INFO_FIELDS] of one sequence; returns the number written. */
+int tc2li_map_graph_connections_info(tc2li_map_graph_handle* graph, int sequence, int64_t* out, int capacity);
+/* out[0] = bytes of the per-sequence record that an update or an erase sends to the device -- all it sends; out[1] = bytes per sequence
+ * that come back beside the counts block (the status words).  Returns 2.  Needs no device. */
+int tc2li_map_graph_connections_limits(int32_t* out, int capacity);
+/* One KeyFrame::UpdateConnections (:391-486) per named sequence (none twice: TC2LI_ERR_INVALID), on the resident tables and into them.
+ * The inputs of tc2li_connections_problem come from the graph: kf_flags are the graph's (bits 0 and 1 mean the same), slot_point is the
+ * slot row of current_rows[i], point_bad is bit 0 of point_flags, the observation rows are the resident ones, the weight rows the resident
+ * weights, is_init_kf is kf_id[current] == init_kf_id[i]; first_connection [n] is mbFirstConnection.  The rules are those written under
+ * tc2li_update_connections_batch, line for line -- votes per slot, the empty-counter return, th = 15 with the lone best keyframe
+ * otherwise (the lowest row among equals), the whole counter as the weight row, equal weights ordered by row descending, AddConnection's
+ * early return leaving a neighbour's ordered list as it is -- and the same device functions compute them.
+ *   counts_out [n][TC2LI_CONNECTIONS_COUNTS]: that entry's counts block, PARENT included; the caller still does AddChild and clears
+ *   mbFirstConnection.
+ *   Status UPDATED: current's weight row := the counter; current's ordered row := the new list; every touched keyframe's weight row gets
+ *   (current, weight) inserted at its place or overwritten; every touched keyframe with changed = 1 gets its ordered row replaced by the
+ *   UpdateBestCovisibles result.  Status UNCHANGED: nothing is written.
+ *   TC2LI_ERR_CAPACITY when a CSR of some sequence would pass the reserve: NO sequence is changed, and of every sequence's counts block
+ *   entries 6 and 7 (0 otherwise) hold the weight and the ordered entries its CSRs would hold.  Both CSRs have two generations per
+ *   sequence: the kernels read the current one and write the other whole, and the host makes the written one current only after every
+ *   sequence of the call has reported that it fitted.
+ *   TC2LI_ERR_INVALID before any launch: no reserve, a sequence out of range, never set or named twice, a current row out of range, more
+ *   than 65535 sequences.
+ * Crossing the bus: host to device one record per sequence (tc2li_map_graph_connections_limits' out[0] bytes) and nothing else; device to
+ * host the counts blocks and out[1] bytes of status per sequence.  No table, list or weight row crosses in either direction.  Three
+ * kernel launches whatever n.  The results are resident and counts_out is written when the call returns.  Returns n. */
+int tc2li_map_graph_update_connections_batch(tc2li_map_graph_handle* graph, const int32_t* sequences, const int32_t* current_rows,
+                                             const uint8_t* first_connection, const int64_t* init_kf_id, int n, int32_t* counts_out, void* stream);
+/* What KeyFrame::SetBadFlag does to covisibility (:600-603, :617-618) for keyframe rows[i] of sequence sequences[i] (none twice): for
+ * every keyframe k of the row's weight row, the row's entry is removed from k's weight row if it is there (EraseConnection, :699-713), and
+ * where it was, k's ordered row is replaced by UpdateBestCovisibles (:216-238) under the resident kf_flags as they are at the call -- the
+ * reference sets mbBad afterwards, at :685; a neighbour that did not hold the entry keeps its ordered row.  Then both rows of the keyframe
+ * itself are emptied.  Flags, observations, slots and the repair of the spanning tree are not part of it: the caller sends those as
+ * edits.  Bus contract and atomicity as tc2li_map_graph_update_connections_batch.  Returns n. */
+int tc2li_map_graph_erase_connections_batch(tc2li_map_graph_handle* graph, const int32_t* sequences, const int32_t* rows, int n, void* stream);
+/* The host twins: plain sequential C++ over host copies of the graph tables and the connection tables; they define the result and need
+ * no device.  in->n_keyframes may be below tables->n_keyframes (the rows beyond are empty); out has tables->n_keyframes rows, arrays with
+ * room for capacities [2] (weight entries, ordered entries) and tables->n_keyframes + 1 offsets.  sizes [2] receives the entries of both
+ * CSRs after the call, also with TC2LI_ERR_CAPACITY, when nothing else is written.  The update writes counts [TC2LI_CONNECTIONS_COUNTS]
+ * and returns its status; with UNCHANGED out is a copy of in.  TC2LI_ERR_INVALID for tables or connections that
+ * tc2li_map_graph_set_batch (the store apart) or tc2li_map_graph_set_connections_batch would refuse, and a row out of range. */
+int tc2li_host_map_graph_update_connections(const tc2li_map_graph_tables* tables, const tc2li_map_graph_connections* in, int32_t current,
+                                            int first_connection, int64_t init_kf_id, tc2li_map_graph_connections* out, const int32_t* capacities,
+                                            int32_t* sizes, int32_t* counts);
+int tc2li_host_map_graph_erase_connections(const tc2li_map_graph_tables* tables, const tc2li_map_graph_connections* in, int32_t row,
+                                           tc2li_map_graph_connections* out, const int32_t* capacities, int32_t* sizes);
+
 /* tc2li_ba_window_batch with the tables of problem p taken from sequence sequences[p] of the graph.
  * NOTE: of a problem only current, cov_kf / n_cov, init_kf_id, the outputs and the capacities are read.  ITS TABLE POINTERS, n_keyframes
  * AND n_points ARE IGNORED WITHOUT AN ERROR: a caller who also passes tables gets the graph's, never its own, however stale they are.
@@ -2342,6 +2433,17 @@ int tc2li_ba_window_graph_batch(tc2li_keyframe_store* store, tc2li_map_graph_han
 int tc2li_ba_window_solve_graph_batch(tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences,
                                       const tc2li_ba_window_solve_problem* problems, int n_problems, const float* inv_level_sigma2, int n_levels,
                                       const tc2li_camera* cam, int group, int32_t* results);
+
+/* tc2li_ba_window_graph_batch with the neighbour list of every problem taken from the graph as well: GetVectorCovisibleKeyFrames()
+ * (SF/src/OptimizerWithLidar.cc:69, SF/src/Optimizer.cc:1127) is the resident ordered row of `current` (tc2li_map_graph_connections), in
+ * its order -- a keyframe of it that is bad or of another map is marked local and not optimised (:73-74), as one of an uploaded list is.
+ * cov_kf / n_cov of every problem must be NULL / 0, and the connections must have been reserved: TC2LI_ERR_INVALID otherwise.  Every
+ * output, count, status and error is bit for bit that of tc2li_ba_window_graph_batch given cov_kf = that row as
+ * tc2li_map_graph_download_connections returns it: the same kernels, which read the list through the sequence's ordered CSR in place of an
+ * uploaded array.  GATHER_BYTES is smaller by exactly the 4 * n_cov bytes no longer sent: the problem records and the level table are all
+ * that goes up. */
+int tc2li_ba_window_graph_cov_batch(tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences,
+                                    const tc2li_ba_window_problem* problems, int n_problems, const float* inv_level_sigma2, int n_levels, void* stream);
 
 /* ---- local mapping: the closing step of LocalLVBundleAdjustment, "Recover optimized data" (SF/src/OptimizerWithLidar.cc:455-485), on the
  * resident graph -----------------------------------------------------------------------------------------------------------------------
@@ -2398,6 +2500,14 @@ int tc2li_host_ba_window_commit_log(const tc2li_map_graph_tables* tables, const 
 int tc2li_ba_window_solve_graph_commit_batch(tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences,
                                              const tc2li_ba_window_solve_problem* problems, int n_problems, const float* inv_level_sigma2,
                                              int n_levels, const tc2li_camera* cam, int group, uint32_t flags, int32_t* results);
+
+/* tc2li_ba_window_solve_graph_commit_batch with the neighbour lists taken from the graph as tc2li_ba_window_graph_cov_batch takes them
+ * (cov_kf / n_cov of every window NULL / 0).  Results, outputs and the graph afterwards are bit for bit those of
+ * tc2li_ba_window_solve_graph_commit_batch given cov_kf = the resident ordered row of every window's current keyframe.  The commit writes
+ * poses, positions, slots and observations; the connections are not touched by it. */
+int tc2li_ba_window_solve_graph_commit_cov_batch(tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences,
+                                                 const tc2li_ba_window_solve_problem* problems, int n_problems, const float* inv_level_sigma2,
+                                                 int n_levels, const tc2li_camera* cam, int group, uint32_t flags, int32_t* results);
 
 /* ---- local mapping: the window of the inertial local BA (OptimizerWithLidar::LocalLVIBA, SF/src/OptimizerWithLidar.cc:489-607 the gather,
  * :632-727 the vertices and the keyframes of the LiDAR edge, :729-800 the inertial links, :832-969 the point vertices and edges, :985-1045

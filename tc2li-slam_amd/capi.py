@@ -3881,6 +3881,91 @@ def host_map_graph_apply(tables, edits, values, capacities):
     return _cut_map_graph_tables(a, counts)
 
 
+_MAP_GRAPH_CONNECTIONS_ARRAYS = ("conn_offsets", "conn_kf", "conn_weight", "ord_offsets", "ord_kf", "ord_weight")
+_MAP_GRAPH_CONNECTIONS_INFO = ("weight_entries", "ordered_entries", "updates", "update_bytes")
+
+
+class MapGraphConnections(C.Structure):
+    """tc2li_map_graph_connections"""
+    _fields_ = [(k, C.c_void_p) for k in _MAP_GRAPH_CONNECTIONS_ARRAYS] + [("n_keyframes", C.c_int32), ("pad_", C.c_int32)]
+
+
+def _pack_map_graph_connections(t, into):
+    a = {k: np.ascontiguousarray(t[k], np.int32).reshape(-1) for k in _MAP_GRAPH_CONNECTIONS_ARRAYS}
+    nk = len(a["conn_offsets"]) - 1
+    if nk < 0 or len(a["ord_offsets"]) != nk + 1:
+        raise ValueError("conn_offsets and ord_offsets have one entry per keyframe row and one more")
+    if min(len(a["conn_kf"]), len(a["conn_weight"])) < int(a["conn_offsets"][-1]) or min(len(a["ord_kf"]), len(a["ord_weight"])) < int(a["ord_offsets"][-1]):
+        raise ValueError("connection arrays are shorter than their offsets say")
+    for k, v in a.items():
+        setattr(into, k, v.ctypes.data)
+    into.n_keyframes = nk
+    return a
+
+
+def _room_for_map_graph_connections(n_keyframes, capacities, fill=0):
+    t, a = MapGraphConnections(), {}
+    for k in _MAP_GRAPH_CONNECTIONS_ARRAYS:
+        n = int(n_keyframes) + 1 if k.endswith("offsets") else int(capacities[0 if k.startswith("conn") else 1])
+        a[k] = np.full(n, fill, np.int32)
+        setattr(t, k, a[k].ctypes.data)
+    return t, a
+
+
+def _cut_map_graph_connections(a, n_keyframes, sizes):
+    nw, no = int(sizes[0]), int(sizes[1])
+    return dict(conn_offsets=a["conn_offsets"][:n_keyframes + 1], conn_kf=a["conn_kf"][:nw], conn_weight=a["conn_weight"][:nw],
+                ord_offsets=a["ord_offsets"][:n_keyframes + 1], ord_kf=a["ord_kf"][:no], ord_weight=a["ord_weight"][:no])
+
+
+def map_graph_connections_limits():
+    """tc2li_map_graph_connections_limits -> {record_bytes, status_bytes}: what an update or an erase of the resident connections moves per
+    sequence, host to device and (beside the counts block) device to host."""
+    out = (C.c_int32 * 2)()
+    f = lib().tc2li_map_graph_connections_limits
+    f.argtypes = [C.c_void_p, C.c_int]
+    _check(f(out, 2))
+    return dict(record_bytes=int(out[0]), status_bytes=int(out[1]))
+
+
+def _host_map_graph_connections(tables, connections, capacities, call):
+    tin, cin = MapGraphTables(), MapGraphConnections()
+    keep = (_pack_map_graph_tables(tables, tin), _pack_map_graph_connections(connections, cin))
+    nk = int(tin.n_keyframes)
+    caps = np.ascontiguousarray(capacities if capacities is not None else
+                                [len(keep[1]["conn_kf"]) + 2 * nk + 2, len(keep[1]["ord_kf"]) + len(keep[1]["conn_kf"]) + 2 * nk + 2], np.int32)
+    cout, a = _room_for_map_graph_connections(nk, caps)
+    sizes = np.zeros(2, np.int32)
+    try:
+        rc = call(C.addressof(tin), C.addressof(cin), C.addressof(cout), caps.ctypes.data, sizes.ctypes.data)
+        _check(rc)
+    except Tc2liError as e:
+        e.sizes = sizes
+        raise
+    del keep
+    return rc, _cut_map_graph_connections(a, nk, sizes)
+
+
+def host_map_graph_update_connections(tables, connections, current, first_connection=0, init_kf_id=-1, capacities=None):
+    """tc2li_host_map_graph_update_connections, the host twin of ResidentMapGraph.update_connections_batch for one sequence: tables as for
+    set_batch, connections as for set_connections_batch (its rows may end before the tables' keyframe rows) -> (counts [8], the
+    connections after the call).  capacities: weight and ordered entries of the result; by default what always suffices.  A refusal for
+    want of room carries the sizes needed as the exception's ``sizes``."""
+    counts = np.zeros(8, np.int32)
+    f = lib().tc2li_host_map_graph_update_connections
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    _, out = _host_map_graph_connections(tables, connections, capacities, lambda t, ci, co, caps, sizes: f(
+        t, ci, int(current), int(bool(first_connection)), int(init_kf_id), co, caps, sizes, counts.ctypes.data))
+    return counts, out
+
+
+def host_map_graph_erase_connections(tables, connections, row, capacities=None):
+    """tc2li_host_map_graph_erase_connections, the host twin of ResidentMapGraph.erase_connections_batch -> the connections after it."""
+    f = lib().tc2li_host_map_graph_erase_connections
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    return _host_map_graph_connections(tables, connections, capacities, lambda t, ci, co, caps, sizes: f(t, ci, int(row), co, caps, sizes))[1]
+
+
 class ResidentMapGraph:
     """``tc2li_map_graph_*``: the input half of the local-BA window problems of n_sequences sequences, resident on the device and edited by
     logs.  capacities: per sequence keyframe rows, slot entries, point rows, observation entries.  Bound to one :class:`KeyframeStore`."""
@@ -3941,6 +4026,70 @@ class ResidentMapGraph:
         _check(f(self._handle(), int(sequence), out, len(_MAP_GRAPH_INFO)))
         return dict(zip(_MAP_GRAPH_INFO, [int(v) for v in out]))
 
+    # ---- the covisibility graph (tc2li_map_graph_connections_*) ----
+    def connections_reserve(self, entries_per_sequence):
+        """tc2li_map_graph_connections_reserve: once per graph, room for that many entries per sequence in the weight and the ordered CSR."""
+        f = lib().tc2li_map_graph_connections_reserve
+        f.argtypes = [C.c_void_p, C.c_int]
+        _check(f(self._handle(), int(entries_per_sequence)))
+
+    def set_connections_batch(self, sequences, tables, stream=0):
+        """tc2li_map_graph_set_connections_batch.  tables: dicts with conn_offsets, conn_kf, conn_weight, ord_offsets, ord_kf, ord_weight."""
+        seq = np.ascontiguousarray(sequences, np.int32).reshape(-1)
+        arr = (MapGraphConnections * max(len(tables), 1))()
+        keep = [_pack_map_graph_connections(t, arr[i]) for i, t in enumerate(tables)]
+        f = lib().tc2li_map_graph_set_connections_batch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _check(f(self._handle(), seq.ctypes.data, C.addressof(arr), len(tables), C.c_void_p(stream)))
+        del keep
+
+    def download_connections(self, sequence, fill=0):
+        """tc2li_map_graph_download_connections -> the resident connections of the sequence as a dict of arrays"""
+        i, c = self.info(sequence), self.connections_info(sequence)
+        caps = np.array([c["weight_entries"], c["ordered_entries"]], np.int32)
+        t, a = _room_for_map_graph_connections(i["n_keyframes"], caps, fill)
+        counts = np.zeros(2, np.int32)
+        f = lib().tc2li_map_graph_download_connections
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _check(f(self._handle(), int(sequence), C.addressof(t), caps.ctypes.data, counts.ctypes.data))
+        return _cut_map_graph_connections(a, int(t.n_keyframes), counts)
+
+    def connections_info(self, sequence):
+        """tc2li_map_graph_connections_info -> {weight_entries, ordered_entries, updates, update_bytes}"""
+        out = (C.c_int64 * len(_MAP_GRAPH_CONNECTIONS_INFO))()
+        f = lib().tc2li_map_graph_connections_info
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        _check(f(self._handle(), int(sequence), out, len(_MAP_GRAPH_CONNECTIONS_INFO)))
+        return dict(zip(_MAP_GRAPH_CONNECTIONS_INFO, [int(v) for v in out]))
+
+    def update_connections_batch(self, sequences, current_rows, first_connection, init_kf_id, stream=0, counts_into=None):
+        """tc2li_map_graph_update_connections_batch: one KeyFrame::UpdateConnections per named sequence on the resident tables ->
+        counts [n, 8] (status, n_counter, n_ordered, n_changed, n_changed_entries, parent, 0, 0).  counts_into: an int32 [n, 8] array that
+        receives the blocks also when the call is refused for want of room (entries 6 and 7 are then the sizes needed)."""
+        seq = np.ascontiguousarray(sequences, np.int32).reshape(-1)
+        cur = np.ascontiguousarray(current_rows, np.int32).reshape(-1)
+        first = np.ascontiguousarray(first_connection, np.uint8).reshape(-1)
+        init = np.ascontiguousarray(init_kf_id, np.int64).reshape(-1)
+        if not len(seq) == len(cur) == len(first) == len(init):
+            raise ValueError("one current row, first_connection and init_kf_id per sequence")
+        counts = np.zeros((max(len(seq), 1), 8), np.int32) if counts_into is None else counts_into
+        if counts.dtype != np.int32 or counts.size < 8 * len(seq) or not counts.flags["C_CONTIGUOUS"]:
+            raise ValueError("counts_into: a contiguous int32 array of [n, 8]")
+        f = lib().tc2li_map_graph_update_connections_batch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _check(f(self._handle(), seq.ctypes.data, cur.ctypes.data, first.ctypes.data, init.ctypes.data, len(seq), counts.ctypes.data, C.c_void_p(stream)))
+        return counts.reshape(-1, 8)[:len(seq)]
+
+    def erase_connections_batch(self, sequences, rows, stream=0):
+        """tc2li_map_graph_erase_connections_batch: what KeyFrame::SetBadFlag does to covisibility, for one keyframe row per named sequence."""
+        seq = np.ascontiguousarray(sequences, np.int32).reshape(-1)
+        row = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        if len(seq) != len(row):
+            raise ValueError("one row per sequence")
+        f = lib().tc2li_map_graph_erase_connections_batch
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _check(f(self._handle(), seq.ctypes.data, row.ctypes.data, len(seq), C.c_void_p(stream)))
+
     def close(self):
         if self._h:
             f = lib().tc2li_map_graph_destroy
@@ -3969,18 +4118,32 @@ def _without_tables(window):
     window.n_keyframes = window.n_points = 0
 
 
-def ba_window_graph_batch(problems, sequences, inv_level_sigma2, store, graph, stream=0, raw=False, fill=0):
+def _without_cov(window):
+    """... and as the entries that read the neighbour list from the graph's ordered connections take it: no cov_kf either"""
+    window.cov_kf = None
+    window.n_cov = 0
+
+
+def ba_window_graph_cov_batch(problems, sequences, inv_level_sigma2, store, graph, stream=0, raw=False, fill=0, keep_cov=False):
+    """tc2li_ba_window_graph_cov_batch: ba_window_graph_batch with the neighbour list of problem i read from the resident ordered row of its
+    current keyframe; the problems' cov_kf does not reach the library (keep_cov=True passes it on, to see it refused)."""
+    return ba_window_graph_batch(problems, sequences, inv_level_sigma2, store, graph, stream, raw, fill, _cov=1 if keep_cov else 2)
+
+
+def ba_window_graph_batch(problems, sequences, inv_level_sigma2, store, graph, stream=0, raw=False, fill=0, _cov=0):
     """tc2li_ba_window_graph_batch: ba_window_batch with the tables of problem i taken from sequence sequences[i] of `graph` (a
     :class:`ResidentMapGraph`).  problems: the dicts of ba_window_batch; of them current, cov_kf, init_kf_id and the capacities reach the library (the
     tables only size the default capacities).  -> as ba_window_batch."""
     arr, outs, keep = pack_ba_window_problems(problems, fill)
     for i in range(len(problems)):
         _without_tables(arr[i])
+        if _cov == 2:
+            _without_cov(arr[i])
     seq = np.ascontiguousarray(sequences, np.int32).reshape(-1)
     if len(seq) != len(problems):
         raise ValueError("one sequence per problem")
     sg = np.ascontiguousarray(inv_level_sigma2, np.float32).reshape(-1)
-    f = lib().tc2li_ba_window_graph_batch
+    f = lib().tc2li_ba_window_graph_cov_batch if _cov else lib().tc2li_ba_window_graph_batch
     f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     _check(f(store._handle(), graph._handle(), seq.ctypes.data, C.addressof(arr), len(problems), sg.ctypes.data, len(sg), C.c_void_p(stream)))
     del keep
@@ -4024,13 +4187,21 @@ def ba_window_solve_graph_batch(problems, sequences, inv_level_sigma2, store, gr
 BA_COMMIT_POSITIONS_F32 = 1
 
 
-def ba_window_solve_graph_commit_batch(problems, sequences, inv_level_sigma2, store, graph, cam5, group=0, fill=0, flags=0):
+def ba_window_solve_graph_commit_cov_batch(problems, sequences, inv_level_sigma2, store, graph, cam5, group=0, fill=0, flags=0):
+    """tc2li_ba_window_solve_graph_commit_cov_batch: ba_window_solve_graph_commit_batch with the neighbour list of window i read from the
+    resident ordered row of its current keyframe; the problems' cov_kf does not reach the library."""
+    return ba_window_solve_graph_commit_batch(problems, sequences, inv_level_sigma2, store, graph, cam5, group, fill, flags, _cov=True)
+
+
+def ba_window_solve_graph_commit_batch(problems, sequences, inv_level_sigma2, store, graph, cam5, group=0, fill=0, flags=0, _cov=False):
     """tc2li_ba_window_solve_graph_commit_batch: ba_window_solve_graph_batch, and every solved window written into its sequence of `graph`
     -- the erase pairs, the free poses and the points, the closing step of LocalLVBundleAdjustment -- without the values leaving the device.
     flags: 0 or BA_COMMIT_POSITIONS_F32.  No sequence twice.  -> as ba_window_solve_batch."""
     arr, outs, keep = pack_ba_window_solve_problems(problems, fill)
     for i in range(len(problems)):
         _without_tables(arr[i].window)
+        if _cov:
+            _without_cov(arr[i].window)
     seq = np.ascontiguousarray(sequences, np.int32).reshape(-1)
     if len(seq) != len(problems):
         raise ValueError("one sequence per problem")
@@ -4038,7 +4209,7 @@ def ba_window_solve_graph_commit_batch(problems, sequences, inv_level_sigma2, st
     cam = np.ascontiguousarray(cam5, np.float64)
     n = len(problems)
     results = np.zeros(max(n, 1), np.int32)
-    f = lib().tc2li_ba_window_solve_graph_commit_batch
+    f = lib().tc2li_ba_window_solve_graph_commit_cov_batch if _cov else lib().tc2li_ba_window_solve_graph_commit_batch
     f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
     _check(f(store._handle(), graph._handle(), seq.ctypes.data, C.addressof(arr), n, sg.ctypes.data, len(sg), cam.ctypes.data, int(group), int(flags),
              results.ctypes.data))

@@ -81,6 +81,7 @@ int ba_window_batch_run(const char* entry, tc2li_keyframe_store* store, const tc
                         MgLease* resident = nullptr);
 // resident: the problems carry no table; problem p reads sequence resident->seq[p] of the map graph, whose lock the lease holds.
 // resident_windows makes such problems of a graph-reading entry's (windows: a copy of them) and takes the lease.
+int resident_cov(const char* entry, MgLease* lease, const tc2li_ba_window_problem* windows, int n_problems);   // ... and reads the neighbour lists from the graph
 int resident_windows(const char* entry, MgLease* lease, tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences, int n_problems,
                      std::vector<tc2li_ba_window_problem>* windows);
 

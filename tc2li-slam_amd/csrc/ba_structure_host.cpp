@@ -476,7 +476,7 @@ namespace {
 // commit: the solved windows are then written into their sequences (tc2li_ba_window_solve_graph_commit_batch)
 int solve_batch(const char* entry, tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences,
                 const tc2li_ba_window_solve_problem* problems, int n_problems, const float* inv_level_sigma2, int n_levels, const tc2li_camera* cam,
-                int group, int32_t* results, bool commit = false, uint32_t flags = 0) {
+                int group, int32_t* results, bool commit = false, uint32_t flags = 0, bool cov = false) {
     if (n_problems < 0 || (n_problems > 0 && (!problems || !results)) || !cam || group < 0 || group >= kMaxLockstepGroups) {
         set_error("%s: invalid argument (group 0 .. %d)", entry, kMaxLockstepGroups - 1);
         return TC2LI_ERR_INVALID;
@@ -503,6 +503,10 @@ int solve_batch(const char* entry, tc2li_keyframe_store* store, tc2li_map_graph_
     if (graph) {
         const int lrc = resident_windows(entry, &lease, store, graph, sequences, n_problems, &windows);
         if (lrc < 0) return lrc;
+        if (cov) {
+            const int crc = resident_cov(entry, &lease, windows.data(), n_problems);
+            if (crc < 0) return crc;
+        }
     }
     BasSpace& S = shutdown_owned<BasSpaces>().s[1 + group];
     std::lock_guard<std::mutex> lk(S.mu);
@@ -533,4 +537,12 @@ extern "C" int tc2li_ba_window_solve_graph_commit_batch(tc2li_keyframe_store* st
     const char* entry = "tc2li_ba_window_solve_graph_commit_batch";
     if (!graph) { set_error("%s: null graph", entry); return TC2LI_ERR_INVALID; }
     return solve_batch(entry, store, graph, sequences, problems, n_problems, inv_level_sigma2, n_levels, cam, group, results, true, flags);
+}
+
+extern "C" int tc2li_ba_window_solve_graph_commit_cov_batch(tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences,
+                                                            const tc2li_ba_window_solve_problem* problems, int n_problems, const float* inv_level_sigma2,
+                                                            int n_levels, const tc2li_camera* cam, int group, uint32_t flags, int32_t* results) {
+    const char* entry = "tc2li_ba_window_solve_graph_commit_cov_batch";
+    if (!graph) { set_error("%s: null graph", entry); return TC2LI_ERR_INVALID; }
+    return solve_batch(entry, store, graph, sequences, problems, n_problems, inv_level_sigma2, n_levels, cam, group, results, true, flags, true);
 }

@@ -20,13 +20,17 @@ constexpr int kBawPoseShift = 3;
 struct BawProblemDev : WindowProblemDev {
     int32_t cov_off, n_cov;                // cov_kf; the list scratch starts at cov_off + 2 * problem index and has n_cov + 2 entries
     int32_t pose_off, pose_cap;            // pose_row / poses7_out / fixed
-    int32_t pad_;
+    int32_t cov_row1;                      // 0: cov_kf is the uploaded list.  Else 1 + the row of BawBatch::ord_offsets whose ordered row of the
+                                           // resident map graph is the list; n_cov is then the most entries it can have
     int64_t init_kf_id;
 };
 
 struct BawBatch : WindowBatch {            // vertex_of is the keyframe's place among the poses
     const double* poses7;
     const int32_t* cov_kf;
+    const int32_t* ord_offsets;            // the ordered connections of the resident map graph (MgConnTables), read where cov_row1 != 0
+    const int32_t* ord_kf;
+    int32_t ord_rows, ord_cap;             // rows of ord_offsets and entries of ord_kf per sequence and generation
     // scratch
     int32_t* list_kf;                      // per problem n_cov + 2: lLocalKeyFrames as rows
     // out

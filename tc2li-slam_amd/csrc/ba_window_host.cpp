@@ -216,6 +216,28 @@ int tc2li::resident_windows(const char* entry, MgLease* lease, tc2li_keyframe_st
     return 0;
 }
 
+// 0, or TC2LI_ERR_INVALID: the lease of an entry that reads the neighbour lists from the graph; the problems carry none
+int tc2li::resident_cov(const char* entry, MgLease* lease, const tc2li_ba_window_problem* windows, int n_problems) {
+    if (!lease->C.ord_kf) { set_error("%s: tc2li_map_graph_connections_reserve was not called", entry); return TC2LI_ERR_INVALID; }
+    for (int p = 0; p < n_problems; ++p)
+        if (windows[p].cov_kf || windows[p].n_cov) { set_error("%s: problem %d: cov_kf / n_cov must be NULL / 0, the list is the graph's", entry, p); return TC2LI_ERR_INVALID; }
+    lease->cov_resident = true;
+    return 0;
+}
+
+extern "C" int tc2li_ba_window_graph_cov_batch(tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences,
+                                               const tc2li_ba_window_problem* problems, int n_problems, const float* inv_level_sigma2, int n_levels, void* stream) {
+    const char* entry = "tc2li_ba_window_graph_cov_batch";
+    if (n_problems > 0 && !problems) { set_error("%s: null problems", entry); return TC2LI_ERR_INVALID; }
+    std::vector<tc2li_ba_window_problem> windows(problems, problems + std::max(n_problems, 0));
+    MgLease lease;
+    int rc = resident_windows(entry, &lease, store, graph, sequences, n_problems, &windows);
+    if (rc < 0) return rc;
+    rc = resident_cov(entry, &lease, windows.data(), n_problems);
+    if (rc < 0) return rc;
+    return ba_window_batch_run(entry, store, windows.data(), n_problems, inv_level_sigma2, n_levels, stream, nullptr, 0, false, &lease);
+}
+
 extern "C" int tc2li_ba_window_graph_batch(tc2li_keyframe_store* store, tc2li_map_graph_handle* graph, const int32_t* sequences, const tc2li_ba_window_problem* problems,
                                            int n_problems, const float* inv_level_sigma2, int n_levels, void* stream) {
     const char* entry = "tc2li_ba_window_graph_batch";
@@ -259,14 +281,21 @@ int tc2li::ba_window_batch_run(const char* entry, tc2li_keyframe_store* store, c
         }
         d.init_kf_id = in.init_kf_id;
         d.cov_off = (int32_t)n_cov; d.n_cov = in.n_cov;
+        if (resident && resident->cov_resident) {   // the list is the resident ordered row of current: no keyframe twice, not current itself
+            const MgSequenceView& s = resident->seq[p];
+            const bool has_row = in.current < s.conn_rows;                           // a row appended since is empty
+            d.n_cov = has_row ? std::min(s.n_kf - 1, s.n_ordered) : 0;               // what the list scratch must hold
+            d.cov_row1 = has_row ? 1 + s.ord_row + in.current : 0;
+        }
         d.pose_off = (int32_t)n_pose; d.pose_cap = std::min(in.pose_capacity, in.n_keyframes);
-        n_cov += in.n_cov; n_pose += d.pose_cap;
+        n_cov += d.n_cov; n_pose += d.pose_cap;
         if (std::max(T.most_rows(p), n_cov + 2 * (size_t)p) > kMaxRows) return too_many_rows(entry, p);
     }
     const size_t np = (size_t)n_problems;
     T.take_inputs(n_levels);
     size_t o_pose, o_cov;
-    if (resident) { o_pose = o_cov = T.io.off; T.io.off += n_cov * 4; }   // the poses are resident; cov_kf follows the level table
+    const bool cov_resident = resident && resident->cov_resident;
+    if (resident) { o_pose = o_cov = T.io.off; T.io.off += cov_resident ? 0 : n_cov * 4; }   // the poses are resident; cov_kf follows the level table
     else { o_pose = T.io.take(T.n_kf * 56); o_cov = T.io.take(n_cov * 4); }
     T.take_outputs(TC2LI_BA_WINDOW_COUNTS);
     const size_t o_p7 = T.io.take(n_pose * 56), o_prow = T.io.take(n_pose * 4), o_fixed = T.io.take(n_pose);
@@ -277,7 +306,7 @@ int tc2li::ba_window_batch_run(const char* entry, tc2li_keyframe_store* store, c
     TC2LI_HIP_CHECK(T.ensure(S));
     TC2LI_HIP_CHECK(T.upload_tables(inv_level_sigma2, n_levels, st, [&](int, const tc2li_ba_window_problem& in, const BawProblemDev& d) {
         if (!resident) T.io.put(o_pose, d.kf_off, in.poses7, (size_t)in.n_keyframes, 56);
-        T.io.put(o_cov, d.cov_off, in.cov_kf, (size_t)in.n_cov, 4);
+        if (!cov_resident) T.io.put(o_cov, d.cov_off, in.cov_kf, (size_t)in.n_cov, 4);
     }));
     if (resident) resident->uploaded = (int64_t)T.up_bytes;
     uint8_t* d = T.d_io;
@@ -292,6 +321,7 @@ int tc2li::ba_window_batch_run(const char* entry, tc2li_keyframe_store* store, c
         B.poses7 = G.poses7;
     }
     B.cov_kf = (const int32_t*)(d + o_cov); B.list_kf = T.dev_work<int32_t>(w_lkf);
+    if (cov_resident) { B.ord_offsets = resident->C.ord_offsets; B.ord_kf = resident->C.ord_kf; B.ord_rows = resident->T.cap_kf + 1; B.ord_cap = resident->C.cap_e; }
     B.counts = (int32_t*)(d + T.o_counts); B.lidar_pose_index = (int32_t*)(d + T.o_lidar); B.pose_row = (int32_t*)(d + o_prow);
     B.poses7_out = (double*)(d + o_p7); B.fixed = d + o_fixed;
     launch_ba_window(B, st);

@@ -26,6 +26,13 @@ __device__ __forceinline__ void baw_problem(const BawBatch& B, const BawProblemD
     const int32_t* slot_row = B.slot_offsets + P.slot_row;
     const int32_t* slot_point = B.slot_point + P.t_slot;
     const int32_t* cov = B.cov_kf + P.cov_off;
+    int n_cov = P.n_cov;
+    if (P.cov_row1) {   // GetVectorCovisibleKeyFrames() as it is resident: the ordered row of the current keyframe, in its order
+        const int row = P.cov_row1 - 1;
+        const int o0 = B.ord_offsets[row];
+        n_cov = min(B.ord_offsets[row + 1] - o0, P.n_cov);
+        cov = B.ord_kf + (size_t)(row / B.ord_rows) * B.ord_cap + o0;
+    }
     const uint8_t* pflags = B.point_flags + P.t_point;
     const int32_t* obs_row = B.obs_offsets + P.obs_row;
     const int32_t* obs_kf = B.obs_kf + P.t_obs;
@@ -52,9 +59,9 @@ __device__ __forceinline__ void baw_problem(const BawBatch& B, const BawProblemD
         if (n_cloud) sh[1] = cur;
         if (kf_id[cur] == init_id) atomicOr(&sh[0], 1);
     }
-    for (int base = 0; base < P.n_cov; base += kWinThreads) {
+    for (int base = 0; base < n_cov; base += kWinThreads) {
         const int i = base + tid;
-        const int k = i < P.n_cov ? cov[i] : -1;
+        const int k = i < n_cov ? cov[i] : -1;
         const int f = k >= 0 ? flags[k] : 3;
         const bool local = !(f & 3);                                                 // :74
         const bool cloud = local && (f & 4);                                         // :231

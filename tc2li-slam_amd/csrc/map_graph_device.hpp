@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/tc2li_hip.h"
+#include "connections_device.hpp"
 
 namespace tc2li {
 
@@ -92,12 +93,58 @@ struct MgCommitBatch {
 void launch_map_graph_commit_erase_log(const MgCommitBatch& B, hipStream_t st);
 void launch_map_graph_commit_scatter(const MgCommitBatch& B, hipStream_t st);
 
+// ---- the covisibility graph of the resident map (include/tc2li_hip.h "the covisibility graph on the resident map graph") ----
+// Two CSRs over the keyframe rows of every sequence, in an allocation of their own made by tc2li_map_graph_connections_reserve: the
+// weights (mConnectedKeyFrameWeights, a row ascending by keyframe row) and the ordered lists (mvpOrderedConnectedKeyFrames /
+// mvOrderedWeights as last written).  Neither can be edited in place -- rows grow, and the current keyframe's rows are replaced -- so
+// both have two generations, as the observation CSR has: an update reads the one and writes the whole of the other, and the host flips
+// the sequence's generation only when every sequence of the call fitted its reserve.  Until then the written generation is not the
+// state: that is what makes a refused call leave no trace.
+struct MgConnTables {
+    int32_t* conn_offsets;                 // [S][2][cap_kf + 1]
+    int32_t* conn_kf;                      // [S][2][cap_e]
+    int32_t* conn_weight;
+    int32_t* ord_offsets;                  // [S][2][cap_kf + 1]
+    int32_t* ord_kf;                       // [S][2][cap_e]
+    int32_t* ord_weight;
+    int32_t cap_e;
+};
+enum MgConnMode { kMgcUpdate = 0, kMgcErase = 1 };
+// One sequence of an update or an erase: 64 bytes, and all that goes up.
+struct MgConnDev {
+    int32_t sequence, obs_generation, conn_generation;
+    int32_t n_kf;                          // the resident keyframe rows
+    int32_t conn_rows;                     // the rows the connection offsets cover; the rows appended since are empty and get their offsets first
+    int32_t current;                       // the keyframe of the call
+    int32_t slot_begin, n_slots;           // its slot row within the sequence's slot_point
+    int64_t init_kf_id;
+    int32_t first_connection, mode;
+    int32_t pad_[4];
+};
+static_assert(sizeof(MgConnDev) == 64, "an update of the connections moves 64 bytes per sequence");
+constexpr int kMgcStatusWords = 4;         // per sequence, device to host: fitted, weight entries, ordered entries of the written generation, 0
+
+struct MgConnBatch {
+    MgTables T;
+    MgConnTables C;
+    int n, max_kf;                         // records; the most keyframe rows among them (the grid of the neighbours' kernel)
+    const MgConnDev* records;
+    ConnBatch B;                           // the resident tables and the scratch as the kernels of tc2li_update_connections_batch read them
+    ConnProblemDev* problems;              // [n] written by the first kernel from the records (= B.problems)
+    int32_t* row_of;                       // [n][2][cap_kf] scratch: a keyframe row's place among the changed touched ones (-1: none), their new list lengths
+    int32_t* status;                       // [n][kMgcStatusWords]
+};
+void launch_map_graph_connections(const MgConnBatch& M, hipStream_t st);
+
 // A sequence as a gather reads it: the sizes, and where its tables start in the slab's tables (WindowProblemDev::t_*, slot_row, obs_row).
 struct MgSequenceView {
     int32_t n_kf, n_points, n_slot, n_obs;
     int32_t t_kf, t_slot, t_point, t_obs, slot_row, obs_row;
     const int32_t* kf_store_slot;          // host: the store slot of every keyframe row
     const int32_t* kf_keys;                // host: the keypoints that slot held when the row's observation indices were checked
+    // the ordered connections, for a gather that takes its neighbour list from them: the sequence's current generation of ord_offsets as
+    // a row of MgConnTables::ord_offsets, the keyframe rows those offsets cover (a row beyond is empty) and the entries of the CSR
+    int32_t ord_row, conn_rows, n_ordered;
 };
 
 }  // namespace tc2li

@@ -2,6 +2,9 @@
 // the host's mirror of per-row metadata (row counts, the store slot and the slot row of every keyframe row, the observation total -- no
 // table), the check of an edit log against it, the log's way to the device (map_graph_kernels.hip) and the plain sequential twin that
 // defines the result.  MgLease (map_graph_host.hpp) is how a gather reads the graph (ba_window_host.cpp).
+// tc2li_map_graph_*connections* (tc2li_hip.h "the covisibility graph on the resident map graph"): the two CSRs of the connections in an
+// allocation of their own, their mirror (generation, rows covered, entries), the check of tables set from the host, the records of an
+// update or an erase for connections_kernels.hip, and the two host twins.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -29,6 +32,12 @@ struct SeqMeta {
     std::vector<int32_t> store_slot;         // [n_kf]
     std::vector<int32_t> n_keys;             // [n_kf] the most keypoints the row's store slot held at a set or an apply: every resident obs_index is below it
     std::vector<int32_t> slot_off{0};        // [n_kf + 1] slot_offsets
+    // the connections (tc2li_map_graph_connections_*): the generation of both CSRs that is current, the keyframe rows their offsets
+    // cover (the rows appended since are empty), their entries
+    int conn_generation = 0, conn_rows = 0, n_weight = 0, n_ordered = 0;
+    int conn_updates = 0;
+    int64_t conn_bytes = 0;
+    void clear_connections() { conn_generation = conn_rows = n_weight = n_ordered = conn_updates = 0; conn_bytes = 0; }
 };
 
 }  // namespace
@@ -52,6 +61,14 @@ struct tc2li_map_graph_handle {
     DevBuf<uint8_t> d_commit;
     DevBuf<int32_t> d_commit_words;
     PinnedBuf<int32_t> h_commit_words;
+    // the connections: their own allocation, made by the reserve; the records, scratch and words of an update or an erase
+    uint8_t* conn_slab = nullptr;
+    MgConnTables C{};
+    PinnedBuf<MgConnDev> h_conn;
+    DevBuf<MgConnDev> d_conn;
+    DevBuf<uint8_t> d_conn_scratch;
+    DevBuf<int32_t> d_conn_words;
+    PinnedBuf<int32_t> h_conn_words;
 };
 
 namespace {
@@ -161,6 +178,7 @@ MgSequenceView view_of(const tc2li_map_graph_handle* g, int s) {
     v.t_obs = (2 * s + m.generation) * g->cap[3];
     v.slot_row = s * (g->cap[0] + 1); v.obs_row = (2 * s + m.generation) * (g->cap[2] + 1);
     v.kf_store_slot = m.store_slot.data(); v.kf_keys = m.n_keys.data();
+    v.ord_row = (2 * s + m.conn_generation) * (g->cap[0] + 1); v.conn_rows = m.conn_rows; v.n_ordered = m.n_ordered;
     return v;
 }
 
@@ -213,6 +231,7 @@ extern "C" int tc2li_map_graph_create(tc2li_keyframe_store* store, int n_sequenc
 extern "C" int tc2li_map_graph_destroy(tc2li_map_graph_handle* g) {
     if (!g) return 0;
     if (g->slab) (void)hipFree(g->slab);
+    if (g->conn_slab) (void)hipFree(g->conn_slab);
     delete g;
     return 0;
 }
@@ -285,6 +304,7 @@ extern "C" int tc2li_map_graph_set_batch(tc2li_map_graph_handle* g, const int32_
         SeqMeta& m = g->seq[sequences[i]];
         m.set = true; m.generation = 0; m.n_kf = t.n_keyframes; m.n_pt = t.n_points; m.n_obs = t.obs_offsets[t.n_points];
         m.applies = 0; m.apply_bytes = 0; m.gather_bytes = 0;
+        m.clear_connections();
         m.store_slot.assign(t.kf_slot, t.kf_slot + t.n_keyframes);
         m.n_keys.resize(t.n_keyframes);
         for (int k = 0; k < t.n_keyframes; ++k) m.n_keys[k] = slots.n[t.kf_slot[k]];
@@ -421,13 +441,427 @@ extern "C" int tc2li_map_graph_download(tc2li_map_graph_handle* g, int sequence,
     return download_locked(me, g, sequence, out, capacities, counts);
 }
 
+// ---- the connections -------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// "" or what tc2li_map_graph_set_connections_batch refuses; rows: the keyframe rows the sequence has
+const char* connections_fault(const tc2li_map_graph_connections& c, int rows) {
+    if (c.n_keyframes < 0 || c.n_keyframes > rows) return "n_keyframes negative or beyond the sequence's keyframe rows";
+    if (!c.conn_offsets || !c.ord_offsets) return "null conn_offsets or ord_offsets";
+    if (!ascending(c.conn_offsets, c.n_keyframes) || !ascending(c.ord_offsets, c.n_keyframes)) return "offsets do not ascend from 0";
+    const int nk = c.n_keyframes, nw = c.conn_offsets[nk], no = c.ord_offsets[nk];
+    if ((nw && (!c.conn_kf || !c.conn_weight)) || (no && (!c.ord_kf || !c.ord_weight))) return "null conn_kf, conn_weight, ord_kf or ord_weight";
+    for (int r = 0; r < nk; ++r)
+        for (int j = c.conn_offsets[r]; j < c.conn_offsets[r + 1]; ++j) {
+            if (c.conn_kf[j] < 0 || c.conn_kf[j] >= nk) return "a keyframe of a weight row is out of range";
+            if (j > c.conn_offsets[r] && c.conn_kf[j] <= c.conn_kf[j - 1]) return "a weight row does not ascend strictly by keyframe";
+            if (c.conn_kf[j] == r) return "a weight row names its own keyframe";
+        }
+    std::vector<int32_t> seen(nk, -1);
+    for (int r = 0; r < nk; ++r)
+        for (int j = c.ord_offsets[r]; j < c.ord_offsets[r + 1]; ++j) {
+            const int k = c.ord_kf[j];
+            if (k < 0 || k >= nk) return "a keyframe of an ordered row is out of range";
+            if (k == r) return "an ordered row names its own keyframe";
+            if (seen[k] == r) return "an ordered row names a keyframe twice";
+            seen[k] = r;
+        }
+    return "";
+}
+
+bool reserved(const char* me, const tc2li_map_graph_handle* g) {
+    if (g && g->conn_slab) return true;
+    set_error("%s: null graph, or tc2li_map_graph_connections_reserve was not called", me);
+    return false;
+}
+
+// The state of the host twins: a keyframe's weights in map order and its lists.
+struct HostConnections {
+    std::vector<std::vector<std::pair<int32_t, int32_t>>> weights, ordered;   // (keyframe, weight)
+    void read(const tc2li_map_graph_connections& c, int rows) {
+        weights.assign(rows, {}); ordered.assign(rows, {});
+        for (int r = 0; r < c.n_keyframes; ++r) {
+            for (int j = c.conn_offsets[r]; j < c.conn_offsets[r + 1]; ++j) weights[r].emplace_back(c.conn_kf[j], c.conn_weight[j]);
+            for (int j = c.ord_offsets[r]; j < c.ord_offsets[r + 1]; ++j) ordered[r].emplace_back(c.ord_kf[j], c.ord_weight[j]);
+        }
+    }
+    // KeyFrame::UpdateBestCovisibles (:216-238) of row k
+    void best_covisibles(int k, const uint8_t* kf_flags) {
+        std::vector<uint64_t> keys;
+        for (const auto& e : weights[k])
+            if (!(kf_flags[e.first] & 1)) keys.push_back(conn::key(e.second, e.first));   // :229
+        std::sort(keys.begin(), keys.end());                                               // :224
+        ordered[k].clear();
+        for (size_t i = keys.size(); i-- > 0;) ordered[k].emplace_back(conn::key_kf(keys[i]), conn::key_weight(keys[i]));   // :231-232
+    }
+    // 0, or TC2LI_ERR_*; sizes is written either way
+    int write(const char* me, tc2li_map_graph_connections* out, const int32_t* capacities, int32_t* sizes) const {
+        size_t nw = 0, no = 0;
+        for (const auto& r : weights) nw += r.size();
+        for (const auto& r : ordered) no += r.size();
+        sizes[0] = (int32_t)nw; sizes[1] = (int32_t)no;
+        if ((int64_t)nw > capacities[0] || (int64_t)no > capacities[1]) {
+            set_error("%s: %zu weight and %zu ordered entries, the capacities are %d and %d", me, nw, no, capacities[0], capacities[1]);
+            return TC2LI_ERR_CAPACITY;
+        }
+        if (!out->conn_offsets || !out->ord_offsets || (nw && (!out->conn_kf || !out->conn_weight)) || (no && (!out->ord_kf || !out->ord_weight))) {
+            set_error("%s: null output array", me);
+            return TC2LI_ERR_INVALID;
+        }
+        int32_t a = 0, b = 0;
+        for (size_t r = 0; r < weights.size(); ++r) {
+            out->conn_offsets[r] = a; out->ord_offsets[r] = b;
+            for (const auto& e : weights[r]) { out->conn_kf[a] = e.first; out->conn_weight[a++] = e.second; }
+            for (const auto& e : ordered[r]) { out->ord_kf[b] = e.first; out->ord_weight[b++] = e.second; }
+        }
+        out->conn_offsets[weights.size()] = a; out->ord_offsets[weights.size()] = b;
+        out->n_keyframes = (int32_t)weights.size();
+        return 0;
+    }
+};
+
+// what both twins check of their inputs
+int twin_check(const char* me, const tc2li_map_graph_tables* t, const tc2li_map_graph_connections* in, int row, const tc2li_map_graph_connections* out,
+               const int32_t* capacities, const int32_t* sizes) {
+    if (!t || !in || !out || !capacities || !sizes) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    const char* what = tables_fault(*t);
+    if (!what[0] && (!ascending(t->slot_offsets, t->n_keyframes) || !ascending(t->obs_offsets, t->n_points))) what = "offsets do not ascend from 0";
+    if (!what[0]) {
+        const int n_slot = t->slot_offsets[t->n_keyframes], n_obs = t->obs_offsets[t->n_points];
+        if ((n_slot && !t->slot_point) || (n_obs && !t->obs_kf)) what = "null slot_point or obs_kf";
+        for (int i = 0; !what[0] && i < n_slot; ++i)
+            if (t->slot_point[i] < -1 || t->slot_point[i] >= t->n_points) what = "slot_point out of range";
+        for (int i = 0; !what[0] && i < n_obs; ++i)
+            if (t->obs_kf[i] < 0 || t->obs_kf[i] >= t->n_keyframes) what = "obs_kf out of range";
+    }
+    if (!what[0]) what = connections_fault(*in, t->n_keyframes);
+    if (!what[0] && (row < 0 || row >= t->n_keyframes)) what = "the keyframe row is out of range";
+    if (what[0]) { set_error("%s: %s", me, what); return TC2LI_ERR_INVALID; }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int tc2li_host_map_graph_update_connections(const tc2li_map_graph_tables* t, const tc2li_map_graph_connections* in, int32_t current,
+                                                       int first_connection, int64_t init_kf_id, tc2li_map_graph_connections* out,
+                                                       const int32_t* capacities, int32_t* sizes, int32_t* counts) {
+    const char* me = "tc2li_host_map_graph_update_connections";
+    if (!counts) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    int rc = twin_check(me, t, in, current, out, capacities, sizes);
+    if (rc < 0) return rc;
+    const int nk = t->n_keyframes, np = t->n_points;
+    HostConnections H;
+    H.read(*in, nk);
+    // the call as a tc2li_connections_problem: the table above "Inputs" in the header
+    std::vector<int32_t> conn_off(nk + 1, 0), conn_kf, conn_weight;
+    for (int r = 0; r < nk; ++r) {
+        for (const auto& e : H.weights[r]) { conn_kf.push_back(e.first); conn_weight.push_back(e.second); }
+        conn_off[r + 1] = (int32_t)conn_kf.size();
+    }
+    std::vector<uint8_t> point_bad(np + 1, 0);
+    for (int p = 0; p < np; ++p) point_bad[p] = t->point_flags[p] & 1;
+    const size_t room = conn_kf.size() + (size_t)nk + 1;
+    std::vector<int32_t> counter_kf(nk + 1), counter_weight(nk + 1), ordered_kf(nk + 1), ordered_weight(nk + 1), touched_kf(nk + 1), changed_off(nk + 2),
+        changed_kf(room), changed_weight(room);
+    std::vector<uint8_t> touched_changed(nk + 1);
+    tc2li_connections_problem pr{};
+    pr.kf_flags = t->kf_flags; pr.conn_offsets = conn_off.data(); pr.conn_kf = conn_kf.data(); pr.conn_weight = conn_weight.data();
+    pr.slot_point = t->slot_point + t->slot_offsets[current]; pr.n_slots = t->slot_offsets[current + 1] - t->slot_offsets[current];
+    pr.point_bad = point_bad.data(); pr.obs_offsets = t->obs_offsets; pr.obs_kf = t->obs_kf;
+    pr.counts = counts; pr.counter_kf = counter_kf.data(); pr.counter_weight = counter_weight.data(); pr.ordered_kf = ordered_kf.data();
+    pr.ordered_weight = ordered_weight.data(); pr.touched_kf = touched_kf.data(); pr.touched_changed = touched_changed.data();
+    pr.changed_offsets = changed_off.data(); pr.changed_kf = changed_kf.data(); pr.changed_weight = changed_weight.data();
+    pr.n_keyframes = nk; pr.n_points = np; pr.current = current;
+    pr.counter_capacity = nk; pr.ordered_capacity = nk; pr.changed_capacity = (int32_t)room - 1;
+    pr.first_connection = first_connection ? 1 : 0; pr.is_init_kf = t->kf_id[current] == init_kf_id ? 1 : 0;
+    rc = tc2li_host_update_connections_batch(&pr, 1);
+    if (rc < 0) return rc;
+    if (counts[TC2LI_CONNECTIONS_STATUS] == TC2LI_CONNECTIONS_UPDATED) {
+        auto& own = H.weights[current];
+        own.clear();                                                                                       // :473
+        for (int i = 0; i < counts[TC2LI_CONNECTIONS_N_COUNTER]; ++i) own.emplace_back(counter_kf[i], counter_weight[i]);
+        H.ordered[current].clear();                                                                        // :474-475
+        for (int i = 0; i < counts[TC2LI_CONNECTIONS_N_ORDERED]; ++i) H.ordered[current].emplace_back(ordered_kf[i], ordered_weight[i]);
+        for (int i = 0, c = 0; i < counts[TC2LI_CONNECTIONS_N_ORDERED]; ++i) {                             // AddConnection (:201-214)
+            const int k = touched_kf[i];
+            const int32_t* w = std::lower_bound(counter_kf.data(), counter_kf.data() + counts[TC2LI_CONNECTIONS_N_COUNTER], k);
+            const int32_t weight = counter_weight[w - counter_kf.data()];
+            auto& row = H.weights[k];
+            auto it = std::lower_bound(row.begin(), row.end(), current, [](const std::pair<int32_t, int32_t>& x, int32_t v) { return x.first < v; });
+            if (it != row.end() && it->first == current) it->second = weight;
+            else row.insert(it, std::make_pair(current, weight));
+            if (!touched_changed[i]) continue;                                                             // :209-210
+            H.ordered[k].clear();
+            for (int j = changed_off[c]; j < changed_off[c + 1]; ++j) H.ordered[k].emplace_back(changed_kf[j], changed_weight[j]);
+            ++c;
+        }
+    }
+    rc = H.write(me, out, capacities, sizes);
+    return rc < 0 ? rc : counts[TC2LI_CONNECTIONS_STATUS];
+}
+
+extern "C" int tc2li_host_map_graph_erase_connections(const tc2li_map_graph_tables* t, const tc2li_map_graph_connections* in, int32_t row,
+                                                      tc2li_map_graph_connections* out, const int32_t* capacities, int32_t* sizes) {
+    const char* me = "tc2li_host_map_graph_erase_connections";
+    const int rc = twin_check(me, t, in, row, out, capacities, sizes);
+    if (rc < 0) return rc;
+    HostConnections H;
+    H.read(*in, t->n_keyframes);
+    for (const auto& e : H.weights[row]) {                                                                 // :600-603
+        auto& theirs = H.weights[e.first];
+        auto it = std::lower_bound(theirs.begin(), theirs.end(), row, [](const std::pair<int32_t, int32_t>& x, int32_t v) { return x.first < v; });
+        if (it == theirs.end() || it->first != row) continue;                                              // :703: bUpdate stays false
+        theirs.erase(it);                                                                                  // :705
+        H.best_covisibles(e.first, t->kf_flags);                                                           // :710-711
+    }
+    H.weights[row].clear();                                                                                // :617
+    H.ordered[row].clear();                                                                                // :618
+    return H.write(me, out, capacities, sizes);
+}
+
+extern "C" int tc2li_map_graph_connections_limits(int32_t* out, int capacity) {
+    if (!out || capacity < 2) { set_error("tc2li_map_graph_connections_limits: room for 2 values is needed"); return TC2LI_ERR_INVALID; }
+    out[0] = (int32_t)sizeof(MgConnDev); out[1] = kMgcStatusWords * 4;
+    return 2;
+}
+
+extern "C" int tc2li_map_graph_connections_reserve(tc2li_map_graph_handle* g, int entries) {
+    const char* me = "tc2li_map_graph_connections_reserve";
+    if (!g) { set_error("%s: null graph", me); return TC2LI_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (g->conn_slab) { set_error("%s: called twice", me); return TC2LI_ERR_INVALID; }
+    if (entries < 1 || 2 * (int64_t)g->n_seq * ((int64_t)entries + 1) > (int64_t)kMaxRows) {
+        set_error("%s: a capacity below 1, or tables of all sequences beyond 2^31 entries", me);
+        return TC2LI_ERR_INVALID;
+    }
+    if (!device_ready()) return TC2LI_ERR_NO_DEVICE;
+    const size_t S = (size_t)g->n_seq, K = (size_t)g->cap[0], E = (size_t)entries;
+    Packer slab;
+    const size_t o_wrow = slab.take(2 * S * (K + 1) * 4), o_wkf = slab.take(2 * S * E * 4), o_ww = slab.take(2 * S * E * 4);
+    const size_t o_orow = slab.take(2 * S * (K + 1) * 4), o_okf = slab.take(2 * S * E * 4), o_ow = slab.take(2 * S * E * 4);
+    TC2LI_HIP_CHECK(hipMalloc((void**)&g->conn_slab, slab.off));
+    uint8_t* b = g->conn_slab;
+    MgConnTables& C = g->C;
+    C.conn_offsets = (int32_t*)(b + o_wrow); C.conn_kf = (int32_t*)(b + o_wkf); C.conn_weight = (int32_t*)(b + o_ww);
+    C.ord_offsets = (int32_t*)(b + o_orow); C.ord_kf = (int32_t*)(b + o_okf); C.ord_weight = (int32_t*)(b + o_ow);
+    C.cap_e = entries;
+    for (SeqMeta& m : g->seq) m.clear_connections();
+    return 0;
+}
+
+extern "C" int tc2li_map_graph_connections_info(tc2li_map_graph_handle* g, int sequence, int64_t* out, int capacity) {
+    const char* me = "tc2li_map_graph_connections_info";
+    if (!reserved(me, g)) return TC2LI_ERR_INVALID;
+    if (!sequence_ok(g, sequence) || !out || capacity < TC2LI_MAP_GRAPH_CONNECTIONS_INFO_FIELDS) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(g->mu);
+    const SeqMeta& m = g->seq[sequence];
+    out[TC2LI_MAP_GRAPH_CONNECTIONS_WEIGHT_ENTRIES] = m.n_weight; out[TC2LI_MAP_GRAPH_CONNECTIONS_ORDERED_ENTRIES] = m.n_ordered;
+    out[TC2LI_MAP_GRAPH_CONNECTIONS_UPDATES] = m.conn_updates; out[TC2LI_MAP_GRAPH_CONNECTIONS_UPDATE_BYTES] = m.conn_bytes;
+    return TC2LI_MAP_GRAPH_CONNECTIONS_INFO_FIELDS;
+}
+
+extern "C" int tc2li_map_graph_set_connections_batch(tc2li_map_graph_handle* g, const int32_t* sequences, const tc2li_map_graph_connections* tables, int n,
+                                                     void* stream) {
+    const char* me = "tc2li_map_graph_set_connections_batch";
+    if (!reserved(me, g)) return TC2LI_ERR_INVALID;
+    if (n < 0 || (n && (!sequences || !tables))) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    if (n == 0) return 0;
+    std::lock_guard<std::mutex> lk(g->mu);
+    std::vector<uint8_t> named(g->n_seq, 0);
+    size_t bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        const tc2li_map_graph_connections& c = tables[i];
+        if (!sequence_ok(g, sequences[i]) || named[sequences[i]] || !g->seq[sequences[i]].set) {
+            set_error("%s: sequence %d out of range, never set or named twice", me, sequences[i]);
+            return TC2LI_ERR_INVALID;
+        }
+        named[sequences[i]] = 1;
+        const char* what = connections_fault(c, g->seq[sequences[i]].n_kf);
+        if (what[0]) { set_error("%s: sequence %d: %s", me, sequences[i], what); return TC2LI_ERR_INVALID; }
+        const int nw = c.conn_offsets[c.n_keyframes], no = c.ord_offsets[c.n_keyframes];
+        if (nw > g->C.cap_e || no > g->C.cap_e) {
+            set_error("%s: sequence %d has %d weight and %d ordered entries; the reserve is %d", me, sequences[i], nw, no, g->C.cap_e);
+            return TC2LI_ERR_CAPACITY;
+        }
+        bytes += 16 * 6 + 2 * ((size_t)c.n_keyframes + 1) * 4 + 2 * ((size_t)nw + (size_t)no) * 4;
+    }
+    if (!device_ready()) return TC2LI_ERR_NO_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : private_stream();
+    TC2LI_HIP_CHECK(g->h_up.ensure(bytes));
+    TC2LI_HIP_CHECK(g->tasks.ensure(6 * (size_t)n));
+    size_t at = 0, n_tasks = 0, max_bytes = 0;
+    auto stage = [&](void* dst, const void* src, size_t b) {
+        if (!b) return;
+        memcpy(g->h_up.p + at, src, b);
+        g->tasks.p[n_tasks++] = CopyTask{dst, g->h_up.p + at, b};
+        max_bytes = std::max(max_bytes, b);
+        at += (b + 15) & ~(size_t)15;
+    };
+    const MgConnTables& C = g->C;
+    const size_t rows = (size_t)g->cap[0] + 1, E = (size_t)C.cap_e;
+    for (int i = 0; i < n; ++i) {                                                    // into generation 0
+        const tc2li_map_graph_connections& c = tables[i];
+        const size_t s = (size_t)sequences[i], nk = (size_t)c.n_keyframes, nw = (size_t)c.conn_offsets[nk], no = (size_t)c.ord_offsets[nk];
+        stage(C.conn_offsets + 2 * s * rows, c.conn_offsets, (nk + 1) * 4); stage(C.conn_kf + 2 * s * E, c.conn_kf, nw * 4); stage(C.conn_weight + 2 * s * E, c.conn_weight, nw * 4);
+        stage(C.ord_offsets + 2 * s * rows, c.ord_offsets, (nk + 1) * 4); stage(C.ord_kf + 2 * s * E, c.ord_kf, no * 4); stage(C.ord_weight + 2 * s * E, c.ord_weight, no * 4);
+    }
+    launch_copy_tasks(g->tasks.p, (int)n_tasks, max_bytes, st);
+    TC2LI_HIP_CHECK(hipGetLastError());
+    TC2LI_HIP_CHECK(stream_wait_blocking(st));
+    for (int i = 0; i < n; ++i) {
+        const tc2li_map_graph_connections& c = tables[i];
+        SeqMeta& m = g->seq[sequences[i]];
+        m.clear_connections();
+        m.conn_rows = c.n_keyframes; m.n_weight = c.conn_offsets[c.n_keyframes]; m.n_ordered = c.ord_offsets[c.n_keyframes];
+    }
+    return n;
+}
+
+extern "C" int tc2li_map_graph_download_connections(tc2li_map_graph_handle* g, int sequence, tc2li_map_graph_connections* out, const int32_t* capacities,
+                                                    int32_t* counts) {
+    const char* me = "tc2li_map_graph_download_connections";
+    if (!reserved(me, g)) return TC2LI_ERR_INVALID;
+    if (!sequence_ok(g, sequence) || !out || !capacities || !counts) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(g->mu);
+    const SeqMeta& m = g->seq[sequence];
+    counts[0] = m.n_weight; counts[1] = m.n_ordered;
+    if (capacities[0] < counts[0] || capacities[1] < counts[1]) { set_error("%s: the arrays are too small", me); return TC2LI_ERR_CAPACITY; }
+    if (!out->conn_offsets || !out->ord_offsets || (m.n_weight && (!out->conn_kf || !out->conn_weight)) || (m.n_ordered && (!out->ord_kf || !out->ord_weight))) {
+        set_error("%s: null array", me);
+        return TC2LI_ERR_INVALID;
+    }
+    out->n_keyframes = m.n_kf;
+    if (m.conn_rows > 0 || m.n_weight || m.n_ordered) {
+        if (!device_ready()) return TC2LI_ERR_NO_DEVICE;
+        const MgConnTables& C = g->C;
+        const size_t gen = 2 * (size_t)sequence + m.conn_generation, rows = (size_t)g->cap[0] + 1, E = (size_t)C.cap_e;
+        auto get = [](void* dst, const void* src, size_t b) { return b ? hipMemcpy(dst, src, b, hipMemcpyDeviceToHost) : hipSuccess; };
+        TC2LI_HIP_CHECK(get(out->conn_offsets, C.conn_offsets + gen * rows, ((size_t)m.conn_rows + 1) * 4));
+        TC2LI_HIP_CHECK(get(out->ord_offsets, C.ord_offsets + gen * rows, ((size_t)m.conn_rows + 1) * 4));
+        TC2LI_HIP_CHECK(get(out->conn_kf, C.conn_kf + gen * E, (size_t)m.n_weight * 4)); TC2LI_HIP_CHECK(get(out->conn_weight, C.conn_weight + gen * E, (size_t)m.n_weight * 4));
+        TC2LI_HIP_CHECK(get(out->ord_kf, C.ord_kf + gen * E, (size_t)m.n_ordered * 4)); TC2LI_HIP_CHECK(get(out->ord_weight, C.ord_weight + gen * E, (size_t)m.n_ordered * 4));
+    }
+    for (int k = m.conn_rows; k <= m.n_kf; ++k) { out->conn_offsets[k] = m.n_weight; out->ord_offsets[k] = m.n_ordered; }   // the rows appended since: empty
+    return 0;
+}
+
+namespace {
+// An update (first_connection / init_kf_id given) or an erase of the connections; the caller has checked the plain arguments.
+int connections_call(const char* me, tc2li_map_graph_handle* g, const int32_t* sequences, const int32_t* rows, const uint8_t* first_connection,
+                     const int64_t* init_kf_id, int n, int32_t* counts_out, int mode, void* stream) {
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (n > 65535) { set_error("%s: at most 65535 sequences in one call", me); return TC2LI_ERR_INVALID; }
+    std::vector<uint8_t> named(g->n_seq, 0);
+    int max_kf = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!sequence_ok(g, sequences[i]) || named[sequences[i]] || !g->seq[sequences[i]].set) {
+            set_error("%s: sequence %d out of range, never set or named twice", me, sequences[i]);
+            return TC2LI_ERR_INVALID;
+        }
+        named[sequences[i]] = 1;
+        const SeqMeta& m = g->seq[sequences[i]];
+        if (rows[i] < 0 || rows[i] >= m.n_kf) { set_error("%s: sequence %d: keyframe row %d is out of range", me, sequences[i], rows[i]); return TC2LI_ERR_INVALID; }
+        max_kf = std::max(max_kf, m.n_kf);
+    }
+    const size_t N = (size_t)n, K = (size_t)g->cap[0], E = (size_t)g->C.cap_e;
+    if (N * (E + K + 1) > kMaxRows) return too_many_rows(me, n - 1);
+    if (!device_ready()) return TC2LI_ERR_NO_DEVICE;
+    hipStream_t st = stream ? (hipStream_t)stream : private_stream();
+    // scratch that can hold the largest lists of every sequence: nothing in it outlives the call
+    Packer work;
+    const size_t o_prob = work.take(N * sizeof(ConnProblemDev)), o_cnkf = work.take(N * K * 4), o_cnw = work.take(N * K * 4), o_okf = work.take(N * K * 4),
+                 o_ow = work.take(N * K * 4), o_tkf = work.take(N * K * 4), o_tw = work.take(N * K * 4), o_ioff = work.take(N * K * 4),
+                 o_tch = work.take(N * K), o_ifound = work.take(N * K), o_choff = work.take((N * K + N) * 4), o_chkf = work.take(N * (E + K) * 4),
+                 o_chw = work.take(N * (E + K) * 4), o_rowof = work.take(2 * N * K * 4), o_hist = work.take(g->cap[0] > kConnLdsKeyframes ? N * K * 4 : 0);
+    const size_t words = N * (TC2LI_CONNECTIONS_COUNTS + kMgcStatusWords);
+    TC2LI_HIP_CHECK(g->h_conn.ensure(N)); TC2LI_HIP_CHECK(g->d_conn.ensure(N)); TC2LI_HIP_CHECK(g->d_conn_scratch.ensure(work.off));
+    TC2LI_HIP_CHECK(g->d_conn_words.ensure(words)); TC2LI_HIP_CHECK(g->h_conn_words.ensure(words));
+    for (int i = 0; i < n; ++i) {
+        const SeqMeta& m = g->seq[sequences[i]];
+        MgConnDev r{};
+        r.sequence = sequences[i]; r.obs_generation = m.generation; r.conn_generation = m.conn_generation; r.n_kf = m.n_kf; r.conn_rows = m.conn_rows;
+        r.current = rows[i]; r.slot_begin = m.slot_off[rows[i]]; r.n_slots = m.slot_off[rows[i] + 1] - m.slot_off[rows[i]];
+        r.init_kf_id = init_kf_id ? init_kf_id[i] : 0; r.first_connection = first_connection ? first_connection[i] : 0; r.mode = mode;
+        g->h_conn.p[i] = r;
+    }
+    TC2LI_HIP_CHECK(hipMemcpyAsync(g->d_conn.p, g->h_conn.p, N * sizeof(MgConnDev), hipMemcpyHostToDevice, st));   // all that goes up
+    uint8_t* w = g->d_conn_scratch.p;
+    MgConnBatch M{};
+    M.T = g->T; M.C = g->C; M.n = n; M.max_kf = max_kf; M.records = g->d_conn.p;
+    M.problems = reinterpret_cast<ConnProblemDev*>(w + o_prob);
+    M.row_of = reinterpret_cast<int32_t*>(w + o_rowof);
+    M.status = g->d_conn_words.p + N * TC2LI_CONNECTIONS_COUNTS;
+    ConnBatch& B = M.B;
+    B.n_problems = n; B.n_items = 0; B.problems = M.problems; B.problem_of_item = nullptr;
+    B.kf_flags = g->T.kf_flags; B.conn_offsets = g->C.conn_offsets; B.conn_kf = g->C.conn_kf; B.conn_weight = g->C.conn_weight;
+    B.slot_point = g->T.slot_point; B.point_bad = g->T.point_flags; B.obs_offsets = g->T.obs_offsets; B.obs_kf = g->T.obs_kf;
+    B.hist = reinterpret_cast<int32_t*>(w + o_hist); B.touched_weight = reinterpret_cast<int32_t*>(w + o_tw); B.item_off = reinterpret_cast<int32_t*>(w + o_ioff);
+    B.item_found = w + o_ifound;
+    B.counts = g->d_conn_words.p; B.counter_kf = reinterpret_cast<int32_t*>(w + o_cnkf); B.counter_weight = reinterpret_cast<int32_t*>(w + o_cnw);
+    B.ordered_kf = reinterpret_cast<int32_t*>(w + o_okf); B.ordered_weight = reinterpret_cast<int32_t*>(w + o_ow); B.touched_kf = reinterpret_cast<int32_t*>(w + o_tkf);
+    B.touched_changed = w + o_tch; B.changed_offsets = reinterpret_cast<int32_t*>(w + o_choff); B.changed_kf = reinterpret_cast<int32_t*>(w + o_chkf);
+    B.changed_weight = reinterpret_cast<int32_t*>(w + o_chw);
+    launch_map_graph_connections(M, st);
+    TC2LI_HIP_CHECK(hipGetLastError());
+    TC2LI_HIP_CHECK(hipMemcpyAsync(g->h_conn_words.p, g->d_conn_words.p, words * 4, hipMemcpyDeviceToHost, st));   // the counts blocks and the status words
+    TC2LI_HIP_CHECK(stream_wait_blocking(st));
+    const int32_t* counts = g->h_conn_words.p;
+    const int32_t* status = counts + N * TC2LI_CONNECTIONS_COUNTS;
+    int short_of_room = -1;
+    for (int i = 0; i < n; ++i) {
+        g->seq[sequences[i]].conn_rows = g->seq[sequences[i]].n_kf;                  // the first kernel gave the appended rows their offsets
+        if (!status[(size_t)i * kMgcStatusWords] && short_of_room < 0) short_of_room = i;
+    }
+    for (int i = 0; i < n; ++i) {
+        const int32_t* c = counts + (size_t)i * TC2LI_CONNECTIONS_COUNTS;
+        const int32_t* s = status + (size_t)i * kMgcStatusWords;
+        if (counts_out) {
+            int32_t* o = counts_out + (size_t)i * TC2LI_CONNECTIONS_COUNTS;
+            memcpy(o, c, TC2LI_CONNECTIONS_COUNTS * 4);
+            if (mode == kMgcErase) o[TC2LI_CONNECTIONS_N_ORDERED] = o[TC2LI_CONNECTIONS_N_CHANGED] = o[TC2LI_CONNECTIONS_N_CHANGED_ENTRIES] = 0;
+            o[6] = short_of_room >= 0 ? s[1] : 0; o[7] = short_of_room >= 0 ? s[2] : 0;
+        }
+        if (short_of_room >= 0) continue;
+        SeqMeta& m = g->seq[sequences[i]];
+        if (c[TC2LI_CONNECTIONS_STATUS] == TC2LI_CONNECTIONS_UPDATED) { m.conn_generation ^= 1; m.n_weight = s[1]; m.n_ordered = s[2]; }
+        ++m.conn_updates;
+        m.conn_bytes = (int64_t)sizeof(MgConnDev);
+    }
+    if (short_of_room >= 0) {
+        const int32_t* s = status + (size_t)short_of_room * kMgcStatusWords;
+        set_error("%s: sequence %d would hold %d weight and %d ordered entries, the reserve is %d; no sequence was changed", me, sequences[short_of_room],
+                  s[1], s[2], g->C.cap_e);
+        return TC2LI_ERR_CAPACITY;
+    }
+    return n;
+}
+}  // namespace
+
+extern "C" int tc2li_map_graph_update_connections_batch(tc2li_map_graph_handle* g, const int32_t* sequences, const int32_t* current_rows,
+                                                        const uint8_t* first_connection, const int64_t* init_kf_id, int n, int32_t* counts_out,
+                                                        void* stream) {
+    const char* me = "tc2li_map_graph_update_connections_batch";
+    if (!reserved(me, g)) return TC2LI_ERR_INVALID;
+    if (n < 0 || (n && (!sequences || !current_rows || !first_connection || !init_kf_id || !counts_out))) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    if (n == 0) return 0;
+    return connections_call(me, g, sequences, current_rows, first_connection, init_kf_id, n, counts_out, kMgcUpdate, stream);
+}
+
+extern "C" int tc2li_map_graph_erase_connections_batch(tc2li_map_graph_handle* g, const int32_t* sequences, const int32_t* rows, int n, void* stream) {
+    const char* me = "tc2li_map_graph_erase_connections_batch";
+    if (!reserved(me, g)) return TC2LI_ERR_INVALID;
+    if (n < 0 || (n && (!sequences || !rows))) { set_error("%s: invalid argument", me); return TC2LI_ERR_INVALID; }
+    if (n == 0) return 0;
+    return connections_call(me, g, sequences, rows, nullptr, nullptr, n, nullptr, kMgcErase, stream);
+}
+
 // ---- what a gather reads ---------------------------------------------------------------------------------------------------------------
 int tc2li::MgLease::acquire(const char* entry, tc2li_map_graph_handle* g, tc2li_keyframe_store* store, const int32_t* sequences_, int n_) {
     if (!g || n_ < 0 || (n_ && !sequences_)) { set_error("%s: null graph or sequences", entry); return TC2LI_ERR_INVALID; }
     if (store != g->store) { set_error("%s: the graph was created on another keyframe store", entry); return TC2LI_ERR_INVALID; }
     g->mu.lock();
     graph = g; sequences = sequences_; n = n_;
-    T = g->T;
+    T = g->T; C = g->C;
     seq.resize(n);
     for (int p = 0; p < n; ++p) {
         if (!sequence_ok(g, sequences[p]) || !g->seq[sequences[p]].set) { set_error("%s: problem %d names sequence %d, which is out of range or was never set", entry, p, sequences[p]); return TC2LI_ERR_INVALID; }

@@ -15,6 +15,8 @@ struct MgLease {
     MgTables T{};
     std::vector<MgSequenceView> seq;       // per problem
     int64_t uploaded = -1;                 // host-to-device bytes of the gather, -1: it did not get that far
+    MgConnTables C{};                      // the connections (all NULL before tc2li_map_graph_connections_reserve)
+    bool cov_resident = false;             // the gather reads every problem's neighbour list from the ordered row of its current keyframe
 
     MgLease() {}
     MgLease(const MgLease&) = delete;
