@@ -343,7 +343,9 @@ void balm_batch_launch_hessian(const BaPhaseHost& ph, int n, const BaBatchExtent
     const char* lean_env = getenv("TC2LI_BALM_HESS_LEAN");
     const int lean = lean_env ? atoi(lean_env) : 3;
     const size_t lds = sizeof(HessLds<kHessPlanesSmall, 8>);
-    const int fuse = x.fuse_linearize && lean != 0;  // the chunks' sums by the window's last chunk (round 5; ba_last_of, ticket word 2)
+    // the chunks' sums by the window's last chunk (round 5; ba_last_of, ticket word 2): the lean forms only -- any other value launches
+    // k_balm_hessian_b, which leaves the sums to k_balm_combine_b
+    const int fuse = x.fuse_linearize && (lean == 3 || lean == 4);
     // compact grids: the prefix over the windows' own chunk / combine-block counts
     BaPhase k = ph;
     auto cut = [&](BaGridKind kind, auto&& own) {
