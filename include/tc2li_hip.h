@@ -467,7 +467,12 @@ typedef struct tc2li_map_point {  /* what Frame::isInFrustum / PredictScale read
 /* The matching loops.  mode 0: best Hamming distance <= TH_HIGH (last-frame overload); mode 1: best / second best with
  * nn_ratio when both lie on one level (local-map overload).  check_orientation applies the 30-bin rotation histogram.
  * match_of_query[q] = matched keypoint or -1; query_of_keypoint[i] (may be NULL) = the query now held by keypoint i.
- * Returns nmatches like the reference. */
+ * Returns nmatches like the reference.
+ * The histogram filter works on KEYPOINTS, as the reference's does (rotHist[bin].push_back(bestIdx2), ORBmatcher.cc:1800; the loop of
+ * :1882-1891 clears CurrentFrame.mvpMapPoints[keypoint] and counts down once per rejected entry).  Two queries share a keypoint when the
+ * earlier one has has_observations == 0 (:1756-1758 does not skip such a keypoint); if either of the two entries falls outside the
+ * three dominant bins the keypoint is cleared: query_of_keypoint[i] = -1, match_of_query = -1 for every query that pointed at it, and
+ * nmatches drops by the number of rejected entries, not of queries. */
 int tc2li_search_by_projection(const tc2li_frame_view* frame, const tc2li_proj_query* queries, int n_queries, int mode,
                                float nn_ratio, int check_orientation, int32_t* match_of_query, int32_t* query_of_keypoint);
 
@@ -626,7 +631,10 @@ typedef struct tc2li_last_frame {      /* what the matcher reads of mLastFrame *
  * the optimised pose rounded through float as Frame::SetPose does, or the prediction when tracking failed),
  * map_point_of_keypoint [n_frames][capacity] = index of the last-frame point now held by keypoint i (mvpMapPoints[i])
  * or -1, outliers already discarded; n_matches[f] = matches after the search stage; n_inliers[f] = the value
- * PoseOptimization returned, -1 when fewer than 20 matches were found (Tracking.cc:2785-2793). */
+ * PoseOptimization returned, -1 when fewer than 20 matches were found (Tracking.cc:2785-2793).
+ * The batched tracking entries (this one, tc2li_track_local_map_batch, tc2li_search_local_points_batch and the keyframe overload of
+ * relocalisation) assume that every source point has observations (Observations() > 0): a match always blocks its keypoint, so no two
+ * points of one search share a keypoint and the histogram filter's removal by keypoint equals a removal by point. */
 int tc2li_track_motion_model_batch(tc2li_orb* orb, int n_frames, const tc2li_keypoint* keypoints, const float* u_right,
                                    int capacity, const tc2li_last_frame* last, const float* pose_pred7,
                                    const tc2li_camera* cam, float b, float th, double* poses7,

@@ -63,6 +63,9 @@ static void ComputeThreeMaxima(const std::vector<int>* histo, int L, int& ind1, 
     else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
 }
 
+// ORBmatcher.cc:1873-1892.  The histogram holds KEYPOINT indices (rotHist[bin].push_back(bestIdx2), :1800); a rejected entry clears
+// CurrentFrame.mvpMapPoints[keypoint] and counts one match down.  Two queries can hold one keypoint (the earlier one's point has no
+// observations, :1756-1758): the keypoint is cleared when either entry is rejected, and both queries lose it.
 int rotation_filter(const FrameView& F, const std::vector<ProjQuery>& queries, std::vector<int>& match_of_query) {
     std::vector<int> rotHist[HISTO_LENGTH];
     const float factor = 1.0f / HISTO_LENGTH;
@@ -72,14 +75,17 @@ int rotation_filter(const FrameView& F, const std::vector<ProjQuery>& queries, s
         if (rot < 0.0) rot += 360.0f;
         int bin = (int)std::round(rot * factor);
         if (bin == HISTO_LENGTH) bin = 0;
-        rotHist[bin].push_back((int)q);
+        rotHist[bin].push_back(match_of_query[q]);
     }
     int ind1 = -1, ind2 = -1, ind3 = -1;
     ComputeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
     int removed = 0;
+    std::vector<uint8_t> cleared(F.keys.size(), 0);
     for (int i = 0; i < HISTO_LENGTH; i++)
         if (i != ind1 && i != ind2 && i != ind3)
-            for (int q : rotHist[i]) { match_of_query[q] = -1; removed++; }
+            for (int key : rotHist[i]) { cleared[key] = 1; removed++; }
+    for (int& m : match_of_query)
+        if (m >= 0 && cleared[m]) m = -1;
     return removed;
 }
 
@@ -182,7 +188,7 @@ std::vector<ProjQuery> build_queries_local_map(const SE3f& Tcw, const CamF& cam,
         if (nScale < 0) nScale = 0; else if (nScale >= nlevels) nScale = nlevels - 1;
         // SearchByProjection(F, vpMapPoints, th, ...) window (ORBmatcher.cc:62-81)
         if (bFarPoints && Pc_dist > thFarPoints) continue;
-        float r = viewCos > 0.998f ? 2.5f : 4.0f;  // RadiusByViewingCos
+        float r = viewCos > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos (ORBmatcher.cc:224-230): a double constant, so float(0.998) is above it
         if (bFactor) r *= th;
         ProjQuery& Q = qs[k];
         Q.u = u; Q.v = v;

@@ -60,9 +60,11 @@ void three_maxima(const int* count, int L, int& ind1, int& ind2, int& ind3) {
     else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
 }
 
-// Rotation consistency of the last-frame overload (SF/src/ORBmatcher.cc:1783-1799, 1858-1881): matches outside the three
-// dominant 30-bin rotation bins are removed; returns how many.
-int rotation_filter(const tc2li_proj_query* queries, int M, const tc2li_keypoint* keys, int32_t* match_of_query) {
+// Rotation consistency of the last-frame overload (SF/src/ORBmatcher.cc:1783-1800, 1873-1892).  The histogram holds KEYPOINT indices
+// (rotHist[bin].push_back(bestIdx2)): an entry outside the three dominant 30-bin rotation bins clears its keypoint and counts one match
+// down.  Two queries hold one keypoint when the earlier one's point has no observations; the keypoint is cleared when either entry is
+// rejected, and every query that pointed at it loses its match.  Returns the number of rejected entries.
+int rotation_filter(const tc2li_proj_query* queries, int M, const tc2li_keypoint* keys, int N, int32_t* match_of_query) {
     const int L = 30;
     const float factor = 1.0f / L;
     std::vector<int> bin_of(M, -1);
@@ -78,8 +80,11 @@ int rotation_filter(const tc2li_proj_query* queries, int M, const tc2li_keypoint
     }
     int ind1 = -1, ind2 = -1, ind3 = -1, removed = 0;
     three_maxima(count, L, ind1, ind2, ind3);
+    std::vector<uint8_t> cleared(N, 0);
     for (int q = 0; q < M; ++q)
-        if (bin_of[q] >= 0 && bin_of[q] != ind1 && bin_of[q] != ind2 && bin_of[q] != ind3) { match_of_query[q] = -1; removed++; }
+        if (bin_of[q] >= 0 && bin_of[q] != ind1 && bin_of[q] != ind2 && bin_of[q] != ind3) { cleared[match_of_query[q]] = 1; removed++; }
+    for (int q = 0; q < M; ++q)
+        if (match_of_query[q] >= 0 && cleared[match_of_query[q]]) match_of_query[q] = -1;
     return removed;
 }
 
@@ -122,7 +127,7 @@ int tc2li_search_by_projection(const tc2li_frame_view* frame, const tc2li_proj_q
     TC2LI_HIP_CHECK(copy_sync(match_of_query, w.d_match.p, M * sizeof(int32_t), hipMemcpyDeviceToHost, ps));
     int nmatches = 0;
     for (int q = 0; q < M; ++q) nmatches += match_of_query[q] >= 0;
-    if (check_orientation) nmatches -= rotation_filter(queries, M, frame->keys, match_of_query);
+    if (check_orientation) nmatches -= rotation_filter(queries, M, frame->keys, N, match_of_query);
     if (query_of_keypoint)
         for (int q = 0; q < M; ++q) if (match_of_query[q] >= 0) query_of_keypoint[match_of_query[q]] = q;
     return nmatches;
@@ -212,7 +217,7 @@ int tc2li_project_local_map(const float pose7[7], const float cam4[4], float bf,
         if (view_cos < viewing_cos_limit) continue;
         const int level = predict_scale_level(M.max_distance_raw / dist, log_scale_factor, n_levels);
         if (far_points && pc_dist > th_far_points) continue;
-        float r = view_cos > 0.998f ? 2.5f : 4.0f;
+        float r = (double)view_cos > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos (ORBmatcher.cc:224-230) compares with the double 0.998: float(0.998) lies above it
         if (factor) r *= th;
         Q.u = u; Q.v = v;
         Q.u_right = u - bf * invz;

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void k_track_queries_local(const TrackFrameDev
         // ratio and window factor; the host takes logf of those and a patch kernel writes level and radius (tracking_host.cpp).
         const float ratio = max_distance_raw / dist;
         const double quot = log((double)ratio) / (double)C.log_scale;
-        float r = view_cos > 0.998f ? 2.5f : 4.0f;
+        float r = (double)view_cos > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos (ORBmatcher.cc:224-230) compares with the double 0.998: float(0.998) lies above it
         if (F.th != 1.0f) r *= F.th;
         int level = 0;
         const double nearest = rint(quot);
